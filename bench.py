@@ -1,12 +1,18 @@
 #!/usr/bin/env python3
 """Benchmark of the hot path: batched slim_yolo_v2_q_bf int8 inference, 416x416, on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 One "step" = one pass of the whole path (conv1..pred, head decode, NMS) over one batch of 64
 synthetic images per GPU, inputs resident in HBM.  Prints ONE JSON line (rank 0).
 Metric (BASELINE.json): images/sec; roofline = int8 MFMA (5.0432 G int8-op/image).
+
+A plain run sets up, warms up (W steps, and at least HEADLINE_WARMUP_SECONDS), times ONE region of exactly K
+steps, writes the last step's detections if --dump-outputs is given, and prints the line.  --full adds everything
+else this script measures or checks: repeated regions, roofline and per-kernel figures, the one-stream / same-input /
+hand-scheduled / sparse / uint8 figures, other_configs, the CPU baselines and, with more than one rank, the
+verification of the gathered detections.
 """
 import argparse
 import json
@@ -45,6 +51,36 @@ PROFILE_ROUND = "r06"       # the round whose kernels this bench.py measures: fi
 KERNEL_STATS_FILES = ["r06_kernel_stats_one_stream.csv", "r05_kernel_stats_one_stream.csv", "r04_kernel_stats_one_stream.csv"]    # newest first
 TRAFFIC_FILES = ["r06_pmc_traffic.json", "r05_pmc_traffic.json", "r04_pmc_traffic.json", "r03_pmc_traffic.json", "r02_pmc_traffic.json", "r01_h_pmc_traffic.json"]     # newest first
 N_INPUTS = 4          # distinct input batches rotated through the timed loop: 4 x 133 MB > the 256 MB Infinity Cache
+# the headline's warm-up lasts at least this long: from a cold start the first ~0.1 s of steps run up to 15 % slower
+# (the clock ramp), which a single timed region of a few steps would otherwise measure
+HEADLINE_WARMUP_SECONDS = 1.0
+DUMP_LIMIT_BYTES = 64_000_000       # --dump-outputs: at most this much in all (above it, a fixed seeded sample of the images)
+
+
+def host_outputs(outs, B):
+    """What a caller of the timed path receives for the B images of one step -- (boxes [B,D,4], scores [B,D], cls [B,D],
+    count [B]) -- on the host as float32.  Entries past count[i] are undefined padding (include/yolo355.h): written as
+    zeros, so that the outputs of two builds compare array for array."""
+    boxes, scores, cls, cnt = (t[:B].detach().cpu().numpy() for t in outs[:4])
+    keep = np.arange(scores.shape[1])[None, :] < cnt[:, None]
+    return {"boxes": np.where(keep[..., None], boxes, 0).astype(np.float32),
+            "scores": np.where(keep, scores, 0).astype(np.float32),
+            "classes": np.where(keep, cls, 0).astype(np.float32),
+            "count": cnt.astype(np.float32)}
+
+
+def write_outputs(path, arrays):
+    """--dump-outputs: every array as <path>/<name>.npy.  Above DUMP_LIMIT_BYTES in all, the same seeded sample of the
+    images from every array, their indices in image_index.npy."""
+    os.makedirs(path, exist_ok=True)
+    n = len(arrays["count"])
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        keep = max(1, (DUMP_LIMIT_BYTES - 65536) // (total // n + 8))
+        idx = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+        arrays = dict({k: a[idx] for k, a in arrays.items()}, image_index=idx.astype(np.float64))
+    for k, a in arrays.items():
+        np.save(os.path.join(path, k + ".npy"), a)
 
 
 def pmc_traffic(kernel):
@@ -307,6 +343,8 @@ def measure_net(args):
     # (Y355_NET_OPT_WORKGROUPS, the nets' throughput mode, is left off: measured slower on both graphs -- SlimYOLOv2 fp32 148.3 k
     # against 137.0 k / 138.0 k img/s at 128 / 192 workgroups, YOLOv3tiny int8 195.6 k against 192.0 k / 194.6 k: profiles/r04_notes.md)
     ts, out = regions(ns, reps, 1.0 if reps >= 15 else 0.0)
+    if getattr(args, "dump_outputs", None):
+        write_outputs(args.dump_outputs, host_outputs(out, B))
     dt = float(np.median(ts))
     ts1, _ = regions(1, min(reps, 5), 0.0)
     dt1 = float(np.median(ts1))
@@ -378,6 +416,8 @@ def bench_yolo_v2(args):
         out = net.forward_device(x)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, host_outputs(out, B))
     net.profile(True)
     acc = None
     for _ in range(5):
@@ -450,6 +490,8 @@ def bench_yolo_v3(args):
         out = net.forward_device(x)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
+    if args.dump_outputs:
+        write_outputs(args.dump_outputs, host_outputs(out, B))
     if net.overflow():
         raise RuntimeError("more than 4096 anchors of an image passed the threshold")
     net.profile(True)
@@ -531,17 +573,24 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=50)
-    ap.add_argument("--warmup", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=10,
+                    help="warm-up steps before the timed region; the headline's warm-up also lasts at least HEADLINE_WARMUP_SECONDS")
     ap.add_argument("--repeats", type=int, default=0,
                     help="the timed region of EXACTLY --steps steps is run this many times; value = median (min / max reported). "
-                         "0 (default) = as many as it takes to time at least 2 s of GPU work, and at least 15")
+                         "0 (default) = once; with --full, as many as it takes to time at least 2 s of GPU work, and at least 15")
+    ap.add_argument("--full", action="store_true",
+                    help="everything beyond the headline: repeated regions, roofline and per-kernel figures, one-stream / same-input / "
+                         "hand-scheduled / sparse / uint8 figures, other_configs, CPU baselines, the multi-GPU gather verification")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the detections of the last step (boxes, scores, classes, count; "
+                         "float32, padding zeroed) as DIR/<name>.npy")
     ap.add_argument("--batch", type=int, default=PER_GPU_BATCH, help="images per GPU per step")
     ap.add_argument("--net-regions", type=int, default=15,
                     help="--workload other than slim_int8 (and the other_configs entries): minimum number of timed regions "
                          "(at 15 or more the regions also have to add up to 1 s)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-sparse", action="store_true", help="skip the extra 'sparse fixture' measurement (SURVEY.md 8d)")
-    ap.add_argument("--no-other-configs", action="store_true", help="skip the short configs[2] / configs[3] measurements")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-sparse", action="store_true", help="--full: skip the extra 'sparse fixture' measurement (SURVEY.md 8d)")
+    ap.add_argument("--no-other-configs", action="store_true", help="--full: skip the short configs[2] / configs[3] measurements")
     ap.add_argument("--no-fuse-front", action="store_true",
                     help="A/B: one launch per layer for conv1 / conv2 instead of the fused front-end kernel (same results)")
     ap.add_argument("--streams", type=int, default=0,
@@ -711,16 +760,37 @@ def main():
 
     own_times = []        # this rank's OWN clock around its steps of every region of the headline run (before the barrier)
 
-    def timed(ns, steps, warmup, repeats, rotate=True, min_seconds=0.0, g=None, solo=False, own=None):
+    warm = {}             # the headline's warm-up: steps run, seconds
+
+    def timed(ns, steps, warmup, repeats, rotate=True, min_seconds=0.0, g=None, solo=False, own=None, warm_seconds=0.0):
         """`repeats` timed regions of EXACTLY `steps` steps each (repeats = 0: until `min_seconds` of timed work and 15 regions),
         every one bracketed by barrier + synchronize on both sides; per region the MAX over ranks.
         solo: this rank alone, no barrier, no gather (the N = 1 sub-result of a multi-GPU run).
+        warm_seconds: after the `warmup` steps, more warm-up steps until that much time has passed since the first
+        (rank 0 decides, so every rank runs as many).
         Returns (list of seconds, last outputs)."""
         pending = [None] * nbuf
         out = None
         sync = dist_on and not solo
+        t_warm = time.perf_counter()
         for i in range(warmup):
             out = step(i, pending, ns, rotate, g, solo)
+        n_warm = warmup
+        while warm_seconds > 0:
+            torch.cuda.synchronize()
+            more = time.perf_counter() - t_warm < warm_seconds
+            if sync:
+                flag = torch.tensor([1 if more else 0], dtype=torch.int32, device=cdev)
+                dist.broadcast(flag, 0)
+                more = bool(flag.item())
+            if not more:
+                break
+            for _ in range(4 * nbuf):
+                out = step(n_warm, pending, ns, rotate, g, solo)
+                n_warm += 1
+        if warm_seconds > 0:
+            torch.cuda.synchronize()
+            warm.update(steps=n_warm, seconds=round(time.perf_counter() - t_warm, 3))
         times = []
         while len(times) < (repeats if repeats > 0 else 15) or (repeats <= 0 and sum(times) < min_seconds and len(times) < 2000):
             torch.cuda.synchronize()
@@ -753,15 +823,19 @@ def main():
     ring_wgs = args.ring_workgroups if nstreams > 1 else 0
     for e in engines:
         e.set_option(2, ring_wgs)                        # Y355_OPT_RING_WORKGROUPS
-    times, out = timed(nstreams, args.steps, args.warmup, args.repeats, True, 2.0, own=own_times)
+    repeats = args.repeats if args.repeats > 0 else (0 if args.full else 1)
+    times, out = timed(nstreams, args.steps, args.warmup, repeats, True, 2.0, own=own_times, warm_seconds=HEADLINE_WARMUP_SECONDS)
     reps = len(times)
     dt = float(np.median(times))
+    ndet = int(out[3][:B].sum().item())
+    if args.dump_outputs and rank == 0:
+        write_outputs(args.dump_outputs, host_outputs(out, B))
     # ---- a first N-GPU run has to diagnose itself (RCCL with more than one rank has never run on the build
     # boxes): every rank's OWN rate (its clock around its own steps, before the closing barrier) so that a slow rank or a slow
     # link shows as min / max over ranks instead of hiding in the MAX time, and the N = 1 sub-result -- rank 0 alone, gather
     # off, the other ranks idle at a barrier -- measured by the same process, to be checked against BENCH's N = 1 line
     per_rank, solo_info = None, None
-    if dist_on:
+    if dist_on and args.full:
         mine = torch.tensor([float(np.median(own_times))], dtype=torch.float64, device=cdev)
         allr = [torch.zeros_like(mine) for _ in range(world)]
         dist.all_gather(allr, mine)
@@ -780,18 +854,19 @@ def main():
     # the same region with the steps dealt to the handles by this script (rounds 2-5's measurement) instead of Pipeline.submit:
     # the product entry point must not cost throughput (within 2 %)
     hand = None
-    if nstreams > 1 and not dist_on:
+    if nstreams > 1 and not dist_on and args.full:
         direct[0] = True
         t_hand, _ = timed(nstreams, args.steps, min(args.warmup, 5), 7)
         direct[0] = False
         hand = float(np.median(t_hand))
     # the same with ONE input batch fed to every step (what rounds 1 and 2 reported: part of it stays in the Infinity Cache)
-    t_same, _ = timed(nstreams, args.steps, min(args.warmup, 5), 5, False)
-    dt_same = float(np.median(t_same))
+    dt_same = one = None
+    if args.full:
+        t_same, _ = timed(nstreams, args.steps, min(args.warmup, 5), 5, False)
+        dt_same = float(np.median(t_same))
     for e in engines:
         e.set_option(2, 0)
-    one = None
-    if nstreams > 1:
+    if nstreams > 1 and args.full:
         t1, _ = timed(1, args.steps, min(args.warmup, 5), 5)
         one = float(np.median(t1))
 
@@ -801,7 +876,7 @@ def main():
     # route y355_pack_dets / y355_allgather_dets / y355_unpack_dets with full records.  Rank 0 rebuilds every rank's shard on
     # its own GPU, runs it through its own engine and compares every byte.  Full records are also TIMED (a short region).
     gather_info = None
-    if dist_on:
+    if dist_on and args.full:
         G_full = G if gather_md == eng.max_det else gather_bufs(eng.max_det)
         for e in engines:
             e.set_option(2, ring_wgs)
@@ -871,89 +946,90 @@ def main():
                                ", and full records through y355_pack_dets / y355_allgather_dets / y355_unpack_dets)")}
         dist.barrier()
 
-    # per-kernel device time with HIP events on the engine's stream (separate profiled steps)
-    eng.profile(True)
-    acc, kacc = [], []
-    nprof = max(5, min(args.steps, 20))
-    with torch.cuda.stream(streams[0]):
-        for i in range(nprof):
-            if frames is not None:
-                eng.forward_frames_device(frames, 0, bufs[0])
-            else:
-                eng.forward_device(x, 0, bufs[0])
-            acc.append(eng.profile_ms())
-        eng.profile(2)              # second pass: the launches' own timestamps (widens the intervals, hence separate)
-        for i in range(nprof):
-            if frames is not None:
-                eng.forward_frames_device(frames, 0, bufs[0])
-            else:
-                eng.forward_device(x, 0, bufs[0])
-            kacc.append(eng.profile_kernels_ms())
-    eng.profile(False)
-    # the launches' own durations INSIDE the throughput mode (every handle in profile mode 2, steps alternating as in the timed
-    # region; a handle's timestamps are read just before its next step, `streams` steps later, so the overlap is kept)
-    kreg = []
-    if nstreams > 1:
-        for e in engines:
-            e.profile(2)
-            e.set_option(2, ring_wgs)
-        nreg = max(4 * nstreams, min(args.steps, 30))
-        for i in range(nreg):
-            e = engines[i % nstreams]
-            with torch.cuda.stream(streams[i % nstreams]):
-                if i >= 2 * nstreams:
-                    kreg.append(e.profile_kernels_ms())
-                if fs is not None:
-                    e.forward_frames_device(fs[i % N_INPUTS], 0, bufs[i % nbuf])
+    if args.full:
+        # per-kernel device time with HIP events on the engine's stream (separate profiled steps)
+        eng.profile(True)
+        acc, kacc = [], []
+        nprof = max(5, min(args.steps, 20))
+        with torch.cuda.stream(streams[0]):
+            for i in range(nprof):
+                if frames is not None:
+                    eng.forward_frames_device(frames, 0, bufs[0])
                 else:
-                    e.forward_device(xs[i % N_INPUTS], 0, bufs[i % nbuf])
-        torch.cuda.synchronize()
-        for e in engines:
-            e.profile(False)
-            e.set_option(2, 0)
-    kernel_ms_region = np.median(np.array(kreg), axis=0) if kreg else None
-    layer_ms = np.median(np.array(acc), axis=0)
-    kernel_ms = np.median(np.array(kacc), axis=0)    # the launches' own start / end timestamps: 10 layers + the 4 head / NMS launches
-    from yolo355.engine import mfma_peak_i8
-    peak_tops, peak_clock = mfma_peak_i8(dev_index, 50.0) if rank == 0 else (0.0, 0.0)
-    ndet = int(out[3][:B].sum().item())
+                    eng.forward_device(x, 0, bufs[0])
+                acc.append(eng.profile_ms())
+            eng.profile(2)              # second pass: the launches' own timestamps (widens the intervals, hence separate)
+            for i in range(nprof):
+                if frames is not None:
+                    eng.forward_frames_device(frames, 0, bufs[0])
+                else:
+                    eng.forward_device(x, 0, bufs[0])
+                kacc.append(eng.profile_kernels_ms())
+        eng.profile(False)
+        # the launches' own durations INSIDE the throughput mode (every handle in profile mode 2, steps alternating as in the timed
+        # region; a handle's timestamps are read just before its next step, `streams` steps later, so the overlap is kept)
+        kreg = []
+        if nstreams > 1:
+            for e in engines:
+                e.profile(2)
+                e.set_option(2, ring_wgs)
+            nreg = max(4 * nstreams, min(args.steps, 30))
+            for i in range(nreg):
+                e = engines[i % nstreams]
+                with torch.cuda.stream(streams[i % nstreams]):
+                    if i >= 2 * nstreams:
+                        kreg.append(e.profile_kernels_ms())
+                    if fs is not None:
+                        e.forward_frames_device(fs[i % N_INPUTS], 0, bufs[i % nbuf])
+                    else:
+                        e.forward_device(xs[i % N_INPUTS], 0, bufs[i % nbuf])
+            torch.cuda.synchronize()
+            for e in engines:
+                e.profile(False)
+                e.set_option(2, 0)
+        kernel_ms_region = np.median(np.array(kreg), axis=0) if kreg else None
+        layer_ms = np.median(np.array(acc), axis=0)
+        kernel_ms = np.median(np.array(kacc), axis=0)    # the launches' own start / end timestamps: 10 layers + the 4 head / NMS launches
+        from yolo355.engine import mfma_peak_i8
+        peak_tops, peak_clock = mfma_peak_i8(dev_index, 50.0) if rank == 0 else (0.0, 0.0)
 
     if rank == 0:
         ms_per_step = dt / args.steps * 1e3
         value = world * B * args.steps / dt
-        conv_ms = float(layer_ms[:10].sum())
-        achieved = B * OPS_PER_IMAGE / (conv_ms * 1e-3) / 1e12
-        # dominant kernel: its own duration (start / end timestamps of the launch, hipExtLaunchKernelGGL: what rocprofv3
-        # reports); the interval between the events before and after it also holds the gap to the neighbouring launches
-        dom_between = float(layer_ms[7] + layer_ms[8]) / 2
-        have_k = kernel_ms[7] > 0 and kernel_ms[8] > 0
-        dom_ms = float(kernel_ms[7] + kernel_ms[8]) / 2 if have_k else dom_between
-        dom_tops = B * 2e6 * LAYER_MMAC[7] / (dom_ms * 1e-3) / 1e12
-        fused = not args.no_fuse_front and layer_ms[1] < 0.2 * layer_ms[0]     # slot 0 then holds conv1 + conv2 (one launch)
-        # conv3_1 -> conv3_2 + pool3 as one launch (pxpair.hip): slot 2 holds the pair, slot 3 reads ~0
-        pair3 = have_k and kernel_ms[2] > 0 and kernel_ms[3] == 0
-        knames = ((["conv1+conv2 (fused front end)"] if fused else ["conv1"]) + LAYER_NAMES[1:] +
-                  ["decode_kernel", "head_kernel", "pairs_kernel", "resolve_emit_kernel"])
-        if pair3:
-            knames[2] = "conv3_1+conv3_2 (fused pair)"
-        layers = {}
-        for i, n in enumerate(LAYER_NAMES):
-            if pair3 and i == 2:
-                layers[knames[i]] = dict(
-                    ms=round(float(layer_ms[i] + layer_ms[i + 1]), 4),
-                    tops=round(B * 2e6 * (LAYER_MMAC[i] + LAYER_MMAC[i + 1]) / ((layer_ms[i] + layer_ms[i + 1]) * 1e-3) / 1e12, 1))
-                continue
-            if pair3 and i == 3:
-                continue
-            if fused and i == 0:
-                layers["conv1+conv2 (fused front end)"] = dict(
-                    ms=round(float(layer_ms[0] + layer_ms[1]), 4),
-                    tops=round(B * 2e6 * (LAYER_MMAC[0] + LAYER_MMAC[1]) / ((layer_ms[0] + layer_ms[1]) * 1e-3) / 1e12, 1))
-            elif fused and i == 1:
-                continue
-            else:
-                layers[n] = dict(ms=round(float(layer_ms[i]), 4), tops=round(B * 2e6 * LAYER_MMAC[i] / (layer_ms[i] * 1e-3) / 1e12, 1))
-        traffic, traffic_src, traffic_kernel = pmc_traffic(DOMINANT_KERNEL)
+        if args.full:
+            conv_ms = float(layer_ms[:10].sum())
+            achieved = B * OPS_PER_IMAGE / (conv_ms * 1e-3) / 1e12
+            # dominant kernel: its own duration (start / end timestamps of the launch, hipExtLaunchKernelGGL: what rocprofv3
+            # reports); the interval between the events before and after it also holds the gap to the neighbouring launches
+            dom_between = float(layer_ms[7] + layer_ms[8]) / 2
+            have_k = kernel_ms[7] > 0 and kernel_ms[8] > 0
+            dom_ms = float(kernel_ms[7] + kernel_ms[8]) / 2 if have_k else dom_between
+            dom_tops = B * 2e6 * LAYER_MMAC[7] / (dom_ms * 1e-3) / 1e12
+            fused = not args.no_fuse_front and layer_ms[1] < 0.2 * layer_ms[0]     # slot 0 then holds conv1 + conv2 (one launch)
+            # conv3_1 -> conv3_2 + pool3 as one launch (pxpair.hip): slot 2 holds the pair, slot 3 reads ~0
+            pair3 = have_k and kernel_ms[2] > 0 and kernel_ms[3] == 0
+            knames = ((["conv1+conv2 (fused front end)"] if fused else ["conv1"]) + LAYER_NAMES[1:] +
+                      ["decode_kernel", "head_kernel", "pairs_kernel", "resolve_emit_kernel"])
+            if pair3:
+                knames[2] = "conv3_1+conv3_2 (fused pair)"
+            layers = {}
+            for i, n in enumerate(LAYER_NAMES):
+                if pair3 and i == 2:
+                    layers[knames[i]] = dict(
+                        ms=round(float(layer_ms[i] + layer_ms[i + 1]), 4),
+                        tops=round(B * 2e6 * (LAYER_MMAC[i] + LAYER_MMAC[i + 1]) / ((layer_ms[i] + layer_ms[i + 1]) * 1e-3) / 1e12, 1))
+                    continue
+                if pair3 and i == 3:
+                    continue
+                if fused and i == 0:
+                    layers["conv1+conv2 (fused front end)"] = dict(
+                        ms=round(float(layer_ms[0] + layer_ms[1]), 4),
+                        tops=round(B * 2e6 * (LAYER_MMAC[0] + LAYER_MMAC[1]) / ((layer_ms[0] + layer_ms[1]) * 1e-3) / 1e12, 1))
+                elif fused and i == 1:
+                    continue
+                else:
+                    layers[n] = dict(ms=round(float(layer_ms[i]), 4), tops=round(B * 2e6 * LAYER_MMAC[i] / (layer_ms[i] * 1e-3) / 1e12, 1))
+            traffic, traffic_src, traffic_kernel = pmc_traffic(DOMINANT_KERNEL)
         res = {
             "metric": "images/sec slim_yolo_v2 int8 416x416", "value": round(value, 1), "unit": "images/sec",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": round(ms_per_step, 4),
@@ -964,64 +1040,70 @@ def main():
                        "streams_per_gpu": nstreams, "ring_workgroups_per_launch": ring_wgs if ring_wgs else "one per CU",
                        **({"gather": "one all_gather_into_tensor per batch (%s), records capped at %d detections per image (%d bytes); "
                                      "this fixture has %d detections per image on average, so %d of rank 0's %d images are cut at the cap "
-                                     "(header word 1 > word 0 tells the receiver); the same region with full records: gather_full_records"
+                                     "(header word 1 > word 0 tells the receiver)%s"
                                      % (args.dist_backend, gather_md, shard.record_bytes(gather_md), ndet // B,
-                                        gather_info["truncated_images"] // world if gather_info else -1, B)} if dist_on else {}),
+                                        (gather_info["truncated_images"] if gather_info else shard.truncated_images(G["recv"][0])) // world, B,
+                                        "; the same region with full records: gather_full_records" if gather_info else "")}
+                          if dist_on else {}),
                        "input": args.input, "input_batches_rotated": N_INPUTS,
                        "detections_per_step_rank0": ndet},
-            # the timed region (exactly `steps` steps between barrier + synchronize) was run `repeats` times: value and
-            # ms_per_step are the MEDIAN region; with 3 engine handles ms_per_step is a throughput period, not a latency
-            "timing": {"repeats": reps, "timed_seconds": round(float(sum(times)), 3), "ms_per_step_min": round(min(times) / args.steps * 1e3, 4),
+            # the timed region (exactly `steps` steps between barrier + synchronize) was run `repeats` times (once unless --repeats or
+            # --full): value and ms_per_step are the MEDIAN region; with several engine handles ms_per_step is a throughput period,
+            # not a latency
+            "timing": {"repeats": reps, "timed_seconds": round(float(sum(times)), 3),
+                       "warmup_steps_run": warm["steps"], "warmup_seconds": warm["seconds"],
+                       "ms_per_step_min": round(min(times) / args.steps * 1e3, 4),
                        "ms_per_step_max": round(max(times) / args.steps * 1e3, 4),
                        "value_min": round(world * B * args.steps / max(times), 1),
                        "value_max": round(world * B * args.steps / min(times), 1)},
+        }
+        if args.full:
             # whole_path_frac = the headline as a fraction of the int8-MFMA roofline (value x 5.0432 G int8-op / peak): the
             # figure BASELINE.json's >= 50 % target is about; `frac` = the same for the dominant kernel alone (named below)
-            "roofline": {"whole_path_frac": round(value / world * OPS_PER_IMAGE / PEAK_I8_DENSE, 4),
-                         "bound": "mfma", "achieved": round(dom_tops, 2), "peak": PEAK_I8_DENSE / 1e12,
-                         "unit": "TFLOP/s", "frac": round(dom_tops * 1e12 / PEAK_I8_DENSE, 4),
-                         "traffic": traffic, "traffic_source": traffic_src, "traffic_kernel": traffic_kernel,
-                         # traffic / launch_ms_rocprof are READ from the committed rocprofv3 passes of this workload (PMC counters cannot be
-                         # collected inside a timed run); stale = the newest committed file is from an earlier round than these kernels
-                         "traffic_stale": bool(traffic_src) and ("/" + PROFILE_ROUND + "_") not in traffic_src,
-                         "launch_ms_rocprof_stale": bool(rocprof_launch_ms(DOMINANT_KERNEL)[1]) and ("/" + PROFILE_ROUND + "_") not in rocprof_launch_ms(DOMINANT_KERNEL)[1],
-                         "kernel": DOMINANT_KERNEL + ", true> (conv6 and conv7: 2 launches/step, the largest share of "
-                                   "the step of any kernel; int8 ops = 2 x 398.72e6 MAC x %d images per launch)" % B,
-                         "launch_ms": round(dom_ms, 4),
-                         "launch_ms_rocprof": rocprof_launch_ms(DOMINANT_KERNEL)[0],
-                         "launch_ms_rocprof_source": rocprof_launch_ms(DOMINANT_KERNEL)[1],
-                         "frac_rocprof": (round(B * 2e6 * LAYER_MMAC[7] / (rocprof_launch_ms(DOMINANT_KERNEL)[0] * 1e-3) / PEAK_I8_DENSE, 4)
-                                          if rocprof_launch_ms(DOMINANT_KERNEL)[0] else None),
-                         "launch_ms_source": ("kernel start/end timestamps of the launch (hipExtLaunchKernelGGL events), mean of "
-                                              "conv6 and conv7, median of %d profiled steps on the engine's stream" % nprof) if have_k
-                         else "interval between hipEventRecord before / after the launch",
-                         # the same launches while `streams` handles share the GPU (the timed region's regime: `ring_workgroups`
-                         # persistent workgroups per launch, other handles' kernels beside them); `frac` describes the kernel alone
-                         # on an idle GPU, whole_path_frac the run
-                         "launch_ms_in_timed_region": (round(float(kernel_ms_region[7] + kernel_ms_region[8]) / 2, 4)
-                                                       if kernel_ms_region is not None and kernel_ms_region[7] > 0 else None),
-                         "launch_ms_between_events": round(dom_between, 4),
-                         "frac_between_events": round(B * 2e6 * LAYER_MMAC[7] / (dom_between * 1e-3) / PEAK_I8_DENSE, 4),
-                         # every launch's own duration (ms): layers (the fused front end under "conv1"), then the head / NMS kernels
-                         "kernel_ms": {n: round(float(kernel_ms[i]), 4) for i, n in enumerate(knames) if kernel_ms[i] > 0},
-                         "kernel_ms_sum": round(float(kernel_ms.sum()), 4),
-                         "kernel_ms_in_timed_region": ({n: round(float(kernel_ms_region[i]), 4) for i, n in enumerate(knames)
-                                                        if kernel_ms_region[i] > 0} if kernel_ms_region is not None else None),
-                         # MFMA-only loop MEASURED IN THIS RUN (y355_mfma_peak_i8: v_mfma_i32_16x16x64_i8 back to back on register
-                         # operands, two waves per SIMD on every CU, ~50 ms) and the in-kernel clock it held
-                         "peak_measured": round(peak_tops, 1),
-                         "peak_measured_implied_clock_ghz": round(peak_tops * 1e12 / (1024 * 32768 / 16) / 1e9, 3),   # 16 cycles per MFMA and SIMD
-                         "frac_of_measured_peak": round(dom_tops / peak_tops, 4) if peak_tops else None,
-                         "whole_path_frac_of_measured_peak": round(value / world * OPS_PER_IMAGE / (peak_tops * 1e12), 4) if peak_tops else None,
-                         "all_conv_achieved": round(achieved, 2),
-                         "all_conv_frac": round(achieved * 1e12 / PEAK_I8_DENSE, 4),
-                         "layers": layers,
-                         "head_ms": round(float(layer_ms[10]), 4), "nms_ms": round(float(layer_ms[11]), 4)},
-        }
-        res["same_input_every_step"] = {
-            "value": round(world * B * args.steps / dt_same, 1), "unit": "images/sec", "ms_per_step": round(dt_same / args.steps * 1e3, 4),
-            "note": "ONE input batch fed to every step (rounds 1 / 2): part of its 133 MB stays in the 256 MB Infinity Cache; "
-                    "`value` rotates %d distinct batches" % N_INPUTS}
+            res["roofline"] = {"whole_path_frac": round(value / world * OPS_PER_IMAGE / PEAK_I8_DENSE, 4),
+                               "bound": "mfma", "achieved": round(dom_tops, 2), "peak": PEAK_I8_DENSE / 1e12,
+                               "unit": "TFLOP/s", "frac": round(dom_tops * 1e12 / PEAK_I8_DENSE, 4),
+                               "traffic": traffic, "traffic_source": traffic_src, "traffic_kernel": traffic_kernel,
+                               # traffic / launch_ms_rocprof are READ from the committed rocprofv3 passes of this workload (PMC counters cannot be
+                               # collected inside a timed run); stale = the newest committed file is from an earlier round than these kernels
+                               "traffic_stale": bool(traffic_src) and ("/" + PROFILE_ROUND + "_") not in traffic_src,
+                               "launch_ms_rocprof_stale": bool(rocprof_launch_ms(DOMINANT_KERNEL)[1]) and ("/" + PROFILE_ROUND + "_") not in rocprof_launch_ms(DOMINANT_KERNEL)[1],
+                               "kernel": DOMINANT_KERNEL + ", true> (conv6 and conv7: 2 launches/step, the largest share of "
+                                         "the step of any kernel; int8 ops = 2 x 398.72e6 MAC x %d images per launch)" % B,
+                               "launch_ms": round(dom_ms, 4),
+                               "launch_ms_rocprof": rocprof_launch_ms(DOMINANT_KERNEL)[0],
+                               "launch_ms_rocprof_source": rocprof_launch_ms(DOMINANT_KERNEL)[1],
+                               "frac_rocprof": (round(B * 2e6 * LAYER_MMAC[7] / (rocprof_launch_ms(DOMINANT_KERNEL)[0] * 1e-3) / PEAK_I8_DENSE, 4)
+                                                if rocprof_launch_ms(DOMINANT_KERNEL)[0] else None),
+                               "launch_ms_source": ("kernel start/end timestamps of the launch (hipExtLaunchKernelGGL events), mean of "
+                                                    "conv6 and conv7, median of %d profiled steps on the engine's stream" % nprof) if have_k
+                               else "interval between hipEventRecord before / after the launch",
+                               # the same launches while `streams` handles share the GPU (the timed region's regime: `ring_workgroups`
+                               # persistent workgroups per launch, other handles' kernels beside them); `frac` describes the kernel alone
+                               # on an idle GPU, whole_path_frac the run
+                               "launch_ms_in_timed_region": (round(float(kernel_ms_region[7] + kernel_ms_region[8]) / 2, 4)
+                                                             if kernel_ms_region is not None and kernel_ms_region[7] > 0 else None),
+                               "launch_ms_between_events": round(dom_between, 4),
+                               "frac_between_events": round(B * 2e6 * LAYER_MMAC[7] / (dom_between * 1e-3) / PEAK_I8_DENSE, 4),
+                               # every launch's own duration (ms): layers (the fused front end under "conv1"), then the head / NMS kernels
+                               "kernel_ms": {n: round(float(kernel_ms[i]), 4) for i, n in enumerate(knames) if kernel_ms[i] > 0},
+                               "kernel_ms_sum": round(float(kernel_ms.sum()), 4),
+                               "kernel_ms_in_timed_region": ({n: round(float(kernel_ms_region[i]), 4) for i, n in enumerate(knames)
+                                                              if kernel_ms_region[i] > 0} if kernel_ms_region is not None else None),
+                               # MFMA-only loop MEASURED IN THIS RUN (y355_mfma_peak_i8: v_mfma_i32_16x16x64_i8 back to back on register
+                               # operands, two waves per SIMD on every CU, ~50 ms) and the in-kernel clock it held
+                               "peak_measured": round(peak_tops, 1),
+                               "peak_measured_implied_clock_ghz": round(peak_tops * 1e12 / (1024 * 32768 / 16) / 1e9, 3),   # 16 cycles per MFMA and SIMD
+                               "frac_of_measured_peak": round(dom_tops / peak_tops, 4) if peak_tops else None,
+                               "whole_path_frac_of_measured_peak": round(value / world * OPS_PER_IMAGE / (peak_tops * 1e12), 4) if peak_tops else None,
+                               "all_conv_achieved": round(achieved, 2),
+                               "all_conv_frac": round(achieved * 1e12 / PEAK_I8_DENSE, 4),
+                               "layers": layers,
+                               "head_ms": round(float(layer_ms[10]), 4), "nms_ms": round(float(layer_ms[11]), 4)}
+            res["same_input_every_step"] = {
+                "value": round(world * B * args.steps / dt_same, 1), "unit": "images/sec", "ms_per_step": round(dt_same / args.steps * 1e3, 4),
+                "note": "ONE input batch fed to every step (rounds 1 / 2): part of its 133 MB stays in the 256 MB Infinity Cache; "
+                        "`value` rotates %d distinct batches" % N_INPUTS}
         res["config"]["entry_point"] = ("Pipeline.submit -> y355_pipeline_submit%s (include/yolo355.h), %d handles, outputs in caller buffers"
                                         % ("_u8" if args.input == "u8" else "", nstreams))
         if hand is not None:
@@ -1036,9 +1118,9 @@ def main():
             res["one_stream"] = {"value": round(v1, 1), "unit": "images/sec", "ms_per_step": round(one / args.steps * 1e3, 4),
                                  "whole_path_frac": round(v1 / world * OPS_PER_IMAGE / PEAK_I8_DENSE, 4),
                                  "note": "one engine handle on one stream: ms_per_step is the latency of a batch"}
-        if world == 1 and not args.no_sparse:
+        if world == 1 and args.full and not args.no_sparse:
             res["sparse_fixture"] = sparse_fixture(args, dev, nstreams, x)
-        if world == 1 and not args.no_sparse and args.input == "f32":
+        if world == 1 and args.full and not args.no_sparse and args.input == "f32":
             # the same workload fed as uint8 HWC BGR frames (BaseTransform fused into the first layer): a quarter of
             # the input bytes, same kernels behind the front end, same detections (tests/test_gpu_parity.py)
             fr4 = torch.from_numpy(synth.make_frames_u8(1000, B, H, W)).to(dev)
@@ -1073,13 +1155,13 @@ def main():
                                "note": "uint8 HWC BGR frames (33 MB per batch instead of 133 MB of fp32 planes), BaseTransform fused into the "
                                        "first layer; same detections (tests/test_gpu_parity.py).  front_end_launch_ms: the fused front end's own "
                                        "duration on this route and on the fp32 route (one handle alone)"}
-        if world == 1 and not args.no_other_configs:
+        if world == 1 and args.full and not args.no_other_configs:
             # BASELINE.json configs[2] / configs[3], a few steps each: a driver-visible number for them
             import copy
             oc = {}
             for wl in ("slim_fp32", "tiny_int8"):
                 a2 = copy.copy(args)
-                a2.workload, a2.steps, a2.warmup, a2.batch = wl, min(args.steps, 10), 3, PER_GPU_BATCH
+                a2.workload, a2.steps, a2.warmup, a2.batch, a2.dump_outputs = wl, min(args.steps, 10), 3, PER_GPU_BATCH, None
                 r = measure_net(a2)
                 oc[wl] = {"workload": r["config"]["workload"], "value": r["value"], "unit": "images/sec",
                           "ms_per_step": r["ms_per_step"], "steps": r["steps"], "dtype": r["dtype"],
@@ -1088,7 +1170,7 @@ def main():
                           "conv_roofline_frac": r["roofline"]["frac"], "conv_achieved_tflops": r["roofline"]["achieved"],
                           "peak_tflops": r["roofline"]["peak"]}
             res["other_configs"] = oc
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"], grid = cpu_baseline()
             res["cpu_baseline_pytorch"], grid2 = cpu_baseline_torch()
             grid.update(grid2)

@@ -2,7 +2,7 @@
 # GPU box: the round's rocprofv3 evidence -> gpurun_out/r03_* (copied into profiles/ afterwards).
 # kernel stats of bench.py's default run and of --streams 1; configs 3/4; then PMC passes (separate, kernel-trace only).
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
-B="--steps 50 --warmup 10 --repeats 5 --no-cpu-baseline --no-sparse --no-other-configs"
+B="--full --steps 50 --warmup 10 --repeats 5 --no-cpu-baseline --no-sparse --no-other-configs"
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r03_ks3 -- python3 bench.py $B > gpurun_out/r03_bench_under_rocprof.json 2> gpurun_out/r03_ks3.err
 cp gpurun_out/r03_ks3/*/*_kernel_stats.csv gpurun_out/r03_kernel_stats.csv
 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/r03_ks1 -- python3 bench.py $B --streams 1 > gpurun_out/r03_bench_under_rocprof_one_stream.json 2> gpurun_out/r03_ks1.err

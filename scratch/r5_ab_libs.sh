@@ -5,7 +5,7 @@ PKG="yolo-compression-and-deployment-in-fpga_amd"
 cp $PKG/yolo355/libyolo355.so /tmp/lib_prod.so
 for r in $(seq 1 ${2:-3}); do for v in $1; do
 cp scratch/variants/lib_$v.so $PKG/yolo355/libyolo355.so
-python bench.py $3 --no-cpu-baseline --no-other-configs --no-sparse --repeats 8 2>/dev/null | python -c "
+python bench.py --full $3 --no-cpu-baseline --no-other-configs --no-sparse --repeats 8 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 km = d['roofline']['kernel_ms']

@@ -2,7 +2,7 @@
 # GPU box: interleaved A/B of the settings of Y355_OPT_FUSE_PAIRS on the headline (three handles) and one stream: r5_ab_pairs.sh "<values>" [rounds]
 cd /tmp && export TMPDIR=/tmp; cd $GRAFT_REPO_ROOT
 for r in $(seq 1 ${2:-3}); do for v in ${1:-0 1 4}; do
-python bench.py --fuse-pairs $v --no-cpu-baseline --no-other-configs --no-sparse --repeats 8 2>/dev/null | python -c "
+python bench.py --full --fuse-pairs $v --no-cpu-baseline --no-other-configs --no-sparse --repeats 8 2>/dev/null | python -c "
 import sys, json
 d = json.loads([l for l in sys.stdin if l.startswith('{')][-1])
 km = d['roofline']['kernel_ms']

@@ -5,6 +5,7 @@ import os
 import subprocess
 import sys
 
+import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -23,7 +24,7 @@ def _run(extra, timeout=900):
 
 @pytest.mark.gpu
 def test_force_dist_bench_verifies_its_gather():
-    d = _run(["--force-dist", "--steps", "3", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--no-sparse", "--no-other-configs"])
+    d = _run(["--full", "--force-dist", "--steps", "3", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--no-sparse", "--no-other-configs"])
     assert d["gather_verified"] is True and d["mismatching_records"] == 0 and d["mismatching_values_c_abi_route"] == 0
     assert d["mismatching_records_full"] == 0 and d["dist_backend"] == "nccl"
     assert d["dist_world_size"] == 1 and d["y355_comm_world"] == 1 and d["records_compared"] == 64
@@ -38,7 +39,7 @@ def test_force_dist_bench_verifies_its_gather():
 
 @pytest.mark.gpu
 def test_bench_line_carries_the_contract_fields():
-    d = _run(["--steps", "4", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--no-sparse", "--no-other-configs"])
+    d = _run(["--full", "--steps", "4", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--no-sparse", "--no-other-configs"])
     for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline",
               "dtype", "data", "config", "roofline", "same_input_every_step", "one_stream", "timing"):
         assert k in d, k
@@ -75,7 +76,8 @@ def test_world2_bench_logic_on_one_gpu():
         env.pop(k, None)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
            "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--dist-backend", "gloo", "--share-gpu",
-           "--steps", "3", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--no-sparse", "--no-other-configs"]
+           "--full", "--steps", "3", "--warmup", "2", "--repeats", "2", "--no-cpu-baseline", "--no-sparse",
+           "--no-other-configs"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=1200)
     assert r.returncode == 0, (r.stdout[-2000:], r.stderr[-3000:])
     lines = [l for l in r.stdout.strip().splitlines() if l.strip().startswith("{")]
@@ -95,3 +97,58 @@ def test_world2_bench_logic_on_one_gpu():
     assert pr["min"] * 2 >= d["value"] * 0.5                # the aggregate cannot be far above twice the slowest rank's own rate
     assert d["n1_same_process"]["value"] > 0 and d["n1_same_process"]["ms_per_step"] > 0
     assert isinstance(d["rccl_version"], str) and d["rccl_version"]
+
+
+@pytest.mark.gpu
+def test_plain_bench_times_its_steps_and_dumps_the_last_one(tmp_path):
+    """A run without --full: one timed region of exactly --steps steps, the headline fields only, and --dump-outputs writes
+    the detections of the last timed step -- the same arrays from two runs with the same arguments."""
+    dumps = []
+    for n in range(2):
+        out = tmp_path / ("run%d" % n)
+        d = _run(["--gpus", "1", "--steps", "5", "--warmup", "2", "--dump-outputs", str(out)])
+        for k in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "dtype", "timing"):
+            assert k in d, k
+        assert d["metric"] == "images/sec slim_yolo_v2 int8 416x416" and d["unit"] == "images/sec" and d["dtype"] == "int8"
+        assert d["steps"] == 5 and d["warmup"] == 2 and d["timing"]["repeats"] == 1 and d["higher_is_better"] is True
+        assert d["timing"]["warmup_steps_run"] >= 2 and d["timing"]["warmup_seconds"] > 0
+        assert d["value"] > 0 and abs(d["value"] * d["ms_per_step"] / 1e3 - 64) < 0.1      # 64 images per step
+        for k in ("roofline", "one_stream", "same_input_every_step", "hand_scheduled", "sparse_fixture", "u8_input", "other_configs",
+                  "cpu_baseline"):
+            assert k not in d, k
+        arrays = {k: np.load(out / (k + ".npy")) for k in ("boxes", "scores", "classes", "count")}
+        assert all(a.dtype == np.float32 for a in arrays.values())
+        assert sum((out / f).stat().st_size for f in os.listdir(out)) <= 64_000_000
+        cnt = arrays["count"]
+        assert cnt.shape == (64,) and arrays["scores"].shape[0] == 64 and arrays["boxes"].shape == arrays["scores"].shape + (4,)
+        assert int(cnt.sum()) == d["config"]["detections_per_step_rank0"] > 0
+        pad = np.arange(arrays["scores"].shape[1])[None, :] >= cnt[:, None]
+        assert not arrays["scores"][pad].any() and not arrays["boxes"][pad].any() and (arrays["scores"][~pad] > 0).all()
+        dumps.append(arrays)
+    for k in dumps[0]:
+        assert np.array_equal(dumps[0][k], dumps[1][k]), k
+
+
+def test_dump_helpers_zero_the_padding_and_stay_under_the_limit(tmp_path, monkeypatch):
+    import importlib.util
+    import torch
+    spec = importlib.util.spec_from_file_location("bench_under_test", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    outs = (torch.rand(4, 6, 4) + 1, torch.rand(4, 6) + 1, torch.randint(1, 3, (4, 6), dtype=torch.int32),
+            torch.tensor([2, 0, 6, 5], dtype=torch.int32))
+    h = bench.host_outputs(outs, 3)                      # rows past B are not the step's
+    assert h["count"].tolist() == [2, 0, 6] and all(a.dtype == np.float32 for a in h.values())
+    assert (h["scores"] != 0).sum(1).tolist() == [2, 0, 6] and (h["boxes"] != 0).all(2).sum(1).tolist() == [2, 0, 6]
+    assert np.array_equal(h["scores"][2], outs[1][2].numpy()) and np.array_equal(h["classes"][0, :2], outs[2][0, :2].numpy())
+    big = {"boxes": np.ones((64, 3380, 4), np.float32), "scores": np.ones((64, 3380), np.float32),
+           "classes": np.ones((64, 3380), np.float32), "count": np.arange(64, dtype=np.float32)}
+    monkeypatch.setattr(bench, "DUMP_LIMIT_BYTES", 1_000_000)
+    for n in range(2):
+        bench.write_outputs(str(tmp_path / str(n)), big)
+    files = sorted(os.listdir(tmp_path / "0"))
+    assert files == ["boxes.npy", "classes.npy", "count.npy", "image_index.npy", "scores.npy"]
+    assert sum((tmp_path / "0" / f).stat().st_size for f in files) <= 1_000_000
+    idx = np.load(tmp_path / "0" / "image_index.npy")
+    assert np.array_equal(np.load(tmp_path / "0" / "count.npy"), idx.astype(np.float32))     # every array: the same images
+    assert np.array_equal(idx, np.load(tmp_path / "1" / "image_index.npy"))                    # a fixed sample

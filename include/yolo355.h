@@ -254,6 +254,34 @@ int y355_conv_op_forward(y355_conv_op *op, const float *x_dev, const float *resi
                          float *out_dev, void *stream);
 int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int batch, int height, int width, float *out_dev, void *stream,
                             int32_t *sa_in, int32_t *exact);
+/* --- general convolution geometry: what nn.Conv2d (groups 1, zero padding) accepts, for the layers the entry points above do
+ * not take (utils/modules.py Conv2d / Conv2d_fuse / Conv2d_fuse_nobias, backbone/darknet.py Conv_BN_LeakyReLU).
+ *   kh, kw 1..32; stride_h, stride_w 1..16; dil_h, dil_w 1..32; pad_top, pad_bottom, pad_left, pad_right 0..64 each (four pads:
+ *   padding='same' pads asymmetrically when dil * (k - 1) is odd, the extra pixel bottom / right).
+ *   Ho = (height + pad_top + pad_bottom - dil_h * (kh - 1) - 1) / stride_h + 1, Wo likewise; both must be >= 1.
+ *   y355_conv_geom_out_size: (Ho, Wo) of a geometry on a height x width map; Y355_EINVAL outside the limits.  No GPU needed.
+ *   y355_conv2d_geom_bf16: y355_conv2d_bf16's arithmetic and arguments for any geometry (w [cout][cin][kh][kw]; residual and
+ *     out [B][cout][Ho][Wo]).
+ *   y355_conv_geom_i8_raw: y355_conv3x3_i8_raw's for any geometry (q_w int8 [cout][cin][kh][kw]; out int64 [B][cout][Ho][Wo] = t',
+ *     Conv2d_fuse(x) == t' / 2^F' exactly).  Y355_ERANGE when 127 * 127 * cin * kh * kw does not fit int32 (cin * kh * kw >
+ *     133144): the int32 accumulator could wrap.  flags: Y355_OP_LEAKY or Y355_OP_RELU; Y355_OP_POOL is Y355_EINVAL.
+ *   y355_conv_op_create_*_geom: a y355_conv_op of that geometry, driven by y355_conv_op_forward / y355_conv_op_forward_i8 as
+ *     above (same route verdict, same *exact contract; out_dev [B][cout][Ho][Wo]).
+ * These always run the general-geometry kernel (convgeom.hip), 3x3 / pad 1 included.  Arguments are checked before any HIP
+ * call. */
+typedef struct y355_conv_geom {
+    int32_t kh, kw, stride_h, stride_w, dil_h, dil_w, pad_top, pad_bottom, pad_left, pad_right;
+} y355_conv_geom;
+int y355_conv_geom_out_size(const y355_conv_geom *g, int height, int width, int *ho, int *wo);
+int y355_conv2d_geom_bf16(int device_id, const float *x, const float *w, const float *bias, const float *residual, int batch, int cin,
+                          int cout, int height, int width, const y355_conv_geom *g, float neg_slope, int out_fp32, float *out);
+int y355_conv_geom_i8_raw(int device_id, const int8_t *q_in, const int8_t *q_w, const int32_t *q_b, int batch, int cin, int cout,
+                          int height, int width, const y355_conv_geom *g, int sa_in, int e_w, int e_b, int flags, int64_t *out,
+                          int32_t *frac_bits);
+int y355_conv_op_create_bf16_geom(int device_id, const float *w, const float *bias, int cin, int cout, const y355_conv_geom *g,
+                                  float neg_slope, y355_conv_op **out);
+int y355_conv_op_create_i8_geom(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, const y355_conv_geom *g,
+                                int e_w, int e_b, int flags, y355_conv_op **out);
 /* F.interpolate(x, scale_factor=2.0, mode='bilinear', align_corners=True) (models/yolo_v3.py:211,215) on fp32:
  * [B][C][H][W] -> [B][C][2H][2W]; fp32 arithmetic (within 1e-6 of torch's) */
 int y355_upsample2x_f32(int device_id, const float *in, int batch, int channels, int height, int width, float *out);

@@ -114,7 +114,8 @@ int prepare_kernels() { return y355_prepare_kernels(); }
 // leakyReLU=False: t' = max(t, 0), F' = F; runs on the generic kernels, whose epilogue honours neg_mul = 0)
 // wabs: max over output channels of sum |q_w| when known (else 0: 127 per weight is assumed) -- only Requant::tmax_log2, the
 // gate of the fp32-exact epilogues, uses this tight bound; `wide` keeps the operand-independent one
-int make_requant(int cin_real, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, int retune,
+// taps: kernel taps per input channel in the worst-case bound (9 for the 3x3 layers; the general geometry of convgeom.hip)
+int make_requant(int cin_real, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, int retune,
                  const int32_t *q_b, int cout, int cout_pad, Requant *rq, int *frac_bits, std::vector<int32_t> *bias_t,
                  std::vector<long long> *bias_w, long long wabs = 0) {
     const int F = std::max(sa_in + e_w, e_b);
@@ -131,7 +132,7 @@ int make_requant(int cin_real, int sa_in, int e_w, int e_b, int sa_out, bool hav
         (*bias_w)[c] = v;
         (*bias_t)[c] = (int32_t)v;     // only used when the 32-bit path is selected below
     }
-    long long tmax = ((long long)127 * 127 * 9 * cin_real) * (1ll << shl) + bmax;
+    long long tmax = ((long long)127 * 127 * taps * cin_real) * (1ll << shl) + bmax;
     if (leaky) tmax *= 8;
     int sh = have_out ? Fp - sa_out : 0;
     if (sh > 62) sh = 62;
@@ -144,7 +145,7 @@ int make_requant(int cin_real, int sa_in, int e_w, int e_b, int sa_out, bool hav
     rq->wide = lim >= std::ldexp(1.0L, 30) ? 1 : 0;
     long long negsafe_t0 = 0;
     {
-        const long long rowsum = wabs > 0 ? wabs : (long long)127 * 9 * cin_real;
+        const long long rowsum = wabs > 0 ? wabs : (long long)127 * taps * cin_real;
         const long long t0 = (127 * rowsum) * (1ll << shl) + bmax;
         int n = 0;
         while (n < 62 && t0 >= (1ll << n)) ++n;
@@ -172,9 +173,9 @@ int make_requant(int cin_real, int sa_in, int e_w, int e_b, int sa_out, bool hav
 }  // namespace
 
 // the integer epilogue of one stand-alone layer without requantisation (the operator objects of ops.hip)
-int y355_op_requant(int cin, int sa_in, int e_w, int e_b, int act, const int32_t *q_b, int cout, int cout_pad, Requant *rq,
+int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int act, const int32_t *q_b, int cout, int cout_pad, Requant *rq,
                     int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w) {
-    return make_requant(cin, sa_in, e_w, e_b, 0, false, act, 10, q_b, cout, cout_pad, rq, frac_bits, bias_t, bias_w);
+    return make_requant(cin, taps, sa_in, e_w, e_b, 0, false, act, 10, q_b, cout, cout_pad, rq, frac_bits, bias_t, bias_w);
 }
 
 struct y355_engine {
@@ -494,7 +495,7 @@ static int refresh_layer(y355_engine *h, int k, bool need_out) {
     if (!L.bias_dirty) return 0;
     std::vector<int32_t> bt;
     std::vector<long long> bw;
-    int rc = make_requant(L.cin, h->sa[k], L.e_w, L.e_b, h->sa[k + 1], h->sa_set[k + 1], L.leaky, h->retune[k],
+    int rc = make_requant(L.cin, 9, h->sa[k], L.e_w, L.e_b, h->sa[k + 1], h->sa_set[k + 1], L.leaky, h->retune[k],
                           L.q_b.data(), L.cout, L.cout_pad, &L.rq, &L.frac_bits, &bt, &bw, L.wabs);
     if (rc) return rc;
     HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
@@ -1208,7 +1209,7 @@ extern "C" int y355_conv3x3_i8_raw(int device_id, const int8_t *q_in, const int8
     int fb = 0;
     std::vector<int32_t> bt;
     std::vector<long long> bw;
-    if (int rc = make_requant(cin, sa_in, e_w, e_b, 0, false, leaky, 10, q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
+    if (int rc = make_requant(cin, 9, sa_in, e_w, e_b, 0, false, leaky, 10, q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
     const size_t in_elems = ((size_t)batch * (H + 2) * (W + 2) + 64) * cpad;
     std::vector<int8_t> xin(in_elems, 0);
     for (int b = 0; b < batch; ++b)
@@ -1288,7 +1289,7 @@ extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const in
     int fb = 0;
     std::vector<int32_t> bt;
     std::vector<long long> bw;
-    if (int rc = make_requant(cin, sa_in, e_w, e_b, sa_out, true, leaky, 10, q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
+    if (int rc = make_requant(cin, 9, sa_in, e_w, e_b, sa_out, true, leaky, 10, q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
     // host-side layout conversion: NCHW -> NHWC with halo and zero channel padding
     const size_t in_elems = ((size_t)batch * (H + 2) * (W + 2) + 64) * cpad;
     std::vector<int8_t> xin(in_elems, 0);

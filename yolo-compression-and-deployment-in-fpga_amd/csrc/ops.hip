@@ -427,7 +427,7 @@ __global__ void raw_to_nchw_f32_kernel(const long long *raw, float *out, int B, 
     } while (0)
 }  // namespace
 int y355_prepare_kernels();
-int y355_op_requant(int cin, int sa_in, int e_w, int e_b, int act, const int32_t *q_b, int cout, int cout_pad, Requant *rq,
+int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int act, const int32_t *q_b, int cout, int cout_pad, Requant *rq,
                     int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w);       // engine.hip
 
 extern "C" int y355_reorg_f32_dev(const float *x_dev, int batch, int channels, int height, int width, int stride, float *out_dev, void *stream) {
@@ -490,6 +490,9 @@ struct y355_conv_op {
     char *in_dev = nullptr, *out_dev = nullptr, *res_dev = nullptr;
     size_t in_cap = 0, out_cap = 0, res_cap = 0;
     size_t geo = 0;                    // (batch, H, W, output type) the halo buffers were last zeroed for
+    // general geometry (y355_conv_op_create_*_geom): the convgeom.hip kernel; w_kid / w_cout_pad = its tile shape and padding
+    int geom = 0;
+    y355_conv_geom g{};
 };
 
 static int op_grow(char **p, size_t *cap, size_t need, bool zero) {
@@ -502,6 +505,11 @@ static int op_grow(char **p, size_t *cap, size_t need, bool zero) {
     *cap = need;
     return 0;
 }
+
+static int geom_forward_bf16(y355_conv_op *op, const float *x_dev, const float *residual_dev, int batch, int height, int width, int out_fp32,
+                             float *out_dev, hipStream_t s);
+static int geom_forward_i8(y355_conv_op *op, const float *x_dev, int batch, int height, int width, float *out_dev, hipStream_t s,
+                           int32_t *sa_in, int32_t *exact);
 
 extern "C" void y355_conv_op_destroy(y355_conv_op *op) {
     if (!op) return;
@@ -540,6 +548,7 @@ extern "C" int y355_conv_op_forward(y355_conv_op *op, const float *x_dev, const 
     if (batch < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
     if (out_fp32 && residual_dev) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
     hipStream_t s = (hipStream_t)stream_;
+    if (op->geom) return geom_forward_bf16(op, x_dev, residual_dev, batch, height, width, out_fp32, out_dev, s);
     DEVCHK(hipSetDevice(op->device));
     const int in_pb = op->cin_pad * 2, taps = op->ksize * op->ksize, stride = op->stride;
     const int kid = y355_convg_select(in_pb, op->cout, 0, height, width, stride);
@@ -662,6 +671,7 @@ extern "C" int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int
     if (!op || op->kind != 1 || !x_dev || !out_dev || !exact) return y355_fail(Y355_EINVAL, "null argument / not an int8 operator");
     if (batch < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
     hipStream_t s = (hipStream_t)stream_;
+    if (op->geom) return geom_forward_i8(op, x_dev, batch, height, width, out_dev, s, sa_in, exact);
     DEVCHK(hipSetDevice(op->device));
     *exact = 0;
     const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * height * width;
@@ -682,7 +692,7 @@ extern "C" int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int
     if (sa != op->sa_cached) {
         std::vector<int32_t> bt;
         std::vector<long long> bw;
-        if (int rc = y355_op_requant(op->cin, sa, op->e_w, op->e_b, op->act, op->qb.data(), op->cout, op->cout_pad8, &op->rq, &op->frac_bits, &bt, &bw))
+        if (int rc = y355_op_requant(op->cin, 9, sa, op->e_w, op->e_b, op->act, op->qb.data(), op->cout, op->cout_pad8, &op->rq, &op->frac_bits, &bt, &bw))
             return rc;
         DEVCHK(hipMemcpy(op->bt_dev, bt.data(), sizeof(int) * op->cout_pad8, hipMemcpyHostToDevice));
         DEVCHK(hipMemcpy(op->bw_dev, bw.data(), sizeof(long long) * op->cout_pad8, hipMemcpyHostToDevice));
@@ -718,6 +728,376 @@ extern "C" int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int
     DEVCHK(hipGetLastError());
     hipLaunchKernelGGL(raw_to_nchw_f32_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const long long *)op->out_dev, out_dev, batch, op->cout, height,
                        width, op->cout_pad8, std::ldexp(1.0f, -op->frac_bits));
+    DEVCHK(hipGetLastError());
+    *exact = 1;
+    return 0;
+}
+
+
+// ==========================================================================================================================
+// General convolution geometry (include/yolo355.h y355_conv_geom): any kernel size, stride, dilation and four zero pads, on the
+// implicit-GEMM kernel of convgeom.hip.  The layouts are those of the entry points above -- input NHWC with a one-pixel halo
+// (nchw_to_nhwc_bf16_kernel / dyadic_to_nhwc_i8_kernel), bf16 output NHWC with a halo back through nhwc_*_to_nchw_kernel, int8
+// t' [pixel][cout_pad] through raw_to_nchw_f32_kernel -- and the integer epilogue is make_requant's with the layer's tap count.
+namespace {
+constexpr long long GEOM_I8_MAX_K = 133144;      // 127 * 127 * cin * kh * kw <= INT32_MAX
+
+int geom_limits(const y355_conv_geom *g) {
+    if (!g) return y355_fail(Y355_EINVAL, "null geometry");
+    if (g->kh < 1 || g->kh > 32 || g->kw < 1 || g->kw > 32) return y355_fail(Y355_EINVAL, "kernel size 1..32");
+    if (g->stride_h < 1 || g->stride_h > 16 || g->stride_w < 1 || g->stride_w > 16) return y355_fail(Y355_EINVAL, "stride 1..16");
+    if (g->dil_h < 1 || g->dil_h > 32 || g->dil_w < 1 || g->dil_w > 32) return y355_fail(Y355_EINVAL, "dilation 1..32");
+    for (int v : {g->pad_top, g->pad_bottom, g->pad_left, g->pad_right})
+        if (v < 0 || v > 64) return y355_fail(Y355_EINVAL, "padding 0..64 on each side");
+    return 0;
+}
+
+int geom_out(const y355_conv_geom *g, int batch, int height, int width, int *ho, int *wo) {
+    if (int rc = geom_limits(g)) return rc;
+    if (batch < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    const int hn = height + g->pad_top + g->pad_bottom - g->dil_h * (g->kh - 1) - 1;
+    const int wn = width + g->pad_left + g->pad_right - g->dil_w * (g->kw - 1) - 1;
+    if (hn < 0 || wn < 0) return y355_fail(Y355_EINVAL, "the dilated kernel is larger than the padded input (Ho or Wo < 1)");
+    *ho = hn / g->stride_h + 1;
+    *wo = wn / g->stride_w + 1;
+    if ((long long)batch * *ho * *wo > 0x7fffffffll || (long long)batch * (height + 2) * (width + 2) > 0x7fffffffll)
+        return y355_fail(Y355_EINVAL, "too many pixels");
+    return 0;
+}
+
+int geom_i8_k(int cin, const y355_conv_geom *g) {
+    if ((long long)cin * g->kh * g->kw > GEOM_I8_MAX_K)
+        return y355_fail(Y355_ERANGE, "127 * 127 * cin * kh * kw does not fit the int32 accumulator (cin * kh * kw > 133144)");
+    return 0;
+}
+
+ConvGeomParams geom_params(const y355_conv_geom &g, int batch, int height, int width, int ho, int wo, int in_pb, int cout_pad, int bn) {
+    ConvGeomParams p{};
+    p.B = batch; p.H = height; p.W = width; p.Ho = ho; p.Wo = wo; p.M = batch * ho * wo;
+    p.in_pb = in_pb; p.nchunk = in_pb / 64;
+    p.kh = g.kh; p.kw = g.kw; p.sh = g.stride_h; p.sw = g.stride_w; p.dh = g.dil_h; p.dw = g.dil_w; p.pt = g.pad_top; p.pl = g.pad_left;
+    p.nblk = cout_pad / bn; p.cout_pad = cout_pad;
+    return p;
+}
+
+int geom_act(int flags) { return (flags & Y355_OP_LEAKY) ? 1 : ((flags & Y355_OP_RELU) ? 2 : 0); }
+int geom_flags(int flags) {
+    if ((flags & Y355_OP_LEAKY) && (flags & Y355_OP_RELU)) return y355_fail(Y355_EINVAL, "LeakyReLU and ReLU are exclusive");
+    if (flags & Y355_OP_POOL) return y355_fail(Y355_EINVAL, "no fused max-pool on the general geometry");
+    return 0;
+}
+}  // namespace
+
+extern "C" int y355_conv_geom_out_size(const y355_conv_geom *g, int height, int width, int *ho, int *wo) {
+    if (!ho || !wo) return y355_fail(Y355_EINVAL, "null argument");
+    return geom_out(g, 1, height, width, ho, wo);
+}
+
+extern "C" int y355_conv2d_geom_bf16(int device_id, const float *x, const float *w, const float *bias, const float *residual, int batch,
+                                     int cin, int cout, int height, int width, const y355_conv_geom *g, float neg_slope, int out_fp32,
+                                     float *out) {
+    if (!x || !w || !out || !g) return y355_fail(Y355_EINVAL, "null argument");
+    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    int Ho = 0, Wo = 0;
+    if (int rc = geom_out(g, batch, height, width, &Ho, &Wo)) return rc;
+    if (out_fp32 && residual) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
+    std::vector<void *> bufs;
+    OPS2CHK(hipSetDevice(device_id));
+    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
+    const int M = batch * Ho * Wo, taps = g->kh * g->kw;
+    const int kid = y355_convgeom_select(M, cout, y355_cu_count());
+    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
+    const int in_pb = (cin + 31) / 32 * 64, cout_pad = (cout + ki.bn - 1) / ki.bn * ki.bn;
+    const size_t wbytes = y355_convgeom_packed_bytes(kid, in_pb, taps, cout_pad);
+    std::vector<char> wpk(wbytes);
+    y355_convgeom_pack(kid, 1, w, nullptr, cout, cin, taps, in_pb, cout_pad, wpk.data());
+    std::vector<float> bpad(cout_pad, 0.f);
+    if (bias) std::copy(bias, bias + cout, bpad.begin());
+    const size_t n_in = (size_t)batch * cin * height * width, n_out = (size_t)batch * cout * Ho * Wo;
+    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
+    const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
+    float *d_x = nullptr, *d_y = nullptr, *d_b = nullptr;
+    char *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_res = nullptr;
+    OPS2CHK(hipMalloc((void **)&d_x, std::max(n_in, n_out) * 4)); bufs.push_back(d_x);
+    OPS2CHK(hipMalloc((void **)&d_y, n_out * 4)); bufs.push_back(d_y);
+    OPS2CHK(hipMalloc((void **)&d_b, cout_pad * 4)); bufs.push_back(d_b);
+    OPS2CHK(hipMalloc((void **)&d_in, in_bytes)); bufs.push_back(d_in);
+    OPS2CHK(hipMalloc((void **)&d_out, out_bytes)); bufs.push_back(d_out);
+    OPS2CHK(hipMalloc((void **)&d_w, wbytes)); bufs.push_back(d_w);
+    OPS2CHK(hipMemset(d_in, 0, in_bytes));
+    OPS2CHK(hipMemset(d_out, 0, out_bytes));
+    OPS2CHK(hipMemcpy(d_w, wpk.data(), wbytes, hipMemcpyHostToDevice));
+    OPS2CHK(hipMemcpy(d_b, bpad.data(), cout_pad * 4, hipMemcpyHostToDevice));
+    if (residual) {
+        OPS2CHK(hipMalloc((void **)&d_res, out_bytes)); bufs.push_back(d_res);
+        OPS2CHK(hipMemset(d_res, 0, out_bytes));
+        OPS2CHK(hipMemcpy(d_x, residual, n_out * 4, hipMemcpyHostToDevice));
+        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, d_x, (unsigned short *)d_res, batch, cout, Ho,
+                           Wo, cout_pad);
+        OPS2CHK(hipDeviceSynchronize());
+    }
+    OPS2CHK(hipMemcpy(d_x, x, n_in * 4, hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, 0, d_x, (unsigned short *)d_in, batch, cin, height,
+                       width, in_pb / 2);
+    ConvGeomParams p = geom_params(*g, batch, height, width, Ho, Wo, in_pb, cout_pad, ki.bn);
+    p.in = d_in; p.w = d_w; p.bias_f = d_b; p.res = d_res; p.out = d_out;
+    p.out_pb = (int)out_pb; p.out_f32 = out_fp32 ? 1 : 0; p.slope = neg_slope;
+    y355_launch_convgeom(kid, 1, p, 0);
+    OPS2CHK(hipGetLastError());
+    if (out_fp32)
+        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, (const float *)d_out, d_y, batch, cout, Ho, Wo,
+                           cout_pad);
+    else
+        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, (const unsigned short *)d_out, d_y, batch,
+                           cout, Ho, Wo, cout_pad);
+    OPS2CHK(hipGetLastError());
+    OPS2CHK(hipDeviceSynchronize());
+    OPS2CHK(hipMemcpy(out, d_y, n_out * 4, hipMemcpyDeviceToHost));
+    for (void *q : bufs) (void)hipFree(q);
+    return 0;
+}
+
+extern "C" int y355_conv_geom_i8_raw(int device_id, const int8_t *q_in, const int8_t *q_w, const int32_t *q_b, int batch, int cin, int cout,
+                                     int height, int width, const y355_conv_geom *g, int sa_in, int e_w, int e_b, int flags, int64_t *out,
+                                     int32_t *frac_bits) {
+    if (!q_in || !q_w || !q_b || !out || !frac_bits || !g) return y355_fail(Y355_EINVAL, "null argument");
+    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    int Ho = 0, Wo = 0;
+    if (int rc = geom_out(g, batch, height, width, &Ho, &Wo)) return rc;
+    if (int rc = geom_flags(flags)) return rc;
+    if (int rc = geom_i8_k(cin, g)) return rc;
+    std::vector<void *> bufs;
+    OPS2CHK(hipSetDevice(device_id));
+    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
+    const int M = batch * Ho * Wo, taps = g->kh * g->kw;
+    const int kid = y355_convgeom_select(M, cout, y355_cu_count());
+    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
+    const int cpad = (cin + 63) / 64 * 64, cout_pad = (cout + ki.bn - 1) / ki.bn * ki.bn;
+    Requant rq{};
+    int fb = 0;
+    std::vector<int32_t> bt;
+    std::vector<long long> bw;
+    if (int rc = y355_op_requant(cin, taps, sa_in, e_w, e_b, geom_act(flags), q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
+    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * cpad;
+    std::vector<int8_t> xin(in_bytes, 0);
+    for (int b = 0; b < batch; ++b)
+        for (int c = 0; c < cin; ++c)
+            for (int y = 0; y < height; ++y)
+                for (int x = 0; x < width; ++x)
+                    xin[(((size_t)b * (height + 2) + y + 1) * (width + 2) + x + 1) * cpad + c] = q_in[(((size_t)b * cin + c) * height + y) * width + x];
+    const size_t wbytes = y355_convgeom_packed_bytes(kid, cpad, taps, cout_pad);
+    std::vector<char> wpk(wbytes);
+    y355_convgeom_pack(kid, 0, nullptr, q_w, cout, cin, taps, cpad, cout_pad, wpk.data());
+    const size_t raw_elems = (size_t)M * cout_pad;
+    char *d_in = nullptr, *d_w = nullptr;
+    long long *d_bw = nullptr, *d_raw = nullptr;
+    OPS2CHK(hipMalloc((void **)&d_in, in_bytes)); bufs.push_back(d_in);
+    OPS2CHK(hipMalloc((void **)&d_w, wbytes)); bufs.push_back(d_w);
+    OPS2CHK(hipMalloc((void **)&d_bw, sizeof(long long) * cout_pad)); bufs.push_back(d_bw);
+    OPS2CHK(hipMalloc((void **)&d_raw, sizeof(long long) * raw_elems)); bufs.push_back(d_raw);
+    OPS2CHK(hipMemcpy(d_in, xin.data(), in_bytes, hipMemcpyHostToDevice));
+    OPS2CHK(hipMemcpy(d_w, wpk.data(), wbytes, hipMemcpyHostToDevice));
+    OPS2CHK(hipMemcpy(d_bw, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
+    ConvGeomParams p = geom_params(*g, batch, height, width, Ho, Wo, cpad, cout_pad, ki.bn);
+    p.in = d_in; p.w = d_w; p.bias_w = d_bw; p.raw = d_raw;
+    p.shl = rq.shl; p.lk = rq.lk; p.neg_mul = rq.neg_mul;
+    y355_launch_convgeom(kid, 0, p, 0);
+    OPS2CHK(hipGetLastError());
+    OPS2CHK(hipDeviceSynchronize());
+    std::vector<long long> o(raw_elems);
+    OPS2CHK(hipMemcpy(o.data(), d_raw, sizeof(long long) * raw_elems, hipMemcpyDeviceToHost));
+    for (void *q : bufs) (void)hipFree(q);
+    for (int b = 0; b < batch; ++b)
+        for (int c = 0; c < cout; ++c)
+            for (int y = 0; y < Ho; ++y)
+                for (int x = 0; x < Wo; ++x)
+                    out[(((size_t)b * cout + c) * Ho + y) * Wo + x] = o[(((size_t)b * Ho + y) * Wo + x) * cout_pad + c];
+    *frac_bits = fb;
+    return 0;
+}
+
+extern "C" int y355_conv_op_create_bf16_geom(int device_id, const float *w, const float *bias, int cin, int cout, const y355_conv_geom *g,
+                                             float neg_slope, y355_conv_op **out) {
+    if (!w || !out || !g) return y355_fail(Y355_EINVAL, "null argument");
+    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    if (int rc = geom_limits(g)) return rc;
+    DEVCHK(hipSetDevice(device_id));
+    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
+    y355_conv_op *op = new y355_conv_op();
+    op->device = device_id;
+    op->kind = 0;
+    op->geom = 1;
+    op->g = *g;
+    op->cin = cin; op->cout = cout; op->slope = neg_slope;
+    op->cin_pad = (cin + 31) / 32 * 32;
+    op->w_host.assign(w, w + (size_t)cout * cin * g->kh * g->kw);
+    op->b_host.assign(cout, 0.f);
+    if (bias) std::copy(bias, bias + cout, op->b_host.begin());
+    *out = op;
+    return 0;
+}
+
+extern "C" int y355_conv_op_create_i8_geom(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, const y355_conv_geom *g,
+                                           int e_w, int e_b, int flags, y355_conv_op **out) {
+    if (!q_w || !q_b || !out || !g) return y355_fail(Y355_EINVAL, "null argument");
+    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    if (int rc = geom_limits(g)) return rc;
+    if (int rc = geom_flags(flags)) return rc;
+    if (int rc = geom_i8_k(cin, g)) return rc;
+    DEVCHK(hipSetDevice(device_id));
+    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
+    y355_conv_op *op = new y355_conv_op();
+    op->device = device_id;
+    op->kind = 1;
+    op->geom = 1;
+    op->g = *g;
+    op->cin = cin; op->cout = cout;
+    op->e_w = e_w; op->e_b = e_b;
+    op->act = geom_act(flags);
+    op->cpad = (cin + 63) / 64 * 64;
+    op->qw.assign(q_w, q_w + (size_t)cout * cin * g->kh * g->kw);
+    op->qb.assign(q_b, q_b + cout);
+    if (hipMalloc((void **)&op->flag_dev, 16) != hipSuccess) {
+        y355_conv_op_destroy(op);
+        return y355_fail(Y355_EHIP, "device allocation failed");
+    }
+    *out = op;
+    return 0;
+}
+
+static int geom_forward_bf16(y355_conv_op *op, const float *x_dev, const float *residual_dev, int batch, int height, int width, int out_fp32,
+                             float *out_dev, hipStream_t s) {
+    int Ho = 0, Wo = 0;
+    if (int rc = geom_out(&op->g, batch, height, width, &Ho, &Wo)) return rc;
+    DEVCHK(hipSetDevice(op->device));
+    const int M = batch * Ho * Wo, taps = op->g.kh * op->g.kw, in_pb = op->cin_pad * 2;
+    const int kid = y355_convgeom_select(M, op->cout, y355_cu_count());
+    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
+    const int cout_pad = (op->cout + ki.bn - 1) / ki.bn * ki.bn;
+    if (op->w_kid != kid || op->w_cout_pad != cout_pad) {          // first call, or a size that selects another tile shape: (re)pack
+        const size_t wbytes = y355_convgeom_packed_bytes(kid, in_pb, taps, cout_pad);
+        std::vector<char> wpk(wbytes);
+        y355_convgeom_pack(kid, 1, op->w_host.data(), nullptr, op->cout, op->cin, taps, in_pb, cout_pad, wpk.data());
+        std::vector<float> bpad(cout_pad, 0.f);
+        std::copy(op->b_host.begin(), op->b_host.end(), bpad.begin());
+        DEVCHK(hipStreamSynchronize(s));                           // a previous forward may still read the old fragments
+        if (op->w_dev) (void)hipFree(op->w_dev);
+        if (op->bias_dev) (void)hipFree(op->bias_dev);
+        op->w_dev = nullptr; op->bias_dev = nullptr;
+        DEVCHK(hipMalloc((void **)&op->w_dev, wbytes));
+        DEVCHK(hipMalloc((void **)&op->bias_dev, sizeof(float) * cout_pad));
+        DEVCHK(hipMemcpy(op->w_dev, wpk.data(), wbytes, hipMemcpyHostToDevice));
+        DEVCHK(hipMemcpy(op->bias_dev, bpad.data(), sizeof(float) * cout_pad, hipMemcpyHostToDevice));
+        op->w_kid = kid;
+        op->w_cout_pad = cout_pad;
+        op->geo = 0;
+    }
+    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * Ho * Wo;
+    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
+    const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
+    // zeroed on (re)allocation and on a new geometry: the staging kernels write the interior and the real channels only
+    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)out_fp32 << 62) ^ ((size_t)1 << 61);
+    const bool regeo = geo != op->geo;
+    op->geo = geo;
+    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
+    if (int rc = op_grow(&op->out_dev, &op->out_cap, out_bytes, true)) return rc;
+    if (regeo) DEVCHK(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
+    if (residual_dev) {
+        if (int rc = op_grow(&op->res_dev, &op->res_cap, out_bytes, true)) return rc;
+        if (regeo) DEVCHK(hipMemsetAsync(op->res_dev, 0, out_bytes, s));
+        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, residual_dev, (unsigned short *)op->res_dev, batch,
+                           op->cout, Ho, Wo, cout_pad);
+    }
+    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (unsigned short *)op->in_dev, batch, op->cin, height,
+                       width, op->cin_pad);
+    ConvGeomParams p = geom_params(op->g, batch, height, width, Ho, Wo, in_pb, cout_pad, ki.bn);
+    p.in = op->in_dev; p.w = op->w_dev; p.bias_f = op->bias_dev; p.res = residual_dev ? op->res_dev : nullptr; p.out = op->out_dev;
+    p.out_pb = (int)out_pb; p.out_f32 = out_fp32 ? 1 : 0; p.slope = op->slope;
+    y355_launch_convgeom(kid, 1, p, s);
+    DEVCHK(hipGetLastError());
+    if (out_fp32)
+        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const float *)op->out_dev, out_dev, batch, op->cout, Ho,
+                           Wo, cout_pad);
+    else
+        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const unsigned short *)op->out_dev, out_dev, batch,
+                           op->cout, Ho, Wo, cout_pad);
+    DEVCHK(hipGetLastError());
+    return 0;
+}
+
+static int geom_forward_i8(y355_conv_op *op, const float *x_dev, int batch, int height, int width, float *out_dev, hipStream_t s,
+                           int32_t *sa_in, int32_t *exact) {
+    int Ho = 0, Wo = 0;
+    if (int rc = geom_out(&op->g, batch, height, width, &Ho, &Wo)) return rc;
+    DEVCHK(hipSetDevice(op->device));
+    *exact = 0;
+    const int M = batch * Ho * Wo, taps = op->g.kh * op->g.kw;
+    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * Ho * Wo;
+    // (1) the exponent of x, as y355_conv_op_forward_i8
+    DEVCHK(hipMemsetAsync(op->flag_dev, 0, 16, s));
+    y355_launch_absmax(x_dev, n_in, op->flag_dev, s);
+    DEVCHK(hipGetLastError());
+    unsigned int bits = 0;
+    DEVCHK(hipMemcpyAsync(&bits, op->flag_dev, 4, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
+    float mx;
+    memcpy(&mx, &bits, 4);
+    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
+    const int sa = (int)std::floor(std::log2((1.0f / mx) * 127.0f));
+    if (sa < -64 || sa > 64) return 0;
+    if (sa_in) *sa_in = sa;
+    // (2) weights for this size's tile shape, the integer epilogue for this exponent (both cached)
+    const int kid = y355_convgeom_select(M, op->cout, y355_cu_count());
+    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
+    const int cout_pad = (op->cout + ki.bn - 1) / ki.bn * ki.bn;
+    if (op->w_kid != kid || op->w_cout_pad != cout_pad) {
+        const size_t wbytes = y355_convgeom_packed_bytes(kid, op->cpad, taps, cout_pad);
+        std::vector<char> wpk(wbytes);
+        y355_convgeom_pack(kid, 0, nullptr, op->qw.data(), op->cout, op->cin, taps, op->cpad, cout_pad, wpk.data());
+        DEVCHK(hipStreamSynchronize(s));
+        if (op->qw_dev) (void)hipFree(op->qw_dev);
+        if (op->bw_dev) (void)hipFree(op->bw_dev);
+        op->qw_dev = nullptr; op->bw_dev = nullptr;
+        DEVCHK(hipMalloc((void **)&op->qw_dev, wbytes));
+        DEVCHK(hipMalloc((void **)&op->bw_dev, sizeof(long long) * cout_pad));
+        DEVCHK(hipMemcpy(op->qw_dev, wpk.data(), wbytes, hipMemcpyHostToDevice));
+        op->w_kid = kid;
+        op->w_cout_pad = cout_pad;
+        op->sa_cached = 1 << 30;                                    // the biases are padded to the new width below
+    }
+    if (sa != op->sa_cached) {
+        std::vector<int32_t> bt;
+        std::vector<long long> bw;
+        if (int rc = y355_op_requant(op->cin, taps, sa, op->e_w, op->e_b, op->act, op->qb.data(), op->cout, cout_pad, &op->rq, &op->frac_bits, &bt,
+                                     &bw))
+            return rc;
+        DEVCHK(hipMemcpy(op->bw_dev, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
+        op->sa_cached = sa;
+    }
+    // (3) stage: int8 NHWC with halo + the dyadic verdict
+    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * op->cpad;
+    const size_t raw_bytes = sizeof(long long) * (size_t)M * cout_pad;
+    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)1 << 61);
+    const bool regeo = geo != op->geo;
+    op->geo = geo;
+    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
+    if (int rc = op_grow(&op->out_dev, &op->out_cap, raw_bytes, false)) return rc;
+    if (regeo) DEVCHK(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
+    hipLaunchKernelGGL(dyadic_to_nhwc_i8_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (int8_t *)op->in_dev, batch, op->cin, height, width,
+                       op->cpad, std::ldexp(1.0f, sa), op->flag_dev + 1);
+    DEVCHK(hipGetLastError());
+    unsigned int bad = 0;
+    DEVCHK(hipMemcpyAsync(&bad, op->flag_dev + 1, 4, hipMemcpyDeviceToHost, s));
+    DEVCHK(hipStreamSynchronize(s));
+    if (bad) return 0;
+    // (4) conv + bias + activation without requantisation, (5) t' / 2^F' -> fp32 NCHW
+    ConvGeomParams p = geom_params(op->g, batch, height, width, Ho, Wo, op->cpad, cout_pad, ki.bn);
+    p.in = op->in_dev; p.w = (const char *)op->qw_dev; p.bias_w = op->bw_dev; p.raw = (long long *)op->out_dev;
+    p.shl = op->rq.shl; p.lk = op->rq.lk; p.neg_mul = op->rq.neg_mul;
+    y355_launch_convgeom(kid, 0, p, s);
+    DEVCHK(hipGetLastError());
+    hipLaunchKernelGGL(raw_to_nchw_f32_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const long long *)op->out_dev, out_dev, batch, op->cout, Ho,
+                       Wo, cout_pad, std::ldexp(1.0f, -op->frac_bits));
     DEVCHK(hipGetLastError());
     *exact = 1;
     return 0;

@@ -437,3 +437,31 @@ bool y355_launch_pw_i8(const ConvGParams &p, hipStream_t s);        // 1x1, int8
 void y355_conv1f_tiles(int H, int W, int *tx, int *ty);
 void y355_launch_conv1f(const Conv1FParams &p, hipStream_t s);
 void y355_pack_conv1f(const float *w, char *dst);
+// General-geometry implicit-GEMM convolution (convgeom.hip): any kernel size, stride, dilation and four pads.
+// GEMM rows = output pixels of the whole batch (m = (b * Ho + oy) * Wo + ox), columns = output channels, K = taps x 64-byte
+// chunks of one input pixel.  Input NHWC with a one-pixel halo (the staging kernels of ops.hip), in_pb bytes per pixel;
+// taps that fall in the padding are zero by a predicate, never by a read.
+struct ConvGeomParams {
+    const char *in;           // [B][H + 2][W + 2][in_pb]
+    const char *w;            // y355_convgeom_pack order
+    const float *bias_f;      // bf16: [cout_pad]
+    const long long *bias_w;  // int8: [cout_pad] pre-shifted (q_b << (F - e_b))
+    const char *res;          // bf16: residual, same layout as out (or null)
+    char *out;                // bf16: [B][Ho + 2][Wo + 2][out_pb] (bf16 or fp32 channels)
+    long long *raw;           // int8: t' [M][cout_pad]
+    int B, H, W, Ho, Wo, M;
+    int in_pb, nchunk;        // bytes per input pixel (multiple of 64), 64-byte chunks per pixel
+    int kh, kw, sh, sw, dh, dw, pt, pl;
+    int nblk, cout_pad, out_pb, out_f32;
+    float slope;              // bf16: y = x >= 0 ? x : slope * x
+    int shl, lk, neg_mul;     // int8: t = acc * 2^shl + bias; t' = t >= 0 ? t * 2^lk : t * neg_mul
+};
+struct ConvGeomInfo { int bm, bn, wm, wn, mt, nt; size_t lds_bytes; };
+#define Y355_GEOM_COUNT 3
+const ConvGeomInfo *y355_convgeom_info(int id);
+int y355_convgeom_select(int M, int cout, int cu);
+int y355_prepare_convgeom(void);
+size_t y355_convgeom_packed_bytes(int id, int in_pb, int taps, int cout_pad);
+void y355_convgeom_pack(int id, int bf, const float *w_f, const int8_t *w_q, int cout, int cin, int taps, int in_pb, int cout_pad,
+                        char *dst);
+void y355_launch_convgeom(int id, int bf, const ConvGeomParams &p, hipStream_t s);

@@ -24,6 +24,7 @@ OPT_FUSE_PAIRS = 3
 NET_OPT_WORKGROUPS = 1
 NET_OPT_THIN_RESIDENT = 2
 EINVAL, EHIP, ENOTREADY = -1, -2, -3
+ERANGE = -4
 
 
 class Config(C.Structure):
@@ -47,6 +48,18 @@ class NetConfig(C.Structure):
 
 ARCH_SLIM_V2, ARCH_TINY_V3, ARCH_YOLO_V2, ARCH_YOLO_V3, ARCH_YOLO_V3_SPP = 0, 1, 2, 3, 4
 DT_INT8, DT_BF16 = 0, 1
+
+
+class ConvGeom(C.Structure):
+    """y355_conv_geom: kernel, stride, dilation and the four zero pads of one convolution"""
+    _fields_ = [(n, C.c_int32) for n in ("kh", "kw", "stride_h", "stride_w", "dil_h", "dil_w",
+                                         "pad_top", "pad_bottom", "pad_left", "pad_right")]
+
+    def astuple(self):
+        return tuple(int(getattr(self, n)) for n, _ in self._fields_)
+
+    def __repr__(self):
+        return "ConvGeom(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n, _ in self._fields_)
 
 
 class LayerStats(C.Structure):
@@ -112,6 +125,14 @@ _SIGS = {
     "y355_conv_op_destroy": (None, [C.c_void_p]),
     "y355_conv_op_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]),
     "y355_conv_op_forward_i8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, P(C.c_int32), P(C.c_int32)]),
+    "y355_conv_geom_out_size": (C.c_int, [P(ConvGeom), C.c_int, C.c_int, P(C.c_int), P(C.c_int)]),
+    "y355_conv2d_geom_bf16": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        C.c_int, P(ConvGeom), C.c_float, C.c_int, C.c_void_p]),
+    "y355_conv_geom_i8_raw": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                        P(ConvGeom), C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, P(C.c_int32)]),
+    "y355_conv_op_create_bf16_geom": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(ConvGeom), C.c_float, P(C.c_void_p)]),
+    "y355_conv_op_create_i8_geom": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(ConvGeom), C.c_int, C.c_int, C.c_int,
+                                              P(C.c_void_p)]),
     "y355_head_f32": (C.c_int, [C.c_int, C.c_int, P(C.c_void_p), P(C.c_int), P(C.c_int), P(C.c_float), P(C.c_float), C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),

@@ -630,33 +630,54 @@ class ConvOp:
     conv2d_bf16 / conv3x3_i8_raw for callers whose tensors are CUDA tensors -- forward takes and returns CUDA tensors on
     torch's current stream, no tensor crosses to the host."""
 
-    def __init__(self, handle, kind, cout, stride, device):
+    def __init__(self, handle, kind, cout, stride, device, geom=None):
         self._h, self.kind, self.cout, self.stride, self.device = handle, kind, int(cout), int(stride), device
+        self.geom = geom
         self._lib = _ffi.lib()
         _live.add(self)
 
     @classmethod
-    def bf16(cls, w, bias, stride=1, neg_slope=1.0, device=None):
+    def bf16(cls, w, bias, stride=1, neg_slope=1.0, device=None, geom=None):
+        """geom (a y355_conv_geom, see conv_geom): any kernel / stride / dilation / padding on the general-geometry kernel; stride is
+        then ignored"""
         dev = _require_gpu(device)
         wi = np.ascontiguousarray(w, dtype=np.float32)
         cout, cin, k, k2 = wi.shape
-        if k != k2:
-            raise ValueError("square kernels only")
         bi = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
         h = C.c_void_p()
+        if geom is not None:
+            g = _geom_for(geom, k, k2)
+            _ffi.check(_ffi.lib().y355_conv_op_create_bf16_geom(dev.index, wi.ctypes.data, None if bi is None else bi.ctypes.data, cin, cout,
+                                                                C.byref(g), float(neg_slope), C.byref(h)))
+            return cls(h, "bf16", cout, g.stride_h, dev, g)
+        if k != k2:
+            raise ValueError("square kernels only")
         _ffi.check(_ffi.lib().y355_conv_op_create_bf16(dev.index, wi.ctypes.data, None if bi is None else bi.ctypes.data, cin, cout, k,
                                                        int(stride), float(neg_slope), C.byref(h)))
         return cls(h, "bf16", cout, stride, dev)
 
     @classmethod
-    def int8(cls, q_w, q_b, e_w, e_b, leaky=True, relu=False, device=None):
+    def int8(cls, q_w, q_b, e_w, e_b, leaky=True, relu=False, device=None, geom=None):
+        """geom: as for bf16; without it the operator is 3x3 / stride 1 / pad 1"""
         dev = _require_gpu(device)
         qw = np.ascontiguousarray(q_w, dtype=np.int8)
         qb = np.ascontiguousarray(q_b, dtype=np.int32)
         h = C.c_void_p()
+        if geom is not None:
+            g = _geom_for(geom, qw.shape[2], qw.shape[3])
+            _ffi.check(_ffi.lib().y355_conv_op_create_i8_geom(dev.index, qw.ctypes.data, qb.ctypes.data, qw.shape[1], qw.shape[0], C.byref(g),
+                                                              int(e_w), int(e_b), _act_flag(leaky, relu), C.byref(h)))
+            return cls(h, "int8", qw.shape[0], g.stride_h, dev, g)
         _ffi.check(_ffi.lib().y355_conv_op_create_i8(dev.index, qw.ctypes.data, qb.ctypes.data, qw.shape[1], qw.shape[0], int(e_w), int(e_b),
                                                      _act_flag(leaky, relu), C.byref(h)))
         return cls(h, "int8", qw.shape[0], 1, dev)
+
+    def _out_hw(self, H, W):
+        if self.geom is not None:
+            return geom_out_size(self.geom, H, W)
+        if self.kind == "bf16" and self.stride == 2:
+            return (H + 1) // 2, (W + 1) // 2
+        return H, W
 
     def close(self):
         if self._h is not None:
@@ -673,7 +694,7 @@ class ConvOp:
         """bf16 form: x CUDA float32 [B,cin,H,W] -> CUDA float32 [B,cout,Ho,Wo] (asynchronous, torch's current stream)."""
         x = x.detach().to(dtype=torch.float32).contiguous()
         B, _, H, W = x.shape
-        Ho, Wo = ((H + 1) // 2, (W + 1) // 2) if self.stride == 2 else (H, W)
+        Ho, Wo = self._out_hw(H, W)
         out = torch.empty((B, self.cout, Ho, Wo), dtype=torch.float32, device=x.device)
         r = None if residual is None else residual.detach().to(dtype=torch.float32).contiguous()
         if r is not None and tuple(r.shape) != tuple(out.shape):
@@ -686,7 +707,8 @@ class ConvOp:
         """int8 form: Conv2d_fuse on a dyadic CUDA tensor, exact; returns None when x is not a dyadic int8 tensor."""
         x = x.detach().to(dtype=torch.float32).contiguous()
         B, _, H, W = x.shape
-        out = torch.empty((B, self.cout, H, W), dtype=torch.float32, device=x.device)
+        Ho, Wo = self._out_hw(H, W)
+        out = torch.empty((B, self.cout, Ho, Wo), dtype=torch.float32, device=x.device)
         sa, exact = C.c_int32(), C.c_int32()
         _ffi.check(self._lib.y355_conv_op_forward_i8(self._h, x.data_ptr(), B, H, W, out.data_ptr(),
                                                      torch.cuda.current_stream(x.device).cuda_stream, C.byref(sa), C.byref(exact)))
@@ -892,3 +914,81 @@ def upsample2x_f32(x, device_id=0):
     out = np.empty((B, Cc, 2 * H, 2 * W), np.float32)
     _ffi.check(lib.y355_upsample2x_f32(int(device_id), xi.ctypes.data, B, Cc, H, W, out.ctypes.data))
     return out
+
+
+# ---- general convolution geometry (y355_conv_geom, convgeom.hip) ---------------------------------------------------------
+def conv_geom(kernel_size, stride=1, dilation=1, padding=0):
+    """y355_conv_geom from int-or-pair kernel_size / stride / dilation and padding given as an int, a pair (h, w) or four pads
+    (top, bottom, left, right)"""
+    def pair(v):
+        return (int(v), int(v)) if np.isscalar(v) else (int(v[0]), int(v[1]))
+    kh, kw = pair(kernel_size)
+    sh, sw = pair(stride)
+    dh, dw = pair(dilation)
+    if np.isscalar(padding):
+        pads = (int(padding),) * 4
+    elif len(padding) == 2:
+        pads = (int(padding[0]), int(padding[0]), int(padding[1]), int(padding[1]))
+    else:
+        pads = tuple(int(p) for p in padding)
+    return _ffi.ConvGeom(kh, kw, sh, sw, dh, dw, *pads)
+
+
+def _as_geom(geom):
+    return geom if isinstance(geom, _ffi.ConvGeom) else _ffi.ConvGeom(*[int(v) for v in geom])
+
+
+def _geom_for(geom, kh, kw):
+    g = _as_geom(geom)
+    if (g.kh, g.kw) != (kh, kw):
+        raise ValueError("geometry %r does not match a %dx%d weight" % (g, kh, kw))
+    return g
+
+
+def geom_out_size(geom, height, width):
+    """(Ho, Wo) of a geometry on a height x width map (y355_conv_geom_out_size; raises Y355Error outside the limits).  No GPU."""
+    g = _as_geom(geom)
+    ho, wo = C.c_int(), C.c_int()
+    _ffi.check(_ffi.lib().y355_conv_geom_out_size(C.byref(g), int(height), int(width), C.byref(ho), C.byref(wo)))
+    return ho.value, wo.value
+
+
+def conv2d_geom_bf16(x, w, geom, bias=None, residual=None, neg_slope=1.0, out_fp32=False, device_id=0):
+    """conv2d_bf16's arithmetic for any geometry (y355_conv2d_geom_bf16): fp32 NCHW in and out, operands and result rounded to bf16"""
+    lib = _ffi.lib()
+    _need_gpu()
+    xi = np.ascontiguousarray(x, dtype=np.float32)
+    wi = np.ascontiguousarray(w, dtype=np.float32)
+    B, Cin, H, W = xi.shape
+    Cout, Cin2, kh, kw = wi.shape
+    if Cin2 != Cin:
+        raise ValueError("weight shape %s does not match the input's %d channels" % (wi.shape, Cin))
+    g = _geom_for(geom, kh, kw)
+    Ho, Wo = geom_out_size(g, H, W)
+    bi = None if bias is None else np.ascontiguousarray(bias, dtype=np.float32)
+    ri = None if residual is None else np.ascontiguousarray(residual, dtype=np.float32)
+    if ri is not None and ri.shape != (B, Cout, Ho, Wo):
+        raise ValueError("residual shape %s, expected %s" % (ri.shape, (B, Cout, Ho, Wo)))
+    out = np.empty((B, Cout, Ho, Wo), np.float32)
+    _ffi.check(lib.y355_conv2d_geom_bf16(int(device_id), xi.ctypes.data, wi.ctypes.data, None if bi is None else bi.ctypes.data,
+                                         None if ri is None else ri.ctypes.data, B, Cin, Cout, H, W, C.byref(g), float(neg_slope),
+                                         1 if out_fp32 else 0, out.ctypes.data))
+    return out
+
+
+def conv_geom_i8_raw(q_in, q_w, q_b, sa_in, e_w, e_b, geom, leaky=True, device_id=0, relu=False):
+    """conv3x3_i8_raw for any geometry (y355_conv_geom_i8_raw): (t' int64 [B,cout,Ho,Wo], F') with value = t' / 2^F', exact"""
+    lib = _ffi.lib()
+    _need_gpu()
+    qi = np.ascontiguousarray(q_in, dtype=np.int8)
+    qw = np.ascontiguousarray(q_w, dtype=np.int8)
+    qb = np.ascontiguousarray(q_b, dtype=np.int32)
+    B, cin, H, W = qi.shape
+    cout = qw.shape[0]
+    g = _geom_for(geom, qw.shape[2], qw.shape[3])
+    Ho, Wo = geom_out_size(g, H, W)
+    out = np.empty((B, cout, Ho, Wo), np.int64)
+    fb = C.c_int32()
+    _ffi.check(lib.y355_conv_geom_i8_raw(int(device_id), qi.ctypes.data, qw.ctypes.data, qb.ctypes.data, B, cin, cout, H, W, C.byref(g),
+                                         int(sa_in), int(e_w), int(e_b), _act_flag(leaky, relu), out.ctypes.data, C.byref(fb)))
+    return out, fb.value

@@ -13,12 +13,57 @@ Round 6: a CUDA tensor stays on the GPU.  The modules keep their weights packed 
 re-packed when a parameter's version changes) and call the device-pointer entry points on torch's current stream; the result is
 a CUDA tensor and no tensor crosses to the host.  (Conv2d_fuse's int8 route reads back eight bytes: the input's exponent and
 the verdict whether it is a dyadic int8 tensor decide the route on the host.)  CPU tensors take the host-pointer entry points.
+
+Any geometry nn.Conv2d accepts with groups=1 and zero padding -- kernel sizes 1..32 (square or not), strides 1..16, dilations
+1..32, pads 0..64 per side, 'valid' and 'same' -- runs: the geometries of the slim / darknet layers on their own kernels as
+before, every other one on the general-geometry kernel (y355_conv2d_geom_bf16 / y355_conv_geom_i8_raw / y355_conv_op_create_*_geom),
+with the same routes and the same exactness.  Grouped convolution, the other padding modes and geometry past those limits raise
+NotImplementedError.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import prep
+from .. import _ffi, prep
+
+GEOM_LIMITS = {"kernel_size": 32, "stride": 16, "dilation": 32, "padding": 64}
+
+
+def conv_geometry(conv):
+    """The y355_conv_geom of an nn.Conv2d: int or pair kernel_size / stride / dilation, int or pair padding, 'valid' and
+    'same' (torch's split: the odd pixel of dilation * (kernel - 1) goes bottom / right).  NotImplementedError for what the
+    kernels do not run: groups != 1, padding_mode != 'zeros', values past GEOM_LIMITS."""
+    if conv.groups != 1:
+        raise NotImplementedError("yolo355 conv: groups=%d; grouped / depthwise convolution is not supported (groups must be 1)"
+                                  % conv.groups)
+    if conv.padding_mode != "zeros":
+        raise NotImplementedError("yolo355 conv: padding_mode=%r; only zero padding ('zeros') is supported" % conv.padding_mode)
+    (kh, kw), (sh, sw), (dh, dw) = conv.kernel_size, conv.stride, conv.dilation
+    if conv.padding == "valid":
+        pads = (0, 0, 0, 0)
+    elif conv.padding == "same":
+        th, tw = dh * (kh - 1), dw * (kw - 1)
+        pads = (th // 2, th - th // 2, tw // 2, tw - tw // 2)
+    else:
+        ph, pw = conv.padding
+        pads = (ph, ph, pw, pw)
+    for name, vals in (("kernel_size", (kh, kw)), ("stride", (sh, sw)), ("dilation", (dh, dw)), ("padding", pads)):
+        lo = 0 if name == "padding" else 1
+        if any(v < lo or v > GEOM_LIMITS[name] for v in vals):
+            raise NotImplementedError("yolo355 conv: %s %s is outside the supported %d..%d" % (name, vals, lo, GEOM_LIMITS[name]))
+    return _ffi.ConvGeom(kh, kw, sh, sw, dh, dw, *pads)
+
+
+def _runs_bf16_kernels(conv):
+    """the geometries y355_conv2d_bf16 / y355_conv_op_create_bf16 run: 1x1 or 3x3 with padding k/2, stride 1 (or 2 for 3x3)"""
+    k = conv.kernel_size[0]
+    return (conv.kernel_size[1] == k and k in (1, 3) and conv.padding == (k // 2, k // 2) and conv.dilation == (1, 1)
+            and conv.stride[0] == conv.stride[1] and (conv.stride[0] == 1 or (conv.stride[0] == 2 and k == 3)))
+
+
+def _runs_i8_kernels(conv):
+    """the geometry of y355_conv3x3_i8_raw / y355_conv_op_create_i8: 3x3 / stride 1 / pad 1 (the slim-YOLOv2 layers)"""
+    return conv.kernel_size == (3, 3) and conv.stride == (1, 1) and conv.padding == (1, 1) and conv.dilation == (1, 1)
 
 
 def _versions(convs):
@@ -41,8 +86,6 @@ def _cached_op(owner, key, convs, build):
 
 def _int8_operands(module, x):
     conv = module.convs[0]
-    if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1):
-        raise NotImplementedError("yolo355 fused conv: only 3x3 / stride 1 / pad 1 (the slim-YOLOv2 layers)")
     try:
         q_in, sa_in = prep.as_dyadic_int8(x)
         q_w, e_w = prep.as_dyadic_int8(conv.weight)
@@ -64,20 +107,22 @@ class _FusedBase(nn.Module):
     leaky = True
 
     def forward(self, x):
-        from ..engine import ConvOp, conv3x3_i8_raw
+        from ..engine import ConvOp, conv3x3_i8_raw, conv_geom_i8_raw
+        conv = self.convs[0]
+        g = conv_geometry(conv)                           # raises for what no kernel runs
+        if _runs_i8_kernels(conv):
+            g, key = None, ("i8", x.device.index)
+        else:
+            key = ("i8", x.device.index, g.astuple())
         if x.is_cuda:
-            conv = self.convs[0]
-            if conv.kernel_size != (3, 3) or conv.stride != (1, 1) or conv.padding != (1, 1) or conv.dilation != (1, 1):
-                raise NotImplementedError("yolo355 fused conv: only 3x3 / stride 1 / pad 1 (the slim-YOLOv2 layers)")
-
             def build():
                 try:
                     q_w, e_w = prep.as_dyadic_int8(conv.weight)
                     q_b, e_b = prep.as_dyadic_int8(conv.bias) if conv.bias is not None else (np.zeros(conv.out_channels, np.int32), 0)
                 except ValueError:
                     return _NoOp()                        # weights that are not dyadic: always the bf16 route
-                return ConvOp.int8(q_w, q_b, e_w, e_b, leaky=self.leaky, relu=not self.leaky, device=x.device)
-            op = _cached_op(self, ("i8", x.device.index), self.convs, build)
+                return ConvOp.int8(q_w, q_b, e_w, e_b, leaky=self.leaky, relu=not self.leaky, device=x.device, geom=g)
+            op = _cached_op(self, key, self.convs, build)
             y = op.forward_i8(x) if not isinstance(op, _NoOp) else None
             return y if y is not None else _conv_bn_act_forward(self.convs, x)
         ops = _int8_operands(self, x)
@@ -85,8 +130,11 @@ class _FusedBase(nn.Module):
             # the reference's module takes any fp32 tensor (utils/modules.py:28-29, :39-40): same layer on the bf16 MFMA
             return _conv_bn_act_forward(self.convs, x)
         q_in, sa_in, q_w, e_w, q_b, e_b = ops
-        t, frac = conv3x3_i8_raw(q_in, q_w, q_b, sa_in, e_w, e_b, leaky=self.leaky, relu=not self.leaky,
-                                 device_id=x.device.index if x.is_cuda and x.device.index is not None else 0)
+        dev = x.device.index if x.is_cuda and x.device.index is not None else 0
+        if g is None:
+            t, frac = conv3x3_i8_raw(q_in, q_w, q_b, sa_in, e_w, e_b, leaky=self.leaky, relu=not self.leaky, device_id=dev)
+        else:
+            t, frac = conv_geom_i8_raw(q_in, q_w, q_b, sa_in, e_w, e_b, g, leaky=self.leaky, relu=not self.leaky, device_id=dev)
         y = torch.from_numpy(t.astype(np.float32) * np.float32(2.0 ** (-frac)))
         return y.to(x.device)
 
@@ -108,13 +156,13 @@ def folded_f32(convs):
 
 
 def _conv_bn_act_forward(convs, x, residual=None):
-    """Eval-mode forward of nn.Sequential(conv, [BatchNorm2d], [LeakyReLU | ReLU]) through y355_conv2d_bf16."""
-    from ..engine import conv2d_bf16
+    """Eval-mode forward of nn.Sequential(conv, [BatchNorm2d], [LeakyReLU | ReLU]) through y355_conv2d_bf16 (the geometries
+    it runs) or y355_conv2d_geom_bf16 (every other one conv_geometry accepts)."""
+    from ..engine import conv2d_bf16, conv2d_geom_bf16
     conv = convs[0]
-    k = conv.kernel_size[0]
-    if conv.kernel_size[0] != conv.kernel_size[1] or k not in (1, 3) or conv.padding != (k // 2, k // 2) \
-            or conv.dilation != (1, 1) or conv.groups != 1 or conv.stride[0] != conv.stride[1]:
-        raise NotImplementedError("yolo355 conv: 1x1, or 3x3 with padding 1; stride 1 (or 2 for 3x3); no dilation / groups")
+    g = conv_geometry(conv)                               # raises for what no kernel runs
+    if _runs_bf16_kernels(conv):
+        g = None
     if any(isinstance(m, nn.BatchNorm2d) and m.training for m in convs):
         raise NotImplementedError("yolo355 is an inference engine: call .eval() first (BatchNorm uses running statistics)")
     slope = 1.0
@@ -125,11 +173,17 @@ def _conv_bn_act_forward(convs, x, residual=None):
             slope = 0.0
     if x.is_cuda:                                         # device-resident: weights packed once, the tensor never leaves the GPU
         from ..engine import ConvOp
-        op = _cached_op(convs, ("bf16", x.device.index), convs,
-                        lambda: ConvOp.bf16(*folded_f32(convs), stride=conv.stride[0], neg_slope=slope, device=x.device))
+        key = ("bf16", x.device.index) if g is None else ("bf16", x.device.index, g.astuple())
+        op = _cached_op(convs, key, convs,
+                        lambda: ConvOp.bf16(*folded_f32(convs), stride=conv.stride[0], neg_slope=slope, device=x.device, geom=g))
         return op.forward(x, residual)
     w, b = folded_f32(convs)
     dev = x.device
+    if g is not None:
+        y = conv2d_geom_bf16(x.detach().float().cpu().numpy(), w, g, b,
+                             None if residual is None else residual.detach().float().cpu().numpy(), neg_slope=slope,
+                             device_id=dev.index if x.is_cuda and dev.index is not None else 0)
+        return torch.from_numpy(y).to(dev)
     y = conv2d_bf16(x.detach().float().cpu().numpy(), w, b,
                     None if residual is None else residual.detach().float().cpu().numpy(),
                     stride=conv.stride[0], neg_slope=slope, device_id=dev.index if x.is_cuda and dev.index is not None else 0)

@@ -36,7 +36,7 @@ extern "C" {
 #define Y355_EINVAL (-1)         /* bad argument */
 #define Y355_EHIP (-2)           /* HIP runtime error */
 #define Y355_ENOTREADY (-3)      /* weights / activation exponents missing */
-#define Y355_ERANGE (-4)         /* exponent gap does not fit the int32 epilogue */
+#define Y355_ERANGE (-4)         /* exponent gap does not fit the int32 epilogue (y355_net: the 64-bit one) */
 #define Y355_EGUARD (-5)         /* 2^15 head-room guard tripped (find=True semantics) */
 
 typedef struct y355_engine y355_engine;
@@ -437,9 +437,9 @@ int y355_debug_nms_stamps(unsigned long long *out_host);
  * fp32; prediction maps stay fp32.  Same handle rules as y355_engine. */
 #define Y355_ARCH_SLIM_V2 0
 #define Y355_ARCH_TINY_V3 1
-#define Y355_ARCH_YOLO_V2 2   /* myYOLOv2 (models/yolo_v2.py:9-232) on DarkNet-19 (backbone/darknet.py:40-110); bf16 only */
-#define Y355_ARCH_YOLO_V3 3   /* myYOLOv3 (models/yolo_v3.py:9-304) on DarkNet-53 (backbone/darknet.py:112-161); bf16 only */
-#define Y355_ARCH_YOLO_V3_SPP 4   /* myYOLOv3Spp (models/yolo_v3_spp.py): SPP in front of the stride-32 branch; bf16 only */
+#define Y355_ARCH_YOLO_V2 2   /* myYOLOv2 (models/yolo_v2.py:9-232) on DarkNet-19 (backbone/darknet.py:40-110) */
+#define Y355_ARCH_YOLO_V3 3   /* myYOLOv3 (models/yolo_v3.py:9-304) on DarkNet-53 (backbone/darknet.py:112-161) */
+#define Y355_ARCH_YOLO_V3_SPP 4   /* myYOLOv3Spp (models/yolo_v3_spp.py): SPP in front of the stride-32 branch */
 #define Y355_DT_INT8 0
 #define Y355_DT_BF16 1
 typedef struct y355_net y355_net;
@@ -479,12 +479,22 @@ int y355_net_load_layer_f32(y355_net *h, int idx, const float *w, const float *b
 /* dtype Y355_DT_INT8: the power-of-two int8 recipe of the q_bf path (retune_bias_quantize.py:73-119,
  * models/slim_yolo_v2.py:16-38) applied to these graphs -- the reference itself has no int8 form of
  * them.  q_w int8 [cout][cin][k][k] (value q_w / 2^e_w), q_b int32 [cout] (value q_b / 2^e_b).
- * LeakyReLU(0.1) runs as the fixed-point slope 205/2048; DESIGN.md lists the integer semantics. */
+ * LeakyReLU(0.1) runs as the fixed-point slope 205/2048; DESIGN.md lists the integer semantics.
+ * Every arch takes both dtypes.  The ops of the DarkNet graphs (Y355_ARCH_YOLO_V2 / _V3 / _V3_SPP) in int8:
+ *   network input  q = clamp(RNE(x * 2^sa_in), +-127), NHWC with 32 bytes per pixel; tensor 0's exponent is sa_in
+ *   residual       (x + block(x)) one rounding after the add: E = F + lk is the exponent of t', s_r the residual's,
+ *                  G = max(E, s_r), u = t' * 2^(G-E) + q_r * 2^(G-s_r) exactly in int64, q = clamp(RNE(u * 2^(s_out-G)))
+ *   reorg          byte permutation into the concat buffer, then q = clamp(RNE(q_in * 2^(s_out - s_in)))
+ *   SPP            max-pools 5 / 9 / 13 (stride 1, windows clipped to the map) on the int8 values, in place, no rescale
+ * Their clamps count in y355_net_counters. */
 int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin,
                            int ksize, int e_w, int e_b);
 /* activation exponents (value = q / 2^sa): sa_in for the network input, sa[t] per activation tensor in
- * graph order; a max-pool output takes its input's exponent (its entry is overridden), a concat
- * buffer has one exponent.  get returns the effective values. */
+ * graph order; a max-pool output takes its input's exponent and the DarkNet graphs' input tensor sa_in
+ * (their entries are overridden), a concat buffer (and the in-place SPP buffer) has one exponent.  get
+ * returns the effective values.  Y355_ERANGE, with the previous exponents kept, when for a residual
+ * layer whose weights are loaded no bound proves the 64-bit sum u of the residual rule (and its rounding)
+ * below 2^62; layers loaded later are checked at the forward, which then returns Y355_ERANGE. */
 int y355_net_set_act_exponents(y355_net *h, int sa_in, const int32_t *sa, int n);
 int y355_net_get_act_exponents(y355_net *h, int32_t *sa_in, int32_t *sa, int n);
 /* outputs clamped to +-127 by the last forward of an int8 net; synchronous */

@@ -28,6 +28,37 @@ __device__ __forceinline__ long long requant_g(int acc, long long bias, const Re
     return y355_rne_shift<long long>(t, rq.sh);
 }
 
+// the same with the int8 residual added before the one rounding (ResQ, y355_common.h)
+__device__ __forceinline__ long long requant_g_res(int acc, long long bias, const RequantG &rq, int qr, const ResQ &rr) {
+    long long t = (long long)acc * (1ll << rq.shl) + bias;
+    t = t >= 0 ? t * (1ll << rq.lk) : t * (long long)rq.neg_mul;
+    const long long u = t * (1ll << rr.t_sh) + (long long)qr * (1ll << rr.r_sh);
+    return y355_rne_shift<long long>(u, rr.sh);
+}
+__device__ __forceinline__ int requant_gen32_res(int acc, int bias, const Requant &rq, int qr, const ResQ &rr) {
+    const int t = (acc << rq.shl) + bias;
+    if (t >= 0) return y355_rne_shift32(t * (1 << rr.p_t) + qr * (1 << rr.p_r), rr.p_d);
+    return y355_rne_shift32(t * rq.neg_mul * (1 << rr.n_t) + qr * (1 << rr.n_r), rr.n_d);
+}
+
+// NT residual bytes of one pixel (int8, halo layout of the residual tensor), sign-extended; one vector load
+template <int NT>
+__device__ __forceinline__ void load_res_i8(const char *src, int (&r)[NT]) {
+    static_assert(NT == 2 || NT == 4 || NT == 8, "NT");
+    if constexpr (NT == 2) {
+        const unsigned int v = *(const unsigned short *)src;
+        r[0] = (int)(signed char)(v & 0xffu);
+        r[1] = (int)(signed char)(v >> 8);
+    } else {
+#pragma unroll
+        for (int t0 = 0; t0 < NT; t0 += 4) {
+            const unsigned int v = *(const unsigned int *)(src + t0);
+#pragma unroll
+            for (int k = 0; k < 4; ++k) r[t0 + k] = (int)(signed char)((v >> (8 * k)) & 0xffu);
+        }
+    }
+}
+
 // ---- four waves per workgroup (round 1): one tile per workgroup, stage -> barrier -> k-steps -> barrier per chunk.  Kept for
 // the thin layers and the small / stride-2 tiles, where its 2-3 workgroups per CU overlap each other's phases.
 template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false>
@@ -221,16 +252,35 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
             }
         } else {
             int q[NT];
+            if (resb) {                                 // residual: added before the one rounding (ResQ)
+                int qr[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                if constexpr (NARROW) {
-                    const int qq = y355_requant_gen32(vi[t], biasn[t], rqn);
-                    q[t] = y355_clamp8<int>(qq);
-                    nsat += (valid && q[t] != qq) ? 1u : 0u;
-                } else {
-                    const long long qq = requant_g(vi[t], biasw[t], rq);
-                    q[t] = y355_clamp8<long long>(qq);
-                    nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
+                for (int t = 0; t < NT; ++t) qr[t] = 0;
+                if (valid) load_res_i8<NT>(resb + ((size_t)(oy + 1) * (Wo + 2) + ox + 1) * p.res_pb + nlane, qr);
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if constexpr (NARROW) {
+                        const int qq = requant_gen32_res(vi[t], biasn[t], rqn, qr[t], p.rr);
+                        q[t] = y355_clamp8<int>(qq);
+                        nsat += (valid && q[t] != qq) ? 1u : 0u;
+                    } else {
+                        const long long qq = requant_g_res(vi[t], biasw[t], rq, qr[t], p.rr);
+                        q[t] = y355_clamp8<long long>(qq);
+                        nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
+                    }
+                }
+            } else {
+#pragma unroll
+                for (int t = 0; t < NT; ++t) {
+                    if constexpr (NARROW) {
+                        const int qq = y355_requant_gen32(vi[t], biasn[t], rqn);
+                        q[t] = y355_clamp8<int>(qq);
+                        nsat += (valid && q[t] != qq) ? 1u : 0u;
+                    } else {
+                        const long long qq = requant_g(vi[t], biasw[t], rq);
+                        q[t] = y355_clamp8<long long>(qq);
+                        nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
+                    }
                 }
             }
             if (valid) store_i8<NT>(dst + nlane, q);
@@ -509,16 +559,35 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
                 }
             } else {
                 int q[NT];
+                if (resb) {                                 // residual: added before the one rounding (ResQ)
+                    int qr[NT];
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    if constexpr (NARROW) {
-                        const int qq = y355_requant_gen32(vi[t], biasn[t], rqn);
-                        q[t] = y355_clamp8<int>(qq);
-                        nsat += (valid && q[t] != qq) ? 1u : 0u;
-                    } else {
-                        const long long qq = requant_g(vi[t], biasw[t], rq);
-                        q[t] = y355_clamp8<long long>(qq);
-                        nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
+                    for (int t = 0; t < NT; ++t) qr[t] = 0;
+                    if (valid) load_res_i8<NT>(resb + ((size_t)(oy + 1) * (Wo + 2) + ox + 1) * p.res_pb + nlane, qr);
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        if constexpr (NARROW) {
+                            const int qq = requant_gen32_res(vi[t], biasn[t], rqn, qr[t], p.rr);
+                            q[t] = y355_clamp8<int>(qq);
+                            nsat += (valid && q[t] != qq) ? 1u : 0u;
+                        } else {
+                            const long long qq = requant_g_res(vi[t], biasw[t], rq, qr[t], p.rr);
+                            q[t] = y355_clamp8<long long>(qq);
+                            nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
+                        }
+                    }
+                } else {
+#pragma unroll
+                    for (int t = 0; t < NT; ++t) {
+                        if constexpr (NARROW) {
+                            const int qq = y355_requant_gen32(vi[t], biasn[t], rqn);
+                            q[t] = y355_clamp8<int>(qq);
+                            nsat += (valid && q[t] != qq) ? 1u : 0u;
+                        } else {
+                            const long long qq = requant_g(vi[t], biasw[t], rq);
+                            q[t] = y355_clamp8<long long>(qq);
+                            nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
+                        }
                     }
                 }
                 if (valid) store_i8<NT>(dst + nlane, q);

@@ -1,6 +1,7 @@
 // yolo355 -- table-driven network executor behind the y355_net_* C ABI (include/yolo355.h):
 //   Y355_ARCH_SLIM_V2  models/slim_yolo_v2.py:386-422, forward :549-622  (SlimYOLOv2, the fp32 model)
 //   Y355_ARCH_TINY_V3  models/tiny_yolo_v3.py:9-273 + backbone/darknet.py:211-255 (YOLOv3tiny)
+//   Y355_ARCH_YOLO_V2, _YOLO_V3, _YOLO_V3_SPP  models/yolo_v2.py, yolo_v3.py, yolo_v3_spp.py (DarkNet-19 / DarkNet-53)
 // in two arithmetic types: bf16 (BN-folded fp32 weights, bf16 MFMA, fp32 accumulate) and int8
 // (per-tensor power-of-two quantisation, the recipe of retune_bias_quantize.py:73-119 applied
 // to these graphs).  Every conv is convg.hip; the ops between the convs are the small kernels
@@ -78,9 +79,9 @@ const OpDef kTinyOps[] = {
     {OP_CONV, 12, 14, 0, 11, 512, 0, 1, 0, ACT_NONE},      // pred_2 (stride 32)
     {OP_CONV, 11, 13, 0, 12, 256, 0, 1, 0, ACT_NONE},      // pred_1 (stride 16)
 };
-// ---- myYOLOv2 (models/yolo_v2.py:26-39, 165-179) on DarkNet-19 (backbone/darknet.py:40-110); bf16 only
+// ---- myYOLOv2 (models/yolo_v2.py:26-39, 165-179) on DarkNet-19 (backbone/darknet.py:40-110)
 const TensorDef kV2T[] = {
-    {3, 1, 0},                                                   //  0 input as bf16 NHWC16
+    {3, 1, 0},                                                   //  0 input: bf16 NHWC16 / int8 NHWC32
     {32, 2, 0}, {64, 4, 0},                                      //  1 conv_1+pool, 2 conv_2+pool
     {128, 4, 0}, {64, 4, 0}, {128, 8, 0},                        //  3..5 conv_3 (last pooled)
     {256, 8, 0}, {128, 8, 0}, {256, 8, 0}, {256, 16, 0},         //  6..8 conv_4 (8 = C_4), 9 maxpool_4
@@ -123,7 +124,7 @@ const OpDef kV2Ops[] = {
     {OP_CONV, 24, 25, 0, 22, 1024, 0, 1, 0, ACT_NONE},           // pred (1x1)
 };
 // ---- myYOLOv3 / myYOLOv3Spp (models/yolo_v3.py:26-61, 203-231; models/yolo_v3_spp.py:31-36) on DarkNet-53
-// (backbone/darknet.py:112-161): built programmatically, weight slots in forward order (bf16 only)
+// (backbone/darknet.py:112-161): built programmatically, weight slots in forward order
 struct V3Graph {
     std::vector<TensorDef> t;
     std::vector<OpDef> ops;
@@ -229,6 +230,7 @@ struct NLayer {
     int e_w = 0, e_b = 0;
     long long *bias_w_dev = nullptr;
     RequantG rq{};
+    ResQ rr{};                // residual layers (OpDef::res1)
     Requant rq1{};            // first layer (conv1.hip epilogue)
     bool dirty = true;
     // 3x3 layers that have a ring instantiation (convr.hip): its id and the weights in its fragment order
@@ -415,6 +417,117 @@ __global__ void absmax_bf16_kernel(const char *t, size_t n_elems, unsigned int *
     const unsigned int u = y355_wave_max_u32(__float_as_uint(m));
     if ((threadIdx.x & 63) == 0) atomicMax(out, u);
 }
+
+// ---- int8 ops of the DarkNet graphs (DESIGN.md "int8 DarkNet"); clamps count into the op's counter
+__device__ __forceinline__ void count_sat(Counters *ctr, unsigned int n) {
+    if (n && ctr) atomicAdd(&ctr->sat, (unsigned long long)n);
+}
+
+// q_in * 2^d, rounded half-to-even (d < 0), clamped to +-127: the rescale between two tensors' exponents
+__device__ __forceinline__ int rescale_i8(int q, int d, unsigned int &nsat) {
+    const int r = d >= 0 ? q * (1 << min(d, 24)) : y355_rne_shift32(q, -d);
+    const int c = y355_clamp8<int>(r);
+    nsat += c != r ? 1u : 0u;
+    return c;
+}
+
+// fp32 NCHW [B][3][H][W] -> int8 NHWC32 with halo: q = clamp(RNE(x * 2^sa_in)) (the slim front end's input rule); one pixel
+// per thread, one 16-byte store (channels 3..15 zero; 16..31 keep the allocation's zeros)
+__global__ void input_i8_kernel(const float *x, char *out, int B, int H, int W, int out_pb, float in_scale, Counters *ctr) {
+    const size_t total = (size_t)B * H * W;
+    const size_t plane = (size_t)H * W;
+    unsigned int nsat = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int xx = (int)(i % W), y = (int)((i / W) % H);
+        const size_t b = i / plane;
+        const float *src = x + b * 3 * plane + (size_t)y * W + xx;
+        unsigned int w = 0;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float r = rintf(src[c * plane] * in_scale);
+            const float q = fminf(fmaxf(r, -127.f), 127.f);
+            nsat += q != r ? 1u : 0u;
+            w |= ((unsigned int)(int)q & 0xffu) << (8 * c);
+        }
+        *(uint4 *)(out + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + xx + 1) * out_pb) = make_uint4(w, 0u, 0u, 0u);
+    }
+    count_sat(ctr, nsat);
+}
+
+// reorg (utils/modules.py:48-57) of int8 NHWC into a concat buffer with the rescale 2^(s_out - s_in):
+// out[.., (sy*s+sx)*C + c] = rescale(in[s*y+sy][s*x+sx][c]); 16 bytes (16 channels) per thread
+__global__ void reorg_i8_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int C, int out_pb, int out_off, int s,
+                                int d, Counters *ctr) {
+    const int Ho = Hin / s, Wo = Win / s, cg = C / 16;
+    const size_t total = (size_t)B * Ho * Wo * s * s * cg;
+    unsigned int nsat = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int g = (int)(i % cg);
+        const int k = (int)((i / cg) % (s * s));
+        const int x = (int)((i / ((size_t)cg * s * s)) % Wo), y = (int)((i / ((size_t)cg * s * s * Wo)) % Ho);
+        const size_t b = i / ((size_t)cg * s * s * Wo * Ho);
+        const int sy = k / s, sx = k % s;
+        const uint4 v = *(const uint4 *)(in + ((b * (Hin + 2) + (size_t)s * y + sy + 1) * (Win + 2) + (size_t)s * x + sx + 1) * in_pb + g * 16);
+        unsigned int u[4] = {v.x, v.y, v.z, v.w};
+        if (d != 0) {
+#pragma unroll
+            for (int w = 0; w < 4; ++w) {
+                unsigned int o = 0;
+#pragma unroll
+                for (int j = 0; j < 4; ++j)
+                    o |= ((unsigned int)rescale_i8((int)(signed char)((u[w] >> (8 * j)) & 0xffu), d, nsat) & 0xffu) << (8 * j);
+                u[w] = o;
+            }
+        }
+        *(uint4 *)(out + ((b * (Ho + 2) + y + 1) * (size_t)(Wo + 2) + x + 1) * out_pb + out_off + (size_t)k * C + g * 16) =
+            make_uint4(u[0], u[1], u[2], u[3]);
+    }
+    count_sat(ctr, nsat);
+}
+
+// SPP (utils/modules.py:66-72) on int8 NHWC, in place in a 4C-channel buffer as spp_bf16_kernel: max-pools 5 / 9 / 13, stride 1,
+// windows clipped to the map (the padding takes part in no max); exact on the int8 values, no requantisation.  16 channels
+// (16 bytes) per thread.
+__global__ void spp_i8_kernel(char *buf, int B, int H, int W, int pb, int C) {
+    const int cg = C / 16;
+    const size_t total = (size_t)B * H * W * cg;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int g = (int)(i % cg);
+        const int x = (int)((i / cg) % W), y = (int)((i / ((size_t)cg * W)) % H);
+        const size_t b = i / ((size_t)cg * W * H);
+        int m5[16], m9[16], m13[16];
+#pragma unroll
+        for (int k = 0; k < 16; ++k) m5[k] = m9[k] = m13[k] = -128;
+        for (int dy = -6; dy <= 6; ++dy) {
+            const int yy = y + dy;
+            if (yy < 0 || yy >= H) continue;
+            for (int dx = -6; dx <= 6; ++dx) {
+                const int xx = x + dx;
+                if (xx < 0 || xx >= W) continue;
+                const uint4 v = *(const uint4 *)(buf + ((b * (H + 2) + yy + 1) * (size_t)(W + 2) + xx + 1) * pb + g * 16);
+                const unsigned int u[4] = {v.x, v.y, v.z, v.w};
+                const int r = max(abs(dy), abs(dx));
+#pragma unroll
+                for (int k = 0; k < 16; ++k) {
+                    const int f = (int)(signed char)((u[k >> 2] >> (8 * (k & 3))) & 0xffu);
+                    m13[k] = max(m13[k], f);
+                    if (r <= 4) m9[k] = max(m9[k], f);
+                    if (r <= 2) m5[k] = max(m5[k], f);
+                }
+            }
+        }
+        char *o = buf + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * pb + g * 16;
+        auto pack = [](const int (&m)[16]) {
+            unsigned int w[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+            for (int k = 0; k < 16; ++k) w[k >> 2] |= ((unsigned int)m[k] & 0xffu) << (8 * (k & 3));
+            return make_uint4(w[0], w[1], w[2], w[3]);
+        };
+        *(uint4 *)(o + (size_t)C) = pack(m5);
+        *(uint4 *)(o + (size_t)C * 2) = pack(m9);
+        *(uint4 *)(o + (size_t)C * 3) = pack(m13);
+    }
+}
 }  // namespace
 
 #ifndef Y355_USE_CONVPXB
@@ -481,8 +594,6 @@ extern "C" void y355_net_destroy(y355_net *h) {
 extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     if (!cfg || !out) return y355_fail(Y355_EINVAL, "null argument");
     if (cfg->arch < 0 || cfg->arch > Y355_ARCH_YOLO_V3_SPP) return y355_fail(Y355_EINVAL, "unknown arch");
-    if (cfg->arch >= Y355_ARCH_YOLO_V2 && cfg->dtype != Y355_DT_BF16)
-        return y355_fail(Y355_EINVAL, "yolo_v2 / yolo_v3 / yolo_v3_spp are built in bf16 only (the reference has no quantized form of them)");
     if (cfg->dtype != Y355_DT_BF16 && cfg->dtype != Y355_DT_INT8) return y355_fail(Y355_EINVAL, "unknown dtype");
     // SlimYOLOv2 has four 2x2 pools (stride 16: models/slim_yolo_v2.py:52); the other graphs reach stride 32
     const int mult = cfg->arch == Y355_ARCH_SLIM_V2 ? 16 : 32;
@@ -808,9 +919,48 @@ extern "C" int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, c
     return 0;
 }
 
+static void act_fixed(int act, int *lk, int *neg_mul);
+
+// exponents of a residual layer's epilogue (ResQ, y355_common.h) and whether its 32-bit form holds for these weights.
+// Nonzero when no bound proves the 64-bit sum u = t' 2^(G-E) + q_r 2^(G-s_r) (and its rounding) below 2^62.
+static int res_params(const y355_net *h, const OpDef &o, const NLayer &L, ResQ *rr, int *narrow) {
+    const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in], sa_o = h->sa[o.out], s_r = h->sa[o.res1 - 1];
+    const int F = std::max(sa_i + L.e_w, L.e_b);
+    const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;
+    int lk, nm;
+    act_fixed(o.act, &lk, &nm);
+    const int E = F + lk, G = std::max(E, s_r);
+    *rr = ResQ{};
+    rr->t_sh = G - E;
+    rr->r_sh = G - s_r;
+    rr->sh = G - sa_o;
+    *narrow = 0;
+    if (shl > 24 || bshl > 40 || rr->t_sh > 62 || rr->r_sh > 62 || rr->sh > 62 || rr->sh < -62) return 1;
+    long double bmax = 0;
+    for (int c = 0; c < L.cout; ++c) bmax = std::max(bmax, std::fabs((long double)L.q_b[c]) * std::ldexp(1.0L, bshl));
+    // worst-case |t'|, as refresh_i8 bounds the plain epilogue
+    const long double tw = ((long double)127 * 127 * o.ksize * o.ksize * o.cin) * std::ldexp(1.0L, shl) + bmax;
+    long double u = tw * std::max(std::ldexp(1.0L, lk), (long double)nm) * std::ldexp(1.0L, rr->t_sh) + 127.0L * std::ldexp(1.0L, rr->r_sh);
+    u = rr->sh < 0 ? u * std::ldexp(1.0L, -rr->sh) : u + std::ldexp(1.0L, rr->sh);
+    if (u >= std::ldexp(1.0L, 62)) return 1;
+    // 32-bit form: both branches over their common power of two, on the layer's own weights (|acc| <= 127 sum |q_w|)
+    const int shp = E - sa_o;
+    const int dp = std::max({shp - lk, s_r - sa_o, 0}), dn = std::max({shp, s_r - sa_o, 0});
+    rr->p_t = lk - shp + dp; rr->p_r = sa_o - s_r + dp; rr->p_d = dp;
+    rr->n_t = dn - shp; rr->n_r = sa_o - s_r + dn; rr->n_d = dn;
+    const long double accmax = L.wabs > 0 ? (long double)127 * L.wabs : (long double)127 * 127 * o.ksize * o.ksize * o.cin;
+    const long double tb = accmax * std::ldexp(1.0L, shl) + bmax, lim = std::ldexp(1.0L, 31);
+    if (dp <= 30 && dn <= 30 && rr->p_t <= 30 && rr->p_r <= 30 && rr->n_t <= 30 && rr->n_r <= 30 && tb < lim && bmax < lim &&
+        tb * std::ldexp(1.0L, rr->p_t) + 127.0L * std::ldexp(1.0L, rr->p_r) + std::ldexp(1.0L, dp) < lim &&
+        tb * nm * std::ldexp(1.0L, rr->n_t) + 127.0L * std::ldexp(1.0L, rr->n_r) + std::ldexp(1.0L, dn) < lim)
+        *narrow = 1;
+    return 0;
+}
+
 // activation exponents of an int8 net: sa_in for the fp32 network input, sa[t] for tensor t (graph
-// order of csrc/net.hip).  A max-pool output takes its input's exponent (the entry given for it is
-// overridden); a concat buffer has ONE exponent that both producers requantise to.
+// order of csrc/net.hip).  A max-pool output takes its input's exponent and the network-input tensor sa_in (the entries
+// given for them are overridden); a concat buffer (and the in-place SPP buffer) has ONE exponent that every producer
+// requantises to.  Y355_ERANGE (nothing changed) when a loaded residual layer's epilogue is not provably in range.
 extern "C" int y355_net_set_act_exponents(y355_net *h, int sa_in, const int32_t *sa, int n) {
     if (!h || !sa) return y355_fail(Y355_EINVAL, "null argument");
     if (h->bf) return y355_fail(Y355_EINVAL, "bf16 nets have no activation exponents");
@@ -818,11 +968,27 @@ extern "C" int y355_net_set_act_exponents(y355_net *h, int sa_in, const int32_t 
     for (int i = 0; i < n; ++i)
         if (sa[i] < -64 || sa[i] > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
     if (sa_in < -64 || sa_in > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
+    const int keep_in = h->sa_in;
+    const std::vector<int> keep = h->sa;
     h->sa_in = sa_in;
     h->sa.assign(sa, sa + n);
     for (int i = 0; i < h->arch->nops; ++i) {
         const OpDef &o = h->arch->ops[i];
         if (o.type == OP_POOL) h->sa[o.out] = h->sa[o.in];      // max-pool does not requantise
+        if (o.type == OP_INPUT) h->sa[o.out] = sa_in;            // the quantised network input
+    }
+    // residual layers whose weights are loaded: the 64-bit sum u must provably fit (checked again at the forward for the others)
+    for (int i = 0; i < h->arch->nops; ++i) {
+        const OpDef &o = h->arch->ops[i];
+        if (o.type != OP_CONV || !o.res1 || !h->L[o.layer].loaded) continue;
+        ResQ rr{};
+        int narrow = 0;
+        if (res_params(h, o, h->L[o.layer], &rr, &narrow)) {
+            h->sa_in = keep_in;
+            h->sa = keep;
+            return y355_fail(Y355_ERANGE, "residual layer: the 64-bit sum of the residual epilogue is not provably in range "
+                                          "for these exponents");
+        }
     }
     h->sa_ok = true;
     for (auto &L : h->L) L.dirty = true;
@@ -890,6 +1056,12 @@ static int refresh_i8(y355_net *h) {
                 if (tb < std::ldexp(1.0L, 30) && pos < std::ldexp(1.0L, 31) && neg < std::ldexp(1.0L, 31) && bmax < std::ldexp(1.0L, 31))
                     L.rq.narrow = L.rq.split = 1;
             }
+        }
+        if (o.res1) {                  // residual: its own 64-bit bound, and its own 32-bit form (no split)
+            int narrow = 0;
+            if (res_params(h, o, L, &L.rr, &narrow)) return y355_fail(Y355_ERANGE, "residual epilogue exceeds 62 bits");
+            L.rq.narrow = narrow;
+            L.rq.split = 0;
         }
         L.rq1 = Requant{};
         L.rq1.shl = shl;
@@ -1026,6 +1198,9 @@ static int in_kbytes(const y355_net *h, const OpDef &o) {
     const int cq = h->bf ? 16 : 32;
     int c = (o.cin + cq - 1) / cq * cq;
     if (h->bf && c > 16) c = (c + 31) / 32 * 32;          // 64-byte k-steps beyond the thin (16-channel) path
+    // int8 stride 2 has no thin form: 64-byte chunks (DarkNet-53's first down-sampling reads 32 real channels of a 64-channel
+    // map, whose upper half its producer wrote as zeros)
+    if (!h->bf && o.stride2) c = (c + 63) / 64 * 64;
     return c * h->es;
 }
 
@@ -1098,6 +1273,7 @@ static int run_op(y355_net *h, int i, int B, const float *x_dev) {
             p.res = tr.dev;
             p.res_pb = (int)tr.pb;
             p.res_off = 0;
+            p.rr = L.rr;
         }
         p.nblk = L.cout_pad / ki.bn;
         p.taps = o.ksize * o.ksize;
@@ -1145,18 +1321,32 @@ static int run_op(y355_net *h, int i, int B, const float *x_dev) {
     } else if (o.type == OP_INPUT) {
         const Tensor &to = h->T[o.out];
         const size_t total = (size_t)B * to.H * to.W;
-        hipLaunchKernelGGL(input_bf16_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, x_dev, to.dev, B,
-                           to.H, to.W, (int)to.pb);
+        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+        if (h->bf)
+            hipLaunchKernelGGL(input_bf16_kernel, dim3(blocks), dim3(256), 0, s, x_dev, to.dev, B, to.H, to.W, (int)to.pb);
+        else
+            hipLaunchKernelGGL(input_i8_kernel, dim3(blocks), dim3(256), 0, s, x_dev, to.dev, B, to.H, to.W, (int)to.pb,
+                               std::ldexp(1.0f, h->sa_in), h->ctr_dev + i);
     } else if (o.type == OP_SPP) {
         const Tensor &t = h->T[o.in];
-        const size_t total = (size_t)B * t.H * t.W * (o.cin / 8);
-        hipLaunchKernelGGL(spp_bf16_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, t.dev, B, t.H, t.W,
-                           (int)t.pb, o.cin);
+        const int per = h->bf ? 8 : 16;                        // channels per thread (16 bytes)
+        const size_t total = (size_t)B * t.H * t.W * (o.cin / per);
+        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+        if (h->bf)
+            hipLaunchKernelGGL(spp_bf16_kernel, dim3(blocks), dim3(256), 0, s, t.dev, B, t.H, t.W, (int)t.pb, o.cin);
+        else
+            hipLaunchKernelGGL(spp_i8_kernel, dim3(blocks), dim3(256), 0, s, t.dev, B, t.H, t.W, (int)t.pb, o.cin);
     } else if (o.type == OP_REORG) {
         const Tensor &ti = h->T[o.in], &to = h->T[o.out];
-        const size_t total = (size_t)B * to.H * to.W * o.ksize * o.ksize * (o.cin / 8);
-        hipLaunchKernelGGL(reorg_bf16_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, ti.dev, to.dev, B,
-                           ti.H, ti.W, (int)ti.pb, o.cin, (int)to.pb, o.choff * h->es, o.ksize);
+        const int per = h->bf ? 8 : 16;
+        const size_t total = (size_t)B * to.H * to.W * o.ksize * o.ksize * (o.cin / per);
+        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
+        if (h->bf)
+            hipLaunchKernelGGL(reorg_bf16_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb, o.cin,
+                               (int)to.pb, o.choff * h->es, o.ksize);
+        else
+            hipLaunchKernelGGL(reorg_i8_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb, o.cin,
+                               (int)to.pb, o.choff, o.ksize, h->sa[o.out] - h->sa[o.in], h->ctr_dev + i);
     } else {
         const Tensor &ti = h->T[o.in], &to = h->T[o.out];
         const size_t total = (size_t)B * to.H * to.W * o.cin;

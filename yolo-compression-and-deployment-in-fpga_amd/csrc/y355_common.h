@@ -374,6 +374,18 @@ struct RequantG {
     int split;     // narrow only: Requant::split (the negative branch's product in two halves)
 };
 
+// int8 residual (backbone/darknet.py:36 `x + block(x)`), one rounding after the add (DESIGN.md "int8 DarkNet"):
+//   E = F + lk (exponent of t'), s_r the residual's, G = max(E, s_r)
+//   u = t' * 2^(G - E) + q_r * 2^(G - s_r);  q = clamp(RNE(u * 2^(s_out - G)))
+// 64-bit form: t_sh = G - E, r_sh = G - s_r, sh = G - s_out.  32-bit form (RequantG::narrow), the same rational per branch
+// over a common power of two 2^d: X = t * 2^(lk - sh' + d) + q_r * 2^(s_out - s_r + d) (t >= 0, sh' = E - s_out) or
+// X = t * neg_mul * 2^(d - sh') + q_r * 2^(s_out - s_r + d) (t < 0); q = clamp(RNE(X * 2^-d)) -- host-checked to fit 31 bits
+struct ResQ {
+    int t_sh, r_sh, sh;       // 64-bit form
+    int p_t, p_r, p_d;        // 32-bit form, t >= 0
+    int n_t, n_r, n_d;        // 32-bit form, t < 0
+};
+
 struct ConvGParams {
     const char *in;           // NHWC with halo, in_pb bytes per pixel
     char *out;                // NHWC, out_pb bytes per pixel
@@ -389,12 +401,13 @@ struct ConvGParams {
     float slope;              // bf16: y = x >= 0 ? x : slope * x
     int out_f32;              // bf16: store fp32 (prediction layers)
     RequantG rq;
-    // bf16: residual added after the activation (backbone/darknet.py:36 `module(x) + x`), same layout as
-    // `out` (halo, pixel pitch res_pb, byte offset res_off of channel 0); null = none
+    // residual added after the activation (backbone/darknet.py:36 `module(x) + x`), same layout as `out` (halo, pixel
+    // pitch res_pb, byte offset res_off of channel 0); null = none.  bf16: added in fp32; int8: ResQ rr below
     const char *res;
     int res_pb, res_off;
     int grid_limit;           // host side only: persistent workgroups of a convr.hip launch (0 = one per CU), Y355_NET_OPT_WORKGROUPS
     int xcd_share_log2;       // convr.hip: work items that read one input are walked by workgroups of one XCD (set by the launcher)
+    ResQ rr;                  // int8 with `res`: the residual's exponent shifts
 };
 
 struct Conv1FParams {

@@ -310,7 +310,7 @@ class _NetModel(nn.Module):
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
 
     def forward_batch(self, x, quantization=False):
-        """Every image of the batch.  quantization=True (YOLOv3tiny only) runs the int8 engine:
+        """Every image of the batch.  quantization=True (YOLOv3tiny, YOLOv2, YOLOv3, YOLOv3-SPP) runs the int8 engine:
         weights quantized per tensor to power-of-two int8 after the BN fold, activation exponents
         frozen at the first quantized call from the bf16 run of that input -- the first-call rule of
         AveragedRangeTracker (models/slim_yolo_v2.py:25-27) applied to this graph."""

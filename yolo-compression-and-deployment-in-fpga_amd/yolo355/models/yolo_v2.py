@@ -2,7 +2,8 @@
 prediction level at stride 32.  Same constructor, attribute names (so checkpoints load unchanged) and eval-mode
 return value.  `forward` / `forward_batch` run the whole graph on the GPU through y355_net (Y355_ARCH_YOLO_V2: 23
 BN-folded convolutions on the bf16 MFMA, pools fused or stand-alone, reorg + concat by channel offsets, head + NMS
--- csrc/net.hip).  `forward_batch_composed` / `prediction_map` run the same graph layer by layer through the
+-- csrc/net.hip); `forward_batch(x, quantization=True)` runs its int8 form (power-of-two weights, exponents frozen at the
+first quantized call).  `forward_batch_composed` / `prediction_map` run the same graph layer by layer through the
 operator API (y355_conv2d_bf16, y355_maxpool2x2_f32, y355_reorg_f32, y355_head_f32 -- SURVEY.md 8f-3), one host round
 trip per layer: the bring-up / cross-check form.  Training is not built."""
 import numpy as np
@@ -71,11 +72,6 @@ class myYOLOv2(_NetModel):
         return head_f32([pred], [self.stride], anchors, self.num_classes, self.input_size, float(self.stride),
                         self.conf_thresh, self.nms_thresh,
                         device_id=x.device.index if x.is_cuda and x.device.index is not None else 0)
-
-    def forward_batch(self, x, quantization=False):
-        if quantization:
-            raise NotImplementedError("yolo355: yolo_v2 has no quantized form (neither has the reference)")
-        return super().forward_batch(x)
 
     def forward(self, x, target=None):
         if target is not None:

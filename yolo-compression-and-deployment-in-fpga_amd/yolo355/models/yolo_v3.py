@@ -3,7 +3,8 @@ DarkNet-53 backbone (stride-2 convolutions, residual blocks), three prediction l
 1x1 convolutions and bilinear x2 up-sampling, optional SPP in front of the stride-32 branch.  Same constructor,
 attribute names (checkpoints load unchanged) and eval-mode return value.  `forward` / `forward_batch` run the whole graph
 on the GPU through y355_net (Y355_ARCH_YOLO_V3 / _SPP: 75 BN-folded convolutions on the bf16 MFMA, stride-2 and residual
-forms of the generic kernel, SPP and bilinear x2 into concat buffers, three-level head -- csrc/net.hip).
+forms of the generic kernel, SPP and bilinear x2 into concat buffers, three-level head -- csrc/net.hip);
+`forward_batch(x, quantization=True)` runs its int8 form (power-of-two weights, exponents frozen at the first quantized call).
 `forward_batch_composed` / `prediction_maps` run the same graph layer by layer through the operator API
 (y355_conv2d_bf16, y355_spp_f32, y355_upsample2x_f32, y355_head_f32 -- SURVEY.md 8f-3): the bring-up / cross-check form.  At 416 x 416 an
 image has 10 647 anchors: the head thresholds and compacts them on the GPU, and at most 4096 may pass conf_thresh.
@@ -113,11 +114,6 @@ class myYOLOv3(_NetModel):
             preds = self.prediction_maps(x)
         return head_f32(preds, self.stride, self.anchor_size.detach().float().cpu().numpy(), self.num_classes, self.input_size,
                         1.0, self.conf_thresh, self.nms_thresh, device_id=_dev(x))
-
-    def forward_batch(self, x, quantization=False):
-        if quantization:
-            raise NotImplementedError("yolo355: yolo_v3 has no quantized form (neither has the reference)")
-        return super().forward_batch(x)
 
     def forward(self, x, target=None):
         if target is not None:

@@ -1,5 +1,5 @@
 """Python handle over the y355_net_* C ABI (include/yolo355.h): the table-driven executor of
-csrc/net.hip for SlimYOLOv2 (fp32 model -> bf16 MFMA) and YOLOv3tiny.  PyTorch is used for
+csrc/net.hip for SlimYOLOv2 (fp32 model -> bf16 MFMA), YOLOv3tiny, YOLOv2, YOLOv3 and YOLOv3-SPP, in bf16 or int8.  PyTorch is used for
 device memory and the stream only; all compute is in libyolo355.so."""
 import ctypes as C
 
@@ -13,6 +13,8 @@ ARCH = {"slim_yolo_v2": _ffi.ARCH_SLIM_V2, "tiny_yolo_v3": _ffi.ARCH_TINY_V3, "y
         "yolo_v3": _ffi.ARCH_YOLO_V3, "yolo_v3_spp": _ffi.ARCH_YOLO_V3_SPP}
 NLEV = {"slim_yolo_v2": 1, "tiny_yolo_v3": 2, "yolo_v2": 1, "yolo_v3": 3, "yolo_v3_spp": 3}
 DTYPE = {"int8": _ffi.DT_INT8, "bf16": _ffi.DT_BF16}
+# prediction maps (fp32 in bf16 nets) by their index from the end of the tensor list (graph order of csrc/net.hip)
+PRED_TAIL = {"slim_yolo_v2": (1,), "tiny_yolo_v3": (2, 1), "yolo_v2": (1,), "yolo_v3": (5, 3, 1), "yolo_v3_spp": (5, 3, 1)}
 
 
 class Net:
@@ -197,9 +199,9 @@ class Net:
         self.forward_device(xd, _ffi.F_TAP)      # tap forward: every tensor is written (the fused front end skips conv1's map)
         sa_in = RangeTracker().update(float(xd.abs().max().item()), True)
         sa = []
+        pred = {self.num_tensors - k for k in PRED_TAIL[self.arch]}
         for t in range(self.num_tensors):
-            c, hh, ww = self.tensor_shape(t)
-            if t >= self.num_tensors - (2 if self.arch == "tiny_yolo_v3" else 1):
+            if t in pred:
                 m = float(np.abs(self.get_tensor(t, B)).max())       # fp32 prediction maps
             else:
                 m = self.tensor_absmax(t, B)

@@ -503,6 +503,23 @@ int y355_net_counters(y355_net *h, int64_t *saturated);
  * batch; arguments and outputs as y355_forward. */
 int y355_net_forward(y355_net *h, const float *x_dev, int batch, int flags,
                      float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev);
+/* The step in front of every family: camera frames as cv2 delivers them, uint8 HWC BGR
+ * [B][src_h][src_w][3] on the device, as the network input.  BaseTransform (data/__init__.py:30-56: cv2.resize to the
+ * network size, /255, -mean, /std), the BGR->RGB swap and the HWC->CHW permute (test.py:79-85) run inside the op that
+ * reads the input: the input op of YOLOv2 / YOLOv3 / YOLOv3-SPP (resize fused into its load), the first layer or the
+ * fused front end of SlimYOLOv2 / YOLOv3tiny (behind a resize stage into a net-owned buffer when src differs from the
+ * network size, or when frames_dev is not 4-byte aligned).  Nothing else is resized at the network size.  Outputs, flags,
+ * taps and int8 clamp counts as y355_net_forward on the normalised tensor of the resized frames, bit for bit;
+ * 1 <= src_h, src_w <= 16384.  With y355_net_profile on, the first timer (op 0) includes that resize stage.
+ * y355_net_set_normalization: mean / std in the reference's BGR order (defaults data/__init__.py:50).
+ * y355_net_resize_u8: the resize stage alone into out_dev [B][H][W][3] (parity tap), on the net's stream.
+ * y355_net_scale_boxes: `bboxes *= [[w, h, w, h]]` of the evaluators (test.py:88-90) on a forward's outputs, in place,
+ * wh_dev [B][2] = (width, height), as y355_scale_boxes. */
+int y355_net_set_normalization(y355_net *h, const float *mean_bgr, const float *std_bgr);
+int y355_net_forward_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int flags,
+                        float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev);
+int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, uint8_t *out_dev);
+int y355_net_scale_boxes(y355_net *h, float *boxes_dev, const int32_t *count_dev, const float *wh_dev, int batch);
 int y355_net_get_candidates(y355_net *h, int batch, float *boxes, float *scores, int32_t *cls);
 /* parity tap: activation tensor idx (graph order, see csrc/net.hip) as fp32 NCHW on the host.
  * Tensor taps and calibration need a forward with Y355_F_TAP: on SlimYOLOv2 / YOLOv3tiny graphs a plain forward runs the first

@@ -14,7 +14,9 @@
 #include "y355_common.h"
 #include <type_traits>
 
-template <int TW, bool WIDE>
+// U8: the input is the camera frame (uint8 HWC BGR, p.x_u8), normalised and quantised through a per-channel byte table as in
+// conv1_fast_kernel (y355_net's first layer when its epilogue needs more than 32 bits)
+template <int TW, bool WIDE, bool U8 = false>
 __global__ __launch_bounds__(256) void conv1_kernel(const Conv1Params p) {
     using T = typename std::conditional<WIDE, long long, int>::type;
     using U = typename UnsignedOf<T>::type;
@@ -37,6 +39,32 @@ __global__ __launch_bounds__(256) void conv1_kernel(const Conv1Params p) {
     unsigned int nsat_in = 0;
 
     // ---- quantise the (TH+2)x(TW+2) input patch: q = clamp(rne(x * 2^sa0))  (:33-35)
+    if constexpr (U8) {
+        __shared__ unsigned short lut[3 * 256];            // bits 0-7 the int8 value, bit 8 "was clamped"
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float r = rintf(y355_norm_u8(tid, p.nmean[c], p.nstd[c]) * sc);
+            const float rc = fminf(fmaxf(r, -127.f), 127.f);
+            lut[c * 256 + tid] = (unsigned short)(((int)rc & 0xff) | (rc != r ? 0x100 : 0));
+        }
+        __syncthreads();
+        const uint8_t *fb = p.x_u8 + (size_t)b * H * W * 3;
+        for (int it = tid; it < PH * PW; it += 256) {
+            const int py = it / PW, px = it % PW;
+            const int gy = y0 + py - 1, gx = x0 + px - 1;
+            const bool inside = (gy >= 0) && (gy < H) && (gx >= 0) && (gx < W);
+            const bool own = inside && py >= 1 && py <= TH && px >= 1 && px <= TW;
+            const size_t o = ((size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1)) * 3;
+            unsigned int w = 0;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const unsigned int e = lut[c * 256 + fb[o + (2 - c)]];      // RGB channel c = BGR byte 2 - c
+                nsat_in += (own && (e & 0x100u)) ? 1u : 0u;
+                w |= (inside ? (e & 0xffu) : 0u) << (8 * c);
+            }
+            patch[it] = w;
+        }
+    } else {
     const float *xb = p.x + (size_t)b * 3 * H * W;
     const size_t plane = (size_t)H * W;
     for (int it0 = tid; it0 < PH * PW; it0 += 256 * 4) {
@@ -68,6 +96,7 @@ __global__ __launch_bounds__(256) void conv1_kernel(const Conv1Params p) {
             }
             patch[it] = w;
         }
+    }
     }
     if (tid < 8) patch[PH * PW + tid] = 0;
     __syncthreads();
@@ -177,11 +206,7 @@ __global__ __launch_bounds__(256) void conv1_fast_kernel(const Conv1Params p) {
         __shared__ unsigned short lut[3 * 256];
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float t = (float)tid;
-            t /= 255.0f;
-            t -= p.nmean[c];
-            t /= p.nstd[c];
-            const float r = rintf(t * sc);
+            const float r = rintf(y355_norm_u8(tid, p.nmean[c], p.nstd[c]) * sc);
             const float rc = fminf(fmaxf(r, -127.f), 127.f);
             lut[c * 256 + tid] = (unsigned short)(((int)rc & 0xff) | (rc != r ? 0x100 : 0));
         }
@@ -375,9 +400,14 @@ void y355_conv1_tiles(int H, int W, int *tx, int *ty) {
 void y355_launch_conv1(const Conv1Params &p, hipStream_t s) {
     const int n = p.tiles_x * p.tiles_y * p.B;
     const bool big = conv1_tw(p.W) == 104;
-    if (p.mode == 0 && !p.guard && p.rq.gen32 && p.x && p.bias_t) {       // y355_net's first layer, general slope in 32 bits
-        if (big) hipLaunchKernelGGL((conv1_fast_kernel<104, false, true>), dim3(n), dim3(256), 0, s, p);
-        else hipLaunchKernelGGL((conv1_fast_kernel<32, false, true>), dim3(n), dim3(256), 0, s, p);
+    if (p.mode == 0 && !p.guard && p.rq.gen32 && p.bias_t) {               // y355_net's first layer, general slope in 32 bits
+        if (p.x) {
+            if (big) hipLaunchKernelGGL((conv1_fast_kernel<104, false, true>), dim3(n), dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((conv1_fast_kernel<32, false, true>), dim3(n), dim3(256), 0, s, p);
+        } else {                                                              // y355_net_forward_u8
+            if (big) hipLaunchKernelGGL((conv1_fast_kernel<104, true, true>), dim3(n), dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((conv1_fast_kernel<32, true, true>), dim3(n), dim3(256), 0, s, p);
+        }
         return;
     }
     if (p.mode == 0 && !p.rq.wide && !p.guard && !p.out_pb) {
@@ -387,6 +417,16 @@ void y355_launch_conv1(const Conv1Params &p, hipStream_t s) {
         } else {
             if (big) hipLaunchKernelGGL((conv1_fast_kernel<104, true>), dim3(n), dim3(256), 0, s, p);
             else hipLaunchKernelGGL((conv1_fast_kernel<32, true>), dim3(n), dim3(256), 0, s, p);
+        }
+        return;
+    }
+    if (!p.x) {                                      // frames (y355_net_forward_u8: the q_bf engine stages these cases in fp32)
+        if (p.rq.wide) {
+            if (big) hipLaunchKernelGGL((conv1_kernel<104, true, true>), dim3(n), dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((conv1_kernel<32, true, true>), dim3(n), dim3(256), 0, s, p);
+        } else {
+            if (big) hipLaunchKernelGGL((conv1_kernel<104, false, true>), dim3(n), dim3(256), 0, s, p);
+            else hipLaunchKernelGGL((conv1_kernel<32, false, true>), dim3(n), dim3(256), 0, s, p);
         }
         return;
     }
@@ -444,11 +484,7 @@ __global__ __launch_bounds__(256) void normalize_u8_kernel(const uint8_t *frames
         const size_t b = i / ((size_t)H * W), r = i % ((size_t)H * W);
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float t = (float)frames[i * 3 + (2 - c)];
-            t /= 255.0f;
-            t -= mean[c];
-            t /= sd[c];
-            x[(b * 3 + c) * (size_t)H * W + r] = t;
+            x[(b * 3 + c) * (size_t)H * W + r] = y355_norm_u8(frames[i * 3 + (2 - c)], mean[c], sd[c]);
         }
     }
 }

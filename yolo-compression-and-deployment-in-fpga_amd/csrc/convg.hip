@@ -772,11 +772,13 @@ void y355_convg_pack(const ConvGInfo &ki, const float *w_f, const int8_t *w_q, i
 }
 
 // ------------------------------------------------------------------------------------------
-// First layer of the bf16 nets: fp32 NCHW -> bf16 -> conv3x3(3 -> 16) + bias + LeakyReLU + 2x2 max
+// First layer of the bf16 nets: fp32 NCHW (or uint8 frames) -> bf16 -> conv3x3(3 -> 16) + bias + LeakyReLU + 2x2 max
 // pool -> bf16 NHWC16 with halo (SlimYOLOv2.conv1 + pool1, models/slim_yolo_v2.py:551-552).
 // LDS patch of 8-byte pixels (r, g, b, 0); K = 3 filter rows x 2 pixels x 4 per MFMA, two MFMAs
 // (pixel columns 0-1, then column 2) per 16 pixels x 16 channels.
-template <int TW>
+// U8: the input is the camera frame (uint8 HWC BGR, p.x_u8): BaseTransform + BGR->RGB through a per-channel table of the bf16
+// values (y355_norm_u8 rounded to bf16 as the fp32 load would be), so the patch holds the same bits.
+template <int TW, bool U8 = false>
 __global__ __launch_bounds__(256) void conv1_bf16_kernel(const Conv1FParams p) {
     constexpr int TH = 16;
     constexpr int PW = TW + 2, PH = TH + 2;
@@ -793,6 +795,23 @@ __global__ __launch_bounds__(256) void conv1_bf16_kernel(const Conv1FParams p) {
     const int b = bid / p.tiles_y;
     const int H = p.H, W = p.W;
     const int y0 = ty * TH, x0 = tx * TW;
+    if constexpr (U8) {
+        __shared__ unsigned short lut[3 * 256];
+#pragma unroll
+        for (int c = 0; c < 3; ++c) lut[c * 256 + tid] = __builtin_bit_cast(unsigned short, (__bf16)y355_norm_u8(tid, p.nmean[c], p.nstd[c]));
+        __syncthreads();
+        const uint8_t *fb = p.x_u8 + (size_t)b * H * W * 3;
+        for (int it = tid; it < PH * PW; it += 256) {
+            const int py = it / PW, px = it % PW;
+            const int gy = y0 + py - 1, gx = x0 + px - 1;
+            const bool inside = (gy >= 0) && (gy < H) && (gx >= 0) && (gx < W);
+            const size_t o = ((size_t)min(max(gy, 0), H - 1) * W + min(max(gx, 0), W - 1)) * 3;
+            unsigned short h[3];
+#pragma unroll
+            for (int c = 0; c < 3; ++c) h[c] = inside ? lut[c * 256 + fb[o + (2 - c)]] : (unsigned short)0;     // RGB c = BGR byte 2 - c
+            patch[it] = make_uint2((unsigned int)h[0] | ((unsigned int)h[1] << 16), (unsigned int)h[2]);
+        }
+    } else {
     const float *xb = p.x + (size_t)b * 3 * H * W;
     const size_t plane = (size_t)H * W;
     for (int it0 = tid; it0 < PH * PW; it0 += 256 * 4) {
@@ -819,6 +838,7 @@ __global__ __launch_bounds__(256) void conv1_bf16_kernel(const Conv1FParams p) {
             w.y = (unsigned int)h[2];
             patch[it] = w;
         }
+    }
     }
     if (tid < 8) patch[PH * PW + tid] = make_uint2(0u, 0u);
     __syncthreads();
@@ -869,8 +889,14 @@ void y355_conv1f_tiles(int H, int W, int *tx, int *ty) {
 
 void y355_launch_conv1f(const Conv1FParams &p, hipStream_t s) {
     const int n = p.tiles_x * p.tiles_y * p.B;
-    if (conv1f_tw(p.W) == 104) hipLaunchKernelGGL((conv1_bf16_kernel<104>), dim3(n), dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((conv1_bf16_kernel<32>), dim3(n), dim3(256), 0, s, p);
+    const bool big = conv1f_tw(p.W) == 104;
+    if (p.x) {
+        if (big) hipLaunchKernelGGL((conv1_bf16_kernel<104>), dim3(n), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((conv1_bf16_kernel<32>), dim3(n), dim3(256), 0, s, p);
+    } else {                                                  // uint8 frames (y355_net_forward_u8)
+        if (big) hipLaunchKernelGGL((conv1_bf16_kernel<104, true>), dim3(n), dim3(256), 0, s, p);
+        else hipLaunchKernelGGL((conv1_bf16_kernel<32, true>), dim3(n), dim3(256), 0, s, p);
+    }
 }
 
 // two B fragments: lane (g = filter row, j = cout) holds k = 4 d' + c, d' = 0,1 -> pixel column

@@ -936,48 +936,6 @@ extern "C" int y355_forward_u8(y355_engine *h, const uint8_t *frames_dev, int ba
     return rc;
 }
 
-// ---- cv2.resize(image, (W, H)) of BaseTransform (data/__init__.py:36) for uint8 HWC frames, INTER_LINEAR: OpenCV's 8-bit
-// fixed-point bilinear (imgproc/resize.cpp: 11-bit coefficients, horizontal pass in int32, vertical pass
-// (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2).  The coefficient tables are computed on the host with
-// OpenCV's own float / double expressions, so the kernel only gathers and does integer arithmetic.
-// Horizontal axis: OpenCV clamps the offset AND zeroes the fraction at both borders.  Vertical axis (`vertical`): it keeps
-// floor(f) and the coefficient pair as they are and clips the two ROW INDICES instead (resizeGeneric_Invoker:
-// `sy = clip(sy0 - ksize2 + 1 + k, 0, ssize.height)`), so a border row is blended with itself through two separately
-// truncated products -- up to 1 LSB below the single-product form; the kernel does the same clipping.
-static void linear_tables(int src, int dst, int *ofs, int *coef, bool vertical) {
-    const double scale = (double)src / (double)dst;
-    for (int d = 0; d < dst; ++d) {
-        float f = (float)((d + 0.5) * scale - 0.5);
-        int sx = (int)std::floor(f);
-        f -= (float)sx;
-        if (!vertical && sx < 0) { sx = 0; f = 0.f; }
-        if (!vertical && sx >= src - 1) { sx = src - 1; f = 0.f; }
-        ofs[d] = sx;
-        const long c0 = std::lrintf((1.f - f) * 2048.f), c1 = std::lrintf(f * 2048.f);     // saturate_cast<short>: round half to even
-        coef[2 * d] = (int)std::min(32767l, std::max(-32768l, c0));
-        coef[2 * d + 1] = (int)std::min(32767l, std::max(-32768l, c1));
-    }
-}
-
-__global__ __launch_bounds__(256) void resize_u8_kernel(const uint8_t *src, uint8_t *dst, const int *tab, int sh, int sw, int dh, int dw) {
-    const int b = blockIdx.y;
-    const int i = blockIdx.x * 256 + threadIdx.x;
-    if (i >= dh * dw) return;
-    const int dy = i / dw, dx = i % dw;
-    const int *xofs = tab, *xa = tab + dw, *yofs = tab + 3 * dw, *yb = tab + 3 * dw + dh;
-    const int sx0 = xofs[dx], sx1 = min(sx0 + 1, sw - 1), a0 = xa[2 * dx], a1 = xa[2 * dx + 1];
-    const int sy0 = min(max(yofs[dy], 0), sh - 1), sy1 = min(max(yofs[dy] + 1, 0), sh - 1), b0 = yb[2 * dy], b1 = yb[2 * dy + 1];
-    const uint8_t *s = src + (size_t)b * sh * sw * 3;
-    uint8_t *d = dst + ((size_t)b * dh * dw + i) * 3;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const int d0 = (int)s[((size_t)sy0 * sw + sx0) * 3 + c] * a0 + (int)s[((size_t)sy0 * sw + sx1) * 3 + c] * a1;
-        const int d1 = (int)s[((size_t)sy1 * sw + sx0) * 3 + c] * a0 + (int)s[((size_t)sy1 * sw + sx1) * 3 + c] * a1;
-        const int v = (((b0 * (d0 >> 4)) >> 16) + ((b1 * (d1 >> 4)) >> 16) + 2) >> 2;
-        d[c] = (uint8_t)min(max(v, 0), 255);
-    }
-}
-
 // frames of any size: cv2.resize to the network size on the GPU, then y355_forward_u8.  frames_dev uint8 [B][src_h][src_w][3].
 // `resized_out_dev` (optional, [B][H][W][3]) receives the resized frames (parity tap).
 extern "C" int y355_forward_u8_resized(y355_engine *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int flags,
@@ -994,15 +952,13 @@ extern "C" int y355_forward_u8_resized(y355_engine *h, const uint8_t *frames_dev
     }
     if (h->rs_src_h != src_h || h->rs_src_w != src_w) {
         std::vector<int> tab(3 * (size_t)(H + W));
-        linear_tables(src_w, W, tab.data(), tab.data() + W, false);
-        linear_tables(src_h, H, tab.data() + 3 * W, tab.data() + 3 * W + H, true);
+        y355_resize_tables(src_h, src_w, H, W, tab.data());
         HIPCHK(hipStreamSynchronize(h->stream));          // a previous forward may still read the old tables
         HIPCHK(hipMemcpy(h->rs_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
         h->rs_src_h = src_h;
         h->rs_src_w = src_w;
     }
-    hipLaunchKernelGGL(resize_u8_kernel, dim3((H * W + 255) / 256, batch), dim3(256), 0, h->stream, frames_dev, h->rs_frames, h->rs_tab,
-                       src_h, src_w, H, W);
+    y355_launch_resize_u8(frames_dev, h->rs_frames, h->rs_tab, batch, src_h, src_w, H, W, h->stream);
     HIPCHK(hipGetLastError());
     if (resized_out_dev)
         HIPCHK(hipMemcpyAsync(resized_out_dev, h->rs_frames, (size_t)batch * H * W * 3, hipMemcpyDeviceToDevice, h->stream));
@@ -1102,12 +1058,15 @@ __global__ void scale_boxes_kernel(float *boxes, const int32_t *count, const flo
         *p = v;
     }
 }
+// (also y355_net_scale_boxes)
+void y355_launch_scale_boxes(float *boxes, const int32_t *count, const float *wh, int batch, int max_det, hipStream_t s) {
+    hipLaunchKernelGGL(scale_boxes_kernel, dim3((max_det + 255) / 256, batch), dim3(256), 0, s, boxes, count, wh, max_det);
+}
 extern "C" int y355_scale_boxes(y355_engine *h, float *boxes_dev, const int32_t *count_dev, const float *wh_dev, int batch) {
     if (!h || !boxes_dev || !count_dev || !wh_dev) return fail(Y355_EINVAL, "null argument");
     if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    const int md = y355_max_det(h);
-    hipLaunchKernelGGL(scale_boxes_kernel, dim3((md + 255) / 256, batch), dim3(256), 0, h->stream, boxes_dev, count_dev, wh_dev, md);
+    y355_launch_scale_boxes(boxes_dev, count_dev, wh_dev, batch, y355_max_det(h), h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }

@@ -211,11 +211,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
         // (byte 3 of a pixel multiplies zero weights)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
-            float t = (float)tid;
-            t /= 255.0f;
-            t -= p.nmean[c];
-            t /= p.nstd[c];
-            const float r = rintf(t * sc);
+            const float r = rintf(y355_norm_u8(tid, p.nmean[c], p.nstd[c]) * sc);
             const float rc = fminf(fmaxf(r, -127.f), 127.f);
             lut[c * 256 + tid] = (((unsigned int)(int)rc & 0xffu) << (8 * c)) | (rc != r ? (1u << 24) : 0u);
         }

@@ -1,4 +1,4 @@
-// yolo355 -- fused front end of the bf16 nets (round 4): fp32 NCHW input -> bf16 -> conv(3 -> 16) + bias + LeakyReLU + 2x2 max
+// yolo355 -- fused front end of the bf16 nets (round 4): fp32 NCHW input (or uint8 HWC BGR frames) -> bf16 -> conv(3 -> 16) + bias + LeakyReLU + 2x2 max
 // pool -> conv(16 -> 32) + bias + LeakyReLU + 2x2 max pool -> bf16 NHWC32 with halo, ONE kernel.
 //
 // Replaces SlimYOLOv2.conv1 + pool1 + conv2 + pool2 (models/slim_yolo_v2.py:549-575, BatchNorm folded on the host) and
@@ -57,8 +57,12 @@ __device__ __forceinline__ unsigned int pk_bf16(float a, float b) {       // (a,
 }
 }  // namespace
 
+// U8: the input is the camera frame (uint8 HWC BGR, p.x_u8); BaseTransform + BGR->RGB are a per-channel table of the bf16 values
+// (y355_norm_u8, rounded as the fp32 path rounds its loads), read in place of the fp32 loads: otherwise the same code and bits
+template <bool U8>
 __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, const int total_tiles) {
     __shared__ __attribute__((aligned(16))) uint2 patch[PH0 * P0];        // bf16 (r, g, b, 0) pixels; later the staged output tile
+    __shared__ unsigned short lut[U8 ? 3 * 256 : 2];
     __shared__ __attribute__((aligned(16))) char p1[P1ROWS * P1P * 32];   // conv1's pooled map, 16 bf16 channels per pixel
     __shared__ __attribute__((aligned(16))) char wl[W1_BYTES + 64];       // conv1's fragments and biases
     char *stg = (char *)patch;
@@ -76,6 +80,11 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
     if (tile >= total_tiles) return;
     const int G_ = gridDim.x;
     // ---- once per workgroup: conv1's fragments into LDS, this wave's conv2 fragments and biases into registers
+    if constexpr (U8) {
+        if (tid < 256)
+#pragma unroll
+            for (int c = 0; c < 3; ++c) lut[c * 256 + tid] = __builtin_bit_cast(unsigned short, (__bf16)y355_norm_u8(tid, p.nmean[c], p.nstd[c]));
+    }
     *(v4i *)(wl + tid * 16) = *(const v4i *)(p.wf + tid * 16);
     if (tid < 4) *(v4i *)(wl + W1_BYTES + 16 * tid) = *(const v4i *)(p.bias1 + 4 * tid);
     const int npass = wave >> 2;                           // this wave's half of conv2's output channels: 8 g + 4 npass + r
@@ -107,21 +116,41 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
         // neighbourhood of every conv1 window then starts on a 16-byte boundary): the first pixel of a lane's aligned 4-pixel
         // group belongs to the previous lane's 32 bytes
         {
-            float4 vf[2][3];
+            float4 vf[U8 ? 1 : 2][3];
+            uint3 vu[U8 ? 2 : 1];                           // U8: four pixels x 3 bytes
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int r = qr0 + 32 * k;
                 const int gy = min(max(y0p + r, 0), H - 1);
                 const int gx = min(max(x0p + 4 * qj, 0), W - 4);
-                const float *xb = p.x + (size_t)b * 3 * plane + (size_t)gy * W + gx;
+                if constexpr (U8) {
+                    // 12 bytes at a multiple of 12 from the frames pointer: dword-aligned because that pointer is
+                    // (y355_net_forward_u8 stages frames at any other address into its own buffer)
+                    const uint8_t *fbase = p.x_u8 + (size_t)b * plane * 3;
+                    vu[k] = *(const uint3 *)(fbase + (unsigned int)(gy * W + gx) * 3u);
+                } else {
+                    const float *xb = p.x + (size_t)b * 3 * plane + (size_t)gy * W + gx;
 #pragma unroll
-                for (int c = 0; c < 3; ++c) vf[k][c] = *(const float4 *)(xb + c * plane);
+                    for (int c = 0; c < 3; ++c) vf[k][c] = *(const float4 *)(xb + c * plane);
+                }
             }
 #pragma unroll
             for (int k = 0; k < 2; ++k) {
                 const int r = qr0 + 32 * k;
                 const int gy = y0p + r, gx = x0p + 4 * qj;
                 unsigned int lo[4], hi[4];
+                if constexpr (U8) {
+                    // bytes of the four pixels: B G R B | G R B G | R B G R (RGB channel c = BGR byte 2 - c)
+                    const unsigned int w0 = vu[k].x, w1 = vu[k].y, w2 = vu[k].z;
+                    const unsigned int ur[4] = {(w0 >> 16) & 0xffu, (w1 >> 8) & 0xffu, w2 & 0xffu, w2 >> 24};
+                    const unsigned int ug[4] = {(w0 >> 8) & 0xffu, w1 & 0xffu, w1 >> 24, (w2 >> 16) & 0xffu};
+                    const unsigned int ub[4] = {w0 & 0xffu, w0 >> 24, (w1 >> 16) & 0xffu, (w2 >> 8) & 0xffu};
+#pragma unroll
+                    for (int px = 0; px < 4; ++px) {
+                        lo[px] = __builtin_amdgcn_perm((unsigned int)lut[256 + ug[px]], (unsigned int)lut[ur[px]], 0x05040100u);
+                        hi[px] = (unsigned int)lut[512 + ub[px]];
+                    }
+                } else {
                 const float xr[4] = {vf[k][0].x, vf[k][0].y, vf[k][0].z, vf[k][0].w};
                 const float xg[4] = {vf[k][1].x, vf[k][1].y, vf[k][1].z, vf[k][1].w};
                 const float xbv[4] = {vf[k][2].x, vf[k][2].y, vf[k][2].z, vf[k][2].w};
@@ -129,6 +158,7 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
                 for (int px = 0; px < 4; ++px) {
                     lo[px] = pk_bf16(xr[px], xg[px]);
                     hi[px] = pk_bf16(xbv[px], 0.f);
+                }
                 }
                 if (border) {                                 // wave-uniform: interior tiles (36 of 64) have no padding to select
                     const bool zero = !((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W);          // conv1's zero padding
@@ -309,5 +339,6 @@ void y355_launch_frontb(const FrontBParams &p, hipStream_t s) {
     q.step_x = grid % p.tiles_x;                           // the walk's stride (one grid) in the tile index's mixed radix
     q.step_y = (grid / p.tiles_x) % p.tiles_y;
     q.step_b = grid / (p.tiles_x * p.tiles_y);
-    hipLaunchKernelGGL(frontb_kernel, dim3(grid), dim3(NTHR), 0, s, q, total);
+    if (p.x) hipLaunchKernelGGL(frontb_kernel<false>, dim3(grid), dim3(NTHR), 0, s, q, total);
+    else hipLaunchKernelGGL(frontb_kernel<true>, dim3(grid), dim3(NTHR), 0, s, q, total);
 }

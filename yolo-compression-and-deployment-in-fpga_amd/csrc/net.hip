@@ -454,6 +454,60 @@ __global__ void input_i8_kernel(const float *x, char *out, int B, int H, int W, 
     count_sat(ctr, nsat);
 }
 
+// BaseTransform constants per RGB channel (data/__init__.py:50 lists them in BGR order)
+struct NormU8 { float mean[3], sd[3]; };
+
+// uint8 HWC BGR frames [B][sh][sw][3] -> the network input tensor with halo, bf16 NHWC16 (I8 = false) or int8 NHWC32 (I8):
+// cv2.resize to the network size fused into the load when the frame is not at it (tab != null: y355_resize_px), then
+// BaseTransform + BGR->RGB through a per-channel byte table in LDS that holds what input_bf16_kernel / input_i8_kernel make
+// of the normalised fp32 value -- its bf16 (RNE), or clamp(RNE(x * 2^sa_in)) with bit 8 = "was clamped" (counted into ctr as
+// input_i8_kernel counts).  One pixel per thread, one 16-byte store (bf16: channels 3..7 zero; int8: 3..15 zero; the rest of
+// the pixel keeps the allocation's zeros).
+template <bool I8>
+__global__ __launch_bounds__(256) void input_u8_kernel(const uint8_t *frames, const int *tab, char *out, int B, int sh, int sw, int H,
+                                                       int W, int out_pb, NormU8 nm, float in_scale, Counters *ctr) {
+    __shared__ unsigned short lut[3 * 256];
+    const int tid = threadIdx.x;
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const float t = y355_norm_u8(tid, nm.mean[c], nm.sd[c]);
+        if constexpr (I8) {
+            const float r = rintf(t * in_scale);
+            const float q = fminf(fmaxf(r, -127.f), 127.f);
+            lut[c * 256 + tid] = (unsigned short)(((int)q & 0xff) | (q != r ? 0x100 : 0));
+        } else {
+            lut[c * 256 + tid] = __builtin_bit_cast(unsigned short, (__bf16)t);
+        }
+    }
+    __syncthreads();
+    const size_t total = (size_t)B * H * W;
+    const size_t plane = (size_t)H * W;
+    unsigned int nsat = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + tid; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int xx = (int)(i % W), y = (int)((i / W) % H);
+        const size_t b = i / plane;
+        int u[3];
+        if (tab) {
+            y355_resize_px(frames + b * sh * sw * 3, tab, sh, sw, H, W, y, xx, u);
+        } else {
+            const uint8_t *px = frames + i * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) u[c] = px[c];
+        }
+        // RGB channel c = BGR byte 2 - c
+        const unsigned int e0 = lut[u[2]], e1 = lut[256 + u[1]], e2 = lut[512 + u[0]];
+        uint4 v;
+        if constexpr (I8) {
+            nsat += ((e0 >> 8) & 1u) + ((e1 >> 8) & 1u) + ((e2 >> 8) & 1u);
+            v = make_uint4((e0 & 0xffu) | ((e1 & 0xffu) << 8) | ((e2 & 0xffu) << 16), 0u, 0u, 0u);
+        } else {
+            v = make_uint4(e0 | (e1 << 16), e2, 0u, 0u);
+        }
+        *(uint4 *)(out + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + xx + 1) * out_pb) = v;
+    }
+    if constexpr (I8) count_sat(ctr, nsat);
+}
+
 // reorg (utils/modules.py:48-57) of int8 NHWC into a concat buffer with the rescale 2^(s_out - s_in):
 // out[.., (sy*s+sx)*C + c] = rescale(in[s*y+sy][s*x+sx][c]); 16 bytes (16 channels) per thread
 __global__ void reorg_i8_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int C, int out_pb, int out_off, int s,
@@ -570,6 +624,23 @@ struct y355_net {
     int profile = 0;
     std::vector<hipEvent_t> ev;
     std::vector<void *> allocs;
+    // uint8 frame input (y355_net_forward_u8): BaseTransform constants (RGB order), the resize stage's tables for one source
+    // size, and the resized frames the conv1 / fused front-end routes read when the frames are not at the network size
+    NormU8 norm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
+    int *rs_tab = nullptr;
+    uint8_t *rs_frames = nullptr;
+    int rs_src_h = 0, rs_src_w = 0;
+};
+
+// the network input of one forward: an fp32 NCHW tensor, or uint8 HWC BGR frames (u8) of src_h x src_w with the resize tables
+// (tab, null when the frames are at the network size).  stage: frames [B][sh][sw][3] the forward first resizes into u8 (the
+// net-owned buffer) with tab, inside the first op's profile interval
+struct NetInput {
+    const float *x = nullptr;
+    const uint8_t *u8 = nullptr;
+    const int *tab = nullptr;
+    int sh = 0, sw = 0;
+    const uint8_t *stage = nullptr;
 };
 
 static int in_kbytes(const y355_net *h, const OpDef &o);
@@ -1206,7 +1277,7 @@ static int in_kbytes(const y355_net *h, const OpDef &o) {
 
 static float act_slope(int act) { return act == ACT_L125 ? 0.125f : act == ACT_L100 ? 0.1f : 1.0f; }
 
-static int run_op(y355_net *h, int i, int B, const float *x_dev) {
+static int run_op(y355_net *h, int i, int B, const NetInput &in) {
     const OpDef &o = h->arch->ops[i];
     hipStream_t s = h->stream;
     if (o.type == OP_CONV1) {
@@ -1214,7 +1285,9 @@ static int run_op(y355_net *h, int i, int B, const float *x_dev) {
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
         if (!h->bf) {
             Conv1Params p{};
-            p.x = x_dev;
+            p.x = in.x;
+            p.x_u8 = in.u8;                                    // (conv1 routes get frames at the network size)
+            for (int c = 0; c < 3; ++c) { p.nmean[c] = h->norm.mean[c]; p.nstd[c] = h->norm.sd[c]; }
             p.out = (int8_t *)h->T[o.out].dev;
             p.out_pb = (int)h->T[o.out].pb;
             p.w = (const int8_t *)h->w0_dev;
@@ -1234,7 +1307,9 @@ static int run_op(y355_net *h, int i, int B, const float *x_dev) {
             return 0;
         }
         Conv1FParams p{};
-        p.x = x_dev;
+        p.x = in.x;
+        p.x_u8 = in.u8;
+        for (int c = 0; c < 3; ++c) { p.nmean[c] = h->norm.mean[c]; p.nstd[c] = h->norm.sd[c]; }
         p.out = h->T[o.out].dev;
         p.w = h->w0_dev;
         p.bias = L.bias_dev;
@@ -1322,10 +1397,16 @@ static int run_op(y355_net *h, int i, int B, const float *x_dev) {
         const Tensor &to = h->T[o.out];
         const size_t total = (size_t)B * to.H * to.W;
         const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-        if (h->bf)
-            hipLaunchKernelGGL(input_bf16_kernel, dim3(blocks), dim3(256), 0, s, x_dev, to.dev, B, to.H, to.W, (int)to.pb);
+        if (in.u8 && h->bf)
+            hipLaunchKernelGGL(input_u8_kernel<false>, dim3(blocks), dim3(256), 0, s, in.u8, in.tab, to.dev, B, in.sh, in.sw, to.H, to.W,
+                               (int)to.pb, h->norm, 1.0f, (Counters *)nullptr);
+        else if (in.u8)
+            hipLaunchKernelGGL(input_u8_kernel<true>, dim3(blocks), dim3(256), 0, s, in.u8, in.tab, to.dev, B, in.sh, in.sw, to.H, to.W,
+                               (int)to.pb, h->norm, std::ldexp(1.0f, h->sa_in), h->ctr_dev + i);
+        else if (h->bf)
+            hipLaunchKernelGGL(input_bf16_kernel, dim3(blocks), dim3(256), 0, s, in.x, to.dev, B, to.H, to.W, (int)to.pb);
         else
-            hipLaunchKernelGGL(input_i8_kernel, dim3(blocks), dim3(256), 0, s, x_dev, to.dev, B, to.H, to.W, (int)to.pb,
+            hipLaunchKernelGGL(input_i8_kernel, dim3(blocks), dim3(256), 0, s, in.x, to.dev, B, to.H, to.W, (int)to.pb,
                                std::ldexp(1.0f, h->sa_in), h->ctr_dev + i);
     } else if (o.type == OP_SPP) {
         const Tensor &t = h->T[o.in];
@@ -1409,15 +1490,12 @@ static HeadParams net_head_params(y355_net *h, float *ob, float *os, int *oc, in
     return p;
 }
 
-extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int flags, float *boxes_dev, float *scores_dev,
-                                int32_t *cls_dev, int32_t *count_dev) {
-    if (!h || !x_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+// the forward behind y355_net_forward and y355_net_forward_u8 (arguments checked, device set, int8 exponents refreshed)
+static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, float *boxes_dev, float *scores_dev, int32_t *cls_dev,
+                       int32_t *count_dev) {
     const bool prof = h->profile != 0;
     const int nops = h->arch->nops;
     if (!h->bf) {
-        if (int rc = refresh_i8(h)) return rc;
         bool need_zero = false;
         h->ctr_dev = h->ctrs.begin(&need_zero);        // steady state: zeroed by the previous forward's fused front end
         if (need_zero) HIPCHK((hipError_t)y355_zero_counters(h->ctr_dev, nops + 1, h->stream));
@@ -1427,6 +1505,10 @@ extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int 
     h->t0_skipped = fuse_front;
     for (int i = 0; i < nops; ++i) {
         if (prof) HIPCHK(hipEventRecord(h->ev[i], h->stream));
+        if (i == 0 && in.stage) {                       // the resize stage in front of conv1 / the fused front end
+            y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, batch, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stream);
+            HIPCHK(hipGetLastError());
+        }
         if (fuse_front && i < 2) {
             if (i == 0) {
                 if (!h->L[h->arch->ops[0].layer].loaded || !h->L[h->arch->ops[1].layer].loaded)
@@ -1434,7 +1516,9 @@ extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int 
                 if (h->bf) {
                     const OpDef &o0 = h->arch->ops[0], &o1 = h->arch->ops[1];
                     FrontBParams fb{};
-                    fb.x = x_dev;
+                    fb.x = in.x;
+                    fb.x_u8 = in.u8;                                // (frames at the network size)
+                    for (int c = 0; c < 3; ++c) { fb.nmean[c] = h->norm.mean[c]; fb.nstd[c] = h->norm.sd[c]; }
                     fb.out = h->T[o1.out].dev;
                     fb.out_pb = (int)h->T[o1.out].pb;
                     fb.wf = (const char *)h->wf_dev;
@@ -1451,7 +1535,9 @@ extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int 
                     continue;
                 }
                 FrontParams fp{};
-                fp.x = x_dev;
+                fp.x = in.x;
+                fp.x_u8 = in.u8;
+                for (int c = 0; c < 3; ++c) { fp.nmean[c] = h->norm.mean[c]; fp.nstd[c] = h->norm.sd[c]; }
                 fp.out = (int8_t *)h->T[h->arch->ops[1].out].dev;
                 fp.wf = h->wf_dev;
                 fp.bias1 = h->fb1_dev;
@@ -1471,7 +1557,7 @@ extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int 
             }
             continue;
         }
-        if (int rc = run_op(h, i, batch, x_dev)) return rc;
+        if (int rc = run_op(h, i, batch, in)) return rc;
     }
     if (prof) HIPCHK(hipEventRecord(h->ev[nops], h->stream));
     HeadParams hp = net_head_params(h, boxes_dev, scores_dev, cls_dev, count_dev);
@@ -1479,6 +1565,106 @@ extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int 
     y355_launch_head_nms(hp, batch, h->ws, h->stream, prof ? h->ev[nops + 1] : nullptr);
     HIPCHK(hipGetLastError());
     if (prof) HIPCHK(hipEventRecord(h->ev[nops + 2], h->stream));
+    return 0;
+}
+
+extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int flags, float *boxes_dev, float *scores_dev,
+                                int32_t *cls_dev, int32_t *count_dev) {
+    if (!h || !x_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (!h->bf)
+        if (int rc = refresh_i8(h)) return rc;
+    NetInput in;
+    in.x = x_dev;
+    return net_forward(h, in, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+}
+
+// BaseTransform constants of the uint8 input, in the reference's BGR order (data/__init__.py:50), as y355_set_normalization
+extern "C" int y355_net_set_normalization(y355_net *h, const float *mean_bgr, const float *std_bgr) {
+    if (!h || !mean_bgr || !std_bgr) return y355_fail(Y355_EINVAL, "null argument");
+    for (int c = 0; c < 3; ++c)
+        if (!(std_bgr[c] > 0.f)) return y355_fail(Y355_EINVAL, "std must be positive");
+    for (int c = 0; c < 3; ++c) {
+        h->norm.mean[c] = mean_bgr[2 - c];
+        h->norm.sd[c] = std_bgr[2 - c];
+    }
+    return 0;
+}
+
+// the resize stage's tables for frames of src_h x src_w (rebuilt when the source size changes) and, with `frames`, the
+// net-owned buffer of resized frames
+static int net_resize_tables(y355_net *h, int src_h, int src_w, bool frames) {
+    const int H = h->cfg.height, W = h->cfg.width;
+    if (!h->rs_tab)
+        if (int rc = nmalloc(h, (void **)&h->rs_tab, sizeof(int) * 3 * (size_t)(H + W), false)) return rc;
+    if (frames && !h->rs_frames)
+        if (int rc = nmalloc(h, (void **)&h->rs_frames, (size_t)h->cfg.max_batch * H * W * 3, false)) return rc;
+    if (h->rs_src_h != src_h || h->rs_src_w != src_w) {
+        std::vector<int> tab(3 * (size_t)(H + W));
+        y355_resize_tables(src_h, src_w, H, W, tab.data());
+        HIPCHK(hipStreamSynchronize(h->stream));          // a previous forward may still read the old tables
+        HIPCHK(hipMemcpy(h->rs_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
+        h->rs_src_h = src_h;
+        h->rs_src_w = src_w;
+    }
+    return 0;
+}
+
+// Camera frames as cv2 delivers them, uint8 HWC BGR [B][src_h][src_w][3], as the network's first input: BaseTransform
+// (data/__init__.py:30-56: resize, /255, -mean, /std), BGR->RGB and HWC->CHW (test.py:79-85) run inside the op that reads the
+// network input -- the input op of the DarkNet graphs (with the resize fused into its load), the first layer or the fused front
+// end of the slim / tiny graphs (behind the resize stage when the frames are not at the network size).  Same outputs, bit for
+// bit, as y355_net_forward on the normalised tensor of the resized frames.
+// The fused front ends load a frame row in 12-byte pieces (4 pixels), dword-aligned only when the frames pointer is: slim / tiny
+// frames at an address that is not a multiple of 4 go through the resize stage (the identity at equal sizes) into the
+// net-owned, aligned buffer.  The input op of the DarkNet graphs and the conv1 kernels read single bytes.
+extern "C" int y355_net_forward_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int flags,
+                                   float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
+    if (!h || !frames_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (!h->bf)
+        if (int rc = refresh_i8(h)) return rc;
+    const int H = h->cfg.height, W = h->cfg.width;
+    NetInput in;
+    in.u8 = frames_dev;
+    in.sh = src_h;
+    in.sw = src_w;
+    const bool fused = h->arch->ops[0].type == OP_INPUT;              // the input op resizes in its own load
+    const bool aligned = ((uintptr_t)frames_dev & 3) == 0;
+    if (src_h != H || src_w != W || (!fused && !aligned)) {
+        if (int rc = net_resize_tables(h, src_h, src_w, !fused)) return rc;
+        in.tab = h->rs_tab;
+        if (!fused) {                                                   // staged: net_forward resizes into rs_frames first
+            in.stage = frames_dev;
+            in.u8 = h->rs_frames;
+        }
+    }
+    return net_forward(h, in, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+}
+
+// parity tap of the resize stage: frames [B][src_h][src_w][3] -> out_dev [B][H][W][3] at the network size, on the net's stream
+extern "C" int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, uint8_t *out_dev) {
+    if (!h || !frames_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = net_resize_tables(h, src_h, src_w, false)) return rc;
+    y355_launch_resize_u8(frames_dev, out_dev, h->rs_tab, batch, src_h, src_w, h->cfg.height, h->cfg.width, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the evaluators' `bboxes *= [[w, h, w, h]]` (test.py:88-90) on a forward's outputs, on the net's stream, in place (as
+// y355_scale_boxes): boxes_dev [B][max_det][4], count_dev [B], wh_dev [B][2] (width, height)
+extern "C" int y355_net_scale_boxes(y355_net *h, float *boxes_dev, const int32_t *count_dev, const float *wh_dev, int batch) {
+    if (!h || !boxes_dev || !count_dev || !wh_dev) return y355_fail(Y355_EINVAL, "null argument");
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    y355_launch_scale_boxes(boxes_dev, count_dev, wh_dev, batch, h->max_det, h->stream);
+    HIPCHK(hipGetLastError());
     return 0;
 }
 

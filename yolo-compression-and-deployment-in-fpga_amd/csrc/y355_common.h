@@ -177,9 +177,11 @@ struct FrontParams {
     unsigned long long *stamps;   // diagnostic builds only (-DFRONT_DIAG=1)
     void *ev_start, *ev_stop;     // host side only: see ConvParams
 };
-// fused front end of the bf16 nets (frontb.hip): fp32 NCHW -> conv(3 -> 16) + pool -> conv(16 -> 32) + pool -> bf16 NHWC
+// fused front end of the bf16 nets (frontb.hip): fp32 NCHW (or uint8 frames) -> conv(3 -> 16) + pool -> conv(16 -> 32) + pool -> bf16 NHWC
 struct FrontBParams {
     const float *x;       // fp32 NCHW [B][3][H][W]
+    const uint8_t *x_u8;  // or (x == nullptr) uint8 HWC BGR frames [B][H][W][3]
+    float nmean[3], nstd[3];
     char *out;            // conv2's pooled output: bf16 NHWC with halo [B][H/4+2][W/4+2][out_pb bytes], channels 0..31
     int out_pb;           // bytes per output pixel (64)
     const char *wf;       // 32 KiB of weight fragments (y355_pack_frontb)
@@ -364,6 +366,41 @@ void y355_launch_absmax(const float *x, size_t n, unsigned int *out_bits, hipStr
 void y355_launch_normalize_u8(const uint8_t *frames, float *x, int B, int H, int W, const float *mean_rgb, const float *std_rgb,
                               hipStream_t s);
 
+// BaseTransform of one byte (data/__init__.py:43-45): ((u / 255) - mean) / std with the reference's fp32 operations in the
+// reference's order.  Every uint8 input route builds its per-channel 256-entry table from this one expression.
+__device__ __forceinline__ float y355_norm_u8(int u, float mean, float sd) {
+    float t = (float)u;
+    t /= 255.0f;
+    t -= mean;
+    t /= sd;
+    return t;
+}
+
+// ---- cv2.resize(image, (W, H)) of BaseTransform (data/__init__.py:36) for uint8 HWC frames (resize.hip)
+// coefficient tables of both axes, tab = [xofs dw | xa 2 dw | yofs dh | yb 2 dh] (3 (dh + dw) ints), computed on the host
+void y355_resize_tables(int sh, int sw, int dh, int dw, int *tab);
+// frames [B][sh][sw][3] -> [B][dh][dw][3], tab on the device
+void y355_launch_resize_u8(const uint8_t *src, uint8_t *dst, const int *tab, int B, int sh, int sw, int dh, int dw, hipStream_t s);
+// one output pixel (dy, dx) of that resize, three bytes in the frame's channel order: OpenCV's 8-bit fixed-point bilinear
+// (imgproc/resize.cpp: 11-bit coefficients, horizontal pass in int32, vertical pass
+// (((b0 * (D0 >> 4)) >> 16) + ((b1 * (D1 >> 4)) >> 16) + 2) >> 2), the two row indices clipped to the frame.
+// s = the frame's first byte
+__device__ __forceinline__ void y355_resize_px(const uint8_t *s, const int *tab, int sh, int sw, int dh, int dw, int dy, int dx,
+                                               int out[3]) {
+    const int *xofs = tab, *xa = tab + dw, *yofs = tab + 3 * dw, *yb = tab + 3 * dw + dh;
+    const int sx0 = xofs[dx], sx1 = min(sx0 + 1, sw - 1), a0 = xa[2 * dx], a1 = xa[2 * dx + 1];
+    const int sy0 = min(max(yofs[dy], 0), sh - 1), sy1 = min(max(yofs[dy] + 1, 0), sh - 1), b0 = yb[2 * dy], b1 = yb[2 * dy + 1];
+#pragma unroll
+    for (int c = 0; c < 3; ++c) {
+        const int d0 = (int)s[((size_t)sy0 * sw + sx0) * 3 + c] * a0 + (int)s[((size_t)sy0 * sw + sx1) * 3 + c] * a1;
+        const int d1 = (int)s[((size_t)sy1 * sw + sx0) * 3 + c] * a0 + (int)s[((size_t)sy1 * sw + sx1) * 3 + c] * a1;
+        const int v = (((b0 * (d0 >> 4)) >> 16) + ((b1 * (d1 >> 4)) >> 16) + 2) >> 2;
+        out[c] = min(max(v, 0), 255);
+    }
+}
+// the evaluators' `bboxes *= [[w, h, w, h]]` of every image, in place (engine.hip); wh [B][2]
+void y355_launch_scale_boxes(float *boxes, const int32_t *count, const float *wh, int batch, int max_det, hipStream_t s);
+
 // ---- generic chunked conv (convg.hip): bf16 nets and the int8 layers conv3x3.hip cannot hold --
 struct RequantG {
     int shl;       // t = acc * 2^shl + bias
@@ -412,6 +449,8 @@ struct ConvGParams {
 
 struct Conv1FParams {
     const float *x;       // fp32 NCHW [B][3][H][W]
+    const uint8_t *x_u8;  // or (x == nullptr) camera frames uint8 HWC BGR [B][H][W][3], normalised on the fly
+    float nmean[3], nstd[3];  // BaseTransform constants per RGB channel (data/__init__.py:50)
     char *out;            // bf16 NHWC16 with halo [B][H/2+2][W/2+2][16]
     const char *w;        // two 1 KiB fragments
     const float *bias;    // [16]

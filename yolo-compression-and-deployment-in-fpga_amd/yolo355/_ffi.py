@@ -202,6 +202,11 @@ _SIGS = {
     "y355_net_get_act_exponents": (C.c_int, [C.c_void_p, P(C.c_int32), P(C.c_int32), C.c_int]),
     "y355_net_counters": (C.c_int, [C.c_void_p, P(C.c_int64)]),
     "y355_net_forward": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_net_set_normalization": (C.c_int, [C.c_void_p, P(C.c_float), P(C.c_float)]),
+    "y355_net_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
+                                      C.c_void_p]),
+    "y355_net_resize_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p]),
+    "y355_net_scale_boxes": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_int]),
     "y355_net_get_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "y355_net_get_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "y355_net_tensor_absmax": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_float)]),

@@ -309,25 +309,47 @@ class _NetModel(nn.Module):
         self.input_size = list(input_size)
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
 
-    def forward_batch(self, x, quantization=False):
-        """Every image of the batch.  quantization=True (YOLOv3tiny, YOLOv2, YOLOv3, YOLOv3-SPP) runs the int8 engine:
-        weights quantized per tensor to power-of-two int8 after the BN fold, activation exponents
-        frozen at the first quantized call from the bf16 run of that input -- the first-call rule of
-        AveragedRangeTracker (models/slim_yolo_v2.py:25-27) applied to this graph."""
+    def _check_inference(self):
         if self.trainable:
             raise NotImplementedError("yolo355 is an inference engine: the training branch is out of scope")
         if self.training and any(isinstance(m, nn.BatchNorm2d) for m in self.modules()):
             raise NotImplementedError("yolo355 folds BatchNorm with its running statistics: call .eval() first")
+
+    def forward_batch(self, x, quantization=False, sizes_wh=None):
+        """Every image of the batch.  quantization=True (YOLOv3tiny, YOLOv2, YOLOv3, YOLOv3-SPP) runs the int8 engine:
+        weights quantized per tensor to power-of-two int8 after the BN fold, activation exponents
+        frozen at the first quantized call from the bf16 run of that input -- the first-call rule of
+        AveragedRangeTracker (models/slim_yolo_v2.py:25-27) applied to this graph.
+        sizes_wh: [B,2] original (width, height) per image: the boxes come back in pixels of the original images
+        (the evaluators' `bboxes *= [[w, h, w, h]]`, test.py:88-90, on the GPU)."""
+        self._check_inference()
         net = self._get_net(int(x.shape[0]))
         if not quantization:
             net.set_thresholds(self.conf_thresh, self.nms_thresh)
-            return net.forward(x)
+            return net.forward(x, sizes_wh=sizes_wh)
         if self.act_exponents is None:
             self.act_exponents = net.calibration_exponents(x)
         qnet = self._get_net(int(x.shape[0]), int8=True)
         qnet.set_act_exponents(*self.act_exponents)
         qnet.set_thresholds(self.conf_thresh, self.nms_thresh)
-        return qnet.forward(x)
+        return qnet.forward(x, sizes_wh=sizes_wh)
+
+    def forward_frames(self, frames, quantization=False, sizes_wh=None):
+        """New: detections for camera frames as cv2 delivers them, uint8 [B,h,w,3] BGR of any size.
+        BaseTransform (data/__init__.py:30-56), BGR->RGB and HWC->CHW (test.py:79-85) run on the GPU inside the op that
+        reads the network input; element i equals forward_batch of the tensor the reference's transform makes of frame
+        i, bit for bit.  quantization=True needs the frozen activation exponents: run one
+        forward_batch(x, quantization=True) first.  sizes_wh as forward_batch."""
+        Net.check_frames(frames)
+        self._check_inference()
+        if quantization and self.act_exponents is None:
+            raise RuntimeError("yolo355: the int8 activation exponents are not frozen yet: run one "
+                               "forward_batch(x, quantization=True) first")
+        net = self._get_net(int(frames.shape[0]), int8=bool(quantization))
+        if quantization:
+            net.set_act_exponents(*self.act_exponents)
+        net.set_thresholds(self.conf_thresh, self.nms_thresh)
+        return net.forward_frames(frames, sizes_wh=sizes_wh)
 
     def _weights_version(self):
         t = list(self.parameters()) + list(self.buffers())

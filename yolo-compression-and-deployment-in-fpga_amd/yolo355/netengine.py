@@ -149,11 +149,18 @@ class Net:
             cur.wait_stream(self._stream)
         return ob, os_, oc, on
 
-    def forward(self, x, tap=False):
-        """list of (bboxes [n,4], scores [n], cls_inds int64 [n]) per image, anchor-index order."""
+    def forward(self, x, tap=False, sizes_wh=None):
+        """list of (bboxes [n,4], scores [n], cls_inds int64 [n]) per image, anchor-index order.
+        sizes_wh: [B,2] original (width, height) per image -- the evaluators' `bboxes *= [[w, h, w, h]]` on the GPU."""
         xd = self._dev_input(x)
         B = xd.shape[0]
-        ob, os_, oc, on = self.forward_device(xd, _ffi.F_TAP if tap else 0)
+        out = self.forward_device(xd, _ffi.F_TAP if tap else 0)
+        return self._collect(B, out, sizes_wh)
+
+    def _collect(self, B, out, sizes_wh=None):
+        ob, os_, oc, on = out
+        if sizes_wh is not None:
+            self.scale_boxes(ob, on, sizes_wh, B)
         n = on[:B].cpu().numpy()
         if self.overflow():
             raise _ffi.Y355Error(-1,
@@ -161,6 +168,83 @@ class Net:
         boxes, scores, cls = ob[:B].cpu().numpy(), os_[:B].cpu().numpy(), oc[:B].cpu().numpy()
         return [(boxes[i, :n[i]].copy(), scores[i, :n[i]].copy(), cls[i, :n[i]].astype(np.int64))
                 for i in range(B)]
+
+    @staticmethod
+    def check_frames(frames):
+        """uint8 [B,h,w,3] (numpy or torch), checked before any device work"""
+        if not isinstance(frames, (np.ndarray, torch.Tensor)):
+            raise ValueError("frames must be a numpy array or a torch tensor, got %s" % type(frames).__name__)
+        dt = frames.dtype
+        if not (dt == np.uint8 if isinstance(frames, np.ndarray) else dt == torch.uint8):
+            raise ValueError("frames must be uint8, got %s" % (dt,))
+        if len(frames.shape) != 4 or frames.shape[3] != 3:
+            raise ValueError("frames must be [B,h,w,3] (HWC BGR), got %s" % (tuple(frames.shape),))
+        if frames.shape[0] < 1 or frames.shape[1] < 1 or frames.shape[2] < 1:
+            raise ValueError("empty frames %s" % (tuple(frames.shape),))
+
+    def _dev_frames(self, frames):
+        self.check_frames(frames)
+        if isinstance(frames, np.ndarray):
+            frames = torch.from_numpy(np.ascontiguousarray(frames))
+        if frames.shape[0] > self.max_batch:
+            raise ValueError("batch %d > max_batch %d" % (frames.shape[0], self.max_batch))
+        return frames.to(self.device).contiguous()
+
+    def _call(self, fn, *args):
+        # stream ordering as forward_device
+        cur = torch.cuda.current_stream(self.device)
+        if cur != self._stream:
+            self._stream.wait_stream(cur)
+        _ffi.check(fn(self._h, *args))
+        if cur != self._stream:
+            cur.wait_stream(self._stream)
+
+    def forward_frames_device(self, frames, flags=0, out=None):
+        """Asynchronous batched forward on camera frames: CUDA uint8 [B,h,w,3] BGR of any size (y355_net_forward_u8:
+        BaseTransform's resize, normalisation, BGR->RGB and HWC->CHW inside the op that reads the network input).
+        Returns the device tensors of forward_device."""
+        if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+            raise ValueError("expected a CUDA uint8 tensor [B,h,w,3]")
+        self.check_frames(frames)
+        frames = frames.contiguous()
+        B, hh, ww = (int(v) for v in frames.shape[:3])
+        if B > self.max_batch:
+            raise ValueError("batch %d > max_batch %d" % (B, self.max_batch))
+        ob, os_, oc, on = out if out is not None else self._buffers(B)
+        self._call(self._lib.y355_net_forward_u8, frames.data_ptr(), hh, ww, B, int(flags), ob.data_ptr(), os_.data_ptr(),
+                   oc.data_ptr(), on.data_ptr())
+        return ob, os_, oc, on
+
+    def forward_frames(self, frames, tap=False, sizes_wh=None):
+        """frames: uint8 [B,h,w,3] BGR (numpy or torch, any size).  Same return as forward() on
+        synth.normalize_frames(resize_linear_u8(frames)) -- bit for bit."""
+        fd = self._dev_frames(frames)
+        B = fd.shape[0]
+        out = self.forward_frames_device(fd, _ffi.F_TAP if tap else 0)
+        return self._collect(B, out, sizes_wh)
+
+    def resize_frames(self, frames):
+        """cv2.resize(image, (W, H)) of BaseTransform for uint8 [B,h,w,3] frames on the GPU (the stage in front of the
+        network); returns a CUDA uint8 tensor [B,H,W,3]."""
+        fd = self._dev_frames(frames)
+        B = fd.shape[0]
+        out = torch.empty((B, self.input_size[0], self.input_size[1], 3), dtype=torch.uint8, device=self.device)
+        self._call(self._lib.y355_net_resize_u8, fd.data_ptr(), int(fd.shape[1]), int(fd.shape[2]), B, out.data_ptr())
+        return out
+
+    def set_normalization(self, mean_bgr, std_bgr):
+        """BaseTransform constants of the frame input, in the reference's BGR order."""
+        m = (C.c_float * 3)(*[float(v) for v in mean_bgr])
+        sd = (C.c_float * 3)(*[float(v) for v in std_bgr])
+        _ffi.check(self._lib.y355_net_set_normalization(self._h, m, sd))
+
+    def scale_boxes(self, boxes, count, sizes_wh, batch=None):
+        """In place on a forward's device outputs: boxes[b, :count[b]] *= [w, h, w, h] with sizes_wh [B,2] (width, height)."""
+        wh = torch.as_tensor(np.asarray(sizes_wh, np.float32).reshape(-1, 2)).to(self.device)
+        B = wh.shape[0] if batch is None else int(batch)
+        if wh.shape[0] != B:
+            raise ValueError("sizes_wh has %d rows for a batch of %d" % (wh.shape[0], B))
+        self._call(self._lib.y355_net_scale_boxes, boxes.data_ptr(), count.data_ptr(), wh.data_ptr(), B)
 
     def overflow(self):
         """True if a forward since the last call dropped candidates (heads with more than 4096 anchors per image)."""

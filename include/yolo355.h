@@ -489,6 +489,19 @@ int y355_net_load_layer_f32(y355_net *h, int idx, const float *w, const float *b
  * Their clamps count in y355_net_counters. */
 int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin,
                            int ksize, int e_w, int e_b);
+/* The same with one power-of-two weight scale per output channel (quantize_tensor(channel_level=True),
+ * retune_bias_quantize.py:73-86): e_w [cout], value of a weight of channel c = q_w / 2^e_w[c], |q_w| <= 127.  The bias keeps
+ * ONE exponent e_b (the reference's per-element bias scales would let a near-zero bias push every shift out of range).
+ * Integer rule, with E = max_c e_w[c]:
+ *   F = max(sa_in + E, e_b),  shl[c] = F - sa_in - e_w[c],  t = acc * 2^shl[c] + q_b[c] * 2^(F - e_b)
+ * and everything after t is the per-tensor rule unchanged (slope neg_mul / 2^lk, sh = F + lk - sa_out, RNE, clamp, the
+ * residual rule, the pooled forms, the clamp counts).  So equal e_w[c] give the integers of y355_net_load_layer_i8, and a
+ * per-channel layer equals the per-tensor layer with the widened integer weights q_w[c] * 2^(E - e_w[c]) at exponent E.
+ * Range proofs run per channel on max_c (127 * sum|q_w[c]| * 2^shl[c]); shl[c] > 24 is Y355_ERANGE at the forward.
+ * |e_w[c]| <= 128.  On SlimYOLOv2 / YOLOv3tiny a layer whose exponents differ takes the first two layers off the fused
+ * front end (its epilogue has one shift per layer): they run one by one, as in a tap forward. */
+int y355_net_load_layer_i8_pc(y355_net *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin,
+                              int ksize, const int32_t *e_w, int e_b);
 /* activation exponents (value = q / 2^sa): sa_in for the network input, sa[t] per activation tensor in
  * graph order; a max-pool output takes its input's exponent and the DarkNet graphs' input tensor sa_in
  * (their entries are overridden), a concat buffer (and the in-place SPP buffer) has one exponent.  get
@@ -538,6 +551,21 @@ int y355_net_debug_nms(y355_net *h, int batch, int32_t *count, int32_t *nedges);
 /* heads with more than 4096 anchors per image (yolo_v3 at 416 x 416): *overflow = 1 if, in a forward since the last call, more
  * than 4096 anchors of an image passed conf_thresh (the excess was dropped: raise the threshold); synchronous; clears the flag */
 int y355_net_overflow(y355_net *h, int *overflow);
+/* debug: the kernel the convolution of weight slot idx ran on in the last forward that reached it (0: it has not run), for
+ * bf16 and int8 nets: one family ... */
+#define Y355_ROUTE_FIRST 1        /* first-layer kernel (conv1.hip) */
+#define Y355_ROUTE_FRONT 2        /* fused front end of SlimYOLOv2 / YOLOv3tiny (front.hip), both layers in one launch */
+#define Y355_ROUTE_RING 3         /* 3x3 ring kernel (convr.hip) */
+#define Y355_ROUTE_POINTWISE 4    /* 1x1 pointwise kernel (convr.hip) */
+#define Y355_ROUTE_GENERIC4 5     /* convg_kernel (convg.hip, four waves) */
+#define Y355_ROUTE_GENERIC8 6     /* convg8_kernel (convg.hip, eight waves) */
+#define Y355_ROUTE_THIN 7         /* bf16 thin 3x3 layer with the weights in registers (convpxb.hip) */
+#define Y355_ROUTE_FAMILY 0xff
+/* ... or-ed with (int8 nets only; a bf16 net reports the family alone): */
+#define Y355_ROUTE_EPI64 0x100        /* the 64-bit epilogue (otherwise the 32-bit one) */
+#define Y355_ROUTE_RESIDUAL 0x200     /* with the residual added in the epilogue */
+#define Y355_ROUTE_PER_CHANNEL 0x400  /* the layer's weight exponents differ between output channels */
+int y355_net_layer_route(y355_net *h, int idx, int32_t *route);
 int y355_net_profile(y355_net *h, int enable);
 int y355_net_num_timers(y355_net *h);          /* ops + head decode + NMS */
 int y355_net_profile_get(y355_net *h, float *ms);

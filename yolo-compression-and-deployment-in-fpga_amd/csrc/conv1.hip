@@ -108,7 +108,8 @@ __global__ __launch_bounds__(256) void conv1_kernel(const Conv1Params p) {
     T bias;
     if constexpr (WIDE) bias = p.bias_w[li];
     else bias = p.bias_t[li];
-    const Requant rq = p.rq;
+    Requant rq = p.rq;
+    if (p.shl_c) rq.shl = p.shl_c[li];              // per-channel weight exponents (y355_net): the shift is the lane's own
     const U gthr = (!p.guard || rq.guard_log2 >= (WIDE ? 63 : 31)) ? ~(U)0 : ((U)1 << rq.guard_log2);
     const int Ho = H >> 1, Wo = W >> 1;
     U amax = 0;
@@ -316,7 +317,10 @@ __global__ __launch_bounds__(256) void conv1_fast_kernel(const Conv1Params p) {
     const int li = lane & 15, g = lane >> 4;
     const v4i bw = *(const v4i *)(p.w + lane * 16);
     const int bias = p.bias_t[li];
-    const Requant rq = p.rq;
+    Requant rq = p.rq;
+    if constexpr (GEN) {                            // y355_net: per-channel weight exponents, the shift is the lane's own
+        if (p.shl_c) rq.shl = p.shl_c[li];
+    }
     const int Ho = H >> 1, Wo = W >> 1;
     unsigned int nsat = 0;
     // sh_l (a left requant shift; sh_r = 0 then) folded into the accumulator shift and the bias; saturation is

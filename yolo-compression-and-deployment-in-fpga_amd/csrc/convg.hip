@@ -22,18 +22,24 @@ typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 
 // integer epilogue with a general LeakyReLU slope neg_mul / 2^lk (DESIGN.md "requantisation"):
 //   t = acc * 2^shl + bias;  t' = t >= 0 ? t * 2^lk : t * neg_mul;  q = clamp(RNE(t' * 2^-sh))
-__device__ __forceinline__ long long requant_g(int acc, long long bias, const RequantG &rq) {
-    long long t = (long long)acc * (1ll << rq.shl) + bias;
+// shl: the output channel's own shift (per-channel weight exponents), a per-lane value
+__device__ __forceinline__ long long requant_g(int acc, int shl, long long bias, const RequantG &rq) {
+    long long t = (long long)acc * (1ll << shl) + bias;
     t = t >= 0 ? t * (1ll << rq.lk) : t * (long long)rq.neg_mul;
     return y355_rne_shift<long long>(t, rq.sh);
 }
 
 // the same with the int8 residual added before the one rounding (ResQ, y355_common.h)
-__device__ __forceinline__ long long requant_g_res(int acc, long long bias, const RequantG &rq, int qr, const ResQ &rr) {
-    long long t = (long long)acc * (1ll << rq.shl) + bias;
+__device__ __forceinline__ long long requant_g_res(int acc, int shl, long long bias, const RequantG &rq, int qr, const ResQ &rr) {
+    long long t = (long long)acc * (1ll << shl) + bias;
     t = t >= 0 ? t * (1ll << rq.lk) : t * (long long)rq.neg_mul;
     const long long u = t * (1ll << rr.t_sh) + (long long)qr * (1ll << rr.r_sh);
     return y355_rne_shift<long long>(u, rr.sh);
+}
+// (the p_* / n_* shifts come from F = max(sa_in + max_c e_w, e_b), lk and the activation exponents: none depends on shl[c])
+__device__ __forceinline__ int requant_gen32_res_t(int t, const Requant &rq, int qr, const ResQ &rr) {
+    if (t >= 0) return y355_rne_shift32(t * (1 << rr.p_t) + qr * (1 << rr.p_r), rr.p_d);
+    return y355_rne_shift32(t * rq.neg_mul * (1 << rr.n_t) + qr * (1 << rr.n_r), rr.n_d);
 }
 __device__ __forceinline__ int requant_gen32_res(int acc, int bias, const Requant &rq, int qr, const ResQ &rr) {
     const int t = (acc << rq.shl) + bias;
@@ -61,7 +67,9 @@ __device__ __forceinline__ void load_res_i8(const char *src, int (&r)[NT]) {
 
 // ---- four waves per workgroup (round 1): one tile per workgroup, stage -> barrier -> k-steps -> barrier per chunk.  Kept for
 // the thin layers and the small / stride-2 tiles, where its 2-3 workgroups per CU overlap each other's phases.
-template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false>
+// PC: the layer's weight exponents differ between output channels (ConvGParams::pc): the accumulator shift is the lane's own
+// (bias word / shl_w); otherwise rq.shl, wave-uniform, and the code of the per-tensor layers is what it was
+template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false>
 __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
     constexpr bool THIN = (CHB == 32);           // 32 B per pixel: a k-step covers two taps
     // input patch of a TH x TW output tile: S*(T-1)+3 pixels a side (stride S, 3x3, pad 1)
@@ -223,6 +231,11 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
     int biasn[NT];                                         // NARROW: the biases fit 32 bits too
 #pragma unroll
     for (int t = 0; t < NT; ++t) biasn[t] = (int)biasw[t];
+    int shlw[PC ? NT : 1] = {};                                         // PC, 64-bit epilogue: the channel's shift (NARROW: in the upper half of biasw, y355_pc_word)
+    if constexpr (PC && !NARROW && !BF) {
+#pragma unroll
+        for (int t = 0; t < NT; ++t) shlw[t] = p.shl_w[nlane + t];
+    }
     const float slope = p.slope;
     const RequantG rq = p.rq;
     Requant rqn{};
@@ -260,11 +273,11 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     if constexpr (NARROW) {
-                        const int qq = requant_gen32_res(vi[t], biasn[t], rqn, qr[t], p.rr);
+                        const int qq = PC ? requant_gen32_res_t(y355_pc_t(vi[t], biasw[t]), rqn, qr[t], p.rr) : requant_gen32_res(vi[t], biasn[t], rqn, qr[t], p.rr);
                         q[t] = y355_clamp8<int>(qq);
                         nsat += (valid && q[t] != qq) ? 1u : 0u;
                     } else {
-                        const long long qq = requant_g_res(vi[t], biasw[t], rq, qr[t], p.rr);
+                        const long long qq = requant_g_res(vi[t], PC ? shlw[PC ? t : 0] : rq.shl, biasw[t], rq, qr[t], p.rr);
                         q[t] = y355_clamp8<long long>(qq);
                         nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
                     }
@@ -273,11 +286,11 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
 #pragma unroll
                 for (int t = 0; t < NT; ++t) {
                     if constexpr (NARROW) {
-                        const int qq = y355_requant_gen32(vi[t], biasn[t], rqn);
+                        const int qq = PC ? y355_requant_gen32_t(y355_pc_t(vi[t], biasw[t]), rqn) : y355_requant_gen32(vi[t], biasn[t], rqn);
                         q[t] = y355_clamp8<int>(qq);
                         nsat += (valid && q[t] != qq) ? 1u : 0u;
                     } else {
-                        const long long qq = requant_g(vi[t], biasw[t], rq);
+                        const long long qq = requant_g(vi[t], PC ? shlw[PC ? t : 0] : rq.shl, biasw[t], rq);
                         q[t] = y355_clamp8<long long>(qq);
                         nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
                     }
@@ -338,7 +351,7 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
 // (58.2 k / 49.2 k): the extra live state spills, and one 8-wave workgroup per CU has nothing to overlap its epilogue with.
 // What bounds this kernel now is the B path: 16-32 KB of fragments per k-step per CU through the vector-memory pipe
 // (profiles/r02_notes.md); the int8 ring kernels avoid exactly that with LDS-DMA weight rings.
-template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false>
+template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false>
 __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams p, const int total) {
     constexpr int NTHR = WM * WN * 64;
     constexpr bool THIN = (CHB == 32);           // 32 B per pixel: a k-step covers two taps
@@ -529,9 +542,14 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
             if constexpr (BF) { biasf[t] = p.bias_f[nlane + t]; biasw[t] = 0; }
             else { biasw[t] = p.bias_w[nlane + t]; biasf[t] = 0.f; }
         }
-        int biasn[NT];                                     // NARROW: the biases fit 32 bits too
+        int biasn[NT];                                         // NARROW: the biases fit 32 bits too
 #pragma unroll
         for (int t = 0; t < NT; ++t) biasn[t] = (int)biasw[t];
+        int shlw[PC ? NT : 1] = {};                                     // PC, 64-bit epilogue: the channel's shift (NARROW: in the upper half of biasw, y355_pc_word)
+        if constexpr (PC && !NARROW && !BF) {
+#pragma unroll
+            for (int t = 0; t < NT; ++t) shlw[t] = p.shl_w[nlane + t];
+        }
         Requant rqn{};
         rqn.shl = rq.shl; rqn.sh = rq.sh; rqn.lk = rq.lk; rqn.neg_mul = rq.neg_mul; rqn.split = rq.split;
 
@@ -567,11 +585,11 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         if constexpr (NARROW) {
-                            const int qq = requant_gen32_res(vi[t], biasn[t], rqn, qr[t], p.rr);
+                            const int qq = PC ? requant_gen32_res_t(y355_pc_t(vi[t], biasw[t]), rqn, qr[t], p.rr) : requant_gen32_res(vi[t], biasn[t], rqn, qr[t], p.rr);
                             q[t] = y355_clamp8<int>(qq);
                             nsat += (valid && q[t] != qq) ? 1u : 0u;
                         } else {
-                            const long long qq = requant_g_res(vi[t], biasw[t], rq, qr[t], p.rr);
+                            const long long qq = requant_g_res(vi[t], PC ? shlw[PC ? t : 0] : rq.shl, biasw[t], rq, qr[t], p.rr);
                             q[t] = y355_clamp8<long long>(qq);
                             nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
                         }
@@ -580,11 +598,11 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         if constexpr (NARROW) {
-                            const int qq = y355_requant_gen32(vi[t], biasn[t], rqn);
+                            const int qq = PC ? y355_requant_gen32_t(y355_pc_t(vi[t], biasw[t]), rqn) : y355_requant_gen32(vi[t], biasn[t], rqn);
                             q[t] = y355_clamp8<int>(qq);
                             nsat += (valid && q[t] != qq) ? 1u : 0u;
                         } else {
-                            const long long qq = requant_g(vi[t], biasw[t], rq);
+                            const long long qq = requant_g(vi[t], PC ? shlw[PC ? t : 0] : rq.shl, biasw[t], rq);
                             q[t] = y355_clamp8<long long>(qq);
                             nsat += (valid && (long long)q[t] != qq) ? 1u : 0u;
                         }
@@ -645,35 +663,44 @@ struct ConvGInst {
     static void launch(const ConvGParams &p, int nblocks, hipStream_t s) {
         if constexpr (EIGHT) {
             // one tile per workgroup (persistent workgroups measured slower: slim fp32, B = 64, 58.2 k vs 63.8 k img/s)
-            if (!BF && p.rq.narrow)
-                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>), dim3(nblocks), dim3(512),
-                                   p.nchunks > 1 ? 2 * SLAB : SLAB, s, p, nblocks);
+            const size_t lds = p.nchunks > 1 ? 2 * SLAB : SLAB;
+            if (!BF && p.rq.narrow && p.pc)
+                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
+            else if (!BF && p.rq.narrow)
+                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
+            else if (!BF && p.pc)
+                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
             else
-                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>), dim3(nblocks), dim3(512),
-                                   p.nchunks > 1 ? 2 * SLAB : SLAB, s, p, nblocks);
+                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
         } else {
-            if (!BF && p.rq.narrow)
+            if (!BF && p.rq.narrow && p.pc)
+                hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>), dim3(nblocks), dim3(256), SLAB, s, p);
+            else if (!BF && p.rq.narrow)
                 hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>), dim3(nblocks), dim3(256), SLAB, s, p);
+            else if (!BF && p.pc)
+                hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>), dim3(nblocks), dim3(256), SLAB, s, p);
             else
                 hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>), dim3(nblocks), dim3(256), SLAB, s, p);
         }
     }
     static int prepare() {
-        const void *fn;
+        const int lds = (int)LDS;
+        auto set = [&](const void *fn) { return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds); };
         if constexpr (EIGHT) {
-            fn = (const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>;
             if constexpr (!BF) {
-                if (int e = (int)hipFuncSetAttribute((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS)) return e;
+                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>)) return e;
+                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>)) return e;
+                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>)) return e;
             }
+            return set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>);
         } else {
-            fn = (const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>;
             if constexpr (!BF) {
-                if (int e = (int)hipFuncSetAttribute((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>,
-                                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS)) return e;
+                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>)) return e;
+                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>)) return e;
+                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>)) return e;
             }
+            return set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>);
         }
-        return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS);
     }
     static constexpr ConvGInfo info() {
         return ConvGInfo{BF ? 1 : 0, CHB, BN, TH, TW, POOL ? 1 : 0, WM, WN, BN / 16 / WN, S, LDS, &launch, &prepare};

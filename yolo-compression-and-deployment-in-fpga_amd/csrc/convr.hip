@@ -332,13 +332,13 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void convr_kernel(const ConvGParam
             char *snk = sink + tid * 16;
             float biasf[NT];
             long long biasw[NT];
-            int biasn[NT];
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
+            for (int t = 0; t < NT; ++t) {            // int8: y355_pc_word(shl[c], bias[c]), the channel's shift in the word's upper half
                 if constexpr (BF) { biasf[t] = p.bias_f[nlane + t]; biasw[t] = 0; }
                 else { biasw[t] = p.bias_w[nlane + t]; biasf[t] = 0.f; }
-                biasn[t] = (int)biasw[t];
             }
+            // one point where all the words are live: their loads retire behind ONE wait, as when only the low halves were used
+            if constexpr (!BF) asm volatile("" : "+v"(biasw[0]), "+v"(biasw[1]), "+v"(biasw[2]), "+v"(biasw[3]));
             Requant rqn{};
             rqn.shl = rq.shl; rqn.sh = rq.sh; rqn.lk = rq.lk; rqn.neg_mul = rq.neg_mul; rqn.split = rq.split;
             auto finish = [&](const float (&vf)[NT], const int (&vi)[NT], bool valid, int oy, int ox) {
@@ -368,7 +368,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void convr_kernel(const ConvGParam
 #pragma unroll
                     for (int t = 0; t < NT; ++t) {
                         if constexpr (NARROW) {
-                            const int qq = y355_requant_gen32(vi[t], biasn[t], rqn);
+                            const int qq = y355_requant_gen32_t(y355_pc_t(vi[t], biasw[t]), rqn);
                             q[t] = y355_clamp8<int>(qq);
                             nsat += (valid && q[t] != qq) ? 1u : 0u;
                         } else {
@@ -433,7 +433,9 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void convr_kernel(const ConvGParam
 // block of 64 output channels in LDS (all k-steps), a wave takes 16 consecutive pixels of the batch at a time, reads their
 // channels straight from global memory as A fragments (all k-steps in flight together) and stores four adjacent channels of
 // four pixels per lane.  Fragment and k order are convg.hip's, the epilogue is its 32-bit general-slope form: bit-identical.
-template <int MAXKS>
+// PC: the layer's weight exponents differ between output channels (ConvGParams::pc): the shift comes from the bias word,
+// per lane; otherwise rq.shl, wave-uniform, and the per-tensor layers run the code they always ran
+template <int MAXKS, bool PC = false>
 __global__ __launch_bounds__(256) void pw_i8_kernel(const ConvGParams p, const int npix, const int ks_n) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -443,9 +445,18 @@ __global__ __launch_bounds__(256) void pw_i8_kernel(const ConvGParams p, const i
     for (int i = tid; i < ks_n * 4 * 64; i += 256) *(v4i *)(smem + i * 16) = *(const v4i *)(wsrc + (size_t)i * 16);
     __syncthreads();
     const int H = p.H, W = p.W, HW = H * W;
-    int biasn[4];
+    int biasn[4], shln[4];                                 // y355_pc_word(shl[c], bias[c])
 #pragma unroll
-    for (int t = 0; t < 4; ++t) biasn[t] = (int)p.bias_w[nb * 64 + li * 4 + t];
+    for (int t = 0; t < 4; ++t) {
+        if constexpr (PC) {
+            const long long w = p.bias_w[nb * 64 + li * 4 + t];
+            biasn[t] = (int)w;
+            shln[t] = (int)(w >> 32);
+        } else {
+            biasn[t] = (int)p.bias_w[nb * 64 + li * 4 + t];
+            shln[t] = 0;
+        }
+    }
     Requant rqn{};
     rqn.shl = p.rq.shl; rqn.sh = p.rq.sh; rqn.lk = p.rq.lk; rqn.neg_mul = p.rq.neg_mul; rqn.split = p.rq.split;
     unsigned int nsat = 0;
@@ -482,7 +493,7 @@ __global__ __launch_bounds__(256) void pw_i8_kernel(const ConvGParams p, const i
             int q[4];
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
-                const int qq = y355_requant_gen32(acc[t][rr], biasn[t], rqn);
+                const int qq = PC ? y355_requant_gen32_t((acc[t][rr] << shln[t]) + biasn[t], rqn) : y355_requant_gen32(acc[t][rr], biasn[t], rqn);
                 q[t] = y355_clamp8<int>(qq);
                 nsat += q[t] != qq ? 1u : 0u;
             }
@@ -501,8 +512,13 @@ bool y355_launch_pw_i8(const ConvGParams &p, hipStream_t s) {
     int per_nb = (npix + 63) / 64;                               // workgroups per n-block: 64 pixels per pass of its four waves
     if (per_nb * p.nblk > 2048) per_nb = 2048 / p.nblk;
     const size_t lds = (size_t)ks_n * 4 * 1024;
-    if (ks_n <= 8) hipLaunchKernelGGL(pw_i8_kernel<8>, dim3(per_nb * p.nblk), dim3(256), lds, s, p, npix, ks_n);
-    else hipLaunchKernelGGL(pw_i8_kernel<16>, dim3(per_nb * p.nblk), dim3(256), lds, s, p, npix, ks_n);
+    if (p.pc) {
+        if (ks_n <= 8) hipLaunchKernelGGL((pw_i8_kernel<8, true>), dim3(per_nb * p.nblk), dim3(256), lds, s, p, npix, ks_n);
+        else hipLaunchKernelGGL((pw_i8_kernel<16, true>), dim3(per_nb * p.nblk), dim3(256), lds, s, p, npix, ks_n);
+    } else {
+        if (ks_n <= 8) hipLaunchKernelGGL(pw_i8_kernel<8>, dim3(per_nb * p.nblk), dim3(256), lds, s, p, npix, ks_n);
+        else hipLaunchKernelGGL(pw_i8_kernel<16>, dim3(per_nb * p.nblk), dim3(256), lds, s, p, npix, ks_n);
+    }
     return true;
 }
 

@@ -227,7 +227,14 @@ struct NLayer {
     size_t w_bytes = 0;
     // int8 nets
     std::vector<int32_t> q_b;
-    int e_w = 0, e_b = 0;
+    int e_w = 0, e_b = 0;     // e_w: the largest of e_wc
+    // weight exponent and sum |q_w| of every output channel (y355_net_load_layer_i8_pc; one value repeated by the per-tensor
+    // load), pc: they differ.  shl_dev [cout_pad]: shl[c] = F - sa_in - e_wc[c] for the 64-bit epilogues and conv1.hip
+    std::vector<int> e_wc;
+    std::vector<long long> wabs_c;
+    bool pc = false;
+    int *shl_dev = nullptr;
+    int route = 0;            // y355_net_layer_route: the kernel the last forward ran this layer on
     long long *bias_w_dev = nullptr;
     RequantG rq{};
     ResQ rr{};                // residual layers (OpDef::res1)
@@ -773,6 +780,7 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
         }
         if (!rc) rc = nmalloc(h, (void **)&L.bias_dev, sizeof(float) * L.cout_pad, true);
         if (!rc) rc = nmalloc(h, (void **)&L.bias_w_dev, sizeof(long long) * L.cout_pad, true);
+        if (!rc && !h->bf) rc = nmalloc(h, (void **)&L.shl_dev, sizeof(int) * L.cout_pad, true);
     }
     if (!rc && A.nops >= 2) {
         const OpDef &o0 = A.ops[0], &o1 = A.ops[1];
@@ -929,8 +937,9 @@ extern "C" int y355_net_load_layer_f32(y355_net *h, int idx, const float *w, con
 
 // replaces load_state_dict of a checkpoint written by quantize_layers (retune_bias_quantize.py:111-119)
 // for one conv of an int8 net: q_w int8 [cout][cin][k][k] (value q_w / 2^e_w), q_b int32 [cout]
-extern "C" int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin,
-                                      int ksize, int e_w, int e_b) {
+// e_wc: one weight exponent per output channel, or null: e_w for all of them
+static int load_layer_i8(y355_net *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin, int ksize,
+                         const int32_t *e_wc, int e_w, int e_b) {
     if (!h || !q_w || !q_b) return y355_fail(Y355_EINVAL, "null argument");
     if (idx < 0 || idx >= h->arch->nlayers) return y355_fail(Y355_EINVAL, "layer index out of range");
     if (h->bf) return y355_fail(Y355_EINVAL, "int8 weights go to an int8 net");
@@ -941,6 +950,8 @@ extern "C" int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, c
                  cout, cin, ksize, ksize);
         return y355_fail(Y355_EINVAL, buf);
     }
+    for (int c = 0; e_wc && c < cout; ++c)                     // (cout is the layer's own by now)
+        if (e_wc[c] < -128 || e_wc[c] > 128) return y355_fail(Y355_EINVAL, "weight exponent out of range");
     HIPCHK(hipSetDevice(h->cfg.device_id));
     HIPCHK(hipStreamSynchronize(h->stream));
     const OpDef &o = h->arch->ops[L.op];
@@ -973,14 +984,19 @@ extern "C" int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, c
         h->front_dirty = true;
     }
     L.q_b.assign(q_b, q_b + cout);
-    L.e_w = e_w;
+    L.e_wc.assign(cout, e_w);
+    if (e_wc) L.e_wc.assign(e_wc, e_wc + cout);
+    L.e_w = *std::max_element(L.e_wc.begin(), L.e_wc.end());
+    L.pc = *std::min_element(L.e_wc.begin(), L.e_wc.end()) != L.e_w;
     L.e_b = e_b;
-    {   // max over output channels of sum |q_w|: the layer's own bound on |acc| (127 * wabs) for the 32-bit-epilogue test
+    {   // sum |q_w| of every output channel and its maximum: the layer's own bound on |acc| (127 * wabs) for the 32-bit-epilogue test
         long long wabs = 0;
         const size_t per = (size_t)cin * ksize * ksize;
+        L.wabs_c.assign(cout, 0);
         for (int c = 0; c < cout; ++c) {
             long long s = 0;
             for (size_t k = 0; k < per; ++k) s += std::abs((int)q_w[(size_t)c * per + k]);
+            L.wabs_c[c] = s;
             wabs = std::max(wabs, s);
         }
         L.wabs = wabs;
@@ -990,6 +1006,31 @@ extern "C" int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, c
     return 0;
 }
 
+extern "C" int y355_net_load_layer_i8(y355_net *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin,
+                                      int ksize, int e_w, int e_b) {
+    return load_layer_i8(h, idx, q_w, q_b, cout, cin, ksize, nullptr, e_w, e_b);
+}
+
+// the same with one power-of-two weight scale per output channel (quantize_tensor(channel_level=True),
+// retune_bias_quantize.py:73-86): value of a weight of channel c = q_w / 2^e_w[c]; the bias keeps one exponent
+extern "C" int y355_net_load_layer_i8_pc(y355_net *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin,
+                                         int ksize, const int32_t *e_w, int e_b) {
+    if (!e_w) return y355_fail(Y355_EINVAL, "null argument");
+    return load_layer_i8(h, idx, q_w, q_b, cout, cin, ksize, e_w, 0, e_b);
+}
+
+// Bound on |acc| * 2^shl[c] over the output channels, shl[c] = F - sa_i - e_wc[c].  own: |acc| <= 127 * (sum |q_w| of the
+// channel), the layer's own weights; otherwise 127 * 127 per product (a per-channel layer always takes its own weights: the
+// worst-case weight in the channel with the largest shift is a bound nobody needs)
+static long double acc_bound(const NLayer &L, const OpDef &o, int F, int sa_i, bool own) {
+    const long double generic = (long double)127 * 127 * o.ksize * o.ksize * o.cin;
+    if (L.wabs <= 0 || (!own && !L.pc)) return generic * std::ldexp(1.0L, F - sa_i - (L.pc ? *std::min_element(L.e_wc.begin(), L.e_wc.end()) : L.e_w));
+    long double m = 0;
+    for (int c = 0; c < L.cout; ++c) m = std::max(m, (long double)127 * L.wabs_c[c] * std::ldexp(1.0L, F - sa_i - L.e_wc[c]));
+    return m;
+}
+static int shl_max(const NLayer &L, int F, int sa_i) { return F - sa_i - *std::min_element(L.e_wc.begin(), L.e_wc.end()); }
+
 static void act_fixed(int act, int *lk, int *neg_mul);
 
 // exponents of a residual layer's epilogue (ResQ, y355_common.h) and whether its 32-bit form holds for these weights.
@@ -997,7 +1038,7 @@ static void act_fixed(int act, int *lk, int *neg_mul);
 static int res_params(const y355_net *h, const OpDef &o, const NLayer &L, ResQ *rr, int *narrow) {
     const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in], sa_o = h->sa[o.out], s_r = h->sa[o.res1 - 1];
     const int F = std::max(sa_i + L.e_w, L.e_b);
-    const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;
+    const int shl = shl_max(L, F, sa_i), bshl = F - L.e_b;
     int lk, nm;
     act_fixed(o.act, &lk, &nm);
     const int E = F + lk, G = std::max(E, s_r);
@@ -1010,7 +1051,7 @@ static int res_params(const y355_net *h, const OpDef &o, const NLayer &L, ResQ *
     long double bmax = 0;
     for (int c = 0; c < L.cout; ++c) bmax = std::max(bmax, std::fabs((long double)L.q_b[c]) * std::ldexp(1.0L, bshl));
     // worst-case |t'|, as refresh_i8 bounds the plain epilogue
-    const long double tw = ((long double)127 * 127 * o.ksize * o.ksize * o.cin) * std::ldexp(1.0L, shl) + bmax;
+    const long double tw = acc_bound(L, o, F, sa_i, false) + bmax;
     long double u = tw * std::max(std::ldexp(1.0L, lk), (long double)nm) * std::ldexp(1.0L, rr->t_sh) + 127.0L * std::ldexp(1.0L, rr->r_sh);
     u = rr->sh < 0 ? u * std::ldexp(1.0L, -rr->sh) : u + std::ldexp(1.0L, rr->sh);
     if (u >= std::ldexp(1.0L, 62)) return 1;
@@ -1019,8 +1060,7 @@ static int res_params(const y355_net *h, const OpDef &o, const NLayer &L, ResQ *
     const int dp = std::max({shp - lk, s_r - sa_o, 0}), dn = std::max({shp, s_r - sa_o, 0});
     rr->p_t = lk - shp + dp; rr->p_r = sa_o - s_r + dp; rr->p_d = dp;
     rr->n_t = dn - shp; rr->n_r = sa_o - s_r + dn; rr->n_d = dn;
-    const long double accmax = L.wabs > 0 ? (long double)127 * L.wabs : (long double)127 * 127 * o.ksize * o.ksize * o.cin;
-    const long double tb = accmax * std::ldexp(1.0L, shl) + bmax, lim = std::ldexp(1.0L, 31);
+    const long double tb = acc_bound(L, o, F, sa_i, true) + bmax, lim = std::ldexp(1.0L, 31);
     if (dp <= 30 && dn <= 30 && rr->p_t <= 30 && rr->p_r <= 30 && rr->n_t <= 30 && rr->n_r <= 30 && tb < lim && bmax < lim &&
         tb * std::ldexp(1.0L, rr->p_t) + 127.0L * std::ldexp(1.0L, rr->p_r) + std::ldexp(1.0L, dp) < lim &&
         tb * nm * std::ldexp(1.0L, rr->n_t) + 127.0L * std::ldexp(1.0L, rr->n_r) + std::ldexp(1.0L, dn) < lim)
@@ -1066,6 +1106,13 @@ extern "C" int y355_net_set_act_exponents(y355_net *h, int sa_in, const int32_t 
     return 0;
 }
 
+extern "C" int y355_net_layer_route(y355_net *h, int idx, int32_t *route) {
+    if (!h || !route) return y355_fail(Y355_EINVAL, "null argument");
+    if (idx < 0 || idx >= h->arch->nlayers) return y355_fail(Y355_EINVAL, "layer index out of range");
+    *route = h->L[idx].route;
+    return 0;
+}
+
 extern "C" int y355_net_get_act_exponents(y355_net *h, int32_t *sa_in, int32_t *sa, int n) {
     if (!h || !sa_in || !sa || n != h->arch->ntensors) return y355_fail(Y355_EINVAL, "bad argument");
     *sa_in = h->sa_in;
@@ -1090,11 +1137,11 @@ static int refresh_i8(y355_net *h) {
         if (!L.dirty) continue;
         const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in], sa_o = h->sa[o.out];
         const int F = std::max(sa_i + L.e_w, L.e_b);
-        const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;
+        const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;      // shl: of the channels with the largest exponent, the smallest
         int lk, nm;
         act_fixed(o.act, &lk, &nm);
         const int sh = F + lk - sa_o;
-        if (shl > 24 || bshl > 40 || sh > 62 || sh < -20) return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
+        if (shl_max(L, F, sa_i) > 24 || bshl > 40 || sh > 62 || sh < -20) return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
         // worst case |t'| (through the slope and a left shift / the rounding add) must stay below 2^62
         std::vector<long long> bw(L.cout_pad, 0);
         long double bmax = 0;
@@ -1102,7 +1149,7 @@ static int refresh_i8(y355_net *h) {
             bw[c] = (long long)L.q_b[c] * (1ll << bshl);
             bmax = std::max(bmax, (long double)std::llabs(bw[c]));
         }
-        long double lim = ((long double)127 * 127 * o.ksize * o.ksize * o.cin) * std::ldexp(1.0L, shl) + bmax;
+        long double lim = acc_bound(L, o, F, sa_i, false) + bmax;
         lim *= std::max(std::ldexp(1.0L, lk), (long double)nm);
         lim = sh < 0 ? lim * std::ldexp(1.0L, -sh) : lim + std::ldexp(1.0L, sh);
         if (lim >= std::ldexp(1.0L, 62)) return y355_fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
@@ -1113,15 +1160,15 @@ static int refresh_i8(y355_net *h) {
         {
             // 32-bit epilogue (y355_requant_gen32) when |t| * max(2^max(0, lk - sh), neg_mul * 2^max(0, -sh)) + rounding < 2^31
             // |acc| <= 127 * (sum |q_w| of the channel): the layer's own weights give a tighter bound than 127 per weight
-            const long double accmax = L.wabs > 0 ? (long double)127 * L.wabs : (long double)127 * 127 * o.ksize * o.ksize * o.cin;
-            long double t32 = accmax * std::ldexp(1.0L, shl) + bmax;
+            const long double accs = acc_bound(L, o, F, sa_i, true);      // max over the channels of |acc| * 2^shl[c]
+            long double t32 = accs + bmax;
             const long double fpos = std::ldexp(1.0L, std::max(0, lk - sh)), fneg = (long double)nm * std::ldexp(1.0L, std::max(0, -sh));
             t32 = t32 * std::max(fpos, fneg) + std::ldexp(1.0L, std::max(sh, 0));
             L.rq.narrow = (t32 < std::ldexp(1.0L, 31) && bmax < std::ldexp(1.0L, 31)) ? 1 : 0;
             L.rq.split = 0;
             if (!L.rq.narrow && sh >= 9 && sh <= 31 && nm >= 1 && nm < 4096) {
                 // t itself and the positive branch fit 32 bits, only t * neg_mul does not: the negative branch goes in two halves
-                const long double tb = accmax * std::ldexp(1.0L, shl) + bmax;
+                const long double tb = accs + bmax;
                 const long double pos = tb * fpos + std::ldexp(1.0L, std::max(sh - lk, 0));
                 const long double neg = (tb / 256 + 1) * nm + 256 + std::ldexp(1.0L, sh - 9);
                 if (tb < std::ldexp(1.0L, 30) && pos < std::ldexp(1.0L, 31) && neg < std::ldexp(1.0L, 31) && bmax < std::ldexp(1.0L, 31))
@@ -1147,7 +1194,7 @@ static int refresh_i8(y355_net *h) {
         L.rq1.gen32 = 0;
         std::vector<int32_t> bt(L.cout_pad, 0);
         if (o.type == OP_CONV1) {
-            long double t32 = ((long double)127 * 127 * o.ksize * o.ksize * o.cin) * std::ldexp(1.0L, shl) + bmax;
+            long double t32 = acc_bound(L, o, F, sa_i, false) + bmax;
             const long double fpos = std::ldexp(1.0L, std::max(0, lk - sh)), fneg = (long double)nm * std::ldexp(1.0L, std::max(0, -sh));
             t32 = t32 * std::max(fpos, fneg) + std::ldexp(1.0L, std::max(sh, 0));
             if (t32 < std::ldexp(1.0L, 31) && bmax < std::ldexp(1.0L, 31)) {
@@ -1162,8 +1209,7 @@ static int refresh_i8(y355_net *h) {
             Requant &fr = i == 0 ? h->frq1 : h->frq2;
             fr = Requant{};
             fr.shl = shl; fr.sh = sh; fr.lk = lk; fr.neg_mul = nm; fr.leaky = (lk || nm != 1) ? 1 : 0; fr.guard_log2 = 63;
-            const long double accmax = L.wabs > 0 ? (long double)127 * L.wabs : (long double)127 * 127 * o.ksize * o.ksize * o.cin;
-            const long double tb = accmax * std::ldexp(1.0L, shl) + bmax;
+            const long double tb = acc_bound(L, o, F, sa_i, true) + bmax;
             fr.tmax_log2 = 0;
             while (fr.tmax_log2 < 62 && std::ldexp(1.0L, fr.tmax_log2) <= tb) ++fr.tmax_log2;
             fr.negsafe = std::ldexp(tb * nm, -sh) <= 127.0L ? 1 : 0;
@@ -1174,12 +1220,21 @@ static int refresh_i8(y355_net *h) {
             HIPCHK(hipMemcpyAsync(i == 0 ? h->fb1_dev : h->fb2_dev, fb.data(), sizeof(int32_t) * fb.size(), hipMemcpyHostToDevice, h->stream));
             h->front_dirty = true;
         }
+        // every output channel's own accumulator shift: in the upper half of the bias word for the 32-bit epilogues of
+        // convg.hip / convr.hip (y355_pc_word; the bias fits 32 bits there), in shl_dev for the 64-bit ones and for conv1.hip
+        std::vector<int> shc(L.cout_pad, 0);
+        for (int c = 0; c < L.cout; ++c) shc[c] = F - sa_i - L.e_wc[c];
+        if (o.type == OP_CONV && L.rq.narrow)
+            for (int c = 0; c < L.cout; ++c) bw[c] = y355_pc_word(shc[c], (int)bw[c]);
+        HIPCHK(hipMemcpyAsync(L.shl_dev, shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipMemcpyAsync(L.bias_w_dev, bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
         HIPCHK(hipStreamSynchronize(h->stream));
         L.dirty = false;
     }
     if (h->front_graph && h->front_dirty) {
-        h->front_ok = y355_front_eligible(h->frq1, h->frq2);
+        // front.hip's epilogue has ONE accumulator shift per layer: a per-channel layer runs on conv1.hip / convg.hip instead
+        const bool pc = h->L[h->arch->ops[0].layer].pc || h->L[h->arch->ops[1].layer].pc;
+        h->front_ok = !pc && y355_front_eligible(h->frq1, h->frq2);
         h->front_dirty = false;
     }
     return 0;
@@ -1281,9 +1336,10 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
     const OpDef &o = h->arch->ops[i];
     hipStream_t s = h->stream;
     if (o.type == OP_CONV1) {
-        const NLayer &L = h->L[o.layer];
+        NLayer &L = h->L[o.layer];
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
         if (!h->bf) {
+            L.route = Y355_ROUTE_FIRST | (L.rq1.gen32 ? 0 : Y355_ROUTE_EPI64) | (L.pc ? Y355_ROUTE_PER_CHANNEL : 0);
             Conv1Params p{};
             p.x = in.x;
             p.x_u8 = in.u8;                                    // (conv1 routes get frames at the network size)
@@ -1293,6 +1349,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
             p.w = (const int8_t *)h->w0_dev;
             p.bias_w = L.bias_w_dev;
             p.bias_t = L.rq1.gen32 ? (const int *)L.bias_dev : nullptr;
+            p.shl_c = L.pc ? L.shl_dev : nullptr;
             p.ctr = h->ctr_dev + i;
             p.B = B;
             p.H = h->cfg.height;
@@ -1318,9 +1375,10 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
         p.W = h->cfg.width;
         y355_conv1f_tiles(p.H, p.W, &p.tiles_x, &p.tiles_y);
         p.slope = act_slope(o.act);
+        L.route = Y355_ROUTE_FIRST;
         y355_launch_conv1f(p, s);
     } else if (o.type == OP_CONV) {
-        const NLayer &L = h->L[o.layer];
+        NLayer &L = h->L[o.layer];
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
         const Tensor &ti = h->T[o.in], &to = h->T[o.out];
         const ConvGInfo &ki = *y355_convg_kernel(h->bf, L.kid);
@@ -1330,8 +1388,11 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
         p.w = L.w_dev;
         p.bias_f = L.bias_dev;
         p.bias_w = L.bias_w_dev;
+        p.shl_w = L.shl_dev;
+        p.pc = L.pc ? 1 : 0;
         p.ctr = h->ctr_dev + i;
         p.rq = L.rq;
+        const int rflags = h->bf ? 0 : ((L.rq.narrow ? 0 : Y355_ROUTE_EPI64) | (o.res1 ? Y355_ROUTE_RESIDUAL : 0) | (L.pc ? Y355_ROUTE_PER_CHANNEL : 0));
         p.B = B;
         p.H = ti.H;
         p.W = ti.W;
@@ -1360,6 +1421,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
             q.w = L.wr_dev;
             q.nblk = L.cout_pad / 64;
             if (y355_launch_pw_i8(q, s)) {
+                L.route = Y355_ROUTE_POINTWISE | rflags;
                 HIPCHK(hipGetLastError());
                 return 0;
             }
@@ -1368,6 +1430,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
             ConvGParams q = p;
             q.w = L.wpb_dev;
             if (y355_launch_convpxb(L.pbid, q, s)) {
+                L.route = Y355_ROUTE_THIN;
                 HIPCHK(hipGetLastError());
                 return 0;
             }
@@ -1377,10 +1440,12 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
             q.w = L.wr_dev;
             q.nblk = L.cout_pad / y355_convr_info(L.rid)->bn;
             if (y355_launch_convr(L.rid, q, h->cfg.device_id, s)) {
+                L.route = Y355_ROUTE_RING | rflags;
                 HIPCHK(hipGetLastError());
                 return 0;
             }
         }
+        L.route = (ki.wm * ki.wn == 8 ? Y355_ROUTE_GENERIC8 : Y355_ROUTE_GENERIC4) | rflags;
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * B, s);
     } else if (o.type == OP_POOL) {
         const Tensor &ti = h->T[o.in], &to = h->T[o.out];
@@ -1531,6 +1596,7 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
                     fb.slope1 = act_slope(o0.act);
                     fb.slope2 = act_slope(o1.act);
                     y355_launch_frontb(fb, h->stream);
+                    h->L[o0.layer].route = h->L[o1.layer].route = Y355_ROUTE_FRONT;
                     HIPCHK(hipGetLastError());
                     continue;
                 }
@@ -1553,6 +1619,7 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
                 fp.rq1 = h->frq1;
                 fp.rq2 = h->frq2;
                 y355_launch_front(fp, h->stream);
+                h->L[h->arch->ops[0].layer].route = h->L[h->arch->ops[1].layer].route = Y355_ROUTE_FRONT;
                 HIPCHK(hipGetLastError());
             }
             continue;

@@ -54,8 +54,8 @@ __device__ __forceinline__ int y355_rne_shift32(int x, int s) {            // s 
     return (x + (1 << (s - 1)) - 1 + ((x >> s) & 1)) >> s;
 }
 // q before clamping for a LeakyReLU slope neg_mul / 2^lk that is not a power of two, 32-bit (Requant::gen32)
-__device__ __forceinline__ int y355_requant_gen32(int acc, int bias, const Requant &rq) {
-    const int t = (acc << rq.shl) + bias;
+// (t = acc * 2^shl + bias is the caller's: shl is rq.shl for a per-tensor epilogue, a per-lane value for a per-channel one)
+__device__ __forceinline__ int y355_requant_gen32_t(int t, const Requant &rq) {
     const int qp = y355_rne_shift32(t, rq.sh - rq.lk);
     int qn;
     if (rq.split) {                                    // wave-uniform
@@ -71,6 +71,17 @@ __device__ __forceinline__ int y355_requant_gen32(int acc, int bias, const Requa
     }
     return t >= 0 ? qp : qn;
 }
+__device__ __forceinline__ int y355_requant_gen32(int acc, int bias, const Requant &rq) {
+    return y355_requant_gen32_t((acc << rq.shl) + bias, rq);
+}
+// Bias word of the 32-bit epilogues of y355_net's int8 convolutions (convg.hip NARROW, convr.hip): the pre-shifted bias fits
+// 32 bits there, so the upper half of the 64-bit word carries the output channel's own accumulator shift shl[c] = F - sa_in -
+// e_w[c] (per-channel weight exponents; all equal for a per-tensor layer).  One load per channel, as before; the shift amount
+// is per lane, no longer wave-uniform.
+__host__ __device__ __forceinline__ long long y355_pc_word(int shl, int bias) {
+    return (long long)(((unsigned long long)(unsigned int)shl << 32) | (unsigned int)bias);
+}
+__device__ __forceinline__ int y355_pc_t(int acc, long long word) { return (acc << (int)(word >> 32)) + (int)word; }
 
 // q before clamping, 32-bit, no branches (production kernels)
 __device__ __forceinline__ int y355_requant_fast(int acc, int bias, const Requant &rq) {
@@ -147,6 +158,7 @@ struct Conv1Params {
     const int8_t *w;      // 64 lanes x 16 B fragment
     const int *bias_t;    // [16]
     const long long *bias_w;
+    const int *shl_c;     // [16] accumulator shift per output channel (per-channel weight exponents), or null: rq.shl
     Counters *ctr;
     int B, H, W;
     int tiles_x, tiles_y;
@@ -403,7 +415,7 @@ void y355_launch_scale_boxes(float *boxes, const int32_t *count, const float *wh
 
 // ---- generic chunked conv (convg.hip): bf16 nets and the int8 layers conv3x3.hip cannot hold --
 struct RequantG {
-    int shl;       // t = acc * 2^shl + bias
+    int shl;       // t = acc * 2^shl + bias (the kernels read it per output channel: bias_w / shl_w of ConvGParams)
     int sh;        // q = clamp(RNE(t' * 2^-sh))
     int lk;        // t' = t >= 0 ? t * 2^lk : t * neg_mul     (LeakyReLU slope neg_mul / 2^lk)
     int neg_mul;
@@ -428,7 +440,7 @@ struct ConvGParams {
     char *out;                // NHWC, out_pb bytes per pixel
     const char *w;            // fragment-packed weights (y355_convg_pack)
     const float *bias_f;      // bf16: [cout_pad]
-    const long long *bias_w;  // int8: [cout_pad] pre-shifted
+    const long long *bias_w;  // int8: [cout_pad] pre-shifted; rq.narrow: y355_pc_word(shl[c], bias[c])
     Counters *ctr;            // int8: saturation counter (or null)
     int B, H, W;
     int in_pb, nchunks;       // bytes per input pixel; chunks of CHB bytes consumed
@@ -445,6 +457,9 @@ struct ConvGParams {
     int grid_limit;           // host side only: persistent workgroups of a convr.hip launch (0 = one per CU), Y355_NET_OPT_WORKGROUPS
     int xcd_share_log2;       // convr.hip: work items that read one input are walked by workgroups of one XCD (set by the launcher)
     ResQ rr;                  // int8 with `res`: the residual's exponent shifts
+    // per-channel weight exponents (appended: the fields above keep their kernel-argument offsets)
+    const int *shl_w;         // int8, 64-bit epilogue (!rq.narrow): [cout_pad] accumulator shift of every output channel
+    int pc;                   // int8: 1 = the shifts differ between channels (convg.hip and pw_i8_kernel take their per-lane-shift instantiation)
 };
 
 struct Conv1FParams {

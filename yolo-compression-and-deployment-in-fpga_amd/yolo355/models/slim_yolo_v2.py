@@ -317,7 +317,7 @@ class _NetModel(nn.Module):
 
     def forward_batch(self, x, quantization=False, sizes_wh=None):
         """Every image of the batch.  quantization=True (YOLOv3tiny, YOLOv2, YOLOv3, YOLOv3-SPP) runs the int8 engine:
-        weights quantized per tensor to power-of-two int8 after the BN fold, activation exponents
+        weights quantized per tensor (self.channel_level: per output channel) to power-of-two int8 after the BN fold, activation exponents
         frozen at the first quantized call from the bf16 run of that input -- the first-call rule of
         AveragedRangeTracker (models/slim_yolo_v2.py:25-27) applied to this graph.
         sizes_wh: [B,2] original (width, height) per image: the boxes come back in pixels of the original images
@@ -356,6 +356,11 @@ class _NetModel(nn.Module):
         return tuple(int(p._version) for p in t) + tuple(p.data_ptr() for p in t)
 
     act_exponents = None      # (sa_in, [sa per tensor]) of the int8 path, frozen at the first quantized call
+    # int8 path: one power-of-two weight scale per output channel instead of one per layer (quantize_tensor's
+    # channel_level, retune_bias_quantize.py:73-86), exponents at most max_spread apart (None: prep.DEFAULT_MAX_SPREAD).
+    # Set before the first quantized call, or any time: the int8 net reloads when they change
+    channel_level = False
+    max_spread = None
 
     def _get_net(self, batch, int8=False):
         slot = "q" if int8 else "f"
@@ -369,10 +374,12 @@ class _NetModel(nn.Module):
                             self.nms_thresh, max_batch=max(batch, 1), device=dev, dtype="int8" if int8 else "bf16")
             st["key"], st["ver"] = key, None
         ver = self._weights_version()
+        if int8:
+            ver = ver + (bool(self.channel_level), self.max_spread)
         if st["ver"] != ver:
             folded = [folded_f32(m) for m in self._conv_modules()]
             if int8:
-                for i, q in enumerate(prep.quantize_folded(folded)):
+                for i, q in enumerate(prep.quantize_folded(folded, bool(self.channel_level), self.max_spread)):
                     st["net"].load_layer_i8(i, q["q_w"], q["q_b"], q["e_w"], q["e_b"])
             else:
                 for i, (w, b) in enumerate(folded):

@@ -88,13 +88,30 @@ class Net:
                                                      w.shape[0], w.shape[1], w.shape[2]))
 
     def load_layer_i8(self, idx, q_w, q_b, e_w, e_b):
-        """int8 nets: q_w [cout,cin,k,k] (|q| <= 127, value q / 2^e_w), q_b int32 [cout] (value q / 2^e_b)."""
+        """int8 nets: q_w [cout,cin,k,k] (|q| <= 127, value q / 2^e_w), q_b int32 [cout] (value q / 2^e_b).
+        e_w: one exponent, or an array [cout] with one per output channel (prep.quantize_folded(channel_level=True))."""
         if np.abs(np.asarray(q_w)).max() > 127:
             raise ValueError("|q_w| > 127")
         qw = np.ascontiguousarray(q_w, dtype=np.int8)
         qb = np.ascontiguousarray(q_b, dtype=np.int32)
-        _ffi.check(self._lib.y355_net_load_layer_i8(self._h, idx, qw.ctypes.data, qb.ctypes.data, qw.shape[0], qw.shape[1],
-                                                    qw.shape[2], int(e_w), int(e_b)))
+        if np.ndim(e_w) == 0:
+            _ffi.check(self._lib.y355_net_load_layer_i8(self._h, idx, qw.ctypes.data, qb.ctypes.data, qw.shape[0], qw.shape[1],
+                                                        qw.shape[2], int(e_w), int(e_b)))
+            return
+        ew = np.ascontiguousarray(e_w, dtype=np.int32)
+        if ew.shape != (qw.shape[0],):
+            raise ValueError("e_w: one exponent per output channel expected, got shape %s" % (ew.shape,))
+        _ffi.check(self._lib.y355_net_load_layer_i8_pc(self._h, idx, qw.ctypes.data, qb.ctypes.data, qw.shape[0], qw.shape[1],
+                                                       qw.shape[2], ew.ctypes.data, int(e_b)))
+
+    # y355_net_layer_route: kernel family (route & 0xff) and flags of the last forward's launch of a layer
+    ROUTE_FIRST, ROUTE_FRONT, ROUTE_RING, ROUTE_POINTWISE, ROUTE_GENERIC4, ROUTE_GENERIC8 = 1, 2, 3, 4, 5, 6
+    ROUTE_EPI64, ROUTE_RESIDUAL, ROUTE_PER_CHANNEL = 0x100, 0x200, 0x400
+
+    def layer_route(self, idx):
+        r = C.c_int32()
+        _ffi.check(self._lib.y355_net_layer_route(self._h, int(idx), C.byref(r)))
+        return r.value
 
     def set_act_exponents(self, sa_in, sa):
         arr = (C.c_int32 * len(sa))(*[int(v) for v in sa])

@@ -35,16 +35,31 @@ def fuse_conv_and_bn(conv, bn, corrected=False):
 
 
 def quantize_tensor(tensor, bitwidth=8, channel_level=False):
-    """retune_bias_quantize.py:73-86: (round(scale*t), scale) with scale = 2^floor(log2(127/max|t|))."""
-    if channel_level:
-        raise NotImplementedError("the reference only uses channel_level=False (retune_bias_quantize.py:115)")
-    _max = tensor.abs().max()
+    """retune_bias_quantize.py:73-86: (round(scale*t), scale) with scale = 2^floor(log2(127/max|t|)).
+    channel_level=True: one scale per slice of dim 0 (output channel), viewed [-1,1,1,1] for a 4-D tensor and
+    [-1,1] otherwise, as the reference does.  (An all-zero channel gives scale = inf and q = nan there;
+    quantize_folded defines that case.)"""
+    if not channel_level:
+        _max = tensor.abs().max()
+        scale = (2 ** (bitwidth - 1) - 1) / _max
+        scale = 2 ** torch.floor(torch.log2(scale))
+        return torch.round(scale * tensor), scale
+    _max = tensor.abs().view(tensor.size(0), -1).max(1)[0]
     scale = (2 ** (bitwidth - 1) - 1) / _max
+    scale = scale.view(-1, 1, 1, 1) if tensor.dim() == 4 else scale.view(-1, 1)
     scale = 2 ** torch.floor(torch.log2(scale))
     return torch.round(scale * tensor), scale
 
 
-quantize_tensor_b = quantize_tensor    # retune_bias_quantize.py:88-97 is the same arithmetic
+def quantize_tensor_b(tensor, bitwidth=8, channel_level=False):
+    """retune_bias_quantize.py:88-97: the same arithmetic; with channel_level=True the scale keeps its 1-D shape
+    (one per element of a bias)."""
+    if not channel_level:
+        return quantize_tensor(tensor, bitwidth)
+    _max = tensor.abs().view(tensor.size(0), -1).max(1)[0]
+    scale = (2 ** (bitwidth - 1) - 1) / _max
+    scale = 2 ** torch.floor(torch.log2(scale))
+    return torch.round(scale * tensor), scale
 
 
 def to_int8_pow2(t):
@@ -91,12 +106,39 @@ def quantize_layers(bitwidth=8, rescale=True, retune=False):
             layer.bias[...] = qb * r / sb if rescale else qb
 
 
-def quantize_folded(folded):
-    """[(W fp32, b fp32)] of BN-folded convs -> [{q_w, e_w, q_b, e_b}]: the per-tensor power-of-two
-    int8 recipe of quantize_layers (retune_bias_quantize.py:111-119) for the y355_net graphs."""
+# Largest gap between the weight exponents of one layer that quantize_folded(channel_level=True) keeps by default.
+# Every bit of spread is a bit taken from the 32-bit epilogue of the layer's kernel; profiles/r10_per_channel_notes.md lists,
+# per architecture and spread 0..8, the layers that leave the 32-bit route and the accuracy, and derives this value.
+DEFAULT_MAX_SPREAD = 4
+
+
+def quantize_folded(folded, channel_level=False, max_spread=None):
+    """[(W fp32, b fp32)] of BN-folded convs -> [{q_w, e_w, q_b, e_b}]: the power-of-two int8 recipe of
+    quantize_layers (retune_bias_quantize.py:111-119) for the y355_net graphs, one weight exponent per tensor.
+    channel_level=True: quantize_tensor(channel_level=True) on the weights, e_w an int32 array [cout]
+    (y355_net_load_layer_i8_pc); the bias keeps one exponent.  Two cases the reference's formula leaves open:
+      * an all-zero output channel (scale = inf there) takes the layer's smallest exponent;
+      * e_w[c] is capped at min_c e_w[c] + max_spread (None: DEFAULT_MAX_SPREAD); the weights of a capped channel are
+        rounded at the capped exponent, round(w * 2^e_w[c]), so they use fewer than 7 bits."""
     out = []
+    if max_spread is None:
+        max_spread = DEFAULT_MAX_SPREAD
     for w, b in folded:
-        qw, ew = to_int8_pow2(torch.as_tensor(w))
+        if not channel_level:
+            qw, ew = to_int8_pow2(torch.as_tensor(w))
+        else:
+            wt = torch.as_tensor(w).detach().float().cpu()
+            live = wt.abs().reshape(wt.size(0), -1).max(1)[0] > 0
+            if not bool(live.any()):
+                raise ValueError("quantize_folded: a layer whose weights are all zero has no scale "
+                                 "(the reference's formula divides by max|w| = 0)")
+            scale = quantize_tensor(wt[live], 8, True)[1].reshape(-1)
+            e_live = torch.log2(scale).to(torch.int64)
+            lo = int(e_live.min())
+            ew = torch.full((wt.size(0),), lo, dtype=torch.int64)
+            ew[live] = torch.clamp(e_live, max=lo + int(max_spread))
+            qw = torch.round(wt * (2.0 ** ew.to(torch.float32)).view(-1, 1, 1, 1)).to(torch.int32).numpy()
+            ew = ew.to(torch.int32).numpy()
         qb, eb = to_int8_pow2(torch.as_tensor(b))
         out.append(dict(q_w=qw, e_w=ew, q_b=qb, e_b=eb))
     return out

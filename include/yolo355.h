@@ -542,6 +542,44 @@ int y355_net_get_candidates(y355_net *h, int batch, float *boxes, float *scores,
 int y355_net_get_tensor(y355_net *h, int idx, int batch, float *dst_host);
 /* max |value| of an activation tensor of the last forward (calibration of the int8 recipe); see the note above */
 int y355_net_tensor_absmax(y355_net *h, int idx, int batch, float *out_max);
+/* Calibration of an int8 net on its own graph: the reference's forward(x, quantization=True) with freeze = not trainable
+ * (models/slim_yolo_v2.py:212-328; AveragedRangeTracker :9-38; the loop of retune_bias_quantize.py:357-369), for all five
+ * families, without fp32 weights and without a second net.
+ * Trackers: n = y355_net_num_trackers = 1 + num_tensors -- [0] the network input, [1 + t] tensor t in graph order; state per
+ * tracker scale (float32) and first_a, as y355_set_trackers.  set installs the state and, for every tracker with
+ * first_a != 0, its exponent floor(log2(scale)) (:33) with the aliasing and the range proof of y355_net_set_act_exponents
+ * (Y355_ERANGE: nothing changed); the other tensors keep their exponents.
+ * y355_net_calibrate: ONE pass over the op table in graph order on batch x_dev (fp32 NCHW); y355_net_calibrate_u8: the same
+ * on uint8 HWC BGR frames (as y355_net_forward_u8), equal bit for bit to the step on the normalised tensor of the resized
+ * frames.  Synchronous.  Every update is y355_tracker_step's arithmetic: the first call ever sets the scale even when
+ * frozen (:25-27), frozen otherwise leaves it (:28-29), else the EMA with `momentum` (:30-31); exponent floor(log2(scale)).
+ *   input     tracker 0 sees max |x| (frames: of the normalised resized frames)
+ *   conv      max |t'| / 2^(F + lk) over the UN-POOLED outputs (the reference tracks in front of the pool, :229-231), t' with
+ *             every output channel's own shift; with a residual max |u| / 2^G, the sum that is stored
+ *   bilinear  the maximum of the blended fp32 values times 2^-s_in;   reorg: the maximum of the source bytes times 2^-s_in
+ *   SPP       in place, contributes nothing;   max-pool outputs and the DarkNet input tensor mirror their source's entry
+ * The integer maxima become float32 as y355_calibrate's absmax_t / frac_bits do.  Each value is computed behind the
+ * exponents already updated in front of it, and the tracker is updated INLINE at the tensor's first producer, which gives
+ * the tensor its exponent for the rest of the step.  A buffer with later producers (YOLOv3tiny's tensor 4, YOLOv2's concat
+ * buffer 23, the concat buffers of YOLOv3 / -SPP) is written by them with that exponent; at the end of the step its update is
+ * redone from the pre-step state with the maximum over ALL producers, so the state and the exponent the handle keeps
+ * reflect the whole buffer (the pass itself ran on the provisional one).  After a step the handle's exponents are the
+ * trackers'.  Convolutions run on the generic kernels (statistics launch, then the write), never on the ring / pointwise /
+ * fused front-end kernels; the next forward takes its usual routes.
+ * sa_in_out (optional): the input's exponent; sa_out (optional) [n - 1]: per tensor; max_out (optional) [n]: the float32
+ * maximum every tracker saw (multi-producer buffers: over all producers).
+ * Errors, checked before any HIP call: a bf16 net or a wrong n Y355_EINVAL, unloaded weights Y355_ENOTREADY.  A step that
+ * fails (Y355_ERANGE: a tracker's scale or exponent out of range, an epilogue or the residual range proof of
+ * y355_net_set_act_exponents not in range) leaves trackers and exponents as they were before it; the tensors and the clamp
+ * counters (y355_net_get_tensor, y355_net_counters) are then partly written and undefined until the next forward or step. */
+int y355_net_num_trackers(y355_net *h);                                   /* 1 + num_tensors */
+int y355_net_set_trackers(y355_net *h, const float *scale, const int32_t *first_a, int n);
+int y355_net_get_trackers(y355_net *h, float *scale, int32_t *first_a, int n);
+int y355_net_calibrate(y355_net *h, const float *x_dev, int batch, int freeze, double momentum,
+                       int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n);
+int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch,
+                          int freeze, double momentum, int32_t *sa_in_out, int32_t *sa_out,
+                          float *max_out, int n);
 int y355_net_max_det(y355_net *h);
 int y355_net_num_anchors_total(y355_net *h);
 int y355_net_sync(y355_net *h);

@@ -14,6 +14,7 @@
 // holds 16 bytes of row/column j at k-offset 16 g), which is why one kernel serves both.
 #include "y355_common.h"
 #include "convg_store.h"
+#include <climits>
 #include <cstring>
 #include <type_traits>
 
@@ -65,11 +66,78 @@ __device__ __forceinline__ void load_res_i8(const char *src, int (&r)[NT]) {
     }
 }
 
+// ---- statistics mode (STAT) of the int8 kernels: calibration on the int8 graph itself (y355_net_calibrate).  The 64-bit
+// epilogue up to t' (residual layers: up to the sum u = t' 2^(G-E) + q_r 2^(G-s_r)) on every UN-POOLED output of the tile
+// (the reference tracks in front of the pool, models/slim_yolo_v2.py:229-231), |.| in int64, reduced within the wave, ONE
+// 64-bit atomicMax per wave into the op's slot (p.ctr->absmax).  Nothing else is written.  acc[m][t][r]: as the epilogues
+// read it -- POOL: position r of 2x2 window (wm MT + m) 4 + g; otherwise tile row (wm MT + m) 16 + 4 g + r.
+template <int MT, int NT, int TH, int TW, bool POOL, int S, bool PC>
+__device__ __forceinline__ void convg_stat(const ConvGParams &p, const v4i (&acc)[MT][NT], int nlane, int wm, int g, int lane,
+                                           int b, int y0, int x0) {
+    constexpr int BM = TH * TW;
+    const RequantG rq = p.rq;
+    // the map the accumulators live on: the conv's own output (before any pool)
+    const int Ho = S == 2 ? (p.H + 1) >> 1 : p.H, Wo = S == 2 ? (p.W + 1) >> 1 : p.W;
+    const char *resb = (!POOL && p.res) ? p.res + (size_t)b * (Ho + 2) * (Wo + 2) * p.res_pb + p.res_off : nullptr;
+    long long biasw[NT];
+    int shl[NT];
+#pragma unroll
+    for (int t = 0; t < NT; ++t) {
+        biasw[t] = p.bias_w[nlane + t];
+        shl[t] = PC ? p.shl_w[nlane + t] : rq.shl;
+    }
+    unsigned long long amax = 0;
+    auto rowpos = [&](int m, int r, int &oy, int &ox) -> bool {
+        if constexpr (POOL) {
+            const int w = (wm * MT + m) * 4 + g;
+            oy = y0 + 2 * (w / (TW / 2)) + (r >> 1);
+            ox = x0 + 2 * (w % (TW / 2)) + (r & 1);
+            return (w * 4 < BM) && oy < Ho && ox < Wo;
+        } else {
+            const int row = (wm * MT + m) * 16 + 4 * g + r;
+            oy = y0 + row / TW;
+            ox = x0 + row % TW;
+            return row < BM && oy < Ho && ox < Wo;
+        }
+    };
+    // One row at a time, in order: the running maximum passes through an opaque register barrier after every row, so the rows
+    // form a serial chain.  (Left free, the compiler evaluates the 4 MT NT independent 64-bit values breadth-first and
+    // reduces them as a tree: about 140 registers of temporaries, which the 8-wave tiles do not have.)
+    unsigned int amax_lo = 0, amax_hi = 0;
+#pragma unroll
+    for (int m = 0; m < MT; ++m) {
+#pragma unroll
+        for (int r = 0; r < 4; ++r) {
+            int oy, ox;
+            const bool valid = rowpos(m, r, oy, ox);
+            int qr[NT];
+#pragma unroll
+            for (int t = 0; t < NT; ++t) qr[t] = 0;
+            if (resb && valid) load_res_i8<NT>(resb + ((size_t)(oy + 1) * (Wo + 2) + ox + 1) * p.res_pb + nlane, qr);
+            amax = ((unsigned long long)amax_hi << 32) | amax_lo;
+#pragma unroll
+            for (int t = 0; t < NT; ++t) {
+                long long v = (long long)acc[m][t][r] * (1ll << shl[t]) + biasw[t];
+                v = v >= 0 ? v * (1ll << rq.lk) : v * (long long)rq.neg_mul;
+                if (resb) v = v * (1ll << p.rr.t_sh) + (long long)qr[t] * (1ll << p.rr.r_sh);
+                const unsigned long long a = (unsigned long long)(v < 0 ? -v : v);
+                amax = (valid && a > amax) ? a : amax;
+            }
+            amax_lo = (unsigned int)amax;
+            amax_hi = (unsigned int)(amax >> 32);
+            asm volatile("" : "+v"(amax_lo), "+v"(amax_hi));
+        }
+    }
+    amax = ((unsigned long long)amax_hi << 32) | amax_lo;
+    const unsigned long long wmax = y355_wave_max_u64(amax);
+    if (lane == 0 && wmax && p.ctr) atomicMax(&p.ctr->absmax, wmax);
+}
+
 // ---- four waves per workgroup (round 1): one tile per workgroup, stage -> barrier -> k-steps -> barrier per chunk.  Kept for
 // the thin layers and the small / stride-2 tiles, where its 2-3 workgroups per CU overlap each other's phases.
 // PC: the layer's weight exponents differ between output channels (ConvGParams::pc): the accumulator shift is the lane's own
 // (bias word / shl_w); otherwise rq.shl, wave-uniform, and the code of the per-tensor layers is what it was
-template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false>
+template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false, bool STAT = false>
 __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
     constexpr bool THIN = (CHB == 32);           // 32 B per pixel: a k-step covers two taps
     // input patch of a TH x TW output tile: S*(T-1)+3 pixels a side (stride S, 3x3, pad 1)
@@ -215,6 +283,10 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
 
     // ---- epilogue
     const int nlane = nb * BN + wn * (NT * 16) + li * NT;       // first of this lane's NT channels
+    if constexpr (STAT && !BF) {                                // statistics mode: the maximum only
+        convg_stat<MT, NT, TH, TW, POOL, S, PC>(p, acc, nlane, wm, g, lane, b, y0, x0);
+        return;
+    }
     const int halo = p.out_halo;
     const int Ho = POOL ? (H >> 1) : (S == 2 ? (H + 1) >> 1 : H), Wo = POOL ? (W >> 1) : (S == 2 ? (W + 1) >> 1 : W);
     char *outb = p.out + (size_t)b * (Ho + 2 * halo) * (Wo + 2 * halo) * p.out_pb + p.out_off;
@@ -351,7 +423,7 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
 // (58.2 k / 49.2 k): the extra live state spills, and one 8-wave workgroup per CU has nothing to overlap its epilogue with.
 // What bounds this kernel now is the B path: 16-32 KB of fragments per k-step per CU through the vector-memory pipe
 // (profiles/r02_notes.md); the int8 ring kernels avoid exactly that with LDS-DMA weight rings.
-template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false>
+template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false, bool STAT = false>
 __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams p, const int total) {
     constexpr int NTHR = WM * WN * 64;
     constexpr bool THIN = (CHB == 32);           // 32 B per pixel: a k-step covers two taps
@@ -447,7 +519,7 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
         }
     };
     constexpr size_t WSTEP = (size_t)WN * NT * 1024;
-    constexpr bool DEEP = true;                  // B fragments two k-steps ahead
+    constexpr bool DEEP = !STAT;                 // B fragments two k-steps ahead (the statistics instantiations: one, to stay inside the register budget)
     v4i b0[NT], b1[NT];
     auto load_b01 = [&](const char *wp) {
 #pragma unroll
@@ -509,7 +581,7 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
         for (int ch = 0; ch < p.nchunks; ++ch) {
             const bool more = ch + 1 < p.nchunks;
             slab = smem + cur * SLAB;
-            if (more) stage_load(b, y0, x0, ch + 1);       // in flight under this chunk's k-steps
+            if (more && !STAT) stage_load(b, y0, x0, ch + 1);       // in flight under this chunk's k-steps
             if constexpr (THIN) {
 #pragma unroll
                 for (int ks = 0; ks < 5; ++ks) kstep(kofs[ks]);
@@ -525,6 +597,7 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
                 }
             }
             if (more) {
+                if constexpr (STAT) stage_load(b, y0, x0, ch + 1);       // (behind them: the staging registers stay free under the k-steps)
                 stage_store(smem + (cur ^ 1) * SLAB);
                 __syncthreads();
                 cur ^= 1;
@@ -532,6 +605,10 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
         }
         // ---- epilogue
         const int nlane = nb * BN + wn * (NT * 16) + li * NT;       // first of this lane's NT channels
+        if constexpr (STAT && !BF) {                                // statistics mode: the maximum only
+            convg_stat<MT, NT, TH, TW, POOL, S, PC>(p, acc, nlane, wm, g, lane, b, y0, x0);
+            return;
+        }
         char *outb = p.out + (size_t)b * (Ho + 2 * halo) * (Wo + 2 * halo) * p.out_pb + p.out_off;
         const char *resb = p.res ? p.res + (size_t)b * (Ho + 2) * (Wo + 2) * p.res_pb + p.res_off : nullptr;
 
@@ -683,6 +760,23 @@ struct ConvGInst {
                 hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>), dim3(nblocks), dim3(256), SLAB, s, p);
         }
     }
+    // statistics mode (int8 only): the 64-bit epilogue's instantiation with STAT, per-tensor or per-channel shifts
+    static void launch_stat(const ConvGParams &p, int nblocks, hipStream_t s) {
+        if constexpr (!BF) {
+            if constexpr (EIGHT) {
+                const size_t lds = p.nchunks > 1 ? 2 * SLAB : SLAB;
+                if (p.pc)
+                    hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, true, true>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
+                else
+                    hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, true>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
+            } else {
+                if (p.pc)
+                    hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, true, true>), dim3(nblocks), dim3(256), SLAB, s, p);
+                else
+                    hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, true>), dim3(nblocks), dim3(256), SLAB, s, p);
+            }
+        }
+    }
     static int prepare() {
         const int lds = (int)LDS;
         auto set = [&](const void *fn) { return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds); };
@@ -691,6 +785,8 @@ struct ConvGInst {
                 if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>)) return e;
                 if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>)) return e;
                 if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>)) return e;
+                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, !BF>)) return e;
+                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF, !BF>)) return e;
             }
             return set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>);
         } else {
@@ -698,12 +794,14 @@ struct ConvGInst {
                 if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>)) return e;
                 if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>)) return e;
                 if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>)) return e;
+                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, !BF>)) return e;
+                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF, !BF>)) return e;
             }
             return set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>);
         }
     }
     static constexpr ConvGInfo info() {
-        return ConvGInfo{BF ? 1 : 0, CHB, BN, TH, TW, POOL ? 1 : 0, WM, WN, BN / 16 / WN, S, LDS, &launch, &prepare};
+        return ConvGInfo{BF ? 1 : 0, CHB, BN, TH, TW, POOL ? 1 : 0, WM, WN, BN / 16 / WN, S, LDS, &launch, &prepare, &launch_stat};
     }
 };
 

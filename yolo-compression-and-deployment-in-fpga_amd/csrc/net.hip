@@ -589,6 +589,78 @@ __global__ void spp_i8_kernel(char *buf, int B, int H, int W, int pb, int C) {
         *(uint4 *)(o + (size_t)C * 3) = pack(m13);
     }
 }
+
+// ---- maxima of a calibration step on the int8 graph (y355_net_calibrate): each reduces within the wave and issues one
+// atomicMax per wave on the bits of a non-negative fp32 / on an unsigned int; nothing else is written
+// bilinear x2: max |blend| of upsample_i8_kernel's fp32 expression, before the rescale
+__global__ void upsample_i8_max_kernel(const char *in, int B, int Hin, int Win, int in_pb, int C, float ry, float rx, unsigned int *out) {
+    const int Ho = 2 * Hin, Wo = 2 * Win;
+    const size_t total = (size_t)B * Ho * Wo * C;
+    float m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        size_t r = i / C;
+        const int x = (int)(r % Wo);
+        r /= Wo;
+        const int y = (int)(r % Ho);
+        const int b = (int)(r / Ho);
+        const float sy = ry * (float)y, sx = rx * (float)x;
+        const int y0 = (int)sy, x0 = (int)sx;
+        const int y1 = min(y0 + 1, Hin - 1), x1 = min(x0 + 1, Win - 1);
+        const float ly = sy - (float)y0, lx = sx - (float)x0;
+        const float hy = 1.f - ly, hx = 1.f - lx;
+        auto ld = [&](int yy, int xx) -> float {
+            return (float)*(const signed char *)(in + (((size_t)b * (Hin + 2) + yy + 1) * (Win + 2) + xx + 1) * in_pb + c);
+        };
+        const float v = hy * (hx * ld(y0, x0) + lx * ld(y0, x1)) + ly * (hx * ld(y1, x0) + lx * ld(y1, x1));
+        m = fmaxf(m, fabsf(v));
+    }
+    const unsigned int u = y355_wave_max_u32(__float_as_uint(m));
+    if ((threadIdx.x & 63) == 0 && u) atomicMax(out, u);
+}
+
+// max |q| over the first C channels of an int8 tensor's interior (reorg's source bytes)
+__global__ void absmax_i8_kernel(const char *in, int B, int H, int W, int pb, int C, unsigned int *out) {
+    const size_t total = (size_t)B * H * W * C;
+    unsigned int m = 0;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int c = (int)(i % C);
+        size_t r = i / C;
+        const int x = (int)(r % W);
+        r /= W;
+        const int y = (int)(r % H);
+        const size_t b = r / H;
+        const int q = (int)*(const signed char *)(in + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * pb + c);
+        m = max(m, (unsigned int)abs(q));
+    }
+    const unsigned int u = y355_wave_max_u32(m);
+    if ((threadIdx.x & 63) == 0 && u) atomicMax(out, u);
+}
+
+// max |x| of the normalised frames (the table entries y355_norm_u8 the H x W network input actually hits): uint8 HWC BGR
+// [B][sh][sw][3], resized on the fly when tab != null (y355_resize_px), as input_u8_kernel reads them
+__global__ __launch_bounds__(256) void absmax_u8_kernel(const uint8_t *frames, const int *tab, int B, int sh, int sw, int H, int W,
+                                                        NormU8 nm, unsigned int *out) {
+    const size_t total = (size_t)B * H * W;
+    const size_t plane = (size_t)H * W;
+    float m = 0.f;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
+        const int xx = (int)(i % W), y = (int)((i / W) % H);
+        const size_t b = i / plane;
+        int u[3];
+        if (tab) {
+            y355_resize_px(frames + b * sh * sw * 3, tab, sh, sw, H, W, y, xx, u);
+        } else {
+            const uint8_t *px = frames + i * 3;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) u[c] = px[c];
+        }
+#pragma unroll
+        for (int c = 0; c < 3; ++c) m = fmaxf(m, fabsf(y355_norm_u8(u[2 - c], nm.mean[c], nm.sd[c])));     // RGB c = BGR byte 2 - c
+    }
+    const unsigned int bits = y355_wave_max_u32(__float_as_uint(m));
+    if ((threadIdx.x & 63) == 0 && bits) atomicMax(out, bits);
+}
 }  // namespace
 
 #ifndef Y355_USE_CONVPXB
@@ -637,6 +709,12 @@ struct y355_net {
     int *rs_tab = nullptr;
     uint8_t *rs_frames = nullptr;
     int rs_src_h = 0, rs_src_w = 0;
+    // calibration on the int8 graph (y355_net_calibrate): AveragedRangeTracker state of the network input [0] and of every
+    // tensor [1 + t] (models/slim_yolo_v2.py:13-14), and one slot of maxima per op ([nops]: the input) on the device
+    std::vector<float> trk_scale;
+    std::vector<int> trk_first;
+    Counters *cal_dev = nullptr;
+    bool calibrating = false;         // run_op: every convolution on convg.hip
 };
 
 // the network input of one forward: an fp32 NCHW tensor, or uint8 HWC BGR frames (u8) of src_h x src_w with the resize tables
@@ -800,6 +878,9 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     const size_t cap = Y355_NMS_CAP;
     if (!rc) rc = nmalloc(h, (void **)&h->absmax_dev, 16, true);
     if (!rc) rc = nmalloc(h, (void **)&h->ctr_dev, sizeof(Counters) * 2 * (A.nops + 1), true);
+    if (!rc && !h->bf) rc = nmalloc(h, (void **)&h->cal_dev, sizeof(Counters) * (A.nops + 1), true);
+    h->trk_scale.assign(A.ntensors + 1, 0.f);
+    h->trk_first.assign(A.ntensors + 1, 0);
     h->ctrs.base = h->ctr_dev;
     h->ctrs.n = A.nops + 1;
     h->ctrs.clean[0] = h->ctrs.clean[1] = true;
@@ -1072,13 +1153,8 @@ static int res_params(const y355_net *h, const OpDef &o, const NLayer &L, ResQ *
 // order of csrc/net.hip).  A max-pool output takes its input's exponent and the network-input tensor sa_in (the entries
 // given for them are overridden); a concat buffer (and the in-place SPP buffer) has ONE exponent that every producer
 // requantises to.  Y355_ERANGE (nothing changed) when a loaded residual layer's epilogue is not provably in range.
-extern "C" int y355_net_set_act_exponents(y355_net *h, int sa_in, const int32_t *sa, int n) {
-    if (!h || !sa) return y355_fail(Y355_EINVAL, "null argument");
-    if (h->bf) return y355_fail(Y355_EINVAL, "bf16 nets have no activation exponents");
-    if (n != h->arch->ntensors) return y355_fail(Y355_EINVAL, "one exponent per tensor expected");
-    for (int i = 0; i < n; ++i)
-        if (sa[i] < -64 || sa[i] > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
-    if (sa_in < -64 || sa_in > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
+// (arguments checked) installs the exponents with the aliasing and the range proof of y355_net_set_act_exponents
+static int install_act_exponents(y355_net *h, int sa_in, const int32_t *sa, int n, bool all_set) {
     const int keep_in = h->sa_in;
     const std::vector<int> keep = h->sa;
     h->sa_in = sa_in;
@@ -1101,9 +1177,19 @@ extern "C" int y355_net_set_act_exponents(y355_net *h, int sa_in, const int32_t 
                                           "for these exponents");
         }
     }
-    h->sa_ok = true;
+    if (all_set) h->sa_ok = true;
     for (auto &L : h->L) L.dirty = true;
     return 0;
+}
+
+extern "C" int y355_net_set_act_exponents(y355_net *h, int sa_in, const int32_t *sa, int n) {
+    if (!h || !sa) return y355_fail(Y355_EINVAL, "null argument");
+    if (h->bf) return y355_fail(Y355_EINVAL, "bf16 nets have no activation exponents");
+    if (n != h->arch->ntensors) return y355_fail(Y355_EINVAL, "one exponent per tensor expected");
+    for (int i = 0; i < n; ++i)
+        if (sa[i] < -64 || sa[i] > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
+    if (sa_in < -64 || sa_in > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
+    return install_act_exponents(h, sa_in, sa, n, true);
 }
 
 extern "C" int y355_net_layer_route(y355_net *h, int idx, int32_t *route) {
@@ -1127,14 +1213,14 @@ static void act_fixed(int act, int *lk, int *neg_mul) {
     else { *lk = 0; *neg_mul = 1; }
 }
 
-static int refresh_i8(y355_net *h) {
-    if (!h->sa_ok) return y355_fail(Y355_ENOTREADY, "activation exponents not set (calibrate first)");
-    for (int i = 0; i < h->arch->nops; ++i) {
+// epilogue constants of the convolution of op i for the handle's current exponents (dirty layers only)
+static int refresh_layer_i8(y355_net *h, int i) {
+    {
         const OpDef &o = h->arch->ops[i];
-        if (o.type != OP_CONV1 && o.type != OP_CONV) continue;
+        if (o.type != OP_CONV1 && o.type != OP_CONV) return 0;
         NLayer &L = h->L[o.layer];
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
-        if (!L.dirty) continue;
+        if (!L.dirty) return 0;
         const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in], sa_o = h->sa[o.out];
         const int F = std::max(sa_i + L.e_w, L.e_b);
         const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;      // shl: of the channels with the largest exponent, the smallest
@@ -1231,6 +1317,13 @@ static int refresh_i8(y355_net *h) {
         HIPCHK(hipStreamSynchronize(h->stream));
         L.dirty = false;
     }
+    return 0;
+}
+
+static int refresh_i8(y355_net *h) {
+    if (!h->sa_ok) return y355_fail(Y355_ENOTREADY, "activation exponents not set (calibrate first)");
+    for (int i = 0; i < h->arch->nops; ++i)
+        if (int rc = refresh_layer_i8(h, i)) return rc;
     if (h->front_graph && h->front_dirty) {
         // front.hip's epilogue has ONE accumulator shift per layer: a per-channel layer runs on conv1.hip / convg.hip instead
         const bool pc = h->L[h->arch->ops[0].layer].pc || h->L[h->arch->ops[1].layer].pc;
@@ -1359,6 +1452,13 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
             p.rq = L.rq1;
             p.mode = 0;
             p.guard = 0;
+            if (h->calibrating && L.dirty) {                   // statistics pass of a calibration step (cal_conv_max): max |t'| only
+                p.mode = 1;
+                p.ctr = h->cal_dev + i;
+                p.bias_t = nullptr;
+                p.shl_c = L.shl_dev;
+                p.rq.gen32 = 0;
+            }
             y355_launch_conv1(p, s);
             HIPCHK(hipGetLastError());
             return 0;
@@ -1416,7 +1516,13 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
         p.slope = act_slope(o.act);
         p.out_f32 = to.pred && h->bf;
         p.grid_limit = h->tput_wgs;
-        if (L.rid == -2) {                                     // int8 1x1: pointwise kernel (convr.hip)
+        if (h->calibrating && L.dirty) {                       // statistics pass of a calibration step (cal_conv_max)
+            p.ctr = h->cal_dev + i;
+            ki.launch_stat(p, p.tiles_x * p.tiles_y * p.nblk * B, s);
+            HIPCHK(hipGetLastError());
+            return 0;
+        }
+        if (L.rid == -2 && !h->calibrating) {                  // int8 1x1: pointwise kernel (convr.hip)
             ConvGParams q = p;
             q.w = L.wr_dev;
             q.nblk = L.cout_pad / 64;
@@ -1435,7 +1541,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
                 return 0;
             }
         }
-        if (L.rid >= 0) {                                      // 3x3: weights through an LDS ring (convr.hip)
+        if (L.rid >= 0 && !h->calibrating) {                   // 3x3: weights through an LDS ring (convr.hip)
             ConvGParams q = p;
             q.w = L.wr_dev;
             q.nblk = L.cout_pad / y355_convr_info(L.rid)->bn;
@@ -1863,6 +1969,293 @@ extern "C" int y355_net_profile_get(y355_net *h, float *ms) {
     HIPCHK(hipEventSynchronize(h->ev[n]));
     for (int i = 0; i < n; ++i) HIPCHK(hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
     return 0;
+}
+
+// ------------------------------------------------------------------------------------------
+// Calibration on the int8 graph itself: the reference's forward(x, quantization=True) with freeze = not trainable
+// (models/slim_yolo_v2.py:212-328, AveragedRangeTracker :9-38; the loop of retune_bias_quantize.py:357-369) as ONE pass over
+// the op table.  Semantics: include/yolo355.h (y355_net_calibrate), DESIGN.md section 6.
+extern "C" int y355_net_num_trackers(y355_net *h) { return h ? h->arch->ntensors + 1 : Y355_EINVAL; }
+
+extern "C" int y355_net_get_trackers(y355_net *h, float *scale, int32_t *first_a, int n) {
+    if (!h || !scale || !first_a) return y355_fail(Y355_EINVAL, "null argument");
+    if (h->bf) return y355_fail(Y355_EINVAL, "bf16 nets have no trackers");
+    if (n != h->arch->ntensors + 1) return y355_fail(Y355_EINVAL, "one tracker for the input and one per tensor expected");
+    for (int i = 0; i < n; ++i) {
+        scale[i] = h->trk_scale[i];
+        first_a[i] = h->trk_first[i];
+    }
+    return 0;
+}
+
+extern "C" int y355_net_set_trackers(y355_net *h, const float *scale, const int32_t *first_a, int n) {
+    if (!h || !scale || !first_a) return y355_fail(Y355_EINVAL, "null argument");
+    if (h->bf) return y355_fail(Y355_EINVAL, "bf16 nets have no trackers");
+    if (n != h->arch->ntensors + 1) return y355_fail(Y355_EINVAL, "one tracker for the input and one per tensor expected");
+    // exponents of the trackers that have seen a batch: floor(log2(scale)) (:33); the others keep the handle's
+    int sa_in = h->sa_in;
+    std::vector<int32_t> sa(h->sa.begin(), h->sa.end());
+    bool all = true;
+    for (int i = 0; i < n; ++i) {
+        if (!first_a[i]) { all = false; continue; }
+        if (!(scale[i] > 0.f) || !std::isfinite(scale[i])) return y355_fail(Y355_EINVAL, "tracker scale is not a positive finite number");
+        const int e = (int)std::floor(std::log2(scale[i]));
+        if (e < -64 || e > 64) return y355_fail(Y355_EINVAL, "tracker exponent out of range");
+        if (i == 0) sa_in = e;
+        else sa[i - 1] = e;
+    }
+    if (int rc = install_act_exponents(h, sa_in, sa.data(), n - 1, all)) return rc;
+    for (int i = 0; i < n; ++i) {
+        h->trk_scale[i] = scale[i];
+        h->trk_first[i] = first_a[i] ? 1 : 0;
+    }
+    return 0;
+}
+
+// the statistics pass of the convolution of op i: its 64-bit epilogue up to t' (residual: up to the sum u) for the exponents in
+// front of it -- none of this depends on the output's exponent -- then max |.| as the fp32 value y355_calibrate forms from
+// absmax_t / frac_bits (engine.hip).  Leaves the layer dirty: refresh_layer_i8 rebuilds its constants for the write pass.
+static int cal_conv_max(y355_net *h, int i, int B, const NetInput &in, float *out_max) {
+    const OpDef &o = h->arch->ops[i];
+    NLayer &L = h->L[o.layer];
+    if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
+    const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in];
+    const int F = std::max(sa_i + L.e_w, L.e_b);
+    const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;
+    int lk, nm;
+    act_fixed(o.act, &lk, &nm);
+    int fb = F + lk;                                           // exponent of the tracked integers
+    if (shl_max(L, F, sa_i) > 24 || bshl > 40) return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
+    std::vector<long long> bw(L.cout_pad, 0);
+    std::vector<int> shc(L.cout_pad, 0);
+    long double bmax = 0;
+    for (int c = 0; c < L.cout; ++c) {
+        bw[c] = (long long)L.q_b[c] * (1ll << bshl);
+        shc[c] = F - sa_i - L.e_wc[c];
+        bmax = std::max(bmax, (long double)std::llabs(bw[c]));
+    }
+    long double lim = (acc_bound(L, o, F, sa_i, false) + bmax) * std::max(std::ldexp(1.0L, lk), (long double)nm);
+    L.rr = ResQ{};
+    if (o.res1) {
+        const int s_r = h->sa[o.res1 - 1], G = std::max(fb, s_r);
+        L.rr.t_sh = G - fb;
+        L.rr.r_sh = G - s_r;
+        if (L.rr.t_sh > 62 || L.rr.r_sh > 62) return y355_fail(Y355_ERANGE, "residual layer: exponent gap too large");
+        lim = lim * std::ldexp(1.0L, L.rr.t_sh) + 127.0L * std::ldexp(1.0L, L.rr.r_sh);
+        fb = G;
+    }
+    if (lim >= std::ldexp(1.0L, 62)) return y355_fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
+    L.rq = RequantG{};
+    L.rq.shl = shl; L.rq.lk = lk; L.rq.neg_mul = nm;
+    L.rq1 = Requant{};
+    L.rq1.shl = shl; L.rq1.leaky = (lk || nm != 1) ? 1 : 0; L.rq1.lk = lk; L.rq1.neg_mul = nm; L.rq1.guard_log2 = 63; L.rq1.wide = 1;
+    L.dirty = true;
+    HIPCHK(hipMemcpyAsync(L.shl_dev, shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(L.bias_w_dev, bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));                   // (the host vectors go out of scope)
+    if (int rc = run_op(h, i, B, in)) return rc;               // calibrating && dirty: the statistics launch
+    unsigned long long m = 0;
+    HIPCHK(hipMemcpyAsync(&m, &h->cal_dev[i].absmax, 8, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    *out_max = (float)(int64_t)m * std::ldexp(1.0f, -fb);
+    return 0;
+}
+
+// one 32-bit maximum of slot i (fp32 bits or an unsigned int) back to the host
+static int cal_read_u32(y355_net *h, int i, unsigned int *v) {
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipMemcpyAsync(v, &h->cal_dev[i].absmax, 4, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    return 0;
+}
+
+static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze, double momentum, std::vector<float> &mx) {
+    const ArchDef &A = *h->arch;
+    const int nops = A.nops, nt = A.ntensors;
+    hipStream_t s = h->stream;
+    const std::vector<float> pre_scale = h->trk_scale;
+    const std::vector<int> pre_first = h->trk_first;
+    HIPCHK(hipMemsetAsync(h->cal_dev, 0, sizeof(Counters) * (nops + 1), s));
+    bool need_zero = false;
+    h->ctr_dev = h->ctrs.begin(&need_zero);                    // the write passes count their clamps as a forward does
+    if (need_zero) HIPCHK((hipError_t)y355_zero_counters(h->ctr_dev, nops + 1, s));
+    h->t0_skipped = false;
+    auto step = [&](int k, float m, int *e) -> int {           // tracker k sees m
+        int32_t first = h->trk_first[k], ex = 0;
+        if (int rc = y355_tracker_step(&h->trk_scale[k], &first, m, freeze, momentum, &ex)) return rc;
+        h->trk_first[k] = first;
+        mx[k] = m;
+        *e = ex;
+        return 0;
+    };
+    // ---- tracker 0: max |x| of the fp32 input / of the normalised resized frames
+    if (in.stage) {                                            // slim / tiny frames of another size: the resize stage first
+        y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, s);
+        HIPCHK(hipGetLastError());
+    }
+    unsigned int *slot_in = (unsigned int *)&h->cal_dev[nops].absmax;
+    if (in.x) {
+        y355_launch_absmax(in.x, (size_t)B * 3 * h->cfg.height * h->cfg.width, slot_in, s);
+    } else {
+        const bool staged = in.stage != nullptr || A.ops[0].type != OP_INPUT;      // in.u8 is at the network size
+        const size_t total = (size_t)B * h->cfg.height * h->cfg.width;
+        hipLaunchKernelGGL(absmax_u8_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, in.u8,
+                           staged ? (const int *)nullptr : in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, h->norm, slot_in);
+    }
+    unsigned int bits = 0;
+    if (int rc = cal_read_u32(h, nops, &bits)) return rc;
+    float m = 0.f;
+    memcpy(&m, &bits, 4);
+    int e = 0;
+    if (int rc = step(0, m, &e)) return rc;
+    h->sa_in = e;
+    // ---- the op table in graph order; first[t]: the op that produced tensor t first, late[t]: a later producer was seen
+    std::vector<int> first(nt, -1), late(nt, 0);
+    NetInput run = in;
+    run.stage = nullptr;                                       // (already resized)
+    for (int i = 0; i < nops; ++i) {
+        const OpDef &o = A.ops[i];
+        const bool inplace = o.type == OP_SPP;
+        float mo = 0.f;
+        if (o.type == OP_CONV1 || o.type == OP_CONV) {
+            if (int rc = cal_conv_max(h, i, B, run, &mo)) return rc;
+        } else if (o.type == OP_UPSAMPLE) {
+            const Tensor &ti = h->T[o.in], &to = h->T[o.out];
+            const size_t total = (size_t)B * to.H * to.W * o.cin;
+            const float ry = (float)(ti.H - 1) / (float)(to.H - 1), rx = (float)(ti.W - 1) / (float)(to.W - 1);
+            hipLaunchKernelGGL(upsample_i8_max_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, ti.dev, B,
+                               ti.H, ti.W, (int)ti.pb, o.cin, ry, rx, (unsigned int *)&h->cal_dev[i].absmax);
+            if (int rc = cal_read_u32(h, i, &bits)) return rc;
+            memcpy(&mo, &bits, 4);
+            mo *= std::ldexp(1.0f, -h->sa[o.in]);
+        } else if (o.type == OP_REORG) {
+            const Tensor &ti = h->T[o.in];
+            const size_t total = (size_t)B * ti.H * ti.W * o.cin;
+            hipLaunchKernelGGL(absmax_i8_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, ti.dev, B, ti.H,
+                               ti.W, (int)ti.pb, o.cin, (unsigned int *)&h->cal_dev[i].absmax);
+            if (int rc = cal_read_u32(h, i, &bits)) return rc;
+            mo = (float)bits * std::ldexp(1.0f, -h->sa[o.in]);
+        }
+        if (o.type == OP_INPUT || o.type == OP_POOL) {         // aliases: the entry mirrors its source's
+            const int src = o.type == OP_INPUT ? 0 : o.in + 1;
+            h->trk_scale[o.out + 1] = h->trk_scale[src];
+            h->trk_first[o.out + 1] = h->trk_first[src];
+            mx[o.out + 1] = mx[src];
+            h->sa[o.out] = o.type == OP_INPUT ? h->sa_in : h->sa[o.in];
+            first[o.out] = i;
+        } else if (!inplace) {
+            if (first[o.out] < 0) {                            // the tensor's first producer: its exponent for this step
+                first[o.out] = i;
+                if (int rc = step(o.out + 1, mo, &e)) return rc;
+                h->sa[o.out] = e;
+            } else {                                           // a later producer writes with that exponent
+                late[o.out] = 1;
+                mx[o.out + 1] = std::max(mx[o.out + 1], mo);
+            }
+        }
+        if (int rc = refresh_layer_i8(h, i)) return rc;        // the write pass's constants
+        if (int rc = run_op(h, i, B, run)) return rc;
+    }
+    // ---- buffers with several producers: the update redone from the pre-step state with the maximum over all of them
+    for (int t = 0; t < nt; ++t) {
+        if (!late[t]) continue;
+        h->trk_scale[t + 1] = pre_scale[t + 1];
+        h->trk_first[t + 1] = pre_first[t + 1];
+        if (int rc = step(t + 1, mx[t + 1], &e)) return rc;
+        h->sa[t] = e;
+    }
+    for (int i = 0; i < nops; ++i) {
+        const OpDef &o = A.ops[i];
+        if (o.type != OP_POOL) continue;
+        h->trk_scale[o.out + 1] = h->trk_scale[o.in + 1];
+        h->trk_first[o.out + 1] = h->trk_first[o.in + 1];
+        mx[o.out + 1] = mx[o.in + 1];
+        h->sa[o.out] = h->sa[o.in];
+    }
+    // the exponents the handle keeps: the residual range proof of y355_net_set_act_exponents
+    for (int i = 0; i < nops; ++i) {
+        const OpDef &o = A.ops[i];
+        if (o.type != OP_CONV || !o.res1) continue;
+        ResQ rr{};
+        int narrow = 0;
+        if (res_params(h, o, h->L[o.layer], &rr, &narrow))
+            return y355_fail(Y355_ERANGE, "residual layer: the 64-bit sum of the residual epilogue is not provably in range "
+                                          "for these exponents");
+    }
+    HIPCHK(hipStreamSynchronize(s));
+    return 0;
+}
+
+static int net_calibrate(y355_net *h, const NetInput &in, int B, int freeze, double momentum, int32_t *sa_in_out, int32_t *sa_out,
+                         float *max_out) {
+    const int keep_in = h->sa_in;
+    const bool keep_ok = h->sa_ok;
+    const std::vector<int> keep = h->sa;
+    const std::vector<float> keep_scale = h->trk_scale;
+    const std::vector<int> keep_first = h->trk_first;
+    std::vector<float> mx(h->arch->ntensors + 1, 0.f);
+    h->calibrating = true;
+    const int rc = net_calibrate_run(h, in, B, freeze, momentum, mx);
+    h->calibrating = false;
+    for (auto &L : h->L) L.dirty = true;
+    h->front_dirty = true;
+    if (rc) {                                                  // the handle keeps the pre-step state
+        const std::string msg = y355_last_error();
+        (void)hipStreamSynchronize(h->stream);
+        h->sa_in = keep_in;
+        h->sa = keep;
+        h->sa_ok = keep_ok;
+        h->trk_scale = keep_scale;
+        h->trk_first = keep_first;
+        return y355_fail(rc, msg);
+    }
+    h->sa_ok = true;
+    if (sa_in_out) *sa_in_out = h->sa_in;
+    for (int t = 0; sa_out && t < h->arch->ntensors; ++t) sa_out[t] = h->sa[t];
+    for (int k = 0; max_out && k <= h->arch->ntensors; ++k) max_out[k] = mx[k];
+    return 0;
+}
+
+static int cal_check(y355_net *h, const void *input, int batch, double momentum, int n) {
+    if (!h || !input) return y355_fail(Y355_EINVAL, "null argument");
+    if (h->bf) return y355_fail(Y355_EINVAL, "calibration steps run on int8 nets");
+    if (n != h->arch->ntensors + 1) return y355_fail(Y355_EINVAL, "one tracker for the input and one per tensor expected");
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (!(momentum >= 0.0 && momentum <= 1.0)) return y355_fail(Y355_EINVAL, "momentum outside [0, 1]");
+    for (const auto &L : h->L)
+        if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
+    return 0;
+}
+
+extern "C" int y355_net_calibrate(y355_net *h, const float *x_dev, int batch, int freeze, double momentum, int32_t *sa_in_out,
+                                  int32_t *sa_out, float *max_out, int n) {
+    if (int rc = cal_check(h, x_dev, batch, momentum, n)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    NetInput in;
+    in.x = x_dev;
+    return net_calibrate(h, in, batch, freeze, momentum, sa_in_out, sa_out, max_out);
+}
+
+extern "C" int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int freeze,
+                                     double momentum, int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n) {
+    if (int rc = cal_check(h, frames_dev, batch, momentum, n)) return rc;
+    if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    const int H = h->cfg.height, W = h->cfg.width;
+    NetInput in;                                               // as y355_net_forward_u8 (conv1.hip reads single bytes: no alignment rule)
+    in.u8 = frames_dev;
+    in.sh = src_h;
+    in.sw = src_w;
+    const bool fused = h->arch->ops[0].type == OP_INPUT;
+    if (src_h != H || src_w != W) {
+        if (int rc = net_resize_tables(h, src_h, src_w, !fused)) return rc;
+        in.tab = h->rs_tab;
+        if (!fused) {
+            in.stage = frames_dev;
+            in.u8 = h->rs_frames;
+        }
+    }
+    return net_calibrate(h, in, batch, freeze, momentum, sa_in_out, sa_out, max_out);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -479,6 +479,9 @@ struct ConvGInfo {
     size_t lds_bytes;
     void (*launch)(const ConvGParams &p, int nblocks, hipStream_t s);
     int (*prepare)(void);
+    // int8: statistics mode -- max |t'| (residual layers: |u|) over the un-pooled outputs into p.ctr->absmax, nothing stored;
+    // p.bias_w plain 64-bit biases, p.shl_w when p.pc (y355_net_calibrate)
+    void (*launch_stat)(const ConvGParams &p, int nblocks, hipStream_t s);
 };
 #define Y355_G_COUNT 11
 const ConvGInfo *y355_convg_kernel(int bf, int id);

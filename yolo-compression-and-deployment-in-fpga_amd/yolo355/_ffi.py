@@ -212,6 +212,13 @@ _SIGS = {
     "y355_net_get_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
     "y355_net_get_tensor": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_void_p]),
     "y355_net_tensor_absmax": (C.c_int, [C.c_void_p, C.c_int, C.c_int, P(C.c_float)]),
+    "y355_net_num_trackers": (C.c_int, [C.c_void_p]),
+    "y355_net_set_trackers": (C.c_int, [C.c_void_p, P(C.c_float), P(C.c_int32), C.c_int]),
+    "y355_net_get_trackers": (C.c_int, [C.c_void_p, P(C.c_float), P(C.c_int32), C.c_int]),
+    "y355_net_calibrate": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_double, P(C.c_int32), P(C.c_int32), P(C.c_float),
+                                     C.c_int]),
+    "y355_net_calibrate_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, P(C.c_int32),
+                                        P(C.c_int32), P(C.c_float), C.c_int]),
     "y355_net_max_det": (C.c_int, [C.c_void_p]),
     "y355_net_num_anchors_total": (C.c_int, [C.c_void_p]),
     "y355_net_sync": (C.c_int, [C.c_void_p]),

@@ -323,12 +323,12 @@ class _NetModel(nn.Module):
         sizes_wh: [B,2] original (width, height) per image: the boxes come back in pixels of the original images
         (the evaluators' `bboxes *= [[w, h, w, h]]`, test.py:88-90, on the GPU)."""
         self._check_inference()
-        net = self._get_net(int(x.shape[0]))
         if not quantization:
+            net = self._get_net(int(x.shape[0]))
             net.set_thresholds(self.conf_thresh, self.nms_thresh)
             return net.forward(x, sizes_wh=sizes_wh)
-        if self.act_exponents is None:
-            self.act_exponents = net.calibration_exponents(x)
+        if self.act_exponents is None:                     # (a model calibrate()d on its int8 net never builds the bf16 one)
+            self.act_exponents = self._get_net(int(x.shape[0])).calibration_exponents(x)
         qnet = self._get_net(int(x.shape[0]), int8=True)
         qnet.set_act_exponents(*self.act_exponents)
         qnet.set_thresholds(self.conf_thresh, self.nms_thresh)
@@ -351,8 +351,53 @@ class _NetModel(nn.Module):
         net.set_thresholds(self.conf_thresh, self.nms_thresh)
         return net.forward_frames(frames, sizes_wh=sizes_wh)
 
+    def calibrate(self, x, freeze=False):
+        """One calibration step on the int8 net itself (Net.calibrate): the reference's forward(x, quantization=True)
+        with freeze = not trainable (models/slim_yolo_v2.py:212-328; the loop of retune_bias_quantize.py:357-369) on this
+        graph -- first call: scale = 127 / max; later calls the EMA, or unchanged with freeze=True.  No bf16 net is built.
+        Stores act_exponents for forward_batch(x, quantization=True) / forward_frames and keeps the tracker state in the
+        buffers act_tracker_scale / act_tracker_first_a (registered at the first call: they travel in the state_dict).
+        Returns (sa_in, [sa per tensor])."""
+        return self._calibrate_step(lambda net: net.calibrate(x, freeze=freeze), int(x.shape[0]))
+
+    def calibrate_frames(self, frames, freeze=False):
+        """calibrate() on camera frames, uint8 [B,h,w,3] BGR of any size (Net.calibrate_frames)."""
+        Net.check_frames(frames)
+        return self._calibrate_step(lambda net: net.calibrate_frames(frames, freeze=freeze), int(frames.shape[0]))
+
+    def _calibrate_step(self, step, batch):
+        self._check_inference()
+        qnet = self._get_net(batch, int8=True)
+        if hasattr(self, "act_tracker_scale"):             # the state this model carries (a reloaded state_dict, an earlier net)
+            qnet.trackers = (self.act_tracker_scale.cpu().numpy(), self.act_tracker_first_a.cpu().numpy())
+        self.act_exponents = step(qnet)
+        scale, first = qnet.trackers
+        self._register_trackers(len(scale))
+        with torch.no_grad():
+            self.act_tracker_scale.copy_(torch.from_numpy(scale))
+            self.act_tracker_first_a.copy_(torch.from_numpy(first))
+        return self.act_exponents
+
+    def _register_trackers(self, n):
+        if not hasattr(self, "act_tracker_scale"):
+            self.register_buffer("act_tracker_scale", torch.zeros(n, dtype=torch.float32))
+            self.register_buffer("act_tracker_first_a", torch.zeros(n, dtype=torch.int32))
+
+    def load_state_dict(self, state_dict, *args, **kwargs):
+        """A calibrated model's state_dict carries its tracker buffers: they are registered here before the load, and the
+        exponents floor(log2(scale)) (models/slim_yolo_v2.py:33) become act_exponents again -- only when every tracker has
+        seen a batch (first_a != 0 everywhere); otherwise act_exponents stays as it was.  A model that has been calibrated
+        has the two buffers for good: loading an uncalibrated state_dict into it needs strict=False."""
+        if "act_tracker_scale" in state_dict:
+            self._register_trackers(int(state_dict["act_tracker_scale"].shape[0]))
+        out = super().load_state_dict(state_dict, *args, **kwargs)
+        if "act_tracker_scale" in state_dict and bool((self.act_tracker_first_a != 0).all()):
+            e = [prep.RangeTracker(s.reshape(1), 1).exponent() for s in self.act_tracker_scale.detach().cpu()]
+            self.act_exponents = (e[0], e[1:])
+        return out
+
     def _weights_version(self):
-        t = list(self.parameters()) + list(self.buffers())
+        t = list(self.parameters()) + [b for n, b in self.named_buffers() if not n.startswith("act_tracker_")]
         return tuple(int(p._version) for p in t) + tuple(p.data_ptr() for p in t)
 
     act_exponents = None      # (sa_in, [sa per tensor]) of the int8 path, frozen at the first quantized call

@@ -309,6 +309,74 @@ class Net:
             sa.append(RangeTracker().update(m, True))
         return sa_in, sa
 
+    # ---- calibration on the int8 graph itself (y355_net_calibrate; semantics in include/yolo355.h and DESIGN.md section 6)
+    @property
+    def num_trackers(self):
+        return self.num_tensors + 1
+
+    @property
+    def trackers(self):
+        """(scale float32 [1 + num_tensors], first_a int32 [...]): the AveragedRangeTracker state of the network input
+        and of every tensor in graph order.  Assigning installs the state and the exponents of the trackers that have seen a
+        batch (first_a != 0)."""
+        n = self.num_trackers
+        scale = np.zeros(n, np.float32)
+        first = np.zeros(n, np.int32)
+        _ffi.check(self._lib.y355_net_get_trackers(self._h, scale.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   first.ctypes.data_as(C.POINTER(C.c_int32)), n))
+        return scale, first
+
+    @trackers.setter
+    def trackers(self, state):
+        scale = np.ascontiguousarray(np.asarray(state[0], np.float32).reshape(-1))
+        first = np.ascontiguousarray(np.asarray(state[1]).reshape(-1).astype(np.int32))
+        if scale.shape != first.shape:
+            raise ValueError("trackers: scale and first_a differ in length")
+        _ffi.check(self._lib.y355_net_set_trackers(self._h, scale.ctypes.data_as(C.POINTER(C.c_float)),
+                                                   first.ctypes.data_as(C.POINTER(C.c_int32)), int(scale.shape[0])))
+
+    def _calibrate(self, fn, head, freeze, momentum):
+        n = self.num_trackers
+        sa_in = C.c_int32()
+        sa = (C.c_int32 * (n - 1))()
+        mx = np.zeros(n, np.float32)
+        self._call(fn, *head, 1 if freeze else 0, float(momentum), C.byref(sa_in), sa, mx.ctypes.data_as(C.POINTER(C.c_float)), n)
+        self.last_calibration_max = mx
+        return sa_in.value, list(sa)
+
+    def calibrate(self, x, freeze=False, momentum=0.1):
+        """One calibration step of an int8 net on batch x (fp32 [B,3,H,W]): every tracker sees the maximum of its tensor
+        on the quantized graph, behind the exponents already updated in front of it.  Returns (sa_in, [sa per tensor]),
+        which the handle now runs with; last_calibration_max holds the float32 maximum every tracker saw."""
+        xd = self._dev_input(x)
+        return self._calibrate(self._lib.y355_net_calibrate, (xd.data_ptr(), int(xd.shape[0])), freeze, momentum)
+
+    def calibrate_frames(self, frames, freeze=False, momentum=0.1):
+        """calibrate() on camera frames, uint8 [B,h,w,3] BGR of any size: the step on
+        synth.normalize_frames(resize_linear_u8(frames)), bit for bit."""
+        fd = self._dev_frames(frames)
+        B, hh, ww = (int(v) for v in fd.shape[:3])
+        return self._calibrate(self._lib.y355_net_calibrate_u8, (fd.data_ptr(), hh, ww, B), freeze, momentum)
+
+    @classmethod
+    def from_package(cls, path, conf_thresh=None, nms_thresh=None, max_batch=1, max_det=0, device=None):
+        """An int8 net from a package of tools/prepare_net.py (integer weights, exponents, tracker state, meta): no fp32
+        weights are needed.  It runs, and calibrates further (calibrate / calibrate_frames), from the package alone."""
+        import json
+        with np.load(path, allow_pickle=False) as z:
+            meta = json.loads(str(z["meta"]))
+            net = cls(meta["arch"], meta["input_size"], meta["num_classes"], meta["anchors"],
+                      meta["conf_thresh"] if conf_thresh is None else conf_thresh,
+                      meta["nms_thresh"] if nms_thresh is None else nms_thresh, max_batch=max_batch, max_det=max_det,
+                      device=device, dtype="int8")
+            for i in range(net.num_layers):
+                e_w = z["e_w_%d" % i]
+                net.load_layer_i8(i, z["q_w_%d" % i], z["q_b_%d" % i], int(e_w) if e_w.ndim == 0 else e_w, int(z["e_b_%d" % i]))
+            net.set_act_exponents(int(z["sa_in"]), [int(v) for v in z["sa"]])
+            net.trackers = (z["tracker_scale"], z["tracker_first_a"])
+        net.package_meta = meta
+        return net
+
     def sync(self):
         _ffi.check(self._lib.y355_net_sync(self._h))
 

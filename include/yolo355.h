@@ -580,6 +580,37 @@ int y355_net_calibrate(y355_net *h, const float *x_dev, int batch, int freeze, d
 int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch,
                           int freeze, double momentum, int32_t *sa_in_out, int32_t *sa_out,
                           float *max_out, int n);
+/* Frame lists: the reference's callers hand the network one image at a time, each of its own size (BaseTransform resizes
+ * per image, data/__init__.py:30-56; test.py:79-90 and the evaluator loops rescale by that image's own (w, h)).  A list is
+ * `batch` frames, each with its own device pointer, size and row pitch; the frames need not share an allocation and no
+ * pointer needs any alignment.  One ragged resize stage (csrc/resize.hip: the arithmetic of y355_net_resize_u8 with the
+ * taps addressed through the pitch, coefficient tables built on the device per frame) writes every frame into the net-owned
+ * buffer at the network size -- a frame already at that size goes through it too, as the identity -- and the forward then is
+ * y355_net_forward_u8 on that buffer.
+ * y355_net_forward_frames: for image i the detections, slice i of every tap tensor (Y355_F_TAP) and the candidates equal
+ * y355_net_forward_u8(h, frames[i].data_dev, height_i, width_i, 1, ...) bit for bit (frames[i] packed); y355_net_counters
+ * is the sum of the clamp counts of those single calls.  With y355_net_profile on, the first timer (op 0) includes the
+ * stage.
+ * y355_net_resize_frames: the stage alone into out_dev [batch][H][W][3] (parity tap), on the net's stream.
+ * y355_net_calibrate_frames: y355_net_calibrate_u8 on the y355_net_resize_frames output at the network size, bit for bit
+ * (a calibration step sees the maximum over the whole batch); arguments, errors and the state a failing step leaves as
+ * y355_net_calibrate_u8.
+ * The `frames` array is read during the call only.  Apart from the first list call of a handle, which allocates the stage's
+ * buffers, a call does not synchronise with the device, allocate or copy: lists whose sizes change from call to call cost
+ * the same as lists whose sizes repeat.
+ * Errors, checked before any HIP call: a null handle / array / output, a batch outside 1..max_batch, a null data_dev, a size
+ * outside 1..16384 or a row_bytes in 1..3 * width - 1 are Y355_EINVAL (and, for y355_net_calibrate_frames, a bf16 net or a
+ * wrong n; unloaded weights Y355_ENOTREADY). */
+typedef struct y355_frame {
+    const uint8_t *data_dev;   /* uint8 HWC BGR, device pointer, any alignment */
+    int32_t height, width;     /* 1 .. 16384 each */
+    int64_t row_bytes;         /* pitch of one row; 0 = width * 3 (packed); otherwise >= width * 3 */
+} y355_frame;
+int y355_net_forward_frames(y355_net *h, const y355_frame *frames /* host array [batch] */, int batch, int flags,
+                            float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev);
+int y355_net_resize_frames(y355_net *h, const y355_frame *frames, int batch, uint8_t *out_dev /* [B][H][W][3] */);
+int y355_net_calibrate_frames(y355_net *h, const y355_frame *frames, int batch, int freeze, double momentum,
+                              int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n);
 int y355_net_max_det(y355_net *h);
 int y355_net_num_anchors_total(y355_net *h);
 int y355_net_sync(y355_net *h);

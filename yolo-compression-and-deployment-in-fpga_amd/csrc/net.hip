@@ -709,6 +709,7 @@ struct y355_net {
     int *rs_tab = nullptr;
     uint8_t *rs_frames = nullptr;
     int rs_src_h = 0, rs_src_w = 0;
+    int *rs_tabs = nullptr;           // frame lists (y355_net_forward_frames): [max_batch][3 (H + W)], one set of tables per frame
     // calibration on the int8 graph (y355_net_calibrate): AveragedRangeTracker state of the network input [0] and of every
     // tensor [1 + t] (models/slim_yolo_v2.py:13-14), and one slot of maxima per op ([nops]: the input) on the device
     std::vector<float> trk_scale;
@@ -719,13 +720,15 @@ struct y355_net {
 
 // the network input of one forward: an fp32 NCHW tensor, or uint8 HWC BGR frames (u8) of src_h x src_w with the resize tables
 // (tab, null when the frames are at the network size).  stage: frames [B][sh][sw][3] the forward first resizes into u8 (the
-// net-owned buffer) with tab, inside the first op's profile interval
+// net-owned buffer) with tab, inside the first op's profile interval.  list: a frame list (host array [batch]) the forward
+// first resizes into u8 (the net-owned buffer, then frames at the network size: tab null) in the same place
 struct NetInput {
     const float *x = nullptr;
     const uint8_t *u8 = nullptr;
     const int *tab = nullptr;
     int sh = 0, sw = 0;
     const uint8_t *stage = nullptr;
+    const y355_frame *list = nullptr;
 };
 
 static int in_kbytes(const y355_net *h, const OpDef &o);
@@ -1680,6 +1683,10 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
             y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, batch, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stream);
             HIPCHK(hipGetLastError());
         }
+        if (i == 0 && in.list) {                        // a frame list: the ragged stage, every frame through it
+            y355_launch_resize_frames(in.list, batch, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+            HIPCHK(hipGetLastError());
+        }
         if (fuse_front && i < 2) {
             if (i == 0) {
                 if (!h->L[h->arch->ops[0].layer].loaded || !h->L[h->arch->ops[1].layer].loaded)
@@ -1826,6 +1833,63 @@ extern "C" int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int sr
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (int rc = net_resize_tables(h, src_h, src_w, false)) return rc;
     y355_launch_resize_u8(frames_dev, out_dev, h->rs_tab, batch, src_h, src_w, h->cfg.height, h->cfg.width, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// ---- frame lists: every frame with its own pointer, size and pitch (the reference's callers: one image at a time, each of
+// its own size).  All frames, those at the network size included, go through the ragged stage of resize.hip into rs_frames;
+// the forward / calibration step then is the same-size uint8 path on that buffer (in.u8 = rs_frames, no table, no stage).
+// The stage builds its tables on the device and takes the descriptors as kernel arguments: nothing is uploaded, nothing
+// waits, whatever the sizes of the previous call were.
+static int frames_check(const y355_net *h, const y355_frame *frames, int batch) {
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    for (int i = 0; i < batch; ++i) {
+        const y355_frame &f = frames[i];
+        if (!f.data_dev) return y355_fail(Y355_EINVAL, "null frame pointer");
+        if (f.height < 1 || f.width < 1 || f.height > 16384 || f.width > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+        if (f.row_bytes != 0 && f.row_bytes < 3 * (int64_t)f.width) return y355_fail(Y355_EINVAL, "row_bytes below width * 3");
+    }
+    return 0;
+}
+
+// the stage's buffers, allocated at the first list call of a handle (frames: rs_frames is needed)
+static int net_list_buffers(y355_net *h, bool frames) {
+    const int H = h->cfg.height, W = h->cfg.width;
+    if (!h->rs_tabs)
+        if (int rc = nmalloc(h, (void **)&h->rs_tabs, sizeof(int) * 3 * (size_t)(H + W) * h->cfg.max_batch, false)) return rc;
+    if (frames && !h->rs_frames)
+        if (int rc = nmalloc(h, (void **)&h->rs_frames, (size_t)h->cfg.max_batch * H * W * 3, false)) return rc;
+    return 0;
+}
+
+static NetInput list_input(const y355_net *h, const y355_frame *frames) {
+    NetInput in;
+    in.u8 = h->rs_frames;
+    in.sh = h->cfg.height;
+    in.sw = h->cfg.width;
+    in.list = frames;
+    return in;
+}
+
+extern "C" int y355_net_forward_frames(y355_net *h, const y355_frame *frames, int batch, int flags, float *boxes_dev,
+                                       float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
+    if (!h || !frames || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
+    if (int rc = frames_check(h, frames, batch)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (!h->bf)
+        if (int rc = refresh_i8(h)) return rc;
+    if (int rc = net_list_buffers(h, true)) return rc;
+    return net_forward(h, list_input(h, frames), batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+}
+
+// parity tap of the ragged stage: the list -> out_dev [batch][H][W][3] at the network size, on the net's stream
+extern "C" int y355_net_resize_frames(y355_net *h, const y355_frame *frames, int batch, uint8_t *out_dev) {
+    if (!h || !frames || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
+    if (int rc = frames_check(h, frames, batch)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = net_list_buffers(h, false)) return rc;
+    y355_launch_resize_frames(frames, batch, out_dev, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -2093,6 +2157,10 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
         y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, s);
         HIPCHK(hipGetLastError());
     }
+    if (in.list) {                                             // a frame list: the ragged stage, every frame through it
+        y355_launch_resize_frames(in.list, B, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, s);
+        HIPCHK(hipGetLastError());
+    }
     unsigned int *slot_in = (unsigned int *)&h->cal_dev[nops].absmax;
     if (in.x) {
         y355_launch_absmax(in.x, (size_t)B * 3 * h->cfg.height * h->cfg.width, slot_in, s);
@@ -2113,6 +2181,7 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
     std::vector<int> first(nt, -1), late(nt, 0);
     NetInput run = in;
     run.stage = nullptr;                                       // (already resized)
+    run.list = nullptr;
     for (int i = 0; i < nops; ++i) {
         const OpDef &o = A.ops[i];
         const bool inplace = o.type == OP_SPP;
@@ -2256,6 +2325,15 @@ extern "C" int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int
         }
     }
     return net_calibrate(h, in, batch, freeze, momentum, sa_in_out, sa_out, max_out);
+}
+
+extern "C" int y355_net_calibrate_frames(y355_net *h, const y355_frame *frames, int batch, int freeze, double momentum,
+                                         int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n) {
+    if (int rc = cal_check(h, frames, batch, momentum, n)) return rc;
+    if (int rc = frames_check(h, frames, batch)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = net_list_buffers(h, true)) return rc;
+    return net_calibrate(h, list_input(h, frames), batch, freeze, momentum, sa_in_out, sa_out, max_out);
 }
 
 // ------------------------------------------------------------------------------------------

@@ -410,6 +410,12 @@ __device__ __forceinline__ void y355_resize_px(const uint8_t *s, const int *tab,
         out[c] = min(max(v, 0), 255);
     }
 }
+// a list of n frames (y355_frame of include/yolo355.h: own pointer, size and row pitch each, any alignment) -> dst [n][dh][dw][3]
+// (dst 4-byte aligned: whole dwords are stored; otherwise bytes), the same arithmetic with the taps addressed through the
+// pitch.  tabs [n][3 (dh + dw)] on the device: every frame's tables, built by a kernel of this launch (bit-identical to
+// y355_resize_tables).  The descriptors travel by value as kernel arguments, 64 frames per launch: `frames` is read here only
+struct y355_frame;
+void y355_launch_resize_frames(const y355_frame *frames, int n, uint8_t *dst, int *tabs, int dh, int dw, hipStream_t s);
 // the evaluators' `bboxes *= [[w, h, w, h]]` of every image, in place (engine.hip); wh [B][2]
 void y355_launch_scale_boxes(float *boxes, const int32_t *count, const float *wh, int batch, int max_det, hipStream_t s);
 

@@ -62,6 +62,11 @@ class ConvGeom(C.Structure):
         return "ConvGeom(%s)" % ", ".join("%s=%d" % (n, getattr(self, n)) for n, _ in self._fields_)
 
 
+class Frame(C.Structure):
+    """y355_frame: one frame of a list -- device pointer (any alignment), size, row pitch in bytes (0 = packed)"""
+    _fields_ = [("data_dev", C.c_void_p), ("height", C.c_int32), ("width", C.c_int32), ("row_bytes", C.c_int64)]
+
+
 class LayerStats(C.Structure):
     _fields_ = [("absmax_t", C.c_int64), ("frac_bits", C.c_int32), ("reserved", C.c_int32),
                 ("saturated", C.c_int64), ("guard", C.c_int64)]
@@ -219,6 +224,10 @@ _SIGS = {
                                      C.c_int]),
     "y355_net_calibrate_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, P(C.c_int32),
                                         P(C.c_int32), P(C.c_float), C.c_int]),
+    "y355_net_forward_frames": (C.c_int, [C.c_void_p, P(Frame), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_net_resize_frames": (C.c_int, [C.c_void_p, P(Frame), C.c_int, C.c_void_p]),
+    "y355_net_calibrate_frames": (C.c_int, [C.c_void_p, P(Frame), C.c_int, C.c_int, C.c_double, P(C.c_int32), P(C.c_int32),
+                                            P(C.c_float), C.c_int]),
     "y355_net_max_det": (C.c_int, [C.c_void_p]),
     "y355_net_num_anchors_total": (C.c_int, [C.c_void_p]),
     "y355_net_sync": (C.c_int, [C.c_void_p]),

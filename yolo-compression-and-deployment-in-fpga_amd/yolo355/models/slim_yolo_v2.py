@@ -351,6 +351,28 @@ class _NetModel(nn.Module):
         net.set_thresholds(self.conf_thresh, self.nms_thresh)
         return net.forward_frames(frames, sizes_wh=sizes_wh)
 
+    def forward_frame_list(self, frames, quantization=False, sizes_wh=None):
+        """forward_frames for a list of frames, each uint8 [h,w,3] BGR of its own size (numpy, CPU or CUDA torch, mixed) --
+        what the reference's callers have: one image at a time, resized per image by BaseTransform.  Element i equals
+        forward_frames(frames[i][None])[0], bit for bit.  sizes_wh="own" rescales every image's boxes by its own
+        (width, height) on the GPU (test.py:88-90); an array as forward_batch.  quantization=True needs the frozen
+        activation exponents, as forward_frames."""
+        Net.check_frame_list(frames)
+        self._check_inference()
+        if quantization and self.act_exponents is None:
+            raise RuntimeError("yolo355: the int8 activation exponents are not frozen yet: run one "
+                               "forward_batch(x, quantization=True) first")
+        net = self._get_net(len(frames), int8=bool(quantization))
+        if quantization:
+            net.set_act_exponents(*self.act_exponents)
+        net.set_thresholds(self.conf_thresh, self.nms_thresh)
+        return net.forward_frame_list(frames, sizes_wh=sizes_wh)
+
+    def calibrate_frame_list(self, frames, freeze=False):
+        """calibrate() on a list of camera frames of any sizes (Net.calibrate_frame_list)."""
+        Net.check_frame_list(frames)
+        return self._calibrate_step(lambda net: net.calibrate_frame_list(frames, freeze=freeze), len(frames))
+
     def calibrate(self, x, freeze=False):
         """One calibration step on the int8 net itself (Net.calibrate): the reference's forward(x, quantization=True)
         with freeze = not trainable (models/slim_yolo_v2.py:212-328; the loop of retune_bias_quantize.py:357-369) on this

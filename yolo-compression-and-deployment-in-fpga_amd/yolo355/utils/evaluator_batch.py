@@ -122,3 +122,68 @@ def coco_data_dict(net, dataset, transform, batch_size=64, num_images=None, **kw
     if pending is not None:
         unpack(pending[0], pending[1]())
     return ids, data_dict
+
+
+def _frame_batches(net, dataset, n, batch_size, **kw):
+    """(first image, ids, detections) per batch of raw frames: dataset.pull_image(i) -> (img uint8 HWC BGR of any size, id),
+    forward_frame_list with every image's boxes rescaled by its own (w, h) on the GPU.  No host transform."""
+    if not hasattr(net, "forward_frame_list"):
+        raise TypeError("%s has no forward_frame_list (the y355_net families have)" % type(net).__name__)
+    for i0, i1 in _batches(n, batch_size):
+        frames, bids = [], []
+        for i in range(i0, i1):
+            img, id_ = dataset.pull_image(i)
+            frames.append(img)
+            bids.append(id_)
+        yield i0, bids, net.forward_frame_list(frames, sizes_wh="own", **kw)
+
+
+def voc_all_boxes_frames(net, dataset, num_classes, batch_size=64, quantization=False, num_images=None):
+    """voc_all_boxes from the raw images: all_boxes[cls][image] = N x 5 float32 (x1, y1, x2, y2, score) as the loop of
+    utils/vocapi_evaluator_mask.py:57-82 builds it, with BaseTransform's resize and normalisation on the GPU.
+    dataset.pull_image(i) -> (img uint8 HWC BGR of any size, id) (data/voc0712.py:148-160); net: a y355_net family model.
+
+        # utils/vocapi_evaluator_mask.py:49-95  (evaluate)
+        - for i in range(num_images):
+        -     im, gt, h, w = self.dataset.pull_item(i)
+        -     x = Variable(im.unsqueeze(0)).to(self.device)
+        -     bboxes, scores, cls_inds = net(x, quantization=..., find=...)
+        -     scale = np.array([[w, h, w, h]]); bboxes *= scale ...
+        + self.all_boxes = voc_all_boxes_frames(net, self.dataset, len(self.labelmap), batch_size=64, quantization=quantization)
+    """
+    n = len(dataset) if num_images is None else int(num_images)
+    all_boxes = [[[] for _ in range(n)] for _ in range(num_classes)]
+    for i0, _, dets in _frame_batches(net, dataset, n, batch_size, quantization=quantization):
+        for k, (bboxes, scores, cls_inds) in enumerate(dets):
+            for j in range(num_classes):
+                inds = np.where(cls_inds == j)[0]
+                if len(inds) == 0:
+                    all_boxes[j][i0 + k] = np.empty([0, 5], dtype=np.float32)
+                    continue
+                all_boxes[j][i0 + k] = np.hstack((bboxes[inds], scores[inds][:, np.newaxis])).astype(np.float32, copy=False)
+    return all_boxes
+
+
+def coco_data_dict_frames(net, dataset, batch_size=64, num_images=None, **kw):
+    """coco_data_dict from the raw images: (ids, data_dict) as utils/cocoapi_evaluator.py:66-98 builds them, without the
+    host transform.  dataset.pull_image(i) -> (img uint8 HWC BGR of any size, id); dataset.class_ids maps class index ->
+    COCO id; kw: quantization=... of forward_frame_list.
+
+        # utils/cocoapi_evaluator.py:66-98
+        - for index in range(num_images):
+        -     img, id_ = self.dataset.pull_image(index)
+        -     x = torch.from_numpy(self.transform(img)[0][:, :, (2, 1, 0)]).permute(2, 0, 1)
+        -     bboxes, scores, cls_inds = model(x.unsqueeze(0).to(self.device)); bboxes *= scale ...
+        + ids, data_dict = coco_data_dict_frames(model, self.dataset, batch_size=64)
+    """
+    n = len(dataset) if num_images is None else int(num_images)
+    ids, data_dict = [], []
+    for _, bids, dets in _frame_batches(net, dataset, n, batch_size, **kw):
+        for id_, (bboxes, scores, cls_inds) in zip(bids, dets):
+            id_ = int(id_)
+            ids.append(id_)
+            for k, box in enumerate(bboxes):
+                x1, y1, x2, y2 = float(box[0]), float(box[1]), float(box[2]), float(box[3])
+                data_dict.append({"image_id": id_, "category_id": dataset.class_ids[int(cls_inds[k])],
+                                  "bbox": [x1, y1, x2 - x1, y2 - y1], "score": float(scores[k])})
+    return ids, data_dict

@@ -46,7 +46,7 @@ def slim_preds(layers, x):
 
 def tiny_preds(layers, x):
     """backbone/darknet.py:238-253 + models/tiny_yolo_v3.py:176-200.  Returns ([pred_1, pred_2], taps)
-    with taps in the tensor order of csrc/net.hip."""
+    with taps in the tensor order of csrc/net_arch.h."""
     t = torch.as_tensor(x, dtype=torch.float32)
     with torch.no_grad():
         taps = []

@@ -82,7 +82,7 @@ def conv_layer(q_in, sa_in, L, sa_out, slope, pool):
 
 
 def upsample_int(q_in, rescale):
-    """the fp32 expression of csrc/net.hip upsample_i8_kernel, operation for operation"""
+    """the fp32 expression of csrc/netops.hip upsample_i8_kernel, operation for operation"""
     B, C, H, W = q_in.shape
     Ho, Wo = 2 * H, 2 * W
     f = np.float32

@@ -71,7 +71,7 @@ def max_spread_of(qlayers):
     return max(int(np.max(L["e_w"]) - np.min(L["e_w"])) for L in qlayers)
 
 
-# SlimYOLOv2 as y355_net runs it in int8 (csrc/net.hip kSlimOps): a chain of 3x3 convs, (layer, pooled), LeakyReLU(0.125),
+# SlimYOLOv2 as y355_net runs it in int8 (csrc/net_arch.h kSlimOps): a chain of 3x3 convs, (layer, pooled), LeakyReLU(0.125),
 # the last one linear; tensor i is the output of layer i
 SLIM_POOL = [1, 1, 0, 1, 0, 1, 0, 0, 0, 0]
 

@@ -56,7 +56,7 @@ class Graph:
 
 
 def v2_graph():
-    """kV2Ops / kV2T of csrc/net.hip (models/yolo_v2.py:165-179)"""
+    """kV2Ops / kV2T of csrc/net_arch.h (models/yolo_v2.py:165-179)"""
     g = Graph()
     for C, d in [(3, 1), (32, 2), (64, 4), (128, 4), (64, 4), (128, 8), (256, 8), (128, 8), (256, 8), (256, 16),
                  (512, 16), (256, 16), (512, 16), (256, 16), (512, 16), (512, 32), (1024, 32), (512, 32), (1024, 32),
@@ -89,7 +89,7 @@ def v2_graph():
 
 
 def v3_graph(spp):
-    """V3Graph of csrc/net.hip (models/yolo_v3.py:203-231, yolo_v3_spp.py:31-36, backbone/darknet.py:112-161)"""
+    """V3Graph of csrc/net_arch.h (models/yolo_v3.py:203-231, yolo_v3_spp.py:31-36, backbone/darknet.py:112-161)"""
     g = Graph()
 
     def resblocks(x, ch, d, n, last_out=-1):

@@ -22,7 +22,7 @@ ARCHS = ("slim_yolo_v2", "tiny_yolo_v3", "yolo_v2", "yolo_v3", "yolo_v3_spp")
 
 
 def slim_graph():
-    """kSlimOps / kSlimT of csrc/net.hip (models/slim_yolo_v2.py:551-567)"""
+    """kSlimOps / kSlimT of csrc/net_arch.h (models/slim_yolo_v2.py:551-567)"""
     g = W.Graph()
     for C, d in [(16, 2), (32, 4), (64, 4), (64, 8), (128, 8), (128, 16), (256, 16), (256, 16), (256, 16), (None, 16)]:
         g.T(C, d)
@@ -35,7 +35,7 @@ def slim_graph():
 
 
 def tiny_graph():
-    """kTinyOps / kTinyT of csrc/net.hip = oracle.net_int8_oracle.TINY_OPS"""
+    """kTinyOps / kTinyT of csrc/net_arch.h = oracle.net_int8_oracle.TINY_OPS"""
     g = W.Graph()
     for C, d in zip(N.TINY_CH, [2, 4, 8, 16, 16, 32, 32, 32, 32, 32, 32, 16, 32, 16, 32]):
         g.T(C, d)

@@ -4,10 +4,11 @@
 //   Y355_ARCH_YOLO_V2, _YOLO_V3, _YOLO_V3_SPP  models/yolo_v2.py, yolo_v3.py, yolo_v3_spp.py (DarkNet-19 / DarkNet-53)
 // in two arithmetic types: bf16 (BN-folded fp32 weights, bf16 MFMA, fp32 accumulate) and int8
 // (per-tensor power-of-two quantisation, the recipe of retune_bias_quantize.py:73-119 applied
-// to these graphs).  Every conv is convg.hip; the ops between the convs are the small kernels
-// in this file.
+// to these graphs).  The op tables are net_arch.h; every conv is convg.hip; the ops between the convs are the small
+// kernels of netops.hip.
 #include "../../include/yolo355.h"
 #include "y355_common.h"
+#include "net_arch.h"
 
 #include <algorithm>
 #include <cmath>
@@ -26,193 +27,6 @@ int y355_prepare_kernels();
     } while (0)
 
 namespace {
-enum { OP_CONV1 = 0, OP_CONV, OP_POOL, OP_UPSAMPLE, OP_INPUT, OP_REORG, OP_SPP };
-enum { ACT_NONE = 0, ACT_L125, ACT_L100 };     // LeakyReLU(0.125) utils/modules.py:15; (0.1) backbone/darknet.py:18
-
-struct TensorDef { int C, div, pred; };        // channels; H = height / div; pred: prediction map (no halo)
-struct OpDef {
-    int type, in, out;
-    int choff;        // first channel written in `out` (concat by construction)
-    int layer;        // weight slot
-    int cin, cout;    // cout 0 = A * (5 + C); cin may be a leading channel range of a wider (concat) buffer
-    int ksize, pool, act;
-    int stride2;      // 1: 3x3 / pad 1 / stride 2 (backbone/darknet.py:124-141)
-    int res1;         // residual tensor + 1 added after the activation (darknet.py:36), 0 = none
-};
-struct ArchDef { int ntensors; const TensorDef *t; int nops; const OpDef *ops; int nlayers; int nlev; int pred_t[3]; float stride[3]; };
-
-// ---- SlimYOLOv2 (models/slim_yolo_v2.py:403-419, 551-567)
-const TensorDef kSlimT[] = {{16, 2, 0}, {32, 4, 0}, {64, 4, 0}, {64, 8, 0}, {128, 8, 0}, {128, 16, 0},
-                            {256, 16, 0}, {256, 16, 0}, {256, 16, 0}, {0, 16, 1}};
-const OpDef kSlimOps[] = {
-    {OP_CONV1, -1, 0, 0, 0, 3, 16, 3, 1, ACT_L125},
-    {OP_CONV, 0, 1, 0, 1, 16, 32, 3, 1, ACT_L125},
-    {OP_CONV, 1, 2, 0, 2, 32, 64, 3, 0, ACT_L125},
-    {OP_CONV, 2, 3, 0, 3, 64, 64, 3, 1, ACT_L125},
-    {OP_CONV, 3, 4, 0, 4, 64, 128, 3, 0, ACT_L125},
-    {OP_CONV, 4, 5, 0, 5, 128, 128, 3, 1, ACT_L125},
-    {OP_CONV, 5, 6, 0, 6, 128, 256, 3, 0, ACT_L125},
-    {OP_CONV, 6, 7, 0, 7, 256, 256, 3, 0, ACT_L125},
-    {OP_CONV, 7, 8, 0, 8, 256, 256, 3, 0, ACT_L125},
-    {OP_CONV, 8, 9, 0, 9, 256, 0, 3, 0, ACT_NONE},
-};
-// ---- YOLOv3tiny (backbone/darknet.py:215-253, models/tiny_yolo_v3.py:27-39, 176-200)
-// tensor 4 is the concat buffer [C_4 (256) | up(conv_1x1_2(C_5)) (128)] (:190)
-const TensorDef kTinyT[] = {{16, 2, 0}, {32, 4, 0}, {64, 8, 0}, {128, 16, 0}, {384, 16, 0}, {256, 32, 0}, {512, 32, 0},
-                            {512, 32, 0}, {1024, 32, 0}, {256, 32, 0}, {128, 32, 0}, {256, 16, 0}, {512, 32, 0},
-                            {0, 16, 1}, {0, 32, 1}};
-const OpDef kTinyOps[] = {
-    {OP_CONV1, -1, 0, 0, 0, 3, 16, 3, 1, ACT_L100},        // conv_1 + maxpool_1
-    {OP_CONV, 0, 1, 0, 1, 16, 32, 3, 1, ACT_L100},         // conv_2 + maxpool_2
-    {OP_CONV, 1, 2, 0, 2, 32, 64, 3, 1, ACT_L100},         // conv_3 + maxpool_3
-    {OP_CONV, 2, 3, 0, 3, 64, 128, 3, 1, ACT_L100},        // conv_4 + maxpool_4
-    {OP_CONV, 3, 4, 0, 4, 128, 256, 3, 0, ACT_L100},       // conv_5 = C_4
-    {OP_POOL, 4, 5, 0, -1, 256, 256, 2, 0, 0},             // maxpool_5 (2x2, stride 2)
-    {OP_CONV, 5, 6, 0, 5, 256, 512, 3, 0, ACT_L100},       // conv_6
-    {OP_POOL, 6, 7, 0, -1, 512, 512, 2, 1, 0},             // maxpool_6: ZeroPad2d((0,1,0,1)) + MaxPool(2, 1)
-    {OP_CONV, 7, 8, 0, 6, 512, 1024, 3, 0, ACT_L100},      // conv_7 = C_5
-    {OP_CONV, 8, 9, 0, 7, 1024, 256, 3, 0, ACT_L125},      // conv_set_2
-    {OP_CONV, 9, 10, 0, 8, 256, 128, 1, 0, ACT_L125},      // conv_1x1_2
-    {OP_UPSAMPLE, 10, 4, 256, -1, 128, 128, 0, 0, 0},      // bilinear x2, align_corners (:188)
-    {OP_CONV, 4, 11, 0, 9, 384, 256, 3, 0, ACT_L125},      // conv_set_1
-    {OP_CONV, 9, 12, 0, 10, 256, 512, 3, 0, ACT_L125},     // extra_conv_2
-    {OP_CONV, 12, 14, 0, 11, 512, 0, 1, 0, ACT_NONE},      // pred_2 (stride 32)
-    {OP_CONV, 11, 13, 0, 12, 256, 0, 1, 0, ACT_NONE},      // pred_1 (stride 16)
-};
-// ---- myYOLOv2 (models/yolo_v2.py:26-39, 165-179) on DarkNet-19 (backbone/darknet.py:40-110)
-const TensorDef kV2T[] = {
-    {3, 1, 0},                                                   //  0 input: bf16 NHWC16 / int8 NHWC32
-    {32, 2, 0}, {64, 4, 0},                                      //  1 conv_1+pool, 2 conv_2+pool
-    {128, 4, 0}, {64, 4, 0}, {128, 8, 0},                        //  3..5 conv_3 (last pooled)
-    {256, 8, 0}, {128, 8, 0}, {256, 8, 0}, {256, 16, 0},         //  6..8 conv_4 (8 = C_4), 9 maxpool_4
-    {512, 16, 0}, {256, 16, 0}, {512, 16, 0}, {256, 16, 0}, {512, 16, 0},   // 10..14 conv_5 (14 = C_5)
-    {512, 32, 0},                                                // 15 maxpool_5
-    {1024, 32, 0}, {512, 32, 0}, {1024, 32, 0}, {512, 32, 0}, {1024, 32, 0},   // 16..20 conv_6 (20 = C_6)
-    {1024, 32, 0},                                               // 21 convsets_1[0]
-    {64, 16, 0},                                                 // 22 route_layer
-    {1280, 32, 0},                                               // 23 cat(reorg(route) [0:256), convsets_1 [256:1280))
-    {1024, 32, 0},                                               // 24 convsets_2
-    {0, 32, 1},                                                  // 25 pred
-};
-const OpDef kV2Ops[] = {
-    {OP_INPUT, -1, 0, 0, -1, 3, 3, 0, 0, 0},
-    {OP_CONV, 0, 1, 0, 0, 3, 32, 3, 1, ACT_L100},
-    {OP_CONV, 1, 2, 0, 1, 32, 64, 3, 1, ACT_L100},
-    {OP_CONV, 2, 3, 0, 2, 64, 128, 3, 0, ACT_L100},
-    {OP_CONV, 3, 4, 0, 3, 128, 64, 1, 0, ACT_L100},
-    {OP_CONV, 4, 5, 0, 4, 64, 128, 3, 1, ACT_L100},
-    {OP_CONV, 5, 6, 0, 5, 128, 256, 3, 0, ACT_L100},
-    {OP_CONV, 6, 7, 0, 6, 256, 128, 1, 0, ACT_L100},
-    {OP_CONV, 7, 8, 0, 7, 128, 256, 3, 0, ACT_L100},
-    {OP_POOL, 8, 9, 0, -1, 256, 256, 2, 0, 0},
-    {OP_CONV, 9, 10, 0, 8, 256, 512, 3, 0, ACT_L100},
-    {OP_CONV, 10, 11, 0, 9, 512, 256, 1, 0, ACT_L100},
-    {OP_CONV, 11, 12, 0, 10, 256, 512, 3, 0, ACT_L100},
-    {OP_CONV, 12, 13, 0, 11, 512, 256, 1, 0, ACT_L100},
-    {OP_CONV, 13, 14, 0, 12, 256, 512, 3, 0, ACT_L100},
-    {OP_POOL, 14, 15, 0, -1, 512, 512, 2, 0, 0},
-    {OP_CONV, 15, 16, 0, 13, 512, 1024, 3, 0, ACT_L100},
-    {OP_CONV, 16, 17, 0, 14, 1024, 512, 1, 0, ACT_L100},
-    {OP_CONV, 17, 18, 0, 15, 512, 1024, 3, 0, ACT_L100},
-    {OP_CONV, 18, 19, 0, 16, 1024, 512, 1, 0, ACT_L100},
-    {OP_CONV, 19, 20, 0, 17, 512, 1024, 3, 0, ACT_L100},
-    {OP_CONV, 20, 21, 0, 18, 1024, 1024, 3, 0, ACT_L125},        // convsets_1[0]
-    {OP_CONV, 21, 23, 256, 19, 1024, 1024, 3, 0, ACT_L125},      // convsets_1[1] -> cat[256:1280)
-    {OP_CONV, 14, 22, 0, 20, 512, 64, 1, 0, ACT_L125},           // route_layer on C_5
-    {OP_REORG, 22, 23, 0, -1, 64, 256, 2, 0, 0},                 // reorg(stride 2) -> cat[0:256)
-    {OP_CONV, 23, 24, 0, 21, 1280, 1024, 3, 0, ACT_L125},        // convsets_2
-    {OP_CONV, 24, 25, 0, 22, 1024, 0, 1, 0, ACT_NONE},           // pred (1x1)
-};
-// ---- myYOLOv3 / myYOLOv3Spp (models/yolo_v3.py:26-61, 203-231; models/yolo_v3_spp.py:31-36) on DarkNet-53
-// (backbone/darknet.py:112-161): built programmatically, weight slots in forward order
-struct V3Graph {
-    std::vector<TensorDef> t;
-    std::vector<OpDef> ops;
-    int nlayers = 0;
-    int pred[3] = {0, 0, 0};
-    int T(int C, int div, int pred_ = 0) { t.push_back(TensorDef{C, div, pred_}); return (int)t.size() - 1; }
-    void conv(int in, int out, int choff, int cin, int cout, int k, int act, int stride2 = 0, int res = -1) {
-        ops.push_back(OpDef{OP_CONV, in, out, choff, nlayers++, cin, cout, k, 0, act, stride2, res + 1});
-    }
-    // resblock(ch) x n on tensor x (div d); the last block may write into `last_out` (a concat buffer, channel offset 0)
-    int resblocks(int x, int ch, int d, int n, int last_out = -1) {
-        for (int i = 0; i < n; ++i) {
-            const int mid = T(ch / 2 < 64 ? 64 : ch / 2, d);                 // >= 64 channels: the kernels write 64-channel blocks
-            conv(x, mid, 0, ch, ch / 2, 1, ACT_L100);
-            const int out = (i == n - 1 && last_out >= 0) ? last_out : T(ch, d);
-            conv(mid, out, 0, ch / 2, ch, 3, ACT_L100, 0, x);
-            x = out;
-        }
-        return x;
-    }
-    explicit V3Graph(bool spp) {
-        const int in = T(3, 1);
-        ops.push_back(OpDef{OP_INPUT, -1, in, 0, -1, 3, 3, 0, 0, 0, 0, 0});
-        int x = T(64, 1);                                                   // 32 real channels
-        conv(in, x, 0, 3, 32, 3, ACT_L100);
-        int y = T(64, 2);
-        conv(x, y, 0, 32, 64, 3, ACT_L100, 1);
-        x = resblocks(y, 64, 2, 1);
-        y = T(128, 4); conv(x, y, 0, 64, 128, 3, ACT_L100, 1);
-        x = resblocks(y, 128, 4, 2);
-        y = T(256, 8); conv(x, y, 0, 128, 256, 3, ACT_L100, 1);
-        const int cat1 = T(384, 8);                                          // [C_3 (256) | up(conv_1x1_2) (128)]
-        const int c3 = resblocks(y, 256, 8, 8, cat1);
-        y = T(512, 16); conv(c3, y, 0, 256, 512, 3, ACT_L100, 1);
-        const int cat2 = T(768, 16);                                         // [C_4 (512) | up(conv_1x1_3) (256)]
-        const int c4 = resblocks(y, 512, 16, 8, cat2);
-        y = T(1024, 32); conv(c4, y, 0, 512, 1024, 3, ACT_L100, 1);
-        int c5;
-        if (spp) {
-            const int sppb = T(4096, 32);                                    // [C_5 | pool5 | pool9 | pool13]
-            c5 = resblocks(y, 1024, 32, 4, sppb);
-            ops.push_back(OpDef{OP_SPP, c5, c5, 1024, -1, 1024, 3072, 0, 0, 0, 0, 0});
-        } else {
-            c5 = resblocks(y, 1024, 32, 4);
-        }
-        // conv_set_3
-        int a = T(512, 32); conv(c5, a, 0, spp ? 4096 : 1024, 512, 1, ACT_L125);
-        int b = T(1024, 32); conv(a, b, 0, 512, 1024, 3, ACT_L125);
-        a = T(512, 32); conv(b, a, 0, 1024, 512, 1, ACT_L125);
-        b = T(1024, 32); conv(a, b, 0, 512, 1024, 3, ACT_L125);
-        const int f3 = T(512, 32); conv(b, f3, 0, 1024, 512, 1, ACT_L125);
-        a = T(256, 32); conv(f3, a, 0, 512, 256, 1, ACT_L125);               // conv_1x1_3
-        ops.push_back(OpDef{OP_UPSAMPLE, a, cat2, 512, -1, 256, 256, 0, 0, 0, 0, 0});
-        // conv_set_2
-        a = T(256, 16); conv(cat2, a, 0, 768, 256, 1, ACT_L125);
-        b = T(512, 16); conv(a, b, 0, 256, 512, 3, ACT_L125);
-        a = T(256, 16); conv(b, a, 0, 512, 256, 1, ACT_L125);
-        b = T(512, 16); conv(a, b, 0, 256, 512, 3, ACT_L125);
-        const int f2 = T(256, 16); conv(b, f2, 0, 512, 256, 1, ACT_L125);
-        a = T(128, 16); conv(f2, a, 0, 256, 128, 1, ACT_L125);               // conv_1x1_2
-        ops.push_back(OpDef{OP_UPSAMPLE, a, cat1, 256, -1, 128, 128, 0, 0, 0, 0, 0});
-        // conv_set_1
-        a = T(128, 8); conv(cat1, a, 0, 384, 128, 1, ACT_L125);
-        b = T(256, 8); conv(a, b, 0, 128, 256, 3, ACT_L125);
-        a = T(128, 8); conv(b, a, 0, 256, 128, 1, ACT_L125);
-        b = T(256, 8); conv(a, b, 0, 128, 256, 3, ACT_L125);
-        const int f1 = T(128, 8); conv(b, f1, 0, 256, 128, 1, ACT_L125);
-        // heads: extra_conv_3 + pred_3, extra_conv_2 + pred_2, extra_conv_1 + pred_1 (models/yolo_v3.py:219-231)
-        a = T(1024, 32); conv(f3, a, 0, 512, 1024, 3, ACT_L125);
-        pred[2] = T(0, 32, 1); conv(a, pred[2], 0, 1024, 0, 1, ACT_NONE);
-        a = T(512, 16); conv(f2, a, 0, 256, 512, 3, ACT_L125);
-        pred[1] = T(0, 16, 1); conv(a, pred[1], 0, 512, 0, 1, ACT_NONE);
-        a = T(256, 8); conv(f1, a, 0, 128, 256, 3, ACT_L125);
-        pred[0] = T(0, 8, 1); conv(a, pred[0], 0, 256, 0, 1, ACT_NONE);
-    }
-    ArchDef arch() const {
-        return ArchDef{(int)t.size(), t.data(), (int)ops.size(), ops.data(), nlayers, 3, {pred[0], pred[1], pred[2]}, {8.f, 16.f, 32.f}};
-    }
-};
-const V3Graph kV3(false), kV3Spp(true);
-const ArchDef kArch[5] = {
-    {10, kSlimT, 10, kSlimOps, 10, 1, {9, -1, -1}, {16.f, 0.f, 0.f}},
-    {15, kTinyT, 16, kTinyOps, 13, 2, {13, 14, -1}, {16.f, 32.f, 0.f}},
-    {26, kV2T, 27, kV2Ops, 23, 1, {25, -1, -1}, {32.f, 0.f, 0.f}},
-    kV3.arch(),
-    kV3Spp.arch(),
-};
-
 struct Tensor {
     int C = 0, Cpad = 0, H = 0, W = 0, halo = 1, pred = 0;
     size_t pb = 0;          // bytes per pixel
@@ -249,418 +63,7 @@ struct NLayer {
     int pbid = -1;
     char *wpb_dev = nullptr;
 };
-
-__global__ void pool_bf16_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int cbytes, int Ho, int Wo,
-                                 int out_pb, int stride) {
-    // 16 bytes (8 bf16 channels) of one output pixel per thread; the zero halo IS the padding
-    const int cg = cbytes / 16;
-    const size_t total = (size_t)B * Ho * Wo * cg;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % cg);
-        size_t r = i / cg;
-        const int x = (int)(r % Wo);
-        r /= Wo;
-        const int y = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const char *src = in + (((size_t)b * (Hin + 2) + y * stride + 1) * (Win + 2) + x * stride + 1) * in_pb + c * 16;
-        uint4 v[4];
-        v[0] = *(const uint4 *)src;
-        v[1] = *(const uint4 *)(src + in_pb);
-        v[2] = *(const uint4 *)(src + (size_t)(Win + 2) * in_pb);
-        v[3] = *(const uint4 *)(src + (size_t)(Win + 2) * in_pb + in_pb);
-        unsigned int o[4];
-        const unsigned int *w0 = (const unsigned int *)&v[0], *w1 = (const unsigned int *)&v[1];
-        const unsigned int *w2 = (const unsigned int *)&v[2], *w3 = (const unsigned int *)&v[3];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            unsigned int res = 0;
-#pragma unroll
-            for (int hf = 0; hf < 2; ++hf) {
-                const int sh = 16 * hf;
-                const float a = __uint_as_float(((w0[k] >> sh) & 0xffffu) << 16), bb = __uint_as_float(((w1[k] >> sh) & 0xffffu) << 16);
-                const float cc = __uint_as_float(((w2[k] >> sh) & 0xffffu) << 16), d = __uint_as_float(((w3[k] >> sh) & 0xffffu) << 16);
-                const float m = fmaxf(fmaxf(a, bb), fmaxf(cc, d));
-                res |= (__float_as_uint(m) >> 16) << sh;
-            }
-            o[k] = res;
-        }
-        *(uint4 *)(out + (((size_t)b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * out_pb + c * 16) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-}
-
-// F.interpolate(scale_factor=2, mode='bilinear', align_corners=True) (models/tiny_yolo_v3.py:188):
-// src = dst * (in - 1) / (out - 1), the two-tap blend of torch's upsample_bilinear2d in fp32.
-__global__ void upsample_bf16_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int C, int out_pb,
-                                     int out_off, float ry, float rx) {
-    const int Ho = 2 * Hin, Wo = 2 * Win;
-    const size_t total = (size_t)B * Ho * Wo * C;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        size_t r = i / C;
-        const int x = (int)(r % Wo);
-        r /= Wo;
-        const int y = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const float sy = ry * (float)y, sx = rx * (float)x;
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = min(y0 + 1, Hin - 1), x1 = min(x0 + 1, Win - 1);
-        const float ly = sy - (float)y0, lx = sx - (float)x0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        auto ld = [&](int yy, int xx) -> float {
-            const unsigned short h = *(const unsigned short *)(in + (((size_t)b * (Hin + 2) + yy + 1) * (Win + 2) + xx + 1) * in_pb + c * 2);
-            return __uint_as_float((unsigned int)h << 16);
-        };
-        const float v = hy * (hx * ld(y0, x0) + lx * ld(y0, x1)) + ly * (hx * ld(y1, x0) + lx * ld(y1, x1));
-        *(unsigned short *)(out + (((size_t)b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * out_pb + out_off + c * 2) =
-            __builtin_bit_cast(unsigned short, (__bf16)v);
-    }
-}
-
-__global__ void pool_i8_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int cbytes, int Ho, int Wo,
-                               int out_pb, int stride) {
-    const int cg = cbytes / 16;
-    const size_t total = (size_t)B * Ho * Wo * cg;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % cg);
-        size_t r = i / cg;
-        const int x = (int)(r % Wo);
-        r /= Wo;
-        const int y = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const char *src = in + (((size_t)b * (Hin + 2) + y * stride + 1) * (Win + 2) + x * stride + 1) * in_pb + c * 16;
-        uint4 v[4];
-        v[0] = *(const uint4 *)src;
-        v[1] = *(const uint4 *)(src + in_pb);
-        v[2] = *(const uint4 *)(src + (size_t)(Win + 2) * in_pb);
-        v[3] = *(const uint4 *)(src + (size_t)(Win + 2) * in_pb + in_pb);
-        unsigned int o[4];
-#pragma unroll
-        for (int k = 0; k < 4; ++k) {
-            unsigned int res = 0;
-#pragma unroll
-            for (int by = 0; by < 4; ++by) {
-                int m = -128;
-#pragma unroll
-                for (int j = 0; j < 4; ++j) m = max(m, (int)(signed char)((((const unsigned int *)&v[j])[k] >> (8 * by)) & 0xffu));
-                res |= (unsigned int)(m & 0xff) << (8 * by);
-            }
-            o[k] = res;
-        }
-        *(uint4 *)(out + (((size_t)b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * out_pb + c * 16) = make_uint4(o[0], o[1], o[2], o[3]);
-    }
-}
-
-// int8 form of the bilinear x2: the blend of the integer values in fp32 (same expression as the bf16
-// kernel), rescaled by the power of two between the two tensors' exponents, rounded half-to-even.
-__global__ void upsample_i8_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int C, int out_pb,
-                                   int out_off, float ry, float rx, float rescale) {
-    const int Ho = 2 * Hin, Wo = 2 * Win;
-    const size_t total = (size_t)B * Ho * Wo * C;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        size_t r = i / C;
-        const int x = (int)(r % Wo);
-        r /= Wo;
-        const int y = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const float sy = ry * (float)y, sx = rx * (float)x;
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = min(y0 + 1, Hin - 1), x1 = min(x0 + 1, Win - 1);
-        const float ly = sy - (float)y0, lx = sx - (float)x0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        auto ld = [&](int yy, int xx) -> float {
-            return (float)*(const signed char *)(in + (((size_t)b * (Hin + 2) + yy + 1) * (Win + 2) + xx + 1) * in_pb + c);
-        };
-        const float v = hy * (hx * ld(y0, x0) + lx * ld(y0, x1)) + ly * (hx * ld(y1, x0) + lx * ld(y1, x1));
-        const float q = fminf(fmaxf(rintf(v * rescale), -127.f), 127.f);
-        *(signed char *)(out + (((size_t)b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * out_pb + out_off + c) = (signed char)(int)q;
-    }
-}
-
-// the same, sixteen channels of one output pixel per thread (16-byte loads and stores; C % 16 == 0, 16-byte aligned pixels):
-// element for element the expression above
-__global__ void upsample_i8x16_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int C, int out_pb,
-                                      int out_off, float ry, float rx, float rescale) {
-    const int Ho = 2 * Hin, Wo = 2 * Win, CG = C / 16;
-    const int total = B * Ho * Wo * CG;
-    for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < total; i += gridDim.x * blockDim.x) {
-        const int cg = i % CG;
-        int r = i / CG;
-        const int x = r % Wo;
-        r /= Wo;
-        const int y = r % Ho;
-        const int b = r / Ho;
-        const float sy = ry * (float)y, sx = rx * (float)x;
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = min(y0 + 1, Hin - 1), x1 = min(x0 + 1, Win - 1);
-        const float ly = sy - (float)y0, lx = sx - (float)x0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        auto ld = [&](int yy, int xx) { return *(const v4i *)(in + (((size_t)b * (Hin + 2) + yy + 1) * (Win + 2) + xx + 1) * in_pb + cg * 16); };
-        const v4i a00 = ld(y0, x0), a01 = ld(y0, x1), a10 = ld(y1, x0), a11 = ld(y1, x1);
-        v4i o;
-#pragma unroll
-        for (int w = 0; w < 4; ++w) {
-            unsigned int word = 0;
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                const float f00 = (float)(signed char)(a00[w] >> (8 * k)), f01 = (float)(signed char)(a01[w] >> (8 * k));
-                const float f10 = (float)(signed char)(a10[w] >> (8 * k)), f11 = (float)(signed char)(a11[w] >> (8 * k));
-                const float v = hy * (hx * f00 + lx * f01) + ly * (hx * f10 + lx * f11);
-                const float q = fminf(fmaxf(rintf(v * rescale), -127.f), 127.f);
-                word |= ((unsigned int)(int)q & 0xffu) << (8 * k);
-            }
-            o[w] = (int)word;
-        }
-        *(v4i *)(out + (((size_t)b * (Ho + 2) + y + 1) * (Wo + 2) + x + 1) * out_pb + out_off + cg * 16) = o;
-    }
-}
-
-__global__ void absmax_bf16_kernel(const char *t, size_t n_elems, unsigned int *out) {
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_elems; i += (size_t)gridDim.x * blockDim.x) {
-        const unsigned short h = ((const unsigned short *)t)[i];
-        m = fmaxf(m, fabsf(__uint_as_float((unsigned int)h << 16)));
-    }
-    const unsigned int u = y355_wave_max_u32(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0) atomicMax(out, u);
-}
-
-// ---- int8 ops of the DarkNet graphs (DESIGN.md "int8 DarkNet"); clamps count into the op's counter
-__device__ __forceinline__ void count_sat(Counters *ctr, unsigned int n) {
-    if (n && ctr) atomicAdd(&ctr->sat, (unsigned long long)n);
-}
-
-// q_in * 2^d, rounded half-to-even (d < 0), clamped to +-127: the rescale between two tensors' exponents
-__device__ __forceinline__ int rescale_i8(int q, int d, unsigned int &nsat) {
-    const int r = d >= 0 ? q * (1 << min(d, 24)) : y355_rne_shift32(q, -d);
-    const int c = y355_clamp8<int>(r);
-    nsat += c != r ? 1u : 0u;
-    return c;
-}
-
-// fp32 NCHW [B][3][H][W] -> int8 NHWC32 with halo: q = clamp(RNE(x * 2^sa_in)) (the slim front end's input rule); one pixel
-// per thread, one 16-byte store (channels 3..15 zero; 16..31 keep the allocation's zeros)
-__global__ void input_i8_kernel(const float *x, char *out, int B, int H, int W, int out_pb, float in_scale, Counters *ctr) {
-    const size_t total = (size_t)B * H * W;
-    const size_t plane = (size_t)H * W;
-    unsigned int nsat = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(i % W), y = (int)((i / W) % H);
-        const size_t b = i / plane;
-        const float *src = x + b * 3 * plane + (size_t)y * W + xx;
-        unsigned int w = 0;
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float r = rintf(src[c * plane] * in_scale);
-            const float q = fminf(fmaxf(r, -127.f), 127.f);
-            nsat += q != r ? 1u : 0u;
-            w |= ((unsigned int)(int)q & 0xffu) << (8 * c);
-        }
-        *(uint4 *)(out + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + xx + 1) * out_pb) = make_uint4(w, 0u, 0u, 0u);
-    }
-    count_sat(ctr, nsat);
-}
-
-// BaseTransform constants per RGB channel (data/__init__.py:50 lists them in BGR order)
-struct NormU8 { float mean[3], sd[3]; };
-
-// uint8 HWC BGR frames [B][sh][sw][3] -> the network input tensor with halo, bf16 NHWC16 (I8 = false) or int8 NHWC32 (I8):
-// cv2.resize to the network size fused into the load when the frame is not at it (tab != null: y355_resize_px), then
-// BaseTransform + BGR->RGB through a per-channel byte table in LDS that holds what input_bf16_kernel / input_i8_kernel make
-// of the normalised fp32 value -- its bf16 (RNE), or clamp(RNE(x * 2^sa_in)) with bit 8 = "was clamped" (counted into ctr as
-// input_i8_kernel counts).  One pixel per thread, one 16-byte store (bf16: channels 3..7 zero; int8: 3..15 zero; the rest of
-// the pixel keeps the allocation's zeros).
-template <bool I8>
-__global__ __launch_bounds__(256) void input_u8_kernel(const uint8_t *frames, const int *tab, char *out, int B, int sh, int sw, int H,
-                                                       int W, int out_pb, NormU8 nm, float in_scale, Counters *ctr) {
-    __shared__ unsigned short lut[3 * 256];
-    const int tid = threadIdx.x;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float t = y355_norm_u8(tid, nm.mean[c], nm.sd[c]);
-        if constexpr (I8) {
-            const float r = rintf(t * in_scale);
-            const float q = fminf(fmaxf(r, -127.f), 127.f);
-            lut[c * 256 + tid] = (unsigned short)(((int)q & 0xff) | (q != r ? 0x100 : 0));
-        } else {
-            lut[c * 256 + tid] = __builtin_bit_cast(unsigned short, (__bf16)t);
-        }
-    }
-    __syncthreads();
-    const size_t total = (size_t)B * H * W;
-    const size_t plane = (size_t)H * W;
-    unsigned int nsat = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + tid; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(i % W), y = (int)((i / W) % H);
-        const size_t b = i / plane;
-        int u[3];
-        if (tab) {
-            y355_resize_px(frames + b * sh * sw * 3, tab, sh, sw, H, W, y, xx, u);
-        } else {
-            const uint8_t *px = frames + i * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) u[c] = px[c];
-        }
-        // RGB channel c = BGR byte 2 - c
-        const unsigned int e0 = lut[u[2]], e1 = lut[256 + u[1]], e2 = lut[512 + u[0]];
-        uint4 v;
-        if constexpr (I8) {
-            nsat += ((e0 >> 8) & 1u) + ((e1 >> 8) & 1u) + ((e2 >> 8) & 1u);
-            v = make_uint4((e0 & 0xffu) | ((e1 & 0xffu) << 8) | ((e2 & 0xffu) << 16), 0u, 0u, 0u);
-        } else {
-            v = make_uint4(e0 | (e1 << 16), e2, 0u, 0u);
-        }
-        *(uint4 *)(out + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + xx + 1) * out_pb) = v;
-    }
-    if constexpr (I8) count_sat(ctr, nsat);
-}
-
-// reorg (utils/modules.py:48-57) of int8 NHWC into a concat buffer with the rescale 2^(s_out - s_in):
-// out[.., (sy*s+sx)*C + c] = rescale(in[s*y+sy][s*x+sx][c]); 16 bytes (16 channels) per thread
-__global__ void reorg_i8_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int C, int out_pb, int out_off, int s,
-                                int d, Counters *ctr) {
-    const int Ho = Hin / s, Wo = Win / s, cg = C / 16;
-    const size_t total = (size_t)B * Ho * Wo * s * s * cg;
-    unsigned int nsat = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int g = (int)(i % cg);
-        const int k = (int)((i / cg) % (s * s));
-        const int x = (int)((i / ((size_t)cg * s * s)) % Wo), y = (int)((i / ((size_t)cg * s * s * Wo)) % Ho);
-        const size_t b = i / ((size_t)cg * s * s * Wo * Ho);
-        const int sy = k / s, sx = k % s;
-        const uint4 v = *(const uint4 *)(in + ((b * (Hin + 2) + (size_t)s * y + sy + 1) * (Win + 2) + (size_t)s * x + sx + 1) * in_pb + g * 16);
-        unsigned int u[4] = {v.x, v.y, v.z, v.w};
-        if (d != 0) {
-#pragma unroll
-            for (int w = 0; w < 4; ++w) {
-                unsigned int o = 0;
-#pragma unroll
-                for (int j = 0; j < 4; ++j)
-                    o |= ((unsigned int)rescale_i8((int)(signed char)((u[w] >> (8 * j)) & 0xffu), d, nsat) & 0xffu) << (8 * j);
-                u[w] = o;
-            }
-        }
-        *(uint4 *)(out + ((b * (Ho + 2) + y + 1) * (size_t)(Wo + 2) + x + 1) * out_pb + out_off + (size_t)k * C + g * 16) =
-            make_uint4(u[0], u[1], u[2], u[3]);
-    }
-    count_sat(ctr, nsat);
-}
-
-// SPP (utils/modules.py:66-72) on int8 NHWC, in place in a 4C-channel buffer as spp_bf16_kernel: max-pools 5 / 9 / 13, stride 1,
-// windows clipped to the map (the padding takes part in no max); exact on the int8 values, no requantisation.  16 channels
-// (16 bytes) per thread.
-__global__ void spp_i8_kernel(char *buf, int B, int H, int W, int pb, int C) {
-    const int cg = C / 16;
-    const size_t total = (size_t)B * H * W * cg;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int g = (int)(i % cg);
-        const int x = (int)((i / cg) % W), y = (int)((i / ((size_t)cg * W)) % H);
-        const size_t b = i / ((size_t)cg * W * H);
-        int m5[16], m9[16], m13[16];
-#pragma unroll
-        for (int k = 0; k < 16; ++k) m5[k] = m9[k] = m13[k] = -128;
-        for (int dy = -6; dy <= 6; ++dy) {
-            const int yy = y + dy;
-            if (yy < 0 || yy >= H) continue;
-            for (int dx = -6; dx <= 6; ++dx) {
-                const int xx = x + dx;
-                if (xx < 0 || xx >= W) continue;
-                const uint4 v = *(const uint4 *)(buf + ((b * (H + 2) + yy + 1) * (size_t)(W + 2) + xx + 1) * pb + g * 16);
-                const unsigned int u[4] = {v.x, v.y, v.z, v.w};
-                const int r = max(abs(dy), abs(dx));
-#pragma unroll
-                for (int k = 0; k < 16; ++k) {
-                    const int f = (int)(signed char)((u[k >> 2] >> (8 * (k & 3))) & 0xffu);
-                    m13[k] = max(m13[k], f);
-                    if (r <= 4) m9[k] = max(m9[k], f);
-                    if (r <= 2) m5[k] = max(m5[k], f);
-                }
-            }
-        }
-        char *o = buf + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * pb + g * 16;
-        auto pack = [](const int (&m)[16]) {
-            unsigned int w[4] = {0u, 0u, 0u, 0u};
-#pragma unroll
-            for (int k = 0; k < 16; ++k) w[k >> 2] |= ((unsigned int)m[k] & 0xffu) << (8 * (k & 3));
-            return make_uint4(w[0], w[1], w[2], w[3]);
-        };
-        *(uint4 *)(o + (size_t)C) = pack(m5);
-        *(uint4 *)(o + (size_t)C * 2) = pack(m9);
-        *(uint4 *)(o + (size_t)C * 3) = pack(m13);
-    }
-}
-
-// ---- maxima of a calibration step on the int8 graph (y355_net_calibrate): each reduces within the wave and issues one
-// atomicMax per wave on the bits of a non-negative fp32 / on an unsigned int; nothing else is written
-// bilinear x2: max |blend| of upsample_i8_kernel's fp32 expression, before the rescale
-__global__ void upsample_i8_max_kernel(const char *in, int B, int Hin, int Win, int in_pb, int C, float ry, float rx, unsigned int *out) {
-    const int Ho = 2 * Hin, Wo = 2 * Win;
-    const size_t total = (size_t)B * Ho * Wo * C;
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        size_t r = i / C;
-        const int x = (int)(r % Wo);
-        r /= Wo;
-        const int y = (int)(r % Ho);
-        const int b = (int)(r / Ho);
-        const float sy = ry * (float)y, sx = rx * (float)x;
-        const int y0 = (int)sy, x0 = (int)sx;
-        const int y1 = min(y0 + 1, Hin - 1), x1 = min(x0 + 1, Win - 1);
-        const float ly = sy - (float)y0, lx = sx - (float)x0;
-        const float hy = 1.f - ly, hx = 1.f - lx;
-        auto ld = [&](int yy, int xx) -> float {
-            return (float)*(const signed char *)(in + (((size_t)b * (Hin + 2) + yy + 1) * (Win + 2) + xx + 1) * in_pb + c);
-        };
-        const float v = hy * (hx * ld(y0, x0) + lx * ld(y0, x1)) + ly * (hx * ld(y1, x0) + lx * ld(y1, x1));
-        m = fmaxf(m, fabsf(v));
-    }
-    const unsigned int u = y355_wave_max_u32(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0 && u) atomicMax(out, u);
-}
-
-// max |q| over the first C channels of an int8 tensor's interior (reorg's source bytes)
-__global__ void absmax_i8_kernel(const char *in, int B, int H, int W, int pb, int C, unsigned int *out) {
-    const size_t total = (size_t)B * H * W * C;
-    unsigned int m = 0;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int c = (int)(i % C);
-        size_t r = i / C;
-        const int x = (int)(r % W);
-        r /= W;
-        const int y = (int)(r % H);
-        const size_t b = r / H;
-        const int q = (int)*(const signed char *)(in + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * pb + c);
-        m = max(m, (unsigned int)abs(q));
-    }
-    const unsigned int u = y355_wave_max_u32(m);
-    if ((threadIdx.x & 63) == 0 && u) atomicMax(out, u);
-}
-
-// max |x| of the normalised frames (the table entries y355_norm_u8 the H x W network input actually hits): uint8 HWC BGR
-// [B][sh][sw][3], resized on the fly when tab != null (y355_resize_px), as input_u8_kernel reads them
-__global__ __launch_bounds__(256) void absmax_u8_kernel(const uint8_t *frames, const int *tab, int B, int sh, int sw, int H, int W,
-                                                        NormU8 nm, unsigned int *out) {
-    const size_t total = (size_t)B * H * W;
-    const size_t plane = (size_t)H * W;
-    float m = 0.f;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(i % W), y = (int)((i / W) % H);
-        const size_t b = i / plane;
-        int u[3];
-        if (tab) {
-            y355_resize_px(frames + b * sh * sw * 3, tab, sh, sw, H, W, y, xx, u);
-        } else {
-            const uint8_t *px = frames + i * 3;
-#pragma unroll
-            for (int c = 0; c < 3; ++c) u[c] = px[c];
-        }
-#pragma unroll
-        for (int c = 0; c < 3; ++c) m = fmaxf(m, fabsf(y355_norm_u8(u[2 - c], nm.mean[c], nm.sd[c])));     // RGB c = BGR byte 2 - c
-    }
-    const unsigned int bits = y355_wave_max_u32(__float_as_uint(m));
-    if ((threadIdx.x & 63) == 0 && bits) atomicMax(out, bits);
-}
+NetMap map_of(const Tensor &t) { return NetMap{t.dev, t.H, t.W, (int)t.pb}; }
 }  // namespace
 
 #ifndef Y355_USE_CONVPXB
@@ -715,7 +118,6 @@ struct y355_net {
     std::vector<float> trk_scale;
     std::vector<int> trk_first;
     Counters *cal_dev = nullptr;
-    bool calibrating = false;         // run_op: every convolution on convg.hip
 };
 
 // the network input of one forward: an fp32 NCHW tensor, or uint8 HWC BGR frames (u8) of src_h x src_w with the resize tables
@@ -815,6 +217,9 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     h->L.resize(A.nlayers);
     for (int i = 0; i < A.nops && !rc; ++i) {
         const OpDef &o = A.ops[i];
+        // the int8 bilinear x2 has one kernel, sixteen channels per thread: every such op of the graph must meet its conditions
+        if (o.type == OP_UPSAMPLE && !h->bf && !y355_upsample_i8_ok(map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin, o.choff))
+            rc = y355_fail(Y355_EINVAL, "no int8 upsampling kernel for an op of this graph at this size");
         if (o.type != OP_CONV1 && o.type != OP_CONV) continue;
         NLayer &L = h->L[o.layer];
         L.op = i;
@@ -1103,6 +508,13 @@ extern "C" int y355_net_load_layer_i8_pc(y355_net *h, int idx, const int8_t *q_w
     return load_layer_i8(h, idx, q_w, q_b, cout, cin, ksize, e_w, 0, e_b);
 }
 
+static void act_fixed(int act, int *lk, int *neg_mul) {
+    // LeakyReLU slope as neg_mul / 2^lk: 0.125 exactly; 0.1 ~ 205 / 2048 (build-defined, DESIGN.md)
+    if (act == ACT_L125) { *lk = 3; *neg_mul = 1; }
+    else if (act == ACT_L100) { *lk = 11; *neg_mul = 205; }
+    else { *lk = 0; *neg_mul = 1; }
+}
+
 // Bound on |acc| * 2^shl[c] over the output channels, shl[c] = F - sa_i - e_wc[c].  own: |acc| <= 127 * (sum |q_w| of the
 // channel), the layer's own weights; otherwise 127 * 127 per product (a per-channel layer always takes its own weights: the
 // worst-case weight in the channel with the largest shift is a bound nobody needs)
@@ -1113,47 +525,98 @@ static long double acc_bound(const NLayer &L, const OpDef &o, int F, int sa_i, b
     for (int c = 0; c < L.cout; ++c) m = std::max(m, (long double)127 * L.wabs_c[c] * std::ldexp(1.0L, F - sa_i - L.e_wc[c]));
     return m;
 }
-static int shl_max(const NLayer &L, int F, int sa_i) { return F - sa_i - *std::min_element(L.e_wc.begin(), L.e_wc.end()); }
 
-static void act_fixed(int act, int *lk, int *neg_mul);
+// The fixed-point epilogue of an int8 convolution up to t' (y355_common.h), for the exponents in front of the layer -- none of
+// this depends on the output's exponent:  t = acc * 2^shc[c] + bw[c] at exponent F = max(sa_i + e_w, e_b),
+// t' = t >= 0 ? t * 2^lk : t * nm at exponent E = F + lk
+struct ConvFixed {
+    int sa_i, F, shl, bshl, lk, nm, E;      // shl: of the channels with the largest weight exponent, the smallest of shc
+    std::vector<long long> bw;              // [cout_pad] q_b << bshl
+    std::vector<int> shc;                   // [cout_pad] every output channel's own accumulator shift
+    long double bmax;                       // max |bw|
+    long double tw, tb;                     // bounds on |t|: worst-case weights / the layer's own (|acc| <= 127 sum |q_w|)
+    long double slope() const { return std::max(std::ldexp(1.0L, lk), (long double)nm); }      // |t'| <= |t| * slope()
+};
+static int conv_fixed(const y355_net *h, const OpDef &o, const NLayer &L, ConvFixed *cf) {
+    cf->sa_i = o.in < 0 ? h->sa_in : h->sa[o.in];
+    cf->F = std::max(cf->sa_i + L.e_w, L.e_b);
+    cf->shl = cf->F - cf->sa_i - L.e_w;
+    cf->bshl = cf->F - L.e_b;
+    act_fixed(o.act, &cf->lk, &cf->nm);
+    cf->E = cf->F + cf->lk;
+    if (cf->F - cf->sa_i - *std::min_element(L.e_wc.begin(), L.e_wc.end()) > 24 || cf->bshl > 40)
+        return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
+    cf->bw.assign(L.cout_pad, 0);
+    cf->shc.assign(L.cout_pad, 0);
+    cf->bmax = 0;
+    for (int c = 0; c < L.cout; ++c) {
+        cf->bw[c] = (long long)L.q_b[c] * (1ll << cf->bshl);
+        cf->shc[c] = cf->F - cf->sa_i - L.e_wc[c];
+        cf->bmax = std::max(cf->bmax, std::fabs((long double)L.q_b[c]) * std::ldexp(1.0L, cf->bshl));
+    }
+    cf->tw = acc_bound(L, o, cf->F, cf->sa_i, false) + cf->bmax;
+    cf->tb = acc_bound(L, o, cf->F, cf->sa_i, true) + cf->bmax;
+    return 0;
+}
+
+// the general-slope epilogue fits 32 bits (y355_requant_gen32) for |t| <= t:
+//   |t| * max(2^max(0, lk - sh), nm * 2^max(0, -sh)) + rounding < 2^31
+static bool fits32(const ConvFixed &cf, long double t, int sh) {
+    const long double fpos = std::ldexp(1.0L, std::max(0, cf.lk - sh)), fneg = (long double)cf.nm * std::ldexp(1.0L, std::max(0, -sh));
+    return t * std::max(fpos, fneg) + std::ldexp(1.0L, std::max(sh, 0)) < std::ldexp(1.0L, 31) && cf.bmax < std::ldexp(1.0L, 31);
+}
+
+// conv1.hip / front.hip epilogue constants: never guarded; the caller adds what its kernel reads beyond these
+static Requant requant_of(const ConvFixed &cf, int sh) {
+    Requant r{};
+    r.shl = cf.shl; r.sh = sh; r.leaky = (cf.lk || cf.nm != 1) ? 1 : 0; r.lk = cf.lk; r.neg_mul = cf.nm; r.guard_log2 = 63;
+    return r;
+}
 
 // exponents of a residual layer's epilogue (ResQ, y355_common.h) and whether its 32-bit form holds for these weights.
 // Nonzero when no bound proves the 64-bit sum u = t' 2^(G-E) + q_r 2^(G-s_r) (and its rounding) below 2^62.
-static int res_params(const y355_net *h, const OpDef &o, const NLayer &L, ResQ *rr, int *narrow) {
-    const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in], sa_o = h->sa[o.out], s_r = h->sa[o.res1 - 1];
-    const int F = std::max(sa_i + L.e_w, L.e_b);
-    const int shl = shl_max(L, F, sa_i), bshl = F - L.e_b;
-    int lk, nm;
-    act_fixed(o.act, &lk, &nm);
-    const int E = F + lk, G = std::max(E, s_r);
+static int res_params(const y355_net *h, const OpDef &o, const ConvFixed &cf, ResQ *rr, int *narrow) {
+    const int sa_o = h->sa[o.out], s_r = h->sa[o.res1 - 1], lk = cf.lk, nm = cf.nm;
+    const int E = cf.E, G = std::max(E, s_r);
     *rr = ResQ{};
     rr->t_sh = G - E;
     rr->r_sh = G - s_r;
     rr->sh = G - sa_o;
     *narrow = 0;
-    if (shl > 24 || bshl > 40 || rr->t_sh > 62 || rr->r_sh > 62 || rr->sh > 62 || rr->sh < -62) return 1;
-    long double bmax = 0;
-    for (int c = 0; c < L.cout; ++c) bmax = std::max(bmax, std::fabs((long double)L.q_b[c]) * std::ldexp(1.0L, bshl));
-    // worst-case |t'|, as refresh_i8 bounds the plain epilogue
-    const long double tw = acc_bound(L, o, F, sa_i, false) + bmax;
-    long double u = tw * std::max(std::ldexp(1.0L, lk), (long double)nm) * std::ldexp(1.0L, rr->t_sh) + 127.0L * std::ldexp(1.0L, rr->r_sh);
+    if (rr->t_sh > 62 || rr->r_sh > 62 || rr->sh > 62 || rr->sh < -62) return 1;
+    long double u = cf.tw * cf.slope() * std::ldexp(1.0L, rr->t_sh) + 127.0L * std::ldexp(1.0L, rr->r_sh);
     u = rr->sh < 0 ? u * std::ldexp(1.0L, -rr->sh) : u + std::ldexp(1.0L, rr->sh);
     if (u >= std::ldexp(1.0L, 62)) return 1;
-    // 32-bit form: both branches over their common power of two, on the layer's own weights (|acc| <= 127 sum |q_w|)
+    // 32-bit form: both branches over their common power of two, on the layer's own weights
     const int shp = E - sa_o;
     const int dp = std::max({shp - lk, s_r - sa_o, 0}), dn = std::max({shp, s_r - sa_o, 0});
     rr->p_t = lk - shp + dp; rr->p_r = sa_o - s_r + dp; rr->p_d = dp;
     rr->n_t = dn - shp; rr->n_r = sa_o - s_r + dn; rr->n_d = dn;
-    const long double tb = acc_bound(L, o, F, sa_i, true) + bmax, lim = std::ldexp(1.0L, 31);
-    if (dp <= 30 && dn <= 30 && rr->p_t <= 30 && rr->p_r <= 30 && rr->n_t <= 30 && rr->n_r <= 30 && tb < lim && bmax < lim &&
+    const long double tb = cf.tb, lim = std::ldexp(1.0L, 31);
+    if (dp <= 30 && dn <= 30 && rr->p_t <= 30 && rr->p_r <= 30 && rr->n_t <= 30 && rr->n_r <= 30 && tb < lim && cf.bmax < lim &&
         tb * std::ldexp(1.0L, rr->p_t) + 127.0L * std::ldexp(1.0L, rr->p_r) + std::ldexp(1.0L, dp) < lim &&
         tb * nm * std::ldexp(1.0L, rr->n_t) + 127.0L * std::ldexp(1.0L, rr->n_r) + std::ldexp(1.0L, dn) < lim)
         *narrow = 1;
     return 0;
 }
 
+// the range proof of every loaded residual layer for the handle's exponents: the 64-bit sum u must provably fit
+static int res_range_check(const y355_net *h) {
+    for (int i = 0; i < h->arch->nops; ++i) {
+        const OpDef &o = h->arch->ops[i];
+        if (o.type != OP_CONV || !o.res1 || !h->L[o.layer].loaded) continue;
+        ConvFixed cf;
+        ResQ rr{};
+        int narrow = 0;
+        if (conv_fixed(h, o, h->L[o.layer], &cf) || res_params(h, o, cf, &rr, &narrow))
+            return y355_fail(Y355_ERANGE, "residual layer: the 64-bit sum of the residual epilogue is not provably in range "
+                                          "for these exponents");
+    }
+    return 0;
+}
+
 // activation exponents of an int8 net: sa_in for the fp32 network input, sa[t] for tensor t (graph
-// order of csrc/net.hip).  A max-pool output takes its input's exponent and the network-input tensor sa_in (the entries
+// order of net_arch.h).  A max-pool output takes its input's exponent and the network-input tensor sa_in (the entries
 // given for them are overridden); a concat buffer (and the in-place SPP buffer) has ONE exponent that every producer
 // requantises to.  Y355_ERANGE (nothing changed) when a loaded residual layer's epilogue is not provably in range.
 // (arguments checked) installs the exponents with the aliasing and the range proof of y355_net_set_act_exponents
@@ -1167,18 +630,10 @@ static int install_act_exponents(y355_net *h, int sa_in, const int32_t *sa, int 
         if (o.type == OP_POOL) h->sa[o.out] = h->sa[o.in];      // max-pool does not requantise
         if (o.type == OP_INPUT) h->sa[o.out] = sa_in;            // the quantised network input
     }
-    // residual layers whose weights are loaded: the 64-bit sum u must provably fit (checked again at the forward for the others)
-    for (int i = 0; i < h->arch->nops; ++i) {
-        const OpDef &o = h->arch->ops[i];
-        if (o.type != OP_CONV || !o.res1 || !h->L[o.layer].loaded) continue;
-        ResQ rr{};
-        int narrow = 0;
-        if (res_params(h, o, h->L[o.layer], &rr, &narrow)) {
-            h->sa_in = keep_in;
-            h->sa = keep;
-            return y355_fail(Y355_ERANGE, "residual layer: the 64-bit sum of the residual epilogue is not provably in range "
-                                          "for these exponents");
-        }
+    if (int rc = res_range_check(h)) {                           // (layers loaded later: checked again at the forward)
+        h->sa_in = keep_in;
+        h->sa = keep;
+        return rc;
     }
     if (all_set) h->sa_ok = true;
     for (auto &L : h->L) L.dirty = true;
@@ -1209,117 +664,67 @@ extern "C" int y355_net_get_act_exponents(y355_net *h, int32_t *sa_in, int32_t *
     return 0;
 }
 
-static void act_fixed(int act, int *lk, int *neg_mul) {
-    // LeakyReLU slope as neg_mul / 2^lk: 0.125 exactly; 0.1 ~ 205 / 2048 (build-defined, DESIGN.md)
-    if (act == ACT_L125) { *lk = 3; *neg_mul = 1; }
-    else if (act == ACT_L100) { *lk = 11; *neg_mul = 205; }
-    else { *lk = 0; *neg_mul = 1; }
-}
-
 // epilogue constants of the convolution of op i for the handle's current exponents (dirty layers only)
 static int refresh_layer_i8(y355_net *h, int i) {
-    {
-        const OpDef &o = h->arch->ops[i];
-        if (o.type != OP_CONV1 && o.type != OP_CONV) return 0;
-        NLayer &L = h->L[o.layer];
-        if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
-        if (!L.dirty) return 0;
-        const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in], sa_o = h->sa[o.out];
-        const int F = std::max(sa_i + L.e_w, L.e_b);
-        const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;      // shl: of the channels with the largest exponent, the smallest
-        int lk, nm;
-        act_fixed(o.act, &lk, &nm);
-        const int sh = F + lk - sa_o;
-        if (shl_max(L, F, sa_i) > 24 || bshl > 40 || sh > 62 || sh < -20) return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
-        // worst case |t'| (through the slope and a left shift / the rounding add) must stay below 2^62
-        std::vector<long long> bw(L.cout_pad, 0);
-        long double bmax = 0;
-        for (int c = 0; c < L.cout; ++c) {
-            bw[c] = (long long)L.q_b[c] * (1ll << bshl);
-            bmax = std::max(bmax, (long double)std::llabs(bw[c]));
-        }
-        long double lim = acc_bound(L, o, F, sa_i, false) + bmax;
-        lim *= std::max(std::ldexp(1.0L, lk), (long double)nm);
-        lim = sh < 0 ? lim * std::ldexp(1.0L, -sh) : lim + std::ldexp(1.0L, sh);
-        if (lim >= std::ldexp(1.0L, 62)) return y355_fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
-        L.rq.shl = shl;
-        L.rq.sh = sh;
-        L.rq.lk = lk;
-        L.rq.neg_mul = nm;
-        {
-            // 32-bit epilogue (y355_requant_gen32) when |t| * max(2^max(0, lk - sh), neg_mul * 2^max(0, -sh)) + rounding < 2^31
-            // |acc| <= 127 * (sum |q_w| of the channel): the layer's own weights give a tighter bound than 127 per weight
-            const long double accs = acc_bound(L, o, F, sa_i, true);      // max over the channels of |acc| * 2^shl[c]
-            long double t32 = accs + bmax;
-            const long double fpos = std::ldexp(1.0L, std::max(0, lk - sh)), fneg = (long double)nm * std::ldexp(1.0L, std::max(0, -sh));
-            t32 = t32 * std::max(fpos, fneg) + std::ldexp(1.0L, std::max(sh, 0));
-            L.rq.narrow = (t32 < std::ldexp(1.0L, 31) && bmax < std::ldexp(1.0L, 31)) ? 1 : 0;
-            L.rq.split = 0;
-            if (!L.rq.narrow && sh >= 9 && sh <= 31 && nm >= 1 && nm < 4096) {
-                // t itself and the positive branch fit 32 bits, only t * neg_mul does not: the negative branch goes in two halves
-                const long double tb = accs + bmax;
-                const long double pos = tb * fpos + std::ldexp(1.0L, std::max(sh - lk, 0));
-                const long double neg = (tb / 256 + 1) * nm + 256 + std::ldexp(1.0L, sh - 9);
-                if (tb < std::ldexp(1.0L, 30) && pos < std::ldexp(1.0L, 31) && neg < std::ldexp(1.0L, 31) && bmax < std::ldexp(1.0L, 31))
-                    L.rq.narrow = L.rq.split = 1;
-            }
-        }
-        if (o.res1) {                  // residual: its own 64-bit bound, and its own 32-bit form (no split)
-            int narrow = 0;
-            if (res_params(h, o, L, &L.rr, &narrow)) return y355_fail(Y355_ERANGE, "residual epilogue exceeds 62 bits");
-            L.rq.narrow = narrow;
-            L.rq.split = 0;
-        }
-        L.rq1 = Requant{};
-        L.rq1.shl = shl;
-        L.rq1.sh = sh;
-        L.rq1.leaky = (lk || nm != 1) ? 1 : 0;
-        L.rq1.lk = lk;
-        L.rq1.neg_mul = nm;
-        L.rq1.guard_log2 = 63;
-        L.rq1.wide = 1;
-        // the first layer runs conv1.hip's fast kernel when the general-slope epilogue fits 32 bits:
-        //   |t| * max(2^max(0, lk - sh), neg_mul * 2^max(0, -sh)) + rounding < 2^31          (y355_requant_gen32)
-        L.rq1.gen32 = 0;
-        std::vector<int32_t> bt(L.cout_pad, 0);
-        if (o.type == OP_CONV1) {
-            long double t32 = acc_bound(L, o, F, sa_i, false) + bmax;
-            const long double fpos = std::ldexp(1.0L, std::max(0, lk - sh)), fneg = (long double)nm * std::ldexp(1.0L, std::max(0, -sh));
-            t32 = t32 * std::max(fpos, fneg) + std::ldexp(1.0L, std::max(sh, 0));
-            if (t32 < std::ldexp(1.0L, 31) && bmax < std::ldexp(1.0L, 31)) {
-                L.rq1.gen32 = 1;
-                for (int c = 0; c < L.cout; ++c) bt[c] = (int32_t)bw[c];
-            }
-            // int8 nets have no float bias: the layer's bias_dev (4 bytes per channel) holds the 32-bit copy
-            HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int32_t) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-        }
-        if (h->front_graph && (i == 0 || i == 1)) {
-            // the same epilogue for front.hip: t = acc * 2^shl + bias below 2^24 (exact in fp32) on the layer's own weights
-            Requant &fr = i == 0 ? h->frq1 : h->frq2;
-            fr = Requant{};
-            fr.shl = shl; fr.sh = sh; fr.lk = lk; fr.neg_mul = nm; fr.leaky = (lk || nm != 1) ? 1 : 0; fr.guard_log2 = 63;
-            const long double tb = acc_bound(L, o, F, sa_i, true) + bmax;
-            fr.tmax_log2 = 0;
-            while (fr.tmax_log2 < 62 && std::ldexp(1.0L, fr.tmax_log2) <= tb) ++fr.tmax_log2;
-            fr.negsafe = std::ldexp(tb * nm, -sh) <= 127.0L ? 1 : 0;
-            // the magic-number rounding needs |t * slope| < 2^22 only where it does not saturate, and |sh| moderate
-            fr.wide = (fr.tmax_log2 > 24 || bmax >= std::ldexp(1.0L, 24) || sh > 30 || sh - lk < -8 || nm < 1 || nm > (1 << lk)) ? 1 : 0;
-            std::vector<int32_t> fb(i == 0 ? 16 : 32, 0);
-            if (!fr.wide) for (int c = 0; c < L.cout; ++c) fb[c] = (int32_t)bw[c];
-            HIPCHK(hipMemcpyAsync(i == 0 ? h->fb1_dev : h->fb2_dev, fb.data(), sizeof(int32_t) * fb.size(), hipMemcpyHostToDevice, h->stream));
-            h->front_dirty = true;
-        }
-        // every output channel's own accumulator shift: in the upper half of the bias word for the 32-bit epilogues of
-        // convg.hip / convr.hip (y355_pc_word; the bias fits 32 bits there), in shl_dev for the 64-bit ones and for conv1.hip
-        std::vector<int> shc(L.cout_pad, 0);
-        for (int c = 0; c < L.cout; ++c) shc[c] = F - sa_i - L.e_wc[c];
-        if (o.type == OP_CONV && L.rq.narrow)
-            for (int c = 0; c < L.cout; ++c) bw[c] = y355_pc_word(shc[c], (int)bw[c]);
-        HIPCHK(hipMemcpyAsync(L.shl_dev, shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipMemcpyAsync(L.bias_w_dev, bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-        HIPCHK(hipStreamSynchronize(h->stream));
-        L.dirty = false;
+    const OpDef &o = h->arch->ops[i];
+    if (o.type != OP_CONV1 && o.type != OP_CONV) return 0;
+    NLayer &L = h->L[o.layer];
+    if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
+    if (!L.dirty) return 0;
+    ConvFixed cf;
+    if (int rc = conv_fixed(h, o, L, &cf)) return rc;
+    const int lk = cf.lk, nm = cf.nm, sh = cf.E - h->sa[o.out];
+    if (sh > 62 || sh < -20) return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
+    // worst case |t'| (through the slope and a left shift / the rounding add) must stay below 2^62
+    long double lim = cf.tw * cf.slope();
+    lim = sh < 0 ? lim * std::ldexp(1.0L, -sh) : lim + std::ldexp(1.0L, sh);
+    if (lim >= std::ldexp(1.0L, 62)) return y355_fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
+    // 32-bit epilogue on the layer's own weights: a tighter bound than 127 per weight
+    L.rq = RequantG{cf.shl, sh, lk, nm, fits32(cf, cf.tb, sh) ? 1 : 0, 0};
+    if (!L.rq.narrow && sh >= 9 && sh <= 31 && nm >= 1 && nm < 4096) {
+        // t itself and the positive branch fit 32 bits, only t * neg_mul does not: the negative branch goes in two halves
+        const long double pos = cf.tb * std::ldexp(1.0L, std::max(0, lk - sh)) + std::ldexp(1.0L, std::max(sh - lk, 0));
+        const long double neg = (cf.tb / 256 + 1) * nm + 256 + std::ldexp(1.0L, sh - 9);
+        if (cf.tb < std::ldexp(1.0L, 30) && pos < std::ldexp(1.0L, 31) && neg < std::ldexp(1.0L, 31) && cf.bmax < std::ldexp(1.0L, 31))
+            L.rq.narrow = L.rq.split = 1;
     }
+    if (o.res1) {                  // residual: its own 64-bit bound, and its own 32-bit form (no split)
+        int narrow = 0;
+        if (res_params(h, o, cf, &L.rr, &narrow)) return y355_fail(Y355_ERANGE, "residual epilogue exceeds 62 bits");
+        L.rq.narrow = narrow;
+        L.rq.split = 0;
+    }
+    L.rq1 = requant_of(cf, sh);
+    L.rq1.wide = 1;
+    if (o.type == OP_CONV1) {
+        // the first layer runs conv1.hip's fast kernel when the epilogue fits 32 bits for worst-case weights.  int8 nets have
+        // no float bias: the layer's bias_dev (4 bytes per channel) holds the 32-bit copy
+        L.rq1.gen32 = fits32(cf, cf.tw, sh) ? 1 : 0;
+        std::vector<int32_t> bt(L.cout_pad, 0);
+        if (L.rq1.gen32) for (int c = 0; c < L.cout; ++c) bt[c] = (int32_t)cf.bw[c];
+        HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int32_t) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+    }
+    if (h->front_graph && (i == 0 || i == 1)) {
+        // the same epilogue for front.hip: t = acc * 2^shl + bias below 2^24 (exact in fp32) on the layer's own weights
+        Requant &fr = i == 0 ? h->frq1 : h->frq2;
+        fr = requant_of(cf, sh);
+        while (fr.tmax_log2 < 62 && std::ldexp(1.0L, fr.tmax_log2) <= cf.tb) ++fr.tmax_log2;
+        fr.negsafe = std::ldexp(cf.tb * nm, -sh) <= 127.0L ? 1 : 0;
+        // the magic-number rounding needs |t * slope| < 2^22 only where it does not saturate, and |sh| moderate
+        fr.wide = (fr.tmax_log2 > 24 || cf.bmax >= std::ldexp(1.0L, 24) || sh > 30 || sh - lk < -8 || nm < 1 || nm > (1 << lk)) ? 1 : 0;
+        std::vector<int32_t> fb(i == 0 ? 16 : 32, 0);
+        if (!fr.wide) for (int c = 0; c < L.cout; ++c) fb[c] = (int32_t)cf.bw[c];
+        HIPCHK(hipMemcpyAsync(i == 0 ? h->fb1_dev : h->fb2_dev, fb.data(), sizeof(int32_t) * fb.size(), hipMemcpyHostToDevice, h->stream));
+        h->front_dirty = true;
+    }
+    // every output channel's own accumulator shift: in the upper half of the bias word for the 32-bit epilogues of
+    // convg.hip / convr.hip (y355_pc_word; the bias fits 32 bits there), in shl_dev for the 64-bit ones and for conv1.hip
+    if (o.type == OP_CONV && L.rq.narrow)
+        for (int c = 0; c < L.cout; ++c) cf.bw[c] = y355_pc_word(cf.shc[c], (int)cf.bw[c]);
+    HIPCHK(hipMemcpyAsync(L.shl_dev, cf.shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(L.bias_w_dev, cf.bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    L.dirty = false;
     return 0;
 }
 
@@ -1336,84 +741,6 @@ static int refresh_i8(y355_net *h) {
     return 0;
 }
 
-// fp32 NCHW [B][3][H][W] -> bf16 NHWC16 with halo (channels 3..15 stay zero)
-__global__ void input_bf16_kernel(const float *x, char *out, int B, int H, int W, int out_pb) {
-    const size_t total = (size_t)B * H * W;
-    const size_t plane = (size_t)H * W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int xx = (int)(i % W), y = (int)((i / W) % H);
-        const size_t b = i / plane;
-        const float *src = x + b * 3 * plane + (size_t)y * W + xx;
-        unsigned short h3[4] = {__builtin_bit_cast(unsigned short, (__bf16)src[0]), __builtin_bit_cast(unsigned short, (__bf16)src[plane]),
-                                __builtin_bit_cast(unsigned short, (__bf16)src[2 * plane]), 0};
-        uint2 u;
-        u.x = (unsigned int)h3[0] | ((unsigned int)h3[1] << 16);
-        u.y = (unsigned int)h3[2];
-        *(uint2 *)(out + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + xx + 1) * out_pb) = u;
-    }
-}
-// utils.modules.reorg_layer (utils/modules.py:48-57) on bf16 NHWC: out[.., (sy*s+sx)*C + c] = in[s*y+sy][s*x+sx][c];
-// 16 bytes (8 channels) per thread
-__global__ void reorg_bf16_kernel(const char *in, char *out, int B, int Hin, int Win, int in_pb, int C, int out_pb, int out_off, int s) {
-    const int Ho = Hin / s, Wo = Win / s, cg = C / 8;
-    const size_t total = (size_t)B * Ho * Wo * s * s * cg;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int g = (int)(i % cg);
-        const int k = (int)((i / cg) % (s * s));
-        const int x = (int)((i / ((size_t)cg * s * s)) % Wo), y = (int)((i / ((size_t)cg * s * s * Wo)) % Ho);
-        const size_t b = i / ((size_t)cg * s * s * Wo * Ho);
-        const int sy = k / s, sx = k % s;
-        const uint4 v = *(const uint4 *)(in + ((b * (Hin + 2) + (size_t)s * y + sy + 1) * (Win + 2) + (size_t)s * x + sx + 1) * in_pb + g * 16);
-        *(uint4 *)(out + ((b * (Ho + 2) + y + 1) * (size_t)(Wo + 2) + x + 1) * out_pb + out_off + ((size_t)k * C + g * 8) * 2) = v;
-    }
-}
-
-// utils.modules.SPP (utils/modules.py:66-72) on bf16 NHWC, in place in a 4C-channel buffer: channels [0, C) are x, the
-// kernel writes max_pool 5 / 9 / 13 (stride 1, windows clipped to the map = -inf padding) to [C,2C), [2C,3C), [3C,4C).
-// bf16 compares as fp32; 8 channels (16 bytes) per thread.
-__global__ void spp_bf16_kernel(char *buf, int B, int H, int W, int pb, int C) {
-    const int cg = C / 8;
-    const size_t total = (size_t)B * H * W * cg;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (size_t)gridDim.x * blockDim.x) {
-        const int g = (int)(i % cg);
-        const int x = (int)((i / cg) % W), y = (int)((i / ((size_t)cg * W)) % H);
-        const size_t b = i / ((size_t)cg * W * H);
-        float m5[8], m9[8], m13[8];
-#pragma unroll
-        for (int k = 0; k < 8; ++k) m5[k] = m9[k] = m13[k] = -INFINITY;
-        for (int dy = -6; dy <= 6; ++dy) {
-            const int yy = y + dy;
-            if (yy < 0 || yy >= H) continue;
-            for (int dx = -6; dx <= 6; ++dx) {
-                const int xx = x + dx;
-                if (xx < 0 || xx >= W) continue;
-                const uint4 v = *(const uint4 *)(buf + ((b * (H + 2) + yy + 1) * (size_t)(W + 2) + xx + 1) * pb + g * 16);
-                const unsigned int u[4] = {v.x, v.y, v.z, v.w};
-                const int r = max(abs(dy), abs(dx));
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    const float f = __uint_as_float((k & 1) ? (u[k >> 1] & 0xffff0000u) : (u[k >> 1] << 16));
-                    m13[k] = fmaxf(m13[k], f);
-                    if (r <= 4) m9[k] = fmaxf(m9[k], f);
-                    if (r <= 2) m5[k] = fmaxf(m5[k], f);
-                }
-            }
-        }
-        char *o = buf + ((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * pb + g * 16;
-        auto pack = [](const float (&m)[8]) {
-            uint4 r;
-            unsigned int w[4];
-#pragma unroll
-            for (int k = 0; k < 4; ++k) w[k] = (__float_as_uint(m[2 * k]) >> 16) | (__float_as_uint(m[2 * k + 1]) & 0xffff0000u);
-            r.x = w[0]; r.y = w[1]; r.z = w[2]; r.w = w[3];
-            return r;
-        };
-        *(uint4 *)(o + (size_t)C * 2) = pack(m5);
-        *(uint4 *)(o + (size_t)C * 4) = pack(m9);
-        *(uint4 *)(o + (size_t)C * 6) = pack(m13);
-    }
-}
-
 // bytes of input channels a convolution consumes per pixel (its K extent): o.cin rounded up to the channel quantum --
 // the whole pixel for ordinary tensors, a leading channel range for concat buffers read before they are complete
 static int in_kbytes(const y355_net *h, const OpDef &o) {
@@ -1428,54 +755,55 @@ static int in_kbytes(const y355_net *h, const OpDef &o) {
 
 static float act_slope(int act) { return act == ACT_L125 ? 0.125f : act == ACT_L100 ? 0.1f : 1.0f; }
 
-static int run_op(y355_net *h, int i, int B, const NetInput &in) {
+// the network-input fields the first-layer launch structs share (Conv1Params, Conv1FParams, FrontParams, FrontBParams);
+// the u8 routes of these kernels get frames at the network size
+template <class P>
+static void fill_input(P &p, const y355_net *h, const NetInput &in, int B) {
+    p.x = in.x;
+    p.x_u8 = in.u8;
+    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->norm.mean[c]; p.nstd[c] = h->norm.sd[c]; }
+    p.B = B;
+    p.H = h->cfg.height;
+    p.W = h->cfg.width;
+}
+
+// what a launch of run_op is for.  The two passes of a calibration step (y355_net_calibrate) run on the generic kernels:
+// PASS_CAL_STAT takes a convolution's maximum |t'| with the constants of cal_conv_max and writes nothing (other ops: no such
+// pass), PASS_CAL_WRITE writes the op's output as a forward does
+enum Pass { PASS_FORWARD = 0, PASS_CAL_STAT, PASS_CAL_WRITE };
+
+static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
     const OpDef &o = h->arch->ops[i];
     hipStream_t s = h->stream;
+    const bool stat = pass == PASS_CAL_STAT, generic_only = pass != PASS_FORWARD;
+    const bool bf = h->bf;
     if (o.type == OP_CONV1) {
         NLayer &L = h->L[o.layer];
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
-        if (!h->bf) {
+        if (!bf) {
             L.route = Y355_ROUTE_FIRST | (L.rq1.gen32 ? 0 : Y355_ROUTE_EPI64) | (L.pc ? Y355_ROUTE_PER_CHANNEL : 0);
             Conv1Params p{};
-            p.x = in.x;
-            p.x_u8 = in.u8;                                    // (conv1 routes get frames at the network size)
-            for (int c = 0; c < 3; ++c) { p.nmean[c] = h->norm.mean[c]; p.nstd[c] = h->norm.sd[c]; }
+            fill_input(p, h, in, B);
             p.out = (int8_t *)h->T[o.out].dev;
             p.out_pb = (int)h->T[o.out].pb;
             p.w = (const int8_t *)h->w0_dev;
             p.bias_w = L.bias_w_dev;
-            p.bias_t = L.rq1.gen32 ? (const int *)L.bias_dev : nullptr;
-            p.shl_c = L.pc ? L.shl_dev : nullptr;
-            p.ctr = h->ctr_dev + i;
-            p.B = B;
-            p.H = h->cfg.height;
-            p.W = h->cfg.width;
+            p.bias_t = L.rq1.gen32 ? (const int *)L.bias_dev : nullptr;          // (never in a statistics pass)
+            p.shl_c = L.pc || stat ? L.shl_dev : nullptr;
+            p.ctr = (stat ? h->cal_dev : h->ctr_dev) + i;
             y355_conv1_tiles(p.H, p.W, &p.tiles_x, &p.tiles_y);
             p.in_scale = std::ldexp(1.0f, h->sa_in);
             p.rq = L.rq1;
-            p.mode = 0;
-            p.guard = 0;
-            if (h->calibrating && L.dirty) {                   // statistics pass of a calibration step (cal_conv_max): max |t'| only
-                p.mode = 1;
-                p.ctr = h->cal_dev + i;
-                p.bias_t = nullptr;
-                p.shl_c = L.shl_dev;
-                p.rq.gen32 = 0;
-            }
+            p.mode = stat ? 1 : 0;                             // 1: max |t'| only
             y355_launch_conv1(p, s);
             HIPCHK(hipGetLastError());
             return 0;
         }
         Conv1FParams p{};
-        p.x = in.x;
-        p.x_u8 = in.u8;
-        for (int c = 0; c < 3; ++c) { p.nmean[c] = h->norm.mean[c]; p.nstd[c] = h->norm.sd[c]; }
+        fill_input(p, h, in, B);
         p.out = h->T[o.out].dev;
         p.w = h->w0_dev;
         p.bias = L.bias_dev;
-        p.B = B;
-        p.H = h->cfg.height;
-        p.W = h->cfg.width;
         y355_conv1f_tiles(p.H, p.W, &p.tiles_x, &p.tiles_y);
         p.slope = act_slope(o.act);
         L.route = Y355_ROUTE_FIRST;
@@ -1484,7 +812,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
         NLayer &L = h->L[o.layer];
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
         const Tensor &ti = h->T[o.in], &to = h->T[o.out];
-        const ConvGInfo &ki = *y355_convg_kernel(h->bf, L.kid);
+        const ConvGInfo &ki = *y355_convg_kernel(bf, L.kid);
         ConvGParams p{};
         p.in = ti.dev;
         p.out = to.dev;
@@ -1493,16 +821,16 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
         p.bias_w = L.bias_w_dev;
         p.shl_w = L.shl_dev;
         p.pc = L.pc ? 1 : 0;
-        p.ctr = h->ctr_dev + i;
+        p.ctr = (stat ? h->cal_dev : h->ctr_dev) + i;
         p.rq = L.rq;
-        const int rflags = h->bf ? 0 : ((L.rq.narrow ? 0 : Y355_ROUTE_EPI64) | (o.res1 ? Y355_ROUTE_RESIDUAL : 0) | (L.pc ? Y355_ROUTE_PER_CHANNEL : 0));
+        const int rflags = bf ? 0 : ((L.rq.narrow ? 0 : Y355_ROUTE_EPI64) | (o.res1 ? Y355_ROUTE_RESIDUAL : 0) | (L.pc ? Y355_ROUTE_PER_CHANNEL : 0));
         p.B = B;
         p.H = ti.H;
         p.W = ti.W;
         p.in_pb = (int)ti.pb;
         p.nchunks = in_kbytes(h, o) / ki.chb;
         p.out_pb = (int)to.pb;
-        p.out_off = o.choff * ((to.pred && h->bf) ? 4 : h->es);
+        p.out_off = o.choff * ((to.pred && bf) ? 4 : h->es);
         p.out_halo = to.halo;
         const int Ho = o.stride2 ? (ti.H + 1) / 2 : ti.H, Wo = o.stride2 ? (ti.W + 1) / 2 : ti.W;
         p.tiles_x = (Wo + ki.tw - 1) / ki.tw;
@@ -1517,15 +845,14 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
         p.nblk = L.cout_pad / ki.bn;
         p.taps = o.ksize * o.ksize;
         p.slope = act_slope(o.act);
-        p.out_f32 = to.pred && h->bf;
+        p.out_f32 = to.pred && bf;
         p.grid_limit = h->tput_wgs;
-        if (h->calibrating && L.dirty) {                       // statistics pass of a calibration step (cal_conv_max)
-            p.ctr = h->cal_dev + i;
+        if (stat) {
             ki.launch_stat(p, p.tiles_x * p.tiles_y * p.nblk * B, s);
             HIPCHK(hipGetLastError());
             return 0;
         }
-        if (L.rid == -2 && !h->calibrating) {                  // int8 1x1: pointwise kernel (convr.hip)
+        if (L.rid == -2 && !generic_only) {                    // int8 1x1: pointwise kernel (convr.hip)
             ConvGParams q = p;
             q.w = L.wr_dev;
             q.nblk = L.cout_pad / 64;
@@ -1544,7 +871,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
                 return 0;
             }
         }
-        if (L.rid >= 0 && !h->calibrating) {                   // 3x3: weights through an LDS ring (convr.hip)
+        if (L.rid >= 0 && !generic_only) {                     // 3x3: weights through an LDS ring (convr.hip)
             ConvGParams q = p;
             q.w = L.wr_dev;
             q.nblk = L.cout_pad / y355_convr_info(L.rid)->bn;
@@ -1556,68 +883,19 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in) {
         }
         L.route = (ki.wm * ki.wn == 8 ? Y355_ROUTE_GENERIC8 : Y355_ROUTE_GENERIC4) | rflags;
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * B, s);
-    } else if (o.type == OP_POOL) {
-        const Tensor &ti = h->T[o.in], &to = h->T[o.out];
-        const int stride = o.pool ? 1 : 2;
-        const size_t total = (size_t)B * to.H * to.W * (o.cin * h->es / 16);
-        const int blocks = (int)std::min<size_t>((total + 255) / 256, 4096);
-        if (h->bf)
-            hipLaunchKernelGGL(pool_bf16_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb,
-                               o.cin * h->es, to.H, to.W, (int)to.pb, stride);
-        else
-            hipLaunchKernelGGL(pool_i8_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb,
-                               o.cin * h->es, to.H, to.W, (int)to.pb, stride);
     } else if (o.type == OP_INPUT) {
-        const Tensor &to = h->T[o.out];
-        const size_t total = (size_t)B * to.H * to.W;
-        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-        if (in.u8 && h->bf)
-            hipLaunchKernelGGL(input_u8_kernel<false>, dim3(blocks), dim3(256), 0, s, in.u8, in.tab, to.dev, B, in.sh, in.sw, to.H, to.W,
-                               (int)to.pb, h->norm, 1.0f, (Counters *)nullptr);
-        else if (in.u8)
-            hipLaunchKernelGGL(input_u8_kernel<true>, dim3(blocks), dim3(256), 0, s, in.u8, in.tab, to.dev, B, in.sh, in.sw, to.H, to.W,
-                               (int)to.pb, h->norm, std::ldexp(1.0f, h->sa_in), h->ctr_dev + i);
-        else if (h->bf)
-            hipLaunchKernelGGL(input_bf16_kernel, dim3(blocks), dim3(256), 0, s, in.x, to.dev, B, to.H, to.W, (int)to.pb);
-        else
-            hipLaunchKernelGGL(input_i8_kernel, dim3(blocks), dim3(256), 0, s, in.x, to.dev, B, to.H, to.W, (int)to.pb,
-                               std::ldexp(1.0f, h->sa_in), h->ctr_dev + i);
+        y355_launch_input(bf, in.x, in.u8, in.tab, in.sh, in.sw, h->norm, map_of(h->T[o.out]), B, bf ? 1.0f : std::ldexp(1.0f, h->sa_in),
+                          h->ctr_dev + i, s);
+    } else if (o.type == OP_POOL) {
+        y355_launch_pool(bf, map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin * h->es, o.pool ? 1 : 2, s);
     } else if (o.type == OP_SPP) {
-        const Tensor &t = h->T[o.in];
-        const int per = h->bf ? 8 : 16;                        // channels per thread (16 bytes)
-        const size_t total = (size_t)B * t.H * t.W * (o.cin / per);
-        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-        if (h->bf)
-            hipLaunchKernelGGL(spp_bf16_kernel, dim3(blocks), dim3(256), 0, s, t.dev, B, t.H, t.W, (int)t.pb, o.cin);
-        else
-            hipLaunchKernelGGL(spp_i8_kernel, dim3(blocks), dim3(256), 0, s, t.dev, B, t.H, t.W, (int)t.pb, o.cin);
+        y355_launch_spp(bf, map_of(h->T[o.in]), B, o.cin, s);
     } else if (o.type == OP_REORG) {
-        const Tensor &ti = h->T[o.in], &to = h->T[o.out];
-        const int per = h->bf ? 8 : 16;
-        const size_t total = (size_t)B * to.H * to.W * o.ksize * o.ksize * (o.cin / per);
-        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-        if (h->bf)
-            hipLaunchKernelGGL(reorg_bf16_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb, o.cin,
-                               (int)to.pb, o.choff * h->es, o.ksize);
-        else
-            hipLaunchKernelGGL(reorg_i8_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb, o.cin,
-                               (int)to.pb, o.choff, o.ksize, h->sa[o.out] - h->sa[o.in], h->ctr_dev + i);
-    } else {
-        const Tensor &ti = h->T[o.in], &to = h->T[o.out];
-        const size_t total = (size_t)B * to.H * to.W * o.cin;
-        const int blocks = (int)std::min<size_t>((total + 255) / 256, 8192);
-        const float ry = (float)(ti.H - 1) / (float)(to.H - 1), rx = (float)(ti.W - 1) / (float)(to.W - 1);
-        if (h->bf)
-            hipLaunchKernelGGL(upsample_bf16_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb, o.cin,
-                               (int)to.pb, o.choff * h->es, ry, rx);
-        else if (o.cin % 16 == 0 && ti.pb % 16 == 0 && to.pb % 16 == 0 && (o.choff * h->es) % 16 == 0 &&
-                 (long long)B * to.H * to.W * (o.cin / 16) < (1ll << 31)) {
-            const int items = B * to.H * to.W * (o.cin / 16);
-            hipLaunchKernelGGL(upsample_i8x16_kernel, dim3((items + 255) / 256), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb,
-                               o.cin, (int)to.pb, o.choff * h->es, ry, rx, std::ldexp(1.0f, h->sa[o.out] - h->sa[o.in]));
-        } else
-            hipLaunchKernelGGL(upsample_i8_kernel, dim3(blocks), dim3(256), 0, s, ti.dev, to.dev, B, ti.H, ti.W, (int)ti.pb, o.cin,
-                               (int)to.pb, o.choff * h->es, ry, rx, std::ldexp(1.0f, h->sa[o.out] - h->sa[o.in]));
+        y355_launch_reorg(bf, map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin, o.choff * h->es, o.ksize,
+                          bf ? 0 : h->sa[o.out] - h->sa[o.in], h->ctr_dev + i, s);
+    } else {                                                   // OP_UPSAMPLE (int8: y355_net_create checked y355_upsample_i8_ok)
+        y355_launch_upsample(bf, map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin, o.choff * h->es,
+                             bf ? 1.0f : std::ldexp(1.0f, h->sa[o.out] - h->sa[o.in]), s);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -1664,6 +942,22 @@ static HeadParams net_head_params(y355_net *h, float *ob, float *os, int *oc, in
     return p;
 }
 
+// batch within the handle's; a frame size (none: 1 x 1) within the resize stage's
+static int range_check(const y355_net *h, int batch, int frame_h = 1, int frame_w = 1) {
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (frame_h < 1 || frame_w < 1 || frame_h > 16384 || frame_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+    return 0;
+}
+
+// the stage in front of the first op: frames of another size (in.stage), or a frame list (every frame through the ragged
+// stage), resized into the net-owned buffer the first op reads
+static int pre_stage(y355_net *h, const NetInput &in, int batch) {
+    if (in.stage) y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, batch, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stream);
+    if (in.list) y355_launch_resize_frames(in.list, batch, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+    if (in.stage || in.list) HIPCHK(hipGetLastError());
+    return 0;
+}
+
 // the forward behind y355_net_forward and y355_net_forward_u8 (arguments checked, device set, int8 exponents refreshed)
 static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, float *boxes_dev, float *scores_dev, int32_t *cls_dev,
                        int32_t *count_dev) {
@@ -1679,65 +973,45 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
     h->t0_skipped = fuse_front;
     for (int i = 0; i < nops; ++i) {
         if (prof) HIPCHK(hipEventRecord(h->ev[i], h->stream));
-        if (i == 0 && in.stage) {                       // the resize stage in front of conv1 / the fused front end
-            y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, batch, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stream);
-            HIPCHK(hipGetLastError());
-        }
-        if (i == 0 && in.list) {                        // a frame list: the ragged stage, every frame through it
-            y355_launch_resize_frames(in.list, batch, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
-            HIPCHK(hipGetLastError());
-        }
+        if (i == 0)                                     // (inside the first op's profile interval)
+            if (int rc = pre_stage(h, in, batch)) return rc;
         if (fuse_front && i < 2) {
-            if (i == 0) {
-                if (!h->L[h->arch->ops[0].layer].loaded || !h->L[h->arch->ops[1].layer].loaded)
-                    return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
-                if (h->bf) {
-                    const OpDef &o0 = h->arch->ops[0], &o1 = h->arch->ops[1];
-                    FrontBParams fb{};
-                    fb.x = in.x;
-                    fb.x_u8 = in.u8;                                // (frames at the network size)
-                    for (int c = 0; c < 3; ++c) { fb.nmean[c] = h->norm.mean[c]; fb.nstd[c] = h->norm.sd[c]; }
-                    fb.out = h->T[o1.out].dev;
-                    fb.out_pb = (int)h->T[o1.out].pb;
-                    fb.wf = (const char *)h->wf_dev;
-                    fb.bias1 = h->L[o0.layer].bias_dev;
-                    fb.bias2 = h->L[o1.layer].bias_dev;
-                    fb.B = batch;
-                    fb.H = h->cfg.height;
-                    fb.W = h->cfg.width;
-                    y355_frontb_tiles(fb.H, fb.W, &fb.tiles_x, &fb.tiles_y);
-                    fb.slope1 = act_slope(o0.act);
-                    fb.slope2 = act_slope(o1.act);
-                    y355_launch_frontb(fb, h->stream);
-                    h->L[o0.layer].route = h->L[o1.layer].route = Y355_ROUTE_FRONT;
-                    HIPCHK(hipGetLastError());
-                    continue;
-                }
+            if (i == 1) continue;
+            const OpDef &o0 = h->arch->ops[0], &o1 = h->arch->ops[1];
+            if (!h->L[o0.layer].loaded || !h->L[o1.layer].loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
+            if (h->bf) {
+                FrontBParams fb{};
+                fill_input(fb, h, in, batch);
+                fb.out = h->T[o1.out].dev;
+                fb.out_pb = (int)h->T[o1.out].pb;
+                fb.wf = (const char *)h->wf_dev;
+                fb.bias1 = h->L[o0.layer].bias_dev;
+                fb.bias2 = h->L[o1.layer].bias_dev;
+                y355_frontb_tiles(fb.H, fb.W, &fb.tiles_x, &fb.tiles_y);
+                fb.slope1 = act_slope(o0.act);
+                fb.slope2 = act_slope(o1.act);
+                y355_launch_frontb(fb, h->stream);
+            } else {
                 FrontParams fp{};
-                fp.x = in.x;
-                fp.x_u8 = in.u8;
-                for (int c = 0; c < 3; ++c) { fp.nmean[c] = h->norm.mean[c]; fp.nstd[c] = h->norm.sd[c]; }
-                fp.out = (int8_t *)h->T[h->arch->ops[1].out].dev;
+                fill_input(fp, h, in, batch);
+                fp.out = (int8_t *)h->T[o1.out].dev;
                 fp.wf = h->wf_dev;
                 fp.bias1 = h->fb1_dev;
                 fp.bias2 = h->fb2_dev;
                 fp.ctr = h->ctr_dev;                                // [0] conv1 (+ input), [1] conv2: the two ops' own counters
                 fp.zero_next = (unsigned long long *)h->ctrs.other_zeroed_by_front();
                 fp.zero_n = (nops + 1) * (int)(sizeof(Counters) / 8);
-                fp.B = batch;
-                fp.H = h->cfg.height;
-                fp.W = h->cfg.width;
                 y355_front_tiles(fp.H, fp.W, &fp.tiles_x, &fp.tiles_y);
                 fp.in_scale = std::ldexp(1.0f, h->sa_in);
                 fp.rq1 = h->frq1;
                 fp.rq2 = h->frq2;
                 y355_launch_front(fp, h->stream);
-                h->L[h->arch->ops[0].layer].route = h->L[h->arch->ops[1].layer].route = Y355_ROUTE_FRONT;
-                HIPCHK(hipGetLastError());
             }
+            h->L[o0.layer].route = h->L[o1.layer].route = Y355_ROUTE_FRONT;
+            HIPCHK(hipGetLastError());
             continue;
         }
-        if (int rc = run_op(h, i, batch, in)) return rc;
+        if (int rc = run_op(h, i, batch, in, PASS_FORWARD)) return rc;
     }
     if (prof) HIPCHK(hipEventRecord(h->ev[nops], h->stream));
     HeadParams hp = net_head_params(h, boxes_dev, scores_dev, cls_dev, count_dev);
@@ -1751,7 +1025,7 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
 extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int flags, float *boxes_dev, float *scores_dev,
                                 int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !x_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (int rc = range_check(h, batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (!h->bf)
         if (int rc = refresh_i8(h)) return rc;
@@ -1796,40 +1070,41 @@ static int net_resize_tables(y355_net *h, int src_h, int src_w, bool frames) {
 // network input -- the input op of the DarkNet graphs (with the resize fused into its load), the first layer or the fused front
 // end of the slim / tiny graphs (behind the resize stage when the frames are not at the network size).  Same outputs, bit for
 // bit, as y355_net_forward on the normalised tensor of the resized frames.
-// The fused front ends load a frame row in 12-byte pieces (4 pixels), dword-aligned only when the frames pointer is: slim / tiny
-// frames at an address that is not a multiple of 4 go through the resize stage (the identity at equal sizes) into the
-// net-owned, aligned buffer.  The input op of the DarkNet graphs and the conv1 kernels read single bytes.
+// align4: the fused front ends load a frame row in 12-byte pieces (4 pixels), dword-aligned only when the frames pointer is:
+// slim / tiny frames at an address that is not a multiple of 4 then go through the resize stage (the identity at equal sizes)
+// into the net-owned, aligned buffer.  The input op of the DarkNet graphs and the conv1 kernels (all a calibration step runs)
+// read single bytes.
+static int u8_input(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, bool align4, NetInput *in) {
+    in->u8 = frames_dev;
+    in->sh = src_h;
+    in->sw = src_w;
+    const bool fused = h->arch->ops[0].type == OP_INPUT;              // the input op resizes in its own load
+    if (src_h == h->cfg.height && src_w == h->cfg.width && (fused || !align4 || ((uintptr_t)frames_dev & 3) == 0)) return 0;
+    if (int rc = net_resize_tables(h, src_h, src_w, !fused)) return rc;
+    in->tab = h->rs_tab;
+    if (!fused) {                                                   // staged: pre_stage resizes into rs_frames first
+        in->stage = frames_dev;
+        in->u8 = h->rs_frames;
+    }
+    return 0;
+}
+
 extern "C" int y355_net_forward_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int flags,
                                    float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !frames_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
-    if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+    if (int rc = range_check(h, batch, src_h, src_w)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (!h->bf)
         if (int rc = refresh_i8(h)) return rc;
-    const int H = h->cfg.height, W = h->cfg.width;
     NetInput in;
-    in.u8 = frames_dev;
-    in.sh = src_h;
-    in.sw = src_w;
-    const bool fused = h->arch->ops[0].type == OP_INPUT;              // the input op resizes in its own load
-    const bool aligned = ((uintptr_t)frames_dev & 3) == 0;
-    if (src_h != H || src_w != W || (!fused && !aligned)) {
-        if (int rc = net_resize_tables(h, src_h, src_w, !fused)) return rc;
-        in.tab = h->rs_tab;
-        if (!fused) {                                                   // staged: net_forward resizes into rs_frames first
-            in.stage = frames_dev;
-            in.u8 = h->rs_frames;
-        }
-    }
+    if (int rc = u8_input(h, frames_dev, src_h, src_w, true, &in)) return rc;
     return net_forward(h, in, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
 }
 
 // parity tap of the resize stage: frames [B][src_h][src_w][3] -> out_dev [B][H][W][3] at the network size, on the net's stream
 extern "C" int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, uint8_t *out_dev) {
     if (!h || !frames_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
-    if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+    if (int rc = range_check(h, batch, src_h, src_w)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (int rc = net_resize_tables(h, src_h, src_w, false)) return rc;
     y355_launch_resize_u8(frames_dev, out_dev, h->rs_tab, batch, src_h, src_w, h->cfg.height, h->cfg.width, h->stream);
@@ -1843,11 +1118,11 @@ extern "C" int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int sr
 // The stage builds its tables on the device and takes the descriptors as kernel arguments: nothing is uploaded, nothing
 // waits, whatever the sizes of the previous call were.
 static int frames_check(const y355_net *h, const y355_frame *frames, int batch) {
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (int rc = range_check(h, batch)) return rc;
     for (int i = 0; i < batch; ++i) {
         const y355_frame &f = frames[i];
         if (!f.data_dev) return y355_fail(Y355_EINVAL, "null frame pointer");
-        if (f.height < 1 || f.width < 1 || f.height > 16384 || f.width > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+        if (int rc = range_check(h, batch, f.height, f.width)) return rc;
         if (f.row_bytes != 0 && f.row_bytes < 3 * (int64_t)f.width) return y355_fail(Y355_EINVAL, "row_bytes below width * 3");
     }
     return 0;
@@ -1898,7 +1173,7 @@ extern "C" int y355_net_resize_frames(y355_net *h, const y355_frame *frames, int
 // y355_scale_boxes): boxes_dev [B][max_det][4], count_dev [B], wh_dev [B][2] (width, height)
 extern "C" int y355_net_scale_boxes(y355_net *h, float *boxes_dev, const int32_t *count_dev, const float *wh_dev, int batch) {
     if (!h || !boxes_dev || !count_dev || !wh_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (int rc = range_check(h, batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     y355_launch_scale_boxes(boxes_dev, count_dev, wh_dev, batch, h->max_det, h->stream);
     HIPCHK(hipGetLastError());
@@ -1907,7 +1182,7 @@ extern "C" int y355_net_scale_boxes(y355_net *h, float *boxes_dev, const int32_t
 
 extern "C" int y355_net_get_candidates(y355_net *h, int batch, float *boxes, float *scores, int32_t *cls) {
     if (!h || !boxes || !scores || !cls) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (int rc = range_check(h, batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(boxes, h->cand_box, sizeof(float) * 4 * h->N * batch, hipMemcpyDeviceToHost));
@@ -1919,7 +1194,7 @@ extern "C" int y355_net_get_candidates(y355_net *h, int batch, float *boxes, flo
 // parity tap: tensor idx as fp32 NCHW [B][C][H][W] on the host (halo and channel padding stripped)
 extern "C" int y355_net_get_tensor(y355_net *h, int idx, int batch, float *dst) {
     if (!h || !dst || idx < 0 || idx >= h->arch->ntensors) return y355_fail(Y355_EINVAL, "bad argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (int rc = range_check(h, batch)) return rc;
     if (idx == h->arch->ops[0].out && h->t0_skipped)
         return y355_fail(Y355_ENOTREADY, "the first layer's map of the last forward was not written (fused front end): "
                                          "run the forward with Y355_F_TAP to read it");
@@ -1953,7 +1228,7 @@ extern "C" int y355_net_get_tensor(y355_net *h, int idx, int batch, float *dst) 
 // max |value| of tensor idx (calibration tap for the int8 recipe); synchronous
 extern "C" int y355_net_tensor_absmax(y355_net *h, int idx, int batch, float *out_max) {
     if (!h || !out_max || idx < 0 || idx >= h->arch->ntensors) return y355_fail(Y355_EINVAL, "bad argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (int rc = range_check(h, batch)) return rc;
     const Tensor &t = h->T[idx];
     if (!h->bf) return y355_fail(Y355_EINVAL, "absmax taps exist on bf16 nets (the calibration run)");
     if (t.pred) return y355_fail(Y355_EINVAL, "prediction maps are fp32: read them with y355_net_get_tensor");
@@ -1963,7 +1238,7 @@ extern "C" int y355_net_tensor_absmax(y355_net *h, int idx, int batch, float *ou
     HIPCHK(hipSetDevice(h->cfg.device_id));
     HIPCHK(hipMemsetAsync(h->absmax_dev, 0, 16, h->stream));
     const size_t n = (size_t)batch * (t.H + 2) * (t.W + 2) * t.Cpad;
-    hipLaunchKernelGGL(absmax_bf16_kernel, dim3(1024), dim3(256), 0, h->stream, t.dev, n, h->absmax_dev);
+    y355_launch_absmax_bf16(t.dev, n, h->absmax_dev, h->stream);
     HIPCHK(hipGetLastError());
     unsigned int bits = 0;
     HIPCHK(hipMemcpyAsync(&bits, h->absmax_dev, 4, hipMemcpyDeviceToHost, h->stream));
@@ -2077,28 +1352,17 @@ extern "C" int y355_net_set_trackers(y355_net *h, const float *scale, const int3
 }
 
 // the statistics pass of the convolution of op i: its 64-bit epilogue up to t' (residual: up to the sum u) for the exponents in
-// front of it -- none of this depends on the output's exponent -- then max |.| as the fp32 value y355_calibrate forms from
-// absmax_t / frac_bits (engine.hip).  Leaves the layer dirty: refresh_layer_i8 rebuilds its constants for the write pass.
+// front of it, then max |.| as the fp32 value y355_calibrate forms from absmax_t / frac_bits (engine.hip).  The layer's
+// constants (stale in a calibration step: net_calibrate_run) are the pass's afterwards; refresh_layer_i8 rebuilds them for the
+// write pass.
 static int cal_conv_max(y355_net *h, int i, int B, const NetInput &in, float *out_max) {
     const OpDef &o = h->arch->ops[i];
     NLayer &L = h->L[o.layer];
     if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
-    const int sa_i = o.in < 0 ? h->sa_in : h->sa[o.in];
-    const int F = std::max(sa_i + L.e_w, L.e_b);
-    const int shl = F - sa_i - L.e_w, bshl = F - L.e_b;
-    int lk, nm;
-    act_fixed(o.act, &lk, &nm);
-    int fb = F + lk;                                           // exponent of the tracked integers
-    if (shl_max(L, F, sa_i) > 24 || bshl > 40) return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
-    std::vector<long long> bw(L.cout_pad, 0);
-    std::vector<int> shc(L.cout_pad, 0);
-    long double bmax = 0;
-    for (int c = 0; c < L.cout; ++c) {
-        bw[c] = (long long)L.q_b[c] * (1ll << bshl);
-        shc[c] = F - sa_i - L.e_wc[c];
-        bmax = std::max(bmax, (long double)std::llabs(bw[c]));
-    }
-    long double lim = (acc_bound(L, o, F, sa_i, false) + bmax) * std::max(std::ldexp(1.0L, lk), (long double)nm);
+    ConvFixed cf;
+    if (int rc = conv_fixed(h, o, L, &cf)) return rc;
+    int fb = cf.E;                                             // exponent of the tracked integers
+    long double lim = cf.tw * cf.slope();
     L.rr = ResQ{};
     if (o.res1) {
         const int s_r = h->sa[o.res1 - 1], G = std::max(fb, s_r);
@@ -2109,15 +1373,13 @@ static int cal_conv_max(y355_net *h, int i, int B, const NetInput &in, float *ou
         fb = G;
     }
     if (lim >= std::ldexp(1.0L, 62)) return y355_fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
-    L.rq = RequantG{};
-    L.rq.shl = shl; L.rq.lk = lk; L.rq.neg_mul = nm;
-    L.rq1 = Requant{};
-    L.rq1.shl = shl; L.rq1.leaky = (lk || nm != 1) ? 1 : 0; L.rq1.lk = lk; L.rq1.neg_mul = nm; L.rq1.guard_log2 = 63; L.rq1.wide = 1;
-    L.dirty = true;
-    HIPCHK(hipMemcpyAsync(L.shl_dev, shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(L.bias_w_dev, bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+    L.rq = RequantG{cf.shl, 0, cf.lk, cf.nm, 0, 0};
+    L.rq1 = requant_of(cf, 0);
+    L.rq1.wide = 1;
+    HIPCHK(hipMemcpyAsync(L.shl_dev, cf.shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+    HIPCHK(hipMemcpyAsync(L.bias_w_dev, cf.bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));                   // (the host vectors go out of scope)
-    if (int rc = run_op(h, i, B, in)) return rc;               // calibrating && dirty: the statistics launch
+    if (int rc = run_op(h, i, B, in, PASS_CAL_STAT)) return rc;
     unsigned long long m = 0;
     HIPCHK(hipMemcpyAsync(&m, &h->cal_dev[i].absmax, 8, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2125,8 +1387,8 @@ static int cal_conv_max(y355_net *h, int i, int B, const NetInput &in, float *ou
     return 0;
 }
 
-// one 32-bit maximum of slot i (fp32 bits or an unsigned int) back to the host
-static int cal_read_u32(y355_net *h, int i, unsigned int *v) {
+// the 32-bit maximum of slot i (fp32 bits or an unsigned int) back to the host
+static int cal_read_u32(y355_net *h, int i, void *v) {
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(v, &h->cal_dev[i].absmax, 4, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -2139,6 +1401,7 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
     hipStream_t s = h->stream;
     const std::vector<float> pre_scale = h->trk_scale;
     const std::vector<int> pre_first = h->trk_first;
+    for (auto &L : h->L) L.dirty = true;                       // the step installs new exponents op by op: every layer's constants are stale
     HIPCHK(hipMemsetAsync(h->cal_dev, 0, sizeof(Counters) * (nops + 1), s));
     bool need_zero = false;
     h->ctr_dev = h->ctrs.begin(&need_zero);                    // the write passes count their clamps as a forward does
@@ -2152,28 +1415,17 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
         *e = ex;
         return 0;
     };
+    auto slot = [&](int i) { return (unsigned int *)&h->cal_dev[i].absmax; };
     // ---- tracker 0: max |x| of the fp32 input / of the normalised resized frames
-    if (in.stage) {                                            // slim / tiny frames of another size: the resize stage first
-        y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, s);
-        HIPCHK(hipGetLastError());
-    }
-    if (in.list) {                                             // a frame list: the ragged stage, every frame through it
-        y355_launch_resize_frames(in.list, B, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, s);
-        HIPCHK(hipGetLastError());
-    }
-    unsigned int *slot_in = (unsigned int *)&h->cal_dev[nops].absmax;
+    if (int rc = pre_stage(h, in, B)) return rc;
     if (in.x) {
-        y355_launch_absmax(in.x, (size_t)B * 3 * h->cfg.height * h->cfg.width, slot_in, s);
+        y355_launch_absmax(in.x, (size_t)B * 3 * h->cfg.height * h->cfg.width, slot(nops), s);
     } else {
         const bool staged = in.stage != nullptr || A.ops[0].type != OP_INPUT;      // in.u8 is at the network size
-        const size_t total = (size_t)B * h->cfg.height * h->cfg.width;
-        hipLaunchKernelGGL(absmax_u8_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 4096)), dim3(256), 0, s, in.u8,
-                           staged ? (const int *)nullptr : in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, h->norm, slot_in);
+        y355_launch_absmax_u8(in.u8, staged ? nullptr : in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, h->norm, slot(nops), s);
     }
-    unsigned int bits = 0;
-    if (int rc = cal_read_u32(h, nops, &bits)) return rc;
     float m = 0.f;
-    memcpy(&m, &bits, 4);
+    if (int rc = cal_read_u32(h, nops, &m)) return rc;
     int e = 0;
     if (int rc = step(0, m, &e)) return rc;
     h->sa_in = e;
@@ -2189,21 +1441,14 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
         if (o.type == OP_CONV1 || o.type == OP_CONV) {
             if (int rc = cal_conv_max(h, i, B, run, &mo)) return rc;
         } else if (o.type == OP_UPSAMPLE) {
-            const Tensor &ti = h->T[o.in], &to = h->T[o.out];
-            const size_t total = (size_t)B * to.H * to.W * o.cin;
-            const float ry = (float)(ti.H - 1) / (float)(to.H - 1), rx = (float)(ti.W - 1) / (float)(to.W - 1);
-            hipLaunchKernelGGL(upsample_i8_max_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, ti.dev, B,
-                               ti.H, ti.W, (int)ti.pb, o.cin, ry, rx, (unsigned int *)&h->cal_dev[i].absmax);
-            if (int rc = cal_read_u32(h, i, &bits)) return rc;
-            memcpy(&mo, &bits, 4);
+            y355_launch_upsample_i8_max(map_of(h->T[o.in]), B, o.cin, slot(i), s);
+            if (int rc = cal_read_u32(h, i, &mo)) return rc;
             mo *= std::ldexp(1.0f, -h->sa[o.in]);
         } else if (o.type == OP_REORG) {
-            const Tensor &ti = h->T[o.in];
-            const size_t total = (size_t)B * ti.H * ti.W * o.cin;
-            hipLaunchKernelGGL(absmax_i8_kernel, dim3((int)std::min<size_t>((total + 255) / 256, 8192)), dim3(256), 0, s, ti.dev, B, ti.H,
-                               ti.W, (int)ti.pb, o.cin, (unsigned int *)&h->cal_dev[i].absmax);
-            if (int rc = cal_read_u32(h, i, &bits)) return rc;
-            mo = (float)bits * std::ldexp(1.0f, -h->sa[o.in]);
+            unsigned int q = 0;
+            y355_launch_absmax_i8(map_of(h->T[o.in]), B, o.cin, slot(i), s);
+            if (int rc = cal_read_u32(h, i, &q)) return rc;
+            mo = (float)q * std::ldexp(1.0f, -h->sa[o.in]);
         }
         if (o.type == OP_INPUT || o.type == OP_POOL) {         // aliases: the entry mirrors its source's
             const int src = o.type == OP_INPUT ? 0 : o.in + 1;
@@ -2223,7 +1468,7 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
             }
         }
         if (int rc = refresh_layer_i8(h, i)) return rc;        // the write pass's constants
-        if (int rc = run_op(h, i, B, run)) return rc;
+        if (int rc = run_op(h, i, B, run, PASS_CAL_WRITE)) return rc;
     }
     // ---- buffers with several producers: the update redone from the pre-step state with the maximum over all of them
     for (int t = 0; t < nt; ++t) {
@@ -2242,15 +1487,7 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
         h->sa[o.out] = h->sa[o.in];
     }
     // the exponents the handle keeps: the residual range proof of y355_net_set_act_exponents
-    for (int i = 0; i < nops; ++i) {
-        const OpDef &o = A.ops[i];
-        if (o.type != OP_CONV || !o.res1) continue;
-        ResQ rr{};
-        int narrow = 0;
-        if (res_params(h, o, h->L[o.layer], &rr, &narrow))
-            return y355_fail(Y355_ERANGE, "residual layer: the 64-bit sum of the residual epilogue is not provably in range "
-                                          "for these exponents");
-    }
+    if (int rc = res_range_check(h)) return rc;
     HIPCHK(hipStreamSynchronize(s));
     return 0;
 }
@@ -2263,9 +1500,7 @@ static int net_calibrate(y355_net *h, const NetInput &in, int B, int freeze, dou
     const std::vector<float> keep_scale = h->trk_scale;
     const std::vector<int> keep_first = h->trk_first;
     std::vector<float> mx(h->arch->ntensors + 1, 0.f);
-    h->calibrating = true;
     const int rc = net_calibrate_run(h, in, B, freeze, momentum, mx);
-    h->calibrating = false;
     for (auto &L : h->L) L.dirty = true;
     h->front_dirty = true;
     if (rc) {                                                  // the handle keeps the pre-step state
@@ -2289,7 +1524,7 @@ static int cal_check(y355_net *h, const void *input, int batch, double momentum,
     if (!h || !input) return y355_fail(Y355_EINVAL, "null argument");
     if (h->bf) return y355_fail(Y355_EINVAL, "calibration steps run on int8 nets");
     if (n != h->arch->ntensors + 1) return y355_fail(Y355_EINVAL, "one tracker for the input and one per tensor expected");
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    if (int rc = range_check(h, batch)) return rc;
     if (!(momentum >= 0.0 && momentum <= 1.0)) return y355_fail(Y355_EINVAL, "momentum outside [0, 1]");
     for (const auto &L : h->L)
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
@@ -2308,22 +1543,10 @@ extern "C" int y355_net_calibrate(y355_net *h, const float *x_dev, int batch, in
 extern "C" int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int freeze,
                                      double momentum, int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n) {
     if (int rc = cal_check(h, frames_dev, batch, momentum, n)) return rc;
-    if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+    if (int rc = range_check(h, batch, src_h, src_w)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    const int H = h->cfg.height, W = h->cfg.width;
-    NetInput in;                                               // as y355_net_forward_u8 (conv1.hip reads single bytes: no alignment rule)
-    in.u8 = frames_dev;
-    in.sh = src_h;
-    in.sw = src_w;
-    const bool fused = h->arch->ops[0].type == OP_INPUT;
-    if (src_h != H || src_w != W) {
-        if (int rc = net_resize_tables(h, src_h, src_w, !fused)) return rc;
-        in.tab = h->rs_tab;
-        if (!fused) {
-            in.stage = frames_dev;
-            in.u8 = h->rs_frames;
-        }
-    }
+    NetInput in;
+    if (int rc = u8_input(h, frames_dev, src_h, src_w, false, &in)) return rc;      // conv1.hip reads single bytes: no alignment rule
     return net_calibrate(h, in, batch, freeze, momentum, sa_in_out, sa_out, max_out);
 }
 

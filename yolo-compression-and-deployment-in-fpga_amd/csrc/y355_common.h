@@ -416,6 +416,29 @@ __device__ __forceinline__ void y355_resize_px(const uint8_t *s, const int *tab,
 // y355_resize_tables).  The descriptors travel by value as kernel arguments, 64 frames per launch: `frames` is read here only
 struct y355_frame;
 void y355_launch_resize_frames(const y355_frame *frames, int n, uint8_t *dst, int *tabs, int dh, int dw, hipStream_t s);
+
+// ---- element-wise ops of the y355_net graphs (netops.hip): bf selects the bf16 form, else int8
+struct NormU8 { float mean[3], sd[3]; };        // BaseTransform constants per RGB channel (data/__init__.py:50 lists them in BGR order)
+struct NetMap { char *dev; int H, W, pb; };     // NHWC tensor with a one-pixel halo, [B][H + 2][W + 2][pb bytes]
+void y355_launch_pool(bool bf, const NetMap &in, const NetMap &out, int B, int cbytes, int stride, hipStream_t s);      // 2x2 max, first cbytes of a pixel
+// bilinear x2 (align_corners) of C channels into byte out_off of out's pixels; int8: times rescale, and only where y355_upsample_i8_ok
+void y355_launch_upsample(bool bf, const NetMap &in, const NetMap &out, int B, int C, int out_off, float rescale, hipStream_t s);
+bool y355_upsample_i8_ok(const NetMap &in, const NetMap &out, int B, int C, int out_off);
+// reorg(stride) of C channels into byte out_off of out's pixels; int8: rescaled by 2^d, clamps counted into ctr
+void y355_launch_reorg(bool bf, const NetMap &in, const NetMap &out, int B, int C, int out_off, int stride, int d, Counters *ctr,
+                       hipStream_t s);
+void y355_launch_spp(bool bf, const NetMap &t, int B, int C, hipStream_t s);          // in place: [x | pool5 | pool9 | pool13], C channels each
+// network input: fp32 NCHW x, or (u8 != null) uint8 HWC BGR frames [B][sh][sw][3], resized in the load when tab != null; int8:
+// q = clamp(RNE(v * in_scale)), clamps counted into ctr
+void y355_launch_input(bool bf, const float *x, const uint8_t *u8, const int *tab, int sh, int sw, const NormU8 &nm, const NetMap &out,
+                       int B, float in_scale, Counters *ctr, hipStream_t s);
+// maxima, atomicMax into *out (bits of a non-negative fp32, or an unsigned int for absmax_i8): all n_elems bf16 values of a
+// buffer; |blend| of the int8 bilinear x2 before its rescale; |q| of the first C channels; the normalised frames as the input reads them
+void y355_launch_absmax_bf16(const char *t, size_t n_elems, unsigned int *out_bits, hipStream_t s);
+void y355_launch_upsample_i8_max(const NetMap &in, int B, int C, unsigned int *out_bits, hipStream_t s);
+void y355_launch_absmax_i8(const NetMap &in, int B, int C, unsigned int *out, hipStream_t s);
+void y355_launch_absmax_u8(const uint8_t *frames, const int *tab, int B, int sh, int sw, int H, int W, const NormU8 &nm,
+                           unsigned int *out_bits, hipStream_t s);
 // the evaluators' `bboxes *= [[w, h, w, h]]` of every image, in place (engine.hip); wh [B][2]
 void y355_launch_scale_boxes(float *boxes, const int32_t *count, const float *wh, int batch, int max_det, hipStream_t s);
 

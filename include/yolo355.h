@@ -169,6 +169,32 @@ int y355_forward_u8(y355_engine *h, const uint8_t *frames_dev, int batch, int fl
 int y355_forward_u8_resized(y355_engine *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int flags,
                             float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev,
                             uint8_t *resized_out_dev);
+/* Frame lists: `batch` frames, each with its own device pointer, size and row pitch (the reference's callers hand the network
+ * one image at a time, each of its own size: data/__init__.py:30-56, test.py:79-90, the evaluator loops).  The frames need
+ * not share an allocation and no pointer needs any alignment.  One ragged resize stage (csrc/resize.hip: the arithmetic of
+ * y355_forward_u8_resized with the taps addressed through the pitch, coefficient tables built on the device per frame) writes
+ * every frame into the engine-owned buffer at the network size -- a frame already at that size goes through it too, as the
+ * identity -- and the forward then is y355_forward_u8 on that buffer.
+ * y355_forward_frames: for image i the detections, the candidates (y355_get_candidates) and, under Y355_F_TAP, slice i of all ten
+ * y355_get_feature maps equal y355_forward_u8_resized(h, frames[i].data_dev, height_i, width_i, 1, ...) bit for bit (frames[i]
+ * packed); y355_forward_counters gives the sums of the saturated / guard counts of those single calls; Y355_F_GUARD as in
+ * y355_forward_u8.
+ * y355_resize_frames: the stage alone into out_dev [batch][H][W][3] (parity tap), on the engine's stream.
+ * The `frames` array is read during the call only; the frame DATA must stay valid (and unchanged) until the forward has run on
+ * the device, as every device input of an asynchronous call.  Apart from the first list call of a handle, which allocates the
+ * stage's buffers (the per-frame tables [max_batch][3 (H + W)] are the list route's own: the table y355_forward_u8_resized
+ * caches per source size is neither used nor invalidated), a call does not synchronise with the device, allocate or copy:
+ * lists whose sizes change from call to call cost the same as lists whose sizes repeat.
+ * Errors, checked before any HIP call: a null handle / array / output, a batch outside 1..max_batch, a null data_dev, a size
+ * outside 1..16384 or a row_bytes in 1..3 * width - 1 are Y355_EINVAL. */
+typedef struct y355_frame {
+    const uint8_t *data_dev;   /* uint8 HWC BGR, device pointer, any alignment */
+    int32_t height, width;     /* 1 .. 16384 each */
+    int64_t row_bytes;         /* pitch of one row; 0 = width * 3 (packed); otherwise >= width * 3 */
+} y355_frame;
+int y355_forward_frames(y355_engine *h, const y355_frame *frames /* host array [batch] */, int batch, int flags,
+                        float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev);
+int y355_resize_frames(y355_engine *h, const y355_frame *frames, int batch, uint8_t *out_dev /* [B][H][W][3] */);
 /* same, host pointers in and out (copies through engine-owned staging buffers); synchronous. */
 int y355_forward_host(y355_engine *h, const float *x_host, int batch, int flags,
                       float *boxes, float *scores, int32_t *cls, int32_t *count);
@@ -351,6 +377,12 @@ int y355_unpack_dets(const void *packed_dev, const int32_t *slot_dev, int record
  *               input must already be complete and caller_stream is ignored).  Outputs: the caller's four device buffers (shapes
  *               as y355_forward) or, all four NULL, pipeline-owned ones read with y355_pipeline_outputs.  A ticket and its
  *               pipeline-owned outputs live until y355_pipeline_depth() (= 2 x handles) further submits.
+ *   submit_frames  the same for a list of frames of any sizes (y355_forward_frames on the ticket's handle; flags, outputs, wait,
+ *               outputs, release, fetch and scale_boxes as for the other two submits; the ticket's result equals a stand-alone
+ *               y355_forward_frames' bit for bit).  The `frames` array is read during the call only; the frame data must stay
+ *               valid until the ticket is done.  The list is checked (the rules of y355_forward_frames) before any HIP call, then
+ *               the ticket's handle (weights loaded, exponents set, its stage buffers), all before the pipeline's own state: a
+ *               rejected submit issues no ticket, consumes no release fence and queues no event wait.
  *   wait        on_stream = 0: block the host until the ticket is done; 1: make `caller_stream` wait for it (no host block)
  *   release     optional: tell the pipeline that work queued on `caller_stream` so far is the last reader of the ticket's
  *               outputs -- the submit that reuses the ticket's slot is ordered behind it
@@ -386,6 +418,8 @@ int y355_pipeline_submit(y355_pipeline *p, const float *x_dev, int batch, int fl
                          float *scores_dev, int32_t *cls_dev, int32_t *count_dev, long long *ticket);
 int y355_pipeline_submit_u8(y355_pipeline *p, const uint8_t *frames_dev, int batch, int flags, void *caller_stream, float *boxes_dev,
                             float *scores_dev, int32_t *cls_dev, int32_t *count_dev, long long *ticket);
+int y355_pipeline_submit_frames(y355_pipeline *p, const y355_frame *frames, int batch, int flags, void *caller_stream,
+                                float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev, long long *ticket);
 int y355_pipeline_wait(y355_pipeline *p, long long ticket, int on_stream, void *caller_stream);
 int y355_pipeline_outputs(y355_pipeline *p, long long ticket, float **boxes_dev, float **scores_dev, int32_t **cls_dev,
                           int32_t **count_dev, int *batch);
@@ -600,12 +634,7 @@ int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int
  * the same as lists whose sizes repeat.
  * Errors, checked before any HIP call: a null handle / array / output, a batch outside 1..max_batch, a null data_dev, a size
  * outside 1..16384 or a row_bytes in 1..3 * width - 1 are Y355_EINVAL (and, for y355_net_calibrate_frames, a bf16 net or a
- * wrong n; unloaded weights Y355_ENOTREADY). */
-typedef struct y355_frame {
-    const uint8_t *data_dev;   /* uint8 HWC BGR, device pointer, any alignment */
-    int32_t height, width;     /* 1 .. 16384 each */
-    int64_t row_bytes;         /* pitch of one row; 0 = width * 3 (packed); otherwise >= width * 3 */
-} y355_frame;
+ * wrong n; unloaded weights Y355_ENOTREADY).  y355_frame: declared with y355_forward_frames above. */
 int y355_net_forward_frames(y355_net *h, const y355_frame *frames /* host array [batch] */, int batch, int flags,
                             float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev);
 int y355_net_resize_frames(y355_net *h, const y355_frame *frames, int batch, uint8_t *out_dev /* [B][H][W][3] */);

@@ -195,6 +195,8 @@ struct y355_engine {
     uint8_t *rs_frames = nullptr;
     int *rs_tab = nullptr;          // [xofs W | xa 2W | yofs H | yb 2H]
     int rs_src_h = 0, rs_src_w = 0;
+    int *rs_tabs = nullptr;         // frame lists (y355_forward_frames): [max_batch][3 (H + W)], one set of tables per frame; the
+                                    // list route never touches rs_tab / rs_src_h / rs_src_w, the same-size route's cached table
     int8_t *w0_dev = nullptr;       // conv1 fragment
     int8_t *wf_dev = nullptr;       // weight fragments of the fused front end (y355_pack_front)
     Counters *ctr_dev = nullptr;    // [10]: the set the last forward / layer run counted into (one of ctrs' two)
@@ -964,6 +966,70 @@ extern "C" int y355_forward_u8_resized(y355_engine *h, const uint8_t *frames_dev
         HIPCHK(hipMemcpyAsync(resized_out_dev, h->rs_frames, (size_t)batch * H * W * 3, hipMemcpyDeviceToDevice, h->stream));
     if (!boxes_dev && !scores_dev && !cls_dev && !count_dev) return 0;      // resize only
     return y355_forward_u8(h, h->rs_frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+}
+
+// ---- frame lists: every frame with its own pointer, size and row pitch (the reference's callers: one image at a time, each
+// of its own size).  All frames, those at the network size included, go through the ragged stage of resize.hip into
+// rs_frames; the forward then is y355_forward_u8 on that buffer.  The stage builds its tables on the device (rs_tabs, one set
+// per frame) and takes the descriptors as kernel arguments: nothing is uploaded, nothing waits, and the same-size route's
+// cached table (rs_tab under rs_src_h / rs_src_w) stays what it was.
+int y355_frames_check(const y355_frame *frames, int batch, int max_batch) {
+    if (!frames) return fail(Y355_EINVAL, "null frame array");
+    if (batch < 1 || batch > max_batch) return fail(Y355_EINVAL, "batch out of range");
+    for (int i = 0; i < batch; ++i) {
+        const y355_frame &f = frames[i];
+        if (!f.data_dev) return fail(Y355_EINVAL, "null frame pointer");
+        if (f.height < 1 || f.width < 1 || f.height > 16384 || f.width > 16384) return fail(Y355_EINVAL, "bad frame size");
+        if (f.row_bytes != 0 && f.row_bytes < 3 * (int64_t)f.width) return fail(Y355_EINVAL, "row_bytes below width * 3");
+    }
+    return 0;
+}
+
+// the stage's buffers, allocated at the first list call of a handle (rs_frames may exist already: y355_forward_u8_resized)
+static int list_buffers(y355_engine *h) {
+    const int H = h->cfg.height, W = h->cfg.width;
+    if (!h->rs_tabs)
+        if (int rc = dmalloc(h, (void **)&h->rs_tabs, sizeof(int) * 3 * (size_t)(H + W) * h->cfg.max_batch, false)) return rc;
+    if (!h->rs_frames) {
+        if (int rc = dmalloc(h, (void **)&h->rs_frames, (size_t)h->cfg.max_batch * H * W * 3, false)) return rc;
+        if (int rc = dmalloc(h, (void **)&h->rs_tab, sizeof(int) * 3 * (size_t)(H + W), false)) return rc;
+    }
+    return 0;
+}
+
+// everything of a list forward that can fail, in front of its first launch (and, for y355_pipeline_submit_frames, in front
+// of the pipeline's own state): the list rules and the handle's readiness (weights, exponents) without a HIP call, then the
+// epilogue tables of layers whose exponents changed and the stage's buffers.  What follows it are launches only.
+int y355_frames_prepare(y355_engine *h, const y355_frame *frames, int batch) {
+    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
+    for (int k = 0; k < 10; ++k) {
+        if (!h->L[k].loaded) return fail(Y355_ENOTREADY, "layer weights not loaded");
+        if (!h->sa_set[k] || !h->sa_set[k + 1]) return fail(Y355_ENOTREADY, "activation exponent not set (calibrate first)");
+    }
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    for (int k = 0; k < 10; ++k)
+        if (int rc = refresh_layer(h, k, true)) return rc;
+    return list_buffers(h);
+}
+
+extern "C" int y355_forward_frames(y355_engine *h, const y355_frame *frames, int batch, int flags, float *boxes_dev,
+                                   float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
+    if (!h || !frames || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return fail(Y355_EINVAL, "null argument");
+    if (int rc = y355_frames_prepare(h, frames, batch)) return rc;
+    y355_launch_resize_frames(frames, batch, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+    HIPCHK(hipGetLastError());
+    return y355_forward_u8(h, h->rs_frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+}
+
+// parity tap of the ragged stage: the list -> out_dev [batch][H][W][3] at the network size, on the engine's stream
+extern "C" int y355_resize_frames(y355_engine *h, const y355_frame *frames, int batch, uint8_t *out_dev) {
+    if (!h || !frames || !out_dev) return fail(Y355_EINVAL, "null argument");
+    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = list_buffers(h)) return rc;
+    y355_launch_resize_frames(frames, batch, out_dev, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+    HIPCHK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int y355_forward_host(y355_engine *h, const float *x_host, int batch, int flags, float *boxes,

@@ -18,6 +18,7 @@
 #include <vector>
 
 int y355_fail(int code, const std::string &msg);     // engine.hip: sets the message y355_last_error() returns
+int y355_frames_prepare(y355_engine *h, const y355_frame *frames, int batch);  // engine.hip: all that can fail in y355_forward_frames
 
 namespace {
 int pfail(int code, const std::string &msg) { return y355_fail(code, msg); }
@@ -189,7 +190,9 @@ static int slot_outputs(y355_pipeline *p, Slot &s) {
     return 0;
 }
 
-static int submit_common(y355_pipeline *p, const void *in_dev, bool u8, int batch, int flags, void *caller_stream, float *boxes_dev,
+enum InputKind { IN_F32, IN_U8, IN_LIST };
+
+static int submit_common(y355_pipeline *p, const void *in_dev, InputKind kind, int batch, int flags, void *caller_stream, float *boxes_dev,
                          float *scores_dev, int32_t *cls_dev, int32_t *count_dev, long long *ticket) {
     if (!p || !in_dev || !ticket) return pfail(Y355_EINVAL, "null argument");
     const bool own = !boxes_dev && !scores_dev && !cls_dev && !count_dev;
@@ -213,8 +216,9 @@ static int submit_common(y355_pipeline *p, const void *in_dev, bool u8, int batc
         boxes_dev = s.boxes; scores_dev = s.scores; cls_dev = s.cls; count_dev = s.count;
     }
     const int ef = flags & (Y355_F_GUARD | Y355_F_TAP);
-    const int rc = u8 ? y355_forward_u8(e, (const uint8_t *)in_dev, batch, ef, boxes_dev, scores_dev, cls_dev, count_dev)
-                      : y355_forward(e, (const float *)in_dev, batch, ef, boxes_dev, scores_dev, cls_dev, count_dev);
+    const int rc = kind == IN_LIST ? y355_forward_frames(e, (const y355_frame *)in_dev, batch, ef, boxes_dev, scores_dev, cls_dev, count_dev)
+                   : kind == IN_U8 ? y355_forward_u8(e, (const uint8_t *)in_dev, batch, ef, boxes_dev, scores_dev, cls_dev, count_dev)
+                                   : y355_forward(e, (const float *)in_dev, batch, ef, boxes_dev, scores_dev, cls_dev, count_dev);
     if (rc) return rc;
     PHIPCHK(hipEventRecord(s.done, es));
     s.o_boxes = boxes_dev; s.o_scores = scores_dev; s.o_cls = cls_dev; s.o_count = count_dev;
@@ -227,11 +231,24 @@ static int submit_common(y355_pipeline *p, const void *in_dev, bool u8, int batc
 
 extern "C" int y355_pipeline_submit(y355_pipeline *p, const float *x_dev, int batch, int flags, void *caller_stream,
                                     float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev, long long *ticket) {
-    return submit_common(p, x_dev, false, batch, flags, caller_stream, boxes_dev, scores_dev, cls_dev, count_dev, ticket);
+    return submit_common(p, x_dev, IN_F32, batch, flags, caller_stream, boxes_dev, scores_dev, cls_dev, count_dev, ticket);
 }
 extern "C" int y355_pipeline_submit_u8(y355_pipeline *p, const uint8_t *frames_dev, int batch, int flags, void *caller_stream,
                                        float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev, long long *ticket) {
-    return submit_common(p, frames_dev, true, batch, flags, caller_stream, boxes_dev, scores_dev, cls_dev, count_dev, ticket);
+    return submit_common(p, frames_dev, IN_U8, batch, flags, caller_stream, boxes_dev, scores_dev, cls_dev, count_dev, ticket);
+}
+// a list of frames of any sizes (y355_forward_frames on the ticket's handle).  Everything that can fail in that forward
+// (the list rules, weights and exponents, the stage's buffers: y355_frames_prepare) runs on the ticket's handle first, the
+// list rules before any HIP call: a rejected submit issues no ticket, consumes no release fence and queues no event wait
+extern "C" int y355_pipeline_submit_frames(y355_pipeline *p, const y355_frame *frames, int batch, int flags, void *caller_stream,
+                                           float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev,
+                                           long long *ticket) {
+    if (!p || !frames || !ticket) return pfail(Y355_EINVAL, "null argument");
+    const bool own = !boxes_dev && !scores_dev && !cls_dev && !count_dev;
+    if (!own && (!boxes_dev || !scores_dev || !cls_dev || !count_dev))
+        return pfail(Y355_EINVAL, "give all four output pointers or none (none = pipeline-owned buffers, y355_pipeline_outputs)");
+    if (int rc = y355_frames_prepare(p->eng[(size_t)(p->next % (long long)p->eng.size())], frames, batch)) return rc;
+    return submit_common(p, frames, IN_LIST, batch, flags, caller_stream, boxes_dev, scores_dev, cls_dev, count_dev, ticket);
 }
 
 static int find_slot(y355_pipeline *p, long long ticket, Slot **out) {

@@ -102,6 +102,8 @@ _SIGS = {
     "y355_forward_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "y355_forward_u8_resized": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, C.c_void_p]),
+    "y355_forward_frames": (C.c_int, [C.c_void_p, P(Frame), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_resize_frames": (C.c_int, [C.c_void_p, P(Frame), C.c_int, C.c_void_p]),
     "y355_forward_host": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
     "y355_forward_counters": (C.c_int, [C.c_void_p, P(C.c_int64), P(C.c_int64)]),
     "y355_get_candidates": (C.c_int, [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]),
@@ -179,6 +181,8 @@ _SIGS = {
                                        C.c_void_p, P(C.c_longlong)]),
     "y355_pipeline_submit_u8": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
                                           C.c_void_p, P(C.c_longlong)]),
+    "y355_pipeline_submit_frames": (C.c_int, [C.c_void_p, P(Frame), C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p,
+                                              C.c_void_p, P(C.c_longlong)]),
     "y355_pipeline_wait": (C.c_int, [C.c_void_p, C.c_longlong, C.c_int, C.c_void_p]),
     "y355_pipeline_outputs": (C.c_int, [C.c_void_p, C.c_longlong, P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_void_p), P(C.c_int)]),
     "y355_pipeline_release": (C.c_int, [C.c_void_p, C.c_longlong, C.c_void_p]),

@@ -11,7 +11,7 @@ import weakref
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, framelist
 from .prep import RETUNE, RangeTracker
 
 NUM_LAYERS = 10
@@ -265,6 +265,59 @@ class Engine:
         boxes, scores, cls = ob[:B].cpu().numpy(), os_[:B].cpu().numpy(), oc[:B].cpu().numpy()
         return [(boxes[i, :n[i]].copy(), scores[i, :n[i]].copy(), cls[i, :n[i]].astype(np.int64))
                 for i in range(B)]
+
+    # ---- frame lists: every frame of its own size (y355_forward_frames; include/yolo355.h and DESIGN.md section 6e)
+    def _frame_list(self, frames):
+        """(y355_frame array, B, sizes) of framelist.frame_list on the engine's stream.  Every tensor the launch reads is
+        held until this handle's next list call."""
+        arr, B, sizes, self._held_frames = framelist.frame_list(frames, self.max_batch, self.device, self._stream)
+        return arr, B, sizes
+
+    def resize_frame_list(self, frames):
+        """cv2.resize(image, (W, H)) of BaseTransform for every frame of a list on the GPU (the ragged stage in front of the
+        network, y355_resize_frames); returns a CUDA uint8 tensor [B,H,W,3]."""
+        arr, B, _ = self._frame_list(frames)
+        out = torch.empty((B, self.input_size[0], self.input_size[1], 3), dtype=torch.uint8, device=self.device)
+        cur = self._enter()
+        _ffi.check(self._lib.y355_resize_frames(self._h, arr, B, out.data_ptr()))
+        self._leave(cur)
+        return out
+
+    def forward_frame_list_device(self, frames, flags=0, out=None):
+        """Asynchronous forward on a list of camera frames, uint8 [h,w,3] BGR each of its own size: numpy, CPU torch and
+        CUDA torch frames may be mixed (y355_forward_frames).  Returns the device tensors of forward_device."""
+        arr, B, _ = self._frame_list(frames)
+        ob, os_, oc, on = out if out is not None else self._buffers(B)
+        cur = self._enter()
+        _ffi.check(self._lib.y355_forward_frames(self._h, arr, B, int(flags), ob.data_ptr(), os_.data_ptr(), oc.data_ptr(),
+                                                 on.data_ptr()))
+        self._leave(cur)
+        return ob, os_, oc, on
+
+    def forward_frame_list(self, frames, find=False, tap=False, sizes_wh=None):
+        """Element i equals forward_frames(frames[i][None])[0] (the frame resized by BaseTransform's cv2.resize), bit for bit.
+        sizes_wh: None, [B,2] original (width, height) per image, or "own": every image's boxes rescaled by its own source
+        (width, height) -- the evaluators' `bboxes *= [[w, h, w, h]]` on the GPU (y355_scale_boxes)."""
+        framelist.check_sizes_wh(sizes_wh)
+        wh = framelist.sizes_wh_tensor(sizes_wh, framelist.check_frame_list(frames), self.device)
+        out = self.forward_frame_list_device(frames, (_ffi.F_GUARD if find else 0) | (_ffi.F_TAP if tap else 0))
+        if wh is not None:
+            cur = self._enter()
+            _ffi.check(self._lib.y355_scale_boxes(self._h, out[0].data_ptr(), out[3].data_ptr(), wh.data_ptr(), len(frames)))
+            self._leave(cur)
+        return self._collect(len(frames), out, find)
+
+    def _collect(self, B, out, find):
+        """the host lists of a forward's device outputs; find: the head-room guard of that forward, as the reference raises it"""
+        ob, os_, oc, on = out
+        n = on[:B].cpu().numpy()
+        if find:
+            sat, guard = self.counters()
+            if guard:
+                print("too high!!!")
+                raise AssertionError("conv output exceeds the 16-bit head-room (find=True): %d positions" % guard)
+        boxes, scores, cls = ob[:B].cpu().numpy(), os_[:B].cpu().numpy(), oc[:B].cpu().numpy()
+        return [(boxes[i, :n[i]].copy(), scores[i, :n[i]].copy(), cls[i, :n[i]].astype(np.int64)) for i in range(B)]
 
     def forward_scaled(self, x, sizes_wh, find=False, frames=False):
         """Batched forward + the evaluators' `bboxes *= [[w, h, w, h]]` on the GPU (y355_scale_boxes).
@@ -525,6 +578,62 @@ class Pipeline:
         self._tickets[t.value % self.depth] = (t.value, B, (ob, os_, oc, on), xd)   # keeps the input alive until its slot is reused
         return t.value
 
+    def submit_frame_list(self, frames, flags=0, out=None, ordered=True):
+        """submit() for a list of camera frames, uint8 [h,w,3] BGR each of its own size (numpy, CPU torch and CUDA torch frames
+        may be mixed; at most max_batch): y355_pipeline_submit_frames.  Host frames go through one pinned buffer and one
+        asynchronous copy on the ticket's stream, CUDA frames are read in place.  Every tensor the launch reads is held in the
+        ticket's record until its slot is reused (`depth` submits later) and marked with record_stream on the handle's
+        stream, so the caller may drop its frames right after the call."""
+        slot = self._next % self.depth
+        stream = self._tstreams[self._next % self.handles]
+        arr, B, _, held = framelist.frame_list(frames, self.max_batch, self.device, stream)
+        ob, os_, oc, on = out if out is not None else self._slot_bufs(slot)
+        t = C.c_longlong()
+        cur = torch.cuda.current_stream(self.device).cuda_stream if ordered else 0
+        _ffi.check(self._lib.y355_pipeline_submit_frames(self._h, arr, B, int(flags) | (_ffi.PIPE_AFTER_STREAM if ordered else 0), cur,
+                                                         ob.data_ptr(), os_.data_ptr(), oc.data_ptr(), on.data_ptr(), C.byref(t)))
+        self._next = t.value + 1
+        self._tickets[t.value % self.depth] = (t.value, B, (ob, os_, oc, on), held)
+        return t.value
+
+    def forward_frame_list(self, frames, find=False, sizes_wh=None):
+        """Any number of frames of any sizes: chunks of max_batch submitted back to back (up to `depth` in flight), results in
+        order; element i equals Engine.forward_frame_list([frames[i]])[0], bit for bit.  sizes_wh: None, [n,2] original
+        (width, height), or "own" (every image by its own source size).  find=True: the 2^15 head-room guard."""
+        framelist.check_sizes_wh(sizes_wh)
+        sizes = framelist.check_frame_list(frames)          # the whole list before the first submit
+        wh = framelist.sizes_wh_tensor(sizes_wh, sizes, self.device)
+        flags = _ffi.F_GUARD if find else 0
+        return self._run_chunks(len(frames), lambda i0, i1: self.submit_frame_list(list(frames[i0:i1]), flags), wh, find)
+
+    def _run_chunks(self, n, submit_chunk, wh, find):
+        """chunks of max_batch through submit_chunk(i0, i1) -> ticket, up to `depth` in flight, results in order.  wh [n,2]
+        (or None): scale_boxes per ticket, its rows kept in the ticket's record and marked for the ticket's stream like the
+        ticket's inputs.  find: every ticket's guard count is read from its handle before that handle's next forward."""
+        res, tickets = [], []
+        guard = 0
+        for i0 in range(0, n, self.max_batch):
+            if len(tickets) == self.depth:                # the oldest ticket's slot is about to be reused: take its result first
+                res.extend(self.fetch(tickets.pop(0)))
+            t = submit_chunk(i0, min(n, i0 + self.max_batch))
+            if wh is not None:
+                whc = wh[i0:i0 + self.max_batch]
+                whc.record_stream(self._tstreams[t % self.handles])
+                self._tickets[t % self.depth] += (whc,)
+                self.scale_boxes(t, whc)
+            tickets.append(t)
+            if find:                                      # the guard count of THIS forward: its handle's counters, read before the next
+                sat, g = C.c_int64(), C.c_int64()
+                eh = C.c_void_p(self._lib.y355_pipeline_engine(self._h, t % self.handles))
+                _ffi.check(self._lib.y355_forward_counters(eh, C.byref(sat), C.byref(g)))
+                guard += g.value
+        for t in tickets:
+            res.extend(self.fetch(t))
+        if find and guard:
+            print("too high!!!")
+            raise AssertionError("conv output exceeds the 16-bit head-room (find=True): %d positions" % guard)
+        return res
+
     def outputs(self, ticket):
         """(boxes [max_batch,max_det,4], scores, cls, count) device tensors of the ticket; rows >= B / entries >= count[b] undefined.
         Read them after wait(ticket)."""
@@ -593,26 +702,7 @@ class Pipeline:
             if wh.shape[0] != n:
                 raise ValueError("sizes_wh has %d rows for a batch of %d" % (wh.shape[0], n))
         flags = _ffi.F_GUARD if find else 0
-        res, tickets = [], []
-        guard = 0
-        for i0 in range(0, n, self.max_batch):
-            if len(tickets) == self.depth:                # the oldest ticket's slot is about to be reused: take its result first
-                res.extend(self.fetch(tickets.pop(0)))
-            t = self.submit(xd[i0:i0 + self.max_batch], flags, frames=frames)
-            if wh is not None:
-                self.scale_boxes(t, wh[i0:i0 + self.max_batch])
-            tickets.append(t)
-            if find:                                      # the guard count of THIS forward: its handle's counters, read before the next
-                sat, g = C.c_int64(), C.c_int64()
-                eh = C.c_void_p(self._lib.y355_pipeline_engine(self._h, t % self.handles))
-                _ffi.check(self._lib.y355_forward_counters(eh, C.byref(sat), C.byref(g)))
-                guard += g.value
-        for t in tickets:
-            res.extend(self.fetch(t))
-        if find and guard:
-            print("too high!!!")
-            raise AssertionError("conv output exceeds the 16-bit head-room (find=True): %d positions" % guard)
-        return res
+        return self._run_chunks(n, lambda i0, i1: self.submit(xd[i0:i1], flags, frames=frames), wh, find)
 
     def sync(self):
         _ffi.check(self._lib.y355_pipeline_sync(self._h))

@@ -22,7 +22,7 @@ import numpy as np
 import torch
 import torch.nn as nn
 
-from .. import prep
+from .. import framelist, prep
 from ..engine import Engine, Pipeline
 from ..netengine import Net
 from ..utils import Conv2d, Conv2d_fuse
@@ -211,6 +211,31 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         eng.set_act_exponents([t.exponent() for t in trackers])
         eng.set_thresholds(self.conf_thresh, self.nms_thresh)
         return eng.forward_frames(frames, find=find)
+
+    def forward_frame_list(self, frames, quantization=True, find=False, sizes_wh=None):
+        """forward_frames for a list of frames, each uint8 [h,w,3] BGR of its own size (numpy, CPU or CUDA torch, mixed) --
+        what the reference's callers have: one image at a time, resized per image by BaseTransform (data/__init__.py:30-56,
+        test.py:79-90).  Element i equals forward_batch of the tensor the reference's transform makes of frame i, bit for bit.
+        sizes_wh: None, an array [n,2], or "own": every image's boxes rescaled by its own (width, height) on the GPU.
+        Up to PIPELINE_CHUNK frames run as one list forward on the engine, more as chunks in flight on the pipeline.
+        quantization=True needs calibrated trackers (one forward(x, quantization=True) before); quantization=False runs
+        the bf16 y355_net of forward_batch(quantization=False)."""
+        framelist.check_frame_list(frames)
+        if self.trainable:
+            raise NotImplementedError("yolo355 is an inference engine: the training branch "
+                                      "(models/slim_yolo_v2.py:360-382) is out of scope")
+        n = len(frames)
+        if not quantization:
+            net = self._get_f32_net(n, find)
+            net.set_thresholds(self.conf_thresh, self.nms_thresh)
+            return net.forward_frame_list(frames, sizes_wh=sizes_wh)
+        trackers = self._tracker_states()
+        if any(t.first_a == 0 for t in trackers):
+            raise RuntimeError("yolo355: calibrate the trackers with one forward(x, quantization=True) first")
+        target = self._get_pipeline(find) if n > self.PIPELINE_CHUNK else self._get_engine(n, find)
+        target.set_act_exponents([t.exponent() for t in trackers])
+        target.set_thresholds(self.conf_thresh, self.nms_thresh)
+        return target.forward_frame_list(frames, find=find, sizes_wh=sizes_wh)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_version(self):

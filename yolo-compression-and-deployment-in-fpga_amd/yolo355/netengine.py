@@ -6,7 +6,7 @@ import ctypes as C
 import numpy as np
 import torch
 
-from . import _ffi
+from . import _ffi, framelist
 from .engine import _require_gpu
 
 ARCH = {"slim_yolo_v2": _ffi.ARCH_SLIM_V2, "tiny_yolo_v3": _ffi.ARCH_TINY_V3, "yolo_v2": _ffi.ARCH_YOLO_V2,
@@ -250,86 +250,13 @@ class Net:
         return out
 
     # ---- frame lists: every frame of its own size (y355_net_forward_frames; include/yolo355.h and DESIGN.md section 6e)
-    @staticmethod
-    def check_frame_list(frames):
-        """A non-empty list or tuple of uint8 [h,w,3] frames (numpy or torch, h, w >= 1), checked before any device work;
-        returns the (h, w) of every frame."""
-        if not isinstance(frames, (list, tuple)):
-            raise ValueError("frames must be a list or tuple of uint8 [h,w,3] frames, got %s" % type(frames).__name__)
-        if len(frames) == 0:
-            raise ValueError("empty frame list")
-        sizes = []
-        for i, f in enumerate(frames):
-            if not isinstance(f, (np.ndarray, torch.Tensor)):
-                raise ValueError("frame %d must be a numpy array or a torch tensor, got %s" % (i, type(f).__name__))
-            if not (f.dtype == np.uint8 if isinstance(f, np.ndarray) else f.dtype == torch.uint8):
-                raise ValueError("frame %d must be uint8, got %s" % (i, f.dtype))
-            if len(f.shape) != 3 or f.shape[2] != 3:
-                raise ValueError("frame %d must be [h,w,3] (HWC BGR), got %s" % (i, tuple(f.shape)))
-            if f.shape[0] < 1 or f.shape[1] < 1:
-                raise ValueError("frame %d is empty: %s" % (i, tuple(f.shape)))
-            sizes.append((int(f.shape[0]), int(f.shape[1])))
-        return sizes
-
-    @staticmethod
-    def pack_frames(frames, out=None):
-        """Host-only: the host frames of a checked list (numpy, CPU torch) back to back in one uint8 buffer, no padding
-        between them -- a frame starts wherever the one before ends, at any byte.  Returns (buffer, offsets, sizes):
-        offsets[i] is frame i's first byte in the buffer (None for a CUDA frame, which is not packed), sizes[i] its (h, w).
-        out: a uint8 buffer of at least the packed size to fill instead of a new one (the pinned staging buffer)."""
-        sizes = Net.check_frame_list(frames)
-        offsets, total = [], 0
-        for f, (hh, ww) in zip(frames, sizes):
-            if isinstance(f, torch.Tensor) and f.is_cuda:
-                offsets.append(None)
-                continue
-            offsets.append(total)
-            total += hh * ww * 3
-        buf = np.empty(total, np.uint8) if out is None else out
-        for f, o, (hh, ww) in zip(frames, offsets, sizes):
-            if o is not None:
-                buf[o:o + hh * ww * 3].reshape(hh, ww, 3)[...] = f if isinstance(f, np.ndarray) else f.numpy()
-        return buf, offsets, sizes
+    check_frame_list = staticmethod(framelist.check_frame_list)
+    pack_frames = staticmethod(framelist.pack_frames)
 
     def _frame_list(self, frames):
-        """(y355_frame array, B, sizes): host frames through one pinned buffer and one asynchronous copy on the net's
-        stream, CUDA frames in place (a row-pitched view passes its pitch).  Every tensor the launch reads is held until
-        this handle's next list call."""
-        sizes = self.check_frame_list(frames)
-        B = len(frames)
-        if B > self.max_batch:
-            raise ValueError("%d frames > max_batch %d" % (B, self.max_batch))
-        held, base = [], 0
-        nbytes = sum(hh * ww * 3 for f, (hh, ww) in zip(frames, sizes) if not (isinstance(f, torch.Tensor) and f.is_cuda))
-        if nbytes:
-            pinned = torch.empty(nbytes, dtype=torch.uint8, pin_memory=True)
-            _, offsets, _ = self.pack_frames(frames, out=pinned.numpy())
-            cur = torch.cuda.current_stream(self.device)
-            with torch.cuda.device(self.device), torch.cuda.stream(self._stream):
-                dev = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
-                dev.copy_(pinned, non_blocking=True)
-            if cur != self._stream:
-                dev.record_stream(self._stream)
-            held += [pinned, dev]
-            base = dev.data_ptr()
-        else:
-            offsets = [None] * B
-        arr = (_ffi.Frame * B)()
-        for i, (f, o, (hh, ww)) in enumerate(zip(frames, offsets, sizes)):
-            arr[i].height, arr[i].width, arr[i].row_bytes = hh, ww, 0
-            if o is not None:
-                arr[i].data_dev = base + o
-                continue
-            if f.device != self.device:
-                f = f.to(self.device)
-            if f.stride(2) == 1 and f.stride(1) == 3 and f.stride(0) >= 3 * ww:
-                arr[i].row_bytes = int(f.stride(0))
-            else:
-                f = f.contiguous()
-            f.record_stream(self._stream)
-            held.append(f)
-            arr[i].data_dev = f.data_ptr()
-        self._held_frames = held
+        """(y355_frame array, B, sizes) of framelist.frame_list on the net's stream.  Every tensor the launch reads is held
+        until this handle's next list call."""
+        arr, B, sizes, self._held_frames = framelist.frame_list(frames, self.max_batch, self.device, self._stream)
         return arr, B, sizes
 
     def forward_frame_list_device(self, frames, flags=0, out=None):
@@ -351,7 +278,7 @@ class Net:
         self._call(self._lib.y355_net_forward_frames, arr, B, _ffi.F_TAP if tap else 0, ob.data_ptr(), os_.data_ptr(),
                    oc.data_ptr(), on.data_ptr())
         if isinstance(sizes_wh, str):
-            sizes_wh = np.asarray([(ww, hh) for hh, ww in sizes], np.float32)
+            sizes_wh = framelist.own_sizes_wh(sizes)
         return self._collect(B, (ob, os_, oc, on), sizes_wh)
 
     def resize_frame_list(self, frames):

@@ -128,7 +128,7 @@ def _frame_batches(net, dataset, n, batch_size, **kw):
     """(first image, ids, detections) per batch of raw frames: dataset.pull_image(i) -> (img uint8 HWC BGR of any size, id),
     forward_frame_list with every image's boxes rescaled by its own (w, h) on the GPU.  No host transform."""
     if not hasattr(net, "forward_frame_list"):
-        raise TypeError("%s has no forward_frame_list (the y355_net families have)" % type(net).__name__)
+        raise TypeError("%s has no forward_frame_list (the yolo355 model drop-ins have)" % type(net).__name__)
     for i0, i1 in _batches(n, batch_size):
         frames, bids = [], []
         for i in range(i0, i1):
@@ -141,7 +141,8 @@ def _frame_batches(net, dataset, n, batch_size, **kw):
 def voc_all_boxes_frames(net, dataset, num_classes, batch_size=64, quantization=False, num_images=None):
     """voc_all_boxes from the raw images: all_boxes[cls][image] = N x 5 float32 (x1, y1, x2, y2, score) as the loop of
     utils/vocapi_evaluator_mask.py:57-82 builds it, with BaseTransform's resize and normalisation on the GPU.
-    dataset.pull_image(i) -> (img uint8 HWC BGR of any size, id) (data/voc0712.py:148-160); net: a y355_net family model.
+    dataset.pull_image(i) -> (img uint8 HWC BGR of any size, id) (data/voc0712.py:148-160); net: a yolo355 model drop-in (the int8 SlimYOLOv2
+    or a y355_net family).
 
         # utils/vocapi_evaluator_mask.py:49-95  (evaluate)
         - for i in range(num_images):

@@ -96,7 +96,30 @@ int y355_set_thresholds(y355_engine *h, float conf_thresh, float nms_thresh);
  * launches) left the library in round 6 -- scratch/pxpair_r5_all_three_kernels.hip, profiles/r05_notes.md sections 3-5.
  * Results are identical bit for bit in both settings.  Values other than 0 / 1: Y355_EINVAL. */
 #define Y355_OPT_FUSE_PAIRS 3
+/* Y355_OPT_MAX_CANDIDATES (default 4096): the most anchors of an image that may pass conf_thresh, 4096 .. min(N, 65536) with
+ * N = y355_num_anchors_total (a head of at most 4096 anchors only takes 4096).  Images with up to 4096 candidates run the
+ * bin-sort / pair-walk / rounds NMS whatever the capacity; above 4096 the handle also launches the large route (radix sort by
+ * (class, score desc, anchor index asc), block-greedy resolve; csrc/nms_large.hip), and every kernel of either route
+ * leaves at once for an image that belongs to the other: no host synchronisation picks the route, the detections are the same
+ * greedy per-class NMS bit for bit.  With the default the handle launches exactly the kernels it launched before the option
+ * existed.  Setting it synchronises the handle's stream, reallocates the head workspace and the engine-owned outputs, and sets
+ * max_det (y355_max_det) again from the configuration: 0 = every candidate, otherwise at most the capacity -- device buffers
+ * handed to y355_forward must be sized by the new y355_max_det.  A forward in which more anchors pass than the capacity holds
+ * drops the excess and raises the flag y355_overflow reads.
+ * Y355_OPT_HEAD_ROUTE (default Y355_HEAD_ROUTE_AUTO): Y355_HEAD_ROUTE_LARGE sends every image through the large route, whatever
+ * its candidate count (tests compare the two routes with it; it also reallocates, like the capacity).
+ * Out-of-range values: Y355_EINVAL.  The NMS diagnostics report an image the large route took as count = its candidates,
+ * nedges = (0, 0). */
+#define Y355_OPT_MAX_CANDIDATES 4
+#define Y355_OPT_HEAD_ROUTE 5
+#define Y355_HEAD_ROUTE_AUTO 0
+#define Y355_HEAD_ROUTE_LARGE 1
 int y355_set_option(y355_engine *h, int option, int value);
+int y355_max_candidates(y355_engine *h);       /* the candidate capacity in force */
+/* heads with more than 4096 anchors per image (e.g. 512 x 512: 5120), or with the large route forced: *overflow = 1 if, in a
+ * forward since the last call, more anchors of an image passed conf_thresh than the candidate capacity holds (the excess was
+ * dropped: raise the threshold or Y355_OPT_MAX_CANDIDATES); synchronous; clears the flag.  Smaller heads: always 0. */
+int y355_overflow(y355_engine *h, int *overflow);
 
 /* replaces load_state_dict of the quantized checkpoint: integer weights as produced by
  * quantize_layers (retune_bias_quantize.py:111-119): q_w[cout][cin][3][3] int8 with value
@@ -315,12 +338,22 @@ int y355_upsample2x_f32(int device_id, const float *in, int batch, int channels,
  * pred[l] = NCHW [B][A*(5+C)][hs[l]][ws[l]] (host), 1 or 2 levels, channel layout [obj x A | cls x A*C | txtytwth x A*4];
  * anchors [nlev][A][2]; wh_mul = the stride for anchors in grid units (yolo_v2), 1 for anchors in pixels (v3 family).
  * Outputs as y355_forward: boxes f32 [B][max_det][4] normalised x1y1x2y2, scores, classes, counts; anchor-index order.
- * Images with more than 4096 anchors (yolo_v3 at 416 x 416: 10 647) are thresholded and compacted on the GPU before the
- * sort; at most 4096 anchors per image may pass conf_thresh (else Y355_EINVAL). */
+ * Images with more than 4096 anchors (yolo_v3 at 416 x 416: 10 647; at most 65 536) are thresholded and compacted on the GPU
+ * before the sort; at most 4096 anchors per image may pass conf_thresh (else Y355_EINVAL; y355_head_f32_ex takes more). */
 int y355_head_f32(int device_id, int nlev, const float *const *pred, const int *hs, const int *ws, const float *strides,
                   const float *anchors, int num_anchors, int num_classes, int in_h, int in_w, float wh_mul,
                   float conf_thresh, float nms_thresh, int batch, int max_det, float *boxes, float *scores,
                   int32_t *cls, int32_t *count);
+/* the same head with the candidate capacity and the route of Y355_OPT_MAX_CANDIDATES / Y355_OPT_HEAD_ROUTE as arguments
+ * (y355_head_f32 = 4096, Y355_HEAD_ROUTE_AUTO, no tap): max_candidates 4096 .. min(N, 65536) with N the anchors per image (4096
+ * for any N); max_det is cut to min(N, max_candidates); more anchors of an image at or above conf_thresh than max_candidates:
+ * Y355_EINVAL, the message names the capacity.  cand_box f32 [B][N][4], cand_score f32 [B][N], cand_cls i32 [B][N] (host; all
+ * three or none): the decode of every anchor in anchor-index order, what both NMS routes read. */
+int y355_head_f32_ex(int device_id, int nlev, const float *const *pred, const int *hs, const int *ws, const float *strides,
+                     const float *anchors, int num_anchors, int num_classes, int in_h, int in_w, float wh_mul,
+                     float conf_thresh, float nms_thresh, int batch, int max_det, int max_candidates, int route,
+                     float *boxes, float *scores, int32_t *cls, int32_t *count, float *cand_box, float *cand_score,
+                     int32_t *cand_cls);
 /* head only: pred int8 [B][A*(5+C)][Hs][Ws] NCHW host -> detections (host), synchronous.
  * Replaces slim_yolo_v2.py:330-358 (decode, score, threshold, per-class NMS). */
 int y355_head_nms(y355_engine *h, const int8_t *pred_q, int batch, int sa_pred,
@@ -342,6 +375,8 @@ int y355_head_nms(y355_engine *h, const int8_t *pred_q, int batch, int sa_pred,
  *   y355_unpack_dets      records -> padded arrays: record r goes to row slot[r] (slot[r] < 0: dropped) */
 typedef struct y355_comm y355_comm;
 #define Y355_COMM_ID_BYTES 128
+/* (the record layout has no limit of its own on max_det: sizes are size_t, one thread per 16 bytes of a record -- max_det above
+ * 4096, as Y355_OPT_MAX_CANDIDATES allows, packs and unpacks like any other; tests/test_head_large.py round-trips 5000) */
 size_t y355_packed_det_bytes(int max_det);
 int y355_comm_unique_id(void *id_out /*[Y355_COMM_ID_BYTES]*/);
 int y355_comm_init(y355_comm **out, int world, int rank, const void *id, int device_id);
@@ -409,7 +444,13 @@ int y355_pipeline_set_act_exponents(y355_pipeline *p, const int32_t *sa);
 int y355_pipeline_set_retune(y355_pipeline *p, const int32_t *retune);
 int y355_pipeline_set_thresholds(y355_pipeline *p, float conf_thresh, float nms_thresh);
 int y355_pipeline_set_normalization(y355_pipeline *p, const float *mean_bgr, const float *std_bgr);
+/* Y355_OPT_MAX_CANDIDATES / Y355_OPT_HEAD_ROUTE also drop the pipeline-owned output buffers (y355_pipeline_max_det may change):
+ * set them while no ticket is out */
 int y355_pipeline_set_option(y355_pipeline *p, int option, int value);
+/* *overflow = 1 if the forward of this ticket dropped candidates beyond the capacity (what y355_overflow tells for a lone
+ * engine; the pipeline moves every forward's flags into its ticket on the handle's stream, so y355_overflow of a pipeline's
+ * handle reads 0).  Waits for that ticket only.  Heads without the flags: 0. */
+int y355_pipeline_ticket_overflow(y355_pipeline *p, long long ticket, int *overflow);
 int y355_pipeline_set_trackers(y355_pipeline *p, const float *scale, const int32_t *first_a);
 int y355_pipeline_get_trackers(y355_pipeline *p, float *scale, int32_t *first_a);
 int y355_pipeline_calibrate(y355_pipeline *p, const float *x_dev, int batch, int freeze, double momentum, int32_t *sa_out,
@@ -502,6 +543,13 @@ int y355_net_set_thresholds(y355_net *h, float conf_thresh, float nms_thresh);
  * q_bf engine's convpx.hip); 0 = the LDS-ring kernels of convr.hip as before.  Same arithmetic up to where the bias enters the fp32
  * accumulation: the two routes agree within 2 bf16 ulps, not bit for bit. */
 #define Y355_NET_OPT_THIN_RESIDENT 2
+/* Y355_NET_OPT_MAX_CANDIDATES (default 4096), Y355_NET_OPT_HEAD_ROUTE (default Y355_HEAD_ROUTE_AUTO): as Y355_OPT_MAX_CANDIDATES /
+ * Y355_OPT_HEAD_ROUTE of the q_bf engine -- the capacity 4096 .. min(y355_net_num_anchors_total, 65536); setting either
+ * synchronises the stream, reallocates the head workspace and sets y355_net_max_det again; y355_net_overflow tells when a
+ * forward dropped candidates beyond the capacity; y355_net_debug_nms reports an image the large route took as count = its
+ * candidates, nedges = (0, 0). */
+#define Y355_NET_OPT_MAX_CANDIDATES 3
+#define Y355_NET_OPT_HEAD_ROUTE 4
 int y355_net_set_option(y355_net *h, int option, int value);
 int y355_net_num_layers(y355_net *h);
 int y355_net_num_tensors(y355_net *h);
@@ -641,13 +689,15 @@ int y355_net_resize_frames(y355_net *h, const y355_frame *frames, int batch, uin
 int y355_net_calibrate_frames(y355_net *h, const y355_frame *frames, int batch, int freeze, double momentum,
                               int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n);
 int y355_net_max_det(y355_net *h);
+int y355_net_max_candidates(y355_net *h);      /* the candidate capacity in force (Y355_NET_OPT_MAX_CANDIDATES) */
 int y355_net_num_anchors_total(y355_net *h);
 int y355_net_sync(y355_net *h);
 /* Diagnostics (no reference counterpart): the last forward's NMS work per image -- count[batch] candidates at or above
  * conf_thresh, nedges[2 * batch] = (suppressing pairs listed, 1 when the list was abandoned for the sorted walk).  Synchronous. */
 int y355_net_debug_nms(y355_net *h, int batch, int32_t *count, int32_t *nedges);
 /* heads with more than 4096 anchors per image (yolo_v3 at 416 x 416): *overflow = 1 if, in a forward since the last call, more
- * than 4096 anchors of an image passed conf_thresh (the excess was dropped: raise the threshold); synchronous; clears the flag */
+ * anchors of an image passed conf_thresh than the candidate capacity holds (4096 unless Y355_NET_OPT_MAX_CANDIDATES raised it; the
+ * excess was dropped: raise the threshold or the capacity); synchronous; clears the flag */
 int y355_net_overflow(y355_net *h, int *overflow);
 /* debug: the kernel the convolution of weight slot idx ran on in the last forward that reached it (0: it has not run), for
  * bf16 and int8 nets: one family ... */

@@ -237,6 +237,41 @@ static int dmalloc(y355_engine *h, void **p, size_t bytes, bool zero) {
     if (zero) HIPCHK(hipMemset(*p, 0, bytes ? bytes : 16));
     return 0;
 }
+static void dfree(y355_engine *h, void *q) {
+    (void)hipFree(q);
+    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), q), h->allocs.end());
+}
+// per-image cap of the returned detections: what the configuration asked for, within the candidates an image can have
+static void set_max_det(y355_engine *h) {
+    const int ncand = std::min(h->N, h->ws.cap ? h->ws.cap : Y355_NMS_CAP);
+    h->max_det = (h->cfg.max_det <= 0 || h->cfg.max_det > ncand) ? ncand : h->cfg.max_det;
+}
+// the head workspace beyond the small route's arrays for candidate capacity `cap` and `route` (y355_head_ws_large), and the
+// engine-owned outputs of the host calls, sized by max_det
+static int head_ws_large(y355_engine *h, int cap, int route) {
+    // the new outputs first, then the workspace (all or nothing): a failure leaves the handle as it was
+    const int ncand = std::min(h->N, cap);
+    const int md = (h->cfg.max_det <= 0 || h->cfg.max_det > ncand) ? ncand : h->cfg.max_det;
+    const size_t B = (size_t)h->cfg.max_batch;
+    float *nb = nullptr, *ns = nullptr;
+    int *nc = nullptr;
+    int rc = dmalloc(h, (void **)&nb, sizeof(float) * 4 * md * B, false);
+    if (!rc) rc = dmalloc(h, (void **)&ns, sizeof(float) * md * B, false);
+    if (!rc) rc = dmalloc(h, (void **)&nc, sizeof(int) * md * B, false);
+    if (!rc)
+        rc = y355_head_ws_large(
+            h->ws, h->N, h->cfg.max_batch, cap, route, [h](void **p, size_t bytes, bool zero) { return dmalloc(h, p, bytes, zero); },
+            [h](void *q) { dfree(h, q); });
+    void *drop[] = {rc ? (void *)nb : (void *)h->o_box, rc ? (void *)ns : (void *)h->o_score, rc ? (void *)nc : (void *)h->o_cls};
+    for (void *q : drop)
+        if (q) dfree(h, q);
+    if (rc) return rc;
+    h->o_box = nb;
+    h->o_score = ns;
+    h->o_cls = nc;
+    set_max_det(h);
+    return 0;
+}
 
 extern "C" void y355_destroy(y355_engine *h) {
     if (!h) return;
@@ -261,7 +296,7 @@ extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
     const int predc = cfg->num_anchors * (5 + cfg->num_classes);
     if (predc > 256) return fail(Y355_EINVAL, "A*(5+C) > 256 not supported");
     const int Hs = cfg->height / 16, Ws = cfg->width / 16, N = Hs * Ws * cfg->num_anchors;
-    if (N > Y355_NMS_CAP) return fail(Y355_EINVAL, "more than 4096 anchors per image not supported");
+    if (N > Y355_NMS_MAX_CAP) return fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
     HIPCHK(hipSetDevice(cfg->device_id));
     if (int e = prepare_kernels()) return e;
     y355_engine *h = new y355_engine();
@@ -269,7 +304,7 @@ extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
     h->Hs = Hs;
     h->Ws = Ws;
     h->N = N;
-    h->max_det = (cfg->max_det <= 0 || cfg->max_det > N) ? N : cfg->max_det;
+    set_max_det(h);
     for (int i = 0; i < 11; ++i) { h->sa[i] = 0; h->sa_set[i] = false; }
     for (int i = 0; i < 10; ++i) h->retune[i] = kRetuneDefault[i];
     if (!cfg->own_stream) {
@@ -338,9 +373,7 @@ extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
     if (!rc) rc = dmalloc(h, (void **)&h->cand_box, sizeof(float) * 4 * N * B, false);
     if (!rc) rc = dmalloc(h, (void **)&h->cand_score, sizeof(float) * N * B, false);
     if (!rc) rc = dmalloc(h, (void **)&h->cand_cls, sizeof(int) * N * B, false);
-    if (!rc) rc = dmalloc(h, (void **)&h->o_box, sizeof(float) * 4 * h->max_det * B, false);
-    if (!rc) rc = dmalloc(h, (void **)&h->o_score, sizeof(float) * h->max_det * B, false);
-    if (!rc) rc = dmalloc(h, (void **)&h->o_cls, sizeof(int) * h->max_det * B, false);
+    if (!rc) rc = head_ws_large(h, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO);       // heads of more than 4096 anchors: the raw decode; the outputs
     if (!rc) rc = dmalloc(h, (void **)&h->o_count, sizeof(int) * B, true);
     if (!rc) {
         bool ok = true;
@@ -374,9 +407,47 @@ extern "C" int y355_set_option(y355_engine *h, int option, int value) {
         if (value < 0 || value > 4096) return fail(Y355_EINVAL, "workgroups per launch out of range");
         h->ring_wgs = value;
         return 0;
+    case Y355_OPT_MAX_CANDIDATES:
+    case Y355_OPT_HEAD_ROUTE: {
+        const bool is_cap = option == Y355_OPT_MAX_CANDIDATES;
+        if (is_cap && value != Y355_NMS_CAP && (value < Y355_NMS_CAP || value > h->N))
+            return fail(Y355_EINVAL, "Y355_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)");
+        if (!is_cap && value != Y355_HEAD_ROUTE_AUTO && value != Y355_HEAD_ROUTE_LARGE)
+            return fail(Y355_EINVAL, "Y355_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)");
+        HIPCHK(hipSetDevice(h->cfg.device_id));
+        HIPCHK(hipStreamSynchronize(h->stream));         // nothing in flight reads the arrays that go
+        const int cap = is_cap ? value : (h->ws.cap ? h->ws.cap : Y355_NMS_CAP), route = is_cap ? h->ws.route : value;
+        if (head_ws_large(h, cap, route)) return fail(Y355_EHIP, "device allocation failed");
+        return 0;
+    }
     default: return fail(Y355_EINVAL, "unknown option");
     }
 }
+
+// heads with more than 4096 anchors per image, or with the large route forced: *overflow = 1 if, in a forward since the last call,
+// more anchors of an image passed conf_thresh than the candidate capacity holds (the excess was dropped); synchronous; clears the flag
+extern "C" int y355_overflow(y355_engine *h, int *overflow) {
+    if (!h || !overflow) return fail(Y355_EINVAL, "null argument");
+    *overflow = 0;
+    if (!h->ws.ovf) return 0;
+    HIPCHK(hipSetDevice(h->cfg.device_id));
+    HIPCHK(hipStreamSynchronize(h->stream));
+    std::vector<int> v(h->cfg.max_batch, 0);
+    HIPCHK(hipMemcpy(v.data(), h->ws.ovf, sizeof(int) * v.size(), hipMemcpyDeviceToHost));
+    for (int x : v) *overflow |= x != 0;
+    if (*overflow) HIPCHK(hipMemset(h->ws.ovf, 0, sizeof(int) * v.size()));
+    return 0;
+}
+// pipeline.hip: the flags of the forwards enqueued so far move to dst_dev [max_batch] on the handle's stream and are cleared
+// behind the copy, so a ticket carries the overflow of its own forward (only for handles that have the flags)
+bool y355_has_overflow_flags(y355_engine *h) { return h->ws.ovf != nullptr; }
+int y355_overflow_take(y355_engine *h, int *dst_dev) {
+    const size_t bytes = sizeof(int) * (size_t)h->cfg.max_batch;
+    HIPCHK(hipMemcpyAsync(dst_dev, h->ws.ovf, bytes, hipMemcpyDeviceToDevice, h->stream));
+    HIPCHK(hipMemsetAsync(h->ws.ovf, 0, bytes, h->stream));
+    return 0;
+}
+extern "C" int y355_max_candidates(y355_engine *h) { return h ? (h->ws.cap ? h->ws.cap : Y355_NMS_CAP) : Y355_EINVAL; }
 
 extern "C" int y355_set_thresholds(y355_engine *h, float conf, float nms) {
     if (!h) return fail(Y355_EINVAL, "null engine");
@@ -756,9 +827,16 @@ static HeadParams head_params(y355_engine *h, int sa_pred, float *ob, float *os,
     // int8 logits keep exp(tw) in a narrow range: the anchor is a good size class (measured: pairs 52 us
     // vs 80 us with area octaves on the benchmark batch)
     p.group_by_area = 0;
-    p.pairs_wgs = h->ring_wgs > 0 ? Y355_TPUT_PAIRS_WGS : 0;    // throughput mode (Y355_OPT_RING_WORKGROUPS set): the pair walk holds one CU per image
     p.Hb = h->Hs;
     p.Wb = h->Ws;
+    if (h->N > Y355_NMS_CAP) {
+        // the candidates arrive thresholded and compacted: their position says nothing about the anchor, and one bin per cell
+        // and anchor (N bins) would not fit the sort's 4096-entry tables -- area octaves on a grid of at most 16 x 16 do
+        p.group_by_area = 1;
+        p.Hb = std::min(16, h->Hs);
+        p.Wb = std::min(16, h->Ws);
+    }
+    p.pairs_wgs = h->ring_wgs > 0 ? Y355_TPUT_PAIRS_WGS : 0;    // throughput mode (Y355_OPT_RING_WORKGROUPS set): the pair walk holds one CU per image
     p.in_w = (float)h->cfg.width;
     p.in_h = (float)h->cfg.height;
     p.conf_thresh = h->cfg.conf_thresh;

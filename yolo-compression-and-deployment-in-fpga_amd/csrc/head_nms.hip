@@ -26,6 +26,7 @@
 // The pruning is exact: a pair is skipped only when real IoU < 0.999*thr and the union is not
 // degenerate, where the fp32 formula of the reference cannot exceed thr.
 #include "y355_common.h"
+#include "head_nms.h"
 #include <algorithm>
 #include <cstdlib>
 
@@ -38,33 +39,6 @@
                                    // pairs_kernel stops writing an image's list beyond that and raises the overflow flag)
 #define WG_EDGE_CAP 8192         // edges one pairs workgroup buffers in LDS
 
-struct HeadWork {
-    float *cbox;          // [B][CAP][4]  compacted candidates, (anchor, bin) order
-    float *cscore;        // [B][CAP]
-    int *ccls;            // [B][CAP]
-    int *corig;           // [B][CAP]     anchor index n = cell*A + a of compact position p
-    int *count;           // [B]          candidates per image
-    unsigned int *edges;  // [B][EDGE_CAP] suppressing pairs (p << 12) | q with p < q (compact positions)
-    int *nedges;          // [B][2]        number of edges; overflow flag (a list did not fit)
-    int *binstart;        // [B][CAP+8]   first compact position of bin (a*HW + by*Ws + bx)
-    float *astat;         // [B][MAXG][4] per candidate group: wmax, hmax, amin, amax (clamped boxes)
-    int *tiny;            // [B][CAP]     positions of candidates with area < AREA_MIN
-    int *ntiny;           // [B]
-    int *ctype;           // [B][CAP]     candidate group of compact position p
-    float *dbox;          // [B][CAP][4]  decode of every anchor, (level, anchor, cell) order
-    float *dscore;        // [B][CAP]
-    int *dcls;            // [B][CAP]
-    // heads with more than CAP anchors per image (three-level models at 416 x 416): decode_kernel writes the raw arrays
-    // (pitch rstride), compact_kernel keeps the anchors at or above conf_thresh in anchor-index order in dbox / dscore /
-    // dcls (at most CAP of them; more sets ovf[b]); the sort then sees an ordinary <= CAP-anchor image
-    float *rbox;          // [B][rstride][4] or null (= small head: decode writes dbox directly)
-    float *rscore;        // [B][rstride]
-    int *rcls;            // [B][rstride]
-    int *rcount;          // [B] anchors kept by the compaction
-    int *ovf;             // [B] 1: more than CAP anchors passed the threshold (the rest were dropped)
-    int rstride;
-    unsigned long long *stamps;   // diagnostics or null
-};
 
 // diagnostics (Y355_NMS_STAMPS=1): s_memtime at the phase boundaries of the first 256 workgroups
 #define NSTAMP(k, wg, slot)                                                                        \
@@ -417,15 +391,6 @@ __global__ __launch_bounds__(1024) void head_kernel(const HeadParams p, const He
     NSTAMP(0, blockIdx.x, 7);
 }
 
-// ---- the reference's suppression test (slim_yolo_v2.py:159-171), same class assumed
-__device__ __forceinline__ bool suppresses_exact(const float4 a, float area_a, const float4 c, float area_c, float thr) {
-    const float xx1 = fmaxf(a.x, c.x), yy1 = fmaxf(a.y, c.y);
-    const float xx2 = fminf(a.z, c.z), yy2 = fminf(a.w, c.w);
-    const float w = fmaxf(1e-28f, xx2 - xx1), h = fmaxf(1e-28f, yy2 - yy1);
-    const float inter = w * h;
-    const float ovr = inter / (area_a + area_c - inter);
-    return !(ovr <= thr);
-}
 // same predicate; the correctly rounded division is only issued when the reciprocal estimate
 // lands within 8 ulp-ish of the threshold (or the union is degenerate)
 __device__ __forceinline__ bool suppresses(const float4 a, float area_a, const float4 c, float area_c, float thr,
@@ -1073,11 +1038,23 @@ void y355_launch_head_nms(const HeadParams &p_in, int batch, const y355_head_ws 
     wk.dbox = (float *)ws.dbox;
     wk.dscore = (float *)ws.dscore;
     wk.dcls = (int *)ws.dcls;
+    bool big = false;
     {
         int n = 0;
         for (int l = 0; l < p.nlev; ++l) n += p.lev[l].Hs * p.lev[l].Ws * p.A;
-        const bool large = n > NMS_CAP;                     // callers allocate the raw arrays for such heads
+        // callers allocate the raw arrays for heads of more than CAP anchors (and for any head whose large route is forced)
+        const bool large = n > NMS_CAP || ws.route == 1;
+        big = ws.cap > NMS_CAP || ws.route == 1;          // the large route's kernels run beside these (nms_large.hip)
         wk.rbox = large ? (float *)ws.rbox : nullptr;
+        wk.lbox = (float *)ws.lbox;
+        wk.lscore = (float *)ws.lscore;
+        wk.lcls = (int *)ws.lcls;
+        wk.lcount = (int *)ws.lcount;
+        wk.lsort = (uint2 *)ws.lsort;
+        wk.lkbox = (float *)ws.lkbox;
+        wk.lkeep = (unsigned char *)ws.lkeep;
+        wk.lcap = ws.cap;
+        wk.lforce = ws.route == 1;
         wk.rscore = (float *)ws.rscore;
         wk.rcls = (int *)ws.rcls;
         wk.rcount = (int *)ws.rcount;
@@ -1094,7 +1071,8 @@ void y355_launch_head_nms(const HeadParams &p_in, int batch, const y355_head_ws 
         int nblk = 0;
         for (int l = 0; l < p.nlev; ++l) nblk += (p.lev[l].Hs * p.lev[l].Ws + ncell - 1) / ncell;
         Y355_LAUNCH(decode_kernel, dim3(nblk, batch), dim3(DEC_THREADS), (size_t)ncell * pitch, s, k0[0], k0[1], p, wk, pitch, ncell);
-        if (large) hipLaunchKernelGGL(compact_kernel, dim3(batch), dim3(1024), 0, s, p, wk);
+        if (large && big) y355_launch_compact_large(p, wk, batch, s);
+        else if (large) hipLaunchKernelGGL(compact_kernel, dim3(batch), dim3(1024), 0, s, p, wk);
     }
     Y355_LAUNCH(head_kernel, dim3(batch), dim3(1024), 0, s, k1[0], k1[1], p, wk);
     if (mid) (void)hipEventRecord(mid, s);
@@ -1103,4 +1081,7 @@ void y355_launch_head_nms(const HeadParams &p_in, int batch, const y355_head_ws 
     else
         Y355_LAUNCH(pairs_kernel<false>, dim3(p.pairs_wgs > 0 ? p.pairs_wgs : Y355_PAIRS_G, batch), dim3(1024), PAIRS_LDS, s, k2[0], k2[1], p, wk, p.nms_thresh);
     Y355_LAUNCH(resolve_emit_kernel, dim3(batch), dim3(1024), 0, s, k3[0], k3[1], p, wk, p.nms_thresh);
+    // images the compaction handed to the large route: the kernels above saw them without candidates (rcount = 0) and wrote
+    // count 0; these write their outputs, and return at once for every other image
+    if (big) y355_launch_nms_large(p, wk, batch, s);
 }

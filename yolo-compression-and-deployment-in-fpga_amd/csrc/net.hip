@@ -135,6 +135,21 @@ struct NetInput {
 
 static int in_kbytes(const y355_net *h, const OpDef &o);
 
+static int nmalloc(y355_net *h, void **p, size_t bytes, bool zero);
+// per-image cap of the returned detections: what the configuration asked for, within the candidates an image can have
+static void set_max_det(y355_net *h) {
+    const int ncand = std::min(h->N, h->ws.cap ? h->ws.cap : Y355_NMS_CAP);
+    h->max_det = (h->cfg.max_det <= 0 || h->cfg.max_det > ncand) ? ncand : h->cfg.max_det;
+}
+// the head workspace beyond the small route's arrays, for candidate capacity `cap` and `route` (y355_head_ws_large)
+static int head_ws_large(y355_net *h, int cap, int route) {
+    return y355_head_ws_large(
+        h->ws, h->N, h->cfg.max_batch, cap, route, [h](void **p, size_t bytes, bool zero) { return nmalloc(h, p, bytes, zero); },
+        [h](void *q) {
+            (void)hipFree(q);
+            h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), q), h->allocs.end());
+        });
+}
 static int nmalloc(y355_net *h, void **p, size_t bytes, bool zero) {
     HIPCHK(hipMalloc(p, bytes ? bytes : 16));
     h->allocs.push_back(*p);
@@ -172,9 +187,9 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     const int Hb = cfg->height / (int)A.stride[0], Wb = cfg->width / (int)A.stride[0];
     (void)Hb;
     (void)Wb;
-    if (N > Y355_NMS_CAP && A.nlev < 3)
-        return y355_fail(Y355_EINVAL, "more than 4096 anchors / sort bins per image not supported");
-    if (N > 16 * Y355_NMS_CAP) return y355_fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
+    // (the candidate sort of these heads bins by area octave or class on a grid of at most 16 x 16: 16 x 256 bins fit its
+    // 4096-entry tables whatever the number of anchors; heads of more than 4096 anchors are thresholded and compacted first)
+    if (N > Y355_NMS_MAX_CAP) return y355_fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
     HIPCHK(hipSetDevice(cfg->device_id));
     if (int e = y355_prepare_kernels()) return e;
     if (y355_prepare_convr(cfg->device_id)) return y355_fail(Y355_EHIP, "hipFuncSetAttribute(convr) / sink allocation failed");
@@ -187,8 +202,7 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     h->predc = predc;
     h->sa.assign(A.ntensors, 0);
     h->N = N;
-    const int ncand = N > Y355_NMS_CAP ? Y355_NMS_CAP : N;     // larger heads are thresholded and compacted first
-    h->max_det = (cfg->max_det <= 0 || cfg->max_det > ncand) ? ncand : cfg->max_det;
+    set_max_det(h);
     if (!cfg->own_stream) h->stream = (hipStream_t)cfg->stream;
     else {
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -307,14 +321,7 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     if (!rc) rc = nmalloc(h, &h->ws.dscore, sizeof(float) * cap * B, true);
     if (!rc) rc = nmalloc(h, &h->ws.dcls, sizeof(int) * cap * B, true);
     if (!rc) rc = nmalloc(h, &h->ws.ctype, sizeof(int) * cap * B, true);          // candidate groups
-    if (N > Y355_NMS_CAP) {
-        h->ws.rstride = (N + 3) / 4 * 4;
-        if (!rc) rc = nmalloc(h, &h->ws.rbox, sizeof(float) * 4 * (size_t)h->ws.rstride * B, true);
-        if (!rc) rc = nmalloc(h, &h->ws.rscore, sizeof(float) * (size_t)h->ws.rstride * B, true);
-        if (!rc) rc = nmalloc(h, &h->ws.rcls, sizeof(int) * (size_t)h->ws.rstride * B, true);
-        if (!rc) rc = nmalloc(h, &h->ws.rcount, sizeof(int) * B, true);
-        if (!rc) rc = nmalloc(h, &h->ws.ovf, sizeof(int) * B, true);
-    }
+    if (!rc) rc = head_ws_large(h, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO);
     if (!rc) rc = nmalloc(h, (void **)&h->cand_box, sizeof(float) * 4 * N * B, false);
     if (!rc) rc = nmalloc(h, (void **)&h->cand_score, sizeof(float) * N * B, false);
     if (!rc) rc = nmalloc(h, (void **)&h->cand_cls, sizeof(int) * N * B, false);
@@ -335,6 +342,19 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
 
 extern "C" int y355_net_set_option(y355_net *h, int option, int value) {
     if (!h) return y355_fail(Y355_EINVAL, "null net");
+    if (option == Y355_NET_OPT_MAX_CANDIDATES || option == Y355_NET_OPT_HEAD_ROUTE) {
+        const bool is_cap = option == Y355_NET_OPT_MAX_CANDIDATES;
+        if (is_cap && value != Y355_NMS_CAP && (value < Y355_NMS_CAP || value > h->N))
+            return y355_fail(Y355_EINVAL, "Y355_NET_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)");
+        if (!is_cap && value != Y355_HEAD_ROUTE_AUTO && value != Y355_HEAD_ROUTE_LARGE)
+            return y355_fail(Y355_EINVAL, "Y355_NET_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)");
+        HIPCHK(hipSetDevice(h->cfg.device_id));
+        HIPCHK(hipStreamSynchronize(h->stream));         // nothing in flight reads the arrays that go
+        const int cap = is_cap ? value : (h->ws.cap ? h->ws.cap : Y355_NMS_CAP), route = is_cap ? h->ws.route : value;
+        if (head_ws_large(h, cap, route)) return y355_fail(Y355_EHIP, "device allocation failed");
+        set_max_det(h);
+        return 0;
+    }
     if (option == Y355_NET_OPT_WORKGROUPS) {
         if (value < 0 || value > 256) return y355_fail(Y355_EINVAL, "workgroups per launch: 0 .. 256");
         h->tput_wgs = value;
@@ -357,6 +377,7 @@ extern "C" int y355_net_set_thresholds(y355_net *h, float conf, float nms) {
 
 extern "C" int y355_net_num_layers(y355_net *h) { return h ? h->arch->nlayers : Y355_EINVAL; }
 extern "C" int y355_net_num_tensors(y355_net *h) { return h ? h->arch->ntensors : Y355_EINVAL; }
+extern "C" int y355_net_max_candidates(y355_net *h) { return h ? (h->ws.cap ? h->ws.cap : Y355_NMS_CAP) : Y355_EINVAL; }
 extern "C" int y355_net_max_det(y355_net *h) { return h ? h->max_det : Y355_EINVAL; }
 extern "C" int y355_net_num_anchors_total(y355_net *h) { return h ? h->N : Y355_EINVAL; }
 
@@ -1565,10 +1586,11 @@ extern "C" int y355_net_calibrate_frames(y355_net *h, const y355_frame *frames, 
 // models/yolo_v3.py:207-262 (anchors in pixels: wh_mul = 1): decode, sigmoid(obj) * softmax(cls), threshold,
 // per-class NMS, survivors in anchor-index order.  Host pointers, synchronous; pred[l] is NCHW
 // [B][A*(5+C)][hs[l]][ws[l]] like the reference's tensors.
-extern "C" int y355_head_f32(int device_id, int nlev, const float *const *pred, const int *hs, const int *ws, const float *strides,
-                             const float *anchors, int num_anchors, int num_classes, int in_h, int in_w, float wh_mul,
-                             float conf_thresh, float nms_thresh, int batch, int max_det, float *boxes, float *scores,
-                             int32_t *cls, int32_t *count) {
+extern "C" int y355_head_f32_ex(int device_id, int nlev, const float *const *pred, const int *hs, const int *ws, const float *strides,
+                                const float *anchors, int num_anchors, int num_classes, int in_h, int in_w, float wh_mul,
+                                float conf_thresh, float nms_thresh, int batch, int max_det, int max_candidates, int route,
+                                float *boxes, float *scores, int32_t *cls, int32_t *count, float *cand_box, float *cand_score,
+                                int32_t *cand_cls) {
     if (!pred || !hs || !ws || !strides || !anchors || !boxes || !scores || !cls || !count) return y355_fail(Y355_EINVAL, "null argument");
     if (nlev < 1 || nlev > 3) return y355_fail(Y355_EINVAL, "1 to 3 prediction levels");
     if (num_anchors < 1 || num_anchors * nlev > Y355_HEAD_MAXA || num_classes < 1 || batch < 1 || max_det < 1)
@@ -1580,9 +1602,15 @@ extern "C" int y355_head_f32(int device_id, int nlev, const float *const *pred, 
         if (!pred[l] || hs[l] < 1 || ws[l] < 1) return y355_fail(Y355_EINVAL, "bad prediction level");
         N += hs[l] * ws[l] * num_anchors;
     }
-    if (N > 16 * Y355_NMS_CAP) return y355_fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
-    const bool large = N > Y355_NMS_CAP;          // threshold-then-compact in front of the sort (head_nms.hip)
-    if (max_det > (large ? Y355_NMS_CAP : N)) max_det = large ? Y355_NMS_CAP : N;
+    if (N > Y355_NMS_MAX_CAP) return y355_fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
+    if (route != Y355_HEAD_ROUTE_AUTO && route != Y355_HEAD_ROUTE_LARGE) return y355_fail(Y355_EINVAL, "head route: 0 (auto) or 1 (large)");
+    if (max_candidates != Y355_NMS_CAP && (max_candidates < Y355_NMS_CAP || max_candidates > N))
+        return y355_fail(Y355_EINVAL, "max_candidates: 4096 .. min(anchors per image, 65536)");
+    if ((cand_box || cand_score || cand_cls) && !(cand_box && cand_score && cand_cls))
+        return y355_fail(Y355_EINVAL, "the candidate tap takes all three arrays or none");
+    const bool large = N > Y355_NMS_CAP || route == Y355_HEAD_ROUTE_LARGE;          // threshold-then-compact in front of the sort (head_nms.hip)
+    const int ncand = std::min(N, max_candidates);
+    if (max_det > ncand) max_det = ncand;
     HIPCHK(hipSetDevice(device_id));
     if (int e = y355_prepare_kernels()) return e;
     std::vector<void *> bufs;
@@ -1628,13 +1656,13 @@ extern "C" int y355_head_f32(int device_id, int nlev, const float *const *pred, 
     if (!rc) rc = alloc(&w.dscore, sizeof(float) * cap * B, true);
     if (!rc) rc = alloc(&w.dcls, sizeof(int) * cap * B, true);
     if (!rc) rc = alloc(&w.ctype, sizeof(int) * cap * B, true);
-    if (large) {
-        w.rstride = (N + 3) / 4 * 4;
-        if (!rc) rc = alloc(&w.rbox, sizeof(float) * 4 * (size_t)w.rstride * B, true);
-        if (!rc) rc = alloc(&w.rscore, sizeof(float) * (size_t)w.rstride * B, true);
-        if (!rc) rc = alloc(&w.rcls, sizeof(int) * (size_t)w.rstride * B, true);
-        if (!rc) rc = alloc(&w.rcount, sizeof(int) * B, true);
-        if (!rc) rc = alloc(&w.ovf, sizeof(int) * B, true);
+    if (!rc) rc = y355_head_ws_large(w, N, B, max_candidates, route, alloc, [](void *) {});
+    float *d_cbox = nullptr, *d_cscore = nullptr;
+    int *d_ccls = nullptr;
+    if (cand_box) {
+        if (!rc) rc = alloc((void **)&d_cbox, sizeof(float) * 4 * (size_t)N * B, false);
+        if (!rc) rc = alloc((void **)&d_cscore, sizeof(float) * (size_t)N * B, false);
+        if (!rc) rc = alloc((void **)&d_ccls, sizeof(int) * (size_t)N * B, false);
     }
     if (!rc) rc = alloc((void **)&d_box, sizeof(float) * 4 * (size_t)max_det * B, true);
     if (!rc) rc = alloc((void **)&d_score, sizeof(float) * (size_t)max_det * B, true);
@@ -1669,6 +1697,9 @@ extern "C" int y355_head_f32(int device_id, int nlev, const float *const *pred, 
     p.out_score = d_score;
     p.out_cls = d_cls;
     p.out_count = d_count;
+    p.cand_box = d_cbox;
+    p.cand_score = d_cscore;
+    p.cand_cls = d_ccls;
     y355_launch_head_nms(p, B, w, 0, nullptr);
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -1676,6 +1707,11 @@ extern "C" int y355_head_f32(int device_id, int nlev, const float *const *pred, 
     if (e == hipSuccess) e = hipMemcpy(scores, d_score, sizeof(float) * (size_t)max_det * B, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(cls, d_cls, sizeof(int) * (size_t)max_det * B, hipMemcpyDeviceToHost);
     if (e == hipSuccess) e = hipMemcpy(count, d_count, sizeof(int) * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && cand_box) {
+        e = hipMemcpy(cand_box, d_cbox, sizeof(float) * 4 * (size_t)N * B, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(cand_score, d_cscore, sizeof(float) * (size_t)N * B, hipMemcpyDeviceToHost);
+        if (e == hipSuccess) e = hipMemcpy(cand_cls, d_ccls, sizeof(int) * (size_t)N * B, hipMemcpyDeviceToHost);
+    }
     bool overflow = false;
     if (e == hipSuccess && large) {
         std::vector<int> ovf(B, 0);
@@ -1683,7 +1719,16 @@ extern "C" int y355_head_f32(int device_id, int nlev, const float *const *pred, 
         for (int v : ovf) overflow |= v != 0;
     }
     release();
-    if (overflow) return y355_fail(Y355_EINVAL, "more than 4096 anchors of an image pass conf_thresh: raise the threshold");
+    if (overflow) return y355_fail(Y355_EINVAL, y355_head_overflow_message(max_candidates));
     if (e != hipSuccess) return y355_fail(Y355_EHIP, std::string("head: ") + hipGetErrorString(e));
     return 0;
+}
+
+extern "C" int y355_head_f32(int device_id, int nlev, const float *const *pred, const int *hs, const int *ws, const float *strides,
+                             const float *anchors, int num_anchors, int num_classes, int in_h, int in_w, float wh_mul,
+                             float conf_thresh, float nms_thresh, int batch, int max_det, float *boxes, float *scores,
+                             int32_t *cls, int32_t *count) {
+    return y355_head_f32_ex(device_id, nlev, pred, hs, ws, strides, anchors, num_anchors, num_classes, in_h, in_w, wh_mul, conf_thresh,
+                            nms_thresh, batch, max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, boxes, scores, cls, count, nullptr, nullptr,
+                            nullptr);
 }

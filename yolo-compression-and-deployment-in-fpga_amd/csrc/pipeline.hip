@@ -17,6 +17,8 @@
 #include <string>
 #include <vector>
 
+bool y355_has_overflow_flags(y355_engine *h);              // engine.hip
+int y355_overflow_take(y355_engine *h, int *dst_dev);
 int y355_fail(int code, const std::string &msg);     // engine.hip: sets the message y355_last_error() returns
 int y355_frames_prepare(y355_engine *h, const y355_frame *frames, int batch);  // engine.hip: all that can fail in y355_forward_frames
 
@@ -32,6 +34,8 @@ int pfail(int code, const std::string &msg) { return y355_fail(code, msg); }
 struct Slot {
     float *boxes = nullptr, *scores = nullptr;      // pipeline-owned outputs of the ticket in this slot (allocated on first use)
     int32_t *cls = nullptr, *count = nullptr;
+    int32_t *ovf = nullptr;                          // [max_batch] overflow flags of the ticket's forward (heads that have them)
+    bool has_ovf = false;
     // what the ticket's forward wrote to (the caller's buffers or the ones above)
     float *o_boxes = nullptr, *o_scores = nullptr;
     int32_t *o_cls = nullptr, *o_count = nullptr;
@@ -61,6 +65,7 @@ extern "C" void y355_pipeline_destroy(y355_pipeline *p) {
         if (e) (void)y355_sync(e);
     for (auto &s : p->slots) {
         (void)hipFree(s.boxes); (void)hipFree(s.scores); (void)hipFree(s.cls); (void)hipFree(s.count);
+        (void)hipFree(s.ovf);
         if (s.done) (void)hipEventDestroy(s.done);
         if (s.released) (void)hipEventDestroy(s.released);
     }
@@ -150,6 +155,21 @@ extern "C" int y355_pipeline_set_normalization(y355_pipeline *p, const float *me
 }
 extern "C" int y355_pipeline_set_option(y355_pipeline *p, int option, int value) {
     if (p && option == Y355_OPT_RING_WORKGROUPS) p->ring_wgs = value;
+    if (p && (option == Y355_OPT_MAX_CANDIDATES || option == Y355_OPT_HEAD_ROUTE)) {
+        // every handle synchronises its stream and reallocates its head workspace; max_det may change with the capacity, so the
+        // pipeline-owned outputs are dropped (allocated again on first use): tickets still out are void
+        for (auto *e : p->eng)
+            if (int rc = y355_set_option(e, option, value)) return rc;
+        PHIPCHK(hipSetDevice(p->cfg.device_id));
+        PHIPCHK(hipDeviceSynchronize());
+        for (auto &s : p->slots) {
+            (void)hipFree(s.boxes); (void)hipFree(s.scores); (void)hipFree(s.cls); (void)hipFree(s.count);
+            s.boxes = s.scores = nullptr;
+            s.cls = s.count = nullptr;
+        }
+        p->max_det = y355_max_det(p->eng[0]);
+        return 0;
+    }
     FOR_ALL(y355_set_option(e, option, value));
 }
 
@@ -220,6 +240,11 @@ static int submit_common(y355_pipeline *p, const void *in_dev, InputKind kind, i
                    : kind == IN_U8 ? y355_forward_u8(e, (const uint8_t *)in_dev, batch, ef, boxes_dev, scores_dev, cls_dev, count_dev)
                                    : y355_forward(e, (const float *)in_dev, batch, ef, boxes_dev, scores_dev, cls_dev, count_dev);
     if (rc) return rc;
+    s.has_ovf = y355_has_overflow_flags(e);           // heads of more than 4096 anchors, or with the large route forced
+    if (s.has_ovf) {
+        if (!s.ovf) PHIPCHK(hipMalloc((void **)&s.ovf, sizeof(int32_t) * (size_t)p->cfg.max_batch));
+        if (int rc2 = y355_overflow_take(e, s.ovf)) return rc2;      // on the handle's stream, behind the forward: no host wait
+    }
     PHIPCHK(hipEventRecord(s.done, es));
     s.o_boxes = boxes_dev; s.o_scores = scores_dev; s.o_cls = cls_dev; s.o_count = count_dev;
     s.ticket = t;
@@ -309,6 +334,24 @@ extern "C" int y355_pipeline_fetch(y355_pipeline *p, long long ticket, float *bo
     PHIPCHK(hipMemcpyAsync(cls, s->o_cls, sizeof(int32_t) * md * B, hipMemcpyDeviceToHost, es));
     PHIPCHK(hipMemcpyAsync(count, s->o_count, sizeof(int32_t) * B, hipMemcpyDeviceToHost, es));
     PHIPCHK(hipStreamSynchronize(es));
+    return 0;
+}
+
+// *overflow = 1 if the ticket's own forward dropped candidates beyond the capacity (y355_overflow of the q_bf engine, recorded per
+// ticket on the handle's stream); waits for that ticket only
+extern "C" int y355_pipeline_ticket_overflow(y355_pipeline *p, long long ticket, int *overflow) {
+    Slot *s = nullptr;
+    if (int rc = find_slot(p, ticket, &s)) return rc;
+    if (!overflow) return pfail(Y355_EINVAL, "null argument");
+    *overflow = 0;
+    if (!s->has_ovf) return 0;
+    PHIPCHK(hipSetDevice(p->cfg.device_id));
+    hipStream_t es = p->copy_stream;
+    PHIPCHK(hipStreamWaitEvent(es, s->done, 0));
+    std::vector<int32_t> v((size_t)p->cfg.max_batch, 0);
+    PHIPCHK(hipMemcpyAsync(v.data(), s->ovf, sizeof(int32_t) * v.size(), hipMemcpyDeviceToHost, es));
+    PHIPCHK(hipStreamSynchronize(es));
+    for (int i = 0; i < s->batch; ++i) *overflow |= v[(size_t)i] != 0;
     return 0;
 }
 

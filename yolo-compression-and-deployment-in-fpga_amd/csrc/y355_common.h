@@ -2,6 +2,8 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <functional>
+#include <string>
 
 #include <hip/hip_ext.h>
 
@@ -366,7 +368,24 @@ struct HeadParams {
 // (raw decode, rstride >= anchors per image), rcount i32, ovf i32 (more than CAP anchors passed conf_thresh: zero it before
 // a forward, check it after).
 struct y355_head_ws { void *cbox, *cscore, *ccls, *corig, *count, *edges, *nedges, *binstart, *astat, *tiny, *ntiny, *ctype, *dbox, *dscore, *dcls;
-                      void *rbox = nullptr, *rscore = nullptr, *rcls = nullptr, *rcount = nullptr, *ovf = nullptr; int rstride = 0; };
+                      void *rbox = nullptr, *rscore = nullptr, *rcls = nullptr, *rcount = nullptr, *ovf = nullptr; int rstride = 0;
+                      // large route (nms_large.hip; y355_head_ws_large fills these): candidate capacity (0 = Y355_NMS_CAP) and route
+                      // (0 = by the image's candidate count, 1 = every image takes the large route)
+                      void *lbox = nullptr, *lscore = nullptr, *lcls = nullptr, *lcount = nullptr, *lsort = nullptr, *lkbox = nullptr,
+                           *lkeep = nullptr; int cap = 0, route = 0; };
+#define Y355_NMS_MAX_CAP (16 * Y355_NMS_CAP)   // most anchors / candidates per image of any head: a rank fits 16 bits
+#define Y355_NMS_MAX_CLASSES 256              // the large route sorts on 8 bits of the class (every head has A * (5 + C) <= 256)
+// (Re)allocates what a head of N anchors per image needs beyond the arrays above for candidate capacity `cap` (Y355_NMS_CAP ..
+// Y355_NMS_MAX_CAP) and `route`: the raw decode arrays (N > Y355_NMS_CAP, or the large route forced) and the large route's
+// lists (cap > Y355_NMS_CAP, or forced).  alloc(ptr, bytes, zero) != 0: failure; release(ptr) frees an earlier array.
+// The caller has synchronised the stream the head runs on.  A failure (non-zero) leaves ws unchanged.
+int y355_head_ws_large(y355_head_ws &ws, int N, int B, int cap, int route, const std::function<int(void **, size_t, bool)> &alloc,
+                       const std::function<void(void *)> &release);
+// the loud failure of a forward in which more anchors of an image passed conf_thresh than the candidate capacity holds
+inline std::string y355_head_overflow_message(int cap) {
+    return "more than " + std::to_string(cap) + " anchors of an image pass conf_thresh: raise the threshold" +
+           (cap < Y355_NMS_MAX_CAP ? std::string(cap > Y355_NMS_CAP ? " or the candidate capacity" : "") : std::string());
+}
 int y355_prepare_head(void);
 // decode, candidate sort, pruned pair walk (edge list), rounds + output.  `mid` (optional) is recorded
 // between the candidate sort and the pair walk.

@@ -23,6 +23,12 @@ OPT_RING_WORKGROUPS = 2
 OPT_FUSE_PAIRS = 3
 NET_OPT_WORKGROUPS = 1
 NET_OPT_THIN_RESIDENT = 2
+OPT_MAX_CANDIDATES = 4
+OPT_HEAD_ROUTE = 5
+NET_OPT_MAX_CANDIDATES = 3
+NET_OPT_HEAD_ROUTE = 4
+HEAD_ROUTE_AUTO = 0
+HEAD_ROUTE_LARGE = 1
 EINVAL, EHIP, ENOTREADY = -1, -2, -3
 ERANGE = -4
 
@@ -140,6 +146,13 @@ _SIGS = {
     "y355_conv_op_create_bf16_geom": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(ConvGeom), C.c_float, P(C.c_void_p)]),
     "y355_conv_op_create_i8_geom": (C.c_int, [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, P(ConvGeom), C.c_int, C.c_int, C.c_int,
                                               P(C.c_void_p)]),
+    "y355_head_f32_ex": (C.c_int, [C.c_int, C.c_int, P(C.c_void_p), P(C.c_int), P(C.c_int), P(C.c_float), P(C.c_float), C.c_int, C.c_int,
+                                   C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p,
+                                   C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_overflow": (C.c_int, [C.c_void_p, P(C.c_int)]),
+    "y355_max_candidates": (C.c_int, [C.c_void_p]),
+    "y355_pipeline_ticket_overflow": (C.c_int, [C.c_void_p, C.c_longlong, P(C.c_int)]),
+    "y355_net_max_candidates": (C.c_int, [C.c_void_p]),
     "y355_head_f32": (C.c_int, [C.c_int, C.c_int, P(C.c_void_p), P(C.c_int), P(C.c_int), P(C.c_float), P(C.c_float), C.c_int, C.c_int,
                                 C.c_int, C.c_int, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int, C.c_void_p, C.c_void_p,
                                 C.c_void_p, C.c_void_p]),

@@ -43,9 +43,16 @@ def _require_gpu(device):
     return torch.device("cuda", dev.index if dev.index is not None else torch.cuda.current_device())
 
 
+def _overflow_message(cap):
+    return "more than %d anchors of an image pass conf_thresh: raise the threshold%s" % (cap, " or max_candidates" if cap > 4096 else "")
+
+
 class Engine:
     def __init__(self, input_size, num_classes, anchors, conf_thresh=0.01, nms_thresh=0.5,
-                 max_batch=1, max_det=0, device=None):
+                 max_batch=1, max_det=0, device=None, max_candidates=None, head_route=None):
+        """max_candidates (default 4096, up to min(anchors per image, 65536)): the most anchors of an image that may pass
+        conf_thresh; head_route 1 sends every image through the NMS route for more than 4096 candidates (Y355_OPT_MAX_CANDIDATES,
+        Y355_OPT_HEAD_ROUTE of include/yolo355.h; set_max_candidates / set_head_route change them later)."""
         self._h = None
         lib = _ffi.lib()
         self.device = _require_gpu(device)
@@ -78,6 +85,10 @@ class Engine:
         self.num_anchors_total = lib.y355_num_anchors_total(h)
         self.conf_thresh, self.nms_thresh = float(conf_thresh), float(nms_thresh)
         self._out = None
+        if max_candidates is not None:
+            self.set_max_candidates(max_candidates)
+        if head_route is not None:
+            self.set_head_route(head_route)
 
     @classmethod
     def _borrowed(cls, handle, like, stream):
@@ -150,6 +161,30 @@ class Engine:
     def set_option(self, option, value):
         """Engine options of include/yolo355.h, e.g. set_option(_ffi.OPT_FUSE_FRONT, 0): one launch per layer."""
         _ffi.check(self._lib.y355_set_option(self._h, int(option), int(value)))
+        if int(option) in (_ffi.OPT_MAX_CANDIDATES, _ffi.OPT_HEAD_ROUTE):      # max_det follows the capacity
+            self.max_det = self._lib.y355_max_det(self._h)
+            self._out = None
+
+    def set_max_candidates(self, n):
+        self.set_option(_ffi.OPT_MAX_CANDIDATES, n)
+
+    def set_head_route(self, route):
+        self.set_option(_ffi.OPT_HEAD_ROUTE, route)
+
+    @property
+    def max_candidates(self):
+        return self._lib.y355_max_candidates(self._h)
+
+    def overflow(self):
+        """True if a forward since the last call dropped candidates beyond max_candidates (heads with more than 4096 anchors
+        per image, or with the large route forced; always False otherwise)."""
+        v = C.c_int(0)
+        _ffi.check(self._lib.y355_overflow(self._h, C.byref(v)))
+        return bool(v.value)
+
+    def _check_overflow(self):
+        if self.overflow():
+            raise _ffi.Y355Error(-1, _overflow_message(self.max_candidates))
 
     def set_thresholds(self, conf_thresh, nms_thresh):
         self.conf_thresh, self.nms_thresh = float(conf_thresh), float(nms_thresh)
@@ -257,6 +292,7 @@ class Engine:
         B = fd.shape[0]
         ob, os_, oc, on = self.forward_frames_device(fd, _ffi.F_GUARD if find else 0)
         n = on[:B].cpu().numpy()
+        self._check_overflow()
         if find:
             sat, guard = self.counters()
             if guard:
@@ -311,6 +347,7 @@ class Engine:
         """the host lists of a forward's device outputs; find: the head-room guard of that forward, as the reference raises it"""
         ob, os_, oc, on = out
         n = on[:B].cpu().numpy()
+        self._check_overflow()
         if find:
             sat, guard = self.counters()
             if guard:
@@ -339,6 +376,7 @@ class Engine:
         _ffi.check(self._lib.y355_scale_boxes(self._h, ob.data_ptr(), on.data_ptr(), wh.data_ptr(), B))
         self._leave(cur)
         n = on[:B].cpu().numpy()
+        self._check_overflow()
         if find:
             sat, guard = self.counters()
             if guard:
@@ -360,6 +398,7 @@ class Engine:
         flags = (_ffi.F_GUARD if find else 0) | (_ffi.F_TAP if tap else 0)
         ob, os_, oc, on = self.forward_device(xd, flags)
         n = on[:B].cpu().numpy()
+        self._check_overflow()
         if find:
             sat, guard = self.counters()
             if guard:
@@ -392,6 +431,7 @@ class Engine:
         n = np.empty((B,), np.int32)
         _ffi.check(self._lib.y355_head_nms(self._h, pq.ctypes.data, B, int(sa_pred), b.ctypes.data, s.ctypes.data,
                                            c.ctypes.data, n.ctypes.data))
+        self._check_overflow()
         return [(b[i, :n[i]].copy(), s[i, :n[i]].copy(), c[i, :n[i]].astype(np.int64)) for i in range(B)]
 
     def sync(self):
@@ -457,7 +497,7 @@ class Pipeline:
     max_batch in flight, results in order -- what models.SlimYOLOv2_quantize_bnfuse.forward_batch and the batched evaluators run."""
 
     def __init__(self, input_size, num_classes, anchors, conf_thresh=0.01, nms_thresh=0.5, max_batch=64, max_det=0,
-                 device=None, handles=0, ring_workgroups=-1):
+                 device=None, handles=0, ring_workgroups=-1, max_candidates=None, head_route=None):
         self._h = None
         lib = _ffi.lib()
         self.device = _require_gpu(device)
@@ -491,6 +531,10 @@ class Pipeline:
         self._bufs = [None] * self.depth                  # torch-owned output buffers, one set per ticket slot
         self._tickets = {}                                # slot -> (ticket, batch, outputs, input) of the ticket that holds it
         self._next = 0
+        if max_candidates is not None:
+            self.set_max_candidates(max_candidates)
+        if head_route is not None:
+            self.set_head_route(head_route)
 
     def close(self):
         if self._h is not None:
@@ -528,6 +572,27 @@ class Pipeline:
 
     def set_option(self, option, value):
         _ffi.check(self._lib.y355_pipeline_set_option(self._h, int(option), int(value)))
+        if int(option) in (_ffi.OPT_MAX_CANDIDATES, _ffi.OPT_HEAD_ROUTE):      # max_det follows the capacity: tickets still out are void
+            self.max_det = self._lib.y355_pipeline_max_det(self._h)
+            self._bufs = [None] * self.depth
+            self._tickets = {}
+
+    def set_max_candidates(self, n):
+        """Y355_OPT_MAX_CANDIDATES on every handle; call it while no ticket is out"""
+        self.set_option(_ffi.OPT_MAX_CANDIDATES, n)
+
+    def set_head_route(self, route):
+        self.set_option(_ffi.OPT_HEAD_ROUTE, route)
+
+    @property
+    def max_candidates(self):
+        return self._lib.y355_max_candidates(self._lib.y355_pipeline_engine(self._h, 0))
+
+    def overflow(self, ticket):
+        """True if the forward of this ticket dropped candidates beyond max_candidates (waits for that ticket only)"""
+        v = C.c_int(0)
+        _ffi.check(self._lib.y355_pipeline_ticket_overflow(self._h, int(ticket), C.byref(v)))
+        return bool(v.value)
 
     def set_normalization(self, mean_bgr, std_bgr):
         _ffi.check(self._lib.y355_pipeline_set_normalization(self._h, (C.c_float * 3)(*[float(v) for v in mean_bgr]),
@@ -681,6 +746,8 @@ class Pipeline:
         c = np.empty((B, md), np.int32)
         n = np.empty((B,), np.int32)
         _ffi.check(self._lib.y355_pipeline_fetch(self._h, int(ticket), b.ctypes.data, s.ctypes.data, c.ctypes.data, n.ctypes.data))
+        if self.overflow(ticket):
+            raise _ffi.Y355Error(-1, _overflow_message(self.max_candidates))
         return [(b[i, :n[i]].copy(), s[i, :n[i]].copy(), c[i, :n[i]].astype(np.int64)) for i in range(B)]
 
     def counters(self):
@@ -968,9 +1035,13 @@ def maxpool2x2_f32(x, device_id=0):
     return out
 
 
-def head_f32(preds, strides, anchors, num_classes, input_size, wh_mul, conf_thresh, nms_thresh, max_det=None, device_id=0):
-    """Detection head on fp32 prediction maps (y355_head_f32).  preds: list (1 or 2 levels) of [B, A*(5+C), Hs, Ws];
-    anchors: [nlev][A][2].  Returns a list over the batch of (boxes [n,4] normalised, scores [n], classes int64 [n])."""
+def head_f32(preds, strides, anchors, num_classes, input_size, wh_mul, conf_thresh, nms_thresh, max_det=None, device_id=0,
+             max_candidates=None, route=None, return_candidates=False):
+    """Detection head on fp32 prediction maps (y355_head_f32_ex).  preds: list (1 to 3 levels) of [B, A*(5+C), Hs, Ws];
+    anchors: [nlev][A][2].  Returns a list over the batch of (boxes [n,4] normalised, scores [n], classes int64 [n]).
+    max_candidates (default 4096, up to min(anchors per image, 65536)): the most anchors of an image that may pass
+    conf_thresh; route 1: every image through the NMS route for more than 4096 candidates.  return_candidates: also the
+    decode of every anchor, (list, (boxes [B,N,4], scores [B,N], classes int32 [B,N]))."""
     import ctypes as C
     lib = _ffi.lib()
     _need_gpu()
@@ -983,16 +1054,21 @@ def head_f32(preds, strides, anchors, num_classes, input_size, wh_mul, conf_thre
     ws = (C.c_int * nlev)(*[p.shape[3] for p in ps])
     st = (C.c_float * nlev)(*[float(s) for s in strides])
     ptrs = (C.c_void_p * nlev)(*[p.ctypes.data for p in ps])
-    N = min(sum(p.shape[2] * p.shape[3] * A for p in ps), 4096)      # the head keeps at most 4096 candidates per image
+    cap = 4096 if max_candidates is None else int(max_candidates)
+    na = sum(p.shape[2] * p.shape[3] * A for p in ps)
+    N = min(na, cap)                                                 # the head keeps at most `cap` candidates per image
     md = N if max_det is None else min(int(max_det), N)
     boxes = np.zeros((B, md, 4), np.float32)
     scores = np.zeros((B, md), np.float32)
     cls = np.zeros((B, md), np.int32)
     count = np.zeros((B,), np.int32)
-    _ffi.check(lib.y355_head_f32(int(device_id), nlev, ptrs, hs, ws, st, an.ctypes.data_as(C.POINTER(C.c_float)), A, int(num_classes),
-                                 int(input_size[0]), int(input_size[1]), float(wh_mul), float(conf_thresh), float(nms_thresh), B, md,
-                                 boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data, count.ctypes.data))
-    return [(boxes[b, :count[b]].copy(), scores[b, :count[b]].copy(), cls[b, :count[b]].astype(np.int64)) for b in range(B)]
+    cand = (np.zeros((B, na, 4), np.float32), np.zeros((B, na), np.float32), np.zeros((B, na), np.int32)) if return_candidates else None
+    _ffi.check(lib.y355_head_f32_ex(int(device_id), nlev, ptrs, hs, ws, st, an.ctypes.data_as(C.POINTER(C.c_float)), A, int(num_classes),
+                                    int(input_size[0]), int(input_size[1]), float(wh_mul), float(conf_thresh), float(nms_thresh), B, md,
+                                    cap, 0 if route is None else int(route), boxes.ctypes.data, scores.ctypes.data, cls.ctypes.data,
+                                    count.ctypes.data, *([c.ctypes.data for c in cand] if cand else [None, None, None])))
+    out = [(boxes[b, :count[b]].copy(), scores[b, :count[b]].copy(), cls[b, :count[b]].astype(np.int64)) for b in range(B)]
+    return (out, cand) if return_candidates else out
 
 
 def upsample2x_f32(x, device_id=0):

@@ -33,6 +33,12 @@ _TRACKERS = ["a_tracker_in", "a_tracker1", "a_tracker2", "a_tracker3_1", "a_trac
              "a_tracker4_2", "a_tracker5", "a_tracker6", "a_tracker7", "a_tracker_pred"]
 
 
+def _cap(model):
+    """a model's max_candidates as Engine / Pipeline / Net take it: None = leave the default capacity (4096) alone"""
+    cap = getattr(model, "max_candidates", 4096)
+    return None if cap == 4096 else cap
+
+
 class AveragedRangeTracker(nn.Module):
     """Checkpoint-compatible holder of the tracker buffers (models/slim_yolo_v2.py:9-14).
     The max|activation| statistics come from the GPU; the state update is prep.RangeTracker."""
@@ -46,8 +52,9 @@ class AveragedRangeTracker(nn.Module):
 
 class SlimYOLOv2_quantize_bnfuse(nn.Module):
     def __init__(self, device, input_size=None, num_classes=20, trainable=False, conf_thresh=0.01,
-                 nms_thresh=0.5, anchor_size=None, hr=False):
+                 nms_thresh=0.5, anchor_size=None, hr=False, max_candidates=4096):
         super().__init__()
+        self.max_candidates = int(max_candidates)      # most anchors of an image that may pass conf_thresh (Engine / Net max_candidates)
         self.device = device
         self.input_size = list(input_size)
         self.num_classes = num_classes
@@ -248,7 +255,7 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
                 self._engine.close()
             dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
             self._engine = Engine(self.input_size, self.num_classes, self.anchor_size.tolist(),
-                                  self.conf_thresh, self.nms_thresh, max_batch=max(batch, 1), device=dev)
+                                  self.conf_thresh, self.nms_thresh, max_batch=max(batch, 1), device=dev, max_candidates=_cap(self))
             self._engine_key = key
             self._loaded_version = None
         ver = self._weights_version()
@@ -276,7 +283,7 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
                 self._pipe.close()
             dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
             self._pipe = Pipeline(self.input_size, self.num_classes, self.anchor_size.tolist(), self.conf_thresh, self.nms_thresh,
-                                  max_batch=self.PIPELINE_CHUNK, device=dev)
+                                  max_batch=self.PIPELINE_CHUNK, device=dev, max_candidates=_cap(self))
             self._pipe_key, self._pipe_loaded = key, None
         ver = (self._weights_version(), bool(find))
         if self._pipe_loaded != ver:
@@ -294,7 +301,7 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
                 st["net"].close()
             dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
             st["net"] = Net("slim_yolo_v2", self.input_size, self.num_classes, self.anchor_size.tolist(), self.conf_thresh,
-                            self.nms_thresh, max_batch=max(batch, 1), device=dev, dtype="bf16")
+                            self.nms_thresh, max_batch=max(batch, 1), device=dev, dtype="bf16", max_candidates=_cap(self))
             st["key"], st["ver"] = key, None
         ver = (self._weights_version(), bool(find))
         if st["ver"] != ver:
@@ -463,7 +470,7 @@ class _NetModel(nn.Module):
                 st["net"].close()
             dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
             st["net"] = Net(self._arch, self.input_size, self.num_classes, self._flat_anchors(), self.conf_thresh,
-                            self.nms_thresh, max_batch=max(batch, 1), device=dev, dtype="int8" if int8 else "bf16")
+                            self.nms_thresh, max_batch=max(batch, 1), device=dev, dtype="int8" if int8 else "bf16", max_candidates=_cap(self))
             st["key"], st["ver"] = key, None
         ver = self._weights_version()
         if int8:
@@ -489,8 +496,9 @@ class SlimYOLOv2(_NetModel):
     _arch = "slim_yolo_v2"
 
     def __init__(self, device, input_size=None, num_classes=20, trainable=False, conf_thresh=0.01,
-                 nms_thresh=0.5, anchor_size=None, hr=False):
+                 nms_thresh=0.5, anchor_size=None, hr=False, max_candidates=4096):
         super().__init__()
+        self.max_candidates = int(max_candidates)      # most anchors of an image that may pass conf_thresh (Engine / Net max_candidates)
         self.device = device
         self.input_size = list(input_size)
         self.num_classes = num_classes

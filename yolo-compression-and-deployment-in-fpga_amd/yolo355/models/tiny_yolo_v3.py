@@ -21,8 +21,9 @@ class YOLOv3tiny(_NetModel):
     _arch = "tiny_yolo_v3"
 
     def __init__(self, device, input_size=None, num_classes=20, trainable=False, conf_thresh=0.01,
-                 nms_thresh=0.50, anchor_size=None, hr=False):
+                 nms_thresh=0.50, anchor_size=None, hr=False, max_candidates=4096):
         super().__init__()
+        self.max_candidates = int(max_candidates)      # most anchors of an image that may pass conf_thresh (Engine / Net max_candidates)
         self.device = device
         self.input_size = list(input_size)
         self.num_classes = num_classes

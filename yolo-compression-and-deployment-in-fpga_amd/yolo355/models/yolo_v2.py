@@ -19,8 +19,9 @@ class myYOLOv2(_NetModel):
     _arch = "yolo_v2"
 
     def __init__(self, device, input_size=None, num_classes=20, trainable=False, conf_thresh=0.001, nms_thresh=0.5,
-                 anchor_size=None, hr=False):
+                 anchor_size=None, hr=False, max_candidates=4096):
         super().__init__()
+        self.max_candidates = int(max_candidates)      # most anchors of an image that may pass conf_thresh (Engine / Net max_candidates)
         if trainable:
             raise NotImplementedError("yolo355 is an inference engine: myYOLOv2(trainable=True) is not built")
         self.device = device

@@ -19,9 +19,11 @@ PRED_TAIL = {"slim_yolo_v2": (1,), "tiny_yolo_v3": (2, 1), "yolo_v2": (1,), "yol
 
 class Net:
     def __init__(self, arch, input_size, num_classes, anchors, conf_thresh=0.01, nms_thresh=0.5,
-                 max_batch=1, max_det=0, device=None, dtype="bf16"):
+                 max_batch=1, max_det=0, device=None, dtype="bf16", max_candidates=None, head_route=None):
         """anchors: [[w, h], ...] -- A pairs for slim_yolo_v2 (grid units), 2*A pairs for tiny_yolo_v3
-        (pixels; the stride-16 level first, data/config.py:27-31)."""
+        (pixels; the stride-16 level first, data/config.py:27-31).  max_candidates (default 4096, up to min(anchors per
+        image, 65536)): the most anchors of an image that may pass conf_thresh; head_route 1: every image through the NMS route
+        for more than 4096 candidates (Y355_NET_OPT_MAX_CANDIDATES / Y355_NET_OPT_HEAD_ROUTE)."""
         self._h = None
         lib = _ffi.lib()
         self.device = _require_gpu(device)
@@ -58,6 +60,10 @@ class Net:
         self.num_layers = lib.y355_net_num_layers(h)
         self.num_tensors = lib.y355_net_num_tensors(h)
         self._out = None
+        if max_candidates is not None:
+            self.set_max_candidates(max_candidates)
+        if head_route is not None:
+            self.set_head_route(head_route)
 
     def close(self):
         if self._h is not None:
@@ -131,6 +137,19 @@ class Net:
     def set_option(self, option, value):
         """1 = Y355_NET_OPT_WORKGROUPS (throughput mode: persistent workgroups per ring launch, 0 = one per CU)"""
         _ffi.check(self._lib.y355_net_set_option(self._h, int(option), int(value)))
+        if int(option) in (_ffi.NET_OPT_MAX_CANDIDATES, _ffi.NET_OPT_HEAD_ROUTE):      # max_det follows the capacity
+            self.max_det = self._lib.y355_net_max_det(self._h)
+            self._out = None
+
+    @property
+    def max_candidates(self):
+        return self._lib.y355_net_max_candidates(self._h)
+
+    def set_max_candidates(self, n):
+        self.set_option(_ffi.NET_OPT_MAX_CANDIDATES, n)
+
+    def set_head_route(self, route):
+        self.set_option(_ffi.NET_OPT_HEAD_ROUTE, route)
 
     def set_thresholds(self, conf_thresh, nms_thresh):
         _ffi.check(self._lib.y355_net_set_thresholds(self._h, float(conf_thresh), float(nms_thresh)))
@@ -180,8 +199,8 @@ class Net:
             self.scale_boxes(ob, on, sizes_wh, B)
         n = on[:B].cpu().numpy()
         if self.overflow():
-            raise _ffi.Y355Error(-1,
-                                 "more than 4096 anchors of an image pass conf_thresh: raise the threshold")
+            raise _ffi.Y355Error(-1, "more than %d anchors of an image pass conf_thresh: raise the threshold%s"
+                                 % (self.max_candidates, " or max_candidates" if self.max_candidates > 4096 else ""))
         boxes, scores, cls = ob[:B].cpu().numpy(), os_[:B].cpu().numpy(), oc[:B].cpu().numpy()
         return [(boxes[i, :n[i]].copy(), scores[i, :n[i]].copy(), cls[i, :n[i]].astype(np.int64))
                 for i in range(B)]

@@ -1,0 +1,183 @@
+// Host-only check of the allocation logic in csrc/head_state.hip (HeadState: create, resize's swap and rollback, destroy) and
+// csrc/resize.hip (FrameStage: lazy buffers, the cached same-size table).  Device memory is the host heap here, through a DevMem
+// whose k-th allocation (or whose upload) fails on demand, so the program needs no GPU.  Built with the address and
+// undefined-behaviour sanitizers by `make -C csrc hostcheck`: a leak, a double free or a use after free ends it non-zero.
+#include "../include/yolo355.h"
+#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/head_nms.h"
+
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <set>
+
+static std::string g_err;
+int y355_fail(int code, const std::string &msg) {
+    g_err = msg;
+    return code;
+}
+
+#define CHECK(c)                                                          \
+    do {                                                                  \
+        if (!(c)) {                                                       \
+            fprintf(stderr, "%s:%d: CHECK(%s) failed\n", __FILE__, __LINE__, #c); \
+            exit(1);                                                      \
+        }                                                                 \
+    } while (0)
+
+namespace {
+std::set<void *> live;
+int n_alloc = 0, fail_at = -1, n_upload = 0;
+bool fail_upload = false;
+
+DevMem host_mem() {
+    DevMem m;
+    m.alloc = [](void **p, size_t bytes, bool zero) -> int {
+        if (n_alloc++ == fail_at) return y355_fail(Y355_EHIP, "injected allocation failure");
+        *p = zero ? calloc(1, bytes ? bytes : 16) : malloc(bytes ? bytes : 16);
+        live.insert(*p);
+        return 0;
+    };
+    m.release = [](void *p) {
+        CHECK(live.erase(p) == 1);          // released once, and only what alloc returned
+        free(p);
+    };
+    m.upload = [](void *dst, const void *src, size_t bytes, hipStream_t) -> int {
+        if (fail_upload) return y355_fail(Y355_EHIP, "injected upload failure");
+        ++n_upload;
+        memcpy(dst, src, bytes);
+        return 0;
+    };
+    return m;
+}
+
+// everything of a HeadState a failed resize must leave alone
+std::vector<uintptr_t> snapshot(const HeadState &s) {
+    const HeadWork &w = s.wk;
+    const void *ptrs[] = {w.cbox, w.cscore, w.ccls, w.corig, w.count, w.edges, w.nedges, w.binstart, w.astat, w.tiny, w.ntiny, w.ctype,
+                          w.dbox, w.dscore, w.dcls, w.rbox, w.rscore, w.rcls, w.rcount, w.ovf, w.lbox, w.lscore, w.lcls, w.lcount, w.lsort,
+                          w.lkbox, w.lkeep, s.cand_box, s.cand_score, s.cand_cls, s.o_box, s.o_score, s.o_cls, s.o_count};
+    std::vector<uintptr_t> v;
+    for (const void *p : ptrs) v.push_back((uintptr_t)p);
+    for (int x : {w.rstride, s.N, s.max_batch, s.cfg_max_det, s.max_det, s.cap, s.route}) v.push_back((uintptr_t)x);
+    for (void *p : s.allocs) v.push_back((uintptr_t)p);
+    return v;
+}
+bool owns_exactly_live(const HeadState &s) { return std::set<void *>(s.allocs.begin(), s.allocs.end()) == live && s.allocs.size() == live.size(); }
+
+void check_head(int N, int B, int cfg_max_det, bool tap, bool outs) {
+    const DevMem mem = host_mem();
+    HeadState st;
+    fail_at = -1;
+    n_alloc = 0;
+    CHECK(y355_head_create(st, N, B, cfg_max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, tap, outs, mem) == 0);
+    const int n_create = n_alloc;
+    CHECK(owns_exactly_live(st) && (int)live.size() == n_create);
+    CHECK((st.cand_box != nullptr) == tap && (st.o_box != nullptr) == outs && (st.o_count != nullptr) == outs);
+    CHECK((st.wk.rbox != nullptr) == (N > Y355_NMS_CAP) && !st.wk.lbox);
+    y355_head_destroy(st);
+    CHECK(live.empty());
+    for (int k = 0; k < n_create; ++k) {            // a create that fails at its k-th allocation frees what it took
+        fail_at = k;
+        n_alloc = 0;
+        CHECK(y355_head_create(st, N, B, cfg_max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, tap, outs, mem) != 0);
+        CHECK(live.empty() && st.allocs.empty() && !st.wk.cbox);
+    }
+    fail_at = -1;
+    CHECK(y355_head_create(st, N, B, cfg_max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, tap, outs, mem) == 0);
+    const int big = std::min(N, 2 * Y355_NMS_CAP);
+    const int steps[][2] = {{big, Y355_HEAD_ROUTE_AUTO},          {Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO}, {Y355_NMS_CAP, Y355_HEAD_ROUTE_LARGE},
+                            {big, Y355_HEAD_ROUTE_LARGE},         {big, Y355_HEAD_ROUTE_AUTO},          {Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO}};
+    for (const auto &sp : steps) {
+        const int cap = sp[0] < Y355_NMS_CAP ? Y355_NMS_CAP : sp[0], route = sp[1];
+        const std::vector<uintptr_t> before = snapshot(st);
+        const std::set<void *> live_before = live;
+        // the step with its k-th allocation failing, k = 0, 1, ...: nothing may change; the first k it does not reach (a step
+        // makes at most 15: 5 raw + 7 large + 3 outputs) is the step itself
+        bool done = false;
+        for (int k = 0; k <= 15 && !done; ++k) {
+            fail_at = k;
+            n_alloc = 0;
+            done = y355_head_resize(st, cap, route) == 0;
+            if (done) CHECK(n_alloc <= k);
+            else CHECK(snapshot(st) == before && live == live_before);
+        }
+        CHECK(done);
+        fail_at = -1;
+        const int ncand = std::min(N, cap);
+        CHECK(st.cap == cap && st.route == route && y355_head_capacity(st) == cap);
+        CHECK(st.max_det == ((cfg_max_det <= 0 || cfg_max_det > ncand) ? ncand : cfg_max_det));
+        CHECK((st.wk.lbox != nullptr) == (cap > Y355_NMS_CAP || route == Y355_HEAD_ROUTE_LARGE));
+        CHECK(owns_exactly_live(st));
+    }
+    y355_head_destroy(st);
+    CHECK(live.empty());
+}
+
+void check_stage() {
+    const int H = 96, W = 160, B = 3;
+    FrameStage st;
+    y355_stage_init(st, H, W, B, host_mem());
+    fail_at = -1;
+    n_alloc = n_upload = 0;
+    // set_normalization: all three channels are checked before one is assigned
+    const NormU8 norm0 = st.norm;
+    const float mean[3] = {0.1f, 0.2f, 0.3f}, bad[3] = {0.f, 1.f, 1.f}, good[3] = {0.5f, 0.6f, 0.7f};
+    CHECK(y355_stage_set_normalization(st, mean, bad) == Y355_EINVAL && g_err == "std must be positive");
+    CHECK(memcmp(&st.norm, &norm0, sizeof norm0) == 0);
+    CHECK(y355_stage_set_normalization(st, mean, good) == 0 && st.norm.mean[0] == 0.3f && st.norm.sd[2] == 0.5f);
+    // tables_for: one allocation, one upload per change of the source size
+    std::vector<int> want(3 * (size_t)(H + W));
+    CHECK(!st.tab && !st.frames && !st.tabs);
+    fail_at = 0;
+    CHECK(y355_stage_tables_for(st, 480, 640, nullptr) != 0 && !st.tab && st.src_h == 0 && live.empty());
+    fail_at = -1;
+    CHECK(y355_stage_tables_for(st, 480, 640, nullptr) == 0 && n_upload == 1 && st.src_h == 480 && st.src_w == 640);
+    y355_resize_tables(480, 640, H, W, want.data());
+    CHECK(memcmp(st.tab, want.data(), sizeof(int) * want.size()) == 0);
+    CHECK(y355_stage_tables_for(st, 480, 640, nullptr) == 0 && n_upload == 1);       // cached
+    CHECK(y355_stage_tables_for(st, 640, 480, nullptr) == 0 && n_upload == 2);       // (a swapped size is another size)
+    y355_resize_tables(640, 480, H, W, want.data());
+    CHECK(memcmp(st.tab, want.data(), sizeof(int) * want.size()) == 0);
+    fail_upload = true;                             // a failed upload forgets the cached size: the next call uploads again
+    CHECK(y355_stage_tables_for(st, 300, 300, nullptr) != 0 && st.src_h == 0 && st.src_w == 0);
+    fail_upload = false;
+    CHECK(y355_stage_tables_for(st, 640, 480, nullptr) == 0 && n_upload == 3);
+    CHECK(live.size() == 1 && !st.frames && !st.tabs);          // each buffer only when its route needs it
+    CHECK(y355_stage_need_list(st) == 0 && st.tabs && !st.frames && live.size() == 2);
+    fail_at = n_alloc;
+    CHECK(y355_stage_need_frames(st) != 0 && !st.frames && live.size() == 2);
+    fail_at = -1;
+    CHECK(y355_stage_need_frames(st) == 0 && st.frames && live.size() == 3);
+    CHECK(y355_stage_need_frames(st) == 0 && y355_stage_need_list(st) == 0 && live.size() == 3);
+    y355_stage_destroy(st);
+    CHECK(live.empty() && !st.tab && !st.frames && !st.tabs);
+    // the list rules, in order
+    uint8_t px[12] = {};
+    y355_frame f[2] = {{px, 1, 2, 0}, {px, 2, 1, 8}};
+    CHECK(y355_frames_check(nullptr, 1, 2) == Y355_EINVAL && g_err == "null frame array");
+    CHECK(y355_frames_check(f, 3, 2) == Y355_EINVAL && g_err == "batch out of range");
+    CHECK(y355_frames_check(f, 2, 2) == 0);
+    f[1].row_bytes = 2;
+    CHECK(y355_frames_check(f, 2, 2) == Y355_EINVAL && g_err == "row_bytes below width * 3");
+    f[1].width = 16385;
+    CHECK(y355_frames_check(f, 2, 2) == Y355_EINVAL && g_err == "bad frame size");
+    f[1].data_dev = nullptr;
+    CHECK(y355_frames_check(f, 2, 2) == Y355_EINVAL && g_err == "null frame pointer");
+}
+}  // namespace
+
+int main() {
+    check_head(2000, 2, 0, true, true);             // a small head: engine-like (tap and host outputs)
+    check_head(2000, 1, 100, false, true);          // y355_head_f32_ex without the tap
+    check_head(10647, 2, 0, true, false);           // more than 4096 anchors: y355_net-like (no host outputs)
+    check_head(10647, 3, 5000, true, true);         // max_det between the two capacities
+    check_stage();
+    CHECK(y355_head_check_option(10647, true, 4096, "m") == 0 && y355_head_check_option(10647, true, 10647, "m") == 0);
+    CHECK(y355_head_check_option(10647, true, 10648, "cap message") == Y355_EINVAL && g_err == "cap message");
+    CHECK(y355_head_check_option(2000, true, 4096, "m") == 0 && y355_head_check_option(2000, true, 4097, "m") == Y355_EINVAL);
+    CHECK(y355_head_check_option(2000, true, 2000, "m") == Y355_EINVAL);
+    CHECK(y355_head_check_option(2000, false, 1, "m") == 0 && y355_head_check_option(2000, false, 2, "route message") == Y355_EINVAL &&
+          g_err == "route message");
+    puts("host_state_check: ok");
+    return 0;
+}

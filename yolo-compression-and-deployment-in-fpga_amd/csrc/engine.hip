@@ -5,6 +5,7 @@
 //   conv4_1(64->128), conv4_2(128->128)+pool, conv5(128->256), conv6, conv7, pred (no act).
 #include "../../include/yolo355.h"
 #include "y355_common.h"
+#include "head_nms.h"
 
 #include <algorithm>
 #include <cmath>
@@ -188,15 +189,8 @@ struct y355_engine {
     int retune[10];
     float trk_scale[11] = {};       // AveragedRangeTracker.scale / first_a of the 11 trackers (models/slim_yolo_v2.py:13-14), y355_calibrate
     int trk_first[11] = {};
-    float nmean[3] = {0.485f, 0.456f, 0.406f};   // BaseTransform constants, RGB order (data/__init__.py:50 lists BGR)
-    float nstd[3] = {0.229f, 0.224f, 0.225f};
     const uint8_t *x_u8 = nullptr;  // uint8 frames of the forward being enqueued (y355_forward_u8)
-    // cv2.resize stage of BaseTransform (y355_forward_u8_resized): frames at the network size + coefficient tables
-    uint8_t *rs_frames = nullptr;
-    int *rs_tab = nullptr;          // [xofs W | xa 2W | yofs H | yb 2H]
-    int rs_src_h = 0, rs_src_w = 0;
-    int *rs_tabs = nullptr;         // frame lists (y355_forward_frames): [max_batch][3 (H + W)], one set of tables per frame; the
-                                    // list route never touches rs_tab / rs_src_h / rs_src_w, the same-size route's cached table
+    FrameStage stage;               // BaseTransform constants, cv2.resize stage of y355_forward_u8_resized / y355_forward_frames
     int8_t *w0_dev = nullptr;       // conv1 fragment
     int8_t *wf_dev = nullptr;       // weight fragments of the fused front end (y355_pack_front)
     Counters *ctr_dev = nullptr;    // [10]: the set the last forward / layer run counted into (one of ctrs' two)
@@ -205,15 +199,8 @@ struct y355_engine {
     int8_t *sink_dev = nullptr;
     unsigned long long *stamps_dev = nullptr;
     int Hs = 0, Ws = 0, N = 0;
-    // head workspace
-    y355_head_ws ws{};
-    float *cand_box = nullptr, *cand_score = nullptr;
-    int *cand_cls = nullptr;
-    // host-call staging
-    float *x_stage = nullptr;
-    float *o_box = nullptr, *o_score = nullptr;
-    int *o_cls = nullptr, *o_count = nullptr;
-    int max_det = 0;
+    HeadState head;                 // the head's workspace, max_det, candidate tap, outputs of the host calls
+    float *x_stage = nullptr;       // host-call staging
     int stamp_layer = -1;
     int profile = 0;
     int fuse_front = 1;             // conv1 + pool1 + conv2 + pool2 as one launch (front.hip) where eligible
@@ -237,47 +224,13 @@ static int dmalloc(y355_engine *h, void **p, size_t bytes, bool zero) {
     if (zero) HIPCHK(hipMemset(*p, 0, bytes ? bytes : 16));
     return 0;
 }
-static void dfree(y355_engine *h, void *q) {
-    (void)hipFree(q);
-    h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), q), h->allocs.end());
-}
-// per-image cap of the returned detections: what the configuration asked for, within the candidates an image can have
-static void set_max_det(y355_engine *h) {
-    const int ncand = std::min(h->N, h->ws.cap ? h->ws.cap : Y355_NMS_CAP);
-    h->max_det = (h->cfg.max_det <= 0 || h->cfg.max_det > ncand) ? ncand : h->cfg.max_det;
-}
-// the head workspace beyond the small route's arrays for candidate capacity `cap` and `route` (y355_head_ws_large), and the
-// engine-owned outputs of the host calls, sized by max_det
-static int head_ws_large(y355_engine *h, int cap, int route) {
-    // the new outputs first, then the workspace (all or nothing): a failure leaves the handle as it was
-    const int ncand = std::min(h->N, cap);
-    const int md = (h->cfg.max_det <= 0 || h->cfg.max_det > ncand) ? ncand : h->cfg.max_det;
-    const size_t B = (size_t)h->cfg.max_batch;
-    float *nb = nullptr, *ns = nullptr;
-    int *nc = nullptr;
-    int rc = dmalloc(h, (void **)&nb, sizeof(float) * 4 * md * B, false);
-    if (!rc) rc = dmalloc(h, (void **)&ns, sizeof(float) * md * B, false);
-    if (!rc) rc = dmalloc(h, (void **)&nc, sizeof(int) * md * B, false);
-    if (!rc)
-        rc = y355_head_ws_large(
-            h->ws, h->N, h->cfg.max_batch, cap, route, [h](void **p, size_t bytes, bool zero) { return dmalloc(h, p, bytes, zero); },
-            [h](void *q) { dfree(h, q); });
-    void *drop[] = {rc ? (void *)nb : (void *)h->o_box, rc ? (void *)ns : (void *)h->o_score, rc ? (void *)nc : (void *)h->o_cls};
-    for (void *q : drop)
-        if (q) dfree(h, q);
-    if (rc) return rc;
-    h->o_box = nb;
-    h->o_score = ns;
-    h->o_cls = nc;
-    set_max_det(h);
-    return 0;
-}
-
 extern "C" void y355_destroy(y355_engine *h) {
     if (!h) return;
     (void)hipSetDevice(h->cfg.device_id);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void *p : h->allocs) (void)hipFree(p);
+    y355_head_destroy(h->head);
+    y355_stage_destroy(h->stage);
     if (h->ev_ok) {
         for (auto &e : h->ev) (void)hipEventDestroy(e);
         for (auto &e : h->kev) { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); }
@@ -304,7 +257,7 @@ extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
     h->Hs = Hs;
     h->Ws = Ws;
     h->N = N;
-    set_max_det(h);
+    y355_stage_init(h->stage, cfg->height, cfg->width, cfg->max_batch, y355_hip_mem());
     for (int i = 0; i < 11; ++i) { h->sa[i] = 0; h->sa_set[i] = false; }
     for (int i = 0; i < 10; ++i) h->retune[i] = kRetuneDefault[i];
     if (!cfg->own_stream) {
@@ -346,7 +299,6 @@ extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
         Hc = L.Hout;
         Wc = L.Wout;
     }
-    const size_t cap = Y355_NMS_CAP;
     if (!rc) rc = dmalloc(h, (void **)&h->w0_dev, 1024, true);
     if (!rc) rc = dmalloc(h, (void **)&h->wf_dev, 16384, true);
     if (!rc) rc = dmalloc(h, (void **)&h->ctr_dev, sizeof(Counters) * 20, true);
@@ -355,26 +307,7 @@ extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
     h->ctrs.clean[0] = h->ctrs.clean[1] = true;        // zeroed by the allocation
     if (!rc) rc = dmalloc(h, (void **)&h->absmax_dev, 16, true);
     if (!rc) rc = dmalloc(h, (void **)&h->sink_dev, 16384, true);
-    if (!rc) rc = dmalloc(h, &h->ws.cbox, sizeof(float) * 4 * cap * B, false);
-    if (!rc) rc = dmalloc(h, &h->ws.cscore, sizeof(float) * cap * B, false);
-    if (!rc) rc = dmalloc(h, &h->ws.ccls, sizeof(int) * cap * B, false);
-    if (!rc) rc = dmalloc(h, &h->ws.corig, sizeof(int) * cap * B, false);
-    if (!rc) rc = dmalloc(h, &h->ws.count, sizeof(int) * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.edges, sizeof(unsigned int) * (size_t)Y355_HEAD_EDGE_CAP * B, false);      // EDGE_CAP pairs per image
-    if (!rc) rc = dmalloc(h, &h->ws.nedges, sizeof(int) * 2 * (size_t)B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.binstart, sizeof(int) * (cap + 8) * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.astat, sizeof(float) * 4 * Y355_HEAD_MAXG * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.tiny, sizeof(int) * cap * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.ntiny, sizeof(int) * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.dbox, sizeof(float) * 4 * cap * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.dscore, sizeof(float) * cap * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.dcls, sizeof(int) * cap * B, true);
-    if (!rc) rc = dmalloc(h, &h->ws.ctype, sizeof(int) * cap * B, true);          // candidate groups
-    if (!rc) rc = dmalloc(h, (void **)&h->cand_box, sizeof(float) * 4 * N * B, false);
-    if (!rc) rc = dmalloc(h, (void **)&h->cand_score, sizeof(float) * N * B, false);
-    if (!rc) rc = dmalloc(h, (void **)&h->cand_cls, sizeof(int) * N * B, false);
-    if (!rc) rc = head_ws_large(h, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO);       // heads of more than 4096 anchors: the raw decode; the outputs
-    if (!rc) rc = dmalloc(h, (void **)&h->o_count, sizeof(int) * B, true);
+    if (!rc) rc = y355_head_create(h->head, N, B, cfg->max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, true, true, y355_hip_mem());
     if (!rc) {
         bool ok = true;
         for (auto &e : h->ev) ok = ok && (hipEventCreate(&e) == hipSuccess);
@@ -410,14 +343,13 @@ extern "C" int y355_set_option(y355_engine *h, int option, int value) {
     case Y355_OPT_MAX_CANDIDATES:
     case Y355_OPT_HEAD_ROUTE: {
         const bool is_cap = option == Y355_OPT_MAX_CANDIDATES;
-        if (is_cap && value != Y355_NMS_CAP && (value < Y355_NMS_CAP || value > h->N))
-            return fail(Y355_EINVAL, "Y355_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)");
-        if (!is_cap && value != Y355_HEAD_ROUTE_AUTO && value != Y355_HEAD_ROUTE_LARGE)
-            return fail(Y355_EINVAL, "Y355_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)");
+        if (int rc = y355_head_check_option(h->N, is_cap, value,
+                                            is_cap ? "Y355_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)"
+                                                   : "Y355_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)"))
+            return rc;
         HIPCHK(hipSetDevice(h->cfg.device_id));
         HIPCHK(hipStreamSynchronize(h->stream));         // nothing in flight reads the arrays that go
-        const int cap = is_cap ? value : (h->ws.cap ? h->ws.cap : Y355_NMS_CAP), route = is_cap ? h->ws.route : value;
-        if (head_ws_large(h, cap, route)) return fail(Y355_EHIP, "device allocation failed");
+        if (y355_head_set_option(h->head, is_cap, value)) return fail(Y355_EHIP, "device allocation failed");
         return 0;
     }
     default: return fail(Y355_EINVAL, "unknown option");
@@ -428,26 +360,18 @@ extern "C" int y355_set_option(y355_engine *h, int option, int value) {
 // more anchors of an image passed conf_thresh than the candidate capacity holds (the excess was dropped); synchronous; clears the flag
 extern "C" int y355_overflow(y355_engine *h, int *overflow) {
     if (!h || !overflow) return fail(Y355_EINVAL, "null argument");
-    *overflow = 0;
-    if (!h->ws.ovf) return 0;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::vector<int> v(h->cfg.max_batch, 0);
-    HIPCHK(hipMemcpy(v.data(), h->ws.ovf, sizeof(int) * v.size(), hipMemcpyDeviceToHost));
-    for (int x : v) *overflow |= x != 0;
-    if (*overflow) HIPCHK(hipMemset(h->ws.ovf, 0, sizeof(int) * v.size()));
+    HIPCHK(y355_head_overflow_read(h->head, h->stream, overflow));
     return 0;
 }
 // pipeline.hip: the flags of the forwards enqueued so far move to dst_dev [max_batch] on the handle's stream and are cleared
 // behind the copy, so a ticket carries the overflow of its own forward (only for handles that have the flags)
-bool y355_has_overflow_flags(y355_engine *h) { return h->ws.ovf != nullptr; }
+bool y355_has_overflow_flags(y355_engine *h) { return h->head.wk.ovf != nullptr; }
 int y355_overflow_take(y355_engine *h, int *dst_dev) {
-    const size_t bytes = sizeof(int) * (size_t)h->cfg.max_batch;
-    HIPCHK(hipMemcpyAsync(dst_dev, h->ws.ovf, bytes, hipMemcpyDeviceToDevice, h->stream));
-    HIPCHK(hipMemsetAsync(h->ws.ovf, 0, bytes, h->stream));
+    HIPCHK(y355_head_overflow_take(h->head, dst_dev, h->stream));
     return 0;
 }
-extern "C" int y355_max_candidates(y355_engine *h) { return h ? (h->ws.cap ? h->ws.cap : Y355_NMS_CAP) : Y355_EINVAL; }
+extern "C" int y355_max_candidates(y355_engine *h) { return h ? y355_head_capacity(h->head) : Y355_EINVAL; }
 
 extern "C" int y355_set_thresholds(y355_engine *h, float conf, float nms) {
     if (!h) return fail(Y355_EINVAL, "null engine");
@@ -584,7 +508,7 @@ static int launch_layer(y355_engine *h, int k, int B, int mode, int guard, const
         Conv1Params p{};
         p.x = x_dev;
         p.x_u8 = x_dev ? nullptr : h->x_u8;
-        for (int c = 0; c < 3; ++c) { p.nmean[c] = h->nmean[c]; p.nstd[c] = h->nstd[c]; }
+        for (int c = 0; c < 3; ++c) { p.nmean[c] = h->stage.norm.mean[c]; p.nstd[c] = h->stage.norm.sd[c]; }
         p.out = L.out_dev;
         p.w = h->w0_dev;
         p.bias_t = L.bias_dev;
@@ -808,7 +732,7 @@ extern "C" int y355_get_feature(y355_engine *h, int idx, int batch, int8_t *dst)
     return 0;
 }
 
-static HeadParams head_params(y355_engine *h, int sa_pred, float *ob, float *os, int *oc, int *on) {
+static HeadParams head_params(y355_engine *h, int sa_pred, float *ob, float *os, int *oc, int *on, bool tap) {
     HeadParams p{};
     const Layer &L = h->L[9];
     p.nlev = 1;
@@ -829,26 +753,11 @@ static HeadParams head_params(y355_engine *h, int sa_pred, float *ob, float *os,
     p.group_by_area = 0;
     p.Hb = h->Hs;
     p.Wb = h->Ws;
-    if (h->N > Y355_NMS_CAP) {
-        // the candidates arrive thresholded and compacted: their position says nothing about the anchor, and one bin per cell
-        // and anchor (N bins) would not fit the sort's 4096-entry tables -- area octaves on a grid of at most 16 x 16 do
-        p.group_by_area = 1;
-        p.Hb = std::min(16, h->Hs);
-        p.Wb = std::min(16, h->Ws);
-    }
+    // more than 4096 anchors: the candidates arrive thresholded and compacted, their position says nothing about the anchor, and
+    // one bin per cell and anchor (N bins) would not fit the sort's 4096-entry tables -- area octaves do
+    if (h->N > Y355_NMS_CAP) y355_head_area_bins(p, h->Hs, h->Ws);
     p.pairs_wgs = h->ring_wgs > 0 ? Y355_TPUT_PAIRS_WGS : 0;    // throughput mode (Y355_OPT_RING_WORKGROUPS set): the pair walk holds one CU per image
-    p.in_w = (float)h->cfg.width;
-    p.in_h = (float)h->cfg.height;
-    p.conf_thresh = h->cfg.conf_thresh;
-    p.nms_thresh = h->cfg.nms_thresh;
-    p.cand_box = h->cand_box;
-    p.cand_score = h->cand_score;
-    p.cand_cls = h->cand_cls;
-    p.max_det = h->max_det;
-    p.out_box = ob;
-    p.out_score = os;
-    p.out_cls = oc;
-    p.out_count = on;
+    y355_head_fill(p, h->head, h->cfg.conf_thresh, h->cfg.nms_thresh, h->cfg.height, h->cfg.width, ob, os, oc, on, tap);
     return p;
 }
 
@@ -858,7 +767,7 @@ static int launch_front(y355_engine *h, int B, const float *x_dev) {
     FrontParams p{};
     p.x = x_dev;
     p.x_u8 = x_dev ? nullptr : h->x_u8;
-    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->nmean[c]; p.nstd[c] = h->nstd[c]; }
+    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->stage.norm.mean[c]; p.nstd[c] = h->stage.norm.sd[c]; }
     p.out = L1.out_dev;
     p.wf = h->wf_dev;
     p.bias1 = L0.bias_dev;
@@ -954,11 +863,10 @@ static int enqueue_forward(y355_engine *h, const float *x_dev, int batch, int fl
         if (int rc = launch_layer(h, k, batch, 0, guard, x_dev)) return rc;
     }
     if (prof) HIPCHK(hipEventRecord(h->ev[10], h->stream));
-    HeadParams hp = head_params(h, h->sa[10], boxes_dev, scores_dev, cls_dev, count_dev);
-    if (!(flags & Y355_F_TAP)) { hp.cand_box = nullptr; hp.cand_score = nullptr; hp.cand_cls = nullptr; }
+    const HeadParams hp = head_params(h, h->sa[10], boxes_dev, scores_dev, cls_dev, count_dev, (flags & Y355_F_TAP) != 0);
     const bool kprof = prof && h->profile == 2;
     for (int i = 10; i < Y355_NUM_KERNEL_TIMERS; ++i) h->kev_set[i] = kprof;
-    y355_launch_head_nms(hp, batch, h->ws, h->stream, prof ? h->ev[11] : nullptr, kprof ? &h->kev[10] : nullptr);
+    y355_launch_head_nms(hp, batch, h->head, h->stream, prof ? h->ev[11] : nullptr, kprof ? &h->kev[10] : nullptr);
     HIPCHK(hipGetLastError());
     if (prof) HIPCHK(hipEventRecord(h->ev[12], h->stream));
     return 0;
@@ -980,12 +888,7 @@ extern "C" int y355_forward(y355_engine *h, const float *x_dev, int batch, int f
 // BaseTransform constants of the uint8 path, in the reference's BGR order (data/__init__.py:50)
 extern "C" int y355_set_normalization(y355_engine *h, const float *mean_bgr, const float *std_bgr) {
     if (!h || !mean_bgr || !std_bgr) return fail(Y355_EINVAL, "null argument");
-    for (int c = 0; c < 3; ++c) {
-        if (!(std_bgr[2 - c] > 0.f)) return fail(Y355_EINVAL, "std must be positive");
-        h->nmean[c] = mean_bgr[2 - c];
-        h->nstd[c] = std_bgr[2 - c];
-    }
-    return 0;
+    return y355_stage_set_normalization(h->stage, mean_bgr, std_bgr);
 }
 
 // The step in front of the path: frames as cv2 delivers them, uint8 HWC BGR [B][H][W][3]
@@ -1006,7 +909,7 @@ extern "C" int y355_forward_u8(y355_engine *h, const uint8_t *frames_dev, int ba
         if (!h->x_stage) {
             if (int rc = dmalloc(h, (void **)&h->x_stage, sizeof(float) * xin * h->cfg.max_batch, false)) return rc;
         }
-        y355_launch_normalize_u8(frames_dev, h->x_stage, batch, h->cfg.height, h->cfg.width, h->nmean, h->nstd, h->stream);
+        y355_launch_normalize_u8(frames_dev, h->x_stage, batch, h->cfg.height, h->cfg.width, h->stage.norm.mean, h->stage.norm.sd, h->stream);
         HIPCHK(hipGetLastError());
         return enqueue_forward(h, h->x_stage, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev, h->profile != 0);
     }
@@ -1026,54 +929,22 @@ extern "C" int y355_forward_u8_resized(y355_engine *h, const uint8_t *frames_dev
     if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return fail(Y355_EINVAL, "bad frame size");
     HIPCHK(hipSetDevice(h->cfg.device_id));
     const int H = h->cfg.height, W = h->cfg.width;
-    if (!h->rs_frames) {
-        if (int rc = dmalloc(h, (void **)&h->rs_frames, (size_t)h->cfg.max_batch * H * W * 3, false)) return rc;
-        if (int rc = dmalloc(h, (void **)&h->rs_tab, sizeof(int) * 3 * (size_t)(H + W), false)) return rc;
-    }
-    if (h->rs_src_h != src_h || h->rs_src_w != src_w) {
-        std::vector<int> tab(3 * (size_t)(H + W));
-        y355_resize_tables(src_h, src_w, H, W, tab.data());
-        HIPCHK(hipStreamSynchronize(h->stream));          // a previous forward may still read the old tables
-        HIPCHK(hipMemcpy(h->rs_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-        h->rs_src_h = src_h;
-        h->rs_src_w = src_w;
-    }
-    y355_launch_resize_u8(frames_dev, h->rs_frames, h->rs_tab, batch, src_h, src_w, H, W, h->stream);
+    FrameStage &st = h->stage;
+    if (int rc = y355_stage_need_frames(st)) return rc;
+    if (int rc = y355_stage_tables_for(st, src_h, src_w, h->stream)) return rc;
+    y355_launch_resize_u8(frames_dev, st.frames, st.tab, batch, src_h, src_w, H, W, h->stream);
     HIPCHK(hipGetLastError());
     if (resized_out_dev)
-        HIPCHK(hipMemcpyAsync(resized_out_dev, h->rs_frames, (size_t)batch * H * W * 3, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(resized_out_dev, st.frames, (size_t)batch * H * W * 3, hipMemcpyDeviceToDevice, h->stream));
     if (!boxes_dev && !scores_dev && !cls_dev && !count_dev) return 0;      // resize only
-    return y355_forward_u8(h, h->rs_frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+    return y355_forward_u8(h, st.frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
 }
 
 // ---- frame lists: every frame with its own pointer, size and row pitch (the reference's callers: one image at a time, each
 // of its own size).  All frames, those at the network size included, go through the ragged stage of resize.hip into
-// rs_frames; the forward then is y355_forward_u8 on that buffer.  The stage builds its tables on the device (rs_tabs, one set
-// per frame) and takes the descriptors as kernel arguments: nothing is uploaded, nothing waits, and the same-size route's
-// cached table (rs_tab under rs_src_h / rs_src_w) stays what it was.
-int y355_frames_check(const y355_frame *frames, int batch, int max_batch) {
-    if (!frames) return fail(Y355_EINVAL, "null frame array");
-    if (batch < 1 || batch > max_batch) return fail(Y355_EINVAL, "batch out of range");
-    for (int i = 0; i < batch; ++i) {
-        const y355_frame &f = frames[i];
-        if (!f.data_dev) return fail(Y355_EINVAL, "null frame pointer");
-        if (f.height < 1 || f.width < 1 || f.height > 16384 || f.width > 16384) return fail(Y355_EINVAL, "bad frame size");
-        if (f.row_bytes != 0 && f.row_bytes < 3 * (int64_t)f.width) return fail(Y355_EINVAL, "row_bytes below width * 3");
-    }
-    return 0;
-}
-
-// the stage's buffers, allocated at the first list call of a handle (rs_frames may exist already: y355_forward_u8_resized)
-static int list_buffers(y355_engine *h) {
-    const int H = h->cfg.height, W = h->cfg.width;
-    if (!h->rs_tabs)
-        if (int rc = dmalloc(h, (void **)&h->rs_tabs, sizeof(int) * 3 * (size_t)(H + W) * h->cfg.max_batch, false)) return rc;
-    if (!h->rs_frames) {
-        if (int rc = dmalloc(h, (void **)&h->rs_frames, (size_t)h->cfg.max_batch * H * W * 3, false)) return rc;
-        if (int rc = dmalloc(h, (void **)&h->rs_tab, sizeof(int) * 3 * (size_t)(H + W), false)) return rc;
-    }
-    return 0;
-}
+// the stage's frames buffer; the forward then is y355_forward_u8 on that buffer.  The stage builds its tables on the device
+// (FrameStage::tabs, one set per frame) and takes the descriptors as kernel arguments: nothing is uploaded, nothing waits, and
+// the same-size route's cached table stays what it was.
 
 // everything of a list forward that can fail, in front of its first launch (and, for y355_pipeline_submit_frames, in front
 // of the pipeline's own state): the list rules and the handle's readiness (weights, exponents) without a HIP call, then the
@@ -1087,16 +958,17 @@ int y355_frames_prepare(y355_engine *h, const y355_frame *frames, int batch) {
     HIPCHK(hipSetDevice(h->cfg.device_id));
     for (int k = 0; k < 10; ++k)
         if (int rc = refresh_layer(h, k, true)) return rc;
-    return list_buffers(h);
+    if (int rc = y355_stage_need_list(h->stage)) return rc;
+    return y355_stage_need_frames(h->stage);
 }
 
 extern "C" int y355_forward_frames(y355_engine *h, const y355_frame *frames, int batch, int flags, float *boxes_dev,
                                    float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !frames || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return fail(Y355_EINVAL, "null argument");
     if (int rc = y355_frames_prepare(h, frames, batch)) return rc;
-    y355_launch_resize_frames(frames, batch, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+    y355_launch_resize_frames(frames, batch, h->stage.frames, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
     HIPCHK(hipGetLastError());
-    return y355_forward_u8(h, h->rs_frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+    return y355_forward_u8(h, h->stage.frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
 }
 
 // parity tap of the ragged stage: the list -> out_dev [batch][H][W][3] at the network size, on the engine's stream
@@ -1104,9 +976,21 @@ extern "C" int y355_resize_frames(y355_engine *h, const y355_frame *frames, int 
     if (!h || !frames || !out_dev) return fail(Y355_EINVAL, "null argument");
     if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (int rc = list_buffers(h)) return rc;
-    y355_launch_resize_frames(frames, batch, out_dev, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+    if (int rc = y355_stage_need_list(h->stage)) return rc;
+    y355_launch_resize_frames(frames, batch, out_dev, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
     HIPCHK(hipGetLastError());
+    return 0;
+}
+
+// the host calls' outputs (HeadState::o_*) of a forward just enqueued, to the caller's arrays; waits for the stream
+static int outputs_to_host(y355_engine *h, int batch, float *boxes, float *scores, int32_t *cls, int32_t *count) {
+    const HeadState &hd = h->head;
+    const size_t md = hd.max_det;
+    HIPCHK(hipMemcpyAsync(boxes, hd.o_box, sizeof(float) * 4 * md * batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(scores, hd.o_score, sizeof(float) * md * batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(cls, hd.o_cls, sizeof(int) * md * batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipMemcpyAsync(count, hd.o_count, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
+    HIPCHK(hipStreamSynchronize(h->stream));
     return 0;
 }
 
@@ -1120,14 +1004,8 @@ extern "C" int y355_forward_host(y355_engine *h, const float *x_host, int batch,
         if (int rc = dmalloc(h, (void **)&h->x_stage, sizeof(float) * xin * h->cfg.max_batch, false)) return rc;
     }
     HIPCHK(hipMemcpyAsync(h->x_stage, x_host, sizeof(float) * xin * batch, hipMemcpyHostToDevice, h->stream));
-    if (int rc = y355_forward(h, h->x_stage, batch, flags, h->o_box, h->o_score, h->o_cls, h->o_count)) return rc;
-    const size_t md = h->max_det;
-    HIPCHK(hipMemcpyAsync(boxes, h->o_box, sizeof(float) * 4 * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(scores, h->o_score, sizeof(float) * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cls, h->o_cls, sizeof(int) * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(count, h->o_count, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    if (int rc = y355_forward(h, h->x_stage, batch, flags, h->head.o_box, h->head.o_score, h->head.o_cls, h->head.o_count)) return rc;
+    return outputs_to_host(h, batch, boxes, scores, cls, count);
 }
 
 extern "C" int y355_forward_counters(y355_engine *h, int64_t *saturated, int64_t *guard) {
@@ -1150,10 +1028,7 @@ extern "C" int y355_get_candidates(y355_engine *h, int batch, float *boxes, floa
     if (!h || !boxes || !scores || !cls) return fail(Y355_EINVAL, "null argument");
     if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(boxes, h->cand_box, sizeof(float) * 4 * h->N * batch, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(scores, h->cand_score, sizeof(float) * h->N * batch, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cls, h->cand_cls, sizeof(int) * h->N * batch, hipMemcpyDeviceToHost));
+    HIPCHK(y355_head_get_candidates(h->head, h->stream, batch, boxes, scores, cls));
     return 0;
 }
 
@@ -1172,19 +1047,13 @@ extern "C" int y355_head_nms(y355_engine *h, const int8_t *pred_q, int batch, in
                     tmp[(((size_t)b * Hs + y) * Ws + x) * CS + c] = pred_q[(((size_t)b * PC + c) * Hs + y) * Ws + x];
     HIPCHK(hipStreamSynchronize(h->stream));
     HIPCHK(hipMemcpy(L.out_dev, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-    HeadParams hp = head_params(h, sa_pred, h->o_box, h->o_score, h->o_cls, h->o_count);
-    y355_launch_head_nms(hp, batch, h->ws, h->stream, nullptr);
+    const HeadState &hd = h->head;
+    y355_launch_head_nms(head_params(h, sa_pred, hd.o_box, hd.o_score, hd.o_cls, hd.o_count, true), batch, hd, h->stream, nullptr);
     HIPCHK(hipGetLastError());
-    const size_t md = h->max_det;
-    HIPCHK(hipMemcpyAsync(boxes, h->o_box, sizeof(float) * 4 * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(scores, h->o_score, sizeof(float) * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cls, h->o_cls, sizeof(int) * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(count, h->o_count, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return outputs_to_host(h, batch, boxes, scores, cls, count);
 }
 
-extern "C" int y355_max_det(y355_engine *h) { return h ? h->max_det : Y355_EINVAL; }
+extern "C" int y355_max_det(y355_engine *h) { return h ? h->head.max_det : Y355_EINVAL; }
 extern "C" int y355_num_anchors_total(y355_engine *h) { return h ? h->N : Y355_EINVAL; }
 
 // Evaluator-side step right after the path: `bboxes *= [[w, h, w, h]]` of every image

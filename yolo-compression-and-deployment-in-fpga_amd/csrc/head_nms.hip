@@ -993,7 +993,7 @@ int y355_prepare_head(void) {
     return (int)hipFuncSetAttribute((const void *)pairs_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, PAIRS_LDS);
 }
 
-void y355_launch_head_nms(const HeadParams &p_in, int batch, const y355_head_ws &ws, hipStream_t s, hipEvent_t mid,
+void y355_launch_head_nms(const HeadParams &p_in, int batch, const HeadState &st, hipStream_t s, hipEvent_t mid,
                           hipEvent_t (*kev)[2]) {
     // Heads with 3 .. MAXG classes sort their candidates (class, bin): NMS is per class (models/slim_yolo_v2.py:196-203,
     // models/tiny_yolo_v3.py:129-136), so a candidate's partners all sit in its class's bins.  The bin grid (any grid over the
@@ -1010,18 +1010,7 @@ void y355_launch_head_nms(const HeadParams &p_in, int batch, const y355_head_ws 
     }
     hipEvent_t none[2] = {nullptr, nullptr};
     hipEvent_t *k0 = kev ? kev[0] : none, *k1 = kev ? kev[1] : none, *k2 = kev ? kev[2] : none, *k3 = kev ? kev[3] : none;
-    HeadWork wk;
-    wk.cbox = (float *)ws.cbox;
-    wk.cscore = (float *)ws.cscore;
-    wk.ccls = (int *)ws.ccls;
-    wk.corig = (int *)ws.corig;
-    wk.count = (int *)ws.count;
-    wk.edges = (unsigned int *)ws.edges;
-    wk.nedges = (int *)ws.nedges;
-    wk.binstart = (int *)ws.binstart;
-    wk.astat = (float *)ws.astat;
-    wk.tiny = (int *)ws.tiny;
-    wk.ntiny = (int *)ws.ntiny;
+    HeadWork wk = st.wk;            // the state's arrays; what follows is decided per launch
     static unsigned long long *g_stamps = nullptr;
 #ifdef Y355_EXPERIMENTS
     static const bool want = getenv("Y355_NMS_STAMPS") != nullptr;
@@ -1034,32 +1023,16 @@ void y355_launch_head_nms(const HeadParams &p_in, int batch, const y355_head_ws 
     }
     wk.stamps = g_stamps;
     y355_nms_stamps_dev = g_stamps;
-    wk.ctype = (int *)ws.ctype;
-    wk.dbox = (float *)ws.dbox;
-    wk.dscore = (float *)ws.dscore;
-    wk.dcls = (int *)ws.dcls;
     bool big = false;
     {
         int n = 0;
         for (int l = 0; l < p.nlev; ++l) n += p.lev[l].Hs * p.lev[l].Ws * p.A;
-        // callers allocate the raw arrays for heads of more than CAP anchors (and for any head whose large route is forced)
-        const bool large = n > NMS_CAP || ws.route == 1;
-        big = ws.cap > NMS_CAP || ws.route == 1;          // the large route's kernels run beside these (nms_large.hip)
-        wk.rbox = large ? (float *)ws.rbox : nullptr;
-        wk.lbox = (float *)ws.lbox;
-        wk.lscore = (float *)ws.lscore;
-        wk.lcls = (int *)ws.lcls;
-        wk.lcount = (int *)ws.lcount;
-        wk.lsort = (uint2 *)ws.lsort;
-        wk.lkbox = (float *)ws.lkbox;
-        wk.lkeep = (unsigned char *)ws.lkeep;
-        wk.lcap = ws.cap;
-        wk.lforce = ws.route == 1;
-        wk.rscore = (float *)ws.rscore;
-        wk.rcls = (int *)ws.rcls;
-        wk.rcount = (int *)ws.rcount;
-        wk.ovf = (int *)ws.ovf;
-        wk.rstride = ws.rstride;
+        // the state holds the raw arrays for heads of more than CAP anchors (and for any head whose large route is forced)
+        const bool large = n > NMS_CAP || st.route == 1;
+        big = st.cap > NMS_CAP || st.route == 1;          // the large route's kernels run beside these (nms_large.hip)
+        if (!large) wk.rbox = nullptr;
+        wk.lcap = st.cap;
+        wk.lforce = st.route == 1;
         // every level's map has the same element size and padded channel count
         // every level's map has the same element size and padded channel count; a workgroup stages dec_cells(A) cells, fewer
         // when a cell is wide (few anchors x an fp32 map of 256 channels would need 263 KB): at most DEC_LDS bytes

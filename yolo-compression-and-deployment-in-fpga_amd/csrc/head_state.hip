@@ -1,0 +1,222 @@
+// yolo355 -- host state of the detection head (HeadState, head_nms.h): what y355_engine, y355_net and y355_head_f32_ex keep
+// for head_nms.hip / nms_large.hip -- the workspace, max_det, the candidate capacity and route, the candidate tap, the host
+// calls' outputs -- and the HIP form of DevMem.  No kernels here; host_state_check.cpp runs this file's allocation logic on
+// the CPU with an allocator that fails on demand.
+#include "../../include/yolo355.h"
+#include "head_nms.h"
+
+#include <algorithm>
+
+int y355_fail(int code, const std::string &msg);
+#define HIPCHK(expr)                                                                        \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess)                                                               \
+            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
+
+static int hip_alloc(void **p, size_t bytes, bool zero) {
+    HIPCHK(hipMalloc(p, bytes ? bytes : 16));
+    if (zero) {
+        const hipError_t e_ = hipMemset(*p, 0, bytes ? bytes : 16);
+        if (e_ != hipSuccess) {
+            (void)hipFree(*p);
+            return y355_fail(Y355_EHIP, std::string("hipMemset(*p, 0, bytes ? bytes : 16): ") + hipGetErrorString(e_));
+        }
+    }
+    return 0;
+}
+static int hip_upload(void *dst, const void *src, size_t bytes, hipStream_t s) {
+    HIPCHK(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
+    return 0;
+}
+const DevMem &y355_hip_mem(void) {
+    static const DevMem m{hip_alloc, [](void *p) { (void)hipFree(p); }, hip_upload};
+    return m;
+}
+
+namespace {
+// allocations of one create / resize: all of them, or none (the destructor returns what a failure left behind)
+struct Fresh {
+    HeadState &st;
+    std::vector<void *> got;
+    int rc = 0;
+    explicit Fresh(HeadState &s) : st(s) {}
+    template <typename T>
+    void get(T **p, size_t bytes, bool zero = true) {
+        void *q = nullptr;
+        if (!rc) rc = st.mem.alloc(&q, bytes, zero);
+        if (rc) return;
+        got.push_back(q);
+        *p = (T *)q;
+    }
+    void commit() {
+        st.allocs.insert(st.allocs.end(), got.begin(), got.end());
+        got.clear();
+    }
+    ~Fresh() {
+        for (void *q : got) st.mem.release(q);
+    }
+};
+void drop(HeadState &st, void *q) {
+    if (!q) return;
+    st.mem.release(q);
+    st.allocs.erase(std::remove(st.allocs.begin(), st.allocs.end(), q), st.allocs.end());
+}
+int max_det_for(int cfg_max_det, int N, int cap) {
+    const int ncand = std::min(N, cap);
+    return (cfg_max_det <= 0 || cfg_max_det > ncand) ? ncand : cfg_max_det;
+}
+}  // namespace
+
+int y355_head_create(HeadState &st, int N, int B_, int cfg_max_det, int cap, int route, bool want_tap, bool want_host_outputs,
+                     const DevMem &mem) {
+    st = HeadState{};
+    st.mem = mem;
+    st.N = N;
+    st.max_batch = B_;
+    st.cfg_max_det = cfg_max_det;
+    st.cap = Y355_NMS_CAP;
+    st.max_det = max_det_for(cfg_max_det, N, Y355_NMS_CAP);
+    const size_t B = (size_t)B_, c = Y355_NMS_CAP;
+    HeadWork &w = st.wk;
+    Fresh f(st);
+    // the small route's arrays (sizes per image: HeadWork); what a kernel reads before it writes starts at zero
+    f.get(&w.cbox, sizeof(float) * 4 * c * B, false);
+    f.get(&w.cscore, sizeof(float) * c * B, false);
+    f.get(&w.ccls, sizeof(int) * c * B, false);
+    f.get(&w.corig, sizeof(int) * c * B, false);
+    f.get(&w.count, sizeof(int) * B);
+    f.get(&w.edges, sizeof(unsigned int) * (size_t)Y355_HEAD_EDGE_CAP * B, false);
+    f.get(&w.nedges, sizeof(int) * 2 * B);
+    f.get(&w.binstart, sizeof(int) * (c + 8) * B);
+    f.get(&w.astat, sizeof(float) * 4 * Y355_HEAD_MAXG * B);
+    f.get(&w.tiny, sizeof(int) * c * B);
+    f.get(&w.ntiny, sizeof(int) * B);
+    f.get(&w.ctype, sizeof(int) * c * B);
+    f.get(&w.dbox, sizeof(float) * 4 * c * B);
+    f.get(&w.dscore, sizeof(float) * c * B);
+    f.get(&w.dcls, sizeof(int) * c * B);
+    if (want_tap) {
+        f.get(&st.cand_box, sizeof(float) * 4 * (size_t)N * B, false);
+        f.get(&st.cand_score, sizeof(float) * (size_t)N * B, false);
+        f.get(&st.cand_cls, sizeof(int) * (size_t)N * B, false);
+    }
+    if (want_host_outputs) f.get(&st.o_count, sizeof(int) * B);
+    if (!f.rc) {
+        f.commit();
+        f.rc = y355_head_resize(st, cap, route);        // the raw decode, the large route's lists, o_box / o_score / o_cls
+    }
+    if (f.rc) y355_head_destroy(st);
+    return f.rc;
+}
+
+void y355_head_destroy(HeadState &st) {
+    for (void *q : st.allocs) st.mem.release(q);
+    const DevMem mem = st.mem;
+    st = HeadState{};
+    st.mem = mem;
+}
+
+int y355_head_resize(HeadState &st, int cap, int route) {
+    static_assert(Y355_NMS_MAX_CAP <= 65536 && Y355_NMS_MAX_CLASSES <= 256, "sort_large_kernel packs class << 16 | rank, 8 + 16 bits");
+    const size_t B = (size_t)st.max_batch, c = (size_t)cap;
+    const int md = max_det_for(st.cfg_max_det, st.N, cap);
+    HeadState nw = st;              // (allocs is copied too: small, and only on this cold path)
+    HeadWork &w = nw.wk;
+    w.lbox = w.lscore = nullptr;
+    w.lcls = w.lcount = nullptr;
+    w.lsort = nullptr;
+    w.lkbox = nullptr;
+    w.lkeep = nullptr;
+    nw.cap = cap;
+    nw.route = route;
+    nw.max_det = md;
+    Fresh f(nw);
+    const bool raw = st.N > Y355_NMS_CAP || route == Y355_HEAD_ROUTE_LARGE, big = cap > Y355_NMS_CAP || route == Y355_HEAD_ROUTE_LARGE;
+    if (raw && !w.rbox) {           // once there they stay: the launcher hides them from a small head on the automatic route
+        w.rstride = (st.N + 3) / 4 * 4;
+        f.get(&w.rbox, sizeof(float) * 4 * (size_t)w.rstride * B);
+        f.get(&w.rscore, sizeof(float) * (size_t)w.rstride * B);
+        f.get(&w.rcls, sizeof(int) * (size_t)w.rstride * B);
+        f.get(&w.rcount, sizeof(int) * B);
+        f.get(&w.ovf, sizeof(int) * B);
+    }
+    if (big) {
+        f.get(&w.lbox, sizeof(float) * 4 * c * B);
+        f.get(&w.lscore, sizeof(float) * c * B);
+        f.get(&w.lcls, sizeof(int) * c * B);
+        f.get(&w.lcount, sizeof(int) * B);
+        f.get(&w.lsort, sizeof(uint2) * 2 * c * B);
+        f.get(&w.lkbox, sizeof(float) * 4 * c * B);
+        f.get(&w.lkeep, c * B);
+    }
+    if (st.o_count) {
+        f.get(&nw.o_box, sizeof(float) * 4 * (size_t)md * B);
+        f.get(&nw.o_score, sizeof(float) * (size_t)md * B);
+        f.get(&nw.o_cls, sizeof(int) * (size_t)md * B);
+    }
+    if (f.rc) return f.rc;
+    f.commit();
+    void *old[] = {st.wk.lbox, st.wk.lscore, st.wk.lcls, st.wk.lcount, st.wk.lsort, st.wk.lkbox, st.wk.lkeep,
+                   st.o_count ? st.o_box : nullptr, st.o_count ? st.o_score : nullptr, st.o_count ? st.o_cls : nullptr};
+    for (void *q : old) drop(nw, q);
+    st = std::move(nw);
+    return 0;
+}
+
+int y355_head_check_option(int N, bool is_cap, int value, const char *msg) {
+    const bool ok = is_cap ? value == Y355_NMS_CAP || (value >= Y355_NMS_CAP && value <= N)
+                           : value == Y355_HEAD_ROUTE_AUTO || value == Y355_HEAD_ROUTE_LARGE;
+    return ok ? 0 : y355_fail(Y355_EINVAL, msg);
+}
+
+hipError_t y355_head_overflow_read(const HeadState &st, hipStream_t s, int *overflow) {
+    *overflow = 0;
+    if (!st.wk.ovf) return hipSuccess;
+    hipError_t e = hipStreamSynchronize(s);
+    std::vector<int> v(st.max_batch, 0);
+    if (e == hipSuccess) e = hipMemcpy(v.data(), st.wk.ovf, sizeof(int) * v.size(), hipMemcpyDeviceToHost);
+    for (int x : v) *overflow |= x != 0;
+    if (e == hipSuccess && *overflow) e = hipMemset(st.wk.ovf, 0, sizeof(int) * v.size());
+    return e;
+}
+
+hipError_t y355_head_overflow_take(const HeadState &st, int *dst_dev, hipStream_t s) {
+    const size_t bytes = sizeof(int) * (size_t)st.max_batch;
+    const hipError_t e = hipMemcpyAsync(dst_dev, st.wk.ovf, bytes, hipMemcpyDeviceToDevice, s);
+    return e != hipSuccess ? e : hipMemsetAsync(st.wk.ovf, 0, bytes, s);
+}
+
+hipError_t y355_head_get_candidates(const HeadState &st, hipStream_t s, int batch, float *boxes, float *scores, int32_t *cls) {
+    const size_t n = (size_t)st.N * batch;
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(boxes, st.cand_box, sizeof(float) * 4 * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(scores, st.cand_score, sizeof(float) * n, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cls, st.cand_cls, sizeof(int) * n, hipMemcpyDeviceToHost);
+    return e;
+}
+
+hipError_t y355_head_debug_counts(const HeadState &st, hipStream_t s, int batch, int32_t *count, int32_t *nedges) {
+    hipError_t e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(count, st.wk.count, sizeof(int) * batch, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(nedges, st.wk.nedges, sizeof(int) * 2 * batch, hipMemcpyDeviceToHost);
+    return e;
+}
+
+void y355_head_fill(HeadParams &p, const HeadState &st, float conf_thresh, float nms_thresh, int in_h, int in_w, float *out_box,
+                    float *out_score, int *out_cls, int *out_count, bool tap) {
+    p.in_w = (float)in_w;
+    p.in_h = (float)in_h;
+    p.conf_thresh = conf_thresh;
+    p.nms_thresh = nms_thresh;
+    p.cand_box = tap ? st.cand_box : nullptr;
+    p.cand_score = tap ? st.cand_score : nullptr;
+    p.cand_cls = tap ? st.cand_cls : nullptr;
+    p.max_det = st.max_det;
+    p.out_box = out_box;
+    p.out_score = out_score;
+    p.out_cls = out_cls;
+    p.out_count = out_count;
+}

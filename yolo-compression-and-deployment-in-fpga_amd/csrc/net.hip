@@ -8,6 +8,7 @@
 // kernels of netops.hip.
 #include "../../include/yolo355.h"
 #include "y355_common.h"
+#include "head_nms.h"
 #include "net_arch.h"
 
 #include <algorithm>
@@ -82,10 +83,8 @@ struct y355_net {
     std::vector<Tensor> T;
     std::vector<NLayer> L;
     char *w0_dev = nullptr;           // first-layer fragments
-    int predc = 0, N = 0, max_det = 0;
-    y355_head_ws ws{};
-    float *cand_box = nullptr, *cand_score = nullptr;
-    int *cand_cls = nullptr;
+    int predc = 0, N = 0;
+    HeadState head;                   // the head's workspace, max_det, candidate tap
     unsigned int *absmax_dev = nullptr;
     // int8 nets: activation exponents (value = q / 2^sa) of the input and of every tensor
     int sa_in = 0;
@@ -106,13 +105,9 @@ struct y355_net {
     int profile = 0;
     std::vector<hipEvent_t> ev;
     std::vector<void *> allocs;
-    // uint8 frame input (y355_net_forward_u8): BaseTransform constants (RGB order), the resize stage's tables for one source
-    // size, and the resized frames the conv1 / fused front-end routes read when the frames are not at the network size
-    NormU8 norm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
-    int *rs_tab = nullptr;
-    uint8_t *rs_frames = nullptr;
-    int rs_src_h = 0, rs_src_w = 0;
-    int *rs_tabs = nullptr;           // frame lists (y355_net_forward_frames): [max_batch][3 (H + W)], one set of tables per frame
+    // uint8 frame input (y355_net_forward_u8, y355_net_forward_frames): BaseTransform constants, the resize tables for one
+    // source size, and the resized frames the conv1 / fused front-end routes read when the frames are not at the network size
+    FrameStage stage;
     // calibration on the int8 graph (y355_net_calibrate): AveragedRangeTracker state of the network input [0] and of every
     // tensor [1 + t] (models/slim_yolo_v2.py:13-14), and one slot of maxima per op ([nops]: the input) on the device
     std::vector<float> trk_scale;
@@ -135,21 +130,6 @@ struct NetInput {
 
 static int in_kbytes(const y355_net *h, const OpDef &o);
 
-static int nmalloc(y355_net *h, void **p, size_t bytes, bool zero);
-// per-image cap of the returned detections: what the configuration asked for, within the candidates an image can have
-static void set_max_det(y355_net *h) {
-    const int ncand = std::min(h->N, h->ws.cap ? h->ws.cap : Y355_NMS_CAP);
-    h->max_det = (h->cfg.max_det <= 0 || h->cfg.max_det > ncand) ? ncand : h->cfg.max_det;
-}
-// the head workspace beyond the small route's arrays, for candidate capacity `cap` and `route` (y355_head_ws_large)
-static int head_ws_large(y355_net *h, int cap, int route) {
-    return y355_head_ws_large(
-        h->ws, h->N, h->cfg.max_batch, cap, route, [h](void **p, size_t bytes, bool zero) { return nmalloc(h, p, bytes, zero); },
-        [h](void *q) {
-            (void)hipFree(q);
-            h->allocs.erase(std::remove(h->allocs.begin(), h->allocs.end(), q), h->allocs.end());
-        });
-}
 static int nmalloc(y355_net *h, void **p, size_t bytes, bool zero) {
     HIPCHK(hipMalloc(p, bytes ? bytes : 16));
     h->allocs.push_back(*p);
@@ -162,6 +142,8 @@ extern "C" void y355_net_destroy(y355_net *h) {
     (void)hipSetDevice(h->cfg.device_id);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
     for (void *p : h->allocs) (void)hipFree(p);
+    y355_head_destroy(h->head);
+    y355_stage_destroy(h->stage);
     for (auto &e : h->ev) (void)hipEventDestroy(e);
     if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
     delete h;
@@ -202,7 +184,7 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     h->predc = predc;
     h->sa.assign(A.ntensors, 0);
     h->N = N;
-    set_max_det(h);
+    y355_stage_init(h->stage, cfg->height, cfg->width, cfg->max_batch, y355_hip_mem());
     if (!cfg->own_stream) h->stream = (hipStream_t)cfg->stream;
     else {
         if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
@@ -223,7 +205,7 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
         t.W = cfg->width / A.t[i].div;
         // a pixel is at least 32 bytes (the thin path of convg.hip)
         const int cq = h->bf ? 16 : 32;
-        t.Cpad = t.pred ? (t.C <= 64 ? 64 : t.C <= 128 ? 128 : 256) : (t.C + cq - 1) / cq * cq;
+        t.Cpad = t.pred ? y355_pred_channels(t.C) : (t.C + cq - 1) / cq * cq;
         t.pb = (size_t)t.Cpad * ((t.pred && h->bf) ? 4 : h->es);
         t.bytes = ((size_t)B * (t.H + 2 * t.halo) * (t.W + 2 * t.halo) + 64) * t.pb;
         rc = nmalloc(h, (void **)&t.dev, t.bytes, true);
@@ -297,7 +279,6 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
             if (!rc && !h->bf) rc = nmalloc(h, (void **)&h->fb2_dev, sizeof(int) * 32, true);
         }
     }
-    const size_t cap = Y355_NMS_CAP;
     if (!rc) rc = nmalloc(h, (void **)&h->absmax_dev, 16, true);
     if (!rc) rc = nmalloc(h, (void **)&h->ctr_dev, sizeof(Counters) * 2 * (A.nops + 1), true);
     if (!rc && !h->bf) rc = nmalloc(h, (void **)&h->cal_dev, sizeof(Counters) * (A.nops + 1), true);
@@ -306,25 +287,7 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     h->ctrs.base = h->ctr_dev;
     h->ctrs.n = A.nops + 1;
     h->ctrs.clean[0] = h->ctrs.clean[1] = true;
-    if (!rc) rc = nmalloc(h, &h->ws.cbox, sizeof(float) * 4 * cap * B, false);
-    if (!rc) rc = nmalloc(h, &h->ws.cscore, sizeof(float) * cap * B, false);
-    if (!rc) rc = nmalloc(h, &h->ws.ccls, sizeof(int) * cap * B, false);
-    if (!rc) rc = nmalloc(h, &h->ws.corig, sizeof(int) * cap * B, false);
-    if (!rc) rc = nmalloc(h, &h->ws.count, sizeof(int) * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.edges, sizeof(unsigned int) * (size_t)Y355_HEAD_EDGE_CAP * B, false);      // EDGE_CAP pairs per image
-    if (!rc) rc = nmalloc(h, &h->ws.nedges, sizeof(int) * 2 * (size_t)B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.binstart, sizeof(int) * (cap + 8) * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.astat, sizeof(float) * 4 * Y355_HEAD_MAXG * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.tiny, sizeof(int) * cap * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.ntiny, sizeof(int) * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.dbox, sizeof(float) * 4 * cap * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.dscore, sizeof(float) * cap * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.dcls, sizeof(int) * cap * B, true);
-    if (!rc) rc = nmalloc(h, &h->ws.ctype, sizeof(int) * cap * B, true);          // candidate groups
-    if (!rc) rc = head_ws_large(h, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO);
-    if (!rc) rc = nmalloc(h, (void **)&h->cand_box, sizeof(float) * 4 * N * B, false);
-    if (!rc) rc = nmalloc(h, (void **)&h->cand_score, sizeof(float) * N * B, false);
-    if (!rc) rc = nmalloc(h, (void **)&h->cand_cls, sizeof(int) * N * B, false);
+    if (!rc) rc = y355_head_create(h->head, N, B, cfg->max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, true, false, y355_hip_mem());
     if (!rc) {
         h->ev.resize(A.nops + 3);
         for (auto &e : h->ev)
@@ -344,15 +307,13 @@ extern "C" int y355_net_set_option(y355_net *h, int option, int value) {
     if (!h) return y355_fail(Y355_EINVAL, "null net");
     if (option == Y355_NET_OPT_MAX_CANDIDATES || option == Y355_NET_OPT_HEAD_ROUTE) {
         const bool is_cap = option == Y355_NET_OPT_MAX_CANDIDATES;
-        if (is_cap && value != Y355_NMS_CAP && (value < Y355_NMS_CAP || value > h->N))
-            return y355_fail(Y355_EINVAL, "Y355_NET_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)");
-        if (!is_cap && value != Y355_HEAD_ROUTE_AUTO && value != Y355_HEAD_ROUTE_LARGE)
-            return y355_fail(Y355_EINVAL, "Y355_NET_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)");
+        if (int rc = y355_head_check_option(h->N, is_cap, value,
+                                            is_cap ? "Y355_NET_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)"
+                                                   : "Y355_NET_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)"))
+            return rc;
         HIPCHK(hipSetDevice(h->cfg.device_id));
         HIPCHK(hipStreamSynchronize(h->stream));         // nothing in flight reads the arrays that go
-        const int cap = is_cap ? value : (h->ws.cap ? h->ws.cap : Y355_NMS_CAP), route = is_cap ? h->ws.route : value;
-        if (head_ws_large(h, cap, route)) return y355_fail(Y355_EHIP, "device allocation failed");
-        set_max_det(h);
+        if (y355_head_set_option(h->head, is_cap, value)) return y355_fail(Y355_EHIP, "device allocation failed");
         return 0;
     }
     if (option == Y355_NET_OPT_WORKGROUPS) {
@@ -377,8 +338,8 @@ extern "C" int y355_net_set_thresholds(y355_net *h, float conf, float nms) {
 
 extern "C" int y355_net_num_layers(y355_net *h) { return h ? h->arch->nlayers : Y355_EINVAL; }
 extern "C" int y355_net_num_tensors(y355_net *h) { return h ? h->arch->ntensors : Y355_EINVAL; }
-extern "C" int y355_net_max_candidates(y355_net *h) { return h ? (h->ws.cap ? h->ws.cap : Y355_NMS_CAP) : Y355_EINVAL; }
-extern "C" int y355_net_max_det(y355_net *h) { return h ? h->max_det : Y355_EINVAL; }
+extern "C" int y355_net_max_candidates(y355_net *h) { return h ? y355_head_capacity(h->head) : Y355_EINVAL; }
+extern "C" int y355_net_max_det(y355_net *h) { return h ? h->head.max_det : Y355_EINVAL; }
 extern "C" int y355_net_num_anchors_total(y355_net *h) { return h ? h->N : Y355_EINVAL; }
 
 extern "C" int y355_net_layer_shape(y355_net *h, int idx, int32_t *shape) {
@@ -782,7 +743,7 @@ template <class P>
 static void fill_input(P &p, const y355_net *h, const NetInput &in, int B) {
     p.x = in.x;
     p.x_u8 = in.u8;
-    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->norm.mean[c]; p.nstd[c] = h->norm.sd[c]; }
+    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->stage.norm.mean[c]; p.nstd[c] = h->stage.norm.sd[c]; }
     p.B = B;
     p.H = h->cfg.height;
     p.W = h->cfg.width;
@@ -905,7 +866,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
         L.route = (ki.wm * ki.wn == 8 ? Y355_ROUTE_GENERIC8 : Y355_ROUTE_GENERIC4) | rflags;
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * B, s);
     } else if (o.type == OP_INPUT) {
-        y355_launch_input(bf, in.x, in.u8, in.tab, in.sh, in.sw, h->norm, map_of(h->T[o.out]), B, bf ? 1.0f : std::ldexp(1.0f, h->sa_in),
+        y355_launch_input(bf, in.x, in.u8, in.tab, in.sh, in.sw, h->stage.norm, map_of(h->T[o.out]), B, bf ? 1.0f : std::ldexp(1.0f, h->sa_in),
                           h->ctr_dev + i, s);
     } else if (o.type == OP_POOL) {
         y355_launch_pool(bf, map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin * h->es, o.pool ? 1 : 2, s);
@@ -922,7 +883,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
     return 0;
 }
 
-static HeadParams net_head_params(y355_net *h, float *ob, float *os, int *oc, int *on) {
+static HeadParams net_head_params(y355_net *h, float *ob, float *os, int *oc, int *on, bool tap) {
     HeadParams p{};
     const ArchDef &A = *h->arch;
     p.nlev = A.nlev;
@@ -944,22 +905,9 @@ static HeadParams net_head_params(y355_net *h, float *ob, float *os, int *oc, in
     p.wh_mul = h->cfg.arch == Y355_ARCH_SLIM_V2 ? 16.0f : (h->cfg.arch == Y355_ARCH_YOLO_V2 ? 32.0f : 1.0f);
     // fp32 / multi-level heads: box sizes spread over many octaves per anchor -> group by area
     // (YOLOv3tiny int8, B = 128: NMS 1.08 -> 0.50 ms; SlimYOLOv2 bf16: 0.45 -> 0.32 ms)
-    p.group_by_area = 1;
+    y355_head_area_bins(p, h->T[A.pred_t[0]].H, h->T[A.pred_t[0]].W);
     p.pairs_wgs = h->tput_wgs > 0 ? 1 : 0;        // throughput mode: the pair walk holds one CU per image
-    p.Hb = std::min(16, h->T[A.pred_t[0]].H);
-    p.Wb = std::min(16, h->T[A.pred_t[0]].W);
-    p.in_w = (float)h->cfg.width;
-    p.in_h = (float)h->cfg.height;
-    p.conf_thresh = h->cfg.conf_thresh;
-    p.nms_thresh = h->cfg.nms_thresh;
-    p.cand_box = h->cand_box;
-    p.cand_score = h->cand_score;
-    p.cand_cls = h->cand_cls;
-    p.max_det = h->max_det;
-    p.out_box = ob;
-    p.out_score = os;
-    p.out_cls = oc;
-    p.out_count = on;
+    y355_head_fill(p, h->head, h->cfg.conf_thresh, h->cfg.nms_thresh, h->cfg.height, h->cfg.width, ob, os, oc, on, tap);
     return p;
 }
 
@@ -973,8 +921,8 @@ static int range_check(const y355_net *h, int batch, int frame_h = 1, int frame_
 // the stage in front of the first op: frames of another size (in.stage), or a frame list (every frame through the ragged
 // stage), resized into the net-owned buffer the first op reads
 static int pre_stage(y355_net *h, const NetInput &in, int batch) {
-    if (in.stage) y355_launch_resize_u8(in.stage, h->rs_frames, in.tab, batch, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stream);
-    if (in.list) y355_launch_resize_frames(in.list, batch, h->rs_frames, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+    if (in.stage) y355_launch_resize_u8(in.stage, h->stage.frames, in.tab, batch, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stream);
+    if (in.list) y355_launch_resize_frames(in.list, batch, h->stage.frames, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
     if (in.stage || in.list) HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1035,9 +983,8 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
         if (int rc = run_op(h, i, batch, in, PASS_FORWARD)) return rc;
     }
     if (prof) HIPCHK(hipEventRecord(h->ev[nops], h->stream));
-    HeadParams hp = net_head_params(h, boxes_dev, scores_dev, cls_dev, count_dev);
-    if (!(flags & Y355_F_TAP)) { hp.cand_box = nullptr; hp.cand_score = nullptr; hp.cand_cls = nullptr; }
-    y355_launch_head_nms(hp, batch, h->ws, h->stream, prof ? h->ev[nops + 1] : nullptr);
+    const HeadParams hp = net_head_params(h, boxes_dev, scores_dev, cls_dev, count_dev, (flags & Y355_F_TAP) != 0);
+    y355_launch_head_nms(hp, batch, h->head, h->stream, prof ? h->ev[nops + 1] : nullptr);
     HIPCHK(hipGetLastError());
     if (prof) HIPCHK(hipEventRecord(h->ev[nops + 2], h->stream));
     return 0;
@@ -1058,32 +1005,7 @@ extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int 
 // BaseTransform constants of the uint8 input, in the reference's BGR order (data/__init__.py:50), as y355_set_normalization
 extern "C" int y355_net_set_normalization(y355_net *h, const float *mean_bgr, const float *std_bgr) {
     if (!h || !mean_bgr || !std_bgr) return y355_fail(Y355_EINVAL, "null argument");
-    for (int c = 0; c < 3; ++c)
-        if (!(std_bgr[c] > 0.f)) return y355_fail(Y355_EINVAL, "std must be positive");
-    for (int c = 0; c < 3; ++c) {
-        h->norm.mean[c] = mean_bgr[2 - c];
-        h->norm.sd[c] = std_bgr[2 - c];
-    }
-    return 0;
-}
-
-// the resize stage's tables for frames of src_h x src_w (rebuilt when the source size changes) and, with `frames`, the
-// net-owned buffer of resized frames
-static int net_resize_tables(y355_net *h, int src_h, int src_w, bool frames) {
-    const int H = h->cfg.height, W = h->cfg.width;
-    if (!h->rs_tab)
-        if (int rc = nmalloc(h, (void **)&h->rs_tab, sizeof(int) * 3 * (size_t)(H + W), false)) return rc;
-    if (frames && !h->rs_frames)
-        if (int rc = nmalloc(h, (void **)&h->rs_frames, (size_t)h->cfg.max_batch * H * W * 3, false)) return rc;
-    if (h->rs_src_h != src_h || h->rs_src_w != src_w) {
-        std::vector<int> tab(3 * (size_t)(H + W));
-        y355_resize_tables(src_h, src_w, H, W, tab.data());
-        HIPCHK(hipStreamSynchronize(h->stream));          // a previous forward may still read the old tables
-        HIPCHK(hipMemcpy(h->rs_tab, tab.data(), sizeof(int) * tab.size(), hipMemcpyHostToDevice));
-        h->rs_src_h = src_h;
-        h->rs_src_w = src_w;
-    }
-    return 0;
+    return y355_stage_set_normalization(h->stage, mean_bgr, std_bgr);
 }
 
 // Camera frames as cv2 delivers them, uint8 HWC BGR [B][src_h][src_w][3], as the network's first input: BaseTransform
@@ -1101,11 +1023,12 @@ static int u8_input(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w
     in->sw = src_w;
     const bool fused = h->arch->ops[0].type == OP_INPUT;              // the input op resizes in its own load
     if (src_h == h->cfg.height && src_w == h->cfg.width && (fused || !align4 || ((uintptr_t)frames_dev & 3) == 0)) return 0;
-    if (int rc = net_resize_tables(h, src_h, src_w, !fused)) return rc;
-    in->tab = h->rs_tab;
-    if (!fused) {                                                   // staged: pre_stage resizes into rs_frames first
+    if (int rc = y355_stage_tables_for(h->stage, src_h, src_w, h->stream)) return rc;
+    in->tab = h->stage.tab;
+    if (!fused) {                                                   // staged: pre_stage resizes into the stage's frames first
+        if (int rc = y355_stage_need_frames(h->stage)) return rc;
         in->stage = frames_dev;
-        in->u8 = h->rs_frames;
+        in->u8 = h->stage.frames;
     }
     return 0;
 }
@@ -1127,41 +1050,26 @@ extern "C" int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int sr
     if (!h || !frames_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
     if (int rc = range_check(h, batch, src_h, src_w)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (int rc = net_resize_tables(h, src_h, src_w, false)) return rc;
-    y355_launch_resize_u8(frames_dev, out_dev, h->rs_tab, batch, src_h, src_w, h->cfg.height, h->cfg.width, h->stream);
+    if (int rc = y355_stage_tables_for(h->stage, src_h, src_w, h->stream)) return rc;
+    y355_launch_resize_u8(frames_dev, out_dev, h->stage.tab, batch, src_h, src_w, h->cfg.height, h->cfg.width, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
 
 // ---- frame lists: every frame with its own pointer, size and pitch (the reference's callers: one image at a time, each of
-// its own size).  All frames, those at the network size included, go through the ragged stage of resize.hip into rs_frames;
-// the forward / calibration step then is the same-size uint8 path on that buffer (in.u8 = rs_frames, no table, no stage).
+// its own size).  All frames, those at the network size included, go through the ragged stage of resize.hip into the stage's frames;
+// the forward / calibration step then is the same-size uint8 path on that buffer (in.u8 = the frames, no table, no stage).
 // The stage builds its tables on the device and takes the descriptors as kernel arguments: nothing is uploaded, nothing
 // waits, whatever the sizes of the previous call were.
-static int frames_check(const y355_net *h, const y355_frame *frames, int batch) {
-    if (int rc = range_check(h, batch)) return rc;
-    for (int i = 0; i < batch; ++i) {
-        const y355_frame &f = frames[i];
-        if (!f.data_dev) return y355_fail(Y355_EINVAL, "null frame pointer");
-        if (int rc = range_check(h, batch, f.height, f.width)) return rc;
-        if (f.row_bytes != 0 && f.row_bytes < 3 * (int64_t)f.width) return y355_fail(Y355_EINVAL, "row_bytes below width * 3");
-    }
-    return 0;
-}
-
-// the stage's buffers, allocated at the first list call of a handle (frames: rs_frames is needed)
+// the stage's buffers, allocated at the first list call of a handle (frames: a forward / calibration step follows)
 static int net_list_buffers(y355_net *h, bool frames) {
-    const int H = h->cfg.height, W = h->cfg.width;
-    if (!h->rs_tabs)
-        if (int rc = nmalloc(h, (void **)&h->rs_tabs, sizeof(int) * 3 * (size_t)(H + W) * h->cfg.max_batch, false)) return rc;
-    if (frames && !h->rs_frames)
-        if (int rc = nmalloc(h, (void **)&h->rs_frames, (size_t)h->cfg.max_batch * H * W * 3, false)) return rc;
-    return 0;
+    if (int rc = y355_stage_need_list(h->stage)) return rc;
+    return frames ? y355_stage_need_frames(h->stage) : 0;
 }
 
 static NetInput list_input(const y355_net *h, const y355_frame *frames) {
     NetInput in;
-    in.u8 = h->rs_frames;
+    in.u8 = h->stage.frames;
     in.sh = h->cfg.height;
     in.sw = h->cfg.width;
     in.list = frames;
@@ -1171,7 +1079,7 @@ static NetInput list_input(const y355_net *h, const y355_frame *frames) {
 extern "C" int y355_net_forward_frames(y355_net *h, const y355_frame *frames, int batch, int flags, float *boxes_dev,
                                        float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !frames || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = frames_check(h, frames, batch)) return rc;
+    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (!h->bf)
         if (int rc = refresh_i8(h)) return rc;
@@ -1182,10 +1090,10 @@ extern "C" int y355_net_forward_frames(y355_net *h, const y355_frame *frames, in
 // parity tap of the ragged stage: the list -> out_dev [batch][H][W][3] at the network size, on the net's stream
 extern "C" int y355_net_resize_frames(y355_net *h, const y355_frame *frames, int batch, uint8_t *out_dev) {
     if (!h || !frames || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = frames_check(h, frames, batch)) return rc;
+    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (int rc = net_list_buffers(h, false)) return rc;
-    y355_launch_resize_frames(frames, batch, out_dev, h->rs_tabs, h->cfg.height, h->cfg.width, h->stream);
+    y355_launch_resize_frames(frames, batch, out_dev, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1196,7 +1104,7 @@ extern "C" int y355_net_scale_boxes(y355_net *h, float *boxes_dev, const int32_t
     if (!h || !boxes_dev || !count_dev || !wh_dev) return y355_fail(Y355_EINVAL, "null argument");
     if (int rc = range_check(h, batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    y355_launch_scale_boxes(boxes_dev, count_dev, wh_dev, batch, h->max_det, h->stream);
+    y355_launch_scale_boxes(boxes_dev, count_dev, wh_dev, batch, h->head.max_det, h->stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -1205,10 +1113,7 @@ extern "C" int y355_net_get_candidates(y355_net *h, int batch, float *boxes, flo
     if (!h || !boxes || !scores || !cls) return y355_fail(Y355_EINVAL, "null argument");
     if (int rc = range_check(h, batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(boxes, h->cand_box, sizeof(float) * 4 * h->N * batch, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(scores, h->cand_score, sizeof(float) * h->N * batch, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(cls, h->cand_cls, sizeof(int) * h->N * batch, hipMemcpyDeviceToHost));
+    HIPCHK(y355_head_get_candidates(h->head, h->stream, batch, boxes, scores, cls));
     return 0;
 }
 
@@ -1285,14 +1190,8 @@ extern "C" int y355_net_counters(y355_net *h, int64_t *saturated) {
 // image passed conf_thresh (the excess was dropped); synchronous; clears the flags
 extern "C" int y355_net_overflow(y355_net *h, int *overflow) {
     if (!h || !overflow) return y355_fail(Y355_EINVAL, "null argument");
-    *overflow = 0;
-    if (!h->ws.ovf) return 0;
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    std::vector<int> v(h->cfg.max_batch, 0);
-    HIPCHK(hipMemcpy(v.data(), h->ws.ovf, sizeof(int) * v.size(), hipMemcpyDeviceToHost));
-    for (int x : v) *overflow |= x != 0;
-    if (*overflow) HIPCHK(hipMemset(h->ws.ovf, 0, sizeof(int) * v.size()));
+    HIPCHK(y355_head_overflow_read(h->head, h->stream, overflow));
     return 0;
 }
 
@@ -1301,9 +1200,7 @@ extern "C" int y355_net_overflow(y355_net *h, int *overflow) {
 extern "C" int y355_net_debug_nms(y355_net *h, int batch, int32_t *count, int32_t *nedges) {
     if (!h || !count || !nedges || batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "bad argument");
     HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    HIPCHK(hipMemcpy(count, h->ws.count, sizeof(int) * batch, hipMemcpyDeviceToHost));
-    HIPCHK(hipMemcpy(nedges, h->ws.nedges, sizeof(int) * 2 * batch, hipMemcpyDeviceToHost));
+    HIPCHK(y355_head_debug_counts(h->head, h->stream, batch, count, nedges));
     return 0;
 }
 
@@ -1443,7 +1340,7 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
         y355_launch_absmax(in.x, (size_t)B * 3 * h->cfg.height * h->cfg.width, slot(nops), s);
     } else {
         const bool staged = in.stage != nullptr || A.ops[0].type != OP_INPUT;      // in.u8 is at the network size
-        y355_launch_absmax_u8(in.u8, staged ? nullptr : in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, h->norm, slot(nops), s);
+        y355_launch_absmax_u8(in.u8, staged ? nullptr : in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stage.norm, slot(nops), s);
     }
     float m = 0.f;
     if (int rc = cal_read_u32(h, nops, &m)) return rc;
@@ -1574,7 +1471,7 @@ extern "C" int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int
 extern "C" int y355_net_calibrate_frames(y355_net *h, const y355_frame *frames, int batch, int freeze, double momentum,
                                          int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n) {
     if (int rc = cal_check(h, frames, batch, momentum, n)) return rc;
-    if (int rc = frames_check(h, frames, batch)) return rc;
+    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
     HIPCHK(hipSetDevice(h->cfg.device_id));
     if (int rc = net_list_buffers(h, true)) return rc;
     return net_calibrate(h, list_input(h, frames), batch, freeze, momentum, sa_in_out, sa_out, max_out);
@@ -1603,29 +1500,15 @@ extern "C" int y355_head_f32_ex(int device_id, int nlev, const float *const *pre
         N += hs[l] * ws[l] * num_anchors;
     }
     if (N > Y355_NMS_MAX_CAP) return y355_fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
-    if (route != Y355_HEAD_ROUTE_AUTO && route != Y355_HEAD_ROUTE_LARGE) return y355_fail(Y355_EINVAL, "head route: 0 (auto) or 1 (large)");
-    if (max_candidates != Y355_NMS_CAP && (max_candidates < Y355_NMS_CAP || max_candidates > N))
-        return y355_fail(Y355_EINVAL, "max_candidates: 4096 .. min(anchors per image, 65536)");
+    if (int rc = y355_head_check_option(N, false, route, "head route: 0 (auto) or 1 (large)")) return rc;
+    if (int rc = y355_head_check_option(N, true, max_candidates, "max_candidates: 4096 .. min(anchors per image, 65536)")) return rc;
     if ((cand_box || cand_score || cand_cls) && !(cand_box && cand_score && cand_cls))
         return y355_fail(Y355_EINVAL, "the candidate tap takes all three arrays or none");
-    const bool large = N > Y355_NMS_CAP || route == Y355_HEAD_ROUTE_LARGE;          // threshold-then-compact in front of the sort (head_nms.hip)
-    const int ncand = std::min(N, max_candidates);
-    if (max_det > ncand) max_det = ncand;
     HIPCHK(hipSetDevice(device_id));
     if (int e = y355_prepare_kernels()) return e;
-    std::vector<void *> bufs;
-    auto alloc = [&](void **p, size_t bytes, bool zero) -> int {
-        if (hipMalloc(p, bytes ? bytes : 16) != hipSuccess) return 1;
-        bufs.push_back(*p);
-        if (zero && hipMemset(*p, 0, bytes ? bytes : 16) != hipSuccess) return 1;
-        return 0;
-    };
-    auto release = [&]() { for (void *q : bufs) (void)hipFree(q); };
-    const int B = batch;
-    const size_t cap = Y355_NMS_CAP;
-    const int cpad = predc <= 64 ? 64 : predc <= 128 ? 128 : 256;
-    y355_head_ws w{};
-    int rc = 0;
+    const int B = batch, cpad = y355_pred_channels(predc);
+    HeadState st;
+    int rc = y355_head_create(st, N, B, max_det, max_candidates, route, cand_box != nullptr, true, y355_hip_mem());
     float *d_pred[3] = {nullptr, nullptr, nullptr};
     for (int l = 0; l < nlev && !rc; ++l) {
         // NCHW -> NHWC with cpad channels
@@ -1636,38 +1519,13 @@ extern "C" int y355_head_f32_ex(int device_id, int nlev, const float *const *pre
                 const float *src = pred[l] + ((size_t)b * predc + c) * px;
                 for (size_t i = 0; i < px; ++i) t[((size_t)b * px + i) * cpad + c] = src[i];
             }
-        rc = alloc((void **)&d_pred[l], t.size() * 4 + 1024, false);
+        if (hipMalloc((void **)&d_pred[l], t.size() * 4 + 1024) != hipSuccess) rc = 1;
         if (!rc && hipMemcpy(d_pred[l], t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = 1;
     }
-    float *d_box = nullptr, *d_score = nullptr;
-    int *d_cls = nullptr, *d_count = nullptr;
-    if (!rc) rc = alloc(&w.cbox, sizeof(float) * 4 * cap * B, false);
-    if (!rc) rc = alloc(&w.cscore, sizeof(float) * cap * B, false);
-    if (!rc) rc = alloc(&w.ccls, sizeof(int) * cap * B, false);
-    if (!rc) rc = alloc(&w.corig, sizeof(int) * cap * B, false);
-    if (!rc) rc = alloc(&w.count, sizeof(int) * B, true);
-    if (!rc) rc = alloc(&w.edges, sizeof(unsigned int) * (size_t)Y355_HEAD_EDGE_CAP * B, false);
-    if (!rc) rc = alloc(&w.nedges, sizeof(int) * 2 * (size_t)B, true);
-    if (!rc) rc = alloc(&w.binstart, sizeof(int) * (cap + 8) * B, true);
-    if (!rc) rc = alloc(&w.astat, sizeof(float) * 4 * Y355_HEAD_MAXG * B, true);
-    if (!rc) rc = alloc(&w.tiny, sizeof(int) * cap * B, true);
-    if (!rc) rc = alloc(&w.ntiny, sizeof(int) * B, true);
-    if (!rc) rc = alloc(&w.dbox, sizeof(float) * 4 * cap * B, true);
-    if (!rc) rc = alloc(&w.dscore, sizeof(float) * cap * B, true);
-    if (!rc) rc = alloc(&w.dcls, sizeof(int) * cap * B, true);
-    if (!rc) rc = alloc(&w.ctype, sizeof(int) * cap * B, true);
-    if (!rc) rc = y355_head_ws_large(w, N, B, max_candidates, route, alloc, [](void *) {});
-    float *d_cbox = nullptr, *d_cscore = nullptr;
-    int *d_ccls = nullptr;
-    if (cand_box) {
-        if (!rc) rc = alloc((void **)&d_cbox, sizeof(float) * 4 * (size_t)N * B, false);
-        if (!rc) rc = alloc((void **)&d_cscore, sizeof(float) * (size_t)N * B, false);
-        if (!rc) rc = alloc((void **)&d_ccls, sizeof(int) * (size_t)N * B, false);
-    }
-    if (!rc) rc = alloc((void **)&d_box, sizeof(float) * 4 * (size_t)max_det * B, true);
-    if (!rc) rc = alloc((void **)&d_score, sizeof(float) * (size_t)max_det * B, true);
-    if (!rc) rc = alloc((void **)&d_cls, sizeof(int) * (size_t)max_det * B, true);
-    if (!rc) rc = alloc((void **)&d_count, sizeof(int) * B, true);
+    auto release = [&]() {
+        for (float *q : d_pred) (void)hipFree(q);
+        y355_head_destroy(st);
+    };
     if (rc) { release(); return y355_fail(Y355_EHIP, "device allocation failed"); }
     HeadParams p{};
     p.nlev = nlev;
@@ -1685,39 +1543,19 @@ extern "C" int y355_head_f32_ex(int device_id, int nlev, const float *const *pre
     p.A = num_anchors;
     p.C = num_classes;
     p.wh_mul = wh_mul;
-    p.group_by_area = 1;
-    p.Hb = std::min(16, hs[0]);
-    p.Wb = std::min(16, ws[0]);
-    p.in_w = (float)in_w;
-    p.in_h = (float)in_h;
-    p.conf_thresh = conf_thresh;
-    p.nms_thresh = nms_thresh;
-    p.max_det = max_det;
-    p.out_box = d_box;
-    p.out_score = d_score;
-    p.out_cls = d_cls;
-    p.out_count = d_count;
-    p.cand_box = d_cbox;
-    p.cand_score = d_cscore;
-    p.cand_cls = d_ccls;
-    y355_launch_head_nms(p, B, w, 0, nullptr);
+    y355_head_area_bins(p, hs[0], ws[0]);
+    y355_head_fill(p, st, conf_thresh, nms_thresh, in_h, in_w, st.o_box, st.o_score, st.o_cls, st.o_count, true);
+    y355_launch_head_nms(p, B, st, 0, nullptr);
+    const size_t md = (size_t)st.max_det;
     hipError_t e = hipGetLastError();
     if (e == hipSuccess) e = hipDeviceSynchronize();
-    if (e == hipSuccess) e = hipMemcpy(boxes, d_box, sizeof(float) * 4 * (size_t)max_det * B, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(scores, d_score, sizeof(float) * (size_t)max_det * B, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(cls, d_cls, sizeof(int) * (size_t)max_det * B, hipMemcpyDeviceToHost);
-    if (e == hipSuccess) e = hipMemcpy(count, d_count, sizeof(int) * B, hipMemcpyDeviceToHost);
-    if (e == hipSuccess && cand_box) {
-        e = hipMemcpy(cand_box, d_cbox, sizeof(float) * 4 * (size_t)N * B, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(cand_score, d_cscore, sizeof(float) * (size_t)N * B, hipMemcpyDeviceToHost);
-        if (e == hipSuccess) e = hipMemcpy(cand_cls, d_ccls, sizeof(int) * (size_t)N * B, hipMemcpyDeviceToHost);
-    }
-    bool overflow = false;
-    if (e == hipSuccess && large) {
-        std::vector<int> ovf(B, 0);
-        e = hipMemcpy(ovf.data(), w.ovf, sizeof(int) * B, hipMemcpyDeviceToHost);
-        for (int v : ovf) overflow |= v != 0;
-    }
+    if (e == hipSuccess) e = hipMemcpy(boxes, st.o_box, sizeof(float) * 4 * md * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(scores, st.o_score, sizeof(float) * md * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(cls, st.o_cls, sizeof(int) * md * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess) e = hipMemcpy(count, st.o_count, sizeof(int) * B, hipMemcpyDeviceToHost);
+    if (e == hipSuccess && cand_box) e = y355_head_get_candidates(st, 0, B, cand_box, cand_score, cand_cls);
+    int overflow = 0;
+    if (e == hipSuccess) e = y355_head_overflow_read(st, 0, &overflow);
     release();
     if (overflow) return y355_fail(Y355_EINVAL, y355_head_overflow_message(max_candidates));
     if (e != hipSuccess) return y355_fail(Y355_EHIP, std::string("head: ") + hipGetErrorString(e));

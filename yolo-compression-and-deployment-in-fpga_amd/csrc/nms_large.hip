@@ -324,49 +324,3 @@ void y355_launch_nms_large(const HeadParams &p, const HeadWork &wk, int batch, h
     hipLaunchKernelGGL(resolve_large_kernel, dim3(NMS_LG, batch), dim3(1024), 0, s, wk, p.C, p.nms_thresh);
     hipLaunchKernelGGL(emit_large_kernel, dim3(batch), dim3(1024), 0, s, p, wk);
 }
-
-// ---- the workspace the large route (and the raw decode in front of it) adds to a head's
-int y355_head_ws_large(y355_head_ws &ws, int N, int B, int cap, int route, const std::function<int(void **, size_t, bool)> &alloc,
-                       const std::function<void(void *)> &release) {
-    static_assert(Y355_NMS_MAX_CAP <= 65536 && Y355_NMS_MAX_CLASSES <= 256, "sort_large_kernel packs class << 16 | rank, 8 + 16 bits");
-    // everything new is allocated first: a failure frees it and leaves ws as it was, usable at its old capacity and route
-    y355_head_ws nw = ws;
-    nw.lbox = nw.lscore = nw.lcls = nw.lcount = nw.lsort = nw.lkbox = nw.lkeep = nullptr;
-    nw.cap = cap;
-    nw.route = route;
-    std::vector<void *> fresh;
-    auto get = [&](void **p, size_t bytes) -> int {
-        const int e = alloc(p, bytes, true);
-        if (!e) fresh.push_back(*p);
-        return e;
-    };
-    int rc = 0;
-    const bool raw = N > Y355_NMS_CAP || route == 1, big = cap > Y355_NMS_CAP || route == 1;
-    if (raw && !nw.rbox) {
-        nw.rstride = (N + 3) / 4 * 4;
-        if (!rc) rc = get(&nw.rbox, sizeof(float) * 4 * (size_t)nw.rstride * B);
-        if (!rc) rc = get(&nw.rscore, sizeof(float) * (size_t)nw.rstride * B);
-        if (!rc) rc = get(&nw.rcls, sizeof(int) * (size_t)nw.rstride * B);
-        if (!rc) rc = get(&nw.rcount, sizeof(int) * B);
-        if (!rc) rc = get(&nw.ovf, sizeof(int) * B);
-    }
-    if (big) {
-        const size_t c = (size_t)cap;
-        if (!rc) rc = get(&nw.lbox, sizeof(float) * 4 * c * B);
-        if (!rc) rc = get(&nw.lscore, sizeof(float) * c * B);
-        if (!rc) rc = get(&nw.lcls, sizeof(int) * c * B);
-        if (!rc) rc = get(&nw.lcount, sizeof(int) * B);
-        if (!rc) rc = get(&nw.lsort, sizeof(uint2) * 2 * c * B);
-        if (!rc) rc = get(&nw.lkbox, sizeof(float) * 4 * c * B);
-        if (!rc) rc = get(&nw.lkeep, c * B);
-    }
-    if (rc) {
-        for (void *q : fresh) release(q);
-        return rc;
-    }
-    void *old[] = {ws.lbox, ws.lscore, ws.lcls, ws.lcount, ws.lsort, ws.lkbox, ws.lkeep};
-    for (void *q : old)
-        if (q) release(q);
-    ws = nw;
-    return 0;
-}

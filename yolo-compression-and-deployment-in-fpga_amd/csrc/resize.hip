@@ -141,3 +141,71 @@ void y355_launch_resize_frames(const y355_frame *frames, int n, uint8_t *dst, in
         else hipLaunchKernelGGL(resize_frames_kernel<false>, grid, dim3(256), 0, s, ch, out, tab, dh, dw);
     }
 }
+
+// ---- the stage's host state (FrameStage, y355_common.h)
+int y355_fail(int code, const std::string &msg);
+
+void y355_stage_init(FrameStage &st, int H, int W, int max_batch, const DevMem &mem) {
+    st = FrameStage{};
+    st.H = H;
+    st.W = W;
+    st.max_batch = max_batch;
+    st.mem = mem;
+}
+
+void y355_stage_destroy(FrameStage &st) {
+    for (void *q : st.allocs) st.mem.release(q);
+    st.allocs.clear();
+    st.tab = st.tabs = nullptr;
+    st.frames = nullptr;
+    st.src_h = st.src_w = 0;
+}
+
+int y355_stage_set_normalization(FrameStage &st, const float *mean_bgr, const float *std_bgr) {
+    for (int c = 0; c < 3; ++c)
+        if (!(std_bgr[c] > 0.f)) return y355_fail(Y355_EINVAL, "std must be positive");
+    for (int c = 0; c < 3; ++c) {
+        st.norm.mean[c] = mean_bgr[2 - c];
+        st.norm.sd[c] = std_bgr[2 - c];
+    }
+    return 0;
+}
+
+template <typename T>
+static int stage_need(FrameStage &st, T **p, size_t bytes) {
+    if (*p) return 0;
+    void *q = nullptr;
+    if (int rc = st.mem.alloc(&q, bytes, false)) return rc;
+    st.allocs.push_back(q);
+    *p = (T *)q;
+    return 0;
+}
+int y355_stage_need_frames(FrameStage &st) { return stage_need(st, &st.frames, (size_t)st.max_batch * st.H * st.W * 3); }
+int y355_stage_need_list(FrameStage &st) { return stage_need(st, &st.tabs, sizeof(int) * 3 * (size_t)(st.H + st.W) * st.max_batch); }
+
+int y355_stage_tables_for(FrameStage &st, int src_h, int src_w, hipStream_t s) {
+    std::vector<int> tab(3 * (size_t)(st.H + st.W));
+    if (int rc = stage_need(st, &st.tab, sizeof(int) * tab.size())) return rc;
+    if (st.src_h == src_h && st.src_w == src_w) return 0;
+    y355_resize_tables(src_h, src_w, st.H, st.W, tab.data());
+    // (the upload waits for s: a previous forward may still read the old tables)
+    if (int rc = st.mem.upload(st.tab, tab.data(), sizeof(int) * tab.size(), s)) {
+        st.src_h = st.src_w = 0;        // the old tables may be partly overwritten
+        return rc;
+    }
+    st.src_h = src_h;
+    st.src_w = src_w;
+    return 0;
+}
+
+int y355_frames_check(const y355_frame *frames, int batch, int max_batch) {
+    if (!frames) return y355_fail(Y355_EINVAL, "null frame array");
+    if (batch < 1 || batch > max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
+    for (int i = 0; i < batch; ++i) {
+        const y355_frame &f = frames[i];
+        if (!f.data_dev) return y355_fail(Y355_EINVAL, "null frame pointer");
+        if (f.height < 1 || f.width < 1 || f.height > 16384 || f.width > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
+        if (f.row_bytes != 0 && f.row_bytes < 3 * (int64_t)f.width) return y355_fail(Y355_EINVAL, "row_bytes below width * 3");
+    }
+    return 0;
+}

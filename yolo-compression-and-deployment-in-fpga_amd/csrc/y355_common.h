@@ -4,6 +4,7 @@
 #include <stdint.h>
 #include <functional>
 #include <string>
+#include <vector>
 
 #include <hip/hip_ext.h>
 
@@ -325,6 +326,16 @@ void y355_launch_conv1(const Conv1Params &p, hipStream_t s);
 void y355_conv1_tiles(int H, int W, int *tx, int *ty);
 void y355_pack_conv1(const int8_t *q_w /*[16][3][3][3]*/, int8_t *dst /*1024*/);
 
+// How a piece of host-side state (HeadState of head_nms.h, FrameStage below) gets and fills device memory: the HIP calls in the
+// handles (y355_hip_mem, head_state.hip), the host heap with a failure at the k-th allocation in host_state_check.cpp.
+struct DevMem {
+    std::function<int(void **p, size_t bytes, bool zero)> alloc;   // != 0: failure, y355_fail holds the message
+    std::function<void(void *p)> release;
+    // host -> device copy once everything enqueued on s has run (what s has in flight may still read dst); != 0: failure
+    std::function<int(void *dst, const void *src, size_t bytes, hipStream_t s)> upload;
+};
+const DevMem &y355_hip_mem(void);
+
 // One prediction map of the detection head.  Channel layout [A obj | A*C cls | A*4 txtytwth],
 // anchor-major (models/slim_yolo_v2.py:330-341, models/tiny_yolo_v3.py:202-222).
 struct HeadLevel {
@@ -360,38 +371,13 @@ struct HeadParams {
 #define Y355_HEAD_EDGE_CAP 28672   // suppressing pairs per image the NMS edge list holds (more: the sorted fallback walk)
 #define Y355_HEAD_MAXA 16
 #define Y355_HEAD_MAXG 32   // candidate groups of the NMS sort: anchor types, area octaves, or -- heads with 3 .. 32 classes -- the classes
-// head_nms.hip workspace, per image: cbox f32[CAP][4], cscore f32[CAP], ccls i32[CAP], corig i32[CAP],
-// count i32, edges u32[Y355_HEAD_EDGE_CAP] (suppressing pairs), nedges i32[2] (count, overflow flag),
-// binstart i32[CAP+8], astat f32[Y355_HEAD_MAXG][4], tiny i32[CAP], ntiny i32, ctype i32[CAP] (candidate group),
-// dbox f32[CAP][4] / dscore f32[CAP] / dcls i32[CAP] (decode of every anchor).
-// Heads with more than Y355_NMS_CAP anchors per image also need rbox f32[rstride][4], rscore f32[rstride], rcls i32[rstride]
-// (raw decode, rstride >= anchors per image), rcount i32, ovf i32 (more than CAP anchors passed conf_thresh: zero it before
-// a forward, check it after).
-struct y355_head_ws { void *cbox, *cscore, *ccls, *corig, *count, *edges, *nedges, *binstart, *astat, *tiny, *ntiny, *ctype, *dbox, *dscore, *dcls;
-                      void *rbox = nullptr, *rscore = nullptr, *rcls = nullptr, *rcount = nullptr, *ovf = nullptr; int rstride = 0;
-                      // large route (nms_large.hip; y355_head_ws_large fills these): candidate capacity (0 = Y355_NMS_CAP) and route
-                      // (0 = by the image's candidate count, 1 = every image takes the large route)
-                      void *lbox = nullptr, *lscore = nullptr, *lcls = nullptr, *lcount = nullptr, *lsort = nullptr, *lkbox = nullptr,
-                           *lkeep = nullptr; int cap = 0, route = 0; };
 #define Y355_NMS_MAX_CAP (16 * Y355_NMS_CAP)   // most anchors / candidates per image of any head: a rank fits 16 bits
 #define Y355_NMS_MAX_CLASSES 256              // the large route sorts on 8 bits of the class (every head has A * (5 + C) <= 256)
-// (Re)allocates what a head of N anchors per image needs beyond the arrays above for candidate capacity `cap` (Y355_NMS_CAP ..
-// Y355_NMS_MAX_CAP) and `route`: the raw decode arrays (N > Y355_NMS_CAP, or the large route forced) and the large route's
-// lists (cap > Y355_NMS_CAP, or forced).  alloc(ptr, bytes, zero) != 0: failure; release(ptr) frees an earlier array.
-// The caller has synchronised the stream the head runs on.  A failure (non-zero) leaves ws unchanged.
-int y355_head_ws_large(y355_head_ws &ws, int N, int B, int cap, int route, const std::function<int(void **, size_t, bool)> &alloc,
-                       const std::function<void(void *)> &release);
 // the loud failure of a forward in which more anchors of an image passed conf_thresh than the candidate capacity holds
 inline std::string y355_head_overflow_message(int cap) {
     return "more than " + std::to_string(cap) + " anchors of an image pass conf_thresh: raise the threshold" +
            (cap < Y355_NMS_MAX_CAP ? std::string(cap > Y355_NMS_CAP ? " or the candidate capacity" : "") : std::string());
 }
-int y355_prepare_head(void);
-// decode, candidate sort, pruned pair walk (edge list), rounds + output.  `mid` (optional) is recorded
-// between the candidate sort and the pair walk.
-// `kev` (optional): start / end events of the four launches decode, candidate sort, pair walk, rounds + output
-void y355_launch_head_nms(const HeadParams &p, int batch, const y355_head_ws &ws, hipStream_t s, hipEvent_t mid,
-                          hipEvent_t (*kev)[2] = nullptr);
 void y355_launch_absmax(const float *x, size_t n, unsigned int *out_bits, hipStream_t s);
 // uint8 HWC BGR frames -> fp32 NCHW RGB, BaseTransform arithmetic (data/__init__.py:30-56, test.py:79)
 void y355_launch_normalize_u8(const uint8_t *frames, float *x, int B, int H, int W, const float *mean_rgb, const float *std_rgb,
@@ -436,8 +422,34 @@ __device__ __forceinline__ void y355_resize_px(const uint8_t *s, const int *tab,
 struct y355_frame;
 void y355_launch_resize_frames(const y355_frame *frames, int n, uint8_t *dst, int *tabs, int dh, int dw, hipStream_t s);
 
-// ---- element-wise ops of the y355_net graphs (netops.hip): bf selects the bf16 form, else int8
+// ---- the uint8 frame stage's host state, one per handle (y355_engine, y355_net; resize.hip): BaseTransform's constants and
+// the buffers of the two resize routes, each allocated when its route first needs it
 struct NormU8 { float mean[3], sd[3]; };        // BaseTransform constants per RGB channel (data/__init__.py:50 lists them in BGR order)
+struct FrameStage {
+    NormU8 norm{{0.485f, 0.456f, 0.406f}, {0.229f, 0.224f, 0.225f}};
+    int H = 0, W = 0, max_batch = 0;            // the network size every frame is resized to
+    int *tab = nullptr;             // same-size frames: [xofs W | xa 2W | yofs H | yb 2H] for sources of src_h x src_w (0: none yet)
+    int src_h = 0, src_w = 0;
+    uint8_t *frames = nullptr;      // [max_batch][H][W][3]: the frames at the network size, where a forward reads them from here
+    int *tabs = nullptr;            // frame lists: [max_batch][3 (H + W)], one set of tables per frame, built on the device; the
+                                    // list route never touches tab / src_h / src_w
+    DevMem mem;
+    std::vector<void *> allocs;
+};
+void y355_stage_init(FrameStage &st, int H, int W, int max_batch, const DevMem &mem);
+void y355_stage_destroy(FrameStage &st);
+// mean / std in the reference's BGR order; a non-positive std fails (Y355_EINVAL) and leaves every channel as it was
+int y355_stage_set_normalization(FrameStage &st, const float *mean_bgr, const float *std_bgr);
+// st.tab holds the tables for same-size frames of src_h x src_w: rebuilt and uploaded (behind what s has in flight) only when
+// the size differs from the cached one; a failed upload forgets the cached size
+int y355_stage_tables_for(FrameStage &st, int src_h, int src_w, hipStream_t s);
+int y355_stage_need_frames(FrameStage &st);     // st.frames
+int y355_stage_need_list(FrameStage &st);       // st.tabs
+// the rules of a frame list (y355_frame of include/yolo355.h), in this order: the array, the batch, then per frame its pointer,
+// its size (1 .. 16384 each way) and its row pitch
+int y355_frames_check(const y355_frame *frames, int batch, int max_batch);
+
+// ---- element-wise ops of the y355_net graphs (netops.hip): bf selects the bf16 form, else int8
 struct NetMap { char *dev; int H, W, pb; };     // NHWC tensor with a one-pixel halo, [B][H + 2][W + 2][pb bytes]
 void y355_launch_pool(bool bf, const NetMap &in, const NetMap &out, int B, int cbytes, int stride, hipStream_t s);      // 2x2 max, first cbytes of a pixel
 // bilinear x2 (align_corners) of C channels into byte out_off of out's pixels; int8: times rescale, and only where y355_upsample_i8_ok

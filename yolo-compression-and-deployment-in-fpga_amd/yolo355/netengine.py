@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _ffi, framelist
-from .engine import _require_gpu
+from .engine import _overflow_message, _require_gpu
 
 ARCH = {"slim_yolo_v2": _ffi.ARCH_SLIM_V2, "tiny_yolo_v3": _ffi.ARCH_TINY_V3, "yolo_v2": _ffi.ARCH_YOLO_V2,
         "yolo_v3": _ffi.ARCH_YOLO_V3, "yolo_v3_spp": _ffi.ARCH_YOLO_V3_SPP}
@@ -199,8 +199,7 @@ class Net:
             self.scale_boxes(ob, on, sizes_wh, B)
         n = on[:B].cpu().numpy()
         if self.overflow():
-            raise _ffi.Y355Error(-1, "more than %d anchors of an image pass conf_thresh: raise the threshold%s"
-                                 % (self.max_candidates, " or max_candidates" if self.max_candidates > 4096 else ""))
+            raise _ffi.Y355Error(-1, _overflow_message(self.max_candidates))
         boxes, scores, cls = ob[:B].cpu().numpy(), os_[:B].cpu().numpy(), oc[:B].cpu().numpy()
         return [(boxes[i, :n[i]].copy(), scores[i, :n[i]].copy(), cls[i, :n[i]].astype(np.int64))
                 for i in range(B)]

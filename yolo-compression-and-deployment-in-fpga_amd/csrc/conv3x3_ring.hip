@@ -15,7 +15,7 @@
 //   * the LDS that buys this comes from the epilogue: the int8 output tile is staged in the slab
 //     slot that just died (in two passes where it is larger than a slot), not in its own buffer.
 // Same math, tile geometry, weight packing and epilogue arithmetic as conv3x3.hip.
-#include "y355_common.h"
+#include "y355_dev.h"
 #ifndef Y355_RING_XCD_SHARE
 #define Y355_RING_XCD_SHARE 1              // 0: plain work-item order (A/B builds)
 #endif
@@ -35,78 +35,7 @@
 // half-tile variants of round 2 live in scratch/ring_experiments/conv3x3_ring_r2_experiments.hip; none of them paid
 // (profiles/r02_notes.md) and the production kernel keeps ONE body.
 
-__device__ __forceinline__ void rglds16(const void *g, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-template <int N>
-__device__ __forceinline__ void rwait_vmcnt() {
-    static_assert(N >= 0, "vmcnt");
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N > 63 ? 63 : N) : "memory");
-}
-
-// fp32 epilogue on exact integers (FPE): 1.5 * 2^23 and the clamp bounds around it
-constexpr float RMAGIC = 12582912.0f, RQLO = 12582785.0f, RQHI = 12583039.0f;
-__device__ __forceinline__ float rvmax(float a, float b) {       // v_max_f32 without the canonicalising multiply
-    float d;
-    asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ float rvmax3(float a, float b, float c) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ float rvmin3(float a, float b, float c) {
-    float d;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-// byte B of w = bits [7:0] of max(a, b), the other bytes kept (B = 0: zeroed) -- front.hip
-template <int B>
-__device__ __forceinline__ void rmax_to_byte(unsigned int &w, float a, float b) {
-    if constexpr (B == 0)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD" : "=v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 1)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 2)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ unsigned int rpack4(float a, float b, float c, float d) {   // low bytes of four floats M + q
-    const unsigned int ab = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x0c0c0400u);
-    const unsigned int cd = __builtin_amdgcn_perm(__float_as_uint(d), __float_as_uint(c), 0x04000c0cu);
-    return ab | cd;
-}
-
-// s_waitcnt needs an immediate; callers pass values that are constants after unrolling, so the switch
-// folds to one instruction
-__device__ __forceinline__ void rwait_vmcnt_dyn(int n) {
-#define RW_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    switch (n < 0 ? 0 : (n > 63 ? 63 : n)) {
-        RW_CASE(0) RW_CASE(1) RW_CASE(2) RW_CASE(3) RW_CASE(4) RW_CASE(5) RW_CASE(6) RW_CASE(7) RW_CASE(8) RW_CASE(9)
-        RW_CASE(10) RW_CASE(11) RW_CASE(12) RW_CASE(13) RW_CASE(14) RW_CASE(15) RW_CASE(16) RW_CASE(17) RW_CASE(18)
-        RW_CASE(19) RW_CASE(20) RW_CASE(21) RW_CASE(22) RW_CASE(23) RW_CASE(24) RW_CASE(25) RW_CASE(26) RW_CASE(27)
-        RW_CASE(28) RW_CASE(29) RW_CASE(30) RW_CASE(31) RW_CASE(32) RW_CASE(33) RW_CASE(34) RW_CASE(35) RW_CASE(36)
-        RW_CASE(37) RW_CASE(38) RW_CASE(39) RW_CASE(40) RW_CASE(41) RW_CASE(42) RW_CASE(43) RW_CASE(44) RW_CASE(45)
-        RW_CASE(46) RW_CASE(47) RW_CASE(48) RW_CASE(49) RW_CASE(50) RW_CASE(51) RW_CASE(52) RW_CASE(53) RW_CASE(54)
-        RW_CASE(55) RW_CASE(56) RW_CASE(57) RW_CASE(58) RW_CASE(59) RW_CASE(60) RW_CASE(61) RW_CASE(62) RW_CASE(63)
-    }
-#undef RW_CASE
-}
-
-// slab pieces issued in steps lo..hi (step u issues one when 1 <= (u mod 9) <= ppw); negative steps
-// are the previous tile's (none before the first tile: its slab went out whole in the prologue)
-constexpr int ring_sp(int lo, int hi, int ppw, bool prev) {
-    int n = 0;
-    for (int u = lo; u <= hi; ++u) {
-        if (u < 0 && !prev) continue;
-        const int t = ((u % 9) + 9) % 9;
-        if (t >= 1 && t <= ppw) ++n;
-    }
-    return n;
-}
+using namespace y355dev;      // LDS-DMA, counted waits, ring_sp, the fp32 epilogue's primitives and MAGIC / QLO / QHI (FPE)
 
 // FPE: the requantisation runs in fp32 on exact integers (launcher-proved: accumulator shift 0, no left requant shift, right
 // shift <= 17, so every t = acc + bias that does not saturate is below 2^24 and converts exactly; a larger one converts to
@@ -202,7 +131,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
         const int gy = min(y0 + ppy0 + j * PSTEP, H + 1), gx = min(x0 + ppx0, W + 1);
         const int8_t *src = inb + ((size_t)gy * (W + 2) + gx) * CIN + pwithin;   // pad pieces read a valid row too
         char *dst = (q < NPIECE) ? smem + slot * SLABB + q * 1024 : smem + OFF_DUMMY;
-        rglds16(src, dst);
+        glds16(src, dst);
     };
     auto issue_w = [&](int nb, int ks, int slot) {
 #pragma unroll
@@ -211,7 +140,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
             const bool ok = NFR % NW == 0 || f < NFR;             // whole rounds of pieces: no dummy destination, no select
             const int8_t *src = p.w + ((size_t)(nb * KS + ks) * NFR + (ok ? f : 0)) * 1024 + lane * 16;
             char *dst = ok ? smem + OFF_W + slot * WB + f * 1024 : smem + OFF_DUMMY;
-            rglds16(src, dst);
+            glds16(src, dst);
         }
     };
     auto wrap = [](int s) { return s >= WSLOTS ? s - WSLOTS : s; };
@@ -254,7 +183,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
     int sl = 0;                                                // slab slot of the current chunk
     int wq = 0;                                                // ring slot of W(s) at step s
     // ---- prologue: (FPE: the biases,) slab 0 whole, then W(0) .. W(PF)
-    if constexpr (FPE) rglds16(p.bias_t + min(lane * 4, p.cstride - 4), wave == 0 ? smem + OFF_BIAS : smem + OFF_DUMMY);
+    if constexpr (FPE) glds16(p.bias_t + min(lane * 4, p.cstride - 4), wave == 0 ? smem + OFF_BIAS : smem + OFF_DUMMY);
 #pragma unroll
     for (int j = 0; j < PPW; ++j) issue_slab_piece(b, y0, x0, 0, 0, j);
 #pragma unroll
@@ -311,8 +240,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
         // W(1..PF), the slab pieces issued with them, and the previous tile's NIT output stores.
         v4i bfb[2][NT];
         v4i afp[2];
-        if (first) rwait_vmcnt<PF * WPW>();
-        else rwait_vmcnt<PF * WPW + ring_sp(-PF, -1, PPW, true) + NIT>();
+        if (first) wait_vmcnt<PF * WPW>();
+        else wait_vmcnt<PF * WPW + ring_sp(-PF, -1, PPW, true) + NIT>();
         __builtin_amdgcn_s_barrier();
         pstamp(first ? 2 : 6);
         if constexpr (FPE) {
@@ -359,10 +288,10 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                             if (n_slab < nr) nr = n_slab;
                         }
                         if (c == 0) {
-                            if (first) rwait_vmcnt_dyn(n0f);
-                            else rwait_vmcnt_dyn(n0l);
+                            if (first) wait_vmcnt_clamped(n0f);
+                            else wait_vmcnt_clamped(n0l);
                         } else {
-                            rwait_vmcnt_dyn(nr);
+                            wait_vmcnt_clamped(nr);
                         }
                     } else {
                         const int lo = s_idx - PF + 1, hi = s_idx - 1;
@@ -375,9 +304,9 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                         }
                         // one wait where the two agree (every step past the tile's first PF): a branch diamond
                         // here would end the scheduling region between the MFMAs and the next step's setup
-                        if (n_first == n_later) rwait_vmcnt_dyn(n_later);
-                        else if (first) rwait_vmcnt_dyn(n_first);
-                        else rwait_vmcnt_dyn(n_later);
+                        if (n_first == n_later) wait_vmcnt_clamped(n_later);
+                        else if (first) wait_vmcnt_clamped(n_first);
+                        else wait_vmcnt_clamped(n_later);
                     }
                     if (fine) stamp();
                 }
@@ -506,7 +435,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                 for (int t = 0; t < NT; ++t) biasf[t] = 0;           // already in the accumulators (their initial value)
             }
             // VGPR operands: an SGPR source takes the fma off the fast issue path (scratch/ubench/valu_rates.hip: 3.0 -> 4.6 cycles)
-            float spv = s_pos, snv = s_neg, mgv = RMAGIC;
+            float spv = s_pos, snv = s_neg, mgv = MAGIC;
             if constexpr (FPE) asm volatile("" : "+v"(spv), "+v"(snv), "+v"(mgv));
             // the two branches of the LeakyReLU, each M + rne(t * scale); y = max(pos, neg).  s_neg = s_pos / 8 here, so
             // y > M + 127 <=> pos > M + 127 and y < M - 127 <=> neg < M - 127: a running max / min of the branches (two
@@ -517,7 +446,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                 neg = fmaf(tf, snv, mgv);
                 return 0.f;
             };
-            float ymx = RMAGIC, ymn = RMAGIC;
+            float ymx = MAGIC, ymn = MAGIC;
             unsigned int satx = 0;                              // sum of (clamped ^ unclamped): non-zero iff something saturated
             if (Y355_DIAG12 && first) stamp();
             char *stg = smem + (STATIC ? 1 : (sl ^ 1)) * SLABB;
@@ -603,15 +532,15 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                                 if constexpr (CL) {
                                     float yc[NT];
 #pragma unroll
-                                    for (int t = 0; t < NT; ++t) yc[t] = __builtin_amdgcn_fmed3f(rvmax(ypos[t], yneg[t]), RQLO, RQHI);
-                                    w = rpack4(yc[0], yc[1], yc[2], yc[3]);
+                                    for (int t = 0; t < NT; ++t) yc[t] = __builtin_amdgcn_fmed3f(vmax(ypos[t], yneg[t]), QLO, QHI);
+                                    w = pack4(yc[0], yc[1], yc[2], yc[3]);
                                 } else {
-                                    ymx = rvmax3(rvmax3(ymx, ypos[0], ypos[1]), ypos[2], ypos[3]);
-                                    ymn = rvmin3(rvmin3(ymn, yneg[0], yneg[1]), yneg[2], yneg[3]);
-                                    rmax_to_byte<0>(w, ypos[0], yneg[0]);
-                                    rmax_to_byte<1>(w, ypos[1], yneg[1]);
-                                    rmax_to_byte<2>(w, ypos[2], yneg[2]);
-                                    rmax_to_byte<3>(w, ypos[3], yneg[3]);
+                                    ymx = vmax3(vmax3(ymx, ypos[0], ypos[1]), ypos[2], ypos[3]);
+                                    ymn = vmin3(vmin3(ymn, yneg[0], yneg[1]), yneg[2], yneg[3]);
+                                    max_to_byte<0>(w, ypos[0], yneg[0]);
+                                    max_to_byte<1>(w, ypos[1], yneg[1]);
+                                    max_to_byte<2>(w, ypos[2], yneg[2]);
+                                    max_to_byte<3>(w, ypos[3], yneg[3]);
                                 }
                             }
                             *(unsigned int *)(stg + lrow * SSTR + ncol) = w;
@@ -621,7 +550,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                 };
                 stage(std::false_type{});
                 if constexpr (FPE) {
-                    if (__builtin_amdgcn_ballot_w64(ymx > RQHI || ymn < RQLO) != 0ull) stage(std::true_type{});
+                    if (__builtin_amdgcn_ballot_w64(ymx > QHI || ymn < QLO) != 0ull) stage(std::true_type{});
                 }
                 if (Y355_DIAG12 && first) stamp();                   // requantised and staged (this wave)
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -639,7 +568,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                     *(v4i *)dst = v;
                 }
             }
-            if constexpr (FPE) satx = (ymx > RQHI || ymn < RQLO) ? 1u : 0u;
+            if constexpr (FPE) satx = (ymx > QHI || ymn < QLO) ? 1u : 0u;
             if (satx) {                                         // cold: count the clamped outputs of real rows exactly
 #pragma unroll
                 for (int m = 0; m < MT; ++m)
@@ -663,8 +592,8 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
                                 asm volatile("" : "+v"(v));        // recompute here: do not keep the hot pass's 96 values alive for this branch
                                 float ypc, ync;
                                 (void)requantf(v, t, ypc, ync);
-                                const float y = rvmax(ypc, ync);
-                                nsat += (real && (y > RQHI || y < RQLO)) ? 1u : 0u;
+                                const float y = vmax(ypc, ync);
+                                nsat += (real && (y > QHI || y < QLO)) ? 1u : 0u;
                             } else {
                                 const int qq = requant(v, t);
                                 nsat += (real && y355_clamp8<int>(qq) != qq) ? 1u : 0u;
@@ -681,7 +610,7 @@ __global__ __launch_bounds__(WM * WN * 64, (WM * WN == 4) ? 2 : 1) void conv3x3_
         tile = ntile;
         b = b2; y0 = y2; x0 = x2; nb = nb2;
     }
-    rwait_vmcnt<0>();       // retire the prefetches before the wave ends
+    wait_vmcnt<0>();       // retire the prefetches before the wave ends
     pstamp(5);
     if (Y355_DIAG12) { nstamp = 28; stamp(); }
     if (nsat) atomicAdd(&p.ctr->sat, (unsigned long long)nsat);
@@ -774,7 +703,8 @@ bool y355_launch_conv_ring(int kid, const ConvParams &p, hipStream_t s) {
     // one stream, B = 64, round 1); round 3's operand-swapped form with 16-byte stores straight from the accumulators
     // (scratch/ring_experiments/conv3x3_ring_r3_swap.hip) shortens the epilogue by 0.9 us and changes nothing end to end
     // fp32 epilogue where the host can prove it exact (header of the kernel): no accumulator / left requant shift, a right shift
-    // of at most 17 bits, the reference's slope
+    // of at most 17 bits, the reference's slope.  (Not y355_fp32_exact: that bounds |t| by the weights; this rule needs no bound on
+    // t -- one that is not exact saturates either way -- and is proved over the whole int32 range by the test of that name.)
 #ifndef Y355_RING_NO_FPE
     if (p.rq.shl == 0 && p.rq.sh_l == 0 && p.rq.sh_r <= 17 && p.rq.neg_mul == 1 && p.cstride >= 4 && p.cstride <= 256)
         return RSet<false, false, true>::launch(kid, p, s);

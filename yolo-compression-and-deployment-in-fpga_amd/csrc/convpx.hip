@@ -15,18 +15,17 @@
 //     contiguous across the wave -- no LDS staging, no second pass;
 //   * work is dealt in groups of 16 pixels / windows over the row-major image; workgroup i owns a contiguous, equal share
 //     of all groups of the batch and walks it in chunks of a few rounds of its waves;
-//   * the input lives in LDS as a ROLLING RING of whole padded rows (slot = absolute padded row & (R - 1)): every row is
-//     copied once per workgroup by LDS-DMA (global_load_lds_dwordx4, 1 KiB pieces that each stay inside one row: the LDS
-//     pitch is padded to a piece multiple), the rows the NEXT chunk adds are in flight while this chunk computes, and the
-//     chunk boundary waits with a COUNTED vmcnt that leaves the chunk's own output stores in flight.  64- and 128-byte
-//     pixels are XOR-swizzled on the source side so that every ds_read_b128 is conflict-free under gfx950's 4 x 16 lane
-//     grouping (chunk ^ 2 ((x >> 2) & 1) resp. chunk ^ 2 ((x >> 1) & 3));
-//   * the epilogue is front.hip's fp32 form (two fma + max on exact integers).  FOLD 2 (accumulator shift 0, |t| < 2^22): bias +
+//   * the input lives in LDS as a ROLLING RING of whole padded rows that LDS-DMA fills one chunk ahead, behind a COUNTED vmcnt
+//     that leaves the chunk's own output stores in flight; 64- and 128-byte pixels are XOR-swizzled on the source side so that
+//     every ds_read_b128 is conflict-free.  The ring, its invariants and its host geometry: y355_rowring.h (shared with
+//     convpxb.hip);
+//   * the epilogue is the fp32 form of y355_fp32epi.h (two fma + max on exact integers).  FOLD 2 (accumulator shift 0, |t| < 2^22): bias +
 //     0x4B400000 rides in as the MFMAs' C operand and the accumulator IS the float 1.5 * 2^23 + t; FOLD 1 (shift 0, |t| < 2^24):
 //     the bias rides in, one v_cvt; FOLD 0: v_cvt + fma; the hot pass stores unclamped and tracks max / min, a cold pass re-does a wave's groups clamped and
 //     counts when a value left [-127, 127].
 // Integer semantics: DESIGN.md section 2, bit for bit those of conv3x3_ring.hip / conv3x3.hip.
-#include "y355_common.h"
+#include "y355_fp32epi.h"
+#include "y355_rowring.h"
 #include <cstring>
 #include <type_traits>
 #ifndef PX_R31
@@ -38,52 +37,12 @@
 #endif
 
 namespace {
-constexpr float MAGIC = 12582912.0f;                 // 1.5 * 2^23
-constexpr float QLO = 12582785.0f, QHI = 12583039.0f;
-
-__device__ __forceinline__ void pglds16(const void *g, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-__device__ __forceinline__ float pvmax(float a, float b) {
-    float d;
-    asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ float pvmax3(float a, float b, float c) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ float pvmin3(float a, float b, float c) {
-    float d;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-// byte B of w = bits [7:0] of max(a, b), the other bytes kept (B = 0: zeroed): the LeakyReLU's max and the int8 pack in one
-// SDWA instruction per output (front.hip)
-template <int B>
-__device__ __forceinline__ void pmax_to_byte(unsigned int &w, float a, float b) {
-    if constexpr (B == 0)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD" : "=v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 1)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 2)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ unsigned int ppack4(float a, float b, float c, float d) {
-    const unsigned int ab = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x0c0c0400u);
-    const unsigned int cd = __builtin_amdgcn_perm(__float_as_uint(d), __float_as_uint(c), 0x04000c0cu);
-    return ab | cd;
-}
+using namespace y355dev;
 
 // geometry shared by the kernel, the launcher and the weight packing
 template <int CIN, int NTN, int NCB, bool POOL>
 struct PxGeom {
     static constexpr int PXB = CIN;                              // bytes per input pixel
-    static constexpr int PPP = 1024 / PXB;                       // pixels per 1 KiB DMA piece (= LDS pitch granule)
     static constexpr int KPP = CIN >= 64 ? CIN / 64 : 1;         // k-steps per tap
     static constexpr int KS = CIN >= 64 ? 9 * KPP : 5;           // CIN = 32: two taps per k-step
     static constexpr int CPB = 16 * NTN;                         // output channels per block (per wave)
@@ -92,34 +51,12 @@ struct PxGeom {
     static_assert(CIN == 32 || CIN == 64 || CIN == 128, "input channels");
     static_assert(!(POOL && CIN < 64), "pooled layers: one tap per k-step");
 };
-
-struct PxArgs {
-    int total_groups;     // groups of 16 pixels / windows in the batch (ngi per image)
-    int ngi;              // groups per image
-    int cg;               // groups per chunk (a multiple of the pixel streams of a workgroup)
-    int pwl;              // LDS row pitch in pixels (a multiple of PPP, >= W + 2)
-    int logr;             // ring of 2^logr rows
-    int ppg;              // DMA pieces a wave issues behind each of its groups
-};
-// image, groups [g0, g1) of it, absolute padded input rows [lo, hi) it reads (row = b * (H + 2) + padded row of the image)
-struct PxChunk { int b, g0, g1, lo, hi; };
-
-// s_waitcnt needs an immediate; n is wave-uniform
-__device__ __forceinline__ void pwait_vmcnt(int n) {
-#define PW_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    switch (n) {
-        PW_CASE(0) PW_CASE(1) PW_CASE(2) PW_CASE(3) PW_CASE(4) PW_CASE(5) PW_CASE(6) PW_CASE(7) PW_CASE(8) PW_CASE(9)
-        PW_CASE(10) PW_CASE(11) PW_CASE(12) PW_CASE(13) PW_CASE(14) PW_CASE(15) PW_CASE(16)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-#undef PW_CASE
-}
 }  // namespace
 
 template <int CIN, int NTN, int NCB, bool POOL, int NW, int FOLD>
-__global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const ConvParams p, const PxArgs a) {
+__global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const ConvParams p, const RowRingArgs a) {
     using G = PxGeom<CIN, NTN, NCB, POOL>;
-    constexpr int PXB = G::PXB, PPP = G::PPP, KPP = G::KPP, KS = G::KS, CPB = G::CPB, COUT = G::COUT;
+    constexpr int PXB = G::PXB, KPP = G::KPP, KS = G::KS, CPB = G::CPB, COUT = G::COUT;
     constexpr int NPS = NW / NCB;                        // pixel streams: waves that share a channel block
     constexpr int NV = POOL ? 4 : 1;                     // conv outputs per column (pooling window)
     static_assert(NW % NCB == 0, "waves per channel block");
@@ -130,11 +67,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const Con
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cb = wave % NCB, ps = wave / NCB;
     const int li = lane & 15, g = lane >> 4;
-    const int H = p.H, W = p.W;
-    const int PW = W + 2, PWL = a.pwl;
-    const int Ho = POOL ? H >> 1 : H, Wo = POOL ? W >> 1 : W;
-    const int npw = Ho * Wo;                             // pixels / windows per image
-    const int rowb = PWL * PXB;                          // bytes per slab row
 
     // ---- weights of this wave's channel block: A fragments [k-step][n-tile], registers for the whole launch
     v4i wf[KS][NTN];
@@ -158,74 +90,19 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const Con
     const float s_pos = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ldexpf(1.0f, rq.lk - rq.sh))));
     const float s_neg = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)rq.neg_mul * ldexpf(1.0f, -rq.sh))));
     const float c_pos = FOLD == 2 ? MAGIC - MAGIC * s_pos : MAGIC, c_neg = FOLD == 2 ? MAGIC - MAGIC * s_neg : MAGIC;
-    // VGPR operands for the epilogue's fma: an SGPR source takes a vector instruction off the fast issue path
-    // (scratch/ubench/valu_rates.hip: 3.0 cycles per SIMD against 4.6)
+    // y355_fp32epi.h's constants (epi_scales / epi_ops) and, in `finish`, its pair arithmetic and clamped word, written out: this
+    // kernel's lambdas capture the scalars one by one, and the shared structs, though equivalent, change its register allocation
     float spv = s_pos, snv = s_neg, cpv = c_pos, cnv = c_neg;
     asm volatile("" : "+v"(spv), "+v"(snv), "+v"(cpv), "+v"(cnv));
     const float scl = ldexpf(1.0f, rq.shl);
-    const float invWo = 1.0f / (float)Wo;
 
-    // ---- this workgroup's share of the batch's groups, walked in chunks of <= cg groups that stay inside one image
-    const int G_ = gridDim.x;
-    const int gbeg = (int)((long long)a.total_groups * blockIdx.x / G_), gend = (int)((long long)a.total_groups * (blockIdx.x + 1) / G_);
-    if (gbeg >= gend) return;
-    constexpr int MUL = POOL ? 2 : 1;
-    const int R = 1 << a.logr, RM = R - 1;
-    auto chunk_at = [&](int gg) {
-        PxChunk c;
-        c.b = gg / a.ngi;
-        c.g0 = gg - c.b * a.ngi;
-        c.g1 = min(min(c.g0 + a.cg, a.ngi), c.g0 + (gend - gg));
-        const int ya = (16 * c.g0) / Wo, yb = (min(16 * c.g1, npw) - 1) / Wo;
-        c.lo = c.b * (H + 2) + MUL * ya;
-        c.hi = c.b * (H + 2) + MUL * yb + (POOL ? 4 : 3);
-        return c;
-    };
-    // absolute padded rows [r0, r1) -> ring slots row & RM; piece q = 1 KiB = PPP pixels of ONE row, by wave q % NW.
-    // Lane l writes LDS chunk l % CPX of pixel l / CPX of the piece and reads the source chunk the swizzle puts there.
-    constexpr int CPX = PXB / 16;                        // 16-byte chunks per pixel
-    const int dpx = lane / CPX, dch = lane % CPX;
-    const int ppr = PWL / PPP;                           // pieces per row
-    // Who sends which piece: a wave owns ONE piece column pc0 (its lanes' pixel, swizzled chunk and byte offset inside a row are
-    // launch constants) and every RS-th row of it -- ppr <= NW: NW / ppr rows per round of the waves (the waves beyond RS * ppr
-    // send nothing); wider rows: every row, the columns pc0, pc0 + NW, ...  A piece then costs one scalar multiply-add for the
-    // row's offsets and the DMA (before: a (row, column) cursor with a wrap loop, ~17 scalar and 6 vector instructions per
-    // piece, 900 - 1 600 scalar instructions per wave and launch: profiles/r04_notes.md 13).
-    const int RS = ppr < NW ? NW / ppr : 1;
-    const int CPW = ppr < NW ? 1 : (ppr + NW - 1) / NW;
-    const int pc0 = ppr < NW ? wave % ppr : wave;
-    const int rr0 = ppr < NW ? (wave / ppr < RS ? wave / ppr : (1 << 28)) : 0;
-    auto lane_off = [&](int pc) {                        // byte offset of this lane's 16 bytes inside a padded input row
-        const int col = pc * PPP + dpx;
-        int sch = dch;
-        if constexpr (CPX == 4) sch ^= ((col >> 2) & 1) << 1;
-        if constexpr (CPX == 8) sch ^= ((col >> 1) & 3) << 1;
-        return min(col, PW - 1) * PXB + 16 * sch;
-    };
-    const int goff0 = lane_off(pc0);
-    // rows r0 + rr, rr = cursor, cursor + RS, ... < nrows: at most about `count` pieces; the cursor travels with the caller
-    auto issue_pieces = [&](int r0, int nrows, int &rr, int count) {
-        int done = 0;
-        for (; rr < nrows && done < count; rr += RS) {
-            const int row = r0 + rr;
-            const int8_t *src = p.in + (size_t)row * (size_t)(PW * PXB);
-            char *dst = smem + (row & RM) * rowb;
-            pglds16(src + goff0, dst + pc0 * 1024);
-            ++done;
-            for (int j = 1; j < CPW; ++j) {              // rows wider than NW pieces (not the shapes of this network)
-                const int pc = pc0 + j * NW;
-                if (pc < ppr) {
-                    pglds16(src + lane_off(pc), dst + pc * 1024);
-                    ++done;
-                }
-            }
-        }
-        return done;
-    };
-    auto issue_rows = [&](int r0, int r1) {
-        int rr = rr0;
-        issue_pieces(r0, r1 - r0, rr, 1 << 30);
-    };
+    // ---- this workgroup's share of the batch's groups, walked in chunks of <= cg groups on the ring of padded input rows
+    using Ring = RowRing<PXB, NW, POOL>;
+    int gbeg, gend;
+    if (!Ring::share(a, gbeg, gend)) return;
+    const Ring ring(a, p.in, smem, p.H, p.W, lane, wave, gend);
+    constexpr int MUL = Ring::MUL;
+    const int H = ring.H, Ho = ring.Ho, Wo = ring.Wo, npw = ring.npw, rowb = ring.rowb, RM = ring.RM;
 
     int nstamp = 0;
     auto stamp = [&]() {
@@ -239,45 +116,33 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const Con
     };
     (void)nstamp;
     stamp();
-    PxChunk ch = chunk_at(gbeg);
-    issue_rows(ch.lo, ch.hi);
+    RowChunk ch = ring.chunk_at(gbeg);
+    ring.issue_rows(ch.lo, ch.hi);
     int loaded = ch.hi;                                  // rows below `loaded` (and not yet overwritten) are in the ring or in flight
     unsigned int nsat = 0;
-    int gg = gbeg, nstores = -1;                         // stores this wave issued in the previous chunk (-1: wait for everything)
+    int gg = gbeg, nstores = -1;                        // stores this wave issued in the previous chunk (-1: wait for everything)
     for (;;) {
         // Everything this chunk reads has landed: the rows were issued BEFORE the previous chunk's output stores, so a counted
         // wait leaves those stores in flight.  Behind the barrier every wave is done with the previous chunk's rows.
         stamp();
-        pwait_vmcnt(nstores);
+        wait_vmcnt_upto<16>(nstores);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         stamp();
         __builtin_amdgcn_s_barrier();
-        if (loaded < ch.hi) {                            // rows that could not be issued ahead (the ring was full: image boundaries)
-            issue_rows(max(loaded, ch.lo), ch.hi);
-            loaded = ch.hi;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
+        ring.late_rows(ch, loaded);
         stamp();
         const int gnext = gg + (ch.g1 - ch.g0);
         const bool more = gnext < gend;
-        PxChunk nx = ch;
-        if (more) nx = chunk_at(gnext);
+        RowChunk nx = ch;
+        if (more) nx = ring.chunk_at(gnext);
         // the next chunk's new rows, as far as they fit beside the rows this chunk still reads, go out a few pieces at a time
         // behind each group's MFMAs (the SIMD's other wave computes while this one issues); the chunk boundary may leave in
         // flight only the stores issued after the LAST piece
-        int pf_r0 = 0, pf_nr = 0;
-        if (more) {
-            const int top = min(nx.hi, ch.lo + R);
-            pf_r0 = max(loaded, nx.lo);
-            if (top > pf_r0) {
-                pf_nr = top - pf_r0;
-                loaded = top;
-            }
-        }
-        int pfc = rr0;
+        int pf_r0, pf_nr;
+        ring.next_window(ch, nx, more, loaded, pf_r0, pf_nr);
+        int pfc = ring.rr0;
         auto prefetch = [&](int count) {
-            if (issue_pieces(pf_r0, pf_nr, pfc, count) > 0) nstores = 0;
+            if (ring.issue_pieces(pf_r0, pf_nr, pfc, count) > 0) nstores = 0;
         };
         stamp();
         int8_t *outb = p.out + (((size_t)ch.b * (Ho + 2) + 1) * (Wo + 2) + 1) * COUT + cb * CPB;    // wave-uniform
@@ -287,14 +152,9 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const Con
         // ---- one group = issue (addresses, B reads, MFMAs) + finish (pool, requantise, pack, store).  (A software pipeline over
         // two accumulator sets with the finish interleaved behind the next group's MFMAs, pinned read-then-MFMA orders and a
         // raised priority for the SIMD's second wave were each measured: no change, profiles/r03_notes.md.)
-        auto locate = [&](int grp, int &oy, int &ox) {
-            const int pc = min(grp * 16 + li, npw - 1);            // padding lanes of an image's last group repeat its last pixel
-            oy = (int)(((float)pc + 0.5f) * invWo);                // pc / Wo (exact: pc < 2^16)
-            ox = pc - oy * Wo;
-        };
         auto issue = [&](int grp, v4i (&acc)[NV][NTN]) {
             int oy, ox;
-            locate(grp, oy, ox);
+            ring.locate(grp, oy, ox);
             const int ar = rbase + MUL * oy, x0 = MUL * ox;        // absolute padded row / padded column of the neighbourhood's corner
             // byte offset inside a row of neighbourhood column c: pixel x0 + c, chunk g (CIN = 32: the half is added per
             // k-step), swizzled by the pixel's x; byte offset of neighbourhood row r in the ring
@@ -302,11 +162,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const Con
             int xoff[NC], roff[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const int x = x0 + c;
-                int sch = CIN == 32 ? 0 : g;
-                if constexpr (CPX == 4) sch ^= ((x >> 2) & 1) << 1;
-                if constexpr (CPX == 8) sch ^= ((x >> 1) & 3) << 1;
-                xoff[c] = x * PXB + 16 * sch;
+                xoff[c] = Ring::read_off(x0 + c, CIN == 32 ? 0 : g);
                 roff[c] = ((ar + c) & RM) * rowb;
             }
 #pragma unroll
@@ -392,13 +248,10 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const Con
         auto finish = [&](int grp, const v4i (&acc)[NV][NTN], auto coldc) {
             constexpr bool COLD = decltype(coldc)::value;
             int oy, ox;
-            locate(grp, oy, ox);
+            ring.locate(grp, oy, ox);
             unsigned int word[NTN];
 #pragma unroll
             for (int n = 0; n < NTN; ++n) {
-                // the two branches of the LeakyReLU, each M + rne(t * scale); y = max(pos, neg).  0 <= s_neg <= s_pos (launcher), so
-                // y > M + 127 <=> pos > M + 127 and y < M - 127 <=> neg < M - 127: the hot pass tracks the branches and packs the
-                // unclamped low bytes with one SDWA max per output
                 float pos[4], neg[4];
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
@@ -408,22 +261,16 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpx_kernel(const Con
                     pos[r] = fmaf(tf, spv, cpv);
                     neg[r] = fmaf(tf, snv, cnv);
                 }
-                if constexpr (!COLD) {
-                    ymx = pvmax3(pvmax3(ymx, pos[0], pos[1]), pos[2], pos[3]);
-                    ymn = pvmin3(pvmin3(ymn, neg[0], neg[1]), neg[2], neg[3]);
-                    pmax_to_byte<0>(word[n], pos[0], neg[0]);
-                    pmax_to_byte<1>(word[n], pos[1], neg[1]);
-                    pmax_to_byte<2>(word[n], pos[2], neg[2]);
-                    pmax_to_byte<3>(word[n], pos[3], neg[3]);
-                } else {
+                if constexpr (!COLD) word[n] = epi_word_hot<false>(pos, neg, ymx, ymn);
+                else {
                     float yc[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) {
-                        const float y = pvmax(pos[r], neg[r]);
+                        const float y = vmax(pos[r], neg[r]);
                         yc[r] = __builtin_amdgcn_fmed3f(y, QLO, QHI);
                         nsat += (grp * 16 + li < npw && y != yc[r]) ? 1u : 0u;
                     }
-                    word[n] = ppack4(yc[0], yc[1], yc[2], yc[3]);
+                    word[n] = pack4(yc[0], yc[1], yc[2], yc[3]);
                 }
             }
             // unconditional: the padding lanes rewrite the image's last pixel with the same bytes, and the number of stores a
@@ -491,29 +338,8 @@ template <int CIN, int NTN, int NCB, bool POOL, int NW>
 struct PxInst {
     using G = PxGeom<CIN, NTN, NCB, POOL>;
     static constexpr int NPS = NW / NCB;
-    // rounds: groups per pixel stream per chunk
-    static PxArgs args(const ConvParams &p, int rounds) {
-        PxArgs a;
-        const int Ho = POOL ? p.H / 2 : p.H, Wo = POOL ? p.W / 2 : p.W;
-        a.ngi = (Ho * Wo + 15) / 16;
-        a.total_groups = a.ngi * p.B;
-        a.cg = rounds * NPS;
-        a.pwl = (p.W + 2 + G::PPP - 1) / G::PPP * G::PPP;
-        // two consecutive chunks of an image are in the ring together: MUL * (output rows they touch) + 2 (+ 1 pooled) rows
-        const int rows2 = (2 * 16 * a.cg + Wo - 1) / Wo + 1;
-        const int need = (POOL ? 2 : 1) * rows2 + (POOL ? 2 : 2);
-        a.logr = 2;
-        while ((1 << a.logr) < need) ++a.logr;
-        // a chunk adds about MUL * 16 cg / Wo rows = that many * pwl / PPP pieces, dealt over NW waves and `rounds` groups each
-        const int newrows = (POOL ? 2 : 1) * ((16 * a.cg + Wo - 1) / Wo + 1);
-        const int ppr = a.pwl / G::PPP, rs = ppr < NW ? NW / ppr : 1, cpw = ppr < NW ? 1 : (ppr + NW - 1) / NW;
-        const int per_wave = (newrows + rs - 1) / rs * cpw;         // a wave sends one piece column of every rs-th row
-        a.ppg = (per_wave + rounds - 1) / rounds;
-        return a;
-    }
-    static size_t lds_bytes(const PxArgs &a) { return ((size_t)a.pwl * G::PXB) << a.logr; }
     template <int FOLD>
-    static void launch_(const ConvParams &p_in, const PxArgs &a, hipStream_t s) {
+    static void launch_(const ConvParams &p_in, const RowRingArgs &a, size_t lds, hipStream_t s) {
         ConvParams p = p_in;
         p.ev_start = p.ev_stop = nullptr;
         int grid = y355_cu_count();                                           // one NW-wave workgroup per CU
@@ -522,16 +348,19 @@ struct PxInst {
         // CUs to the other handles' kernels: 64 / 96 / 128 / 160 / 256 workgroups -> 272.7 / 286.2 / 293.5 / 289.2 / 285.8 k img/s
         if (p_in.grid_limit > 0 && p_in.grid_limit < grid) grid = p_in.grid_limit;
         if (grid > a.total_groups) grid = a.total_groups;
-        Y355_LAUNCH((convpx_kernel<CIN, NTN, NCB, POOL, NW, FOLD>), dim3(grid), dim3(NW * 64), lds_bytes(a), s, p_in.ev_start, p_in.ev_stop, p, a);
+        Y355_LAUNCH((convpx_kernel<CIN, NTN, NCB, POOL, NW, FOLD>), dim3(grid), dim3(NW * 64), lds, s, p_in.ev_start, p_in.ev_stop, p, a);
     }
+    // rounds: groups per pixel stream per chunk
     static bool launch(const ConvParams &p, int rounds, hipStream_t s) {
         if (p.cstride != G::COUT || !p.out_halo || p.W < 16 || (POOL && ((p.H | p.W) & 1))) return false;
         if ((long long)p.B * (p.H + 2) * (p.W + 2) * G::PXB >= (1ll << 31)) return false;     // 32-bit row arithmetic
-        const PxArgs a = args(p, rounds);
-        if (lds_bytes(a) > 160 * 1024) return false;
-        if (p.rq.shl == 0 && p.rq.tmax_log2 <= 22 && p.rq.sh <= 22 && p.rq.sh - p.rq.lk >= -8) launch_<2>(p, a, s);
-        else if (p.rq.shl == 0) launch_<1>(p, a, s);
-        else launch_<0>(p, a, s);
+        const RowRingArgs a = rowring_args<G::PXB, NW, NPS, POOL>(p.B, p.H, p.W, rounds);
+        const size_t lds = rowring_lds_bytes<G::PXB>(a);
+        if (lds > 160 * 1024) return false;
+        const int fold = y355_fp32_fold(p.rq);
+        if (fold == 2) launch_<2>(p, a, lds, s);
+        else if (fold == 1) launch_<1>(p, a, lds, s);
+        else launch_<0>(p, a, lds, s);
         return true;
     }
     static int prepare() {
@@ -580,8 +409,7 @@ bool y355_pack_px(int kid, const int8_t *q_w, int cout, int cin, int8_t *dst) {
 // false = not available for this launch (statistics mode, head-room guard, 64-bit epilogue, t beyond fp32's exact range, a
 // map too wide for two slabs in LDS): the caller falls back to the ring / v2 / generic kernels.  `p.w` = y355_pack_px layout.
 bool y355_launch_conv_px(int kid, const ConvParams &p, hipStream_t s) {
-    if ((p.mode & 0xff) != 0 || p.rq.wide || p.guard || p.rq.tmax_log2 > 24) return false;
-    if (p.rq.neg_mul < 0 || p.rq.neg_mul > (1 << p.rq.lk)) return false;      // the epilogue assumes a LeakyReLU slope in [0, 1]
+    if ((p.mode & 0xff) != 0 || p.guard || !y355_fp32_exact(p.rq) || !y355_fp32_slope_ok(p.rq)) return false;
     switch (kid) {
     case Y355_K_CONV3_1: return PX_C3_1::launch(p, PX_R31, s);
     case Y355_K_CONV3_2: return PX_C3_2::launch(p, 2, s);

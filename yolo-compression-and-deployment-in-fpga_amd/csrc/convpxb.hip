@@ -17,7 +17,7 @@
 // operand) -> [2x2 max] -> LeakyReLU(slope) -> bf16 (RNE) -- no saturation, no cold pass, no counters.
 // Parity: tolerance against the fp32 oracle (tests/test_fp32_models.py); the accumulation order differs from convr's in where the bias
 // enters, so the two routes are not bit-identical and are compared within 2 bf16 ulps (tests/test_fp32_models.py::test_convpxb_...).
-#include "y355_common.h"
+#include "y355_rowring.h"
 #include <cstring>
 #include <type_traits>
 #ifndef PXB_R31
@@ -26,23 +26,13 @@
 #endif
 
 namespace {
+using namespace y355dev;
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
-
-__device__ __forceinline__ void bglds16(const void *g, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-__device__ __forceinline__ unsigned int pk2(float a, float b) {       // (a, b) -> two bf16 (RNE), a in the low half
-    typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-    const v2bf v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned int, v);
-}
 
 // PXB = bytes per input pixel (2 x channels): 64 or 128
 template <int PXB, int NTN, int NCB, bool POOL>
 struct PbGeom {
-    static constexpr int PPP = 1024 / PXB;                       // pixels per 1 KiB DMA piece
     static constexpr int KPP = PXB / 64;                         // k-steps (32 channels) per tap
     static constexpr int KS = 9 * KPP;
     static constexpr int CPB = 16 * NTN;                         // output channels per block (per wave)
@@ -50,27 +40,12 @@ struct PbGeom {
     static constexpr int NFRAG = NCB * KS * NTN;
     static_assert(PXB == 64 || PXB == 128, "input channels 32 or 64");
 };
-struct PbArgs {
-    int total_groups, ngi, cg, pwl, logr, ppg;                   // as convpx.hip's PxArgs
-};
-struct PbChunk { int b, g0, g1, lo, hi; };
-
-__device__ __forceinline__ void bwait_vmcnt(int n) {
-#define BW_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    switch (n) {
-        BW_CASE(0) BW_CASE(1) BW_CASE(2) BW_CASE(3) BW_CASE(4) BW_CASE(5) BW_CASE(6) BW_CASE(7) BW_CASE(8) BW_CASE(9)
-        BW_CASE(10) BW_CASE(11) BW_CASE(12) BW_CASE(13) BW_CASE(14) BW_CASE(15) BW_CASE(16) BW_CASE(17) BW_CASE(18) BW_CASE(19)
-        BW_CASE(20) BW_CASE(21) BW_CASE(22) BW_CASE(23) BW_CASE(24)
-        default: asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); break;
-    }
-#undef BW_CASE
-}
 }  // namespace
 
 template <int PXB, int NTN, int NCB, bool POOL, int NW>
-__global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpxb_kernel(const ConvGParams p, const PbArgs a) {
+__global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpxb_kernel(const ConvGParams p, const RowRingArgs a) {
     using G = PbGeom<PXB, NTN, NCB, POOL>;
-    constexpr int PPP = G::PPP, KPP = G::KPP, KS = G::KS, CPB = G::CPB;
+    constexpr int KPP = G::KPP, KS = G::KS, CPB = G::CPB;
     constexpr int NPS = NW / NCB;                        // pixel streams: waves that share a channel block
     constexpr int NV = POOL ? 4 : 1;                     // conv outputs per column (pooling window)
     constexpr int SPG = NTN / 2;                         // 16-byte stores per lane and group
@@ -80,12 +55,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpxb_kernel(const Co
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int cb = wave % NCB, ps = wave / NCB;
-    const int li = lane & 15, g = lane >> 4;
-    const int H = p.H, W = p.W;
-    const int PW = W + 2, PWL = a.pwl;
-    const int Ho = POOL ? H >> 1 : H, Wo = POOL ? W >> 1 : W;
-    const int npw = Ho * Wo;
-    const int rowb = PWL * PXB;
+    const int g = lane >> 4;
 
     // ---- weights of this wave's channel block: A fragments [k-step][n-tile], registers for the whole launch
     v4i wf[KS][NTN];
@@ -98,119 +68,51 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpxb_kernel(const Co
 #pragma unroll
     for (int n = 0; n < NTN; ++n) cin[n] = *(const v4f *)(p.bias_f + cb * CPB + 4 * NTN * g + 4 * n);
     float slope = p.slope;
-    asm volatile("" : "+v"(slope));                      // a VGPR operand for the epilogue's multiply (front.hip)
-    const float invWo = 1.0f / (float)Wo;
+    asm volatile("" : "+v"(slope));                      // a VGPR operand for the epilogue's multiply (y355_fp32epi.h has the measurement)
 
-    // ---- this workgroup's share of the batch's groups, walked in chunks of <= cg groups that stay inside one image
-    const int G_ = gridDim.x;
-    const int gbeg = (int)((long long)a.total_groups * blockIdx.x / G_), gend = (int)((long long)a.total_groups * (blockIdx.x + 1) / G_);
-    if (gbeg >= gend) return;
-    constexpr int MUL = POOL ? 2 : 1;
-    const int R = 1 << a.logr, RM = R - 1;
-    auto chunk_at = [&](int gg) {
-        PbChunk c;
-        c.b = gg / a.ngi;
-        c.g0 = gg - c.b * a.ngi;
-        c.g1 = min(min(c.g0 + a.cg, a.ngi), c.g0 + (gend - gg));
-        const int ya = (16 * c.g0) / Wo, yb = (min(16 * c.g1, npw) - 1) / Wo;
-        c.lo = c.b * (H + 2) + MUL * ya;
-        c.hi = c.b * (H + 2) + MUL * yb + (POOL ? 4 : 3);
-        return c;
-    };
-    // LDS-DMA of whole padded rows into ring slots row & RM, 1 KiB pieces of PPP pixels (convpx.hip: same swizzles)
-    constexpr int CPX = PXB / 16;
-    const int dpx = lane / CPX, dch = lane % CPX;
-    const int ppr = PWL / PPP;
-    const int RS = ppr < NW ? NW / ppr : 1;
-    const int CPW = ppr < NW ? 1 : (ppr + NW - 1) / NW;
-    const int pc0 = ppr < NW ? wave % ppr : wave;
-    const int rr0 = ppr < NW ? (wave / ppr < RS ? wave / ppr : (1 << 28)) : 0;
-    auto lane_off = [&](int pc) {
-        const int col = pc * PPP + dpx;
-        int sch = dch;
-        if constexpr (CPX == 4) sch ^= ((col >> 2) & 1) << 1;
-        if constexpr (CPX == 8) sch ^= ((col >> 1) & 3) << 1;
-        return min(col, PW - 1) * PXB + 16 * sch;
-    };
-    const int goff0 = lane_off(pc0);
-    auto issue_pieces = [&](int r0, int nrows, int &rr, int count) {
-        int done = 0;
-        for (; rr < nrows && done < count; rr += RS) {
-            const int row = r0 + rr;
-            const char *src = p.in + (size_t)row * (size_t)(PW * PXB);
-            char *dst = smem + (row & RM) * rowb;
-            bglds16(src + goff0, dst + pc0 * 1024);
-            ++done;
-            for (int j = 1; j < CPW; ++j) {
-                const int pc = pc0 + j * NW;
-                if (pc < ppr) {
-                    bglds16(src + lane_off(pc), dst + pc * 1024);
-                    ++done;
-                }
-            }
-        }
-        return done;
-    };
-    auto issue_rows = [&](int r0, int r1) {
-        int rr = rr0;
-        issue_pieces(r0, r1 - r0, rr, 1 << 30);
-    };
+    // ---- this workgroup's share of the batch's groups, walked in chunks of <= cg groups on the ring of padded input rows
+    // (y355_rowring.h, shared with convpx.hip: the ring's invariants, the counted wait and the swizzles)
+    using Ring = RowRing<PXB, NW, POOL>;
+    int gbeg, gend;
+    if (!Ring::share(a, gbeg, gend)) return;
+    const Ring ring(a, p.in, smem, p.H, p.W, lane, wave, gend);
+    constexpr int MUL = Ring::MUL;
+    const int H = ring.H, Ho = ring.Ho, Wo = ring.Wo, rowb = ring.rowb, RM = ring.RM;
 
-    PbChunk ch = chunk_at(gbeg);
-    issue_rows(ch.lo, ch.hi);
+    RowChunk ch = ring.chunk_at(gbeg);
+    ring.issue_rows(ch.lo, ch.hi);
     int loaded = ch.hi;
     int gg = gbeg, nstores = -1;                         // stores this wave issued behind its last DMA piece (-1: wait for everything)
     for (;;) {
-        bwait_vmcnt(nstores);
+        wait_vmcnt_upto<24>(nstores);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         __builtin_amdgcn_s_barrier();
-        if (loaded < ch.hi) {                            // rows that could not be issued ahead (the ring was full: image boundaries)
-            issue_rows(max(loaded, ch.lo), ch.hi);
-            loaded = ch.hi;
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();
-        }
+        ring.late_rows(ch, loaded);
         const int gnext = gg + (ch.g1 - ch.g0);
         const bool more = gnext < gend;
-        PbChunk nx = ch;
-        if (more) nx = chunk_at(gnext);
-        int pf_r0 = 0, pf_nr = 0;
-        if (more) {
-            const int top = min(nx.hi, ch.lo + R);
-            pf_r0 = max(loaded, nx.lo);
-            if (top > pf_r0) {
-                pf_nr = top - pf_r0;
-                loaded = top;
-            }
-        }
-        int pfc = rr0;
+        RowChunk nx = ch;
+        if (more) nx = ring.chunk_at(gnext);
+        int pf_r0, pf_nr;
+        ring.next_window(ch, nx, more, loaded, pf_r0, pf_nr);
+        int pfc = ring.rr0;
         auto prefetch = [&](int count) {
-            if (issue_pieces(pf_r0, pf_nr, pfc, count) > 0) nstores = 0;
+            if (ring.issue_pieces(pf_r0, pf_nr, pfc, count) > 0) nstores = 0;
         };
         char *outb = p.out + (((size_t)ch.b * (Ho + 2) + 1) * (Wo + 2) + 1) * (size_t)p.out_pb + p.out_off + cb * CPB * 2;    // wave-uniform
         const int rbase = ch.b * (H + 2);
 
-        auto locate = [&](int grp, int &oy, int &ox) {
-            const int pc = min(grp * 16 + li, npw - 1);            // padding lanes of an image's last group repeat its last pixel
-            oy = (int)(((float)pc + 0.5f) * invWo);                // pc / Wo (exact: pc < 2^16)
-            ox = pc - oy * Wo;
-        };
         auto mfma = [&](const v4i &wa, const v4i &b, const v4f &c) {
             return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, wa), __builtin_bit_cast(v8bf, b), c, 0, 0, 0);
         };
         auto issue = [&](int grp, v4f (&acc)[NV][NTN]) {
             int oy, ox;
-            locate(grp, oy, ox);
+            ring.locate(grp, oy, ox);
             const int ar = rbase + MUL * oy, x0 = MUL * ox;
             constexpr int NC = POOL ? 4 : 3;
             int xoff[NC], roff[NC];
 #pragma unroll
             for (int c = 0; c < NC; ++c) {
-                const int x = x0 + c;
-                int sch = g;
-                if constexpr (CPX == 4) sch ^= ((x >> 2) & 1) << 1;
-                if constexpr (CPX == 8) sch ^= ((x >> 1) & 3) << 1;
-                xoff[c] = x * PXB + 16 * sch;
+                xoff[c] = Ring::read_off(x0 + c, g);
                 roff[c] = ((ar + c) & RM) * rowb;
             }
 #pragma unroll
@@ -275,7 +177,7 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpxb_kernel(const Co
         };
         auto finish = [&](int grp, const v4f (&acc)[NV][NTN]) {
             int oy, ox;
-            locate(grp, oy, ox);
+            ring.locate(grp, oy, ox);
             unsigned int word[NTN][2];
 #pragma unroll
             for (int n = 0; n < NTN; ++n) {
@@ -286,8 +188,8 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpxb_kernel(const Co
                     if constexpr (POOL) t = fmaxf(fmaxf(t, acc[1][n][r]), fmaxf(acc[2][n][r], acc[3][n][r]));   // the max commutes with the monotone LeakyReLU
                     y[r] = fmaxf(t, t * slope);                    // LeakyReLU for 0 <= slope <= 1 (launcher); slope 1: identity
                 }
-                word[n][0] = pk2(y[0], y[1]);
-                word[n][1] = pk2(y[2], y[3]);
+                word[n][0] = pk_bf16(y[0], y[1]);
+                word[n][1] = pk_bf16(y[2], y[3]);
             }
             // unconditional: the padding lanes rewrite the image's last pixel with the same bytes, and the number of stores a
             // wave has in flight stays a function of its group count (the counted wait above)
@@ -348,24 +250,8 @@ template <int PXB, int NTN, int NCB, bool POOL, int NW>
 struct PbInst {
     using G = PbGeom<PXB, NTN, NCB, POOL>;
     static constexpr int NPS = NW / NCB;
-    static PbArgs args(const ConvGParams &p, int rounds) {
-        PbArgs a;
-        const int Ho = POOL ? p.H / 2 : p.H, Wo = POOL ? p.W / 2 : p.W;
-        a.ngi = (Ho * Wo + 15) / 16;
-        a.total_groups = a.ngi * p.B;
-        a.cg = rounds * NPS;
-        a.pwl = (p.W + 2 + G::PPP - 1) / G::PPP * G::PPP;
-        const int rows2 = (2 * 16 * a.cg + Wo - 1) / Wo + 1;
-        const int need = (POOL ? 2 : 1) * rows2 + 2;
-        a.logr = 2;
-        while ((1 << a.logr) < need) ++a.logr;
-        const int newrows = (POOL ? 2 : 1) * ((16 * a.cg + Wo - 1) / Wo + 1);
-        const int ppr = a.pwl / G::PPP, rs = ppr < NW ? NW / ppr : 1, cpw = ppr < NW ? 1 : (ppr + NW - 1) / NW;
-        const int per_wave = (newrows + rs - 1) / rs * cpw;
-        a.ppg = (per_wave + rounds - 1) / rounds;
-        return a;
-    }
-    static size_t lds_bytes(const PbArgs &a) { return ((size_t)a.pwl * PXB) << a.logr; }
+    static RowRingArgs args(const ConvGParams &p, int rounds) { return rowring_args<PXB, NW, NPS, POOL>(p.B, p.H, p.W, rounds); }
+    static size_t lds_bytes(const RowRingArgs &a) { return rowring_lds_bytes<PXB>(a); }
     static bool launch(const ConvGParams &p, int rounds, hipStream_t s) {
         const int Wo = POOL ? p.W / 2 : p.W;
         if (p.in_pb != PXB || !p.out_halo || p.out_f32 || p.res || p.taps != 9 || !p.bias_f || p.W < 16 || Wo < 1) return false;
@@ -375,7 +261,7 @@ struct PbInst {
         if ((long long)p.B * (p.H + 2) * (p.W + 2) * PXB >= (1ll << 31)) return false;      // 32-bit row arithmetic
         // the largest chunk (groups per pixel stream: `rounds` at most) whose ring of whole padded rows fits LDS -- a bf16 row is twice
         // an int8 row, so the shapes of this network take about half of convpx.hip's chunk; a map too wide for any chunk is declined
-        PbArgs a = args(p, rounds);
+        RowRingArgs a = args(p, rounds);
         while (lds_bytes(a) > 160 * 1024 && rounds > 1) a = args(p, --rounds);
         if (lds_bytes(a) > 160 * 1024) return false;
         int grid = y355_cu_count();                                // one NW-wave workgroup per CU

@@ -15,7 +15,7 @@
 // of a lane's four adjacent channels straight from registers (16 lanes = one 128-byte line of a pixel); int8 -- convg.hip's
 // integer pipeline (32-bit form where the host proved it fits, else 64-bit), 4-byte stores, saturation counted; 2x2 max first
 // on pooled tiles; the store count per tile is static (rows outside the map go to a sink) so that the next tile's counted waits hold.
-#include "y355_common.h"
+#include "y355_dev.h"
 #include <mutex>
 #include <hip/hip_ext.h>
 #include <type_traits>
@@ -24,33 +24,7 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 
 namespace {
-__device__ __forceinline__ void fglds16(const void *g, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-__device__ __forceinline__ void fwait_vmcnt_dyn(int n) {
-#define FW_CASE(k) case k: asm volatile("s_waitcnt vmcnt(" #k ")" ::: "memory"); break;
-    switch (n < 0 ? 0 : (n > 63 ? 63 : n)) {
-        FW_CASE(0) FW_CASE(1) FW_CASE(2) FW_CASE(3) FW_CASE(4) FW_CASE(5) FW_CASE(6) FW_CASE(7) FW_CASE(8) FW_CASE(9)
-        FW_CASE(10) FW_CASE(11) FW_CASE(12) FW_CASE(13) FW_CASE(14) FW_CASE(15) FW_CASE(16) FW_CASE(17) FW_CASE(18)
-        FW_CASE(19) FW_CASE(20) FW_CASE(21) FW_CASE(22) FW_CASE(23) FW_CASE(24) FW_CASE(25) FW_CASE(26) FW_CASE(27)
-        FW_CASE(28) FW_CASE(29) FW_CASE(30) FW_CASE(31) FW_CASE(32) FW_CASE(33) FW_CASE(34) FW_CASE(35) FW_CASE(36)
-        FW_CASE(37) FW_CASE(38) FW_CASE(39) FW_CASE(40) FW_CASE(41) FW_CASE(42) FW_CASE(43) FW_CASE(44) FW_CASE(45)
-        FW_CASE(46) FW_CASE(47) FW_CASE(48) FW_CASE(49) FW_CASE(50) FW_CASE(51) FW_CASE(52) FW_CASE(53) FW_CASE(54)
-        FW_CASE(55) FW_CASE(56) FW_CASE(57) FW_CASE(58) FW_CASE(59) FW_CASE(60) FW_CASE(61) FW_CASE(62) FW_CASE(63)
-    }
-#undef FW_CASE
-}
-// slab pieces issued in steps lo..hi (step u issues one when 1 <= (u mod 9) <= ppw); negative steps are the previous tile's
-constexpr int fring_sp(int lo, int hi, int ppw, bool prev) {
-    int n = 0;
-    for (int u = lo; u <= hi; ++u) {
-        if (u < 0 && !prev) continue;
-        const int t = ((u % 9) + 9) % 9;
-        if (t >= 1 && t <= ppw) ++n;
-    }
-    return n;
-}
+using namespace y355dev;
 constexpr int PF = 4;        // ring of PF + 2 = 6 weight slots: divides the k-steps of every multi-chunk layer here (STATIC below)
 }  // namespace
 
@@ -120,7 +94,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void convr_kernel(const ConvGParam
         const int gy = min(y0 + ppy0 + j * PSTEP, H + 1), gx = min(x0 + ppx0, W + 1);
         const char *src = inb + ((size_t)gy * (W + 2) + gx) * CINB + pwithin;   // pad pieces read a valid row too
         char *dst = (q < NPIECE) ? smem + slot * SLABB + q * 1024 : smem + OFF_DUMMY;
-        fglds16(src, dst);
+        glds16(src, dst);
     };
     auto issue_w = [&](int nb, int ks, int slot) {
 #pragma unroll
@@ -129,7 +103,7 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void convr_kernel(const ConvGParam
             const bool ok = f < NFR;
             const char *src = p.w + ((size_t)(nb * KS + ks) * NFR + (ok ? f : 0)) * 1024 + lane * 16;
             char *dst = ok ? smem + OFF_W + slot * WB + f * 1024 : smem + OFF_DUMMY;
-            fglds16(src, dst);
+            glds16(src, dst);
         }
     };
     auto wrap = [](int s) { return s >= WSLOTS ? s - WSLOTS : s; };
@@ -197,8 +171,8 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void convr_kernel(const ConvGParam
         // are W(1..PF), the slab pieces issued with them, and the previous tile's NIT output stores)
         v4i bfb[2][NT];
         v4i afp[2];
-        if (first) fwait_vmcnt_dyn(PF * WPW);
-        else fwait_vmcnt_dyn(PF * WPW + fring_sp(-PF, -1, PPW, true) + NIT);
+        if (first) wait_vmcnt_clamped(PF * WPW);
+        else wait_vmcnt_clamped(PF * WPW + ring_sp(-PF, -1, PPW, true) + NIT);
         __builtin_amdgcn_s_barrier();
         {
             const char *wb0 = smem + OFF_W + (STATIC ? 0 : wq) * WB + (wn * NT) * 1024 + lane * 16;
@@ -217,16 +191,16 @@ __global__ __launch_bounds__(WM * WN * 64, 1) void convr_kernel(const ConvGParam
                 {
                     constexpr int n_slab = (9 - PPW) * WPW;
                     const int lo = s_idx - PF + 1, hi = s_idx - 1;
-                    int n_first = (PF - 1) * WPW + fring_sp(lo, hi, PPW, false);
-                    int n_later = (PF - 1) * WPW + fring_sp(lo, hi, PPW, true) + (s_idx < PF ? NIT : 0);
+                    int n_first = (PF - 1) * WPW + ring_sp(lo, hi, PPW, false);
+                    int n_later = (PF - 1) * WPW + ring_sp(lo, hi, PPW, true) + (s_idx < PF ? NIT : 0);
                     if (t == 0) {
                         if (c > 0 && n_slab < n_first) n_first = n_slab;
                         const int n_slab2 = n_slab + (c == 0 ? NIT : 0);
                         if (n_slab2 < n_later) n_later = n_slab2;
                     }
-                    if (n_first == n_later) fwait_vmcnt_dyn(n_later);
-                    else if (first) fwait_vmcnt_dyn(n_first);
-                    else fwait_vmcnt_dyn(n_later);
+                    if (n_first == n_later) wait_vmcnt_clamped(n_later);
+                    else if (first) wait_vmcnt_clamped(n_first);
+                    else wait_vmcnt_clamped(n_later);
                 }
                 __builtin_amdgcn_s_barrier();
                 // refill: one slab piece (t = 1..PPW) into the slot that died two barriers ago, W(s+1+PF) into the ring slot

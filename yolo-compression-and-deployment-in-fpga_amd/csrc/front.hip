@@ -16,15 +16,14 @@
 //     then holds FOUR CHANNELS of ONE window in an accumulator, the pool is an element-wise max over the four MFMA
 //     results (no cross-lane step), and the int8 results leave as one packed ds_write_b32 / b64 per lane;
 //   * the biases ride in as the MFMAs' C operand (when the layer's accumulator shift is zero: template FOLD);
-//   * the requantisation runs in fp32 on exact integers: t < 2^24 (host-checked, Requant::tmax_log2), so
-//         q = low byte of med3(max(fma(t, 2^(lk-sh), M), fma(t, 2^-sh, M)), M - 127, M + 127),   M = 1.5 * 2^23
-//     is RNE(t' * 2^-sh) clamped, bit for bit the integer pipeline of DESIGN.md section 2: the fma rounds the exact
-//     product once, to the integer grid of [2^23, 2^24), ties to even; five VALU operations instead of eight;
+//   * the requantisation runs in fp32 on exact integers, t < 2^24 (host-checked, Requant::tmax_log2): two fma and a max
+//     per output, five VALU operations instead of eight, bit for bit the integer pipeline of DESIGN.md section 2
+//     (y355_fp32epi.h has the form and its proof);
 //   * the input quantisation uses the same fma: q = low byte of fma(x, 2^sa0, M); three values are packed with two
 //     v_perm_b32; clamped inputs are detected from max |x| and handled (and counted exactly) in a cold pass.
 // Integer semantics are those of conv1.hip / conv3x3.hip, bit for bit; saturation is detected with one op per output
 // and counted exactly (own pixels only) in a cold second pass.
-#include "y355_common.h"
+#include "y355_fp32epi.h"
 #include <type_traits>
 #include <cstring>
 #include <cmath>
@@ -42,6 +41,7 @@
 #endif
 
 namespace {
+using namespace y355dev;
 constexpr int TOY = 13, TOX = 13;                    // pooled conv2 outputs per tile
 constexpr int P1H = 2 * TOY + 2, P1W = 2 * TOX + 2;  // pooled conv1 tile with its halo (windows of conv1)
 constexpr int PH0 = 2 * P1H + 2;                     // input patch rows (= columns used)
@@ -53,131 +53,18 @@ constexpr int BW1 = P1W / 4, BH1 = P1H / 4;          // blocks per row / rows of
 constexpr int NW2 = TOY * TOX;                       // 169 conv2 windows = 11 groups of 16 (7 padding slots)
 constexpr int NG2 = (NW2 + 15) / 16;
 constexpr int QITEMS = 4;                            // input items (row, 4-pixel group) per thread: 16 wave-items of 4 rows
-constexpr float MAGIC = 12582912.0f;                 // 1.5 * 2^23
-constexpr float QLO = 12582785.0f, QHI = 12583039.0f;   // MAGIC -+ 127
 static_assert(P1H % 4 == 0 && P1W % 4 == 0 && PH0 <= 4 * 4 * QITEMS && P0 % 4 == 0 && P0 >= PH0 + 2, "front geometry");
 
-__device__ __forceinline__ void front_lds_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-// bare instructions: hipcc canonicalises (quiets) both operands of fmaxf / fabsf chains
-__device__ __forceinline__ float vmax(float a, float b) {
-    float d;
-    asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
+// bare instruction: hipcc canonicalises (quiets) both operands of fmaxf / fabsf chains
 __device__ __forceinline__ float vmax3abs(float a, float b, float c) {      // max(a, |b|, |c|)
     float d;
     asm("v_max3_f32 %0, %1, |%2|, |%3|" : "=v"(d) : "v"(a), "v"(b), "v"(c));
     return d;
 }
-__device__ __forceinline__ float vmax3(float a, float b, float c) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ float vmin3(float a, float b, float c) {
-    float d;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-// lane i of each row of 16 lanes receives lane i + 1's value (lane 15: zero)
-__device__ __forceinline__ unsigned int row_next(unsigned int v) {
-    return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x101 /* row_shl:1 */, 0xf, 0xf, true);
-}
-// bytes 0 of four registers -> one dword
-__device__ __forceinline__ unsigned int pack4(float a, float b, float c, float d) {
-    const unsigned int ab = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x0c0c0400u);
-    const unsigned int cd = __builtin_amdgcn_perm(__float_as_uint(d), __float_as_uint(c), 0x04000c0cu);
-    return ab | cd;
-}
 // (r, g, b) bytes 0 -> pixel word (r, g, b, 0)
 __device__ __forceinline__ unsigned int pack3(float r, float g, float b) {
     const unsigned int rg = __builtin_amdgcn_perm(__float_as_uint(g), __float_as_uint(r), 0x0c0c0400u);
     return __builtin_amdgcn_perm(__float_as_uint(b), rg, 0x0c040100u);
-}
-
-// fp32 form of the epilogue of one layer (see the header): q = low byte of yc
-// FOLD (accumulator shift 0, |t| < 2^22, |sh| small: y355_launch_front): the MFMAs' C operand is bias + 0x4B400000, so the
-// int32 accumulator IS the bit pattern of the float M + t (no v_cvt), and M + t * s = fma(M + t, s, M * (1 - s)) exactly
-// (M * (1 - s) is representable for 2^-22 <= s <= 2^8).
-struct RqF {
-    float s_pos, s_neg;      // 2^(lk - sh), neg_mul * 2^-sh
-    float scl;               // !FOLD: 2^shl
-};
-template <bool FOLD>
-__device__ __forceinline__ RqF make_rqf(const Requant &rq) {
-    RqF r;
-    // wave-uniform: the two scales wait in SGPRs between the phases that use them
-    r.s_pos = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ldexpf(1.0f, rq.lk - rq.sh))));
-    r.s_neg = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)rq.neg_mul * ldexpf(1.0f, -rq.sh))));
-    r.scl = ldexpf(1.0f, rq.shl);
-    return r;
-}
-// pooled accumulator -> the two branches of the LeakyReLU, each M + rne(t * scale), unclamped.  y = max(pos, neg) (RNE is
-// monotone: round(max) = max(round)); with 0 <= s_neg <= s_pos (y355_front_eligible): t >= 0 -> pos >= neg >= M, t < 0 ->
-// pos <= neg <= M, so  y > M + 127 <=> pos > M + 127  and  y < M - 127 <=> neg < M - 127.
-// The scales and addends are VGPR operands on purpose: an SGPR source takes a vector instruction off the fast issue path
-// (scratch/ubench/valu_rates.hip: v_fma_f32 3.0 cycles per SIMD with VGPR sources, 4.6 with one SGPR source).
-struct RqV {
-    float sp, sn, cp, cn;    // the scales; the addends: FOLD M * (1 - s), else M
-};
-template <bool FOLD>
-__device__ __forceinline__ RqV make_rqv(const RqF &r) {
-    RqV v = {r.s_pos, r.s_neg, FOLD ? MAGIC - MAGIC * r.s_pos : MAGIC, FOLD ? MAGIC - MAGIC * r.s_neg : MAGIC};
-    asm volatile("" : "+v"(v.sp), "+v"(v.sn), "+v"(v.cp), "+v"(v.cn));
-    return v;
-}
-template <bool FOLD>
-__device__ __forceinline__ void rq_pair(int m, float biasf, const RqF &r, const RqV &v, float &pos, float &neg) {
-    const float tf = FOLD ? __int_as_float(m) : fmaf((float)m, r.scl, biasf);   // (float)m exact: |t| < 2^24
-    pos = fmaf(tf, v.sp, v.cp);
-    neg = fmaf(tf, v.sn, v.cn);
-}
-// byte B of w = bits [7:0] of max(a, b), the other bytes kept (B = 0: zeroed): the LeakyReLU's max and the int8 pack in one
-// SDWA instruction per output (the same issue cost as the plain v_max_f32)
-template <int B>
-__device__ __forceinline__ void max_to_byte(unsigned int &w, float a, float b) {
-    if constexpr (B == 0)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD" : "=v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 1)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 2)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-}
-// The epilogue of four pooled accumulators of one lane -> packed int8 word.
-//   hot (CLAMP = false): unclamped low bytes; ymx / ymn track the branches that can leave [-127, 127] (two ops per four outputs each)
-//   CLAMP: clamped bytes; nbad = outputs that were clamped
-//   NEGSAFE (y355_launch_front: no accumulator the weights allow can drive the negative branch below -127): ymn is not tracked
-template <bool FOLD, bool CLAMP, bool NEGSAFE>
-__device__ __forceinline__ unsigned int rq_word(const int (&m)[4], const float (&biasf)[4], const RqF &r, const RqV &v, float &ymx,
-                                                float &ymn, unsigned int &nbad) {
-    float pos[4], neg[4];
-#pragma unroll
-    for (int q = 0; q < 4; ++q) rq_pair<FOLD>(m[q], biasf[q], r, v, pos[q], neg[q]);
-    unsigned int w;
-    if constexpr (!CLAMP) {
-        ymx = vmax3(vmax3(ymx, pos[0], pos[1]), pos[2], pos[3]);
-        if constexpr (!NEGSAFE) ymn = vmin3(vmin3(ymn, neg[0], neg[1]), neg[2], neg[3]);
-        max_to_byte<0>(w, pos[0], neg[0]);
-        max_to_byte<1>(w, pos[1], neg[1]);
-        max_to_byte<2>(w, pos[2], neg[2]);
-        max_to_byte<3>(w, pos[3], neg[3]);
-    } else {
-        float yc[4];
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            const float y = vmax(pos[q], neg[q]);
-            yc[q] = __builtin_amdgcn_fmed3f(y, QLO, QHI);
-            nbad += y != yc[q] ? 1u : 0u;
-        }
-        w = pack4(yc[0], yc[1], yc[2], yc[3]);
-    }
-    return w;
 }
 }  // namespace
 
@@ -203,7 +90,8 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
     // ---- nothing but a few constants stays in registers across phases: the weight fragments and biases (16 KiB + 192 B,
     // L2-resident) are re-read per tile just ahead of the phase that uses them (128 registers per lane at four workgroups per CU)
     const Requant rq1 = p.rq1, rq2 = p.rq2;
-    const RqF f1 = make_rqf<FOLD>(rq1), f2 = make_rqf<FOLD>(rq2);
+    constexpr int FOLDC = FOLD ? 2 : 0;                // y355_fp32epi.h's fold class: this kernel has no class 1
+    const EpiScales f1 = epi_scales(rq1), f2 = epi_scales(rq2);
     if constexpr (U8) {
         // normalise + quantise is a function of the byte: per channel a 256-entry table built with the reference's
         // fp32 operations in the reference's order ((u/255 - mean)/std, data/__init__.py:43-45; round(x * 2^sa),
@@ -238,7 +126,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
         *(v4i *)(wl + tid * 16) = *(const v4i *)(p.wf + tid * 16);
         if (tid < 4) *(v4i *)(wl + 4096 + 16 * tid) = *(const v4i *)(p.bias1 + 4 * tid);
     }
-    front_lds_barrier();                                // the table / the fragments are complete
+    lds_barrier();                                // the table / the fragments are complete
     unsigned int nsat_in = 0, nsat1 = 0, nsat2 = 0;
 
     // ---- a tile's input patch: QITEMS x (3 x float4 | 12 bytes) per thread, all in flight together.  (Issuing the next
@@ -401,7 +289,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
             b1v = *(const v4i *)(p.bias1 + 4 * g_);
         }
         stamp();
-        front_lds_barrier();                              // B1: patch complete
+        lds_barrier();                              // B1: patch complete
         stamp();
         if constexpr (!U8) {
 #pragma unroll
@@ -440,7 +328,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
             constexpr bool CLAMP = COLD || !FRONT_HOTCOLD, WRITE = !COLD || FRONT_HOTCOLD;
             unsigned int satx = 0;
             float ymx = MAGIC, ymn = MAGIC;
-            const RqV v1 = make_rqv<FOLD>(f1);
+            const EpiOps v1 = epi_ops<FOLDC>(f1);
             auto body = [&](int r2, int bx) {                      // hot: compile-time (unrolled); cold: scalars
                 // two ds_read_b64 (2 LDS cycles each, 64 banks, 32-lane groups: conflict-free with P0 = 8 mod 64), not the
                 // ds_read2_b64 the compiler merges plain loads into (8 cycles, 32 banks, 16-lane groups: 2-way conflicts on top)
@@ -456,7 +344,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
 #pragma unroll
                 for (int r = 0; r < 4; ++r) m[r] = max(max(a0[r], a1[r]), max(a2[r], a3[r]));
                 unsigned int nbad = 0;
-                unsigned int word = rq_word<FOLD, CLAMP, NEGSAFE>(m, bf1, f1, v1, ymx, ymn, nbad);
+                unsigned int word = epi_word<FOLDC, CLAMP, NEGSAFE>(m, bf1, f1, v1, true, ymx, ymn, nbad);
                 if constexpr (!COLD) {
                     if constexpr (!FRONT_HOTCOLD) satx += nbad;
                 } else {
@@ -517,7 +405,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
                     w2[n][ky][dx] = *(const v4i *)(p.wf + 4096 + ((3 * n + ky) * 2 + dx) * 1024 + lane_ * 16);
         const v4i b2v[2] = {*(const v4i *)(p.bias2 + 8 * g_), *(const v4i *)(p.bias2 + 8 * g_ + 4)};   // channel 8 g + 4 n + r
         stamp();
-        front_lds_barrier();                              // B2: p1 complete
+        lds_barrier();                              // B2: p1 complete
         stamp();
 
         // ---- C2: conv2 + pool2 -> staged int8 tile.  Group = 16 consecutive windows of the 13 x 13 grid (the last group's
@@ -529,7 +417,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
             constexpr bool CLAMP = COLD || !FRONT_HOTCOLD, WRITE = !COLD || FRONT_HOTCOLD;
             unsigned int satx = 0;
             float ymx = MAGIC, ymn = MAGIC;
-            const RqV v2 = make_rqv<FOLD>(f2);
+            const EpiOps v2 = epi_ops<FOLDC>(f2);
             v4i cin2[2];
             float bf2[2][4];
 #pragma unroll
@@ -571,7 +459,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
                     int m[4];
 #pragma unroll
                     for (int r = 0; r < 4; ++r) m[r] = max(max(acc[0][0][r], acc[0][1][r]), max(acc[1][0][r], acc[1][1][r]));
-                    word[n] = rq_word<FOLD, CLAMP, NEGSAFE>(m, bf2[n], f2, v2, ymx, ymn, nbad);
+                    word[n] = epi_word<FOLDC, CLAMP, NEGSAFE>(m, bf2[n], f2, v2, true, ymx, ymn, nbad);
                 }
                 if constexpr (!COLD) {
                     if constexpr (!FRONT_HOTCOLD) satx += nbad;
@@ -586,7 +474,7 @@ __global__ __launch_bounds__(256, FRONT_OCC) void front_kernel(const FrontParams
         };
         if (__builtin_amdgcn_ballot_w64(c2(FF{}) != 0) != 0ull) nsat2 += c2(TT{});
         stamp();
-        front_lds_barrier();                              // B3: staged tile complete
+        lds_barrier();                              // B3: staged tile complete
         stamp();
 
         // ---- OUT: NHWC32 with halo, 16 bytes per thread and item (item = 2 * window + half)
@@ -652,11 +540,9 @@ void y355_pack_front(const int8_t *q_w1 /*[16][3][3][3]*/, const int8_t *q_w2 /*
     }
 }
 
-// true when the fused launch covers these two layers: 32-bit epilogues whose t stays below 2^24 (exact in fp32)
-// and a LeakyReLU slope in [0, 1] (the epilogue takes max(t * s_pos, t * s_neg) and reads a clamp off the branch that can reach it)
+// true when the fused launch covers these two layers: the fp32 epilogue's host rules (y355_common.h) hold for both
 bool y355_front_eligible(const Requant &rq1, const Requant &rq2) {
-    auto slope_ok = [](const Requant &rq) { return rq.neg_mul >= 0 && rq.neg_mul <= (1 << rq.lk); };
-    return !rq1.wide && !rq2.wide && rq1.tmax_log2 <= 24 && rq2.tmax_log2 <= 24 && slope_ok(rq1) && slope_ok(rq2);
+    return y355_fp32_exact(rq1) && y355_fp32_exact(rq2) && y355_fp32_slope_ok(rq1) && y355_fp32_slope_ok(rq2);
 }
 
 void y355_launch_front(const FrontParams &p, hipStream_t s) {
@@ -666,8 +552,7 @@ void y355_launch_front(const FrontParams &p, hipStream_t s) {
 #endif
     int grid = FRONT_GRID;
     if (grid > total) grid = total;
-    auto foldable = [](const Requant &rq) { return rq.shl == 0 && rq.tmax_log2 <= 22 && rq.sh <= 22 && rq.sh - rq.lk >= -8; };
-    const bool fold = foldable(p.rq1) && foldable(p.rq2);
+    const bool fold = y355_fp32_fold(p.rq1) == 2 && y355_fp32_fold(p.rq2) == 2;
     FrontParams q = p;
     q.ev_start = q.ev_stop = nullptr;
     q.in_thr = 127.5f / p.in_scale;

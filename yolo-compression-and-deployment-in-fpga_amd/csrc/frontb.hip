@@ -17,10 +17,11 @@
 // 512 threads, two workgroups per CU (56.6 KB of LDS each: input patch of 8-byte pixels, conv1's pooled 16-channel map, the
 // staged output aliased onto the patch).  conv2's weight fragments stay in registers for the whole launch (waves 0-3 own
 // output channels {8 g + r}, waves 4-7 {8 g + 4 + r}: 12 fragments each); conv1's eight fragments are read from LDS.
-#include "y355_common.h"
+#include "y355_dev.h"
 #include <cstring>
 
 namespace {
+using namespace y355dev;
 typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int TOY = 13, TOX = 13;                    // pooled conv2 outputs per tile
@@ -34,27 +35,6 @@ constexpr int NW2 = TOY * TOX, NG2 = (NW2 + 15) / 16;   // 169 conv2 windows = 1
 constexpr int NTHR = 512, NWAVE = 8;
 constexpr int W1_BYTES = 8 * 1024, W2_BYTES = 24 * 1024;
 static_assert(NW1 % 16 == 0 && PH0 <= 4 * NWAVE * 2 && P0 >= PH0 + 2, "front geometry");
-
-__device__ __forceinline__ void fb_barrier() {
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();
-    asm volatile("" ::: "memory");
-}
-__device__ __forceinline__ unsigned int row_next(unsigned int v) {        // lane i of each row of 16 lanes gets lane i + 1's value
-    return (unsigned int)__builtin_amdgcn_update_dpp(0, (int)v, 0x101 /* row_shl:1 */, 0xf, 0xf, true);
-}
-// bare instructions: hipcc canonicalises (quiets) both operands of fmaxf chains and turns `m >= 0 ? m : m * s` into a compare + select
-// (v_cndmask on vcc: 22 cycles back to back, profiles/r04_notes.md section 9)
-__device__ __forceinline__ float fb_max(float a, float b) {
-    float d;
-    asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ unsigned int pk_bf16(float a, float b) {       // (a, b) -> two bf16 (RNE), a in the low half
-    typedef __bf16 v2bf __attribute__((ext_vector_type(2)));
-    const v2bf v = {(__bf16)a, (__bf16)b};
-    return __builtin_bit_cast(unsigned int, v);
-}
 }  // namespace
 
 // U8: the input is the camera frame (uint8 HWC BGR, p.x_u8); BaseTransform + BGR->RGB are a per-channel table of the bf16 values
@@ -98,7 +78,7 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
                 w2[ky][dx][h] = *(const v4i *)(p.wf + W1_BYTES + ((((npass * 3 + ky) * 2 + dx) * 2 + h) * 1024) + lane * 16);
     const float4 b2q = *(const float4 *)(p.bias2 + 8 * g + 4 * npass);
     const float b2[4] = {b2q.x, b2q.y, b2q.z, b2q.w};
-    fb_barrier();
+    lds_barrier();
 
     // Q: wave-item q = wave + 8 k covers patch rows 4 q .. 4 q + 3; lane = 16 * (row in the item) + 4-pixel group j (j = 15 idle)
     const int qr0 = 4 * wave + g, qj = li;
@@ -176,7 +156,7 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
                 }
             }
         }
-        fb_barrier();                                       // B1: patch complete
+        lds_barrier();                                       // B1: patch complete
 
         // ---- C1: conv1 + bias + LeakyReLU + pool1 -> p1.  Group = 16 consecutive windows of the 28 x 28 window grid; lane
         // (li, g): window li; MFMA h takes neighbourhood rows 2 h, 2 h + 1: lane group g = (row g >> 1, pixel pair g & 1)
@@ -204,7 +184,7 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
                     // (the pool stays C++: an inline-asm read of an MFMA result gets no hazard wait states from the compiler -- the first
                     // version of this line read accumulators the matrix pipe had not written yet, and two forwards of one input differed)
                     const float m = fmaxf(fmaxf(acc[0][r], acc[1][r]), fmaxf(acc[2][r], acc[3][r])) + b1[r];
-                    y[r] = fb_max(m, m * slope1);
+                    y[r] = vmax(m, m * slope1);
                 }
                 uint2 o = make_uint2(pk_bf16(y[0], y[1]), pk_bf16(y[2], y[3]));
                 if (border) {                                 // windows outside the image: conv2's zero padding
@@ -214,7 +194,7 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
                 *(uint2 *)(p1 + (py * P1P + px) * 32 + 8 * g_) = o;
             }
         }
-        fb_barrier();                                       // B2: p1 complete (and the patch is dead: stg may be written)
+        lds_barrier();                                       // B2: p1 complete (and the patch is dead: stg may be written)
 
         // ---- C2: conv2 + bias + LeakyReLU + pool2 -> staged bf16 tile.  Group = 16 windows of the 13 x 13 grid (the last
         // group's padding slots repeat window 168); neighbourhood row t, MFMA h = pixels 2 h, 2 h + 1: lane group g = (pixel
@@ -250,12 +230,12 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
                     const float m = fmaxf(fmaxf(acc[0][0][r], acc[0][1][r]), fmaxf(acc[1][0][r], acc[1][1][r])) + b2[r];
-                    y[r] = fb_max(m, m * slope2);
+                    y[r] = vmax(m, m * slope2);
                 }
                 *(uint2 *)(stg + wraw * 64 + 16 * g_ + 8 * npass) = make_uint2(pk_bf16(y[0], y[1]), pk_bf16(y[2], y[3]));
             }
         }
-        fb_barrier();                                       // B3: staged tile complete
+        lds_barrier();                                       // B3: staged tile complete
 
         // ---- OUT: NHWC (32 bf16 channels at the head of a pixel of out_pb bytes) with halo, 16 bytes per thread and item
         {
@@ -275,7 +255,7 @@ __global__ __launch_bounds__(512, 4) void frontb_kernel(const FrontBParams p, co
         ty += p.step_y;
         if (ty >= p.tiles_y) { ty -= p.tiles_y; ++b; }
         b += p.step_b;
-        fb_barrier();                                       // B4: the staged tile (= the patch) has been read out
+        lds_barrier();                                       // B4: the staged tile (= the patch) has been read out
     }
 }
 

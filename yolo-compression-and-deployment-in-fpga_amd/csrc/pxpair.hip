@@ -24,73 +24,20 @@
 //     immediate -- 5 vector adds per row instead of ~70 address instructions per group in convpx's flat walk;
 //   * input rows (32-byte pixels) arrive by LDS-DMA into a ring of 12 rows, one interval ahead (the conv3_1 role waits for its own DMA with
 //     vmcnt(0): it issues no other vector-memory operation).
-// Epilogues: front.hip's fp32 form on exact integers, FOLD 1 / 2 per layer; the hot passes do not clamp and
+// Epilogues: the fp32 form on exact integers (y355_fp32epi.h), FOLD 1 / 2 per layer; the hot passes do not clamp and
 // track the LeakyReLU branches' extremes, a cold pass redoes a wave's share clamped and counts (per layer, and for conv3_1 only
 // on the rows the band owns) when a value left [-127, 127].  Integer semantics bit for bit those of convpx.hip.
-#include "y355_common.h"
+#include "y355_fp32epi.h"
 #include <cstring>
 #include <type_traits>
 
 namespace {
-constexpr float MAGIC = 12582912.0f;                 // 1.5 * 2^23
-constexpr float QLO = 12582785.0f, QHI = 12583039.0f;
+using namespace y355dev;
 constexpr int RMID = 16;                             // map ring, rows (power of two: phase B's lanes mask)
 constexpr int RIN = 12;                              // input ring, rows (scalar modulo)
 constexpr int NGMAX = 7;                             // 16-pixel groups per map row: W <= 112
 typedef unsigned int v2u __attribute__((ext_vector_type(2)));     // (a uint2 store into LDS gets an s_waitcnt vmcnt(0) in front of it: the
                                                                   // compiler cannot tell it from an LDS-DMA destination; an ext_vector store does not)
-
-__device__ __forceinline__ void qglds16(const void *g, void *lds) {
-    __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
-                                     (__attribute__((address_space(3))) void *)lds, 16, 0, 0);
-}
-__device__ __forceinline__ float qvmax(float a, float b) {
-    float d;
-    asm("v_max_f32 %0, %1, %2" : "=v"(d) : "v"(a), "v"(b));
-    return d;
-}
-__device__ __forceinline__ float qvmax3(float a, float b, float c) {
-    float d;
-    asm("v_max3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-__device__ __forceinline__ float qvmin3(float a, float b, float c) {
-    float d;
-    asm("v_min3_f32 %0, %1, %2, %3" : "=v"(d) : "v"(a), "v"(b), "v"(c));
-    return d;
-}
-template <int B>
-__device__ __forceinline__ void qmax_to_byte(unsigned int &w, float a, float b) {
-    if constexpr (B == 0)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_0 dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:DWORD" : "=v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 1)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_1 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else if constexpr (B == 2)
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_2 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-    else
-        asm("v_max_f32_sdwa %0, %1, %2 dst_sel:BYTE_3 dst_unused:UNUSED_PRESERVE src0_sel:DWORD src1_sel:DWORD" : "+v"(w) : "v"(a), "v"(b));
-}
-__device__ __forceinline__ unsigned int qpack4(float a, float b, float c, float d) {
-    const unsigned int ab = __builtin_amdgcn_perm(__float_as_uint(b), __float_as_uint(a), 0x0c0c0400u);
-    const unsigned int cd = __builtin_amdgcn_perm(__float_as_uint(d), __float_as_uint(c), 0x04000c0cu);
-    return ab | cd;
-}
-// the fp32 epilogue's constants of one layer (VGPR operands: an SGPR source takes a vector instruction off the fast issue path)
-struct Epi {
-    float sp, sn, cp, cn;
-};
-template <int FOLD>
-__device__ __forceinline__ Epi make_epi(const Requant &rq) {
-    const float s_pos = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int(ldexpf(1.0f, rq.lk - rq.sh))));
-    const float s_neg = __int_as_float(__builtin_amdgcn_readfirstlane(__float_as_int((float)rq.neg_mul * ldexpf(1.0f, -rq.sh))));
-    Epi e;
-    e.sp = s_pos;
-    e.sn = s_neg;
-    e.cp = FOLD == 2 ? MAGIC - MAGIC * s_pos : MAGIC;
-    e.cn = FOLD == 2 ? MAGIC - MAGIC * s_neg : MAGIC;
-    asm volatile("" : "+v"(e.sp), "+v"(e.sn), "+v"(e.cp), "+v"(e.cn));
-    return e;
-}
 }  // namespace
 
 #ifndef PAIR_ABL
@@ -146,7 +93,7 @@ __global__ __launch_bounds__(512, 2) void pxpair3r_kernel(const PairParams p) {
             const int rr = q / PPR, pc = q - rr * PPR, row = ra + rr;
             const int px = min(pc * 32 + (lane >> 1), W + 1);
             const int8_t *src = p.in + ((size_t)(b * (H + 2) + row) * (W + 2) + px) * 32 + (lane & 1) * 16;
-            qglds16(src, inp + (row % RIN) * IPITCH + pc * 1024);
+            glds16(src, inp + (row % RIN) * IPITCH + pc * 1024);
         }
     };
     const int G_ = gridDim.x, Rtot = p.B * Ho;
@@ -190,7 +137,8 @@ __global__ __launch_bounds__(512, 2) void pxpair3r_kernel(const PairParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) cina[n][r] = F1 == 2 ? b1[r] + 0x4B400000 : b1[r];
         }
-        const Epi e1 = make_epi<F1>(p.rq1);
+        const EpiScales s1 = epi_scales(p.rq1);
+        const EpiOps e1 = epi_ops<F1>(s1);
         // lane constants: a lane stores its pixel's whole 16-byte chunk g
         int cl[5];
 #pragma unroll
@@ -241,27 +189,22 @@ __global__ __launch_bounds__(512, 2) void pxpair3r_kernel(const PairParams p) {
                             auto out2 = [&](const v4i (&acc)[4], v4i &word, int n_, int rr, bool cok) {
                                 float pos[2], neg[2];
     #pragma unroll
-                                for (int u = 0; u < 2; ++u) {
-                                    const int v = acc[n_][2 * rr + u];
-                                    const float tf = F1 == 2 ? __int_as_float(v) : (float)v;
-                                    pos[u] = fmaf(tf, e1.sp, e1.cp);
-                                    neg[u] = fmaf(tf, e1.sn, e1.cn);
-                                }
+                                for (int u = 0; u < 2; ++u) epi_pair<F1>(acc[n_][2 * rr + u], 0.f, s1, e1, pos[u], neg[u]);
                                 unsigned int w = (unsigned int)word[n_];
                                 if constexpr (!COLD) {
-                                    ymx = qvmax3(ymx, pos[0], pos[1]);
-                                    ymn = qvmin3(ymn, neg[0], neg[1]);
+                                    ymx = vmax3(ymx, pos[0], pos[1]);
+                                    ymn = vmin3(ymn, neg[0], neg[1]);
                                     if (rr == 0) {
-                                        qmax_to_byte<0>(w, pos[0], neg[0]);
-                                        qmax_to_byte<1>(w, pos[1], neg[1]);
+                                        max_to_byte<0>(w, pos[0], neg[0]);
+                                        max_to_byte<1>(w, pos[1], neg[1]);
                                     } else {
-                                        qmax_to_byte<2>(w, pos[0], neg[0]);
-                                        qmax_to_byte<3>(w, pos[1], neg[1]);
+                                        max_to_byte<2>(w, pos[0], neg[0]);
+                                        max_to_byte<3>(w, pos[1], neg[1]);
                                     }
                                 } else {
     #pragma unroll
                                     for (int u = 0; u < 2; ++u) {
-                                        const float y = qvmax(pos[u], neg[u]), yc = __builtin_amdgcn_fmed3f(y, QLO, QHI);
+                                        const float y = vmax(pos[u], neg[u]), yc = __builtin_amdgcn_fmed3f(y, QLO, QHI);
                                         nsat += (cok && y != yc) ? 1u : 0u;
                                         const unsigned int by = __float_as_uint(yc) & 0xffu;
                                         w = (rr == 0 && u == 0) ? by : (w | (by << (8 * (2 * rr + u))));
@@ -360,7 +303,8 @@ __global__ __launch_bounds__(512, 2) void pxpair3r_kernel(const PairParams p) {
 #pragma unroll
             for (int r = 0; r < 4; ++r) cinb[n][r] = F2 == 2 ? b2[r] + 0x4B400000 : b2[r];
         }
-        const Epi e2 = make_epi<F2>(p.rq2);
+        const EpiScales s2 = epi_scales(p.rq2);
+        const EpiOps e2 = epi_ops<F2>(s2);
         const float invWo = 1.0f / (float)Wo;
         for (int r0 = rbeg; r0 < rend;) {
             const int b = bd.b, j0 = bd.j0, j1 = bd.j1;
@@ -450,31 +394,10 @@ __global__ __launch_bounds__(512, 2) void pxpair3r_kernel(const PairParams p) {
                         unsigned int word[2];
     #pragma unroll
                         for (int n = 0; n < 2; ++n) {
-                            float pos[4], neg[4];
+                            int m[4];
     #pragma unroll
-                            for (int r = 0; r < 4; ++r) {
-                                const int m = max(max(acc[0][n][r], acc[1][n][r]), max(acc[2][n][r], acc[3][n][r]));
-                                const float tf = F2 == 2 ? __int_as_float(m) : (float)m;
-                                pos[r] = fmaf(tf, e2.sp, e2.cp);
-                                neg[r] = fmaf(tf, e2.sn, e2.cn);
-                            }
-                            if constexpr (!COLD) {
-                                zmx = qvmax3(qvmax3(zmx, pos[0], pos[1]), pos[2], pos[3]);
-                                zmn = qvmin3(qvmin3(zmn, neg[0], neg[1]), neg[2], neg[3]);
-                                qmax_to_byte<0>(word[n], pos[0], neg[0]);
-                                qmax_to_byte<1>(word[n], pos[1], neg[1]);
-                                qmax_to_byte<2>(word[n], pos[2], neg[2]);
-                                qmax_to_byte<3>(word[n], pos[3], neg[3]);
-                            } else {
-                                float yc[4];
-    #pragma unroll
-                                for (int r = 0; r < 4; ++r) {
-                                    const float y = qvmax(pos[r], neg[r]);
-                                    yc[r] = __builtin_amdgcn_fmed3f(y, QLO, QHI);
-                                    nsat += (grp * 16 + li < nwin && y != yc[r]) ? 1u : 0u;
-                                }
-                                word[n] = qpack4(yc[0], yc[1], yc[2], yc[3]);
-                            }
+                            for (int r = 0; r < 4; ++r) m[r] = max(max(acc[0][n][r], acc[1][n][r]), max(acc[2][n][r], acc[3][n][r]));
+                            word[n] = epi_word<F2, COLD, false>(m, {0.f, 0.f, 0.f, 0.f}, s2, e2, grp * 16 + li < nwin, zmx, zmn, nsat);
                         }
                         int8_t *dst = outb + (((j0 + oyr) * (Wo + 2) + ox) * 64 + 8 * g);
                         *(v2u *)dst = (v2u){word[0], word[1]};
@@ -518,10 +441,6 @@ size_t pair_lds(int W) {
     const int MPITCH = 4 * (W + 2) * 16, IPITCH = ((W + 2 + 31) >> 5) * 1024;
     return (size_t)RMID * MPITCH + (size_t)RIN * IPITCH + 1024;    // + one piece: the last group's lanes past the row end read (and discard) it
 }
-int fold_of(const Requant &rq) {
-    if (rq.shl != 0) return 0;
-    return (rq.tmax_log2 <= 22 && rq.sh <= 22 && rq.sh - rq.lk >= -8) ? 2 : 1;
-}
 template <int F1, int F2>
 void launch_(const PairParams &p, int grid, size_t lds, hipStream_t s) {
     PairParams q = p;
@@ -542,8 +461,7 @@ int y355_prepare_pair3(void) {
 // with the accumulator shift 0, a map narrow enough for the two rings
 bool y355_pair3_eligible(const Requant &rq1, const Requant &rq2, int H, int W) {
     for (const Requant *rq : {&rq1, &rq2}) {
-        if (rq->wide || rq->tmax_log2 > 24 || fold_of(*rq) == 0) return false;
-        if (rq->neg_mul < 0 || rq->neg_mul > (1 << rq->lk)) return false;
+        if (!y355_fp32_exact(*rq) || !y355_fp32_slope_ok(*rq) || y355_fp32_fold(*rq) == 0) return false;
     }
     if ((H | W) & 1 || W < 16 || W > 16 * NGMAX || H < 2) return false;
     return pair_lds(W) <= 160 * 1024;
@@ -558,7 +476,7 @@ bool y355_launch_pair3(const PairParams &p, hipStream_t s) {
     if (p.grid_limit > 0 && p.grid_limit < grid) grid = p.grid_limit;
     if (grid > total) grid = total;
     const size_t lds = pair_lds(p.W);
-    const int f1 = fold_of(p.rq1), f2 = fold_of(p.rq2);
+    const int f1 = y355_fp32_fold(p.rq1), f2 = y355_fp32_fold(p.rq2);
     if (f1 == 2 && f2 == 2) launch_<2, 2>(p, grid, lds, s);
     else if (f1 == 2) launch_<2, 1>(p, grid, lds, s);
     else if (f2 == 2) launch_<1, 2>(p, grid, lds, s);

@@ -42,15 +42,19 @@ struct Requant {
     // 1: the general slope fits 32 bits (host-checked: |t| * max(2^max(0, lk - sh), neg_mul * 2^max(0, -sh)) < 2^31):
     //   q = t >= 0 ? rne(t * 2^(lk - sh)) : rne(t * neg_mul * 2^-sh)          (y355_requant_gen32; first layer of y355_net)
     int gen32;
-    // |t| = |(acc << shl) + bias_t| < 2^tmax_log2 for worst-case operands (<= 24: t is exact in fp32, front.hip's epilogue)
+    // |t| = |(acc << shl) + bias_t| < 2^tmax_log2 for worst-case operands (<= 24: t is exact in fp32, y355_fp32_exact)
     int tmax_log2;
     // gen32 only: 1 = the negative branch's product t * neg_mul does not fit 32 bits but t does; it is taken in two halves
     // (y355_requant_gen32): needs sh >= 9 and (|t| / 256 + 1) * neg_mul + 256 < 2^31 (host-checked)
     int split;
     // 1: the LeakyReLU's negative branch cannot leave [-127, 127]: |t| * neg_mul * 2^-sh <= 127 for the worst-case |t| of these weights
-    // (host-checked on the exact bound, not on 2^tmax_log2): front.hip's hot passes then do not track that branch's minimum
+    // (host-checked on the exact bound, not on 2^tmax_log2): the hot passes of y355_fp32epi.h's NEGSAFE form (front.hip) then do not track that branch's minimum
     int negsafe;
 };
+// Host rules of the fp32 epilogue on exact integers (y355_fp32epi.h has their reasons): slope in [0, 1]; t exact; the FOLD class
+inline bool y355_fp32_slope_ok(const Requant &rq) { return rq.neg_mul >= 0 && rq.neg_mul <= (1 << rq.lk); }
+inline bool y355_fp32_exact(const Requant &rq) { return !rq.wide && rq.tmax_log2 <= 24; }
+inline int y355_fp32_fold(const Requant &rq) { return rq.shl != 0 ? 0 : (rq.tmax_log2 <= 22 && rq.sh <= 22 && rq.sh - rq.lk >= -8) ? 2 : 1; }
 
 __device__ __forceinline__ int y355_rne_shift32(int x, int s) {            // s wave-uniform
     if (s <= 0) return x << (-s);

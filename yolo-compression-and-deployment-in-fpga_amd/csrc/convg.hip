@@ -13,13 +13,9 @@
 // channels; byte-wise the A/B fragments of the two MFMA shapes are identical (lane (g, j)
 // holds 16 bytes of row/column j at k-offset 16 g), which is why one kernel serves both.
 #include "y355_common.h"
-#include "convg_store.h"
+#include "convg_shared.h"
 #include <climits>
-#include <cstring>
 #include <type_traits>
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 
 // integer epilogue with a general LeakyReLU slope neg_mul / 2^lk (DESIGN.md "requantisation"):
 //   t = acc * 2^shl + bias;  t' = t >= 0 ? t * 2^lk : t * neg_mul;  q = clamp(RNE(t' * 2^-sh))
@@ -139,20 +135,11 @@ __device__ __forceinline__ void convg_stat(const ConvGParams &p, const v4i (&acc
 // (bias word / shl_w); otherwise rq.shl, wave-uniform, and the code of the per-tensor layers is what it was
 template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false, bool STAT = false>
 __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
-    constexpr bool THIN = (CHB == 32);           // 32 B per pixel: a k-step covers two taps
-    // input patch of a TH x TW output tile: S*(T-1)+3 pixels a side (stride S, 3x3, pad 1)
-    constexpr int PW = S * (TW - 1) + 3, PH = S * (TH - 1) + 3, NPIX = PH * PW;
-    static_assert(S == 1 || (S == 2 && !POOL && !THIN), "stride 2: plain 64-byte-chunk tiles only");
-    constexpr int STRIDE = CHB + 16;             // 16-byte pad: conflict-free ds_read_b128 across pixels
-    constexpr int CPP = CHB / 16;
-    constexpr int SUB = THIN ? 1 : CHB / 64;     // k-steps per tap and chunk
-    constexpr int BM = TH * TW;
-    constexpr int MT_TOT = (BM + 15) / 16;
-    constexpr int MT = (MT_TOT + WM - 1) / WM;
-    constexpr int NT = BN / 16 / WN;
+    using T = ConvGTile<CHB, BN, TH, TW, POOL, WM, WN, S>;
+    constexpr bool THIN = T::THIN;
+    constexpr int PW = T::PW, NPIX = T::NPIX, STRIDE = T::STRIDE, CPP = T::CPP, SUB = T::SUB, BM = T::BM, MT = T::MT, NT = T::NT;
     static_assert(WM * WN == 4, "4 waves");
-    static_assert(!POOL || (TH % 2 == 0 && TW % 2 == 0), "pooled tiles are even");
-    using ACC = typename std::conditional<BF, v4f, v4i>::type;
+    using ACC = MmaAcc<BF>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -205,10 +192,7 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            if constexpr (BF) acc[m][t] = (v4f){0.f, 0.f, 0.f, 0.f};
-            else acc[m][t] = (v4i){0, 0, 0, 0};
-        }
+        for (int t = 0; t < NT; ++t) acc[m][t] = ACC{};
 
     const char *wp = p.w + ((size_t)(nb * KS) * WN + wn) * NT * 1024 + lane * 16;
     constexpr size_t WSTEP = (size_t)WN * NT * 1024;
@@ -225,13 +209,7 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
         for (int m = 0; m < MT; ++m) {
             const v4i a = *(const v4i *)(smem + abase[m] + ko);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                if constexpr (BF)
-                    acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, bcur[t]),
-                                                                        acc[m][t], 0, 0, 0);
-                else
-                    acc[m][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bcur[t], acc[m][t], 0, 0, 0);
-            }
+            for (int t = 0; t < NT; ++t) mma_step<BF>(acc[m][t], a, bcur[t]);
         }
 #pragma unroll
         for (int t = 0; t < NT; ++t) bcur[t] = bnext[t];
@@ -265,20 +243,7 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
             }
         }
         __syncthreads();
-        if constexpr (THIN) {
-#pragma unroll
-            for (int ks = 0; ks < 5; ++ks) kstep(kofs[ks]);
-        } else {
-#pragma unroll
-            for (int sub = 0; sub < SUB; ++sub) {
-                if (taps == 9) {
-#pragma unroll
-                    for (int tap = 0; tap < 9; ++tap) kstep(((tap / 3) * PW + tap % 3) * STRIDE + sub * 64);
-                } else {
-                    kstep((PW + 1) * STRIDE + sub * 64);
-                }
-            }
-        }
+        CONVG_WALK_CHUNK(T, T::SUB, taps, kofs, kstep)
     }
 
     // ---- epilogue
@@ -426,21 +391,11 @@ __global__ __launch_bounds__(256) void convg_kernel(const ConvGParams p) {
 template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S, bool NARROW = false, bool PC = false, bool STAT = false>
 __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams p, const int total) {
     constexpr int NTHR = WM * WN * 64;
-    constexpr bool THIN = (CHB == 32);           // 32 B per pixel: a k-step covers two taps
-    // input patch of a TH x TW output tile: S*(T-1)+3 pixels a side (stride S, 3x3, pad 1)
-    constexpr int PW = S * (TW - 1) + 3, PH = S * (TH - 1) + 3, NPIX = PH * PW;
-    static_assert(S == 1 || (S == 2 && !POOL && !THIN), "stride 2: plain 64-byte-chunk tiles only");
-    constexpr int STRIDE = CHB + 16;             // 16-byte pad: conflict-free ds_read_b128 across pixels
-    constexpr int CPP = CHB / 16;
-    constexpr int SUB = THIN ? 1 : CHB / 64;     // k-steps per tap and chunk
-    constexpr int BM = TH * TW;
-    constexpr int MT_TOT = (BM + 15) / 16;
-    constexpr int MT = (MT_TOT + WM - 1) / WM;
-    constexpr int NT = BN / 16 / WN;
+    using T = ConvGTile<CHB, BN, TH, TW, POOL, WM, WN, S>;
+    constexpr bool THIN = T::THIN;
+    constexpr int PW = T::PW, NPIX = T::NPIX, STRIDE = T::STRIDE, CPP = T::CPP, SUB = T::SUB, BM = T::BM, MT = T::MT, NT = T::NT, SLAB = T::SLAB;
     static_assert(WM * WN == 8, "8 waves");
-    constexpr int SLAB = (NPIX * STRIDE + 15) / 16 * 16;
-    static_assert(!POOL || (TH % 2 == 0 && TW % 2 == 0), "pooled tiles are even");
-    using ACC = typename std::conditional<BF, v4f, v4i>::type;
+    using ACC = MmaAcc<BF>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -547,10 +502,7 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
 #pragma unroll
         for (int m = 0; m < MT; ++m)
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                if constexpr (BF) acc[m][t] = (v4f){0.f, 0.f, 0.f, 0.f};
-                else acc[m][t] = (v4i){0, 0, 0, 0};
-            }
+            for (int t = 0; t < NT; ++t) acc[m][t] = ACC{};
         int ksg = 0;
         const char *slab = smem;
         auto kstep = [&](int ko) {
@@ -562,13 +514,7 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
             for (int m = 0; m < MT; ++m) {
                 const v4i a = *(const v4i *)(slab + abase[m] + ko);
 #pragma unroll
-                for (int t = 0; t < NT; ++t) {
-                    if constexpr (BF)
-                        acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, b0[t]),
-                                                                            acc[m][t], 0, 0, 0);
-                    else
-                        acc[m][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, b0[t], acc[m][t], 0, 0, 0);
-                }
+                for (int t = 0; t < NT; ++t) mma_step<BF>(acc[m][t], a, b0[t]);
             }
 #pragma unroll
             for (int t = 0; t < NT; ++t) {
@@ -582,20 +528,7 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
             const bool more = ch + 1 < p.nchunks;
             slab = smem + cur * SLAB;
             if (more && !STAT) stage_load(b, y0, x0, ch + 1);       // in flight under this chunk's k-steps
-            if constexpr (THIN) {
-#pragma unroll
-                for (int ks = 0; ks < 5; ++ks) kstep(kofs[ks]);
-            } else {
-#pragma unroll 1
-                for (int sub = 0; sub < SUB; ++sub) {
-                    if (taps == 9) {
-#pragma unroll
-                        for (int tap = 0; tap < 9; ++tap) kstep(((tap / 3) * PW + tap % 3) * STRIDE + sub * 64);
-                    } else {
-                        kstep((PW + 1) * STRIDE + sub * 64);
-                    }
-                }
-            }
+            CONVG_WALK_CHUNK(T, 1, taps, kofs, kstep)
             if (more) {
                 if constexpr (STAT) stage_load(b, y0, x0, ch + 1);       // (behind them: the staging registers stay free under the k-steps)
                 stage_store(smem + (cur ^ 1) * SLAB);
@@ -734,71 +667,48 @@ __global__ __launch_bounds__(WM * WN * 64) void convg8_kernel(const ConvGParams 
 // ------------------------------------------------------------------------------------------
 template <bool BF, int CHB, int BN, int TH, int TW, bool POOL, int WM, int WN, int S = 1>
 struct ConvGInst {
-    static constexpr size_t SLAB = ((size_t)(S * (TH - 1) + 3) * (S * (TW - 1) + 3) * (CHB + 16) + 15) / 16 * 16;
+    static constexpr size_t SLAB = ConvGTile<CHB, BN, TH, TW, POOL, WM, WN, S>::SLAB;
     static constexpr bool EIGHT = (WM * WN == 8);
     static constexpr size_t LDS = EIGHT ? 2 * SLAB : SLAB;
-    static void launch(const ConvGParams &p, int nblocks, hipStream_t s) {
-        if constexpr (EIGHT) {
-            // one tile per workgroup (persistent workgroups measured slower: slim fp32, B = 64, 58.2 k vs 63.8 k img/s)
-            const size_t lds = p.nchunks > 1 ? 2 * SLAB : SLAB;
-            if (!BF && p.rq.narrow && p.pc)
-                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
-            else if (!BF && p.rq.narrow)
-                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
-            else if (!BF && p.pc)
-                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
-            else
-                hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
-        } else {
-            if (!BF && p.rq.narrow && p.pc)
-                hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>), dim3(nblocks), dim3(256), SLAB, s, p);
-            else if (!BF && p.rq.narrow)
-                hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>), dim3(nblocks), dim3(256), SLAB, s, p);
-            else if (!BF && p.pc)
-                hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>), dim3(nblocks), dim3(256), SLAB, s, p);
-            else
-                hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>), dim3(nblocks), dim3(256), SLAB, s, p);
-        }
-    }
-    // statistics mode (int8 only): the 64-bit epilogue's instantiation with STAT, per-tensor or per-channel shifts
-    static void launch_stat(const ConvGParams &p, int nblocks, hipStream_t s) {
+    // the instantiations of this tile: the plain one; int8 also the 32-bit epilogue (NARROW) and / or per-channel shifts (PC),
+    // and statistics mode (STAT: the 64-bit epilogue's, per-tensor or per-channel).  f(NARROW, PC, STAT) as std::bool_constant
+    template <class F>
+    static int variant(bool narrow, bool pc, bool stat, F &&f) {
+        using Y = std::true_type;
+        using N = std::false_type;
         if constexpr (!BF) {
-            if constexpr (EIGHT) {
-                const size_t lds = p.nchunks > 1 ? 2 * SLAB : SLAB;
-                if (p.pc)
-                    hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, true, true>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
-                else
-                    hipLaunchKernelGGL((convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, true>), dim3(nblocks), dim3(512), lds, s, p, nblocks);
-            } else {
-                if (p.pc)
-                    hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, true, true>), dim3(nblocks), dim3(256), SLAB, s, p);
-                else
-                    hipLaunchKernelGGL((convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, true>), dim3(nblocks), dim3(256), SLAB, s, p);
-            }
+            if (stat) return pc ? f(N{}, Y{}, Y{}) : f(N{}, N{}, Y{});
+            if (narrow) return pc ? f(Y{}, Y{}, N{}) : f(Y{}, N{}, N{});
+            if (pc) return f(N{}, Y{}, N{});
         }
+        return f(N{}, N{}, N{});
+    }
+    // the 4-wave and the 8-wave kernel behind one name, with its launch geometry; one tile per workgroup (persistent 8-wave
+    // workgroups measured slower: slim fp32, B = 64, 58.2 k vs 63.8 k img/s)
+    template <bool NARROW, bool PC, bool STAT>
+    struct Kernel {
+        static const void *fn() {
+            if constexpr (EIGHT) return (const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, NARROW, PC, STAT>;
+            else return (const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, NARROW, PC, STAT>;
+        }
+        static int launch(ConvGParams p, int nblocks, hipStream_t s) {
+            void *args[] = {&p, &nblocks};              // (p) for 4 waves, (p, total) for 8: the runtime reads as many as the kernel has
+            const size_t lds = EIGHT && p.nchunks > 1 ? 2 * SLAB : SLAB;
+            return (int)hipLaunchKernel(fn(), dim3(nblocks), dim3(EIGHT ? 512 : 256), args, lds, s);
+        }
+        static int prepare() { return (int)hipFuncSetAttribute(fn(), hipFuncAttributeMaxDynamicSharedMemorySize, (int)LDS); }
+    };
+    static int launch_as(bool narrow, bool stat, const ConvGParams &p, int nblocks, hipStream_t s) {
+        return variant(narrow, p.pc, stat, [&](auto n, auto pc, auto st) { return Kernel<decltype(n)::value, decltype(pc)::value, decltype(st)::value>::launch(p, nblocks, s); });
+    }
+    static void launch(const ConvGParams &p, int nblocks, hipStream_t s) { launch_as(p.rq.narrow, false, p, nblocks, s); }
+    static void launch_stat(const ConvGParams &p, int nblocks, hipStream_t s) {      // int8 only
+        if constexpr (!BF) launch_as(false, true, p, nblocks, s);
     }
     static int prepare() {
-        const int lds = (int)LDS;
-        auto set = [&](const void *fn) { return (int)hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, lds); };
-        if constexpr (EIGHT) {
-            if constexpr (!BF) {
-                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>)) return e;
-                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>)) return e;
-                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>)) return e;
-                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, !BF>)) return e;
-                if (int e = set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF, !BF>)) return e;
-            }
-            return set((const void *)convg8_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>);
-        } else {
-            if constexpr (!BF) {
-                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF>)) return e;
-                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, !BF, !BF>)) return e;
-                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF>)) return e;
-                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, false, !BF>)) return e;
-                if (int e = set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S, false, !BF, !BF>)) return e;
-            }
-            return set((const void *)convg_kernel<BF, CHB, BN, TH, TW, POOL, WM, WN, S>);
-        }
+        for (int v = 0; v < (BF ? 1 : 8); ++v)
+            if (int e = variant(v & 1, v & 2, v & 4, [](auto n, auto pc, auto st) { return Kernel<decltype(n)::value, decltype(pc)::value, decltype(st)::value>::prepare(); })) return e;
+        return 0;
     }
     static constexpr ConvGInfo info() {
         return ConvGInfo{BF ? 1 : 0, CHB, BN, TH, TW, POOL ? 1 : 0, WM, WN, BN / 16 / WN, S, LDS, &launch, &prepare, &launch_stat};
@@ -857,43 +767,18 @@ size_t y355_convg_packed_bytes(const ConvGInfo &ki, int in_pb, int taps, int cou
     return (size_t)(cout_pad / ki.bn) * y355_convg_ksteps(ki, in_pb, taps) * ki.wn * ki.nt * 1024;
 }
 
-// B-fragment order as conv3x3.hip (y355_pack_weights): frag(nb, ks, wn, t), lane (g, j) holds the 16
-// bytes at k-offset 16 g of output channel n = nb*BN + wn*NT*16 + j*NT + t.  k-steps run
-// chunk-major: ks = (chunk * SUB + sub) * taps + tap covers input bytes [64*(chunk*SUB+sub), +64).
-// `w` is [cout][cin][k][k] (k = 1 or 3), fp32 (bf16 nets: rounded to nearest-even here) or int8.
+// B-fragment order as conv3x3.hip (y355_pack_weights), y355_pack_bfrags.  k-steps run chunk-major:
+// ks = (chunk * SUB + sub) * taps + tap covers input bytes [64*(chunk*SUB+sub), +64); thin kernels: k-step ks holds taps 2 ks
+// and 2 ks + 1, 32 bytes each.  `w` is [cout][cin][k][k] (k = 1 or 3), fp32 or int8.
 void y355_convg_pack(const ConvGInfo &ki, const float *w_f, const int8_t *w_q, int cout, int cin, int ksize,
                      int in_pb, int cout_pad, char *dst) {
-    const int taps = ksize * ksize;
-    const int es = ki.bf ? 2 : 1, epg = 16 / es;          // element size, elements per lane
-    const int KS = y355_convg_ksteps(ki, in_pb, taps), NT = ki.nt, WN = ki.wn, BN = ki.bn;
-    const int nblk = cout_pad / BN;
-    for (int nb = 0; nb < nblk; ++nb)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int wn = 0; wn < WN; ++wn)
-                for (int t = 0; t < NT; ++t) {
-                    char *f = dst + ((((size_t)nb * KS + ks) * WN + wn) * NT + t) * 1024;
-                    for (int l = 0; l < 64; ++l) {
-                        const int g = l >> 4, j = l & 15;
-                        const int n = nb * BN + wn * NT * 16 + j * NT + t;
-                        for (int e = 0; e < epg; ++e) {
-                            int tap, ci;
-                            if (ki.chb == 32) { tap = 2 * ks + (g >> 1); ci = (g & 1) * epg + e; }
-                            else { tap = ks % taps; ci = (ks / taps) * (64 / es) + g * epg + e; }
-                            const bool ok = tap < taps && n < cout && ci < cin;
-                            const size_t wi = ((size_t)n * cin + ci) * taps + tap;
-                            if (ki.bf) {
-                                const float v = ok ? w_f[wi] : 0.f;
-                                unsigned int u;
-                                memcpy(&u, &v, 4);
-                                u = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;      // RNE (weights are finite)
-                                const unsigned short h = (unsigned short)u;
-                                memcpy(f + l * 16 + e * 2, &h, 2);
-                            } else {
-                                f[l * 16 + e] = ok ? (char)w_q[wi] : 0;
-                            }
-                        }
-                    }
-                }
+    const int taps = ksize * ksize, KS = y355_convg_ksteps(ki, in_pb, taps);
+    const int kel = ki.bf ? 32 : 64;                      // elements of a k-step
+    const bool thin = ki.chb == 32;
+    y355_pack_bfrags(ki.bf, KS, ki.bn, ki.wn, ki.nt, w_f, w_q, cout, cin, taps, cout_pad, dst, [=](int ks, int k, int &tap, int &ci) {
+        if (thin) { tap = 2 * ks + k / (kel / 2); ci = k % (kel / 2); }
+        else { tap = ks % taps; ci = (ks / taps) * kel + k; }
+    });
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1034,10 +919,7 @@ void y355_pack_conv1f(const float *w /*[16][3][3][3]*/, char *dst /*2048*/) {
                 const int d = 2 * f + (e >> 2), c = e & 3;
                 float v = 0.f;
                 if (g < 3 && d < 3 && c < 3) v = w[((j * 3 + c) * 3 + g) * 3 + d];
-                unsigned int u;
-                memcpy(&u, &v, 4);
-                u = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-                const unsigned short h = (unsigned short)u;
+                const unsigned short h = y355_bf16_rne(v);
                 memcpy(dst + f * 1024 + l * 16 + e * 2, &h, 2);
             }
         }

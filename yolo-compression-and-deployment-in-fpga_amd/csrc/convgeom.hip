@@ -17,12 +17,8 @@
 // stage.  B fragments come from global memory (L2-resident, packed by y355_convgeom_pack), one k-step ahead.  Waits are the
 // compiler's.
 #include "y355_common.h"
-#include "convg_store.h"
-#include <cstring>
+#include "convg_shared.h"
 #include <type_traits>
-
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 
 namespace {
 constexpr int GK = 4;                     // 64-byte k-steps per stage (one tap) at most
@@ -37,7 +33,7 @@ __global__ __launch_bounds__(256) void convgeom_kernel(const ConvGeomParams p) {
     static_assert(WM * WN == 4, "4 waves");
     static_assert(256 % BM == 0 && (GK * 4) % TPR == 0, "staging split");
     (void)BN;
-    using ACC = typename std::conditional<BF, v4f, v4i>::type;
+    using ACC = MmaAcc<BF>;
     extern __shared__ __attribute__((aligned(16))) char smem[];
 
     const int tid = threadIdx.x;
@@ -95,10 +91,7 @@ __global__ __launch_bounds__(256) void convgeom_kernel(const ConvGeomParams p) {
 #pragma unroll
     for (int m = 0; m < MT; ++m)
 #pragma unroll
-        for (int t = 0; t < NT; ++t) {
-            if constexpr (BF) acc[m][t] = (v4f){0.f, 0.f, 0.f, 0.f};
-            else acc[m][t] = (v4i){0, 0, 0, 0};
-        }
+        for (int t = 0; t < NT; ++t) acc[m][t] = ACC{};
 
     const char *wp = p.w + ((size_t)nb * KS * WN + wn) * NT * 1024 + lane * 16;
     constexpr size_t WSTEP = (size_t)WN * NT * 1024;
@@ -115,13 +108,7 @@ __global__ __launch_bounds__(256) void convgeom_kernel(const ConvGeomParams p) {
         for (int m = 0; m < MT; ++m) {
             const v4i a = *(const v4i *)(slab + abase[m] + ko);
 #pragma unroll
-            for (int t = 0; t < NT; ++t) {
-                if constexpr (BF)
-                    acc[m][t] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(v8bf, a), __builtin_bit_cast(v8bf, bcur[t]),
-                                                                        acc[m][t], 0, 0, 0);
-                else
-                    acc[m][t] = __builtin_amdgcn_mfma_i32_16x16x64_i8(a, bcur[t], acc[m][t], 0, 0, 0);
-            }
+            for (int t = 0; t < NT; ++t) mma_step<BF>(acc[m][t], a, bcur[t]);
         }
 #pragma unroll
         for (int t = 0; t < NT; ++t) bcur[t] = bnext[t];
@@ -251,40 +238,16 @@ size_t y355_convgeom_packed_bytes(int id, int in_pb, int taps, int cout_pad) {
     return (size_t)(cout_pad / ki.bn) * taps * (in_pb / 64) * ki.wn * ki.nt * 1024;
 }
 
-// B fragment (nb, ks, wn, t), lane (g, j): the 16 bytes at k-offset 16 g of output channel n = nb*BN + wn*NT*16 + j*NT + t,
-// ks = tap * nchunk + chunk covering input bytes [64 chunk, + 64) at tap = ky * kw + kx.  w is [cout][cin][kh][kw], fp32
-// (rounded to bf16, nearest-even) or int8.
+// B fragments (y355_pack_bfrags) with the k-steps tap-major: ks = tap * nchunk + chunk covers input bytes [64 chunk, + 64) at
+// tap = ky * kw + kx.  w is [cout][cin][kh][kw], fp32 or int8.
 void y355_convgeom_pack(int id, int bf, const float *w_f, const int8_t *w_q, int cout, int cin, int taps, int in_pb, int cout_pad,
                         char *dst) {
     const ConvGeomInfo &ki = g_geom[id].info;
-    const int es = bf ? 2 : 1, epg = 16 / es;
-    const int nch = in_pb / 64, KS = taps * nch, NT = ki.nt, WN = ki.wn, BN = ki.bn;
-    for (int nb = 0; nb < cout_pad / BN; ++nb)
-        for (int ks = 0; ks < KS; ++ks)
-            for (int wn = 0; wn < WN; ++wn)
-                for (int t = 0; t < NT; ++t) {
-                    char *f = dst + ((((size_t)nb * KS + ks) * WN + wn) * NT + t) * 1024;
-                    const int tap = ks / nch, ch = ks % nch;
-                    for (int l = 0; l < 64; ++l) {
-                        const int g = l >> 4, j = l & 15;
-                        const int n = nb * BN + wn * NT * 16 + j * NT + t;
-                        for (int e = 0; e < epg; ++e) {
-                            const int ci = ch * (64 / es) + g * epg + e;
-                            const bool ok = n < cout && ci < cin;
-                            const size_t wi = ((size_t)n * cin + ci) * taps + tap;
-                            if (bf) {
-                                const float v = ok ? w_f[wi] : 0.f;
-                                unsigned int u;
-                                memcpy(&u, &v, 4);
-                                u = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;      // RNE (weights are finite)
-                                const unsigned short h = (unsigned short)u;
-                                memcpy(f + l * 16 + e * 2, &h, 2);
-                            } else {
-                                f[l * 16 + e] = ok ? (char)w_q[wi] : 0;
-                            }
-                        }
-                    }
-                }
+    const int nch = in_pb / 64, kel = bf ? 32 : 64;
+    y355_pack_bfrags(bf != 0, taps * nch, ki.bn, ki.wn, ki.nt, w_f, w_q, cout, cin, taps, cout_pad, dst, [=](int ks, int k, int &tap, int &ci) {
+        tap = ks / nch;
+        ci = (ks % nch) * kel + k;
+    });
 }
 
 void y355_launch_convgeom(int id, int bf, const ConvGeomParams &p, hipStream_t s) {

@@ -27,9 +27,6 @@
 
 namespace {
 using namespace y355dev;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
-
 // PXB = bytes per input pixel (2 x channels): 64 or 128
 template <int PXB, int NTN, int NCB, bool POOL>
 struct PbGeom {
@@ -218,13 +215,6 @@ __global__ __launch_bounds__(NW * 64, (NW + 3) / 4) void convpxb_kernel(const Co
 
 // ------------------------------------------------------------------------------------------
 namespace {
-__host__ inline unsigned short f2bf(float f) {                    // RNE, as the device's conversion
-    unsigned int u;
-    memcpy(&u, &f, 4);
-    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
-    u += 0x7fffu + ((u >> 16) & 1u);
-    return (unsigned short)(u >> 16);
-}
 // A fragments: fragment ((cb * KS + ks) * NTN + n), lane (i = l & 15, g = l >> 4), 8 bf16:
 //   row i = output channel cb * CPB + 4 NTN (i >> 2) + 4 n + (i & 3);  k = tap ks / KPP, input channels 32 (ks % KPP) + 8 g .. + 7
 template <int PXB, int NTN, int NCB, bool POOL>
@@ -242,7 +232,7 @@ void pb_pack(const float *w, int cout, int cin, char *dst) {
                     if (ch >= cout) continue;
                     for (int kk = 0; kk < 8; ++kk)
                         if (c0 + kk < cin)
-                            d[((((size_t)cb * G::KS + ks) * NTN + n) * 1024 + l * 16) / 2 + kk] = f2bf(w[((size_t)ch * cin + c0 + kk) * 9 + tap]);
+                            d[((((size_t)cb * G::KS + ks) * NTN + n) * 1024 + l * 16) / 2 + kk] = y355_bf16_rne(w[((size_t)ch * cin + c0 + kk) * 9 + tap]);
                 }
 }
 

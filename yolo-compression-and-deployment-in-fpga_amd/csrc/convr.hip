@@ -20,9 +20,6 @@
 #include <hip/hip_ext.h>
 #include <type_traits>
 
-typedef float v4f __attribute__((ext_vector_type(4)));
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-
 namespace {
 using namespace y355dev;
 constexpr int PF = 4;        // ring of PF + 2 = 6 weight slots: divides the k-steps of every multi-chunk layer here (STATIC below)

@@ -22,8 +22,6 @@
 
 namespace {
 using namespace y355dev;
-typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
-typedef float v4f __attribute__((ext_vector_type(4)));
 constexpr int TOY = 13, TOX = 13;                    // pooled conv2 outputs per tile
 constexpr int P1H = 2 * TOY + 2, P1W = 2 * TOX + 2;  // pooled conv1 tile with its halo
 constexpr int PH0 = 2 * P1H + 2;                     // input patch rows (= columns used)
@@ -264,13 +262,6 @@ void y355_frontb_tiles(int H, int W, int *tx, int *ty) {
     *ty = (H / 4 + TOY - 1) / TOY;
 }
 
-static unsigned short bf16_rne(float v) {
-    unsigned int u;
-    memcpy(&u, &v, 4);
-    u = (u + 0x7fffu + ((u >> 16) & 1u)) >> 16;
-    return (unsigned short)u;
-}
-
 // Weight fragments of the bf16 front end (32 KiB): MFMA A operands, lane (i = l & 15: accumulator row, g = l >> 4), 8 bf16.
 //   conv1, variant v = 2 dy + dx (offset of the conv output inside the pooling window), half h, at (2 v + h) * 1024:
 //     row i = output channel i; element e of lane group g: neighbourhood row 2 h + (g >> 1), pixel 2 (g & 1) + (e >> 2), colour e & 3
@@ -287,7 +278,7 @@ void y355_pack_frontb(const float *w1 /*[16][3][3][3]*/, const float *w2 /*[32][
                     for (int e = 0; e < 8; ++e) {
                         const int ky = 2 * h + (g >> 1) - (v >> 1), kx = 2 * (g & 1) + (e >> 2) - (v & 1), c = e & 3;
                         if (ky < 0 || ky > 2 || kx < 0 || kx > 2 || c > 2) continue;
-                        const unsigned short hb = bf16_rne(w1[((i * 3 + c) * 3 + ky) * 3 + kx]);
+                        const unsigned short hb = y355_bf16_rne(w1[((i * 3 + c) * 3 + ky) * 3 + kx]);
                         memcpy(dst + (2 * v + h) * 1024 + l * 16 + e * 2, &hb, 2);
                     }
                 }
@@ -304,7 +295,7 @@ void y355_pack_frontb(const float *w1 /*[16][3][3][3]*/, const float *w2 /*[32][
                             if (kx < 0 || kx > 2) continue;
                             for (int e = 0; e < 8; ++e) {
                                 const int ci = 8 * (g & 1) + e;
-                                const unsigned short hb = bf16_rne(w2[((ch * 16 + ci) * 3 + ky) * 3 + kx]);
+                                const unsigned short hb = y355_bf16_rne(w2[((ch * 16 + ci) * 3 + ky) * 3 + kx]);
                                 memcpy(dst + W1_BYTES + ((((n * 3 + ky) * 2 + dx) * 2 + h) * 1024) + l * 16 + e * 2, &hb, 2);
                             }
                         }

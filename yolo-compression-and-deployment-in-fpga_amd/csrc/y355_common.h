@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <string.h>
 #include <functional>
 #include <string>
 #include <vector>
@@ -9,6 +10,8 @@
 #include <hip/hip_ext.h>
 
 typedef int v4i __attribute__((ext_vector_type(4)));
+typedef float v4f __attribute__((ext_vector_type(4)));
+typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
 #define Y355_STAMP_ROWS 4096      // rows of 32 stamps in the diagnostic builds' stamp buffer (y355_debug_stamps)
 
 // launch; with both events given the launch records its own start / end timestamps into them (profile mode 2: the
@@ -218,6 +221,14 @@ void y355_front_tiles(int H, int W, int *tx, int *ty);
 void y355_pack_front(const int8_t *q_w1, const int8_t *q_w2, int8_t *dst /*16384; a null tensor leaves its part zero*/);
 bool y355_front_eligible(const Requant &rq1, const Requant &rq2);
 void y355_launch_front(const FrontParams &p, hipStream_t s);
+
+// fp32 -> bf16 bits on the host, round to nearest-even as the device's conversion (a NaN stays a quiet NaN): the weight packers
+inline unsigned short y355_bf16_rne(float v) {
+    unsigned int u;
+    memcpy(&u, &v, 4);
+    if ((u & 0x7fffffffu) > 0x7f800000u) return (unsigned short)((u >> 16) | 0x40);
+    return (unsigned short)((u + 0x7fffu + ((u >> 16) & 1u)) >> 16);
+}
 
 template <typename T>
 __device__ __forceinline__ T y355_rne_shift(T t, int sh) {

@@ -718,6 +718,63 @@ int y355_net_profile(y355_net *h, int enable);
 int y355_net_num_timers(y355_net *h);          /* ops + head decode + NMS */
 int y355_net_profile_get(y355_net *h, float *ms);
 
+/* ------------------------------------------------------------------------------------------
+ * y355_apeval: VOC mAP of a whole dataset run, on the GPU, from detections that never leave it (csrc/apeval.hip).  Replaces
+ * what follows the evaluators' loops: write_voc_results_file + voc_eval + voc_ap (utils/vocapi_evaluator_mask.py:140-336,
+ * utils/vocapi_evaluator.py alike).  Per class, voc_eval's semantics in every detail:
+ *   quantisation  Y355_AP_Q_VOCFILE (what the reference scores: the values it wrote to the results file):
+ *                 score_q = rint(double(score) * 1000) / 1000, coord_q = rint(double(float32(coord) + float32(1)) * 10) / 10 --
+ *                 the '{:.3f}' / '{:.1f}' -> float() round trip; the + 1 on detections only.  Y355_AP_Q_NONE: the raw float32 values.
+ *   rank          score_q descending, then image index ascending, then position in the image's list ascending (a stable sort
+ *                 of the reference's file order; np.argsort(-confidence) leaves the order inside a tie group undefined)
+ *   match         float64 in the reference's operation order, no + 1 in the areas; ovmax = np.max (a NaN overlap makes it NaN),
+ *                 jmax = first index of the maximum; ovmax > ovthresh (strictly): difficult box -> neither, unmarked box -> TP
+ *                 and marked, marked box -> FP; otherwise, and without a box of the class in the image, FP
+ *   curve         inclusive sums of TP / FP; rec = tp / double(npos) (npos = non-difficult boxes; 0 gives NaN);
+ *                 prec = tp / max(tp + fp, DBL_EPSILON)
+ *   AP            Y355_AP_VOC07: the eleven thresholds t = k * 0.1, p = max(prec[rec >= t]) or 0, ap += p / 11.
+ *                 Y355_AP_AREA: precision envelope from the right, sum of (mrec[i + 1] - mrec[i]) * mpre[i + 1] where recall
+ *                 changes.  A class without any detection: ap = -1 (included in the mean, as np.mean(aps) includes it); with
+ *                 detections and npos = 0: 0.0 under VOC07, NaN under AREA.
+ * One handle is single-threaded; it owns a device store of max_dets detection records, its workspaces and one HIP stream.
+ *   create    num_classes 1..256, num_images 1..2^24, max_dets 1..2^27 (about 70 bytes of device memory each)
+ *   set_gt    the ground truth of the whole image list, host pointers, CSR by image: offsets[num_images + 1], boxes [n][4]
+ *             x1 y1 x2 y2, cls [n] in 0..num_classes - 1, difficult [n]; synchronous; may be called again
+ *   add       one batch of engine outputs (the four buffers of y355_forward / y355_pipeline_outputs / y355_net_forward; device
+ *             pointers) = images first_image .. first_image + batch - 1.  Only the first count[b] entries of an image are read
+ *             (count outside 0..max_det is clamped); max_det 1..2^20.  Asynchronous and free of host synchronisation: with
+ *             after_stream the append runs ON that stream, behind the work already queued there (the producer of the buffers),
+ *             so work the caller queues on it afterwards -- y355_pipeline_release -- follows the read; NULL: the buffers are
+ *             complete, the append runs on the handle's stream, which waits for no other.  HIP's null (default) stream is the
+ *             handle 0 as well: name it Y355_AP_NULL_STREAM, and the append runs on the null stream behind its work.  Batches may come in any order and from several streams.  An
+ *             image is added at most once between resets (not checked).
+ *   add_host  the same from host arrays; synchronous
+ *   reset     drops the detections, keeps the ground truth; synchronous
+ *   compute   synchronous (waits for every add).  Y355_ERANGE, the message giving the numbers, when more than max_dets
+ *             detections were added since the last reset (the excess was counted, never stored) or a class index inside count
+ *             was outside 0..num_classes - 1; reset makes the handle usable again.  Y355_ENOTREADY without ground truth.
+ *             ap [C], npos [C], ndet [C] detections per class, *mean_ap = the sum of ap in class order / C.
+ *   curve     parity tap: class cls of the last successful compute in rank order -- rec, prec, flag (1 TP, 2 FP, 0 neither),
+ *             each capacity long or NULL; *n = the class's detections (also when capacity is smaller)
+ * Arguments are checked before any HIP call. */
+typedef struct y355_apeval y355_apeval;
+#define Y355_AP_VOC07 0
+#define Y355_AP_AREA 1
+#define Y355_AP_Q_VOCFILE 0
+#define Y355_AP_Q_NONE 1
+#define Y355_AP_NULL_STREAM ((void *)1)   /* after_stream of y355_apeval_add: the null stream itself (NULL means "no producer") */
+int y355_apeval_create(int device_id, int num_classes, int num_images, int64_t max_dets, y355_apeval **out);
+void y355_apeval_destroy(y355_apeval *e);
+int y355_apeval_set_gt(y355_apeval *e, const int32_t *offsets, const float *boxes, const int32_t *cls, const uint8_t *difficult);
+int y355_apeval_add(y355_apeval *e, int first_image, int batch, int max_det, const float *boxes_dev, const float *scores_dev,
+                    const int32_t *cls_dev, const int32_t *count_dev, void *after_stream);
+int y355_apeval_add_host(y355_apeval *e, int first_image, int batch, int max_det, const float *boxes, const float *scores,
+                         const int32_t *cls, const int32_t *count);
+int y355_apeval_reset(y355_apeval *e);
+int y355_apeval_compute(y355_apeval *e, double ovthresh, int metric, int quantize, double *ap, int32_t *npos, int64_t *ndet,
+                        double *mean_ap);
+int y355_apeval_curve(y355_apeval *e, int cls, int64_t capacity, double *rec, double *prec, uint8_t *flag, int64_t *n);
+
 #ifdef __cplusplus
 }
 #endif

@@ -31,6 +31,9 @@ HEAD_ROUTE_AUTO = 0
 HEAD_ROUTE_LARGE = 1
 EINVAL, EHIP, ENOTREADY = -1, -2, -3
 ERANGE = -4
+AP_VOC07, AP_AREA = 0, 1
+AP_Q_VOCFILE, AP_Q_NONE = 0, 1
+AP_NULL_STREAM = 1          # Y355_AP_NULL_STREAM: HIP's null stream as y355_apeval_add's after_stream (0 means "no producer")
 
 
 class Config(C.Structure):
@@ -253,6 +256,14 @@ _SIGS = {
     "y355_net_profile": (C.c_int, [C.c_void_p, C.c_int]),
     "y355_net_num_timers": (C.c_int, [C.c_void_p]),
     "y355_net_profile_get": (C.c_int, [C.c_void_p, P(C.c_float)]),
+    "y355_apeval_create": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int64, P(C.c_void_p)]),
+    "y355_apeval_destroy": (None, [C.c_void_p]),
+    "y355_apeval_set_gt": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_apeval_add": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_apeval_add_host": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_apeval_reset": (C.c_int, [C.c_void_p]),
+    "y355_apeval_compute": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_double)]),
+    "y355_apeval_curve": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64)]),
 }
 
 

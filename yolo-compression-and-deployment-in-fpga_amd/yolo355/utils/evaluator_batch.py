@@ -1,7 +1,9 @@
 """Evaluator-side batching.  The reference's evaluators call the network one image at a time
 (utils/vocapi_evaluator_mask.py:57-82, utils/vocapi_evaluator.py, utils/cocoapi_evaluator.py:70-98) and rescale the
 boxes on the host.  These helpers produce the same data structures with batched forwards and the rescale on the GPU
-(`forward_batch(..., sizes_wh=...)` -> y355_scale_boxes); the mAP computation that follows them is untouched.
+(`forward_batch(..., sizes_wh=...)` -> y355_scale_boxes); the VOC mAP computation that follows them (evaluate_detections:
+write_voc_results_file + voc_eval, :140-341) is `voc_map` / `voc_map_from_all_boxes` below, on the GPU (yolo355.apeval); COCO's
+(pycocotools) is untouched.
 
     # utils/vocapi_evaluator_mask.py:49-95  (evaluate)
     - for i in range(num_images): ... bboxes, scores, cls_inds = net(x, quantization=..., find=...) ...
@@ -188,3 +190,101 @@ def coco_data_dict_frames(net, dataset, batch_size=64, num_images=None, **kw):
                 data_dict.append({"image_id": id_, "category_id": dataset.class_ids[int(cls_inds[k])],
                                   "bbox": [x1, y1, x2 - x1, y2 - y1], "score": float(scores[k])})
     return ids, data_dict
+
+
+# ---------------------------------------------------------------------------------------------------- VOC mAP (yolo355.apeval)
+def voc_ground_truth(annopath, image_ids, labelmap):
+    """The ground truth voc_eval reads (utils/vocapi_evaluator_mask.py:98-115, :257-268), as ApEval takes it: one array per image
+    of rows (cls, xmin, ymin, xmax, ymax, difficult).  annopath: the '%s.xml' pattern of the VOC Annotations directory;
+    image_ids: the names of the image-set file, in dataset order; objects whose name is not in labelmap are skipped (voc_eval
+    never selects them)."""
+    import xml.etree.ElementTree as ET
+    index = {name: i for i, name in enumerate(labelmap)}
+    gts = []
+    for image_id in image_ids:
+        rows = []
+        for obj in ET.parse(annopath % image_id).findall("object"):
+            c = index.get(obj.find("name").text.strip())
+            if c is None:
+                continue
+            d = obj.find("difficult")
+            bb = obj.find("bndbox")
+            rows.append([c] + [float(bb.find(k).text) for k in ("xmin", "ymin", "xmax", "ymax")] + [int(d.text) if d is not None else 0])
+        gts.append(np.asarray(rows, np.float64).reshape(-1, 6))
+    return gts
+
+
+def voc_map_from_all_boxes(all_boxes, ground_truth, use_07_metric=True, ovthresh=0.5):
+    """The replacement for evaluate_detections(box_list) (utils/vocapi_evaluator_mask.py:339-341): all_boxes[cls][image] = N x 5
+    (x1, y1, x2, y2, score) or [] / an empty array -> (aps float64 [C], mean).  The reference's own write_voc_results_file stops
+    at `if dets == []` on NumPy >= 2; here nothing is written: the file's rounding is part of ApEval's arithmetic."""
+    from ..apeval import ApEval
+    C, n = len(all_boxes), len(ground_truth)
+    per = [[np.asarray(all_boxes[j][i], np.float32).reshape(-1, 5) for j in range(C)] for i in range(n)]
+    ev = ApEval(C, ground_truth, max_dets=max(1, sum(len(a) for p in per for a in p)))
+    try:
+        for i0, i1 in _batches(n, 1024):
+            # per image the classes in ascending order: every class keeps the order of its own results file
+            ev.add_detections(i0, [(np.concatenate([a[:, :4] for a in p]), np.concatenate([a[:, 4] for a in p]),
+                                    np.concatenate([np.full(len(a), j, np.int32) for j, a in enumerate(p)])) for p in per[i0:i1]])
+        return ev.compute(ovthresh=ovthresh, use_07_metric=use_07_metric)
+    finally:
+        ev.close()
+
+
+def _pipeline_admits(net, batch, quantization=False, find=False):
+    """_submit's rule for the y355_pipeline behind a calibrated q_bf model, restated (the existing helpers stay as they are);
+    tests/test_voc_ap_ref.py holds the two together"""
+    return bool(quantization and not find and hasattr(net, "submit_batch") and hasattr(net, "_tracker_states")
+                and all(t.first_a != 0 for t in net._tracker_states())
+                and batch <= 2 * _ffi.PIPE_DEFAULT_HANDLES * getattr(net, "PIPELINE_CHUNK", 0))
+
+
+def voc_map(net, dataset, num_classes, ground_truth, batch_size=64, quantization=False, find=False, num_images=None,
+            use_07_metric=True, max_dets=None):
+    """The whole evaluate() of utils/vocapi_evaluator_mask.py:49-95 -> (aps float64 [C], mean): voc_all_boxes' loop with the mAP
+    behind it.  A calibrated q_bf model (the rule of _submit) is device-resident end to end: Pipeline.submit -> scale_boxes ->
+    ApEval.add on the ticket's stream -> release; no detection is copied to the host and nothing waits for the GPU before
+    compute().  Every other model goes through forward_batch(..., sizes_wh=) and ApEval.add_detections.
+    dataset.pull_item(i) -> (im [3,H,W] tensor, gt, h, w); ground_truth: voc_ground_truth(...) for the same images."""
+    from ..apeval import ApEval
+    n = len(dataset) if num_images is None else int(num_images)
+    dev = net.device if isinstance(getattr(net, "device", None), (str, torch.device)) else "cuda:0"
+    ev = ApEval(num_classes, ground_truth[:n], max_dets=max_dets, device=dev)
+    try:
+        out = []            # (pipeline, ticket, token) of the batch before: its overflow flag is read one batch late, and the token
+                            # keeps what the ticket's launches read (the sizes scale_boxes multiplies by) alive until then
+        def settle():
+            from ..engine import _overflow_message
+            for pipe, t, _ in out:
+                if pipe.overflow(t):                        # as Pipeline.fetch reports it
+                    raise _ffi.Y355Error(-1, _overflow_message(pipe.max_candidates))
+            del out[:]
+        for i0, i1 in _batches(n, batch_size):
+            ims, sizes = [], []
+            for i in range(i0, i1):
+                im, gt, h, w = dataset.pull_item(i)
+                ims.append(torch.as_tensor(im))
+                sizes.append((w, h))
+            x = torch.stack(ims).float()
+            sizes = np.asarray(sizes, np.float32)
+            if _pipeline_admits(net, i1 - i0, quantization=quantization, find=find):
+                token = net.submit_batch(x, quantization=True, find=False, sizes_wh=sizes)
+                pipe, tickets, wh = token
+                settle()
+                for k, t in enumerate(tickets):
+                    first = i0 + k * pipe.max_batch
+                    st = pipe.stream(t)
+                    ev.add(first, *pipe.outputs(t), after_stream=st, batch=min(i1 - first, pipe.max_batch))
+                    with torch.cuda.stream(st):             # the append just queued there is the last reader of the ticket's outputs
+                        pipe.release(t)
+                    if wh is not None:
+                        wh.record_stream(st)                # the caching allocator must not hand the block on before scale_boxes ran
+                    out.append((pipe, t, token))
+            else:
+                settle()
+                ev.add_detections(i0, _run(net, x, sizes, quantization=quantization, find=find))
+        settle()
+        return ev.compute(use_07_metric=use_07_metric)
+    finally:
+        ev.close()

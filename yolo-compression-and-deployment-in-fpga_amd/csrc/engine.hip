@@ -173,10 +173,10 @@ int make_requant(int cin_real, int taps, int sa_in, int e_w, int e_b, int sa_out
 }
 }  // namespace
 
-// the integer epilogue of one stand-alone layer without requantisation (the operator objects of ops.hip)
-int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int act, const int32_t *q_b, int cout, int cout_pad, Requant *rq,
-                    int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w) {
-    return make_requant(cin, taps, sa_in, e_w, e_b, 0, false, act, 10, q_b, cout, cout_pad, rq, frac_bits, bias_t, bias_w);
+// the integer epilogue of one stand-alone layer (the operator layer of ops.hip)
+int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, const int32_t *q_b, int cout,
+                    int cout_pad, Requant *rq, int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w) {
+    return make_requant(cin, taps, sa_in, e_w, e_b, sa_out, have_out, act, 10, q_b, cout, cout_pad, rq, frac_bits, bias_t, bias_w);
 }
 
 struct y355_engine {
@@ -1157,179 +1157,5 @@ extern "C" int y355_profile_kernels_get(y355_engine *h, float *ms) {
         ms[k] = 0.f;
         if (h->kev_set[k]) HIPCHK(hipEventElapsedTime(&ms[k], h->kev[k][0], h->kev[k][1]));
     }
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Operator-level conv + bias + LeakyReLU WITHOUT requantisation: t' (int64) and F' such that the
-// reference's Conv2d_fuse output is exactly t' / 2^F' (utils/modules.py:20-29 on fake-quantized
-// operands).  Host pointers, synchronous.
-extern "C" int y355_conv3x3_i8_raw(int device_id, const int8_t *q_in, const int8_t *q_w, const int32_t *q_b,
-                                   int batch, int cin, int cout, int H, int W, int sa_in, int e_w, int e_b,
-                                   int flags, int64_t *out, int32_t *frac_bits) {
-    if (!q_in || !q_w || !q_b || !out || !frac_bits) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || cin < 1 || cin > 256 || cout < 1 || H < 1 || W < 1) return fail(Y355_EINVAL, "bad shape (cin <= 256)");
-    if ((flags & Y355_OP_LEAKY) && (flags & Y355_OP_RELU)) return fail(Y355_EINVAL, "LeakyReLU and ReLU are exclusive");
-    const int leaky = (flags & Y355_OP_LEAKY) ? 1 : ((flags & Y355_OP_RELU) ? 2 : 0);
-    HIPCHK(hipSetDevice(device_id));
-    if (int e = prepare_kernels()) return e;
-    const int cpad = cin <= 16 ? 16 : cin <= 32 ? 32 : cin <= 64 ? 64 : cin <= 128 ? 128 : 256;
-    const int sel = cpad == 16 ? 0 : cpad == 32 ? 1 : cpad == 64 ? 2 : cpad == 128 ? 3 : 4;
-    const ConvKernelInfo &ki = *y355_conv_kernel(Y355_K_GEN16 + sel);
-    const int cout_pad = (cout + ki.bn - 1) / ki.bn * ki.bn;
-    Requant rq{};
-    int fb = 0;
-    std::vector<int32_t> bt;
-    std::vector<long long> bw;
-    if (int rc = make_requant(cin, 9, sa_in, e_w, e_b, 0, false, leaky, 10, q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
-    const size_t in_elems = ((size_t)batch * (H + 2) * (W + 2) + 64) * cpad;
-    std::vector<int8_t> xin(in_elems, 0);
-    for (int b = 0; b < batch; ++b)
-        for (int c = 0; c < cin; ++c)
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x)
-                    xin[(((size_t)b * (H + 2) + y + 1) * (W + 2) + x + 1) * cpad + c] =
-                        q_in[(((size_t)b * cin + c) * H + y) * W + x];
-    std::vector<int8_t> packed(y355_packed_bytes(ki, cout_pad));
-    y355_pack_weights(ki, q_w, cout, cin, cout_pad, packed.data());
-    const size_t raw_elems = (size_t)batch * H * W * cout_pad;
-    int8_t *d_in = nullptr, *d_w = nullptr;
-    int *d_b = nullptr;
-    long long *d_bw = nullptr, *d_raw = nullptr;
-    Counters *d_c = nullptr;
-    auto cleanup = [&]() {
-        (void)hipFree(d_in); (void)hipFree(d_w); (void)hipFree(d_b); (void)hipFree(d_bw); (void)hipFree(d_raw); (void)hipFree(d_c);
-    };
-#define RAWCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            cleanup();                                                                      \
-            return fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-        }                                                                                   \
-    } while (0)
-    RAWCHK(hipMalloc((void **)&d_in, in_elems));
-    RAWCHK(hipMalloc((void **)&d_w, packed.size()));
-    RAWCHK(hipMalloc((void **)&d_b, sizeof(int) * cout_pad));
-    RAWCHK(hipMalloc((void **)&d_bw, sizeof(long long) * cout_pad));
-    RAWCHK(hipMalloc((void **)&d_raw, sizeof(long long) * raw_elems));
-    RAWCHK(hipMalloc((void **)&d_c, sizeof(Counters)));
-    RAWCHK(hipMemcpy(d_in, xin.data(), in_elems, hipMemcpyHostToDevice));
-    RAWCHK(hipMemcpy(d_w, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    RAWCHK(hipMemcpy(d_b, bt.data(), sizeof(int) * cout_pad, hipMemcpyHostToDevice));
-    RAWCHK(hipMemcpy(d_bw, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
-    RAWCHK(hipMemset(d_c, 0, sizeof(Counters)));
-    ConvParams p{};
-    p.in = d_in; p.out = nullptr; p.w = d_w; p.bias_t = d_b; p.bias_w = d_bw; p.ctr = d_c; p.raw = d_raw;
-    p.B = batch; p.H = H; p.W = W; p.cstride = cout_pad; p.out_halo = 0;
-    p.tiles_x = (W + ki.tw - 1) / ki.tw; p.tiles_y = (H + ki.th - 1) / ki.th; p.nblk = cout_pad / ki.bn;
-    p.rq = rq; p.mode = 1; p.guard = 0;
-    ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, 0);
-    RAWCHK(hipGetLastError());
-    RAWCHK(hipDeviceSynchronize());
-    std::vector<long long> o(raw_elems);
-    RAWCHK(hipMemcpy(o.data(), d_raw, sizeof(long long) * raw_elems, hipMemcpyDeviceToHost));
-    cleanup();
-    for (int b = 0; b < batch; ++b)
-        for (int c = 0; c < cout; ++c)
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x)
-                    out[(((size_t)b * cout + c) * H + y) * W + x] = o[(((size_t)b * H + y) * W + x) * cout_pad + c];
-    *frac_bits = fb;
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Operator-level fused layer on caller data (utils/modules.py Conv2d_fuse drop-in, unit tests)
-extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const int8_t *q_w, const int32_t *q_b,
-                                     int batch, int cin, int cout, int H, int W, int sa_in, int e_w, int e_b,
-                                     int sa_out, int flags, int8_t *out, y355_layer_stats *stats) {
-    if (!q_in || !q_w || !q_b || !out) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || cin < 1 || cin > 256 || cout < 1 || H < 1 || W < 1) return fail(Y355_EINVAL, "bad shape (cin <= 256)");
-    if ((flags & Y355_OP_LEAKY) && (flags & Y355_OP_RELU)) return fail(Y355_EINVAL, "LeakyReLU and ReLU are exclusive");
-    const int pool = (flags & Y355_OP_POOL) ? 1 : 0, leaky = (flags & Y355_OP_LEAKY) ? 1 : ((flags & Y355_OP_RELU) ? 2 : 0);
-    if (pool && ((H | W) & 1)) return fail(Y355_EINVAL, "pooling needs even H, W");
-    HIPCHK(hipSetDevice(device_id));
-    if (int e = prepare_kernels()) return e;
-    const int cpad = cin <= 16 ? 16 : cin <= 32 ? 32 : cin <= 64 ? 64 : cin <= 128 ? 128 : 256;
-    const int sel = cpad == 16 ? 0 : cpad == 32 ? 1 : cpad == 64 ? 2 : cpad == 128 ? 3 : 4;
-    const int kid = (pool ? Y355_K_GEN16P : Y355_K_GEN16) + sel;
-    const ConvKernelInfo &ki = *y355_conv_kernel(kid);
-    const int cout_pad = (cout + ki.bn - 1) / ki.bn * ki.bn;
-    const int Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-    Requant rq{};
-    int fb = 0;
-    std::vector<int32_t> bt;
-    std::vector<long long> bw;
-    if (int rc = make_requant(cin, 9, sa_in, e_w, e_b, sa_out, true, leaky, 10, q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
-    // host-side layout conversion: NCHW -> NHWC with halo and zero channel padding
-    const size_t in_elems = ((size_t)batch * (H + 2) * (W + 2) + 64) * cpad;
-    std::vector<int8_t> xin(in_elems, 0);
-    for (int b = 0; b < batch; ++b)
-        for (int c = 0; c < cin; ++c)
-            for (int y = 0; y < H; ++y)
-                for (int x = 0; x < W; ++x)
-                    xin[(((size_t)b * (H + 2) + y + 1) * (W + 2) + x + 1) * cpad + c] =
-                        q_in[(((size_t)b * cin + c) * H + y) * W + x];
-    std::vector<int8_t> packed(y355_packed_bytes(ki, cout_pad));
-    y355_pack_weights(ki, q_w, cout, cin, cout_pad, packed.data());
-    const size_t out_elems = (size_t)batch * Ho * Wo * cout_pad;
-    int8_t *d_in = nullptr, *d_w = nullptr, *d_out = nullptr;
-    int *d_b = nullptr;
-    long long *d_bw = nullptr;
-    Counters *d_c = nullptr;
-    int rc = 0;
-    auto cleanup = [&]() {
-        (void)hipFree(d_in); (void)hipFree(d_w); (void)hipFree(d_out); (void)hipFree(d_b); (void)hipFree(d_bw); (void)hipFree(d_c);
-    };
-#define OPCHK(expr)                                                                         \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            cleanup();                                                                      \
-            return fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));      \
-        }                                                                                   \
-    } while (0)
-    OPCHK(hipMalloc((void **)&d_in, in_elems));
-    OPCHK(hipMalloc((void **)&d_w, packed.size()));
-    OPCHK(hipMalloc((void **)&d_out, out_elems + 64));
-    OPCHK(hipMalloc((void **)&d_b, sizeof(int) * cout_pad));
-    OPCHK(hipMalloc((void **)&d_bw, sizeof(long long) * cout_pad));
-    OPCHK(hipMalloc((void **)&d_c, sizeof(Counters)));
-    OPCHK(hipMemcpy(d_in, xin.data(), in_elems, hipMemcpyHostToDevice));
-    OPCHK(hipMemcpy(d_w, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    OPCHK(hipMemcpy(d_b, bt.data(), sizeof(int) * cout_pad, hipMemcpyHostToDevice));
-    OPCHK(hipMemcpy(d_bw, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
-    OPCHK(hipMemset(d_out, 0, out_elems + 64));
-    Counters cz{};
-    Counters cs{};
-    for (int mode = 1; mode >= 0; --mode) {
-        OPCHK(hipMemset(d_c, 0, sizeof(Counters)));
-        ConvParams p{};
-        p.in = d_in; p.out = d_out; p.w = d_w; p.bias_t = d_b; p.bias_w = d_bw; p.ctr = d_c;
-        p.B = batch; p.H = H; p.W = W; p.cstride = cout_pad; p.out_halo = 0;
-        p.tiles_x = (W + ki.tw - 1) / ki.tw; p.tiles_y = (H + ki.th - 1) / ki.th; p.nblk = cout_pad / ki.bn;
-        p.rq = rq; p.mode = mode; p.guard = 1;
-        ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, 0);
-        OPCHK(hipGetLastError());
-        OPCHK(hipDeviceSynchronize());
-        OPCHK(hipMemcpy(mode ? &cs : &cz, d_c, sizeof(Counters), hipMemcpyDeviceToHost));
-    }
-    std::vector<int8_t> o(out_elems);
-    OPCHK(hipMemcpy(o.data(), d_out, out_elems, hipMemcpyDeviceToHost));
-    cleanup();
-    for (int b = 0; b < batch; ++b)
-        for (int c = 0; c < cout; ++c)
-            for (int y = 0; y < Ho; ++y)
-                for (int x = 0; x < Wo; ++x)
-                    out[(((size_t)b * cout + c) * Ho + y) * Wo + x] = o[(((size_t)b * Ho + y) * Wo + x) * cout_pad + c];
-    if (stats) {
-        stats->absmax_t = (int64_t)cs.absmax;
-        stats->frac_bits = fb;
-        stats->reserved = 0;
-        stats->saturated = (int64_t)cz.sat;
-        stats->guard = (int64_t)cz.guard;
-    }
-    (void)rc;
     return 0;
 }

@@ -1,9 +1,24 @@
-// yolo355 -- operator-level entry points for the two element-wise ops of the path that the fused
-// layers absorb: stand-alone forms for unit tests and for callers that hold their own
-// int8 tensors.  Host pointers, synchronous; NCHW like the reference's tensors.
-//   y355_quantize_input_f32_i8  AveragedRangeTracker.quantize_activation on the network input
-//                               (models/slim_yolo_v2.py:33-38): q = clamp(RNE(x * 2^sa), +-127)
-//   y355_maxpool2x2_i8          nn.MaxPool2d(2, 2) (:61,65,71,77) on int8
+// yolo355 -- the operator layer: the stand-alone y355_* entry points that the drop-in modules (utils.modules), the composed
+// YOLOv2 / v3 models and the operator tests go through.  Tensors are NCHW like the reference's.  Every operator has ONE
+// implementation:
+//   element-wise (reorg, SPP, 2x2 max-pool, bilinear 2x upsampling, on fp32)
+//       the *_dev form checks the shape and launches on the caller's stream; the host-pointer form checks the pointers,
+//       uploads, calls the *_dev form on the null stream, synchronises and downloads (host_form).  The two int8 helpers of
+//       the slim path (input fake-quant, int8 max-pool) have a host-pointer form only.
+//   convolution: y355_conv_op, an operator whose weights live packed on the device
+//       bf16  conv_forward_bf16: conv + bias + LeakyReLU(slope) [+ residual], operands and result rounded to bf16, fp32
+//             accumulation.  The 3x3 / 1x1 kernels of convg.hip and the general geometry of convgeom.hip differ in conv_plan
+//             (kernel id, output size), in op_weights' packer and at the launch; the weight cache, the workspaces, the
+//             re-zeroing for a new geometry, staging and unstaging are written once.
+//       int8  y355_conv_op_forward_i8: Conv2d_fuse on a dyadic tensor, exact.  Exponent detection, then i8_prepare (weights,
+//             the requantisation constants cached per exponent, workspaces), staging with the dyadic verdict, i8_launch (the
+//             Y355_K_GEN16.. kernels of conv3x3.hip, or convgeom.hip) and unstaging.
+//       The host-pointer forms run on a temporary operator made by the same create functions: y355_conv2d_bf16 and
+//       y355_conv2d_geom_bf16 through conv_forward_bf16; y355_conv3x3_i8_raw and y355_conv_geom_i8_raw, whose input is int8
+//       at a GIVEN exponent, enter below the exponent detection, at i8_prepare / i8_launch.  y355_conv3x3_i8_fused (the
+//       requantising layer with its statistics pass) shares the kernel ladder, the parameter fill and the host layout helpers.
+// Errors: HIPTRY returns Y355_EHIP with the failing call; temporary device memory belongs to a Scratch and a temporary
+// operator to an OpOwner, so no return path frees by hand.  Argument checks come before the first HIP call.
 #include "../../include/yolo355.h"
 #include "y355_common.h"
 
@@ -13,19 +28,29 @@
 #include <string>
 #include <vector>
 
-int y355_fail(int code, const std::string &msg);
-#define OPSCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            (void)hipFree(d_in);                                                            \
-            (void)hipFree(d_out);                                                           \
-            (void)hipFree(d_cnt);                                                           \
-            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-        }                                                                                   \
+#define HIPTRY(expr)                                                                                            \
+    do {                                                                                                        \
+        hipError_t e_ = (expr);                                                                                 \
+        if (e_ != hipSuccess) return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
     } while (0)
 
 namespace {
+// temporary device memory of one call: freed when the call returns, whichever way
+struct Scratch {
+    std::vector<void *> bufs;
+    ~Scratch() { for (void *p : bufs) (void)hipFree(p); }
+    template <class T> hipError_t get(T **p, size_t bytes) {
+        const hipError_t e = hipMalloc((void **)p, bytes);
+        if (e == hipSuccess) bufs.push_back(*p);
+        return e;
+    }
+};
+
+inline int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 16384); }
+inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
+
+// ---- kernels: element-wise ------------------------------------------------------------------------------------------------
+// AveragedRangeTracker.quantize_activation on the network input (models/slim_yolo_v2.py:33-38): q = clamp(RNE(x * 2^sa), +-127)
 __global__ void quantize_f32_i8_kernel(const float *x, int8_t *q, size_t n, float scale, unsigned long long *nclamped) {
     unsigned int c = 0;
     for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
@@ -37,6 +62,7 @@ __global__ void quantize_f32_i8_kernel(const float *x, int8_t *q, size_t n, floa
     if (c) atomicAdd(nclamped, (unsigned long long)c);
 }
 
+// nn.MaxPool2d(2, 2) (models/slim_yolo_v2.py:61,65,71,77) on int8
 __global__ void maxpool2x2_i8_kernel(const int8_t *in, int8_t *out, size_t planes, int H, int W) {
     const int Ho = H >> 1, Wo = W >> 1;
     const size_t n = planes * Ho * Wo;
@@ -47,77 +73,8 @@ __global__ void maxpool2x2_i8_kernel(const int8_t *in, int8_t *out, size_t plane
         out[i] = (int8_t)max(max((int)s[0], (int)s[1]), max((int)s[W], (int)s[W + 1]));
     }
 }
-}  // namespace
 
-extern "C" int y355_quantize_input_f32_i8(int device_id, const float *x, size_t n, int sa, int8_t *q, int64_t *clamped) {
-    if (!x || !q) return y355_fail(Y355_EINVAL, "null argument");
-    if (n == 0) return y355_fail(Y355_EINVAL, "empty tensor");
-    if (sa < -64 || sa > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
-    float *d_in = nullptr;
-    int8_t *d_out = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    OPSCHK(hipSetDevice(device_id));
-    OPSCHK(hipMalloc((void **)&d_in, n * sizeof(float)));
-    OPSCHK(hipMalloc((void **)&d_out, n));
-    OPSCHK(hipMalloc((void **)&d_cnt, 8));
-    OPSCHK(hipMemcpy(d_in, x, n * sizeof(float), hipMemcpyHostToDevice));
-    OPSCHK(hipMemset(d_cnt, 0, 8));
-    const int blocks = (int)std::min<size_t>((n + 255) / 256, 8192);
-    hipLaunchKernelGGL(quantize_f32_i8_kernel, dim3(blocks), dim3(256), 0, 0, d_in, d_out, n, std::ldexp(1.0f, sa), d_cnt);
-    OPSCHK(hipGetLastError());
-    OPSCHK(hipDeviceSynchronize());
-    OPSCHK(hipMemcpy(q, d_out, n, hipMemcpyDeviceToHost));
-    unsigned long long c = 0;
-    OPSCHK(hipMemcpy(&c, d_cnt, 8, hipMemcpyDeviceToHost));
-    if (clamped) *clamped = (int64_t)c;
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    (void)hipFree(d_cnt);
-    return 0;
-}
-
-extern "C" int y355_maxpool2x2_i8(int device_id, const int8_t *in, int batch, int channels, int height, int width, int8_t *out) {
-    if (!in || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || height < 2 || width < 2) return y355_fail(Y355_EINVAL, "bad shape");
-    if ((height | width) & 1) return y355_fail(Y355_EINVAL, "pooling needs even H, W");
-    const size_t planes = (size_t)batch * channels, nin = planes * height * width, nout = nin / 4;
-    int8_t *d_in = nullptr, *d_out = nullptr;
-    unsigned long long *d_cnt = nullptr;
-    OPSCHK(hipSetDevice(device_id));
-    OPSCHK(hipMalloc((void **)&d_in, nin));
-    OPSCHK(hipMalloc((void **)&d_out, nout));
-    OPSCHK(hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice));
-    const int blocks = (int)std::min<size_t>((nout + 255) / 256, 8192);
-    hipLaunchKernelGGL(maxpool2x2_i8_kernel, dim3(blocks), dim3(256), 0, 0, d_in, d_out, planes, height, width);
-    OPSCHK(hipGetLastError());
-    OPSCHK(hipDeviceSynchronize());
-    OPSCHK(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost));
-    (void)hipFree(d_in);
-    (void)hipFree(d_out);
-    return 0;
-}
-
-// ------------------------------------------------------------------------------------------
-// Operator API of the wider model families, stand-alone forms.  Host pointers, fp32
-// NCHW like the reference's tensors, synchronous.
-//   y355_reorg_f32    utils.modules.reorg_layer (utils/modules.py:43-57): out[b][(sy*s+sx)*C + c][y][x] =
-//                     in[b][c][s*y+sy][s*x+sx]  (data movement: bit-exact)
-//   y355_spp_f32      utils.modules.SPP (:59-72): cat[x, maxpool5(x), maxpool9(x), maxpool13(x)], stride 1,
-//                     padding k/2 with -inf  (max of fp32: bit-exact)
-//   y355_conv2d_bf16  utils.modules.Conv2d / backbone.darknet.Conv_BN_LeakyReLU / resblock with BN folded
-//                     by the caller: conv (1x1, or 3x3 pad 1; stride 1, or 2 for 3x3) + bias +
-//                     LeakyReLU(neg_slope) [+ residual], operands rounded to bf16, fp32 accumulation on
-//                     v_mfma_f32_16x16x32_bf16 (convg.hip), result rounded to bf16
-namespace {
-#define OPS2CHK(expr)                                                                       \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) {                                                             \
-            for (void *q_ : bufs) (void)hipFree(q_);                                        \
-            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-        }                                                                                   \
-    } while (0)
-
+// utils.modules.reorg_layer (utils/modules.py:43-57): out[b][(sy*s+sx)*C + c][y][x] = in[b][c][s*y+sy][s*x+sx]  (bit-exact)
 __global__ void reorg_f32_kernel(const float *in, float *out, int B, int C, int H, int W, int s) {
     const int Ho = H / s, Wo = W / s;
     const size_t n = (size_t)B * C * s * s * Ho * Wo;
@@ -130,6 +87,7 @@ __global__ void reorg_f32_kernel(const float *in, float *out, int B, int C, int 
     }
 }
 
+// utils.modules.SPP (:59-72): cat[x, maxpool5(x), maxpool9(x), maxpool13(x)], stride 1, padding k/2 with -inf  (bit-exact)
 __global__ void spp_f32_kernel(const float *in, float *out, size_t planes_b, int C, int H, int W) {
     // one thread per input element: writes x and the three window maxima (windows clipped to the map:
     // the -inf padding of max_pool2d never wins)
@@ -162,34 +120,6 @@ __global__ void spp_f32_kernel(const float *in, float *out, size_t planes_b, int
     }
 }
 
-// fp32 NCHW -> bf16 NHWC with a one-pixel halo and cpad channels (buffer zeroed beforehand)
-__global__ void nchw_to_nhwc_bf16_kernel(const float *in, unsigned short *out, int B, int C, int H, int W, int cpad) {
-    const size_t n = (size_t)B * C * H * W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W), y = (int)((i / W) % H);
-        const int c = (int)((i / ((size_t)W * H)) % C);
-        const size_t b = i / ((size_t)W * H * C);
-        out[((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * cpad + c] = __builtin_bit_cast(unsigned short, (__bf16)in[i]);
-    }
-}
-__global__ void nhwc_bf16_to_nchw_kernel(const unsigned short *in, float *out, int B, int C, int H, int W, int cpad) {
-    const size_t n = (size_t)B * C * H * W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W), y = (int)((i / W) % H);
-        const int c = (int)((i / ((size_t)W * H)) % C);
-        const size_t b = i / ((size_t)W * H * C);
-        out[i] = __uint_as_float((unsigned int)in[((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * cpad + c] << 16);
-    }
-}
-__global__ void nhwc_f32_to_nchw_kernel(const float *in, float *out, int B, int C, int H, int W, int cpad) {
-    const size_t n = (size_t)B * C * H * W;
-    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const int x = (int)(i % W), y = (int)((i / W) % H);
-        const int c = (int)((i / ((size_t)W * H)) % C);
-        const size_t b = i / ((size_t)W * H * C);
-        out[i] = in[((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * cpad + c];
-    }
-}
 __global__ void maxpool2x2_f32_kernel(const float *in, float *out, size_t planes, int H, int W) {
     const int Ho = H >> 1, Wo = W >> 1;
     const size_t n = planes * Ho * Wo;
@@ -218,184 +148,36 @@ __global__ void upsample2x_f32_kernel(const float *in, float *out, size_t planes
         out[i] = (1.f - ly) * top + ly * bot;
     }
 }
-inline int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 16384); }
-}  // namespace
 
-extern "C" int y355_reorg_f32(int device_id, const float *x, int batch, int channels, int height, int width, int stride, float *out) {
-    if (!x || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || stride < 1 || height < stride || width < stride) return y355_fail(Y355_EINVAL, "bad shape");
-    if (height % stride || width % stride) return y355_fail(Y355_EINVAL, "reorg needs H, W divisible by the stride");
-    const size_t n = (size_t)batch * channels * height * width;
-    std::vector<void *> bufs;
-    float *d_in = nullptr, *d_out = nullptr;
-    OPS2CHK(hipSetDevice(device_id));
-    OPS2CHK(hipMalloc((void **)&d_in, n * 4)); bufs.push_back(d_in);
-    OPS2CHK(hipMalloc((void **)&d_out, n * 4)); bufs.push_back(d_out);
-    OPS2CHK(hipMemcpy(d_in, x, n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(reorg_f32_kernel, dim3(grid_for(n)), dim3(256), 0, 0, d_in, d_out, batch, channels, height, width, stride);
-    OPS2CHK(hipGetLastError());
-    OPS2CHK(hipDeviceSynchronize());
-    OPS2CHK(hipMemcpy(out, d_out, n * 4, hipMemcpyDeviceToHost));
-    for (void *q : bufs) (void)hipFree(q);
-    return 0;
-}
-
-extern "C" int y355_spp_f32(int device_id, const float *x, int batch, int channels, int height, int width, float *out) {
-    if (!x || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    const size_t n = (size_t)batch * channels * height * width;
-    std::vector<void *> bufs;
-    float *d_in = nullptr, *d_out = nullptr;
-    OPS2CHK(hipSetDevice(device_id));
-    OPS2CHK(hipMalloc((void **)&d_in, n * 4)); bufs.push_back(d_in);
-    OPS2CHK(hipMalloc((void **)&d_out, n * 16)); bufs.push_back(d_out);
-    OPS2CHK(hipMemcpy(d_in, x, n * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(spp_f32_kernel, dim3(grid_for(n)), dim3(256), 0, 0, d_in, d_out, (size_t)batch, channels, height, width);
-    OPS2CHK(hipGetLastError());
-    OPS2CHK(hipDeviceSynchronize());
-    OPS2CHK(hipMemcpy(out, d_out, n * 16, hipMemcpyDeviceToHost));
-    for (void *q : bufs) (void)hipFree(q);
-    return 0;
-}
-
-extern "C" int y355_conv2d_bf16(int device_id, const float *x, const float *w, const float *bias, const float *residual,
-                                int batch, int cin, int cout, int height, int width, int ksize, int stride, float neg_slope,
-                                int out_fp32, float *out) {
-    if (!x || !w || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || cin < 1 || cout < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    if (ksize != 1 && ksize != 3) return y355_fail(Y355_EINVAL, "kernel size 1 or 3 (padding k/2)");
-    if (stride != 1 && !(stride == 2 && ksize == 3)) return y355_fail(Y355_EINVAL, "stride 1, or 2 with a 3x3 kernel");
-    const bool thin = (cin <= 16 && ksize == 3 && stride == 1);
-    const int cin_pad = thin ? 16 : (cin + 31) / 32 * 32;
-    const int in_pb = cin_pad * 2;
-    const int kid = y355_convg_select(in_pb, cout, 0, height, width, stride);
-    const ConvGInfo *ki = y355_convg_kernel(1, kid);
-    if (!ki) return y355_fail(Y355_EINVAL, "no kernel for this shape");
-    const int Ho = stride == 2 ? (height + 1) / 2 : height, Wo = stride == 2 ? (width + 1) / 2 : width;
-    const int cout_pad = (cout + ki->bn - 1) / ki->bn * ki->bn;
-    const int taps = ksize * ksize;
-    const size_t wbytes = y355_convg_packed_bytes(*ki, in_pb, taps, cout_pad);
-    std::vector<char> wpk(wbytes);
-    y355_convg_pack(*ki, w, nullptr, cout, cin, ksize, in_pb, cout_pad, wpk.data());
-    std::vector<float> bpad(cout_pad, 0.f);
-    if (bias) std::copy(bias, bias + cout, bpad.begin());
-    const size_t n_in = (size_t)batch * cin * height * width, n_out = (size_t)batch * cout * Ho * Wo;
-    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
-    if (out_fp32 && residual) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
-    const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
-    std::vector<void *> bufs;
-    float *d_x = nullptr, *d_y = nullptr, *d_b = nullptr;
-    char *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_res = nullptr;
-    OPS2CHK(hipSetDevice(device_id));
-    if (int e = y355_prepare_convg()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
-    OPS2CHK(hipMalloc((void **)&d_x, std::max(n_in, n_out) * 4)); bufs.push_back(d_x);
-    OPS2CHK(hipMalloc((void **)&d_y, n_out * 4)); bufs.push_back(d_y);
-    OPS2CHK(hipMalloc((void **)&d_b, cout_pad * 4)); bufs.push_back(d_b);
-    OPS2CHK(hipMalloc((void **)&d_in, in_bytes)); bufs.push_back(d_in);
-    OPS2CHK(hipMalloc((void **)&d_out, out_bytes)); bufs.push_back(d_out);
-    OPS2CHK(hipMalloc((void **)&d_w, wbytes)); bufs.push_back(d_w);
-    OPS2CHK(hipMemset(d_in, 0, in_bytes));
-    OPS2CHK(hipMemset(d_out, 0, out_bytes));
-    OPS2CHK(hipMemcpy(d_w, wpk.data(), wbytes, hipMemcpyHostToDevice));
-    OPS2CHK(hipMemcpy(d_b, bpad.data(), cout_pad * 4, hipMemcpyHostToDevice));
-    if (residual) {
-        OPS2CHK(hipMalloc((void **)&d_res, out_bytes)); bufs.push_back(d_res);
-        OPS2CHK(hipMemset(d_res, 0, out_bytes));
-        OPS2CHK(hipMemcpy(d_x, residual, n_out * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, d_x, (unsigned short *)d_res, batch, cout, Ho,
-                           Wo, cout_pad);
-        OPS2CHK(hipDeviceSynchronize());
+// ---- kernels: layouts of the convolutions ---------------------------------------------------------------------------------
+// fp32 NCHW -> bf16 NHWC with a one-pixel halo and cpad channels (buffer zeroed beforehand)
+__global__ void nchw_to_nhwc_bf16_kernel(const float *in, unsigned short *out, int B, int C, int H, int W, int cpad) {
+    const size_t n = (size_t)B * C * H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        const int c = (int)((i / ((size_t)W * H)) % C);
+        const size_t b = i / ((size_t)W * H * C);
+        out[((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * cpad + c] = __builtin_bit_cast(unsigned short, (__bf16)in[i]);
     }
-    OPS2CHK(hipMemcpy(d_x, x, n_in * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, 0, d_x, (unsigned short *)d_in, batch, cin, height,
-                       width, cin_pad);
-    ConvGParams p{};
-    p.in = d_in;
-    p.out = d_out;
-    p.w = d_w;
-    p.bias_f = d_b;
-    p.B = batch;
-    p.H = height;
-    p.W = width;
-    p.in_pb = in_pb;
-    p.nchunks = in_pb / ki->chb;
-    p.out_pb = (int)out_pb;
-    p.out_off = 0;
-    p.out_halo = 1;
-    p.tiles_x = (Wo + ki->tw - 1) / ki->tw;
-    p.tiles_y = (Ho + ki->th - 1) / ki->th;
-    p.nblk = cout_pad / ki->bn;
-    p.taps = taps;
-    p.slope = neg_slope;
-    p.out_f32 = out_fp32 ? 1 : 0;
-    p.res = d_res;
-    p.res_pb = (int)out_pb;
-    p.res_off = 0;
-    ki->launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, 0);
-    OPS2CHK(hipGetLastError());
-    if (out_fp32)
-        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, (const float *)d_out, d_y, batch, cout, Ho, Wo,
-                           cout_pad);
-    else
-        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, (const unsigned short *)d_out, d_y, batch,
-                           cout, Ho, Wo, cout_pad);
-    OPS2CHK(hipGetLastError());
-    OPS2CHK(hipDeviceSynchronize());
-    OPS2CHK(hipMemcpy(out, d_y, n_out * 4, hipMemcpyDeviceToHost));
-    for (void *q : bufs) (void)hipFree(q);
-    return 0;
 }
-
-extern "C" int y355_maxpool2x2_f32(int device_id, const float *in, int batch, int channels, int height, int width, float *out) {
-    if (!in || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || height < 2 || width < 2) return y355_fail(Y355_EINVAL, "bad shape");
-    if ((height | width) & 1) return y355_fail(Y355_EINVAL, "pooling needs even H, W");
-    const size_t planes = (size_t)batch * channels, nin = planes * height * width, nout = nin / 4;
-    std::vector<void *> bufs;
-    float *d_in = nullptr, *d_out = nullptr;
-    OPS2CHK(hipSetDevice(device_id));
-    OPS2CHK(hipMalloc((void **)&d_in, nin * 4)); bufs.push_back(d_in);
-    OPS2CHK(hipMalloc((void **)&d_out, nout * 4)); bufs.push_back(d_out);
-    OPS2CHK(hipMemcpy(d_in, in, nin * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(maxpool2x2_f32_kernel, dim3(grid_for(nout)), dim3(256), 0, 0, d_in, d_out, planes, height, width);
-    OPS2CHK(hipGetLastError());
-    OPS2CHK(hipDeviceSynchronize());
-    OPS2CHK(hipMemcpy(out, d_out, nout * 4, hipMemcpyDeviceToHost));
-    for (void *q : bufs) (void)hipFree(q);
-    return 0;
+__global__ void nhwc_bf16_to_nchw_kernel(const unsigned short *in, float *out, int B, int C, int H, int W, int cpad) {
+    const size_t n = (size_t)B * C * H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        const int c = (int)((i / ((size_t)W * H)) % C);
+        const size_t b = i / ((size_t)W * H * C);
+        out[i] = __uint_as_float((unsigned int)in[((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * cpad + c] << 16);
+    }
 }
-
-extern "C" int y355_upsample2x_f32(int device_id, const float *in, int batch, int channels, int height, int width, float *out) {
-    if (!in || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    const size_t planes = (size_t)batch * channels, nin = planes * height * width, nout = nin * 4;
-    std::vector<void *> bufs;
-    float *d_in = nullptr, *d_out = nullptr;
-    OPS2CHK(hipSetDevice(device_id));
-    OPS2CHK(hipMalloc((void **)&d_in, nin * 4)); bufs.push_back(d_in);
-    OPS2CHK(hipMalloc((void **)&d_out, nout * 4)); bufs.push_back(d_out);
-    OPS2CHK(hipMemcpy(d_in, in, nin * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(upsample2x_f32_kernel, dim3(grid_for(nout)), dim3(256), 0, 0, d_in, d_out, planes, height, width);
-    OPS2CHK(hipGetLastError());
-    OPS2CHK(hipDeviceSynchronize());
-    OPS2CHK(hipMemcpy(out, d_out, nout * 4, hipMemcpyDeviceToHost));
-    for (void *q : bufs) (void)hipFree(q);
-    return 0;
+__global__ void nhwc_f32_to_nchw_kernel(const float *in, float *out, int B, int C, int H, int W, int cpad) {
+    const size_t n = (size_t)B * C * H * W;
+    for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
+        const int x = (int)(i % W), y = (int)((i / W) % H);
+        const int c = (int)((i / ((size_t)W * H)) % C);
+        const size_t b = i / ((size_t)W * H * C);
+        out[i] = in[((b * (H + 2) + y + 1) * (size_t)(W + 2) + x + 1) * cpad + c];
+    }
 }
-
-
-// ==========================================================================================================================
-// Device-resident operator forms (round 6).  The entry points above take host pointers and copy through
-// temporary device buffers -- right for unit tests, wrong for a caller whose tensors already live on the GPU
-// (utils.modules.Conv2d / Conv2d_fuse / reorg_layer / SPP called on CUDA tensors).  These take DEVICE pointers (fp32 NCHW, the
-// reference's tensors) and a stream, launch behind whatever that stream holds and return without a host round trip.
-//   y355_reorg_f32_dev / y355_spp_f32_dev / y355_maxpool2x2_f32_dev / y355_upsample2x_f32_dev: one launch each
-//   y355_conv_op: a convolution whose weights were packed onto the device ONCE (create), then forward per call;
-//     bf16 form = y355_conv2d_bf16's arithmetic; int8 form = y355_conv3x3_i8_raw's (Conv2d_fuse on dyadic operands, exact):
-//     the input's exponent and the verdict "is x a dyadic int8 tensor" are needed on the HOST (they select the route and the
-//     requantisation constants): two 4-byte read-backs per call, nothing else leaves the device.
-// A y355_conv_op owns its packed weights and growable workspaces; single-threaded like an engine handle.
-namespace {
 // fp32 NCHW dyadic tensor -> int8 NHWC with halo (cpad channels): q = x * 2^sa; *bad += values that are not integers in [-127, 127]
 __global__ void dyadic_to_nhwc_i8_kernel(const float *in, int8_t *out, int B, int C, int H, int W, int cpad, float scale, unsigned int *bad) {
     const size_t n = (size_t)B * C * H * W;
@@ -420,326 +202,215 @@ __global__ void raw_to_nchw_f32_kernel(const long long *raw, float *out, int B, 
         out[i] = (float)raw[((b * H + y) * (size_t)W + x) * cpad + c] * inv;
     }
 }
-#define DEVCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess) return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
+
+// ---- host-side layout helpers of the int8 host-pointer forms ---------------------------------------------------------------
+// int8 NCHW -> NHWC with a one-pixel halo and cpad channels, zero elsewhere; `bytes` = the device buffer's size
+std::vector<int8_t> nhwc_halo_i8(const int8_t *q, int batch, int cin, int H, int W, int cpad, size_t bytes) {
+    std::vector<int8_t> xin(bytes, 0);
+    for (int b = 0; b < batch; ++b)
+        for (int c = 0; c < cin; ++c)
+            for (int y = 0; y < H; ++y)
+                for (int x = 0; x < W; ++x)
+                    xin[(((size_t)b * (H + 2) + y + 1) * (W + 2) + x + 1) * cpad + c] = q[(((size_t)b * cin + c) * H + y) * W + x];
+    return xin;
+}
+// [B][Ho][Wo][cout_pad] -> NCHW, the cout real channels
+template <class S, class D> void nhwc_to_nchw(const S *o, D *out, int batch, int cout, int Ho, int Wo, int cout_pad) {
+    for (int b = 0; b < batch; ++b)
+        for (int c = 0; c < cout; ++c)
+            for (int y = 0; y < Ho; ++y)
+                for (int x = 0; x < Wo; ++x)
+                    out[(((size_t)b * cout + c) * Ho + y) * Wo + x] = (D)o[(((size_t)b * Ho + y) * Wo + x) * cout_pad + c];
+}
+
+// host-pointer form of an element-wise fp32 operator: upload, the *_dev form on the null stream, synchronise, download
+template <class F> int host_form(int device_id, const float *x, size_t n_in, float *out, size_t n_out, F dev_form) {
+    Scratch tmp;
+    float *d_in = nullptr, *d_out = nullptr;
+    HIPTRY(hipSetDevice(device_id));
+    HIPTRY(tmp.get(&d_in, n_in * 4));
+    HIPTRY(tmp.get(&d_out, n_out * 4));
+    HIPTRY(hipMemcpy(d_in, x, n_in * 4, hipMemcpyHostToDevice));
+    if (int rc = dev_form(d_in, d_out)) return rc;
+    HIPTRY(hipDeviceSynchronize());
+    HIPTRY(hipMemcpy(out, d_out, n_out * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+// the shape checks of the element-wise operators; *n = elements of the input
+int map_shape(int batch, int channels, int height, int width, int min_hw, size_t *n) {
+    if (batch < 1 || channels < 1 || height < min_hw || width < min_hw) return y355_fail(Y355_EINVAL, "bad shape");
+    *n = (size_t)batch * channels * height * width;
+    return 0;
+}
+int reorg_shape(int batch, int channels, int height, int width, int stride, size_t *n) {
+    if (stride < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    if (int rc = map_shape(batch, channels, height, width, stride, n)) return rc;
+    if (height % stride || width % stride) return y355_fail(Y355_EINVAL, "reorg needs H, W divisible by the stride");
+    return 0;
+}
+int pool_shape(int batch, int channels, int height, int width, size_t *n) {
+    if (int rc = map_shape(batch, channels, height, width, 2, n)) return rc;
+    if ((height | width) & 1) return y355_fail(Y355_EINVAL, "pooling needs even H, W");
+    return 0;
+}
 }  // namespace
-int y355_prepare_kernels();
-int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int act, const int32_t *q_b, int cout, int cout_pad, Requant *rq,
-                    int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w);       // engine.hip
+
+// ==========================================================================================================================
+// Element-wise operators
+extern "C" int y355_quantize_input_f32_i8(int device_id, const float *x, size_t n, int sa, int8_t *q, int64_t *clamped) {
+    if (!x || !q) return y355_fail(Y355_EINVAL, "null argument");
+    if (n == 0) return y355_fail(Y355_EINVAL, "empty tensor");
+    if (sa < -64 || sa > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
+    Scratch tmp;
+    float *d_in = nullptr;
+    int8_t *d_out = nullptr;
+    unsigned long long *d_cnt = nullptr;
+    HIPTRY(hipSetDevice(device_id));
+    HIPTRY(tmp.get(&d_in, n * sizeof(float)));
+    HIPTRY(tmp.get(&d_out, n));
+    HIPTRY(tmp.get(&d_cnt, 8));
+    HIPTRY(hipMemcpy(d_in, x, n * sizeof(float), hipMemcpyHostToDevice));
+    HIPTRY(hipMemset(d_cnt, 0, 8));
+    const int blocks = (int)std::min<size_t>((n + 255) / 256, 8192);
+    hipLaunchKernelGGL(quantize_f32_i8_kernel, dim3(blocks), dim3(256), 0, 0, d_in, d_out, n, std::ldexp(1.0f, sa), d_cnt);
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipDeviceSynchronize());
+    HIPTRY(hipMemcpy(q, d_out, n, hipMemcpyDeviceToHost));
+    unsigned long long c = 0;
+    HIPTRY(hipMemcpy(&c, d_cnt, 8, hipMemcpyDeviceToHost));
+    if (clamped) *clamped = (int64_t)c;
+    return 0;
+}
+
+extern "C" int y355_maxpool2x2_i8(int device_id, const int8_t *in, int batch, int channels, int height, int width, int8_t *out) {
+    if (!in || !out) return y355_fail(Y355_EINVAL, "null argument");
+    size_t nin = 0;
+    if (int rc = pool_shape(batch, channels, height, width, &nin)) return rc;
+    const size_t nout = nin / 4;
+    Scratch tmp;
+    int8_t *d_in = nullptr, *d_out = nullptr;
+    HIPTRY(hipSetDevice(device_id));
+    HIPTRY(tmp.get(&d_in, nin));
+    HIPTRY(tmp.get(&d_out, nout));
+    HIPTRY(hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice));
+    const int blocks = (int)std::min<size_t>((nout + 255) / 256, 8192);
+    hipLaunchKernelGGL(maxpool2x2_i8_kernel, dim3(blocks), dim3(256), 0, 0, d_in, d_out, (size_t)batch * channels, height, width);
+    HIPTRY(hipGetLastError());
+    HIPTRY(hipDeviceSynchronize());
+    HIPTRY(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost));
+    return 0;
+}
 
 extern "C" int y355_reorg_f32_dev(const float *x_dev, int batch, int channels, int height, int width, int stride, float *out_dev, void *stream) {
     if (!x_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || stride < 1 || height < stride || width < stride) return y355_fail(Y355_EINVAL, "bad shape");
-    if (height % stride || width % stride) return y355_fail(Y355_EINVAL, "reorg needs H, W divisible by the stride");
-    const size_t n = (size_t)batch * channels * height * width;
+    size_t n = 0;
+    if (int rc = reorg_shape(batch, channels, height, width, stride, &n)) return rc;
     hipLaunchKernelGGL(reorg_f32_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x_dev, out_dev, batch, channels, height, width, stride);
-    DEVCHK(hipGetLastError());
+    HIPTRY(hipGetLastError());
     return 0;
 }
 extern "C" int y355_spp_f32_dev(const float *x_dev, int batch, int channels, int height, int width, float *out_dev, void *stream) {
     if (!x_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    const size_t n = (size_t)batch * channels * height * width;
+    size_t n = 0;
+    if (int rc = map_shape(batch, channels, height, width, 1, &n)) return rc;
     hipLaunchKernelGGL(spp_f32_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x_dev, out_dev, (size_t)batch, channels, height, width);
-    DEVCHK(hipGetLastError());
+    HIPTRY(hipGetLastError());
     return 0;
 }
 extern "C" int y355_maxpool2x2_f32_dev(const float *in_dev, int batch, int channels, int height, int width, float *out_dev, void *stream) {
     if (!in_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || height < 2 || width < 2 || ((height | width) & 1)) return y355_fail(Y355_EINVAL, "bad shape (even H, W)");
-    const size_t planes = (size_t)batch * channels, nout = planes * height * width / 4;
-    hipLaunchKernelGGL(maxpool2x2_f32_kernel, dim3(grid_for(nout)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, planes, height, width);
-    DEVCHK(hipGetLastError());
+    size_t n = 0;
+    if (int rc = pool_shape(batch, channels, height, width, &n)) return rc;
+    hipLaunchKernelGGL(maxpool2x2_f32_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, (size_t)batch * channels,
+                       height, width);
+    HIPTRY(hipGetLastError());
     return 0;
 }
 extern "C" int y355_upsample2x_f32_dev(const float *in_dev, int batch, int channels, int height, int width, float *out_dev, void *stream) {
     if (!in_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || channels < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    const size_t planes = (size_t)batch * channels, nout = planes * height * width * 4;
-    hipLaunchKernelGGL(upsample2x_f32_kernel, dim3(grid_for(nout)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, planes, height, width);
-    DEVCHK(hipGetLastError());
+    size_t n = 0;
+    if (int rc = map_shape(batch, channels, height, width, 1, &n)) return rc;
+    hipLaunchKernelGGL(upsample2x_f32_kernel, dim3(grid_for(n * 4)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, (size_t)batch * channels,
+                       height, width);
+    HIPTRY(hipGetLastError());
     return 0;
 }
 
+extern "C" int y355_reorg_f32(int device_id, const float *x, int batch, int channels, int height, int width, int stride, float *out) {
+    if (!x || !out) return y355_fail(Y355_EINVAL, "null argument");
+    size_t n = 0;
+    if (int rc = reorg_shape(batch, channels, height, width, stride, &n)) return rc;
+    return host_form(device_id, x, n, out, n,
+                     [&](const float *dx, float *dy) { return y355_reorg_f32_dev(dx, batch, channels, height, width, stride, dy, nullptr); });
+}
+extern "C" int y355_spp_f32(int device_id, const float *x, int batch, int channels, int height, int width, float *out) {
+    if (!x || !out) return y355_fail(Y355_EINVAL, "null argument");
+    size_t n = 0;
+    if (int rc = map_shape(batch, channels, height, width, 1, &n)) return rc;
+    return host_form(device_id, x, n, out, n * 4,
+                     [&](const float *dx, float *dy) { return y355_spp_f32_dev(dx, batch, channels, height, width, dy, nullptr); });
+}
+extern "C" int y355_maxpool2x2_f32(int device_id, const float *in, int batch, int channels, int height, int width, float *out) {
+    if (!in || !out) return y355_fail(Y355_EINVAL, "null argument");
+    size_t n = 0;
+    if (int rc = pool_shape(batch, channels, height, width, &n)) return rc;
+    return host_form(device_id, in, n, out, n / 4,
+                     [&](const float *dx, float *dy) { return y355_maxpool2x2_f32_dev(dx, batch, channels, height, width, dy, nullptr); });
+}
+extern "C" int y355_upsample2x_f32(int device_id, const float *in, int batch, int channels, int height, int width, float *out) {
+    if (!in || !out) return y355_fail(Y355_EINVAL, "null argument");
+    size_t n = 0;
+    if (int rc = map_shape(batch, channels, height, width, 1, &n)) return rc;
+    return host_form(device_id, in, n, out, n * 4,
+                     [&](const float *dx, float *dy) { return y355_upsample2x_f32_dev(dx, batch, channels, height, width, dy, nullptr); });
+}
+
+// ==========================================================================================================================
+// y355_conv_op: a convolution whose weights are packed onto the device by the operator and whose workspaces grow on demand;
+// single-threaded like an engine handle.  The forwards take DEVICE pointers (fp32 NCHW) and a stream, launch behind whatever
+// that stream holds and return without waiting.  The int8 form needs two things on the HOST -- the input's exponent and the
+// verdict "is x a dyadic int8 tensor" select the route and the requantisation constants: two 4-byte read-backs per call.
+// General geometry (include/yolo355.h y355_conv_geom): any kernel size, stride, dilation and four zero pads on the
+// implicit-GEMM kernel of convgeom.hip, in the same layouts -- input NHWC with a one-pixel halo, bf16 output NHWC with a halo,
+// int8 t' [pixel][cout_pad] -- and with make_requant's integer epilogue at the layer's tap count.
 struct y355_conv_op {
     int device = 0, kind = 0;          // kind 0 bf16, 1 int8
     int cin = 0, cout = 0, ksize = 3, stride = 1;
-    float slope = 1.f;
-    // bf16
-    int cin_pad = 0;
-    char *w_dev = nullptr;             // y355_convg_pack layouts, one per kernel id the shapes select (packed on demand from w_host)
+    int geom = 0;                      // 1: general geometry g on convgeom.hip; 0: ksize / stride on convg.hip (bf16), 3x3 on conv3x3.hip (int8)
+    y355_conv_geom g{};
+    int cpad = 0;                      // channels of a staged input pixel (bf16 or int8 elements)
+    // packed weights, for the kernel id and padded width the last shapes selected (op_weights); -1: nothing packed
+    char *w_dev = nullptr;
     int w_kid = -1, w_cout_pad = 0;
+    // bf16
+    float slope = 1.f;
     std::vector<float> w_host, b_host;
     float *bias_dev = nullptr;
     // int8
     std::vector<int8_t> qw;
     std::vector<int32_t> qb;
-    int e_w = 0, e_b = 0, act = 0, cpad = 0, cout_pad8 = 0;
-    int8_t *qw_dev = nullptr;
-    int *bt_dev = nullptr;
+    int e_w = 0, e_b = 0, act = 0;
+    int *bt_dev = nullptr;             // 3x3 only: the 32-bit biases
     long long *bw_dev = nullptr;
-    int sa_cached = 1 << 30;
+    int sa_cached = NO_SA;             // the input exponent rq / frac_bits / the device biases were made for
     Requant rq{};
     int frac_bits = 0;
-    Counters *ctr_dev = nullptr;
+    Counters *ctr_dev = nullptr;       // 3x3 only
     unsigned int *flag_dev = nullptr;  // [0] absmax bits, [1] non-dyadic count
     // workspaces (grown on demand)
     char *in_dev = nullptr, *out_dev = nullptr, *res_dev = nullptr;
     size_t in_cap = 0, out_cap = 0, res_cap = 0;
     size_t geo = 0;                    // (batch, H, W, output type) the halo buffers were last zeroed for
-    // general geometry (y355_conv_op_create_*_geom): the convgeom.hip kernel; w_kid / w_cout_pad = its tile shape and padding
-    int geom = 0;
-    y355_conv_geom g{};
+    static constexpr int NO_SA = 1 << 30;
 };
 
-static int op_grow(char **p, size_t *cap, size_t need, bool zero) {
-    if (*cap >= need) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    DEVCHK(hipMalloc((void **)p, need));
-    if (zero) DEVCHK(hipMemset(*p, 0, need));
-    *cap = need;
-    return 0;
-}
-
-static int geom_forward_bf16(y355_conv_op *op, const float *x_dev, const float *residual_dev, int batch, int height, int width, int out_fp32,
-                             float *out_dev, hipStream_t s);
-static int geom_forward_i8(y355_conv_op *op, const float *x_dev, int batch, int height, int width, float *out_dev, hipStream_t s,
-                           int32_t *sa_in, int32_t *exact);
-
-extern "C" void y355_conv_op_destroy(y355_conv_op *op) {
-    if (!op) return;
-    (void)hipSetDevice(op->device);
-    (void)hipDeviceSynchronize();
-    for (void *q : {(void *)op->w_dev, (void *)op->bias_dev, (void *)op->qw_dev, (void *)op->bt_dev, (void *)op->bw_dev, (void *)op->ctr_dev,
-                    (void *)op->flag_dev, (void *)op->in_dev, (void *)op->out_dev, (void *)op->res_dev})
-        if (q) (void)hipFree(q);
-    delete op;
-}
-
-extern "C" int y355_conv_op_create_bf16(int device_id, const float *w, const float *bias, int cin, int cout, int ksize, int stride,
-                                        float neg_slope, y355_conv_op **out) {
-    if (!w || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    if (ksize != 1 && ksize != 3) return y355_fail(Y355_EINVAL, "kernel size 1 or 3 (padding k/2)");
-    if (stride != 1 && !(stride == 2 && ksize == 3)) return y355_fail(Y355_EINVAL, "stride 1, or 2 with a 3x3 kernel");
-    DEVCHK(hipSetDevice(device_id));
-    if (int e = y355_prepare_convg()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
-    y355_conv_op *op = new y355_conv_op();
-    op->device = device_id;
-    op->kind = 0;
-    op->cin = cin; op->cout = cout; op->ksize = ksize; op->stride = stride; op->slope = neg_slope;
-    const bool thin = (cin <= 16 && ksize == 3 && stride == 1);
-    op->cin_pad = thin ? 16 : (cin + 31) / 32 * 32;
-    op->w_host.assign(w, w + (size_t)cout * cin * ksize * ksize);
-    op->b_host.assign(cout, 0.f);
-    if (bias) std::copy(bias, bias + cout, op->b_host.begin());
-    *out = op;
-    return 0;
-}
-
-extern "C" int y355_conv_op_forward(y355_conv_op *op, const float *x_dev, const float *residual_dev, int batch, int height, int width,
-                                    int out_fp32, float *out_dev, void *stream_) {
-    if (!op || op->kind != 0 || !x_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument / not a bf16 operator");
-    if (batch < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    if (out_fp32 && residual_dev) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
-    hipStream_t s = (hipStream_t)stream_;
-    if (op->geom) return geom_forward_bf16(op, x_dev, residual_dev, batch, height, width, out_fp32, out_dev, s);
-    DEVCHK(hipSetDevice(op->device));
-    const int in_pb = op->cin_pad * 2, taps = op->ksize * op->ksize, stride = op->stride;
-    const int kid = y355_convg_select(in_pb, op->cout, 0, height, width, stride);
-    const ConvGInfo *ki = y355_convg_kernel(1, kid);
-    if (!ki) return y355_fail(Y355_EINVAL, "no kernel for this shape");
-    const int Ho = stride == 2 ? (height + 1) / 2 : height, Wo = stride == 2 ? (width + 1) / 2 : width;
-    const int cout_pad = (op->cout + ki->bn - 1) / ki->bn * ki->bn;
-    if (op->w_kid != kid || op->w_cout_pad != cout_pad) {          // first call, or a map size that selects another tile shape: (re)pack
-        const size_t wbytes = y355_convg_packed_bytes(*ki, in_pb, taps, cout_pad);
-        std::vector<char> wpk(wbytes);
-        y355_convg_pack(*ki, op->w_host.data(), nullptr, op->cout, op->cin, op->ksize, in_pb, cout_pad, wpk.data());
-        std::vector<float> bpad(cout_pad, 0.f);
-        std::copy(op->b_host.begin(), op->b_host.end(), bpad.begin());
-        DEVCHK(hipStreamSynchronize(s));                           // a previous forward may still read the old fragments
-        if (op->w_dev) (void)hipFree(op->w_dev);
-        if (op->bias_dev) (void)hipFree(op->bias_dev);
-        op->w_dev = nullptr; op->bias_dev = nullptr;
-        DEVCHK(hipMalloc((void **)&op->w_dev, wbytes));
-        DEVCHK(hipMalloc((void **)&op->bias_dev, sizeof(float) * cout_pad));
-        DEVCHK(hipMemcpy(op->w_dev, wpk.data(), wbytes, hipMemcpyHostToDevice));
-        DEVCHK(hipMemcpy(op->bias_dev, bpad.data(), sizeof(float) * cout_pad, hipMemcpyHostToDevice));
-        op->w_kid = kid;
-        op->w_cout_pad = cout_pad;
-        op->geo = 0;                                               // halo layouts depend on the padded channel counts: re-zero below
-    }
-    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * Ho * Wo;
-    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
-    const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
-    // a buffer is zeroed when it is (re)allocated: the staging kernels only write the interior, so the halo and the padding
-    // channels stay zero for every later call of the same or a smaller size... as long as the geometry is the same: a new
-    // geometry re-zeroes (cheap next to a reallocation)
-    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)out_fp32 << 62) ^ ((size_t)1 << 61);
-    const bool regeo = geo != op->geo;
-    op->geo = geo;
-    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
-    if (int rc = op_grow(&op->out_dev, &op->out_cap, out_bytes, true)) return rc;
-    if (regeo) {
-        DEVCHK(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
-        DEVCHK(hipMemsetAsync(op->out_dev, 0, out_bytes, s));
-    }
-    if (residual_dev) {
-        if (int rc = op_grow(&op->res_dev, &op->res_cap, out_bytes, true)) return rc;
-        if (regeo) DEVCHK(hipMemsetAsync(op->res_dev, 0, out_bytes, s));
-        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, residual_dev, (unsigned short *)op->res_dev, batch,
-                           op->cout, Ho, Wo, cout_pad);
-    }
-    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (unsigned short *)op->in_dev, batch, op->cin, height,
-                       width, op->cin_pad);
-    ConvGParams p{};
-    p.in = op->in_dev;
-    p.out = op->out_dev;
-    p.w = op->w_dev;
-    p.bias_f = op->bias_dev;
-    p.B = batch;
-    p.H = height;
-    p.W = width;
-    p.in_pb = in_pb;
-    p.nchunks = in_pb / ki->chb;
-    p.out_pb = (int)out_pb;
-    p.out_off = 0;
-    p.out_halo = 1;
-    p.tiles_x = (Wo + ki->tw - 1) / ki->tw;
-    p.tiles_y = (Ho + ki->th - 1) / ki->th;
-    p.nblk = cout_pad / ki->bn;
-    p.taps = taps;
-    p.slope = op->slope;
-    p.out_f32 = out_fp32 ? 1 : 0;
-    p.res = residual_dev ? op->res_dev : nullptr;
-    p.res_pb = (int)out_pb;
-    p.res_off = 0;
-    ki->launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, s);
-    DEVCHK(hipGetLastError());
-    if (out_fp32)
-        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const float *)op->out_dev, out_dev, batch, op->cout, Ho,
-                           Wo, cout_pad);
-    else
-        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const unsigned short *)op->out_dev, out_dev, batch,
-                           op->cout, Ho, Wo, cout_pad);
-    DEVCHK(hipGetLastError());
-    return 0;
-}
-
-extern "C" int y355_conv_op_create_i8(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, int e_w, int e_b, int flags,
-                                      y355_conv_op **out) {
-    if (!q_w || !q_b || !out) return y355_fail(Y355_EINVAL, "null argument");
-    if (cin < 1 || cin > 256 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape (cin <= 256)");
-    if ((flags & Y355_OP_LEAKY) && (flags & Y355_OP_RELU)) return y355_fail(Y355_EINVAL, "LeakyReLU and ReLU are exclusive");
-    DEVCHK(hipSetDevice(device_id));
-    if (int e = y355_prepare_kernels()) return e;
-    y355_conv_op *op = new y355_conv_op();
-    op->device = device_id;
-    op->kind = 1;
-    op->cin = cin; op->cout = cout;
-    op->e_w = e_w; op->e_b = e_b;
-    op->act = (flags & Y355_OP_LEAKY) ? 1 : ((flags & Y355_OP_RELU) ? 2 : 0);
-    op->cpad = cin <= 16 ? 16 : cin <= 32 ? 32 : cin <= 64 ? 64 : cin <= 128 ? 128 : 256;
-    const int sel = op->cpad == 16 ? 0 : op->cpad == 32 ? 1 : op->cpad == 64 ? 2 : op->cpad == 128 ? 3 : 4;
-    const ConvKernelInfo &ki = *y355_conv_kernel(Y355_K_GEN16 + sel);
-    op->cout_pad8 = (cout + ki.bn - 1) / ki.bn * ki.bn;
-    op->qw.assign(q_w, q_w + (size_t)cout * cin * 9);
-    op->qb.assign(q_b, q_b + cout);
-    std::vector<int8_t> packed(y355_packed_bytes(ki, op->cout_pad8));
-    y355_pack_weights(ki, q_w, cout, cin, op->cout_pad8, packed.data());
-    auto bail = [&](int rc) { std::string keep = y355_last_error(); y355_conv_op_destroy(op); return y355_fail(rc, keep); };
-    if (hipMalloc((void **)&op->qw_dev, packed.size()) != hipSuccess || hipMalloc((void **)&op->bt_dev, sizeof(int) * op->cout_pad8) != hipSuccess ||
-        hipMalloc((void **)&op->bw_dev, sizeof(long long) * op->cout_pad8) != hipSuccess || hipMalloc((void **)&op->ctr_dev, sizeof(Counters)) != hipSuccess ||
-        hipMalloc((void **)&op->flag_dev, 16) != hipSuccess ||
-        hipMemcpy(op->qw_dev, packed.data(), packed.size(), hipMemcpyHostToDevice) != hipSuccess) {
-        y355_fail(Y355_EHIP, "device allocation failed");
-        return bail(Y355_EHIP);
-    }
-    *out = op;
-    return 0;
-}
-
-// Conv2d_fuse(x) for a dyadic x (utils/modules.py:20-29 on the fake-quantised operands of the quantized path): exact.
-// *exact = 0: x is not a dyadic int8 tensor (out_dev untouched) -- the caller takes the bf16 route.
-extern "C" int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int batch, int height, int width, float *out_dev, void *stream_,
-                                       int32_t *sa_in, int32_t *exact) {
-    if (!op || op->kind != 1 || !x_dev || !out_dev || !exact) return y355_fail(Y355_EINVAL, "null argument / not an int8 operator");
-    if (batch < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    hipStream_t s = (hipStream_t)stream_;
-    if (op->geom) return geom_forward_i8(op, x_dev, batch, height, width, out_dev, s, sa_in, exact);
-    DEVCHK(hipSetDevice(op->device));
-    *exact = 0;
-    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * height * width;
-    // (1) the exponent of x: floor(log2(127 / max|x|)) -- the tensor is q / 2^e with |q| <= 127 (prep.as_dyadic_int8)
-    DEVCHK(hipMemsetAsync(op->flag_dev, 0, 16, s));
-    y355_launch_absmax(x_dev, n_in, op->flag_dev, s);
-    DEVCHK(hipGetLastError());
-    unsigned int bits = 0;
-    DEVCHK(hipMemcpyAsync(&bits, op->flag_dev, 4, hipMemcpyDeviceToHost, s));
-    DEVCHK(hipStreamSynchronize(s));
-    float mx;
-    memcpy(&mx, &bits, 4);
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;                              // all zero / not finite: not this route
-    const int sa = (int)std::floor(std::log2((1.0f / mx) * 127.0f));
-    if (sa < -64 || sa > 64) return 0;
-    if (sa_in) *sa_in = sa;
-    // (2) the integer epilogue for this exponent (cached)
-    if (sa != op->sa_cached) {
-        std::vector<int32_t> bt;
-        std::vector<long long> bw;
-        if (int rc = y355_op_requant(op->cin, 9, sa, op->e_w, op->e_b, op->act, op->qb.data(), op->cout, op->cout_pad8, &op->rq, &op->frac_bits, &bt, &bw))
-            return rc;
-        DEVCHK(hipMemcpy(op->bt_dev, bt.data(), sizeof(int) * op->cout_pad8, hipMemcpyHostToDevice));
-        DEVCHK(hipMemcpy(op->bw_dev, bw.data(), sizeof(long long) * op->cout_pad8, hipMemcpyHostToDevice));
-        op->sa_cached = sa;
-    }
-    // (3) stage: int8 NHWC with halo + the dyadic verdict
-    const size_t in_bytes = ((size_t)batch * (height + 2) * (width + 2) + 64) * op->cpad;
-    const size_t raw_bytes = sizeof(long long) * (size_t)batch * height * width * op->cout_pad8;
-    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)1 << 61);
-    const bool regeo = geo != op->geo;
-    op->geo = geo;
-    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
-    if (int rc = op_grow(&op->out_dev, &op->out_cap, raw_bytes, false)) return rc;
-    if (regeo) DEVCHK(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
-    hipLaunchKernelGGL(dyadic_to_nhwc_i8_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (int8_t *)op->in_dev, batch, op->cin, height, width,
-                       op->cpad, std::ldexp(1.0f, sa), op->flag_dev + 1);
-    DEVCHK(hipGetLastError());
-    unsigned int bad = 0;
-    DEVCHK(hipMemcpyAsync(&bad, op->flag_dev + 1, 4, hipMemcpyDeviceToHost, s));
-    DEVCHK(hipStreamSynchronize(s));
-    if (bad) return 0;
-    // (4) conv + bias + activation without requantisation (statistics mode dumps t'), (5) t' / 2^F' -> fp32 NCHW
-    const int sel = op->cpad == 16 ? 0 : op->cpad == 32 ? 1 : op->cpad == 64 ? 2 : op->cpad == 128 ? 3 : 4;
-    const ConvKernelInfo &ki = *y355_conv_kernel(Y355_K_GEN16 + sel);
-    DEVCHK(hipMemsetAsync(op->ctr_dev, 0, sizeof(Counters), s));
-    ConvParams p{};
-    p.in = (const int8_t *)op->in_dev; p.out = nullptr; p.w = op->qw_dev; p.bias_t = op->bt_dev; p.bias_w = op->bw_dev; p.ctr = op->ctr_dev;
-    p.raw = (long long *)op->out_dev;
-    p.B = batch; p.H = height; p.W = width; p.cstride = op->cout_pad8; p.out_halo = 0;
-    p.tiles_x = (width + ki.tw - 1) / ki.tw; p.tiles_y = (height + ki.th - 1) / ki.th; p.nblk = op->cout_pad8 / ki.bn;
-    p.rq = op->rq; p.mode = 1; p.guard = 0;
-    ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, s);
-    DEVCHK(hipGetLastError());
-    hipLaunchKernelGGL(raw_to_nchw_f32_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const long long *)op->out_dev, out_dev, batch, op->cout, height,
-                       width, op->cout_pad8, std::ldexp(1.0f, -op->frac_bits));
-    DEVCHK(hipGetLastError());
-    *exact = 1;
-    return 0;
-}
-
-
-// ==========================================================================================================================
-// General convolution geometry (include/yolo355.h y355_conv_geom): any kernel size, stride, dilation and four zero pads, on the
-// implicit-GEMM kernel of convgeom.hip.  The layouts are those of the entry points above -- input NHWC with a one-pixel halo
-// (nchw_to_nhwc_bf16_kernel / dyadic_to_nhwc_i8_kernel), bf16 output NHWC with a halo back through nhwc_*_to_nchw_kernel, int8
-// t' [pixel][cout_pad] through raw_to_nchw_f32_kernel -- and the integer epilogue is make_requant's with the layer's tap count.
 namespace {
+struct OpOwner {                       // the temporary operator of a host-pointer form
+    y355_conv_op *op = nullptr;
+    ~OpOwner() { y355_conv_op_destroy(op); }
+};
+
 constexpr long long GEOM_I8_MAX_K = 133144;      // 127 * 127 * cin * kh * kw <= INT32_MAX
 
 int geom_limits(const y355_conv_geom *g) {
@@ -781,16 +452,337 @@ ConvGeomParams geom_params(const y355_conv_geom &g, int batch, int height, int w
 }
 
 int geom_act(int flags) { return (flags & Y355_OP_LEAKY) ? 1 : ((flags & Y355_OP_RELU) ? 2 : 0); }
-int geom_flags(int flags) {
+int act_flags(int flags) {
     if ((flags & Y355_OP_LEAKY) && (flags & Y355_OP_RELU)) return y355_fail(Y355_EINVAL, "LeakyReLU and ReLU are exclusive");
+    return 0;
+}
+int geom_flags(int flags) {
+    if (int rc = act_flags(flags)) return rc;
     if (flags & Y355_OP_POOL) return y355_fail(Y355_EINVAL, "no fused max-pool on the general geometry");
     return 0;
 }
+
+// the generic 3x3 int8 kernel of conv3x3.hip for cin input channels (pool: the one with the fused max-pool): its id, and the
+// channels its input pixels are padded to
+int gen16_kernel(int cin, int pool, int *cpad) {
+    *cpad = cin <= 16 ? 16 : cin <= 32 ? 32 : cin <= 64 ? 64 : cin <= 128 ? 128 : 256;
+    const int sel = *cpad == 16 ? 0 : *cpad == 32 ? 1 : *cpad == 64 ? 2 : *cpad == 128 ? 3 : 4;
+    return (pool ? Y355_K_GEN16P : Y355_K_GEN16) + sel;
+}
+int gen16_shape(int batch, int cin, int cout, int H, int W, int flags) {
+    if (batch < 1 || cin < 1 || cin > 256 || cout < 1 || H < 1 || W < 1) return y355_fail(Y355_EINVAL, "bad shape (cin <= 256)");
+    return act_flags(flags);
+}
+// the launch parameters of such a kernel, but for where the result goes (out / raw) and the pass (mode, guard)
+ConvParams gen16_params(const ConvKernelInfo &ki, const int8_t *in, const int8_t *w, const int *bias_t, const long long *bias_w, Counters *ctr,
+                        int batch, int H, int W, int cout_pad, const Requant &rq) {
+    ConvParams p{};
+    p.in = in; p.w = w; p.bias_t = bias_t; p.bias_w = bias_w; p.ctr = ctr;
+    p.B = batch; p.H = H; p.W = W; p.cstride = cout_pad; p.out_halo = 0;
+    p.tiles_x = (W + ki.tw - 1) / ki.tw; p.tiles_y = (H + ki.th - 1) / ki.th; p.nblk = cout_pad / ki.bn;
+    p.rq = rq;
+    return p;
+}
+
+int op_grow(char **p, size_t *cap, size_t need, bool zero) {
+    if (*cap >= need) return 0;
+    if (*p) (void)hipFree(*p);
+    *p = nullptr;
+    *cap = 0;
+    HIPTRY(hipMalloc((void **)p, need));
+    if (zero) HIPTRY(hipMemset(*p, 0, need));
+    *cap = need;
+    return 0;
+}
+
+// what one forward at batch x height x width runs: the kernel, the output map, the padded output channels
+struct ConvPlan {
+    int kid = 0, Ho = 0, Wo = 0, cout_pad = 0;
+    const ConvGInfo *kg = nullptr;     // bf16 3x3 / 1x1
+};
+// the output size only: the argument checks that come before any HIP call
+int conv_out_size(const y355_conv_op *op, int batch, int height, int width, ConvPlan *pl) {
+    if (op->geom) return geom_out(&op->g, batch, height, width, &pl->Ho, &pl->Wo);
+    if (batch < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    pl->Ho = op->stride == 2 ? (height + 1) / 2 : height;
+    pl->Wo = op->stride == 2 ? (width + 1) / 2 : width;
+    return 0;
+}
+// the kernel for that size (the device is set: the general geometry sizes its tiles by the compute units)
+int conv_plan(const y355_conv_op *op, int batch, int height, int width, ConvPlan *pl) {
+    int bn = 0;
+    if (op->geom) {
+        pl->kid = y355_convgeom_select(batch * pl->Ho * pl->Wo, op->cout, y355_cu_count());
+        bn = y355_convgeom_info(pl->kid)->bn;
+    } else if (op->kind == 0) {
+        pl->kid = y355_convg_select(op->cpad * 2, op->cout, 0, height, width, op->stride);
+        pl->kg = y355_convg_kernel(1, pl->kid);
+        if (!pl->kg) return y355_fail(Y355_EINVAL, "no kernel for this shape");
+        bn = pl->kg->bn;
+    } else {
+        int cpad = 0;
+        pl->kid = gen16_kernel(op->cin, 0, &cpad);
+        bn = y355_conv_kernel(pl->kid)->bn;
+    }
+    pl->cout_pad = round_up(op->cout, bn);
+    return 0;
+}
+
+// The packed weights for kernel pl.kid at pl.cout_pad output channels, with the bias vector that is padded alike: packed from
+// the host copy on first use, and again when a map size selects another tile shape.
+int op_weights(y355_conv_op *op, const ConvPlan &pl, hipStream_t s) {
+    if (op->w_kid == pl.kid && op->w_cout_pad == pl.cout_pad) return 0;
+    const int taps = op->geom ? op->g.kh * op->g.kw : op->ksize * op->ksize, in_pb = op->kind ? op->cpad : op->cpad * 2;
+    const float *wf = op->kind ? nullptr : op->w_host.data();
+    const int8_t *wq = op->kind ? op->qw.data() : nullptr;
+    std::vector<char> wpk;
+    if (op->geom) {
+        wpk.resize(y355_convgeom_packed_bytes(pl.kid, in_pb, taps, pl.cout_pad));
+        y355_convgeom_pack(pl.kid, op->kind ? 0 : 1, wf, wq, op->cout, op->cin, taps, in_pb, pl.cout_pad, wpk.data());
+    } else if (op->kind == 0) {
+        wpk.resize(y355_convg_packed_bytes(*pl.kg, in_pb, taps, pl.cout_pad));
+        y355_convg_pack(*pl.kg, wf, nullptr, op->cout, op->cin, op->ksize, in_pb, pl.cout_pad, wpk.data());
+    } else {
+        const ConvKernelInfo &ki = *y355_conv_kernel(pl.kid);
+        wpk.resize(y355_packed_bytes(ki, pl.cout_pad));
+        y355_pack_weights(ki, wq, op->cout, op->cin, pl.cout_pad, (int8_t *)wpk.data());
+    }
+    HIPTRY(hipStreamSynchronize(s));                               // a previous forward may still read the old fragments
+    // nothing is packed from here until everything below has succeeded: a failure must not leave the key of a tile whose
+    // fragments are gone, or a later forward at that tile's size would launch on a null pointer
+    op->w_kid = -1;
+    op->sa_cached = y355_conv_op::NO_SA;                           // the int8 biases are padded to the new width by i8_prepare
+    (void)hipFree(op->w_dev);
+    (void)hipFree(op->bias_dev);
+    (void)hipFree(op->bw_dev);
+    op->w_dev = nullptr; op->bias_dev = nullptr; op->bw_dev = nullptr;
+    HIPTRY(hipMalloc((void **)&op->w_dev, wpk.size()));
+    HIPTRY(hipMemcpy(op->w_dev, wpk.data(), wpk.size(), hipMemcpyHostToDevice));
+    if (op->kind == 0) {
+        std::vector<float> bpad(pl.cout_pad, 0.f);
+        std::copy(op->b_host.begin(), op->b_host.end(), bpad.begin());
+        HIPTRY(hipMalloc((void **)&op->bias_dev, sizeof(float) * pl.cout_pad));
+        HIPTRY(hipMemcpy(op->bias_dev, bpad.data(), sizeof(float) * pl.cout_pad, hipMemcpyHostToDevice));
+        op->geo = 0;                                               // halo layouts depend on the padded channel counts: re-zero
+    } else {
+        HIPTRY(hipMalloc((void **)&op->bw_dev, sizeof(long long) * pl.cout_pad));
+    }
+    op->w_kid = pl.kid;
+    op->w_cout_pad = pl.cout_pad;
+    return 0;
+}
+
+int attr_fail(int e) { return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e)); }
+
+y355_conv_op *op_new(int device_id, int kind, int cin, int cout, const y355_conv_geom *g) {
+    y355_conv_op *op = new y355_conv_op();
+    op->device = device_id; op->kind = kind; op->cin = cin; op->cout = cout;
+    if (g) {
+        op->geom = 1;
+        op->g = *g;
+    }
+    return op;
+}
 }  // namespace
+
+extern "C" void y355_conv_op_destroy(y355_conv_op *op) {
+    if (!op) return;
+    (void)hipSetDevice(op->device);
+    (void)hipDeviceSynchronize();
+    for (void *q : {(void *)op->w_dev, (void *)op->bias_dev, (void *)op->bt_dev, (void *)op->bw_dev, (void *)op->ctr_dev, (void *)op->flag_dev,
+                    (void *)op->in_dev, (void *)op->out_dev, (void *)op->res_dev})
+        if (q) (void)hipFree(q);
+    delete op;
+}
 
 extern "C" int y355_conv_geom_out_size(const y355_conv_geom *g, int height, int width, int *ho, int *wo) {
     if (!ho || !wo) return y355_fail(Y355_EINVAL, "null argument");
     return geom_out(g, 1, height, width, ho, wo);
+}
+
+// ---- create ----------------------------------------------------------------------------------------------------------------
+static int create_bf16(int device_id, const float *w, const float *bias, int cin, int cout, int ksize, int stride, const y355_conv_geom *g,
+                       float neg_slope, y355_conv_op **out) {
+    HIPTRY(hipSetDevice(device_id));
+    if (int e = g ? y355_prepare_convgeom() : y355_prepare_convg()) return attr_fail(e);
+    y355_conv_op *op = op_new(device_id, 0, cin, cout, g);
+    op->ksize = ksize; op->stride = stride; op->slope = neg_slope;
+    const bool thin = !g && cin <= 16 && ksize == 3 && stride == 1;
+    op->cpad = thin ? 16 : round_up(cin, 32);
+    op->w_host.assign(w, w + (size_t)cout * cin * (g ? g->kh * g->kw : ksize * ksize));
+    op->b_host.assign(cout, 0.f);
+    if (bias) std::copy(bias, bias + cout, op->b_host.begin());
+    *out = op;
+    return 0;
+}
+
+extern "C" int y355_conv_op_create_bf16(int device_id, const float *w, const float *bias, int cin, int cout, int ksize, int stride,
+                                        float neg_slope, y355_conv_op **out) {
+    if (!w || !out) return y355_fail(Y355_EINVAL, "null argument");
+    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    if (ksize != 1 && ksize != 3) return y355_fail(Y355_EINVAL, "kernel size 1 or 3 (padding k/2)");
+    if (stride != 1 && !(stride == 2 && ksize == 3)) return y355_fail(Y355_EINVAL, "stride 1, or 2 with a 3x3 kernel");
+    return create_bf16(device_id, w, bias, cin, cout, ksize, stride, nullptr, neg_slope, out);
+}
+
+extern "C" int y355_conv_op_create_bf16_geom(int device_id, const float *w, const float *bias, int cin, int cout, const y355_conv_geom *g,
+                                             float neg_slope, y355_conv_op **out) {
+    if (!w || !out || !g) return y355_fail(Y355_EINVAL, "null argument");
+    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    if (int rc = geom_limits(g)) return rc;
+    return create_bf16(device_id, w, bias, cin, cout, 3, 1, g, neg_slope, out);
+}
+
+// 3x3: the kernel depends on cin alone, so the weights are packed here and every forward finds them
+static int create_i8(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, const y355_conv_geom *g, int e_w, int e_b, int flags,
+                     y355_conv_op **out) {
+    HIPTRY(hipSetDevice(device_id));
+    if (g) {
+        if (int e = y355_prepare_convgeom()) return attr_fail(e);
+    } else if (int e = y355_prepare_kernels()) {
+        return e;
+    }
+    OpOwner own{op_new(device_id, 1, cin, cout, g)};
+    y355_conv_op *op = own.op;
+    op->e_w = e_w; op->e_b = e_b;
+    op->act = geom_act(flags);
+    op->qw.assign(q_w, q_w + (size_t)cout * cin * (g ? g->kh * g->kw : 9));
+    op->qb.assign(q_b, q_b + cout);
+    HIPTRY(hipMalloc((void **)&op->flag_dev, 16));
+    if (g) {
+        op->cpad = round_up(cin, 64);
+    } else {
+        ConvPlan pl;
+        (void)gen16_kernel(cin, 0, &op->cpad);
+        if (int rc = conv_plan(op, 1, 1, 1, &pl)) return rc;
+        if (int rc = op_weights(op, pl, nullptr)) return rc;
+        HIPTRY(hipMalloc((void **)&op->bt_dev, sizeof(int) * pl.cout_pad));
+        HIPTRY(hipMalloc((void **)&op->ctr_dev, sizeof(Counters)));
+    }
+    *out = op;
+    own.op = nullptr;
+    return 0;
+}
+
+extern "C" int y355_conv_op_create_i8(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, int e_w, int e_b, int flags,
+                                      y355_conv_op **out) {
+    if (!q_w || !q_b || !out) return y355_fail(Y355_EINVAL, "null argument");
+    if (int rc = gen16_shape(1, cin, cout, 1, 1, flags)) return rc;
+    return create_i8(device_id, q_w, q_b, cin, cout, nullptr, e_w, e_b, flags, out);
+}
+
+extern "C" int y355_conv_op_create_i8_geom(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, const y355_conv_geom *g,
+                                           int e_w, int e_b, int flags, y355_conv_op **out) {
+    if (!q_w || !q_b || !out || !g) return y355_fail(Y355_EINVAL, "null argument");
+    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    if (int rc = geom_limits(g)) return rc;
+    if (int rc = geom_flags(flags)) return rc;
+    if (int rc = geom_i8_k(cin, g)) return rc;
+    return create_i8(device_id, q_w, q_b, cin, cout, g, e_w, e_b, flags, out);
+}
+
+// ---- bf16 forward ----------------------------------------------------------------------------------------------------------
+static int conv_forward_bf16(y355_conv_op *op, const float *x_dev, const float *residual_dev, int batch, int height, int width, int out_fp32,
+                             float *out_dev, hipStream_t s) {
+    if (out_fp32 && residual_dev) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
+    ConvPlan pl;
+    if (int rc = conv_out_size(op, batch, height, width, &pl)) return rc;
+    HIPTRY(hipSetDevice(op->device));
+    if (int rc = conv_plan(op, batch, height, width, &pl)) return rc;
+    if (int rc = op_weights(op, pl, s)) return rc;
+    const int Ho = pl.Ho, Wo = pl.Wo, cout_pad = pl.cout_pad, in_pb = op->cpad * 2;
+    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * Ho * Wo;
+    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
+    const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
+    // a buffer is zeroed when it is (re)allocated: the staging kernels only write the interior and the real channels, so the
+    // halo and the padding channels stay zero for every later call of the same or a smaller size... as long as the geometry is
+    // the same: a new geometry re-zeroes (cheap next to a reallocation)
+    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)out_fp32 << 62) ^ ((size_t)1 << 61);
+    const bool regeo = geo != op->geo;
+    op->geo = geo;
+    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
+    if (int rc = op_grow(&op->out_dev, &op->out_cap, out_bytes, true)) return rc;
+    if (regeo) {
+        HIPTRY(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
+        if (!op->geom) HIPTRY(hipMemsetAsync(op->out_dev, 0, out_bytes, s));   // convgeom.hip writes every channel of a pixel it owns
+    }
+    if (residual_dev) {
+        if (int rc = op_grow(&op->res_dev, &op->res_cap, out_bytes, true)) return rc;
+        if (regeo) HIPTRY(hipMemsetAsync(op->res_dev, 0, out_bytes, s));
+        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, residual_dev, (unsigned short *)op->res_dev, batch,
+                           op->cout, Ho, Wo, cout_pad);
+    }
+    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (unsigned short *)op->in_dev, batch, op->cin, height,
+                       width, op->cpad);
+    const char *res = residual_dev ? op->res_dev : nullptr;
+    if (op->geom) {
+        ConvGeomParams p = geom_params(op->g, batch, height, width, Ho, Wo, in_pb, cout_pad, y355_convgeom_info(pl.kid)->bn);
+        p.in = op->in_dev; p.w = op->w_dev; p.bias_f = op->bias_dev; p.res = res; p.out = op->out_dev;
+        p.out_pb = (int)out_pb; p.out_f32 = out_fp32 ? 1 : 0; p.slope = op->slope;
+        y355_launch_convgeom(pl.kid, 1, p, s);
+    } else {
+        const ConvGInfo &ki = *pl.kg;
+        ConvGParams p{};
+        p.in = op->in_dev; p.out = op->out_dev; p.w = op->w_dev; p.bias_f = op->bias_dev;
+        p.B = batch; p.H = height; p.W = width;
+        p.in_pb = in_pb; p.nchunks = in_pb / ki.chb;
+        p.out_pb = (int)out_pb; p.out_off = 0; p.out_halo = 1;
+        p.tiles_x = (Wo + ki.tw - 1) / ki.tw; p.tiles_y = (Ho + ki.th - 1) / ki.th; p.nblk = cout_pad / ki.bn;
+        p.taps = op->ksize * op->ksize;
+        p.slope = op->slope;
+        p.out_f32 = out_fp32 ? 1 : 0;
+        p.res = res; p.res_pb = (int)out_pb; p.res_off = 0;
+        ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, s);
+    }
+    HIPTRY(hipGetLastError());
+    if (out_fp32)
+        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const float *)op->out_dev, out_dev, batch, op->cout, Ho,
+                           Wo, cout_pad);
+    else
+        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const unsigned short *)op->out_dev, out_dev, batch,
+                           op->cout, Ho, Wo, cout_pad);
+    HIPTRY(hipGetLastError());
+    return 0;
+}
+
+extern "C" int y355_conv_op_forward(y355_conv_op *op, const float *x_dev, const float *residual_dev, int batch, int height, int width,
+                                    int out_fp32, float *out_dev, void *stream) {
+    if (!op || op->kind != 0 || !x_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument / not a bf16 operator");
+    if (batch < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    return conv_forward_bf16(op, x_dev, residual_dev, batch, height, width, out_fp32, out_dev, (hipStream_t)stream);
+}
+
+// host-pointer form on a temporary operator (owned): upload x and the residual, the shared forward on the null stream,
+// synchronise, download
+static int bf16_host_form(y355_conv_op *op_, const float *x, const float *residual, int batch, int height, int width, int out_fp32, float *out) {
+    OpOwner own{op_};
+    ConvPlan pl;
+    if (int rc = conv_out_size(own.op, batch, height, width, &pl)) return rc;
+    const size_t n_in = (size_t)batch * own.op->cin * height * width, n_out = (size_t)batch * own.op->cout * pl.Ho * pl.Wo;
+    Scratch tmp;
+    float *d_x = nullptr, *d_r = nullptr, *d_y = nullptr;
+    HIPTRY(tmp.get(&d_x, n_in * 4));
+    HIPTRY(tmp.get(&d_y, n_out * 4));
+    HIPTRY(hipMemcpy(d_x, x, n_in * 4, hipMemcpyHostToDevice));
+    if (residual) {
+        HIPTRY(tmp.get(&d_r, n_out * 4));
+        HIPTRY(hipMemcpy(d_r, residual, n_out * 4, hipMemcpyHostToDevice));
+    }
+    if (int rc = conv_forward_bf16(own.op, d_x, d_r, batch, height, width, out_fp32, d_y, nullptr)) return rc;
+    HIPTRY(hipDeviceSynchronize());
+    HIPTRY(hipMemcpy(out, d_y, n_out * 4, hipMemcpyDeviceToHost));
+    return 0;
+}
+
+extern "C" int y355_conv2d_bf16(int device_id, const float *x, const float *w, const float *bias, const float *residual,
+                                int batch, int cin, int cout, int height, int width, int ksize, int stride, float neg_slope,
+                                int out_fp32, float *out) {
+    if (!x || !w || !out) return y355_fail(Y355_EINVAL, "null argument");
+    if (batch < 1 || cin < 1 || cout < 1 || height < 1 || width < 1) return y355_fail(Y355_EINVAL, "bad shape");
+    if (out_fp32 && residual) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
+    y355_conv_op *op = nullptr;
+    if (int rc = y355_conv_op_create_bf16(device_id, w, bias, cin, cout, ksize, stride, neg_slope, &op)) return rc;
+    return bf16_host_form(op, x, residual, batch, height, width, out_fp32, out);
 }
 
 extern "C" int y355_conv2d_geom_bf16(int device_id, const float *x, const float *w, const float *bias, const float *residual, int batch,
@@ -801,60 +793,128 @@ extern "C" int y355_conv2d_geom_bf16(int device_id, const float *x, const float 
     int Ho = 0, Wo = 0;
     if (int rc = geom_out(g, batch, height, width, &Ho, &Wo)) return rc;
     if (out_fp32 && residual) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
-    std::vector<void *> bufs;
-    OPS2CHK(hipSetDevice(device_id));
-    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
-    const int M = batch * Ho * Wo, taps = g->kh * g->kw;
-    const int kid = y355_convgeom_select(M, cout, y355_cu_count());
-    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
-    const int in_pb = (cin + 31) / 32 * 64, cout_pad = (cout + ki.bn - 1) / ki.bn * ki.bn;
-    const size_t wbytes = y355_convgeom_packed_bytes(kid, in_pb, taps, cout_pad);
-    std::vector<char> wpk(wbytes);
-    y355_convgeom_pack(kid, 1, w, nullptr, cout, cin, taps, in_pb, cout_pad, wpk.data());
-    std::vector<float> bpad(cout_pad, 0.f);
-    if (bias) std::copy(bias, bias + cout, bpad.begin());
-    const size_t n_in = (size_t)batch * cin * height * width, n_out = (size_t)batch * cout * Ho * Wo;
-    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
-    const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
-    float *d_x = nullptr, *d_y = nullptr, *d_b = nullptr;
-    char *d_in = nullptr, *d_out = nullptr, *d_w = nullptr, *d_res = nullptr;
-    OPS2CHK(hipMalloc((void **)&d_x, std::max(n_in, n_out) * 4)); bufs.push_back(d_x);
-    OPS2CHK(hipMalloc((void **)&d_y, n_out * 4)); bufs.push_back(d_y);
-    OPS2CHK(hipMalloc((void **)&d_b, cout_pad * 4)); bufs.push_back(d_b);
-    OPS2CHK(hipMalloc((void **)&d_in, in_bytes)); bufs.push_back(d_in);
-    OPS2CHK(hipMalloc((void **)&d_out, out_bytes)); bufs.push_back(d_out);
-    OPS2CHK(hipMalloc((void **)&d_w, wbytes)); bufs.push_back(d_w);
-    OPS2CHK(hipMemset(d_in, 0, in_bytes));
-    OPS2CHK(hipMemset(d_out, 0, out_bytes));
-    OPS2CHK(hipMemcpy(d_w, wpk.data(), wbytes, hipMemcpyHostToDevice));
-    OPS2CHK(hipMemcpy(d_b, bpad.data(), cout_pad * 4, hipMemcpyHostToDevice));
-    if (residual) {
-        OPS2CHK(hipMalloc((void **)&d_res, out_bytes)); bufs.push_back(d_res);
-        OPS2CHK(hipMemset(d_res, 0, out_bytes));
-        OPS2CHK(hipMemcpy(d_x, residual, n_out * 4, hipMemcpyHostToDevice));
-        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, d_x, (unsigned short *)d_res, batch, cout, Ho,
-                           Wo, cout_pad);
-        OPS2CHK(hipDeviceSynchronize());
+    y355_conv_op *op = nullptr;
+    if (int rc = y355_conv_op_create_bf16_geom(device_id, w, bias, cin, cout, g, neg_slope, &op)) return rc;
+    return bf16_host_form(op, x, residual, batch, height, width, out_fp32, out);
+}
+
+// ---- int8 forward ----------------------------------------------------------------------------------------------------------
+// "Run an int8 input at exponent sa": everything up to the staging of the input -- the kernel and its weights, the integer
+// epilogue for this exponent (cached), the workspaces (in_dev zeroed where the staging does not write; *in_bytes its size).
+static int i8_prepare(y355_conv_op *op, int batch, int height, int width, int sa, hipStream_t s, ConvPlan *pl, size_t *in_bytes) {
+    if (int rc = conv_plan(op, batch, height, width, pl)) return rc;
+    if (int rc = op_weights(op, *pl, s)) return rc;
+    if (sa != op->sa_cached) {
+        std::vector<int32_t> bt;
+        std::vector<long long> bw;
+        if (int rc = y355_op_requant(op->cin, op->geom ? op->g.kh * op->g.kw : 9, sa, op->e_w, op->e_b, 0, false, op->act, op->qb.data(), op->cout,
+                                     pl->cout_pad, &op->rq, &op->frac_bits, &bt, &bw))
+            return rc;
+        if (op->bt_dev) HIPTRY(hipMemcpy(op->bt_dev, bt.data(), sizeof(int) * pl->cout_pad, hipMemcpyHostToDevice));
+        HIPTRY(hipMemcpy(op->bw_dev, bw.data(), sizeof(long long) * pl->cout_pad, hipMemcpyHostToDevice));
+        op->sa_cached = sa;
     }
-    OPS2CHK(hipMemcpy(d_x, x, n_in * 4, hipMemcpyHostToDevice));
-    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, 0, d_x, (unsigned short *)d_in, batch, cin, height,
-                       width, in_pb / 2);
-    ConvGeomParams p = geom_params(*g, batch, height, width, Ho, Wo, in_pb, cout_pad, ki.bn);
-    p.in = d_in; p.w = d_w; p.bias_f = d_b; p.res = d_res; p.out = d_out;
-    p.out_pb = (int)out_pb; p.out_f32 = out_fp32 ? 1 : 0; p.slope = neg_slope;
-    y355_launch_convgeom(kid, 1, p, 0);
-    OPS2CHK(hipGetLastError());
-    if (out_fp32)
-        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, (const float *)d_out, d_y, batch, cout, Ho, Wo,
-                           cout_pad);
-    else
-        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, 0, (const unsigned short *)d_out, d_y, batch,
-                           cout, Ho, Wo, cout_pad);
-    OPS2CHK(hipGetLastError());
-    OPS2CHK(hipDeviceSynchronize());
-    OPS2CHK(hipMemcpy(out, d_y, n_out * 4, hipMemcpyDeviceToHost));
-    for (void *q : bufs) (void)hipFree(q);
+    // the 3x3 kernels prefetch past the last pixel: 64 pixels of slack
+    *in_bytes = ((size_t)batch * (height + 2) * (width + 2) + (op->geom ? 0 : 64)) * op->cpad;
+    const size_t raw_bytes = sizeof(long long) * (size_t)batch * pl->Ho * pl->Wo * pl->cout_pad;
+    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)1 << 61);
+    const bool regeo = geo != op->geo;
+    op->geo = geo;
+    if (int rc = op_grow(&op->in_dev, &op->in_cap, *in_bytes, true)) return rc;
+    if (int rc = op_grow(&op->out_dev, &op->out_cap, raw_bytes, false)) return rc;
+    if (regeo) HIPTRY(hipMemsetAsync(op->in_dev, 0, *in_bytes, s));
     return 0;
+}
+// conv + bias + activation without requantisation on the staged input: t' [pixel][cout_pad] int64 into out_dev
+static int i8_launch(y355_conv_op *op, const ConvPlan &pl, int batch, int height, int width, hipStream_t s) {
+    if (op->geom) {
+        ConvGeomParams p = geom_params(op->g, batch, height, width, pl.Ho, pl.Wo, op->cpad, pl.cout_pad, y355_convgeom_info(pl.kid)->bn);
+        p.in = op->in_dev; p.w = op->w_dev; p.bias_w = op->bw_dev; p.raw = (long long *)op->out_dev;
+        p.shl = op->rq.shl; p.lk = op->rq.lk; p.neg_mul = op->rq.neg_mul;
+        y355_launch_convgeom(pl.kid, 0, p, s);
+    } else {
+        const ConvKernelInfo &ki = *y355_conv_kernel(pl.kid);
+        HIPTRY(hipMemsetAsync(op->ctr_dev, 0, sizeof(Counters), s));
+        ConvParams p = gen16_params(ki, (const int8_t *)op->in_dev, (const int8_t *)op->w_dev, op->bt_dev, op->bw_dev, op->ctr_dev, batch, height,
+                                    width, pl.cout_pad, op->rq);
+        p.raw = (long long *)op->out_dev; p.mode = 1; p.guard = 0;      // statistics mode dumps t'
+        ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, s);
+    }
+    HIPTRY(hipGetLastError());
+    return 0;
+}
+
+// Conv2d_fuse(x) for a dyadic x (utils/modules.py:20-29 on the fake-quantised operands of the quantized path): exact.
+// *exact = 0: x is not a dyadic int8 tensor (out_dev untouched) -- the caller takes the bf16 route.
+extern "C" int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int batch, int height, int width, float *out_dev, void *stream,
+                                       int32_t *sa_in, int32_t *exact) {
+    if (!op || op->kind != 1 || !x_dev || !out_dev || !exact) return y355_fail(Y355_EINVAL, "null argument / not an int8 operator");
+    ConvPlan pl;
+    if (int rc = conv_out_size(op, batch, height, width, &pl)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    HIPTRY(hipSetDevice(op->device));
+    *exact = 0;
+    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * pl.Ho * pl.Wo;
+    // (1) the exponent of x: floor(log2(127 / max|x|)) -- the tensor is q / 2^e with |q| <= 127 (prep.as_dyadic_int8)
+    HIPTRY(hipMemsetAsync(op->flag_dev, 0, 16, s));
+    y355_launch_absmax(x_dev, n_in, op->flag_dev, s);
+    HIPTRY(hipGetLastError());
+    unsigned int bits = 0;
+    HIPTRY(hipMemcpyAsync(&bits, op->flag_dev, 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipStreamSynchronize(s));
+    float mx;
+    memcpy(&mx, &bits, 4);
+    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;                              // all zero / not finite: not this route
+    const int sa = (int)std::floor(std::log2((1.0f / mx) * 127.0f));
+    if (sa < -64 || sa > 64) return 0;
+    if (sa_in) *sa_in = sa;
+    // (2) weights, integer epilogue, workspaces; (3) stage: int8 NHWC with halo + the dyadic verdict
+    size_t in_bytes = 0;
+    if (int rc = i8_prepare(op, batch, height, width, sa, s, &pl, &in_bytes)) return rc;
+    hipLaunchKernelGGL(dyadic_to_nhwc_i8_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (int8_t *)op->in_dev, batch, op->cin, height, width,
+                       op->cpad, std::ldexp(1.0f, sa), op->flag_dev + 1);
+    HIPTRY(hipGetLastError());
+    unsigned int bad = 0;
+    HIPTRY(hipMemcpyAsync(&bad, op->flag_dev + 1, 4, hipMemcpyDeviceToHost, s));
+    HIPTRY(hipStreamSynchronize(s));
+    if (bad) return 0;
+    // (4) the convolution, (5) t' / 2^F' -> fp32 NCHW
+    if (int rc = i8_launch(op, pl, batch, height, width, s)) return rc;
+    hipLaunchKernelGGL(raw_to_nchw_f32_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const long long *)op->out_dev, out_dev, batch, op->cout, pl.Ho,
+                       pl.Wo, pl.cout_pad, std::ldexp(1.0f, -op->frac_bits));
+    HIPTRY(hipGetLastError());
+    *exact = 1;
+    return 0;
+}
+
+// conv + bias + activation WITHOUT requantisation on caller data: t' (int64) and F' such that the reference's Conv2d_fuse
+// output is exactly t' / 2^F' (utils/modules.py:20-29 on fake-quantized operands).  The input is int8 at the GIVEN exponent
+// sa_in, so these forms enter below the exponent detection.  Host pointers, synchronous, on a temporary operator (owned).
+static int i8_raw_host_form(y355_conv_op *op_, const int8_t *q_in, int batch, int height, int width, int sa_in, int64_t *out, int32_t *frac_bits) {
+    OpOwner own{op_};
+    y355_conv_op *op = own.op;
+    ConvPlan pl;
+    size_t in_bytes = 0;
+    if (int rc = conv_out_size(op, batch, height, width, &pl)) return rc;
+    if (int rc = i8_prepare(op, batch, height, width, sa_in, nullptr, &pl, &in_bytes)) return rc;
+    const std::vector<int8_t> xin = nhwc_halo_i8(q_in, batch, op->cin, height, width, op->cpad, in_bytes);
+    HIPTRY(hipMemcpy(op->in_dev, xin.data(), in_bytes, hipMemcpyHostToDevice));
+    if (int rc = i8_launch(op, pl, batch, height, width, nullptr)) return rc;
+    HIPTRY(hipDeviceSynchronize());
+    std::vector<long long> o((size_t)batch * pl.Ho * pl.Wo * pl.cout_pad);
+    HIPTRY(hipMemcpy(o.data(), op->out_dev, sizeof(long long) * o.size(), hipMemcpyDeviceToHost));
+    nhwc_to_nchw(o.data(), out, batch, op->cout, pl.Ho, pl.Wo, pl.cout_pad);
+    *frac_bits = op->frac_bits;
+    return 0;
+}
+
+extern "C" int y355_conv3x3_i8_raw(int device_id, const int8_t *q_in, const int8_t *q_w, const int32_t *q_b, int batch, int cin, int cout,
+                                   int H, int W, int sa_in, int e_w, int e_b, int flags, int64_t *out, int32_t *frac_bits) {
+    if (!q_in || !q_w || !q_b || !out || !frac_bits) return y355_fail(Y355_EINVAL, "null argument");
+    if (int rc = gen16_shape(batch, cin, cout, H, W, flags)) return rc;
+    y355_conv_op *op = nullptr;
+    if (int rc = y355_conv_op_create_i8(device_id, q_w, q_b, cin, cout, e_w, e_b, flags, &op)) return rc;
+    return i8_raw_host_form(op, q_in, batch, H, W, sa_in, out, frac_bits);
 }
 
 extern "C" int y355_conv_geom_i8_raw(int device_id, const int8_t *q_in, const int8_t *q_w, const int32_t *q_b, int batch, int cin, int cout,
@@ -864,241 +924,68 @@ extern "C" int y355_conv_geom_i8_raw(int device_id, const int8_t *q_in, const in
     if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
     int Ho = 0, Wo = 0;
     if (int rc = geom_out(g, batch, height, width, &Ho, &Wo)) return rc;
-    if (int rc = geom_flags(flags)) return rc;
-    if (int rc = geom_i8_k(cin, g)) return rc;
-    std::vector<void *> bufs;
-    OPS2CHK(hipSetDevice(device_id));
-    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
-    const int M = batch * Ho * Wo, taps = g->kh * g->kw;
-    const int kid = y355_convgeom_select(M, cout, y355_cu_count());
-    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
-    const int cpad = (cin + 63) / 64 * 64, cout_pad = (cout + ki.bn - 1) / ki.bn * ki.bn;
+    y355_conv_op *op = nullptr;
+    if (int rc = y355_conv_op_create_i8_geom(device_id, q_w, q_b, cin, cout, g, e_w, e_b, flags, &op)) return rc;
+    return i8_raw_host_form(op, q_in, batch, height, width, sa_in, out, frac_bits);
+}
+
+// The fused layer on caller data (utils/modules.py Conv2d_fuse drop-in, unit tests): conv + bias + activation [+ 2x2 max-pool]
+// requantised to sa_out.  Two passes: statistics (max |t'|), then the requantised one that stores and counts saturations.
+extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const int8_t *q_w, const int32_t *q_b, int batch, int cin, int cout,
+                                     int H, int W, int sa_in, int e_w, int e_b, int sa_out, int flags, int8_t *out, y355_layer_stats *stats) {
+    if (!q_in || !q_w || !q_b || !out) return y355_fail(Y355_EINVAL, "null argument");
+    if (int rc = gen16_shape(batch, cin, cout, H, W, flags)) return rc;
+    const int pool = (flags & Y355_OP_POOL) ? 1 : 0;
+    if (pool && ((H | W) & 1)) return y355_fail(Y355_EINVAL, "pooling needs even H, W");
+    HIPTRY(hipSetDevice(device_id));
+    if (int e = y355_prepare_kernels()) return e;
+    int cpad = 0;
+    const ConvKernelInfo &ki = *y355_conv_kernel(gen16_kernel(cin, pool, &cpad));
+    const int cout_pad = round_up(cout, ki.bn), Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
     Requant rq{};
     int fb = 0;
     std::vector<int32_t> bt;
     std::vector<long long> bw;
-    if (int rc = y355_op_requant(cin, taps, sa_in, e_w, e_b, geom_act(flags), q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
-    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * cpad;
-    std::vector<int8_t> xin(in_bytes, 0);
-    for (int b = 0; b < batch; ++b)
-        for (int c = 0; c < cin; ++c)
-            for (int y = 0; y < height; ++y)
-                for (int x = 0; x < width; ++x)
-                    xin[(((size_t)b * (height + 2) + y + 1) * (width + 2) + x + 1) * cpad + c] = q_in[(((size_t)b * cin + c) * height + y) * width + x];
-    const size_t wbytes = y355_convgeom_packed_bytes(kid, cpad, taps, cout_pad);
-    std::vector<char> wpk(wbytes);
-    y355_convgeom_pack(kid, 0, nullptr, q_w, cout, cin, taps, cpad, cout_pad, wpk.data());
-    const size_t raw_elems = (size_t)M * cout_pad;
-    char *d_in = nullptr, *d_w = nullptr;
-    long long *d_bw = nullptr, *d_raw = nullptr;
-    OPS2CHK(hipMalloc((void **)&d_in, in_bytes)); bufs.push_back(d_in);
-    OPS2CHK(hipMalloc((void **)&d_w, wbytes)); bufs.push_back(d_w);
-    OPS2CHK(hipMalloc((void **)&d_bw, sizeof(long long) * cout_pad)); bufs.push_back(d_bw);
-    OPS2CHK(hipMalloc((void **)&d_raw, sizeof(long long) * raw_elems)); bufs.push_back(d_raw);
-    OPS2CHK(hipMemcpy(d_in, xin.data(), in_bytes, hipMemcpyHostToDevice));
-    OPS2CHK(hipMemcpy(d_w, wpk.data(), wbytes, hipMemcpyHostToDevice));
-    OPS2CHK(hipMemcpy(d_bw, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
-    ConvGeomParams p = geom_params(*g, batch, height, width, Ho, Wo, cpad, cout_pad, ki.bn);
-    p.in = d_in; p.w = d_w; p.bias_w = d_bw; p.raw = d_raw;
-    p.shl = rq.shl; p.lk = rq.lk; p.neg_mul = rq.neg_mul;
-    y355_launch_convgeom(kid, 0, p, 0);
-    OPS2CHK(hipGetLastError());
-    OPS2CHK(hipDeviceSynchronize());
-    std::vector<long long> o(raw_elems);
-    OPS2CHK(hipMemcpy(o.data(), d_raw, sizeof(long long) * raw_elems, hipMemcpyDeviceToHost));
-    for (void *q : bufs) (void)hipFree(q);
-    for (int b = 0; b < batch; ++b)
-        for (int c = 0; c < cout; ++c)
-            for (int y = 0; y < Ho; ++y)
-                for (int x = 0; x < Wo; ++x)
-                    out[(((size_t)b * cout + c) * Ho + y) * Wo + x] = o[(((size_t)b * Ho + y) * Wo + x) * cout_pad + c];
-    *frac_bits = fb;
-    return 0;
-}
-
-extern "C" int y355_conv_op_create_bf16_geom(int device_id, const float *w, const float *bias, int cin, int cout, const y355_conv_geom *g,
-                                             float neg_slope, y355_conv_op **out) {
-    if (!w || !out || !g) return y355_fail(Y355_EINVAL, "null argument");
-    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    if (int rc = geom_limits(g)) return rc;
-    DEVCHK(hipSetDevice(device_id));
-    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
-    y355_conv_op *op = new y355_conv_op();
-    op->device = device_id;
-    op->kind = 0;
-    op->geom = 1;
-    op->g = *g;
-    op->cin = cin; op->cout = cout; op->slope = neg_slope;
-    op->cin_pad = (cin + 31) / 32 * 32;
-    op->w_host.assign(w, w + (size_t)cout * cin * g->kh * g->kw);
-    op->b_host.assign(cout, 0.f);
-    if (bias) std::copy(bias, bias + cout, op->b_host.begin());
-    *out = op;
-    return 0;
-}
-
-extern "C" int y355_conv_op_create_i8_geom(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, const y355_conv_geom *g,
-                                           int e_w, int e_b, int flags, y355_conv_op **out) {
-    if (!q_w || !q_b || !out || !g) return y355_fail(Y355_EINVAL, "null argument");
-    if (cin < 1 || cout < 1) return y355_fail(Y355_EINVAL, "bad shape");
-    if (int rc = geom_limits(g)) return rc;
-    if (int rc = geom_flags(flags)) return rc;
-    if (int rc = geom_i8_k(cin, g)) return rc;
-    DEVCHK(hipSetDevice(device_id));
-    if (int e = y355_prepare_convgeom()) return y355_fail(Y355_EHIP, std::string("kernel attributes: ") + hipGetErrorString((hipError_t)e));
-    y355_conv_op *op = new y355_conv_op();
-    op->device = device_id;
-    op->kind = 1;
-    op->geom = 1;
-    op->g = *g;
-    op->cin = cin; op->cout = cout;
-    op->e_w = e_w; op->e_b = e_b;
-    op->act = geom_act(flags);
-    op->cpad = (cin + 63) / 64 * 64;
-    op->qw.assign(q_w, q_w + (size_t)cout * cin * g->kh * g->kw);
-    op->qb.assign(q_b, q_b + cout);
-    if (hipMalloc((void **)&op->flag_dev, 16) != hipSuccess) {
-        y355_conv_op_destroy(op);
-        return y355_fail(Y355_EHIP, "device allocation failed");
+    if (int rc = y355_op_requant(cin, 9, sa_in, e_w, e_b, sa_out, true, geom_act(flags), q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
+    const size_t in_bytes = ((size_t)batch * (H + 2) * (W + 2) + 64) * cpad, out_elems = (size_t)batch * Ho * Wo * cout_pad;
+    const std::vector<int8_t> xin = nhwc_halo_i8(q_in, batch, cin, H, W, cpad, in_bytes);
+    std::vector<int8_t> packed(y355_packed_bytes(ki, cout_pad));
+    y355_pack_weights(ki, q_w, cout, cin, cout_pad, packed.data());
+    Scratch tmp;
+    int8_t *d_in = nullptr, *d_w = nullptr, *d_out = nullptr;
+    int *d_b = nullptr;
+    long long *d_bw = nullptr;
+    Counters *d_c = nullptr;
+    HIPTRY(tmp.get(&d_in, in_bytes));
+    HIPTRY(tmp.get(&d_w, packed.size()));
+    HIPTRY(tmp.get(&d_out, out_elems + 64));
+    HIPTRY(tmp.get(&d_b, sizeof(int) * cout_pad));
+    HIPTRY(tmp.get(&d_bw, sizeof(long long) * cout_pad));
+    HIPTRY(tmp.get(&d_c, sizeof(Counters)));
+    HIPTRY(hipMemcpy(d_in, xin.data(), in_bytes, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(d_w, packed.data(), packed.size(), hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(d_b, bt.data(), sizeof(int) * cout_pad, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(d_bw, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
+    HIPTRY(hipMemset(d_out, 0, out_elems + 64));
+    Counters cz{}, cs{};
+    for (int mode = 1; mode >= 0; --mode) {
+        HIPTRY(hipMemset(d_c, 0, sizeof(Counters)));
+        ConvParams p = gen16_params(ki, d_in, d_w, d_b, d_bw, d_c, batch, H, W, cout_pad, rq);
+        p.out = d_out; p.mode = mode; p.guard = 1;
+        ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, 0);
+        HIPTRY(hipGetLastError());
+        HIPTRY(hipDeviceSynchronize());
+        HIPTRY(hipMemcpy(mode ? &cs : &cz, d_c, sizeof(Counters), hipMemcpyDeviceToHost));
     }
-    *out = op;
-    return 0;
-}
-
-static int geom_forward_bf16(y355_conv_op *op, const float *x_dev, const float *residual_dev, int batch, int height, int width, int out_fp32,
-                             float *out_dev, hipStream_t s) {
-    int Ho = 0, Wo = 0;
-    if (int rc = geom_out(&op->g, batch, height, width, &Ho, &Wo)) return rc;
-    DEVCHK(hipSetDevice(op->device));
-    const int M = batch * Ho * Wo, taps = op->g.kh * op->g.kw, in_pb = op->cin_pad * 2;
-    const int kid = y355_convgeom_select(M, op->cout, y355_cu_count());
-    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
-    const int cout_pad = (op->cout + ki.bn - 1) / ki.bn * ki.bn;
-    if (op->w_kid != kid || op->w_cout_pad != cout_pad) {          // first call, or a size that selects another tile shape: (re)pack
-        const size_t wbytes = y355_convgeom_packed_bytes(kid, in_pb, taps, cout_pad);
-        std::vector<char> wpk(wbytes);
-        y355_convgeom_pack(kid, 1, op->w_host.data(), nullptr, op->cout, op->cin, taps, in_pb, cout_pad, wpk.data());
-        std::vector<float> bpad(cout_pad, 0.f);
-        std::copy(op->b_host.begin(), op->b_host.end(), bpad.begin());
-        DEVCHK(hipStreamSynchronize(s));                           // a previous forward may still read the old fragments
-        if (op->w_dev) (void)hipFree(op->w_dev);
-        if (op->bias_dev) (void)hipFree(op->bias_dev);
-        op->w_dev = nullptr; op->bias_dev = nullptr;
-        DEVCHK(hipMalloc((void **)&op->w_dev, wbytes));
-        DEVCHK(hipMalloc((void **)&op->bias_dev, sizeof(float) * cout_pad));
-        DEVCHK(hipMemcpy(op->w_dev, wpk.data(), wbytes, hipMemcpyHostToDevice));
-        DEVCHK(hipMemcpy(op->bias_dev, bpad.data(), sizeof(float) * cout_pad, hipMemcpyHostToDevice));
-        op->w_kid = kid;
-        op->w_cout_pad = cout_pad;
-        op->geo = 0;
+    std::vector<int8_t> o(out_elems);
+    HIPTRY(hipMemcpy(o.data(), d_out, out_elems, hipMemcpyDeviceToHost));
+    nhwc_to_nchw(o.data(), out, batch, cout, Ho, Wo, cout_pad);
+    if (stats) {
+        stats->absmax_t = (int64_t)cs.absmax;
+        stats->frac_bits = fb;
+        stats->reserved = 0;
+        stats->saturated = (int64_t)cz.sat;
+        stats->guard = (int64_t)cz.guard;
     }
-    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * Ho * Wo;
-    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
-    const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
-    // zeroed on (re)allocation and on a new geometry: the staging kernels write the interior and the real channels only
-    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)out_fp32 << 62) ^ ((size_t)1 << 61);
-    const bool regeo = geo != op->geo;
-    op->geo = geo;
-    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
-    if (int rc = op_grow(&op->out_dev, &op->out_cap, out_bytes, true)) return rc;
-    if (regeo) DEVCHK(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
-    if (residual_dev) {
-        if (int rc = op_grow(&op->res_dev, &op->res_cap, out_bytes, true)) return rc;
-        if (regeo) DEVCHK(hipMemsetAsync(op->res_dev, 0, out_bytes, s));
-        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, residual_dev, (unsigned short *)op->res_dev, batch,
-                           op->cout, Ho, Wo, cout_pad);
-    }
-    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (unsigned short *)op->in_dev, batch, op->cin, height,
-                       width, op->cin_pad);
-    ConvGeomParams p = geom_params(op->g, batch, height, width, Ho, Wo, in_pb, cout_pad, ki.bn);
-    p.in = op->in_dev; p.w = op->w_dev; p.bias_f = op->bias_dev; p.res = residual_dev ? op->res_dev : nullptr; p.out = op->out_dev;
-    p.out_pb = (int)out_pb; p.out_f32 = out_fp32 ? 1 : 0; p.slope = op->slope;
-    y355_launch_convgeom(kid, 1, p, s);
-    DEVCHK(hipGetLastError());
-    if (out_fp32)
-        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const float *)op->out_dev, out_dev, batch, op->cout, Ho,
-                           Wo, cout_pad);
-    else
-        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const unsigned short *)op->out_dev, out_dev, batch,
-                           op->cout, Ho, Wo, cout_pad);
-    DEVCHK(hipGetLastError());
-    return 0;
-}
-
-static int geom_forward_i8(y355_conv_op *op, const float *x_dev, int batch, int height, int width, float *out_dev, hipStream_t s,
-                           int32_t *sa_in, int32_t *exact) {
-    int Ho = 0, Wo = 0;
-    if (int rc = geom_out(&op->g, batch, height, width, &Ho, &Wo)) return rc;
-    DEVCHK(hipSetDevice(op->device));
-    *exact = 0;
-    const int M = batch * Ho * Wo, taps = op->g.kh * op->g.kw;
-    const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * Ho * Wo;
-    // (1) the exponent of x, as y355_conv_op_forward_i8
-    DEVCHK(hipMemsetAsync(op->flag_dev, 0, 16, s));
-    y355_launch_absmax(x_dev, n_in, op->flag_dev, s);
-    DEVCHK(hipGetLastError());
-    unsigned int bits = 0;
-    DEVCHK(hipMemcpyAsync(&bits, op->flag_dev, 4, hipMemcpyDeviceToHost, s));
-    DEVCHK(hipStreamSynchronize(s));
-    float mx;
-    memcpy(&mx, &bits, 4);
-    if (!(mx > 0.f) || !std::isfinite(mx)) return 0;
-    const int sa = (int)std::floor(std::log2((1.0f / mx) * 127.0f));
-    if (sa < -64 || sa > 64) return 0;
-    if (sa_in) *sa_in = sa;
-    // (2) weights for this size's tile shape, the integer epilogue for this exponent (both cached)
-    const int kid = y355_convgeom_select(M, op->cout, y355_cu_count());
-    const ConvGeomInfo &ki = *y355_convgeom_info(kid);
-    const int cout_pad = (op->cout + ki.bn - 1) / ki.bn * ki.bn;
-    if (op->w_kid != kid || op->w_cout_pad != cout_pad) {
-        const size_t wbytes = y355_convgeom_packed_bytes(kid, op->cpad, taps, cout_pad);
-        std::vector<char> wpk(wbytes);
-        y355_convgeom_pack(kid, 0, nullptr, op->qw.data(), op->cout, op->cin, taps, op->cpad, cout_pad, wpk.data());
-        DEVCHK(hipStreamSynchronize(s));
-        if (op->qw_dev) (void)hipFree(op->qw_dev);
-        if (op->bw_dev) (void)hipFree(op->bw_dev);
-        op->qw_dev = nullptr; op->bw_dev = nullptr;
-        DEVCHK(hipMalloc((void **)&op->qw_dev, wbytes));
-        DEVCHK(hipMalloc((void **)&op->bw_dev, sizeof(long long) * cout_pad));
-        DEVCHK(hipMemcpy(op->qw_dev, wpk.data(), wbytes, hipMemcpyHostToDevice));
-        op->w_kid = kid;
-        op->w_cout_pad = cout_pad;
-        op->sa_cached = 1 << 30;                                    // the biases are padded to the new width below
-    }
-    if (sa != op->sa_cached) {
-        std::vector<int32_t> bt;
-        std::vector<long long> bw;
-        if (int rc = y355_op_requant(op->cin, taps, sa, op->e_w, op->e_b, op->act, op->qb.data(), op->cout, cout_pad, &op->rq, &op->frac_bits, &bt,
-                                     &bw))
-            return rc;
-        DEVCHK(hipMemcpy(op->bw_dev, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
-        op->sa_cached = sa;
-    }
-    // (3) stage: int8 NHWC with halo + the dyadic verdict
-    const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * op->cpad;
-    const size_t raw_bytes = sizeof(long long) * (size_t)M * cout_pad;
-    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)1 << 61);
-    const bool regeo = geo != op->geo;
-    op->geo = geo;
-    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
-    if (int rc = op_grow(&op->out_dev, &op->out_cap, raw_bytes, false)) return rc;
-    if (regeo) DEVCHK(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
-    hipLaunchKernelGGL(dyadic_to_nhwc_i8_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (int8_t *)op->in_dev, batch, op->cin, height, width,
-                       op->cpad, std::ldexp(1.0f, sa), op->flag_dev + 1);
-    DEVCHK(hipGetLastError());
-    unsigned int bad = 0;
-    DEVCHK(hipMemcpyAsync(&bad, op->flag_dev + 1, 4, hipMemcpyDeviceToHost, s));
-    DEVCHK(hipStreamSynchronize(s));
-    if (bad) return 0;
-    // (4) conv + bias + activation without requantisation, (5) t' / 2^F' -> fp32 NCHW
-    ConvGeomParams p = geom_params(op->g, batch, height, width, Ho, Wo, op->cpad, cout_pad, ki.bn);
-    p.in = op->in_dev; p.w = (const char *)op->qw_dev; p.bias_w = op->bw_dev; p.raw = (long long *)op->out_dev;
-    p.shl = op->rq.shl; p.lk = op->rq.lk; p.neg_mul = op->rq.neg_mul;
-    y355_launch_convgeom(kid, 0, p, s);
-    DEVCHK(hipGetLastError());
-    hipLaunchKernelGGL(raw_to_nchw_f32_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const long long *)op->out_dev, out_dev, batch, op->cout, Ho,
-                       Wo, cout_pad, std::ldexp(1.0f, -op->frac_bits));
-    DEVCHK(hipGetLastError());
-    *exact = 1;
     return 0;
 }

@@ -108,6 +108,13 @@ struct Counters {
     unsigned long long guard; // head-room violations
 };
 
+// engine.hip, for the other translation units
+int y355_fail(int code, const std::string &msg);     // keeps msg for y355_last_error(), returns code
+int y355_prepare_kernels();                          // one-time kernel attributes of the int8 engine's kernels; a y355 error code
+// the integer epilogue of one stand-alone layer (the operator layer of ops.hip): make_requant, with requantisation to sa_out
+// when have_out, else none (t' is the result)
+int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, const int32_t *q_b, int cout,
+                    int cout_pad, Requant *rq, int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w);
 int y355_cu_count(void);       // engine.hip: compute units of the current device (cached per device), 256 on an MI355X in SPX mode
 int y355_zero_counters(Counters *c, int n, hipStream_t s);    // engine.hip: a kernel launch, not hipMemsetAsync; returns the launch status (hipError_t)
 

@@ -13,6 +13,7 @@ import numpy as np
 import torch
 
 from . import _ffi
+from ._handle import Handle, _require_gpu
 
 
 def _gt_arrays(ground_truth, num_classes):
@@ -29,35 +30,21 @@ def _gt_arrays(ground_truth, num_classes):
     return off, np.ascontiguousarray(g[:, 1:5], np.float32), cls, np.ascontiguousarray(g[:, 5] != 0, np.uint8)
 
 
-class ApEval:
+class ApEval(Handle):
+    _destroy = "y355_apeval_destroy"
+
     def __init__(self, num_classes, ground_truth, max_dets=None, device=0):
-        self._h = None
         lib = _ffi.lib()
-        if not torch.cuda.is_available():
-            raise RuntimeError("yolo355: no GPU visible; ApEval has no CPU fallback")
-        self.device = torch.device(device if isinstance(device, (str, torch.device)) else "cuda:%d" % int(device))
-        if self.device.index is None:
-            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.device = _require_gpu(device if isinstance(device, (str, torch.device)) else "cuda:%d" % int(device))
         self.num_classes, self.num_images = int(num_classes), len(ground_truth)
         # default capacity: 256 detections per image (VOC07 at conf_thresh 0.01 stays well below), at least 65536
         self.max_dets = int(max_dets) if max_dets is not None else min(1 << 27, max(1 << 16, 256 * self.num_images))
         off, boxes, cls, diff = _gt_arrays(ground_truth, self.num_classes)
         h = C.c_void_p()
         _ffi.check(lib.y355_apeval_create(self.device.index, self.num_classes, self.num_images, self.max_dets, C.byref(h)))
-        self._h, self._lib = h, lib
+        self._own(lib, h)
         _ffi.check(lib.y355_apeval_set_gt(h, off.ctypes.data, boxes.ctypes.data, cls.ctypes.data, diff.ctypes.data))
         self.npos = self.ndet = self.mean_abi = None
-
-    def close(self):
-        if self._h is not None:
-            self._lib.y355_apeval_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def add(self, first_image, boxes, scores, cls, count, after_stream=None, batch=None):
         """One batch of engine outputs, CUDA tensors: boxes float32 [B,max_det,4], scores float32 [B,max_det], cls int32

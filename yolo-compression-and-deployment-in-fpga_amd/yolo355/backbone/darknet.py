@@ -101,7 +101,7 @@ class _Pool2(nn.Module):
 
     def forward(self, x):
         import torch
-        from ..engine import maxpool2x2_f32
+        from ..ops import maxpool2x2_f32
         y = maxpool2x2_f32(x.detach().float().cpu().numpy(), device_id=x.device.index if x.is_cuda and x.device.index is not None else 0)
         return torch.from_numpy(y).to(x.device)
 

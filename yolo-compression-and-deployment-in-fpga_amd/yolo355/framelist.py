@@ -101,14 +101,17 @@ def check_sizes_wh(sizes_wh):
         raise ValueError('sizes_wh: an array [n,2] or "own", got %r' % (sizes_wh,))
 
 
+def wh_tensor(sizes_wh, n, device, what="batch"):
+    """the (width, height) rows of sizes_wh as a float32 device tensor [n,2]; n None: as many as there are"""
+    wh = torch.as_tensor(np.asarray(sizes_wh, np.float32).reshape(-1, 2)).to(device)
+    if n is not None and wh.shape[0] != n:
+        raise ValueError("sizes_wh has %d rows for a %s of %d" % (wh.shape[0], what, n))
+    return wh
+
+
 def sizes_wh_tensor(sizes_wh, sizes, device):
     """sizes_wh (None, an array [n,2] or "own") of a checked list with these (h, w) as a float32 device tensor [n,2], or None"""
     check_sizes_wh(sizes_wh)
     if sizes_wh is None:
         return None
-    if isinstance(sizes_wh, str):
-        sizes_wh = own_sizes_wh(sizes)
-    wh = torch.as_tensor(np.asarray(sizes_wh, np.float32).reshape(-1, 2)).to(device)
-    if wh.shape[0] != len(sizes):
-        raise ValueError("sizes_wh has %d rows for a list of %d" % (wh.shape[0], len(sizes)))
-    return wh
+    return wh_tensor(own_sizes_wh(sizes) if isinstance(sizes_wh, str) else sizes_wh, len(sizes), device, "list")

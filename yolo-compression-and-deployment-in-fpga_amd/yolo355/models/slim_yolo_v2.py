@@ -39,6 +39,26 @@ def _cap(model):
     return None if cap == 4096 else cap
 
 
+def _device(model):
+    return model.device if isinstance(model.device, (str, torch.device)) else "cuda:0"
+
+
+def _cached(slots, slot, key, batch, version, build, load):
+    """The handle in slots[slot], kept there as (handle, key, version): build() makes a new one (the old one is closed
+    first) when the configuration key changed or its max_batch does not hold `batch`, load(handle) runs when the weight
+    version changed.  An empty slot is a missing key."""
+    h, k, v = slots.get(slot, (None, None, None))
+    if h is None or k != key or h.max_batch < batch:
+        if h is not None:
+            h.close()
+        h, v = build(), None
+        slots[slot] = (h, key, None)
+    if v != version:
+        load(h)
+        slots[slot] = (h, key, version)
+    return h
+
+
 class AveragedRangeTracker(nn.Module):
     """Checkpoint-compatible holder of the tracker buffers (models/slim_yolo_v2.py:9-14).
     The max|activation| statistics come from the GPU; the state update is prep.RangeTracker."""
@@ -92,15 +112,15 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         self.pred = nn.Conv2d(256, self.anchor_number * (1 + 4 + self.num_classes), 3, 1, padding=1)
         self.a_tracker_pred = AveragedRangeTracker()
 
-        self._engine = None
-        self._engine_key = None
-        self._loaded_version = None
-        self._loaded_find = None
-        self._pipe = None               # y355_pipeline: batches larger than PIPELINE_CHUNK and the asynchronous submit / collect
-        self._pipe_key = None
-        self._pipe_loaded = None
-
     PIPELINE_CHUNK = 64                 # images per ticket of the pipeline (BASELINE.json's batch: the kernels' tuned regime)
+
+    @property
+    def _engine(self):
+        return self.__dict__.get("_engine_state", (None,))[0]
+
+    @property
+    def _pipe(self):                    # y355_pipeline: batches larger than PIPELINE_CHUNK and the asynchronous submit / collect
+        return self.__dict__.get("_pipe_state", (None,))[0]
 
     # ------------------------------------------------------------------ reference API
     def set_grid(self, input_size):
@@ -144,13 +164,8 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
             sa = [t.exponent() for t in trackers]
         if B > self.PIPELINE_CHUNK:
             # more than one batch-64 forward: chunks in flight on the pipeline's handles (y355_pipeline), results in order
-            pipe = self._get_pipeline(find)
-            pipe.set_act_exponents(sa)
-            pipe.set_thresholds(self.conf_thresh, self.nms_thresh)
-            return pipe.forward(x, find=find, sizes_wh=sizes_wh)
-        eng = self._get_engine(B, find)
-        eng.set_act_exponents(sa)
-        eng.set_thresholds(self.conf_thresh, self.nms_thresh)
+            return self._primed(self._get_pipeline(find), sa).forward(x, find=find, sizes_wh=sizes_wh)
+        eng = self._primed(self._get_engine(B, find), sa)
         if sizes_wh is not None:
             return eng.forward_scaled(x, sizes_wh, find=find)
         return eng.forward(x, find=find)
@@ -162,26 +177,9 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         outstanding; the trackers must be calibrated (one forward(x, quantization=True) before)."""
         if not quantization or self.trainable:
             raise NotImplementedError("submit_batch runs the int8 path (quantization=True, eval)")
-        trackers = self._tracker_states()
-        if any(t.first_a == 0 for t in trackers):
-            raise RuntimeError("yolo355: calibrate the trackers with one forward(x, quantization=True) first")
-        pipe = self._get_pipeline(find)
-        pipe.set_act_exponents([t.exponent() for t in trackers])
-        pipe.set_thresholds(self.conf_thresh, self.nms_thresh)
-        xd = pipe._dev_input(x)
-        n = int(xd.shape[0])
-        if n > pipe.depth * pipe.max_batch:
-            raise ValueError("submit_batch takes at most %d images at a time" % (pipe.depth * pipe.max_batch))
-        wh = None
-        if sizes_wh is not None:
-            wh = torch.as_tensor(np.asarray(sizes_wh, np.float32).reshape(-1, 2)).to(pipe.device)
-        tickets = []
-        for i0 in range(0, n, pipe.max_batch):
-            t = pipe.submit(xd[i0:i0 + pipe.max_batch], 0)
-            if wh is not None:
-                pipe.scale_boxes(t, wh[i0:i0 + pipe.max_batch])
-            tickets.append(t)
-        return (pipe, tickets, wh)
+        sa = self._frozen_exponents()
+        pipe = self._primed(self._get_pipeline(find), sa)
+        return (pipe,) + pipe.submit_batch(x, sizes_wh)
 
     def collect_batch(self, token):
         pipe, tickets, _ = token
@@ -212,12 +210,7 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         layer.  Element i equals forward(x_i) for the tensor the reference's transform makes of frame i.
         The trackers must be calibrated (one forward on a normalised tensor) beforehand."""
         eng = self._get_engine(int(frames.shape[0]), find)
-        trackers = self._tracker_states()
-        if any(t.first_a == 0 for t in trackers):
-            raise RuntimeError("yolo355: calibrate the trackers with one forward(x, quantization=True) first")
-        eng.set_act_exponents([t.exponent() for t in trackers])
-        eng.set_thresholds(self.conf_thresh, self.nms_thresh)
-        return eng.forward_frames(frames, find=find)
+        return self._primed(eng, self._frozen_exponents()).forward_frames(frames, find=find)
 
     def forward_frame_list(self, frames, quantization=True, find=False, sizes_wh=None):
         """forward_frames for a list of frames, each uint8 [h,w,3] BGR of its own size (numpy, CPU or CUDA torch, mixed) --
@@ -236,33 +229,38 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
             net = self._get_f32_net(n, find)
             net.set_thresholds(self.conf_thresh, self.nms_thresh)
             return net.forward_frame_list(frames, sizes_wh=sizes_wh)
-        trackers = self._tracker_states()
-        if any(t.first_a == 0 for t in trackers):
-            raise RuntimeError("yolo355: calibrate the trackers with one forward(x, quantization=True) first")
+        sa = self._frozen_exponents()
         target = self._get_pipeline(find) if n > self.PIPELINE_CHUNK else self._get_engine(n, find)
-        target.set_act_exponents([t.exponent() for t in trackers])
-        target.set_thresholds(self.conf_thresh, self.nms_thresh)
-        return target.forward_frame_list(frames, find=find, sizes_wh=sizes_wh)
+        return self._primed(target, sa).forward_frame_list(frames, find=find, sizes_wh=sizes_wh)
 
     # ------------------------------------------------------------------ engine plumbing
     def _weights_version(self):
         return tuple(int(p._version) for p in self.parameters()) + tuple(p.data_ptr() for p in self.parameters())
 
+    def _frozen_exponents(self):
+        """the 11 activation exponents of the calibrated trackers"""
+        trackers = self._tracker_states()
+        if any(t.first_a == 0 for t in trackers):
+            raise RuntimeError("yolo355: calibrate the trackers with one forward(x, quantization=True) first")
+        return [t.exponent() for t in trackers]
+
+    def _primed(self, target, sa):
+        """an Engine or a Pipeline with these exponents and the model's thresholds"""
+        target.set_act_exponents(sa)
+        target.set_thresholds(self.conf_thresh, self.nms_thresh)
+        return target
+
+    def _config(self):
+        """(what a handle is rebuilt for, the arguments Engine / Pipeline / Net share)"""
+        anchors = self.anchor_size.tolist()
+        return ((tuple(self.input_size), self.num_classes, tuple(map(tuple, anchors))),
+                (self.input_size, self.num_classes, anchors, self.conf_thresh, self.nms_thresh))
+
     def _get_engine(self, batch, find):
-        key = (tuple(self.input_size), self.num_classes, tuple(map(tuple, self.anchor_size.tolist())))
-        if self._engine is None or self._engine_key != key or self._engine.max_batch < batch:
-            if self._engine is not None:
-                self._engine.close()
-            dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
-            self._engine = Engine(self.input_size, self.num_classes, self.anchor_size.tolist(),
-                                  self.conf_thresh, self.nms_thresh, max_batch=max(batch, 1), device=dev, max_candidates=_cap(self))
-            self._engine_key = key
-            self._loaded_version = None
-        ver = self._weights_version()
-        if self._loaded_version != ver or self._loaded_find != find:
-            self._load_into(self._engine, find)
-            self._loaded_version, self._loaded_find = ver, find
-        return self._engine
+        key, args = self._config()
+        return _cached(self.__dict__, "_engine_state", key, batch, (self._weights_version(), bool(find)),
+                       lambda: Engine(*args, max_batch=max(batch, 1), device=_device(self), max_candidates=_cap(self)),
+                       lambda eng: self._load_into(eng, find))
 
     def _load_into(self, target, find):
         """the ten dyadic layers of this model into an Engine or a Pipeline"""
@@ -277,44 +275,29 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         target.set_retune(prep.RETUNE)
 
     def _get_pipeline(self, find):
-        key = (tuple(self.input_size), self.num_classes, tuple(map(tuple, self.anchor_size.tolist())))
-        if self._pipe is None or self._pipe_key != key:
-            if self._pipe is not None:
-                self._pipe.close()
-            dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
-            self._pipe = Pipeline(self.input_size, self.num_classes, self.anchor_size.tolist(), self.conf_thresh, self.nms_thresh,
-                                  max_batch=self.PIPELINE_CHUNK, device=dev, max_candidates=_cap(self))
-            self._pipe_key, self._pipe_loaded = key, None
-        ver = (self._weights_version(), bool(find))
-        if self._pipe_loaded != ver:
-            self._pipe.sync()
-            self._load_into(self._pipe, find)
-            self._pipe_loaded = ver
-        return self._pipe
+        key, args = self._config()
+
+        def load(pipe):
+            pipe.sync()
+            self._load_into(pipe, find)
+        return _cached(self.__dict__, "_pipe_state", key, 0, (self._weights_version(), bool(find)),
+                       lambda: Pipeline(*args, max_batch=self.PIPELINE_CHUNK, device=_device(self), max_candidates=_cap(self)), load)
 
     def _get_f32_net(self, batch, find):
         """y355_net (Y355_ARCH_SLIM_V2, bf16) loaded with this model's conv weights and biases as they are."""
-        key = (tuple(self.input_size), self.num_classes, tuple(map(tuple, self.anchor_size.tolist())))
-        st = self.__dict__.setdefault("_f32", dict(net=None, key=None, ver=None))
-        if st["net"] is None or st["key"] != key or st["net"].max_batch < batch:
-            if st["net"] is not None:
-                st["net"].close()
-            dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
-            st["net"] = Net("slim_yolo_v2", self.input_size, self.num_classes, self.anchor_size.tolist(), self.conf_thresh,
-                            self.nms_thresh, max_batch=max(batch, 1), device=dev, dtype="bf16", max_candidates=_cap(self))
-            st["key"], st["ver"] = key, None
-        ver = (self._weights_version(), bool(find))
-        if st["ver"] != ver:
-            mods = [getattr(self, n).convs[0] for n in _CONVS] + [self.pred]
-            for i, m in enumerate(mods):
+        key, args = self._config()
+
+        def load(net):
+            for i, m in enumerate([getattr(self, n).convs[0] for n in _CONVS] + [self.pred]):
                 w = m.weight.detach().float().cpu().numpy()
                 b = m.bias.detach().float().cpu().numpy()
                 if find:                                    # the checkpoint holds W * 2^r, the forward divides by 2^r
                     sc = np.float32(2.0 ** -prep.RETUNE[i])
                     w, b = w * sc, b * sc
-                st["net"].load_layer(i, w, b)
-            st["ver"] = ver
-        return st["net"]
+                net.load_layer(i, w, b)
+        return _cached(self.__dict__, "_f32", key, batch, (self._weights_version(), bool(find)),
+                       lambda: Net("slim_yolo_v2", *args, max_batch=max(batch, 1), device=_device(self), dtype="bf16",
+                                   max_candidates=_cap(self)), load)
 
     def _tracker_states(self):
         return [prep.RangeTracker(getattr(self, n).scale, int(getattr(self, n).first_a.item())) for n in _TRACKERS]
@@ -355,16 +338,20 @@ class _NetModel(nn.Module):
         sizes_wh: [B,2] original (width, height) per image: the boxes come back in pixels of the original images
         (the evaluators' `bboxes *= [[w, h, w, h]]`, test.py:88-90, on the GPU)."""
         self._check_inference()
-        if not quantization:
-            net = self._get_net(int(x.shape[0]))
-            net.set_thresholds(self.conf_thresh, self.nms_thresh)
-            return net.forward(x, sizes_wh=sizes_wh)
-        if self.act_exponents is None:                     # (a model calibrate()d on its int8 net never builds the bf16 one)
+        if quantization and self.act_exponents is None:    # (a model calibrate()d on its int8 net never builds the bf16 one)
             self.act_exponents = self._get_net(int(x.shape[0])).calibration_exponents(x)
-        qnet = self._get_net(int(x.shape[0]), int8=True)
-        qnet.set_act_exponents(*self.act_exponents)
-        qnet.set_thresholds(self.conf_thresh, self.nms_thresh)
-        return qnet.forward(x, sizes_wh=sizes_wh)
+        return self._ready_net(int(x.shape[0]), quantization).forward(x, sizes_wh=sizes_wh)
+
+    def _ready_net(self, batch, quantization):
+        """the bf16 net, or the int8 net with the frozen activation exponents, at the model's thresholds"""
+        if quantization and self.act_exponents is None:
+            raise RuntimeError("yolo355: the int8 activation exponents are not frozen yet: run one "
+                               "forward_batch(x, quantization=True) first")
+        net = self._get_net(batch, int8=bool(quantization))
+        if quantization:
+            net.set_act_exponents(*self.act_exponents)
+        net.set_thresholds(self.conf_thresh, self.nms_thresh)
+        return net
 
     def forward_frames(self, frames, quantization=False, sizes_wh=None):
         """New: detections for camera frames as cv2 delivers them, uint8 [B,h,w,3] BGR of any size.
@@ -374,14 +361,7 @@ class _NetModel(nn.Module):
         forward_batch(x, quantization=True) first.  sizes_wh as forward_batch."""
         Net.check_frames(frames)
         self._check_inference()
-        if quantization and self.act_exponents is None:
-            raise RuntimeError("yolo355: the int8 activation exponents are not frozen yet: run one "
-                               "forward_batch(x, quantization=True) first")
-        net = self._get_net(int(frames.shape[0]), int8=bool(quantization))
-        if quantization:
-            net.set_act_exponents(*self.act_exponents)
-        net.set_thresholds(self.conf_thresh, self.nms_thresh)
-        return net.forward_frames(frames, sizes_wh=sizes_wh)
+        return self._ready_net(int(frames.shape[0]), quantization).forward_frames(frames, sizes_wh=sizes_wh)
 
     def forward_frame_list(self, frames, quantization=False, sizes_wh=None):
         """forward_frames for a list of frames, each uint8 [h,w,3] BGR of its own size (numpy, CPU or CUDA torch, mixed) --
@@ -391,14 +371,7 @@ class _NetModel(nn.Module):
         activation exponents, as forward_frames."""
         Net.check_frame_list(frames)
         self._check_inference()
-        if quantization and self.act_exponents is None:
-            raise RuntimeError("yolo355: the int8 activation exponents are not frozen yet: run one "
-                               "forward_batch(x, quantization=True) first")
-        net = self._get_net(len(frames), int8=bool(quantization))
-        if quantization:
-            net.set_act_exponents(*self.act_exponents)
-        net.set_thresholds(self.conf_thresh, self.nms_thresh)
-        return net.forward_frame_list(frames, sizes_wh=sizes_wh)
+        return self._ready_net(len(frames), quantization).forward_frame_list(frames, sizes_wh=sizes_wh)
 
     def calibrate_frame_list(self, frames, freeze=False):
         """calibrate() on a list of camera frames of any sizes (Net.calibrate_frame_list)."""
@@ -462,29 +435,21 @@ class _NetModel(nn.Module):
     max_spread = None
 
     def _get_net(self, batch, int8=False):
-        slot = "q" if int8 else "f"
-        st = self.__dict__.setdefault("_nets", {}).setdefault(slot, dict(net=None, key=None, ver=None))
-        key = (tuple(self.input_size), self.num_classes, tuple(map(tuple, self._flat_anchors())))
-        if st["net"] is None or st["key"] != key or st["net"].max_batch < batch:
-            if st["net"] is not None:
-                st["net"].close()
-            dev = self.device if isinstance(self.device, (str, torch.device)) else "cuda:0"
-            st["net"] = Net(self._arch, self.input_size, self.num_classes, self._flat_anchors(), self.conf_thresh,
-                            self.nms_thresh, max_batch=max(batch, 1), device=dev, dtype="int8" if int8 else "bf16", max_candidates=_cap(self))
-            st["key"], st["ver"] = key, None
-        ver = self._weights_version()
-        if int8:
-            ver = ver + (bool(self.channel_level), self.max_spread)
-        if st["ver"] != ver:
+        anchors = self._flat_anchors()
+        ver = self._weights_version() + ((bool(self.channel_level), self.max_spread) if int8 else ())
+
+        def load(net):
             folded = [folded_f32(m) for m in self._conv_modules()]
             if int8:
                 for i, q in enumerate(prep.quantize_folded(folded, bool(self.channel_level), self.max_spread)):
-                    st["net"].load_layer_i8(i, q["q_w"], q["q_b"], q["e_w"], q["e_b"])
+                    net.load_layer_i8(i, q["q_w"], q["q_b"], q["e_w"], q["e_b"])
             else:
                 for i, (w, b) in enumerate(folded):
-                    st["net"].load_layer(i, w, b)
-            st["ver"] = ver
-        return st["net"]
+                    net.load_layer(i, w, b)
+        return _cached(self.__dict__.setdefault("_nets", {}), "q" if int8 else "f", (tuple(self.input_size), self.num_classes, tuple(map(tuple, anchors))), batch, ver,
+                       lambda: Net(self._arch, self.input_size, self.num_classes, anchors, self.conf_thresh, self.nms_thresh,
+                                   max_batch=max(batch, 1), device=_device(self), dtype="int8" if int8 else "bf16",
+                                   max_candidates=_cap(self)), load)
 
 
 class SlimYOLOv2(_NetModel):

@@ -56,7 +56,7 @@ class myYOLOv2(_NetModel):
         fp_1 = self.reorg(self.route_layer(fp_1))
         fp = torch.cat([fp_1, fp_2], dim=1)
         fp = self.convsets_2(fp)
-        from ..engine import conv2d_bf16
+        from ..ops import conv2d_bf16
         w = self.pred.weight.detach().float().cpu().numpy()
         b = self.pred.bias.detach().float().cpu().numpy()
         y = conv2d_bf16(fp.detach().float().cpu().numpy(), w, b, stride=1, neg_slope=1.0, out_fp32=True,
@@ -64,7 +64,7 @@ class myYOLOv2(_NetModel):
         return y
 
     def forward_batch_composed(self, x):
-        from ..engine import head_f32
+        from ..ops import head_f32
         if self.training:
             raise NotImplementedError("yolo355 is an inference engine: call .eval() first")
         with torch.no_grad():

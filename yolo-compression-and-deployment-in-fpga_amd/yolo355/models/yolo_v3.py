@@ -23,13 +23,13 @@ def _dev(x):
 
 
 def _pred(conv, x):
-    from ..engine import conv2d_bf16
+    from ..ops import conv2d_bf16
     return conv2d_bf16(x.detach().float().cpu().numpy(), conv.weight.detach().float().cpu().numpy(),
                        conv.bias.detach().float().cpu().numpy(), stride=1, neg_slope=1.0, out_fp32=True, device_id=_dev(x))
 
 
 def _up(x):
-    from ..engine import upsample2x_f32
+    from ..ops import upsample2x_f32
     return torch.from_numpy(upsample2x_f32(x.detach().float().cpu().numpy(), device_id=_dev(x))).to(x.device)
 
 
@@ -108,7 +108,7 @@ class myYOLOv3(_NetModel):
         return [p1, p2, p3]
 
     def forward_batch_composed(self, x):
-        from ..engine import head_f32
+        from ..ops import head_f32
         if self.training:
             raise NotImplementedError("yolo355 is an inference engine: call .eval() first")
         with torch.no_grad():

@@ -7,7 +7,7 @@ import numpy as np
 import torch
 
 from . import _ffi, framelist
-from .engine import _overflow_message, _require_gpu
+from ._handle import (Handle, StreamBound, _require_gpu, dev_input, fill_config, float3_pair, i8_layer, raise_overflow, split_dets)
 
 ARCH = {"slim_yolo_v2": _ffi.ARCH_SLIM_V2, "tiny_yolo_v3": _ffi.ARCH_TINY_V3, "yolo_v2": _ffi.ARCH_YOLO_V2,
         "yolo_v3": _ffi.ARCH_YOLO_V3, "yolo_v3_spp": _ffi.ARCH_YOLO_V3_SPP}
@@ -17,14 +17,15 @@ DTYPE = {"int8": _ffi.DT_INT8, "bf16": _ffi.DT_BF16}
 PRED_TAIL = {"slim_yolo_v2": (1,), "tiny_yolo_v3": (2, 1), "yolo_v2": (1,), "yolo_v3": (5, 3, 1), "yolo_v3_spp": (5, 3, 1)}
 
 
-class Net:
+class Net(StreamBound, Handle):
+    _destroy = "y355_net_destroy"
+
     def __init__(self, arch, input_size, num_classes, anchors, conf_thresh=0.01, nms_thresh=0.5,
                  max_batch=1, max_det=0, device=None, dtype="bf16", max_candidates=None, head_route=None):
         """anchors: [[w, h], ...] -- A pairs for slim_yolo_v2 (grid units), 2*A pairs for tiny_yolo_v3
         (pixels; the stride-16 level first, data/config.py:27-31).  max_candidates (default 4096, up to min(anchors per
         image, 65536)): the most anchors of an image that may pass conf_thresh; head_route 1: every image through the NMS route
         for more than 4096 candidates (Y355_NET_OPT_MAX_CANDIDATES / Y355_NET_OPT_HEAD_ROUTE)."""
-        self._h = None
         lib = _ffi.lib()
         self.device = _require_gpu(device)
         self.arch = arch
@@ -36,25 +37,13 @@ class Net:
             raise ValueError("%s needs a multiple of %d anchors" % (arch, nlev))
         self.max_batch = int(max_batch)
         cfg = _ffi.NetConfig()
-        cfg.device_id = self.device.index
         cfg.arch, cfg.dtype = ARCH[arch], DTYPE[dtype]
-        cfg.height, cfg.width = self.input_size
-        cfg.num_classes = self.num_classes
-        cfg.num_anchors = len(self.anchors) // nlev
         if len(self.anchors) > _ffi.MAX_ANCHORS:
             raise ValueError("too many anchors")
-        for i, (w, h) in enumerate(self.anchors):
-            cfg.anchors[2 * i], cfg.anchors[2 * i + 1] = w, h
-        cfg.conf_thresh, cfg.nms_thresh = float(conf_thresh), float(nms_thresh)
-        cfg.max_batch, cfg.max_det = self.max_batch, int(max_det)
-        with torch.cuda.device(self.device):
-            self._stream = torch.cuda.current_stream(self.device)
-            cfg.stream = C.c_void_p(self._stream.cuda_stream)
-            cfg.own_stream = 0
-            h = C.c_void_p()
-            _ffi.check(lib.y355_net_create(C.byref(cfg), C.byref(h)))
-        self._h = h
-        self._lib = lib
+        fill_config(cfg, self.device, self.input_size, self.num_classes, self.anchors, conf_thresh, nms_thresh, self.max_batch, max_det)
+        cfg.num_anchors = len(self.anchors) // nlev       # per level; the anchor array holds every level's
+        self._create(lib, cfg, lib.y355_net_create)
+        h = self._h
         self.max_det = lib.y355_net_max_det(h)
         self.num_anchors_total = lib.y355_net_num_anchors_total(h)
         self.num_layers = lib.y355_net_num_layers(h)
@@ -64,17 +53,6 @@ class Net:
             self.set_max_candidates(max_candidates)
         if head_route is not None:
             self.set_head_route(head_route)
-
-    def close(self):
-        if self._h is not None:
-            self._lib.y355_net_destroy(self._h)
-            self._h = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
     def layer_shape(self, idx):
         s = (C.c_int32 * 4)()
@@ -96,10 +74,7 @@ class Net:
     def load_layer_i8(self, idx, q_w, q_b, e_w, e_b):
         """int8 nets: q_w [cout,cin,k,k] (|q| <= 127, value q / 2^e_w), q_b int32 [cout] (value q / 2^e_b).
         e_w: one exponent, or an array [cout] with one per output channel (prep.quantize_folded(channel_level=True))."""
-        if np.abs(np.asarray(q_w)).max() > 127:
-            raise ValueError("|q_w| > 127")
-        qw = np.ascontiguousarray(q_w, dtype=np.int8)
-        qb = np.ascontiguousarray(q_b, dtype=np.int32)
+        qw, qb = i8_layer(q_w, q_b)
         if np.ndim(e_w) == 0:
             _ffi.check(self._lib.y355_net_load_layer_i8(self._h, idx, qw.ctypes.data, qb.ctypes.data, qw.shape[0], qw.shape[1],
                                                         qw.shape[2], int(e_w), int(e_b)))
@@ -155,35 +130,10 @@ class Net:
         _ffi.check(self._lib.y355_net_set_thresholds(self._h, float(conf_thresh), float(nms_thresh)))
 
     def _dev_input(self, x):
-        if isinstance(x, np.ndarray):
-            x = torch.from_numpy(x)
-        if x.dim() != 4 or x.shape[1] != 3 or list(x.shape[2:]) != self.input_size:
-            raise ValueError("expected [B,3,%d,%d], got %s" % (self.input_size[0], self.input_size[1], tuple(x.shape)))
-        if x.shape[0] > self.max_batch:
-            raise ValueError("batch %d > max_batch %d" % (x.shape[0], self.max_batch))
-        return x.to(device=self.device, dtype=torch.float32).contiguous()
-
-    def _buffers(self, B):
-        if self._out is None:
-            md = self.max_det
-            self._out = (torch.empty((self.max_batch, md, 4), dtype=torch.float32, device=self.device),
-                         torch.empty((self.max_batch, md), dtype=torch.float32, device=self.device),
-                         torch.empty((self.max_batch, md), dtype=torch.int32, device=self.device),
-                         torch.zeros((self.max_batch,), dtype=torch.int32, device=self.device))
-        return self._out
+        return dev_input(x, self.input_size, self.device, self.max_batch)
 
     def forward_device(self, xd, flags=0, out=None):
-        B = xd.shape[0]
-        ob, os_, oc, on = out if out is not None else self._buffers(B)
-        # stream ordering as in engine.Engine: kernels run on the stream current at construction
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:
-            self._stream.wait_stream(cur)
-        _ffi.check(self._lib.y355_net_forward(self._h, xd.data_ptr(), B, int(flags), ob.data_ptr(), os_.data_ptr(),
-                                              oc.data_ptr(), on.data_ptr()))
-        if cur != self._stream:
-            cur.wait_stream(self._stream)
-        return ob, os_, oc, on
+        return self._launch(self._lib.y355_net_forward, (xd.data_ptr(),), xd.shape[0], flags, out)
 
     def forward(self, x, tap=False, sizes_wh=None):
         """list of (bboxes [n,4], scores [n], cls_inds int64 [n]) per image, anchor-index order.
@@ -197,12 +147,10 @@ class Net:
         ob, os_, oc, on = out
         if sizes_wh is not None:
             self.scale_boxes(ob, on, sizes_wh, B)
-        n = on[:B].cpu().numpy()
+        n = on[:B].cpu()                                  # synchronises: the flag below is this forward's
         if self.overflow():
-            raise _ffi.Y355Error(-1, _overflow_message(self.max_candidates))
-        boxes, scores, cls = ob[:B].cpu().numpy(), os_[:B].cpu().numpy(), oc[:B].cpu().numpy()
-        return [(boxes[i, :n[i]].copy(), scores[i, :n[i]].copy(), cls[i, :n[i]].astype(np.int64))
-                for i in range(B)]
+            raise_overflow(self.max_candidates)
+        return split_dets(ob, os_, oc, n, B)
 
     @staticmethod
     def check_frames(frames):
@@ -225,15 +173,6 @@ class Net:
             raise ValueError("batch %d > max_batch %d" % (frames.shape[0], self.max_batch))
         return frames.to(self.device).contiguous()
 
-    def _call(self, fn, *args):
-        # stream ordering as forward_device
-        cur = torch.cuda.current_stream(self.device)
-        if cur != self._stream:
-            self._stream.wait_stream(cur)
-        _ffi.check(fn(self._h, *args))
-        if cur != self._stream:
-            cur.wait_stream(self._stream)
-
     def forward_frames_device(self, frames, flags=0, out=None):
         """Asynchronous batched forward on camera frames: CUDA uint8 [B,h,w,3] BGR of any size (y355_net_forward_u8:
         BaseTransform's resize, normalisation, BGR->RGB and HWC->CHW inside the op that reads the network input).
@@ -245,10 +184,7 @@ class Net:
         B, hh, ww = (int(v) for v in frames.shape[:3])
         if B > self.max_batch:
             raise ValueError("batch %d > max_batch %d" % (B, self.max_batch))
-        ob, os_, oc, on = out if out is not None else self._buffers(B)
-        self._call(self._lib.y355_net_forward_u8, frames.data_ptr(), hh, ww, B, int(flags), ob.data_ptr(), os_.data_ptr(),
-                   oc.data_ptr(), on.data_ptr())
-        return ob, os_, oc, on
+        return self._launch(self._lib.y355_net_forward_u8, (frames.data_ptr(), hh, ww), B, flags, out)
 
     def forward_frames(self, frames, tap=False, sizes_wh=None):
         """frames: uint8 [B,h,w,3] BGR (numpy or torch, any size).  Same return as forward() on
@@ -271,33 +207,19 @@ class Net:
     check_frame_list = staticmethod(framelist.check_frame_list)
     pack_frames = staticmethod(framelist.pack_frames)
 
-    def _frame_list(self, frames):
-        """(y355_frame array, B, sizes) of framelist.frame_list on the net's stream.  Every tensor the launch reads is held
-        until this handle's next list call."""
-        arr, B, sizes, self._held_frames = framelist.frame_list(frames, self.max_batch, self.device, self._stream)
-        return arr, B, sizes
-
     def forward_frame_list_device(self, frames, flags=0, out=None):
         """Asynchronous forward on a list of camera frames, uint8 [h,w,3] BGR each of its own size: numpy, CPU torch and
         CUDA torch frames may be mixed (y355_net_forward_frames).  Returns the device tensors of forward_device."""
         arr, B, _ = self._frame_list(frames)
-        ob, os_, oc, on = out if out is not None else self._buffers(B)
-        self._call(self._lib.y355_net_forward_frames, arr, B, int(flags), ob.data_ptr(), os_.data_ptr(), oc.data_ptr(),
-                   on.data_ptr())
-        return ob, os_, oc, on
+        return self._launch(self._lib.y355_net_forward_frames, (arr,), B, flags, out)
 
     def forward_frame_list(self, frames, tap=False, sizes_wh=None):
         """Element i equals forward_frames(frames[i][None])[0], bit for bit.  sizes_wh: as forward(), or "own": every
         image's boxes rescaled by its own (width, height) -- the evaluators' `bboxes *= [[w, h, w, h]]` on the GPU."""
-        if isinstance(sizes_wh, str) and sizes_wh != "own":
-            raise ValueError('sizes_wh: an array [B,2] or "own", got %r' % (sizes_wh,))
-        arr, B, sizes = self._frame_list(frames)
-        ob, os_, oc, on = self._buffers(B)
-        self._call(self._lib.y355_net_forward_frames, arr, B, _ffi.F_TAP if tap else 0, ob.data_ptr(), os_.data_ptr(),
-                   oc.data_ptr(), on.data_ptr())
+        framelist.check_sizes_wh(sizes_wh)
         if isinstance(sizes_wh, str):
-            sizes_wh = framelist.own_sizes_wh(sizes)
-        return self._collect(B, (ob, os_, oc, on), sizes_wh)
+            sizes_wh = framelist.own_sizes_wh(framelist.check_frame_list(frames))
+        return self._collect(len(frames), self.forward_frame_list_device(frames, _ffi.F_TAP if tap else 0), sizes_wh)
 
     def resize_frame_list(self, frames):
         """cv2.resize(image, (W, H)) of BaseTransform for every frame of a list on the GPU (the stage in front of the
@@ -315,17 +237,12 @@ class Net:
 
     def set_normalization(self, mean_bgr, std_bgr):
         """BaseTransform constants of the frame input, in the reference's BGR order."""
-        m = (C.c_float * 3)(*[float(v) for v in mean_bgr])
-        sd = (C.c_float * 3)(*[float(v) for v in std_bgr])
-        _ffi.check(self._lib.y355_net_set_normalization(self._h, m, sd))
+        _ffi.check(self._lib.y355_net_set_normalization(self._h, *float3_pair(mean_bgr, std_bgr)))
 
     def scale_boxes(self, boxes, count, sizes_wh, batch=None):
         """In place on a forward's device outputs: boxes[b, :count[b]] *= [w, h, w, h] with sizes_wh [B,2] (width, height)."""
-        wh = torch.as_tensor(np.asarray(sizes_wh, np.float32).reshape(-1, 2)).to(self.device)
-        B = wh.shape[0] if batch is None else int(batch)
-        if wh.shape[0] != B:
-            raise ValueError("sizes_wh has %d rows for a batch of %d" % (wh.shape[0], B))
-        self._call(self._lib.y355_net_scale_boxes, boxes.data_ptr(), count.data_ptr(), wh.data_ptr(), B)
+        wh = framelist.wh_tensor(sizes_wh, None if batch is None else int(batch), self.device)
+        self._call(self._lib.y355_net_scale_boxes, boxes.data_ptr(), count.data_ptr(), wh.data_ptr(), wh.shape[0])
 
     def overflow(self):
         """True if a forward since the last call dropped candidates (heads with more than 4096 anchors per image)."""

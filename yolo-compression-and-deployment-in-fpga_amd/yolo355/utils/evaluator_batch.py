@@ -19,6 +19,7 @@ import numpy as np
 import torch
 
 from .. import _ffi
+from .._handle import raise_overflow
 
 
 def _batches(n, bs):
@@ -255,10 +256,9 @@ def voc_map(net, dataset, num_classes, ground_truth, batch_size=64, quantization
         out = []            # (pipeline, ticket, token) of the batch before: its overflow flag is read one batch late, and the token
                             # keeps what the ticket's launches read (the sizes scale_boxes multiplies by) alive until then
         def settle():
-            from ..engine import _overflow_message
             for pipe, t, _ in out:
                 if pipe.overflow(t):                        # as Pipeline.fetch reports it
-                    raise _ffi.Y355Error(-1, _overflow_message(pipe.max_candidates))
+                    raise_overflow(pipe.max_candidates)
             del out[:]
         for i0, i1 in _batches(n, batch_size):
             ims, sizes = [], []

@@ -107,7 +107,7 @@ class _FusedBase(nn.Module):
     leaky = True
 
     def forward(self, x):
-        from ..engine import ConvOp, conv3x3_i8_raw, conv_geom_i8_raw
+        from ..ops import ConvOp, conv3x3_i8_raw, conv_geom_i8_raw
         conv = self.convs[0]
         g = conv_geometry(conv)                           # raises for what no kernel runs
         if _runs_i8_kernels(conv):
@@ -158,7 +158,7 @@ def folded_f32(convs):
 def _conv_bn_act_forward(convs, x, residual=None):
     """Eval-mode forward of nn.Sequential(conv, [BatchNorm2d], [LeakyReLU | ReLU]) through y355_conv2d_bf16 (the geometries
     it runs) or y355_conv2d_geom_bf16 (every other one conv_geometry accepts)."""
-    from ..engine import conv2d_bf16, conv2d_geom_bf16
+    from ..ops import conv2d_bf16, conv2d_geom_bf16
     conv = convs[0]
     g = conv_geometry(conv)                               # raises for what no kernel runs
     if _runs_bf16_kernels(conv):
@@ -172,7 +172,7 @@ def _conv_bn_act_forward(convs, x, residual=None):
         elif isinstance(m, nn.ReLU):
             slope = 0.0
     if x.is_cuda:                                         # device-resident: weights packed once, the tensor never leaves the GPU
-        from ..engine import ConvOp
+        from ..ops import ConvOp
         key = ("bf16", x.device.index) if g is None else ("bf16", x.device.index, g.astuple())
         op = _cached_op(convs, key, convs,
                         lambda: ConvOp.bf16(*folded_f32(convs), stride=conv.stride[0], neg_slope=slope, device=x.device, geom=g))
@@ -238,7 +238,7 @@ class reorg_layer(nn.Module):
         self.stride = stride
 
     def forward(self, x):
-        from ..engine import reorg_f32, reorg_f32_dev
+        from ..ops import reorg_f32, reorg_f32_dev
         if x.is_cuda:
             return reorg_f32_dev(x, self.stride)
         y = reorg_f32(x.detach().float().cpu().numpy(), self.stride, device_id=x.device.index if x.is_cuda and x.device.index is not None else 0)
@@ -250,7 +250,7 @@ class SPP(nn.Module):
     Runs y355_spp_f32: bit-exact."""
 
     def forward(self, x):
-        from ..engine import spp_f32, spp_f32_dev
+        from ..ops import spp_f32, spp_f32_dev
         if x.is_cuda:
             return spp_f32_dev(x)
         y = spp_f32(x.detach().float().cpu().numpy(), device_id=x.device.index if x.is_cuda and x.device.index is not None else 0)

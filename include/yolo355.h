@@ -719,7 +719,7 @@ int y355_net_num_timers(y355_net *h);          /* ops + head decode + NMS */
 int y355_net_profile_get(y355_net *h, float *ms);
 
 /* ------------------------------------------------------------------------------------------
- * y355_apeval: VOC mAP of a whole dataset run, on the GPU, from detections that never leave it (csrc/apeval.hip).  Replaces
+ * y355_apeval: VOC mAP (and, further down, COCO AP) of a whole dataset run, on the GPU, from detections that never leave it (csrc/apeval.hip).  Replaces
  * what follows the evaluators' loops: write_voc_results_file + voc_eval + voc_ap (utils/vocapi_evaluator_mask.py:140-336,
  * utils/vocapi_evaluator.py alike).  Per class, voc_eval's semantics in every detail:
  *   quantisation  Y355_AP_Q_VOCFILE (what the reference scores: the values it wrote to the results file):
@@ -774,6 +774,46 @@ int y355_apeval_reset(y355_apeval *e);
 int y355_apeval_compute(y355_apeval *e, double ovthresh, int metric, int quantize, double *ap, int32_t *npos, int64_t *ndet,
                         double *mean_ap);
 int y355_apeval_curve(y355_apeval *e, int cls, int64_t capacity, double *rec, double *prec, uint8_t *flag, int64_t *n);
+
+/* COCO bbox AP of the same store (csrc/cocoeval.hip): COCOeval(cocoGt, cocoGt.loadRes(data_dict), 'bbox') with evaluate(),
+ * accumulate() and summarize(), i.e. what follows the loop of utils/cocoapi_evaluator.py:53-126, in float64 and in pycocotools'
+ * operation order (DESIGN.md section 6c has the contract point by point):
+ *   detections    the stored float32 x1 y1 x2 y2 and score, never quantised: x = x1, y = y1, w = double(x2) - double(x1),
+ *                 h = double(y2) - double(y1), area = w * h; the right edge is x + w
+ *   images        evaluated in ascending image id: image_rank[i] = the place of image index i in that order
+ *   groups        per (image, category): detections stable-sorted by score descending (ties keep list position), the first
+ *                 max_dets[M - 1] kept; IoU = maskApi.c's bbIou (a crowd box divides by the detection's area alone)
+ *   match         per area range (both ends inclusive; a box is ignored when it is crowd or its area is outside) and per
+ *                 threshold, greedily in score order: the free kept box of the largest IoU >= min(t, 1 - 1e-10), of equal ones
+ *                 the later; only without one, an ignored box by the same rule, crowd boxes being free however often they were
+ *                 taken.  An unmatched detection whose area is outside the range is ignored too.
+ *   accumulate    per (category, area range, budget): every image's first max_dets[m] detections, images in rank order,
+ *                 stable-sorted by score descending; tp / fp sums over the detections not ignored, rc = tp / npig,
+ *                 pr = tp / (fp + tp + DBL_EPSILON), the envelope from the right, precision[t][r] = pr at the first entry with
+ *                 rc >= rec_thrs[r], or 0; recall[t] = the last rc, or 0 without detections; all -1 when npig = 0
+ * The limits, checked before any HIP call: T 1..16, R 1..1024, A 1..8, M 1..8, max_dets ascending and 1..2^20.
+ *   set_gt_coco   the ground truth of the whole image list, host pointers, CSR by image like set_gt: boxes_xywh [n][4] and
+ *                 area [n] in float64 (area is the annotation's own field), cls [n] in 0..num_classes - 1, iscrowd [n],
+ *                 image_rank [num_images] a permutation of 0..num_images - 1 (a rank twice -- duplicate image ids -- is
+ *                 Y355_EINVAL) or NULL = the identity.  Independent of set_gt: one handle may hold either or both.  Synchronous;
+ *                 may be called again (the detections stay: the ranks are read by compute_coco alone).
+ *   compute_coco  synchronous.  iou_thrs [T], rec_thrs [R], area_rng [A][2], max_dets [M]; precision [T][R][K][A][M] and
+ *                 recall [T][K][A][M] (K = num_classes), the layout of COCOeval.eval.  stats [12] or NULL: summarize()'s twelve
+ *                 numbers (AP, AP50, AP75, AP small / medium / large, AR at max_dets 0 / 1 / 2, AR small / medium / large), each
+ *                 the in-order sum of the selected entries > -1 divided by their count, or -1 without any; filled only for the
+ *                 default parameter shape T = 10, R = 101, A = 4, M = 3 (threshold 0 is AP50's, threshold 5 AP75's).
+ *                 Y355_ERANGE and Y355_ENOTREADY as compute.
+ *   coco_matches  parity tap of the last successful compute_coco: the group (image index, cls) under area range area_index.
+ *                 *num_d = the detections kept, *num_g = the group's boxes; when num_d <= cap_d and num_g <= cap_g also (each
+ *                 may be NULL) det_pos [cap_d] = the detections' positions in the image's list, in score order; dt_match
+ *                 [T][cap_d] = the matched box as its index among the group's boxes in annotation order, or -1; dt_ignore
+ *                 [T][cap_d]; gt_marked [T][cap_g] = the boxes taken.  Y355_ENOTREADY after an add or a reset. */
+int y355_apeval_set_gt_coco(y355_apeval *e, const int32_t *offsets, const double *boxes_xywh, const double *area, const int32_t *cls,
+                            const uint8_t *iscrowd, const int32_t *image_rank);
+int y355_apeval_compute_coco(y355_apeval *e, const double *iou_thrs, int T, const double *rec_thrs, int R, const double *area_rng, int A,
+                             const int32_t *max_dets, int M, double *precision, double *recall, double *stats);
+int y355_apeval_coco_matches(y355_apeval *e, int image, int cls, int area_index, int64_t cap_d, int64_t cap_g, int64_t *num_d,
+                             int64_t *num_g, int32_t *det_pos, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_marked);
 
 #ifdef __cplusplus
 }

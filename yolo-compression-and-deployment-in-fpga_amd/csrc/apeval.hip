@@ -11,8 +11,9 @@
 //            (the first detection in rank order that matches a box is its true positive, every later one a false positive)
 //   score    one workgroup per class: inclusive scans of the flags, rec / prec, the reverse running maximum, the eleven thresholds
 //            or the envelope sum
-#include "../../include/yolo355.h"
-#include "y355_common.h"
+// The handle, the sort's entry points (ap_keys / ap_sort / ap_class_bounds) and the workgroup scans are in apeval_shared.h:
+// cocoeval.hip scores the same store the COCO way.
+#include "apeval_shared.h"
 
 #include <cfloat>
 #include <cmath>
@@ -20,69 +21,7 @@
 #include <string>
 #include <vector>
 
-int y355_fail(int code, const std::string &msg);
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
-#define AP_POS_BITS 20            // position of a detection in its image's list: max_det <= 2^20
-#define AP_TILE 1024              // keys per workgroup of a sort pass: 4 waves x 4 rounds x 64
-#define AP_SCORE_THREADS 1024
-
-struct y355_apeval {
-    int device = 0, C = 0, num_images = 0;
-    long long cap = 0;
-    hipStream_t s = nullptr;
-    hipEvent_t ev = nullptr;
-    // ground truth, CSR by image
-    bool have_gt = false;
-    long long n_gt = 0;
-    int *gt_off = nullptr;
-    float *gt_box = nullptr;
-    int *gt_cls = nullptr;
-    uint8_t *gt_diff = nullptr;
-    unsigned int *gt_first = nullptr;     // [n_gt] smallest rank that matched the box
-    std::vector<int32_t> npos;
-    // the store
-    unsigned long long *ctr = nullptr;    // [0] detections offered, [1] of them with a class outside [0, C); [2..7] OR / AND of the keys
-    unsigned long long *d_imgpos = nullptr;
-    uint8_t *d_cls = nullptr;
-    float *d_score = nullptr;
-    float *d_box = nullptr;
-    // compute workspace
-    unsigned long long *khi = nullptr;
-    unsigned int *perm[2] = {nullptr, nullptr};
-    unsigned int *hist = nullptr;         // [256][tiles]
-    unsigned int *dtot = nullptr;         // [256] keys per digit of the pass at hand
-    int *jm = nullptr;
-    uint8_t *flag = nullptr;
-    double *rec = nullptr, *prec = nullptr;
-    long long *start = nullptr;           // [C + 1]
-    double *ap = nullptr;                 // [C]
-    // staging of add_host
-    void *stage = nullptr;
-    size_t stage_bytes = 0;
-    // last compute
-    bool have_curve = false;
-    int cur = 0;
-    std::vector<long long> h_start;
-};
-
 namespace {
-__device__ __forceinline__ unsigned long long wave_or(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v |= (unsigned long long)__shfl_xor((long long)v, o, 64);
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_and(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v &= (unsigned long long)__shfl_xor((long long)v, o, 64);
-    return v;
-}
-
 // ---- append: one workgroup per image of the batch
 __global__ void __launch_bounds__(256) ap_append_kernel(const float *boxes, const float *scores, const int *cls, const int *count, int first_image,
                                                         int max_det, int C, long long cap, unsigned long long *ctr, unsigned long long *imgpos,
@@ -127,8 +66,10 @@ __device__ __forceinline__ double ap_coord_q(float v, int quantize) {
 }
 
 // ---- keys: khi ascending = score_q descending (NaN last, as np.argsort(-confidence) places it); OR / AND of every key word
+// with rank: the word that is sorted (and reduced) is w0[i] = rank[image] << AP_POS_BITS | position instead of the store's own
 __global__ void __launch_bounds__(256) ap_keys_kernel(long long n, int quantize, const float *sscore, const unsigned long long *imgpos,
-                                                      const uint8_t *scls, unsigned long long *khi, unsigned int *perm, unsigned long long *ctr) {
+                                                      const uint8_t *scls, unsigned long long *khi, unsigned int *perm, unsigned long long *ctr,
+                                                      const int *rank, unsigned long long *w0) {
     unsigned long long lo_or = 0, lo_and = ~0ull, hi_or = 0, hi_and = ~0ull, c_or = 0, c_and = ~0ull;
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         const double q = ap_score_q(sscore[i], quantize) + 0.0;           // -0.0 -> +0.0: equal scores, equal keys
@@ -141,7 +82,12 @@ __global__ void __launch_bounds__(256) ap_keys_kernel(long long n, int quantize,
         }
         khi[i] = k;
         perm[i] = (unsigned int)i;
-        const unsigned long long ip = imgpos[i], cc = scls[i];
+        unsigned long long ip = imgpos[i];
+        if (rank) {
+            ip = ((unsigned long long)rank[ip >> AP_POS_BITS] << AP_POS_BITS) | (ip & ((1ull << AP_POS_BITS) - 1));
+            w0[i] = ip;
+        }
+        const unsigned long long cc = scls[i];
         lo_or |= ip, lo_and &= ip, hi_or |= k, hi_and &= k, c_or |= cc, c_and &= cc;
     }
     lo_or = wave_or(lo_or), hi_or = wave_or(hi_or), c_or = wave_or(c_or);
@@ -153,15 +99,15 @@ __global__ void __launch_bounds__(256) ap_keys_kernel(long long n, int quantize,
     }
 }
 
-// digit `pass` of the key of store entry e: bytes 0..7 of image / position, 8..15 of the score key, 16 the class
-__device__ __forceinline__ unsigned int ap_digit(int pass, unsigned int e, const unsigned long long *imgpos, const unsigned long long *khi,
+// the digit `pass` (ApPass) of the key of store entry e
+__device__ __forceinline__ unsigned int ap_digit(ApPass pass, unsigned int e, const unsigned long long *imgpos, const unsigned long long *khi,
                                                  const uint8_t *scls) {
-    if (pass < 8) return (unsigned int)(imgpos[e] >> (8 * pass)) & 255u;
-    if (pass < 16) return (unsigned int)(khi[e] >> (8 * (pass - 8))) & 255u;
+    if (pass.src == 0) return (unsigned int)(imgpos[e] >> pass.shift) & pass.mask;
+    if (pass.src == 1) return (unsigned int)(khi[e] >> pass.shift) & pass.mask;
     return scls[e];
 }
 
-__global__ void __launch_bounds__(256) ap_hist_kernel(long long n, int pass, int tiles, const unsigned int *perm, const unsigned long long *imgpos,
+__global__ void __launch_bounds__(256) ap_hist_kernel(long long n, ApPass pass, int tiles, const unsigned int *perm, const unsigned long long *imgpos,
                                                       const unsigned long long *khi, const uint8_t *scls, unsigned int *hist) {
     __shared__ unsigned int h[256];
     h[threadIdx.x] = 0;
@@ -208,7 +154,7 @@ __global__ void __launch_bounds__(256) ap_scan_kernel(unsigned int *hist, int ti
 }
 
 // stable scatter of one tile: wave w owns keys [256 w, 256 w + 256) of the tile and walks them 64 at a time in order
-__global__ void __launch_bounds__(256) ap_scatter_kernel(long long n, int pass, int tiles, const unsigned int *perm_in, unsigned int *perm_out,
+__global__ void __launch_bounds__(256) ap_scatter_kernel(long long n, ApPass pass, int tiles, const unsigned int *perm_in, unsigned int *perm_out,
                                                          const unsigned long long *imgpos, const unsigned long long *khi, const uint8_t *scls,
                                                          const unsigned int *hist, const unsigned int *tot) {
     __shared__ unsigned int wcnt[4][256];
@@ -324,44 +270,6 @@ __global__ void __launch_bounds__(256) ap_flag_kernel(long long n, const int *jm
     flag[r] = j == -2 ? 0 : j == -1 ? 2 : gt_first[j] == (unsigned int)r ? 1 : 2;
 }
 
-// inclusive scan over the workgroup; sh: one slot per wave
-__device__ __forceinline__ unsigned long long block_scan_add(unsigned long long v, unsigned long long *sh, unsigned long long *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long u = (unsigned long long)__shfl_up((long long)v, o, 64);
-        if (lane >= o) v += u;
-    }
-    __syncthreads();
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    unsigned long long off = 0, all = 0;
-    for (int k = 0; k < AP_SCORE_THREADS / 64; ++k) {
-        if (k < w) off += sh[k];
-        all += sh[k];
-    }
-    *total = all;
-    return v + off;
-}
-__device__ __forceinline__ double block_scan_max(double v, double *sh, double *total) {
-    const int lane = threadIdx.x & 63, w = threadIdx.x >> 6;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const double u = __shfl_up(v, o, 64);
-        if (lane >= o) v = fmax(v, u);
-    }
-    __syncthreads();
-    if (lane == 63) sh[w] = v;
-    __syncthreads();
-    double off = 0.0, all = 0.0;          // precisions are >= 0
-    for (int k = 0; k < AP_SCORE_THREADS / 64; ++k) {
-        if (k < w) off = fmax(off, sh[k]);
-        all = fmax(all, sh[k]);
-    }
-    *total = all;
-    return fmax(v, off);
-}
-
 // one workgroup per class: curve (rec, prec in rank order) and AP
 __global__ void __launch_bounds__(AP_SCORE_THREADS) ap_score_kernel(int metric, const long long *start, const int *npos, const uint8_t *flag,
                                                                     double *rec, double *prec, double *ap) {
@@ -449,14 +357,6 @@ __global__ void __launch_bounds__(AP_SCORE_THREADS) ap_score_kernel(int metric, 
     }
 }
 
-template <typename T> int ap_alloc(T **p, size_t count) {
-    HIPCHK(hipMalloc((void **)p, (count ? count : 1) * sizeof(T)));
-    return 0;
-}
-int ap_enter(y355_apeval *e) {
-    HIPCHK(hipSetDevice(e->device));
-    return 0;
-}
 int ap_check_add(y355_apeval *e, int first_image, int batch, int max_det, const void *a, const void *b, const void *c, const void *d) {
     if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
     if (!a || !b || !c || !d) return y355_fail(Y355_EINVAL, "null detection buffer");
@@ -471,6 +371,53 @@ void ap_launch_append(y355_apeval *e, int first_image, int batch, int max_det, c
                        e->d_imgpos, e->d_cls, e->d_score, e->d_box);
 }
 }  // namespace
+
+int ap_store_count(y355_apeval *e, long long *n) {
+    unsigned long long h[2];
+    HIPCHK(hipStreamSynchronize(e->s));
+    HIPCHK(hipMemcpy(h, e->ctr, sizeof h, hipMemcpyDeviceToHost));
+    if (h[1]) return y355_fail(Y355_ERANGE, std::to_string(h[1]) + " detections carry a class index outside 0 .. " + std::to_string(e->C - 1));
+    if (h[0] > (unsigned long long)e->cap)
+        return y355_fail(Y355_ERANGE, std::to_string(h[0]) + " detections were added, the store holds max_dets = " + std::to_string(e->cap));
+    *n = (long long)h[0];
+    return 0;
+}
+
+int ap_keys(y355_apeval *e, long long n, int quantize, const int *rank, unsigned long long *w0_out, unsigned long long h[8]) {
+    hipStream_t s = e->s;
+    const unsigned long long init[6] = {0, ~0ull, 0, ~0ull, 0, ~0ull};
+    HIPCHK(hipMemcpyAsync(e->ctr + 2, init, sizeof init, hipMemcpyHostToDevice, s));
+    const int nb = (int)((n + 255) / 256);
+    hipLaunchKernelGGL(ap_keys_kernel, dim3(nb < 256 ? nb : 256), dim3(256), 0, s, n, quantize, e->d_score, e->d_imgpos, e->d_cls, e->khi, e->perm[0],
+                       e->ctr, rank, w0_out);
+    HIPCHK(hipMemcpyAsync(h, e->ctr, 8 * sizeof(unsigned long long), hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    e->cur = 0;
+    return 0;
+}
+
+int ap_sort(y355_apeval *e, long long n, const unsigned long long *w0, const unsigned long long h[8], const ApPass *passes, int np) {
+    hipStream_t s = e->s;
+    const int tiles = (int)((n + AP_TILE - 1) / AP_TILE);
+    int cur = e->cur;
+    for (int p = 0; p < np; ++p) {                        // a digit every key shares moves nothing
+        const ApPass pass = passes[p];
+        const unsigned long long diff = (h[2 + 2 * pass.src] ^ h[3 + 2 * pass.src]) >> pass.shift;
+        if (!(diff & pass.mask)) continue;
+        hipLaunchKernelGGL(ap_hist_kernel, dim3(tiles), dim3(256), 0, s, n, pass, tiles, e->perm[cur], w0, e->khi, e->d_cls, e->hist);
+        hipLaunchKernelGGL(ap_scan_kernel, dim3(256), dim3(256), 0, s, e->hist, tiles, e->dtot);
+        hipLaunchKernelGGL(ap_scatter_kernel, dim3(tiles), dim3(256), 0, s, n, pass, tiles, e->perm[cur], e->perm[cur ^ 1], w0, e->khi, e->d_cls,
+                           e->hist, e->dtot);
+        cur ^= 1;
+    }
+    e->cur = cur;
+    HIPCHK(hipGetLastError());
+    return 0;
+}
+
+void ap_class_bounds(y355_apeval *e, long long n) {
+    hipLaunchKernelGGL(ap_bounds_kernel, dim3((int)((n + 256) / 256)), dim3(256), 0, e->s, n, e->C, e->perm[e->cur], e->d_cls, e->start);
+}
 
 extern "C" {
 
@@ -520,6 +467,7 @@ void y355_apeval_destroy(y355_apeval *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->s) (void)hipStreamSynchronize(e->s);
+    y355_coco_destroy(e);
     void *bufs[] = {e->gt_off, e->gt_box, e->gt_cls, e->gt_diff, e->gt_first, e->ctr, e->d_imgpos, e->d_cls, e->d_score, e->d_box, e->khi,
                     e->perm[0], e->perm[1], e->hist, e->dtot, e->jm, e->flag, e->rec, e->prec, e->start, e->ap, e->stage};
     for (void *p : bufs)
@@ -567,6 +515,7 @@ int y355_apeval_add(y355_apeval *e, int first_image, int batch, int max_det, con
     if (int rc = ap_check_add(e, first_image, batch, max_det, boxes_dev, scores_dev, cls_dev, count_dev)) return rc;
     if (ap_enter(e)) return Y355_EHIP;
     e->have_curve = false;
+    y355_coco_invalidate(e);
     if (!after_stream) {
         ap_launch_append(e, first_image, batch, max_det, boxes_dev, scores_dev, cls_dev, count_dev, e->s);
         HIPCHK(hipGetLastError());
@@ -587,6 +536,7 @@ int y355_apeval_add_host(y355_apeval *e, int first_image, int batch, int max_det
     if (int rc = ap_check_add(e, first_image, batch, max_det, boxes, scores, cls, count)) return rc;
     if (ap_enter(e)) return Y355_EHIP;
     e->have_curve = false;
+    y355_coco_invalidate(e);
     const size_t m = (size_t)batch * max_det, need = m * 24 + (size_t)batch * 4;
     if (need > e->stage_bytes) {
         HIPCHK(hipStreamSynchronize(e->s));
@@ -612,6 +562,7 @@ int y355_apeval_reset(y355_apeval *e) {
     if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
     if (ap_enter(e)) return Y355_EHIP;
     e->have_curve = false;
+    y355_coco_invalidate(e);
     HIPCHK(hipMemsetAsync(e->ctr, 0, 8 * sizeof(unsigned long long), e->s));      // behind every append so far
     HIPCHK(hipStreamSynchronize(e->s));
     return 0;
@@ -627,35 +578,19 @@ int y355_apeval_compute(y355_apeval *e, double ovthresh, int metric, int quantiz
     if (ap_enter(e)) return Y355_EHIP;
     e->have_curve = false;
     hipStream_t s = e->s;
-    unsigned long long h[8];
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemcpy(h, e->ctr, 2 * sizeof(unsigned long long), hipMemcpyDeviceToHost));
-    if (h[1]) return y355_fail(Y355_ERANGE, std::to_string(h[1]) + " detections carry a class index outside 0 .. " + std::to_string(e->C - 1));
-    if (h[0] > (unsigned long long)e->cap)
-        return y355_fail(Y355_ERANGE, std::to_string(h[0]) + " detections were added, the store holds max_dets = " + std::to_string(e->cap));
-    const long long n = (long long)h[0];
+    long long n = 0;
+    if (int rc = ap_store_count(e, &n)) return rc;
     const int C = e->C;
     const int q = quantize == Y355_AP_Q_VOCFILE;          // the kernels' flag: 1 = round as the results file does
     e->h_start.assign(C + 1, 0);
     if (n > 0) {
-        const unsigned long long init[6] = {0, ~0ull, 0, ~0ull, 0, ~0ull};
-        HIPCHK(hipMemcpyAsync(e->ctr + 2, init, sizeof init, hipMemcpyHostToDevice, s));
-        const int nb = (int)((n + 255) / 256), tiles = (int)((n + AP_TILE - 1) / AP_TILE);
-        hipLaunchKernelGGL(ap_keys_kernel, dim3(nb < 256 ? nb : 256), dim3(256), 0, s, n, q, e->d_score, e->d_imgpos, e->d_cls, e->khi, e->perm[0], e->ctr);
-        HIPCHK(hipMemcpyAsync(h, e->ctr, sizeof h, hipMemcpyDeviceToHost, s));
-        HIPCHK(hipStreamSynchronize(s));
-        int cur = 0;
-        for (int pass = 0; pass < 17; ++pass) {       // a digit every key shares moves nothing
-            const unsigned long long diff = pass < 8 ? (h[2] ^ h[3]) >> (8 * pass) : pass < 16 ? (h[4] ^ h[5]) >> (8 * (pass - 8)) : h[6] ^ h[7];
-            if (!(diff & 255)) continue;
-            hipLaunchKernelGGL(ap_hist_kernel, dim3(tiles), dim3(256), 0, s, n, pass, tiles, e->perm[cur], e->d_imgpos, e->khi, e->d_cls, e->hist);
-            hipLaunchKernelGGL(ap_scan_kernel, dim3(256), dim3(256), 0, s, e->hist, tiles, e->dtot);
-            hipLaunchKernelGGL(ap_scatter_kernel, dim3(tiles), dim3(256), 0, s, n, pass, tiles, e->perm[cur], e->perm[cur ^ 1], e->d_imgpos, e->khi,
-                               e->d_cls, e->hist, e->dtot);
-            cur ^= 1;
-        }
-        e->cur = cur;
-        hipLaunchKernelGGL(ap_bounds_kernel, dim3((int)((n + 256) / 256)), dim3(256), 0, s, n, C, e->perm[cur], e->d_cls, e->start);
+        unsigned long long h[8];
+        if (int rc = ap_keys(e, n, q, nullptr, nullptr, h)) return rc;
+        ApPass passes[17];                                // image / position bytes, score-key bytes, the class
+        for (int p = 0; p < 17; ++p) passes[p] = ApPass{p < 8 ? 0 : p < 16 ? 1 : 2, p < 16 ? 8 * (p & 7) : 0, 255u};
+        if (int rc = ap_sort(e, n, e->d_imgpos, h, passes, 17)) return rc;
+        const int nb = (int)((n + 255) / 256), cur = e->cur;
+        ap_class_bounds(e, n);
         if (e->n_gt > 0) HIPCHK(hipMemsetAsync(e->gt_first, 0xff, (size_t)e->n_gt * sizeof(unsigned int), s));
         hipLaunchKernelGGL(ap_match_kernel, dim3(nb), dim3(256), 0, s, n, ovthresh, q, e->perm[cur], e->d_imgpos, e->d_cls, e->d_box, e->gt_off,
                            e->gt_box, e->gt_cls, e->gt_diff, e->gt_first, e->jm);

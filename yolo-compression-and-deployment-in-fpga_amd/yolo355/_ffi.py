@@ -264,6 +264,11 @@ _SIGS = {
     "y355_apeval_reset": (C.c_int, [C.c_void_p]),
     "y355_apeval_compute": (C.c_int, [C.c_void_p, C.c_double, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_double)]),
     "y355_apeval_curve": (C.c_int, [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_void_p, C.c_void_p, P(C.c_int64)]),
+    "y355_apeval_set_gt_coco": (C.c_int, [C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_apeval_compute_coco": (C.c_int, [C.c_void_p, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int,
+                                           C.c_void_p, C.c_void_p, C.c_void_p]),
+    "y355_apeval_coco_matches": (C.c_int, [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int64, C.c_int64, P(C.c_int64), P(C.c_int64),
+                                           C.c_void_p, C.c_void_p, C.c_void_p, C.c_void_p]),
 }
 
 

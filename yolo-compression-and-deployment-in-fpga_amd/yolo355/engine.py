@@ -522,6 +522,23 @@ class Pipeline(Handle):
                 self._scale_ticket(tickets[-1], wh[i0:i0 + self.max_batch])
         return tickets, wh
 
+    def submit_frame_batch(self, frames, sizes_wh=None):
+        """submit_batch for a list of up to depth * max_batch camera frames, each of its own size: its chunks of max_batch
+        through submit_frame_list back to back, each with scale_boxes by its rows of sizes_wh (None, [n,2], or "own").  Returns
+        (tickets, wh)."""
+        framelist.check_sizes_wh(sizes_wh)
+        sizes = framelist.check_frame_list(frames)
+        n = len(frames)
+        if n > self.depth * self.max_batch:
+            raise ValueError("submit_frame_batch takes at most %d frames at a time" % (self.depth * self.max_batch))
+        wh = framelist.sizes_wh_tensor(sizes_wh, sizes, self.device)
+        tickets = []
+        for i0 in range(0, n, self.max_batch):
+            tickets.append(self.submit_frame_list(list(frames[i0:i0 + self.max_batch])))
+            if wh is not None:
+                self._scale_ticket(tickets[-1], wh[i0:i0 + self.max_batch])
+        return tickets, wh
+
     def _record(self, ticket):
         rec = self._tickets.get(ticket % self.depth)
         if rec is None or rec[0] != ticket:

@@ -181,6 +181,15 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         pipe = self._primed(self._get_pipeline(find), sa)
         return (pipe,) + pipe.submit_batch(x, sizes_wh)
 
+    def submit_frame_list(self, frames, quantization=True, find=False, sizes_wh=None):
+        """submit_batch for a list of camera frames, uint8 [h,w,3] BGR each of its own size (forward_frame_list's input);
+        collect_batch(token) gives what forward_frame_list would have returned."""
+        if not quantization or self.trainable:
+            raise NotImplementedError("submit_frame_list runs the int8 path (quantization=True, eval)")
+        sa = self._frozen_exponents()
+        pipe = self._primed(self._get_pipeline(find), sa)
+        return (pipe,) + pipe.submit_frame_batch(frames, sizes_wh)
+
     def collect_batch(self, token):
         pipe, tickets, _ = token
         out = []

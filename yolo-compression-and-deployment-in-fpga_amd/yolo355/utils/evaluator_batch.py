@@ -3,7 +3,7 @@
 boxes on the host.  These helpers produce the same data structures with batched forwards and the rescale on the GPU
 (`forward_batch(..., sizes_wh=...)` -> y355_scale_boxes); the VOC mAP computation that follows them (evaluate_detections:
 write_voc_results_file + voc_eval, :140-341) is `voc_map` / `voc_map_from_all_boxes` below, on the GPU (yolo355.apeval); COCO's
-(pycocotools) is untouched.
+(pycocotools' COCOeval, utils/cocoapi_evaluator.py:100-124) is `coco_map` / `coco_stats_from_data_dict`, on the GPU as well.
 
     # utils/vocapi_evaluator_mask.py:49-95  (evaluate)
     - for i in range(num_images): ... bboxes, scores, cls_inds = net(x, quantization=..., find=...) ...
@@ -286,5 +286,117 @@ def voc_map(net, dataset, num_classes, ground_truth, batch_size=64, quantization
                 ev.add_detections(i0, _run(net, x, sizes, quantization=quantization, find=find))
         settle()
         return ev.compute(use_07_metric=use_07_metric)
+    finally:
+        ev.close()
+
+
+# ---------------------------------------------------------------------------------------------------- COCO AP (yolo355.apeval)
+def coco_ground_truth(annotations, image_ids, class_ids):
+    """The ground truth COCOeval reads from an instances_*.json, as CocoEval takes it: one float64 array per image of rows
+    (cls, x, y, w, h, area, iscrowd), annotations in file order.  annotations: the path of the file or its loaded dict; image_ids:
+    the ids the evaluator's loop returns, in its order; class_ids: dataset.class_ids (class index -> COCO category id);
+    annotations of other categories or other images are skipped."""
+    if not isinstance(annotations, dict):
+        import json
+        with open(annotations) as f:
+            annotations = json.load(f)
+    index = {int(c): k for k, c in enumerate(class_ids)}
+    where = {int(id_): i for i, id_ in enumerate(image_ids)}
+    if len(where) != len(image_ids):
+        raise ValueError("duplicate image ids")
+    rows = [[] for _ in image_ids]
+    for ann in annotations["annotations"]:
+        i, k = where.get(int(ann["image_id"])), index.get(int(ann["category_id"]))
+        if i is None or k is None:
+            continue
+        x, y, w, h = ann["bbox"]
+        rows[i].append([k, x, y, w, h, ann["area"], int(ann.get("iscrowd", 0))])
+    return [np.asarray(r, np.float64).reshape(-1, 7) for r in rows]
+
+
+class CocoStats(tuple):
+    """(stats[0], stats[1]) as COCOAPIEvaluator.evaluate returns them; .stats: all twelve; .precision / .recall: COCOeval.eval's"""
+    stats = precision = recall = None
+
+
+def _coco_result(ev):
+    stats = ev.compute()
+    res = CocoStats((float(stats[0]), float(stats[1])))
+    res.stats, res.precision, res.recall = stats, ev.precision, ev.recall
+    return res
+
+
+def coco_stats_from_data_dict(ids, data_dict, ground_truth, class_ids):
+    """The consumer of what coco_data_dict / coco_data_dict_frames return -- the replacement for cocoGt.loadRes(data_dict) +
+    COCOeval(...).evaluate() / accumulate() / summarize() (utils/cocoapi_evaluator.py:100-124) -> CocoStats.  ground_truth:
+    coco_ground_truth(...) for the same ids in the same order."""
+    from ..apeval import CocoEval
+    index = {int(c): k for k, c in enumerate(class_ids)}
+    where = {int(id_): i for i, id_ in enumerate(ids)}
+    per = [([], [], []) for _ in ids]
+    for d in data_dict:
+        b, s, c = per[where[int(d["image_id"])]]
+        x, y, w, h = d["bbox"]
+        x2, y2 = np.float32(x + w), np.float32(y + h)
+        # CocoEval takes the float32 corners the data_dict was made from ([x1, y1, x2 - x1, y2 - y1] on Python floats)
+        if np.float32(x) != x or np.float32(y) != y or float(x2) - x != w or float(y2) - y != h:
+            raise ValueError("data_dict bbox %r was not built from float32 corners" % (d["bbox"],))
+        b.append([x, y, x2, y2])
+        s.append(d["score"])
+        c.append(index[int(d["category_id"])])
+    ev = CocoEval(len(class_ids), ground_truth, image_ids=list(ids), max_dets=max(1, len(data_dict)))
+    try:
+        for i0, i1 in _batches(len(per), 1024):
+            ev.add_detections(i0, [(np.asarray(b, np.float32).reshape(-1, 4), np.asarray(s, np.float32), np.asarray(c, np.int32))
+                                   for b, s, c in per[i0:i1]])
+        return _coco_result(ev)
+    finally:
+        ev.close()
+
+
+def coco_map(net, dataset, ground_truth, batch_size=64, quantization=False, num_images=None, max_dets=None):
+    """The whole COCOAPIEvaluator.evaluate (utils/cocoapi_evaluator.py:53-126) from the raw images -> CocoStats, i.e.
+    (stats[0], stats[1]) with all twelve in .stats.  A calibrated q_bf model (the rule of _submit) is device-resident end to end:
+    Pipeline.submit -> scale_boxes -> CocoEval.add on the ticket's stream -> release, as voc_map; every other model goes through
+    forward_frame_list(..., sizes_wh="own") and CocoEval.add_detections.  dataset.pull_image(i) -> (img uint8 HWC BGR of any size,
+    id); dataset.class_ids: class index -> COCO id; ground_truth: coco_ground_truth(...) for the same images in the same order."""
+    from ..apeval import CocoEval
+    n = len(dataset) if num_images is None else int(num_images)
+    dev = net.device if isinstance(getattr(net, "device", None), (str, torch.device)) else "cuda:0"
+    ev = CocoEval(len(dataset.class_ids), ground_truth[:n], max_dets=max_dets, device=dev)
+    ids = []                # learnt from the loop, as the reference's; the order of the ids matters to compute() alone
+    try:
+        out = []            # as voc_map: the overflow flag of a ticket is read one batch late, its token kept alive until then
+
+        def settle():
+            for pipe, t, _ in out:
+                if pipe.overflow(t):
+                    raise_overflow(pipe.max_candidates)
+            del out[:]
+        for i0, i1 in _batches(n, batch_size):
+            frames = []
+            for i in range(i0, i1):
+                img, id_ = dataset.pull_image(i)
+                frames.append(img)
+                ids.append(int(id_))
+            if _pipeline_admits(net, i1 - i0, quantization=quantization) and hasattr(net, "submit_frame_list"):
+                token = net.submit_frame_list(frames, quantization=True, find=False, sizes_wh="own")
+                pipe, tickets, wh = token
+                settle()
+                for k, t in enumerate(tickets):
+                    first = i0 + k * pipe.max_batch
+                    st = pipe.stream(t)
+                    ev.add(first, *pipe.outputs(t), after_stream=st, batch=min(i1 - first, pipe.max_batch))
+                    with torch.cuda.stream(st):
+                        pipe.release(t)
+                    if wh is not None:
+                        wh.record_stream(st)
+                    out.append((pipe, t, token))
+            else:
+                settle()
+                ev.add_detections(i0, net.forward_frame_list(frames, sizes_wh="own", quantization=quantization))
+        settle()
+        ev.set_image_ids(ids)
+        return _coco_result(ev)
     finally:
         ev.close()

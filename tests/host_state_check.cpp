@@ -1,9 +1,10 @@
-// Host-only check of the allocation logic in csrc/head_state.hip (HeadState: create, resize's swap and rollback, destroy) and
-// csrc/resize.hip (FrameStage: lazy buffers, the cached same-size table).  Device memory is the host heap here, through a DevMem
-// whose k-th allocation (or whose upload) fails on demand, so the program needs no GPU.  Built with the address and
+// Host-only check of the allocation logic in csrc/head_state.hip (HeadState: create, resize's swap and rollback, destroy),
+// csrc/resize.hip (FrameStage: lazy buffers, the cached same-size table) and csrc/handle_core.h (HandleCore: a create's
+// allocations and its unwinding; not its stream and events, which need a device).  Device memory is the host heap here, through
+// a DevMem whose k-th allocation (or whose upload) fails on demand, so the program needs no GPU.  Built with the address and
 // undefined-behaviour sanitizers by `make -C csrc hostcheck`: a leak, a double free or a use after free ends it non-zero.
 #include "../include/yolo355.h"
-#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/head_nms.h"
+#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/handle_core.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -15,6 +16,7 @@ int y355_fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
+extern "C" const char *y355_last_error(void) { return g_err.c_str(); }
 
 #define CHECK(c)                                                          \
     do {                                                                  \
@@ -164,6 +166,45 @@ void check_stage() {
     f[1].data_dev = nullptr;
     CHECK(y355_frames_check(f, 2, 2) == Y355_EINVAL && g_err == "null frame pointer");
 }
+
+// a create's worth of allocations on a HandleCore (a borrowed null stream: no HIP object is made), as y355_create and
+// y355_net_create make them: layer buffers, then the counter sets, the absmax word and the head
+int core_create(HandleCore &c, int N, bool outs) {
+    int rc = y355_core_open(&c, 0, nullptr, false, 96, 160, 2, N, 0.01f, 0.5f, host_mem());
+    char *layer[6] = {};
+    for (int k = 0; k < 6 && !rc; ++k) rc = y355_core_alloc(&c, &layer[k], (size_t)1000 * k, k % 2 == 0);
+    if (!rc) rc = y355_core_state(&c, 11, 0, outs);
+    if (!rc) rc = y355_stage_need_frames(c.stage);
+    return rc ? y355_core_unwind(rc, [&c] { y355_core_close(&c); }) : 0;
+}
+void check_core(int N, bool outs) {
+    fail_at = -1;
+    n_alloc = 0;
+    {
+        HandleCore c;
+        CHECK(core_create(c, N, outs) == 0 && !c.own_stream && !c.stream && c.ev.empty());
+        CHECK(c.ctrs.base == c.ctr_dev && c.ctrs.n == 11 && c.ctrs.clean[0] && c.ctrs.clean[1] && c.absmax_dev);
+        CHECK(c.allocs.size() == 8 && c.allocs.size() + c.head.allocs.size() + c.stage.allocs.size() == live.size());
+        CHECK(y355_core_range(&c, 0) == Y355_EINVAL && g_err == "batch out of range" && y355_core_range(&c, 3) == Y355_EINVAL);
+        CHECK(y355_core_range(&c, 2, 16385, 1) == Y355_EINVAL && g_err == "bad frame size" && y355_core_range(&c, 2, 16384, 1) == 0);
+        y355_core_close(&c);
+        CHECK(live.empty() && c.allocs.empty());
+        y355_core_close(&c);                        // a second close is harmless
+    }
+    const int n_create = n_alloc;
+    for (int k = 0; k < n_create; ++k) {            // the k-th allocation fails: everything taken goes back once, the message stays
+        HandleCore c;
+        fail_at = k;
+        n_alloc = 0;
+        g_err.clear();
+        CHECK(core_create(c, N, outs) == Y355_EHIP);
+        CHECK(live.empty() && c.allocs.empty() && c.head.allocs.empty() && c.stage.allocs.empty() && !c.stage.frames);
+        CHECK(g_err == "injected allocation failure" && std::string(y355_last_error()) == "injected allocation failure");
+        y355_core_close(&c);
+        CHECK(live.empty());
+    }
+    fail_at = -1;
+}
 }  // namespace
 
 int main() {
@@ -172,10 +213,18 @@ int main() {
     check_head(10647, 2, 0, true, false);           // more than 4096 anchors: y355_net-like (no host outputs)
     check_head(10647, 3, 5000, true, true);         // max_det between the two capacities
     check_stage();
+    check_core(180, true);                          // engine-like: host outputs
+    check_core(10647, false);                       // y355_net-like, more than 4096 anchors
     CHECK(y355_head_check_option(10647, true, 4096, "m") == 0 && y355_head_check_option(10647, true, 10647, "m") == 0);
     CHECK(y355_head_check_option(10647, true, 10648, "cap message") == Y355_EINVAL && g_err == "cap message");
     CHECK(y355_head_check_option(2000, true, 4096, "m") == 0 && y355_head_check_option(2000, true, 4097, "m") == Y355_EINVAL);
     CHECK(y355_head_check_option(2000, true, 2000, "m") == Y355_EINVAL);
+    int e = 0;
+    CHECK(y355_tracker_exponent(0.f, &e) == 1 && y355_tracker_exponent(-1.f, &e) == 1 && y355_tracker_exponent(INFINITY, &e) == 1);
+    CHECK(y355_tracker_exponent(1.f, &e) == 0 && e == 0 && y355_tracker_exponent(0.75f, &e) == 0 && e == -1);
+    CHECK(y355_tracker_exponent(1e-30f, &e) == 2 && y355_tracker_exponent(1e30f, &e) == 2 && y355_tracker_exponent(63.5f, &e) == 0 && e == 5);
+    CHECK(y355_core_check_config(80, 96, 16, 5, 16, 2, 1, 150) == 0 && y355_core_check_config(80, 96, 32, 5, 16, 2, 1, 150) == Y355_EINVAL &&
+          g_err == "input size must be a positive multiple of 32");
     CHECK(y355_head_check_option(2000, false, 1, "m") == 0 && y355_head_check_option(2000, false, 2, "route message") == Y355_EINVAL &&
           g_err == "route message");
     puts("host_state_check: ok");

@@ -8,13 +8,6 @@
 #include <string>
 #include <vector>
 
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 #define AP_POS_BITS 20            // position of a detection in its image's list: max_det <= 2^20
 #define AP_TILE 1024              // keys per workgroup of a sort pass: 4 waves x 4 rounds x 64
 #define AP_SCORE_THREADS 1024

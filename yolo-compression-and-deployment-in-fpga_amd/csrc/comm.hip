@@ -15,13 +15,6 @@
 #include <cstring>
 #include <string>
 
-int y355_fail(int code, const std::string &msg);
-#define COMMCHK(expr)                                                                          \
-    do {                                                                                       \
-        hipError_t e_ = (expr);                                                                \
-        if (e_ != hipSuccess) return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 namespace {
 // the slice of the NCCL API this file uses (rccl.h: ncclUniqueId is 128 bytes, ncclChar = 0)
 typedef struct { char internal[128]; } nccl_uid;
@@ -86,7 +79,7 @@ extern "C" int y355_comm_init(y355_comm **out, int world, int rank, const void *
     if (!out || !id) return y355_fail(Y355_EINVAL, "null argument");
     if (world < 1 || rank < 0 || rank >= world) return y355_fail(Y355_EINVAL, "bad world / rank");
     if (int rc = load_rccl()) return rc;
-    COMMCHK(hipSetDevice(device_id));
+    HIPCHK(hipSetDevice(device_id));
     nccl_uid uid;
     memcpy(&uid, id, sizeof uid);
     y355_comm *c = new y355_comm();
@@ -155,7 +148,7 @@ extern "C" int y355_pack_dets_capped(const float *boxes_dev, const float *scores
     const int rec16 = 1 + max_det + (max_det * 2 + 3) / 4;
     hipLaunchKernelGGL(pack_dets_kernel, dim3((rec16 + 255) / 256, records), dim3(256), 0, (hipStream_t)stream,
                        (const float4 *)boxes_dev, scores_dev, cls_dev, count_dev, batch, src_max_det, max_det, (v4i *)packed_dev);
-    COMMCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -168,7 +161,7 @@ extern "C" int y355_allgather_dets(y355_comm *c, const void *packed_send_dev, vo
                                    void *stream) {
     if (!c || !packed_send_dev || !packed_recv_dev) return y355_fail(Y355_EINVAL, "null argument");
     if (records < 1 || max_det < 1) return y355_fail(Y355_EINVAL, "bad records / max_det");
-    COMMCHK(hipSetDevice(c->device_id));
+    HIPCHK(hipSetDevice(c->device_id));
     const size_t bytes = (size_t)records * y355_packed_det_bytes(max_det);
     if (int rc = g_rccl.AllGather(packed_send_dev, packed_recv_dev, bytes, /*ncclChar*/ 0, c->comm, (hipStream_t)stream))
         return nccl_fail("ncclAllGather", rc);
@@ -201,6 +194,6 @@ extern "C" int y355_unpack_dets(const void *packed_dev, const int32_t *slot_dev,
     if (records < 1 || max_det < 1) return y355_fail(Y355_EINVAL, "bad records / max_det");
     hipLaunchKernelGGL(unpack_dets_kernel, dim3((max_det + 255) / 256, records), dim3(256), 0, (hipStream_t)stream,
                        (const char *)packed_dev, slot_dev, records, max_det, (float4 *)boxes_dev, scores_dev, cls_dev, count_dev);
-    COMMCHK(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }

@@ -5,7 +5,7 @@
 //   conv4_1(64->128), conv4_2(128->128)+pool, conv5(128->256), conv6, conv7, pred (no act).
 #include "../../include/yolo355.h"
 #include "y355_common.h"
-#include "head_nms.h"
+#include "handle_core.h"
 
 #include <algorithm>
 #include <cmath>
@@ -21,12 +21,6 @@ int y355_fail(int code, const std::string &msg) {
     return code;
 }
 static int fail(int code, const std::string &msg) { return y355_fail(code, msg); }
-#define HIPCHK(expr)                                                                      \
-    do {                                                                                  \
-        hipError_t e_ = (expr);                                                           \
-        if (e_ != hipSuccess)                                                             \
-            return fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
 
 extern "C" const char *y355_last_error(void) { return g_err.c_str(); }
 extern "C" int y355_version(void) { return 2; }       // 2: round 6 (y355_pipeline_*, y355_calibrate, y355_conv_op, *_dev operators)
@@ -107,8 +101,6 @@ int y355_cu_count(void) {
     return cached[dev];
 }
 namespace {
-int prepare_kernels() { return y355_prepare_kernels(); }
-
 // Fill the integer epilogue of one layer.  Returns Y355_ERANGE when the int32 path could
 // overflow for worst-case operands.
 // act: 0 none (prediction layer), 1 LeakyReLU(0.125) (t' = t >= 0 ? 8 t : t, F' = F + 3), 2 ReLU (utils/modules.py:26 with
@@ -180,9 +172,8 @@ int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int sa_out, 
 }
 
 struct y355_engine {
-    y355_config cfg{};
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
+    y355_config cfg{};              // anchors and classes; the rest of it lives in the core
+    HandleCore core;
     Layer L[10];
     int sa[11];
     bool sa_set[11];
@@ -190,88 +181,52 @@ struct y355_engine {
     float trk_scale[11] = {};       // AveragedRangeTracker.scale / first_a of the 11 trackers (models/slim_yolo_v2.py:13-14), y355_calibrate
     int trk_first[11] = {};
     const uint8_t *x_u8 = nullptr;  // uint8 frames of the forward being enqueued (y355_forward_u8)
-    FrameStage stage;               // BaseTransform constants, cv2.resize stage of y355_forward_u8_resized / y355_forward_frames
     int8_t *w0_dev = nullptr;       // conv1 fragment
     int8_t *wf_dev = nullptr;       // weight fragments of the fused front end (y355_pack_front)
-    Counters *ctr_dev = nullptr;    // [10]: the set the last forward / layer run counted into (one of ctrs' two)
-    CounterSets ctrs;
-    unsigned int *absmax_dev = nullptr;
     int8_t *sink_dev = nullptr;
     unsigned long long *stamps_dev = nullptr;
-    int Hs = 0, Ws = 0, N = 0;
-    HeadState head;                 // the head's workspace, max_det, candidate tap, outputs of the host calls
+    int Hs = 0, Ws = 0;
     float *x_stage = nullptr;       // host-call staging
     int stamp_layer = -1;
-    int profile = 0;
     int fuse_front = 1;             // conv1 + pool1 + conv2 + pool2 as one launch (front.hip) where eligible
     int fuse_pairs = 1;             // conv3_1 -> conv3_2 + pool3 as one launch (pxpair.hip) where eligible
     int l2_batch = 0;               // images of conv3_1's map that the last launches left valid in L[2].out_dev (the fused pair writes none)
     int l0_batch = 0;               // images of conv1's pooled map that the last launches left valid in L[0].out_dev (the fused
                                     // front end keeps that map on chip: 0 after a fused forward)
     int ring_wgs = 0;               // persistent workgroups per ring launch (0 = one per CU)
-    hipEvent_t ev[Y355_NUM_TIMERS + 1];
     // kernel start / stop timestamps of the launches themselves (profile mode 2): 0..9 layers (the fused front end in slot 0),
     // 10 decode, 11 candidate sort, 12 pair walk, 13 rounds + output
-    hipEvent_t kev[Y355_NUM_KERNEL_TIMERS][2];
+    hipEvent_t kev[Y355_NUM_KERNEL_TIMERS][2] = {};       // (null: not created)
     bool kev_set[Y355_NUM_KERNEL_TIMERS] = {};
-    bool ev_ok = false;
-    std::vector<void *> allocs;
 };
 
-static int dmalloc(y355_engine *h, void **p, size_t bytes, bool zero) {
-    HIPCHK(hipMalloc(p, bytes ? bytes : 16));
-    h->allocs.push_back(*p);
-    if (zero) HIPCHK(hipMemset(*p, 0, bytes ? bytes : 16));
-    return 0;
-}
 extern "C" void y355_destroy(y355_engine *h) {
     if (!h) return;
-    (void)hipSetDevice(h->cfg.device_id);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : h->allocs) (void)hipFree(p);
-    y355_head_destroy(h->head);
-    y355_stage_destroy(h->stage);
-    if (h->ev_ok) {
-        for (auto &e : h->ev) (void)hipEventDestroy(e);
-        for (auto &e : h->kev) { (void)hipEventDestroy(e[0]); (void)hipEventDestroy(e[1]); }
-    }
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    y355_core_close(&h->core);
+    for (auto &e : h->kev)
+        for (hipEvent_t k : e)
+            if (k) (void)hipEventDestroy(k);
     delete h;
 }
 
 extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
     if (!cfg || !out) return fail(Y355_EINVAL, "null argument");
-    if (cfg->height <= 0 || cfg->width <= 0 || cfg->height % 16 || cfg->width % 16)
-        return fail(Y355_EINVAL, "input size must be a positive multiple of 16");
-    if (cfg->num_anchors < 1 || cfg->num_anchors > Y355_MAX_ANCHORS || cfg->num_classes < 1)
-        return fail(Y355_EINVAL, "bad anchors / classes");
-    if (cfg->max_batch < 1) return fail(Y355_EINVAL, "max_batch < 1");
     const int predc = cfg->num_anchors * (5 + cfg->num_classes);
-    if (predc > 256) return fail(Y355_EINVAL, "A*(5+C) > 256 not supported");
     const int Hs = cfg->height / 16, Ws = cfg->width / 16, N = Hs * Ws * cfg->num_anchors;
-    if (N > Y355_NMS_MAX_CAP) return fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
+    if (int rc = y355_core_check_config(cfg->height, cfg->width, 16, cfg->num_anchors, Y355_MAX_ANCHORS, cfg->num_classes, cfg->max_batch, N))
+        return rc;
     HIPCHK(hipSetDevice(cfg->device_id));
-    if (int e = prepare_kernels()) return e;
+    if (int e = y355_prepare_kernels()) return e;
     y355_engine *h = new y355_engine();
     h->cfg = *cfg;
     h->Hs = Hs;
     h->Ws = Ws;
-    h->N = N;
-    y355_stage_init(h->stage, cfg->height, cfg->width, cfg->max_batch, y355_hip_mem());
     for (int i = 0; i < 11; ++i) { h->sa[i] = 0; h->sa_set[i] = false; }
     for (int i = 0; i < 10; ++i) h->retune[i] = kRetuneDefault[i];
-    if (!cfg->own_stream) {
-        h->stream = (hipStream_t)cfg->stream;      // NULL = default stream (torch's default on ROCm)
-    } else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete h;
-            return fail(Y355_EHIP, "hipStreamCreate failed");
-        }
-        h->own_stream = true;
-    }
     const int B = cfg->max_batch;
     int Hc = cfg->height, Wc = cfg->width;
-    int rc = 0;
+    int rc = y355_core_open(&h->core, cfg->device_id, cfg->stream, cfg->own_stream != 0, Hc, Wc, B, N, cfg->conf_thresh, cfg->nms_thresh,
+                            y355_hip_mem());
     for (int k = 0; k < 10 && !rc; ++k) {
         Layer &L = h->L[k];
         const LayerDef &d = kLayers[k];
@@ -292,35 +247,22 @@ extern "C" int y355_create(const y355_config *cfg, y355_engine **out) {
         }
         // slack rows so that clamped / masked tile reads of the next layer stay inside
         L.out_bytes = ((size_t)B * (L.Hout + 2 * L.halo) * (L.Wout + 2 * L.halo) + 64) * L.cout_pad;
-        rc = dmalloc(h, (void **)&L.out_dev, L.out_bytes, true);
-        if (!rc) rc = dmalloc(h, (void **)&L.bias_dev, sizeof(int) * L.cout_pad, true);
-        if (!rc) rc = dmalloc(h, (void **)&L.bias_w_dev, sizeof(long long) * L.cout_pad, true);
-        if (!rc && k > 0) rc = dmalloc(h, (void **)&L.w_dev, y355_packed_bytes(*y355_conv_kernel(L.kid), L.cout_pad), true);
+        rc = y355_core_alloc(&h->core, &L.out_dev, L.out_bytes, true);
+        if (!rc) rc = y355_core_alloc(&h->core, &L.bias_dev, sizeof(int) * L.cout_pad, true);
+        if (!rc) rc = y355_core_alloc(&h->core, &L.bias_w_dev, sizeof(long long) * L.cout_pad, true);
+        if (!rc && k > 0) rc = y355_core_alloc(&h->core, &L.w_dev, y355_packed_bytes(*y355_conv_kernel(L.kid), L.cout_pad), true);
         Hc = L.Hout;
         Wc = L.Wout;
     }
-    if (!rc) rc = dmalloc(h, (void **)&h->w0_dev, 1024, true);
-    if (!rc) rc = dmalloc(h, (void **)&h->wf_dev, 16384, true);
-    if (!rc) rc = dmalloc(h, (void **)&h->ctr_dev, sizeof(Counters) * 20, true);
-    h->ctrs.base = h->ctr_dev;
-    h->ctrs.n = 10;
-    h->ctrs.clean[0] = h->ctrs.clean[1] = true;        // zeroed by the allocation
-    if (!rc) rc = dmalloc(h, (void **)&h->absmax_dev, 16, true);
-    if (!rc) rc = dmalloc(h, (void **)&h->sink_dev, 16384, true);
-    if (!rc) rc = y355_head_create(h->head, N, B, cfg->max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, true, true, y355_hip_mem());
-    if (!rc) {
-        bool ok = true;
-        for (auto &e : h->ev) ok = ok && (hipEventCreate(&e) == hipSuccess);
-        for (auto &e : h->kev) ok = ok && (hipEventCreate(&e[0]) == hipSuccess) && (hipEventCreate(&e[1]) == hipSuccess);
-        h->ev_ok = ok;
-        if (!ok) rc = fail(Y355_EHIP, "hipEventCreate failed");
-    }
-    if (rc) {
-        std::string keep = g_err;
-        y355_destroy(h);
-        g_err = keep;
-        return rc;
-    }
+    if (!rc) rc = y355_core_alloc(&h->core, &h->w0_dev, 1024, true);
+    if (!rc) rc = y355_core_alloc(&h->core, &h->wf_dev, 16384, true);
+    if (!rc) rc = y355_core_alloc(&h->core, &h->sink_dev, 16384, true);
+    if (!rc) rc = y355_core_state(&h->core, 10, cfg->max_det, true);
+    if (!rc) rc = y355_core_events(&h->core, Y355_NUM_TIMERS);
+    for (auto &e : h->kev)
+        for (hipEvent_t &k : e)
+            if (!rc && hipEventCreate(&k) != hipSuccess) rc = fail(Y355_EHIP, "hipEventCreate failed");
+    if (rc) return y355_core_unwind(rc, [h] { y355_destroy(h); });
     *out = h;
     return 0;
 }
@@ -343,14 +285,9 @@ extern "C" int y355_set_option(y355_engine *h, int option, int value) {
     case Y355_OPT_MAX_CANDIDATES:
     case Y355_OPT_HEAD_ROUTE: {
         const bool is_cap = option == Y355_OPT_MAX_CANDIDATES;
-        if (int rc = y355_head_check_option(h->N, is_cap, value,
-                                            is_cap ? "Y355_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)"
-                                                   : "Y355_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)"))
-            return rc;
-        HIPCHK(hipSetDevice(h->cfg.device_id));
-        HIPCHK(hipStreamSynchronize(h->stream));         // nothing in flight reads the arrays that go
-        if (y355_head_set_option(h->head, is_cap, value)) return fail(Y355_EHIP, "device allocation failed");
-        return 0;
+        return y355_core_head_option(&h->core, is_cap, value,
+                                     is_cap ? "Y355_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)"
+                                            : "Y355_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)");
     }
     default: return fail(Y355_EINVAL, "unknown option");
     }
@@ -359,25 +296,19 @@ extern "C" int y355_set_option(y355_engine *h, int option, int value) {
 // heads with more than 4096 anchors per image, or with the large route forced: *overflow = 1 if, in a forward since the last call,
 // more anchors of an image passed conf_thresh than the candidate capacity holds (the excess was dropped); synchronous; clears the flag
 extern "C" int y355_overflow(y355_engine *h, int *overflow) {
-    if (!h || !overflow) return fail(Y355_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(y355_head_overflow_read(h->head, h->stream, overflow));
-    return 0;
+    return (!h || !overflow) ? fail(Y355_EINVAL, "null argument") : y355_core_overflow(&h->core, overflow);
 }
 // pipeline.hip: the flags of the forwards enqueued so far move to dst_dev [max_batch] on the handle's stream and are cleared
 // behind the copy, so a ticket carries the overflow of its own forward (only for handles that have the flags)
-bool y355_has_overflow_flags(y355_engine *h) { return h->head.wk.ovf != nullptr; }
+bool y355_has_overflow_flags(y355_engine *h) { return h->core.head.wk.ovf != nullptr; }
 int y355_overflow_take(y355_engine *h, int *dst_dev) {
-    HIPCHK(y355_head_overflow_take(h->head, dst_dev, h->stream));
+    HIPCHK(y355_head_overflow_take(h->core.head, dst_dev, h->core.stream));
     return 0;
 }
-extern "C" int y355_max_candidates(y355_engine *h) { return h ? y355_head_capacity(h->head) : Y355_EINVAL; }
+extern "C" int y355_max_candidates(y355_engine *h) { return h ? y355_head_capacity(h->core.head) : Y355_EINVAL; }
 
 extern "C" int y355_set_thresholds(y355_engine *h, float conf, float nms) {
-    if (!h) return fail(Y355_EINVAL, "null engine");
-    h->cfg.conf_thresh = conf;
-    h->cfg.nms_thresh = nms;
-    return 0;
+    return !h ? fail(Y355_EINVAL, "null engine") : y355_core_set_thresholds(&h->core, conf, nms);
 }
 
 extern "C" int y355_load_layer(y355_engine *h, int idx, const int8_t *q_w, const int32_t *q_b, int cout, int cin,
@@ -390,8 +321,8 @@ extern "C" int y355_load_layer(y355_engine *h, int idx, const int8_t *q_w, const
         snprintf(buf, sizeof buf, "layer %d expects [%d,%d,3,3], got [%d,%d,3,3]", idx, L.cout, L.cin, cout, cin);
         return fail(Y355_EINVAL, buf);
     }
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     if (idx == 0) {
         int8_t frag[1024];
         y355_pack_conv1(q_w, frag);
@@ -424,7 +355,7 @@ extern "C" int y355_load_layer(y355_engine *h, int idx, const int8_t *q_w, const
         std::vector<int8_t> px(pxb);
         if (y355_pack_px(L.kid, q_w, cout, cin, px.data())) {
             if (!L.wpx_dev) {
-                if (int rc = dmalloc(h, (void **)&L.wpx_dev, px.size(), false)) return rc;
+                if (int rc = y355_core_alloc(&h->core, &L.wpx_dev, px.size(), false)) return rc;
             }
             HIPCHK(hipMemcpy(L.wpx_dev, px.data(), px.size(), hipMemcpyHostToDevice));
         }
@@ -437,28 +368,22 @@ extern "C" int y355_load_layer(y355_engine *h, int idx, const int8_t *q_w, const
     return 0;
 }
 
-extern "C" int y355_set_act_exponents(y355_engine *h, const int32_t *sa) {
-    if (!h || !sa) return fail(Y355_EINVAL, "null argument");
-    for (int i = 0; i < 11; ++i)
-        if (sa[i] < -64 || sa[i] > 64) return fail(Y355_EINVAL, "activation exponent out of range");
-    // only what changes makes a layer's epilogue stale (callers set the same frozen exponents before every forward: that must
-    // not cost ten bias uploads and stream synchronisations per call)
-    for (int i = 0; i < 11; ++i) {
-        if (h->sa_set[i] && h->sa[i] == sa[i]) continue;
-        h->sa[i] = sa[i];
-        h->sa_set[i] = true;
-        if (i < 10) h->L[i].bias_dirty = true;
-        if (i > 0) h->L[i - 1].bias_dirty = true;
-    }
-    return 0;
-}
-
+// only what changes makes a layer's epilogue stale (callers set the same frozen exponents before every forward: that must
+// not cost ten bias uploads and stream synchronisations per call)
 static int set_one_exponent(y355_engine *h, int i, int v) {
     if (h->sa_set[i] && h->sa[i] == v) return 0;
     h->sa[i] = v;
     h->sa_set[i] = true;
     if (i < 10) h->L[i].bias_dirty = true;
     if (i > 0) h->L[i - 1].bias_dirty = true;
+    return 0;
+}
+
+extern "C" int y355_set_act_exponents(y355_engine *h, const int32_t *sa) {
+    if (!h || !sa) return fail(Y355_EINVAL, "null argument");
+    for (int i = 0; i < 11; ++i)
+        if (sa[i] < -64 || sa[i] > 64) return fail(Y355_EINVAL, "activation exponent out of range");
+    for (int i = 0; i < 11; ++i) set_one_exponent(h, i, sa[i]);
     return 0;
 }
 
@@ -495,10 +420,16 @@ static int refresh_layer(y355_engine *h, int k, bool need_out) {
     int rc = make_requant(L.cin, 9, h->sa[k], L.e_w, L.e_b, h->sa[k + 1], h->sa_set[k + 1], L.leaky, h->retune[k],
                           L.q_b.data(), L.cout, L.cout_pad, &L.rq, &L.frac_bits, &bt, &bw, L.wabs);
     if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(L.bias_w_dev, bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));   // bt is a stack-owned vector
+    HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipMemcpyAsync(L.bias_w_dev, bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));   // bt is a stack-owned vector
     L.bias_dirty = !h->sa_set[k + 1];
+    return 0;
+}
+
+static int refresh_layers(y355_engine *h) {        // what a forward needs: every layer, with its output exponent
+    for (int k = 0; k < 10; ++k)
+        if (int rc = refresh_layer(h, k, true)) return rc;
     return 0;
 }
 
@@ -508,12 +439,12 @@ static int launch_layer(y355_engine *h, int k, int B, int mode, int guard, const
         Conv1Params p{};
         p.x = x_dev;
         p.x_u8 = x_dev ? nullptr : h->x_u8;
-        for (int c = 0; c < 3; ++c) { p.nmean[c] = h->stage.norm.mean[c]; p.nstd[c] = h->stage.norm.sd[c]; }
+        for (int c = 0; c < 3; ++c) { p.nmean[c] = h->core.stage.norm.mean[c]; p.nstd[c] = h->core.stage.norm.sd[c]; }
         p.out = L.out_dev;
         p.w = h->w0_dev;
         p.bias_t = L.bias_dev;
         p.bias_w = L.bias_w_dev;
-        p.ctr = h->ctr_dev;
+        p.ctr = h->core.ctr_dev;
         p.B = B;
         p.H = L.Hin;
         p.W = L.Win;
@@ -522,7 +453,7 @@ static int launch_layer(y355_engine *h, int k, int B, int mode, int guard, const
         p.rq = L.rq;
         p.mode = mode;
         p.guard = guard;
-        y355_launch_conv1(p, h->stream);
+        y355_launch_conv1(p, h->core.stream);
         if (mode == 0) h->l0_batch = B;
     } else {
         const ConvKernelInfo &ki = *y355_conv_kernel(L.kid);
@@ -532,11 +463,11 @@ static int launch_layer(y355_engine *h, int k, int B, int mode, int guard, const
         p.w = L.w_dev;
         p.bias_t = L.bias_dev;
         p.bias_w = L.bias_w_dev;
-        p.ctr = h->ctr_dev + k;
+        p.ctr = h->core.ctr_dev + k;
         p.sink = h->sink_dev;
         p.stamps = (h->stamp_layer == k) ? h->stamps_dev : nullptr;
         h->kev_set[k] = false;
-        if (h->profile == 2 && mode == 0) { p.ev_start = h->kev[k][0]; p.ev_stop = h->kev[k][1]; }
+        if (h->core.profile == 2 && mode == 0) { p.ev_start = h->kev[k][0]; p.ev_stop = h->kev[k][1]; }
         p.grid_limit = h->ring_wgs * kGridLimitPct[k] / 100;
         p.B = B;
         p.H = L.Hin;
@@ -563,18 +494,18 @@ static int launch_layer(y355_engine *h, int k, int B, int mode, int guard, const
         if (L.wpx_dev && !((no_px_mask >> k) & 1)) {
             ConvParams q = p;
             q.w = L.wpx_dev;
-            if (y355_launch_conv_px(L.kid, q, h->stream)) {
+            if (y355_launch_conv_px(L.kid, q, h->core.stream)) {
                 HIPCHK(hipGetLastError());
                 h->kev_set[k] = p.ev_start != nullptr;
                 return 0;
             }
         }
-        if (!((no_ring_mask >> k) & 1) && y355_launch_conv_ring(L.kid, p, h->stream)) {
+        if (!((no_ring_mask >> k) & 1) && y355_launch_conv_ring(L.kid, p, h->core.stream)) {
             HIPCHK(hipGetLastError());
             h->kev_set[k] = p.ev_start != nullptr;
             return 0;
         }
-        ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * B, h->stream);
+        ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * B, h->core.stream);
     }
     HIPCHK(hipGetLastError());
     return 0;
@@ -582,35 +513,29 @@ static int launch_layer(y355_engine *h, int k, int B, int mode, int guard, const
 
 extern "C" int y355_input_absmax(y355_engine *h, const float *x_dev, int batch, float *out_max) {
     if (!h || !x_dev || !out_max) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipMemsetAsync(h->absmax_dev, 0, 16, h->stream));
-    y355_launch_absmax(x_dev, (size_t)batch * 3 * h->cfg.height * h->cfg.width, h->absmax_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    unsigned int bits = 0;
-    HIPCHK(hipMemcpyAsync(&bits, h->absmax_dev, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    memcpy(out_max, &bits, 4);
-    return 0;
+    if (int rc = y355_core_enter(&h->core, batch)) return rc;
+    HIPCHK(hipMemsetAsync(h->core.absmax_dev, 0, 16, h->core.stream));
+    y355_launch_absmax(x_dev, (size_t)batch * 3 * h->core.H * h->core.W, h->core.absmax_dev, h->core.stream);
+    return y355_core_absmax_read(&h->core, out_max);
 }
 
 extern "C" int y355_run_layer(y355_engine *h, int idx, int batch, int mode, const float *x_dev) {
     if (!h) return fail(Y355_EINVAL, "null engine");
     if (idx < 0 || idx >= 10 || (mode != 0 && mode != 1)) return fail(Y355_EINVAL, "bad layer / mode");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
+    if (int rc = y355_core_range(&h->core, batch)) return rc;
     if (idx == 0 && !x_dev) return fail(Y355_EINVAL, "layer 0 needs the network input");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core)) return rc;
     if (int rc = refresh_layer(h, idx, mode == 0)) return rc;
-    HIPCHK(hipMemsetAsync(h->ctr_dev + idx, 0, sizeof(Counters), h->stream));
+    HIPCHK(hipMemsetAsync(h->core.ctr_dev + idx, 0, sizeof(Counters), h->core.stream));
     return launch_layer(h, idx, batch, mode, 1, x_dev);
 }
 
 extern "C" int y355_layer_stats_get(y355_engine *h, int idx, y355_layer_stats *out) {
     if (!h || !out || idx < 0 || idx >= 10) return fail(Y355_EINVAL, "bad argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core)) return rc;
     Counters c;
-    HIPCHK(hipMemcpyAsync(&c, h->ctr_dev + idx, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(&c, h->core.ctr_dev + idx, sizeof c, hipMemcpyDeviceToHost, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     out->absmax_t = (int64_t)c.absmax;
     out->frac_bits = h->L[idx].frac_bits;
     out->reserved = (int32_t)c.in_sat;
@@ -636,16 +561,13 @@ static int tracker_update(float *scale, int *first, int i, float max_abs, int fr
         const float keep = (float)(1.0 - momentum), mom = (float)momentum;
         *scale = *scale * keep + s * mom;
     }
-    const float sc = *scale;
-    if (!(sc > 0.f) || !std::isfinite(sc)) {
+    const int bad = y355_tracker_exponent(*scale, exp_out);
+    if (bad == 1) {
         char buf[160];
-        snprintf(buf, sizeof buf, "tracker %d: scale %g is not a positive finite number (max|activation| = %g)", i, (double)sc, (double)max_abs);
+        snprintf(buf, sizeof buf, "tracker %d: scale %g is not a positive finite number (max|activation| = %g)", i, (double)*scale, (double)max_abs);
         return fail(Y355_ERANGE, buf);
     }
-    const int e = (int)std::floor(std::log2(sc));
-    if (e < -64 || e > 64) return fail(Y355_ERANGE, "tracker exponent out of range");
-    *exp_out = e;
-    return 0;
+    return bad ? fail(Y355_ERANGE, "tracker exponent out of range") : 0;
 }
 
 // the update of ONE tracker as a host utility (no GPU): the arithmetic y355_calibrate applies, testable against torch on the CPU
@@ -660,19 +582,13 @@ extern "C" int y355_tracker_step(float *scale, int32_t *first_a, float max_abs, 
 
 extern "C" int y355_set_trackers(y355_engine *h, const float *scale, const int32_t *first_a) {
     if (!h || !scale || !first_a) return fail(Y355_EINVAL, "null argument");
-    for (int i = 0; i < 11; ++i) {
-        h->trk_scale[i] = scale[i];
-        h->trk_first[i] = first_a[i] ? 1 : 0;
-    }
+    y355_trackers_set(h->trk_scale, h->trk_first, 11, scale, first_a);
     return 0;
 }
 
 extern "C" int y355_get_trackers(y355_engine *h, float *scale, int32_t *first_a) {
     if (!h || !scale || !first_a) return fail(Y355_EINVAL, "null argument");
-    for (int i = 0; i < 11; ++i) {
-        scale[i] = h->trk_scale[i];
-        first_a[i] = h->trk_first[i];
-    }
+    y355_trackers_get(h->trk_scale, h->trk_first, 11, scale, first_a);
     return 0;
 }
 
@@ -682,7 +598,7 @@ extern "C" int y355_get_trackers(y355_engine *h, float *scale, int32_t *first_a)
 extern "C" int y355_calibrate(y355_engine *h, const float *x_dev, int batch, int freeze, double momentum, int32_t *sa_out,
                               float *max_out) {
     if (!h || !x_dev) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
+    if (batch < 1 || batch > h->core.max_batch) return fail(Y355_EINVAL, "batch out of range");
     if (!(momentum >= 0.0 && momentum <= 1.0)) return fail(Y355_EINVAL, "momentum outside [0, 1]");
     float m = 0.f;
     if (int rc = y355_input_absmax(h, x_dev, batch, &m)) return rc;
@@ -710,8 +626,7 @@ extern "C" int y355_calibrate(y355_engine *h, const float *x_dev, int batch, int
 
 extern "C" int y355_get_feature(y355_engine *h, int idx, int batch, int8_t *dst) {
     if (!h || !dst || idx < 0 || idx >= 10) return fail(Y355_EINVAL, "bad argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core, batch)) return rc;
     if (idx == 0 && batch > h->l0_batch)
         return fail(Y355_ENOTREADY, "conv1's map of the last forward was not written (fused front end): "
                                     "run with y355_set_option(h, Y355_OPT_FUSE_FRONT, 0) to tap it");
@@ -721,7 +636,7 @@ extern "C" int y355_get_feature(y355_engine *h, int idx, int batch, int8_t *dst)
     const Layer &L = h->L[idx];
     const int Hp = L.Hout + 2 * L.halo, Wp = L.Wout + 2 * L.halo, CS = L.cout_pad;
     std::vector<int8_t> tmp((size_t)batch * Hp * Wp * CS);
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     HIPCHK(hipMemcpy(tmp.data(), L.out_dev, tmp.size(), hipMemcpyDeviceToHost));
     for (int b = 0; b < batch; ++b)
         for (int c = 0; c < L.cout; ++c)
@@ -755,9 +670,9 @@ static HeadParams head_params(y355_engine *h, int sa_pred, float *ob, float *os,
     p.Wb = h->Ws;
     // more than 4096 anchors: the candidates arrive thresholded and compacted, their position says nothing about the anchor, and
     // one bin per cell and anchor (N bins) would not fit the sort's 4096-entry tables -- area octaves do
-    if (h->N > Y355_NMS_CAP) y355_head_area_bins(p, h->Hs, h->Ws);
+    if (h->core.N > Y355_NMS_CAP) y355_head_area_bins(p, h->Hs, h->Ws);
     p.pairs_wgs = h->ring_wgs > 0 ? Y355_TPUT_PAIRS_WGS : 0;    // throughput mode (Y355_OPT_RING_WORKGROUPS set): the pair walk holds one CU per image
-    y355_head_fill(p, h->head, h->cfg.conf_thresh, h->cfg.nms_thresh, h->cfg.height, h->cfg.width, ob, os, oc, on, tap);
+    y355_head_fill(p, h->core.head, h->core.conf_thresh, h->core.nms_thresh, h->core.H, h->core.W, ob, os, oc, on, tap);
     return p;
 }
 
@@ -767,13 +682,13 @@ static int launch_front(y355_engine *h, int B, const float *x_dev) {
     FrontParams p{};
     p.x = x_dev;
     p.x_u8 = x_dev ? nullptr : h->x_u8;
-    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->stage.norm.mean[c]; p.nstd[c] = h->stage.norm.sd[c]; }
+    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->core.stage.norm.mean[c]; p.nstd[c] = h->core.stage.norm.sd[c]; }
     p.out = L1.out_dev;
     p.wf = h->wf_dev;
     p.bias1 = L0.bias_dev;
     p.bias2 = L1.bias_dev;
-    p.ctr = h->ctr_dev;
-    p.zero_next = (unsigned long long *)h->ctrs.other_zeroed_by_front();
+    p.ctr = h->core.ctr_dev;
+    p.zero_next = (unsigned long long *)h->core.ctrs.other_zeroed_by_front();
     p.zero_n = 10 * (int)(sizeof(Counters) / 8);
     p.B = B;
     p.H = L0.Hin;
@@ -784,8 +699,8 @@ static int launch_front(y355_engine *h, int B, const float *x_dev) {
     p.rq2 = L1.rq;
     p.stamps = (h->stamp_layer == 0) ? h->stamps_dev : nullptr;
     h->kev_set[0] = h->kev_set[1] = false;
-    if (h->profile == 2) { p.ev_start = h->kev[0][0]; p.ev_stop = h->kev[0][1]; h->kev_set[0] = true; }
-    y355_launch_front(p, h->stream);
+    if (h->core.profile == 2) { p.ev_start = h->kev[0][0]; p.ev_stop = h->kev[0][1]; h->kev_set[0] = true; }
+    y355_launch_front(p, h->core.stream);
     HIPCHK(hipGetLastError());
     return 0;
 }
@@ -816,8 +731,8 @@ static int launch_pair3(y355_engine *h, int B) {
     p.w2 = Bl.wpx_dev;
     p.bias1 = A.bias_dev;
     p.bias2 = Bl.bias_dev;
-    p.ctr1 = h->ctr_dev + 2;
-    p.ctr2 = h->ctr_dev + 3;
+    p.ctr1 = h->core.ctr_dev + 2;
+    p.ctr2 = h->core.ctr_dev + 3;
     p.rq1 = A.rq;
     p.rq2 = Bl.rq;
     p.B = B;
@@ -826,8 +741,8 @@ static int launch_pair3(y355_engine *h, int B) {
     p.grid_limit = h->ring_wgs * kGridLimitPct[2] / 100;
     p.stamps = (h->stamp_layer == 2) ? h->stamps_dev : nullptr;
     h->kev_set[2] = h->kev_set[3] = false;
-    if (h->profile == 2) { p.ev_start = h->kev[2][0]; p.ev_stop = h->kev[2][1]; }
-    if (!y355_launch_pair3(p, h->stream)) return 0;
+    if (h->core.profile == 2) { p.ev_start = h->kev[2][0]; p.ev_stop = h->kev[2][1]; }
+    if (!y355_launch_pair3(p, h->core.stream)) return 0;
     HIPCHK(hipGetLastError());
     h->kev_set[2] = p.ev_start != nullptr;
     h->l2_batch = 0;
@@ -837,16 +752,14 @@ static int launch_pair3(y355_engine *h, int B) {
 // enqueue one forward on `s` (refresh_layer must have run)
 static int enqueue_forward(y355_engine *h, const float *x_dev, int batch, int flags, float *boxes_dev, float *scores_dev,
                            int32_t *cls_dev, int32_t *count_dev, bool prof) {
-    bool need_zero = false;
-    h->ctr_dev = h->ctrs.begin(&need_zero);          // steady state: zeroed by the previous forward's front end, no launch here
-    if (need_zero) HIPCHK((hipError_t)y355_zero_counters(h->ctr_dev, 10, h->stream));
+    if (int rc = y355_core_begin_counters(&h->core)) return rc;
     const int guard = (flags & Y355_F_GUARD) ? 1 : 0;
     // the fused front end covers the 32-bit epilogue without the head-room guard; conv2's packed weights must be the
     // resident-weight layout (one n-block of 32 channels), which they are for this network
     const bool fused = h->fuse_front && !guard && y355_front_eligible(h->L[0].rq, h->L[1].rq) && h->L[1].cout_pad == 32;
     bool pair3 = false;
     for (int k = 0; k < 10; ++k) {
-        if (prof) HIPCHK(hipEventRecord(h->ev[k], h->stream));
+        if (prof) HIPCHK(hipEventRecord(h->core.ev[k], h->core.stream));
         if (fused && k == 0) {
             h->l0_batch = 0;
             if (int rc = launch_front(h, batch, x_dev)) return rc;
@@ -862,33 +775,36 @@ static int enqueue_forward(y355_engine *h, const float *x_dev, int batch, int fl
         if (pair3 && k == 3) continue;
         if (int rc = launch_layer(h, k, batch, 0, guard, x_dev)) return rc;
     }
-    if (prof) HIPCHK(hipEventRecord(h->ev[10], h->stream));
+    if (prof) HIPCHK(hipEventRecord(h->core.ev[10], h->core.stream));
     const HeadParams hp = head_params(h, h->sa[10], boxes_dev, scores_dev, cls_dev, count_dev, (flags & Y355_F_TAP) != 0);
-    const bool kprof = prof && h->profile == 2;
+    const bool kprof = prof && h->core.profile == 2;
     for (int i = 10; i < Y355_NUM_KERNEL_TIMERS; ++i) h->kev_set[i] = kprof;
-    y355_launch_head_nms(hp, batch, h->head, h->stream, prof ? h->ev[11] : nullptr, kprof ? &h->kev[10] : nullptr);
+    y355_launch_head_nms(hp, batch, h->core.head, h->core.stream, prof ? h->core.ev[11] : nullptr, kprof ? &h->kev[10] : nullptr);
     HIPCHK(hipGetLastError());
-    if (prof) HIPCHK(hipEventRecord(h->ev[12], h->stream));
+    if (prof) HIPCHK(hipEventRecord(h->core.ev[12], h->core.stream));
     return 0;
 }
 
 extern "C" int y355_forward(y355_engine *h, const float *x_dev, int batch, int flags, float *boxes_dev,
                             float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !x_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    for (int k = 0; k < 10; ++k)
-        if (int rc = refresh_layer(h, k, true)) return rc;
-    const bool prof = h->profile != 0;
+    if (int rc = y355_core_enter(&h->core, batch)) return rc;
+    if (int rc = refresh_layers(h)) return rc;
+    const bool prof = h->core.profile != 0;
     // (rounds 2-5 carried a hipGraph replay of the step's launches behind -DY355_EXPERIMENTS: measured, no gain; removed with the
     // alternating counter sets, which a captured graph would freeze)
     return enqueue_forward(h, x_dev, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev, prof);
 }
 
+// the fp32 staging tensor [max_batch][3][H][W] of the host call and of the uint8 forwards that take the fp32 route
+static int need_x_stage(y355_engine *h) {
+    return h->x_stage ? 0 : y355_core_alloc(&h->core, &h->x_stage, sizeof(float) * 3 * h->core.H * h->core.W * h->core.max_batch, false);
+}
+
 // BaseTransform constants of the uint8 path, in the reference's BGR order (data/__init__.py:50)
 extern "C" int y355_set_normalization(y355_engine *h, const float *mean_bgr, const float *std_bgr) {
     if (!h || !mean_bgr || !std_bgr) return fail(Y355_EINVAL, "null argument");
-    return y355_stage_set_normalization(h->stage, mean_bgr, std_bgr);
+    return y355_stage_set_normalization(h->core.stage, mean_bgr, std_bgr);
 }
 
 // The step in front of the path: frames as cv2 delivers them, uint8 HWC BGR [B][H][W][3]
@@ -898,23 +814,18 @@ extern "C" int y355_set_normalization(y355_engine *h, const float *mean_bgr, con
 extern "C" int y355_forward_u8(y355_engine *h, const uint8_t *frames_dev, int batch, int flags, float *boxes_dev,
                                float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !frames_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    for (int k = 0; k < 10; ++k)
-        if (int rc = refresh_layer(h, k, true)) return rc;
+    if (int rc = y355_core_enter(&h->core, batch)) return rc;
+    if (int rc = refresh_layers(h)) return rc;
     const bool fused = !h->L[0].rq.wide && !(flags & Y355_F_GUARD);
     if (!fused) {
         // 64-bit epilogue / guard runs take the fp32 tensor: normalise into the staging buffer first
-        const size_t xin = (size_t)3 * h->cfg.height * h->cfg.width;
-        if (!h->x_stage) {
-            if (int rc = dmalloc(h, (void **)&h->x_stage, sizeof(float) * xin * h->cfg.max_batch, false)) return rc;
-        }
-        y355_launch_normalize_u8(frames_dev, h->x_stage, batch, h->cfg.height, h->cfg.width, h->stage.norm.mean, h->stage.norm.sd, h->stream);
+        if (int rc = need_x_stage(h)) return rc;
+        y355_launch_normalize_u8(frames_dev, h->x_stage, batch, h->core.H, h->core.W, h->core.stage.norm.mean, h->core.stage.norm.sd, h->core.stream);
         HIPCHK(hipGetLastError());
-        return enqueue_forward(h, h->x_stage, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev, h->profile != 0);
+        return enqueue_forward(h, h->x_stage, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev, h->core.profile != 0);
     }
     h->x_u8 = frames_dev;
-    const int rc = enqueue_forward(h, nullptr, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev, h->profile != 0);
+    const int rc = enqueue_forward(h, nullptr, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev, h->core.profile != 0);
     h->x_u8 = nullptr;
     return rc;
 }
@@ -925,17 +836,12 @@ extern "C" int y355_forward_u8_resized(y355_engine *h, const uint8_t *frames_dev
                                        float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev,
                                        uint8_t *resized_out_dev) {
     if (!h || !frames_dev) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    if (src_h < 1 || src_w < 1 || src_h > 16384 || src_w > 16384) return fail(Y355_EINVAL, "bad frame size");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    const int H = h->cfg.height, W = h->cfg.width;
-    FrameStage &st = h->stage;
+    if (int rc = y355_core_enter(&h->core, batch, src_h, src_w)) return rc;
+    FrameStage &st = h->core.stage;
     if (int rc = y355_stage_need_frames(st)) return rc;
-    if (int rc = y355_stage_tables_for(st, src_h, src_w, h->stream)) return rc;
-    y355_launch_resize_u8(frames_dev, st.frames, st.tab, batch, src_h, src_w, H, W, h->stream);
-    HIPCHK(hipGetLastError());
+    if (int rc = y355_core_resize_u8(&h->core, frames_dev, src_h, src_w, batch, st.frames)) return rc;
     if (resized_out_dev)
-        HIPCHK(hipMemcpyAsync(resized_out_dev, st.frames, (size_t)batch * H * W * 3, hipMemcpyDeviceToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(resized_out_dev, st.frames, (size_t)batch * st.H * st.W * 3, hipMemcpyDeviceToDevice, h->core.stream));
     if (!boxes_dev && !scores_dev && !cls_dev && !count_dev) return 0;      // resize only
     return y355_forward_u8(h, st.frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
 }
@@ -950,93 +856,66 @@ extern "C" int y355_forward_u8_resized(y355_engine *h, const uint8_t *frames_dev
 // of the pipeline's own state): the list rules and the handle's readiness (weights, exponents) without a HIP call, then the
 // epilogue tables of layers whose exponents changed and the stage's buffers.  What follows it are launches only.
 int y355_frames_prepare(y355_engine *h, const y355_frame *frames, int batch) {
-    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
+    if (int rc = y355_frames_check(frames, batch, h->core.max_batch)) return rc;
     for (int k = 0; k < 10; ++k) {
         if (!h->L[k].loaded) return fail(Y355_ENOTREADY, "layer weights not loaded");
         if (!h->sa_set[k] || !h->sa_set[k + 1]) return fail(Y355_ENOTREADY, "activation exponent not set (calibrate first)");
     }
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    for (int k = 0; k < 10; ++k)
-        if (int rc = refresh_layer(h, k, true)) return rc;
-    if (int rc = y355_stage_need_list(h->stage)) return rc;
-    return y355_stage_need_frames(h->stage);
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    if (int rc = refresh_layers(h)) return rc;
+    if (int rc = y355_stage_need_list(h->core.stage)) return rc;
+    return y355_stage_need_frames(h->core.stage);
 }
 
 extern "C" int y355_forward_frames(y355_engine *h, const y355_frame *frames, int batch, int flags, float *boxes_dev,
                                    float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !frames || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return fail(Y355_EINVAL, "null argument");
     if (int rc = y355_frames_prepare(h, frames, batch)) return rc;
-    y355_launch_resize_frames(frames, batch, h->stage.frames, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
+    y355_launch_resize_frames(frames, batch, h->core.stage.frames, h->core.stage.tabs, h->core.H, h->core.W, h->core.stream);
     HIPCHK(hipGetLastError());
-    return y355_forward_u8(h, h->stage.frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
+    return y355_forward_u8(h, h->core.stage.frames, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
 }
 
 // parity tap of the ragged stage: the list -> out_dev [batch][H][W][3] at the network size, on the engine's stream
 extern "C" int y355_resize_frames(y355_engine *h, const y355_frame *frames, int batch, uint8_t *out_dev) {
-    if (!h || !frames || !out_dev) return fail(Y355_EINVAL, "null argument");
-    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (int rc = y355_stage_need_list(h->stage)) return rc;
-    y355_launch_resize_frames(frames, batch, out_dev, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return (!h || !frames || !out_dev) ? fail(Y355_EINVAL, "null argument") : y355_core_resize_frames(&h->core, frames, batch, out_dev);
 }
 
 // the host calls' outputs (HeadState::o_*) of a forward just enqueued, to the caller's arrays; waits for the stream
 static int outputs_to_host(y355_engine *h, int batch, float *boxes, float *scores, int32_t *cls, int32_t *count) {
-    const HeadState &hd = h->head;
+    const HeadState &hd = h->core.head;
     const size_t md = hd.max_det;
-    HIPCHK(hipMemcpyAsync(boxes, hd.o_box, sizeof(float) * 4 * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(scores, hd.o_score, sizeof(float) * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(cls, hd.o_cls, sizeof(int) * md * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipMemcpyAsync(count, hd.o_count, sizeof(int) * batch, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(boxes, hd.o_box, sizeof(float) * 4 * md * batch, hipMemcpyDeviceToHost, h->core.stream));
+    HIPCHK(hipMemcpyAsync(scores, hd.o_score, sizeof(float) * md * batch, hipMemcpyDeviceToHost, h->core.stream));
+    HIPCHK(hipMemcpyAsync(cls, hd.o_cls, sizeof(int) * md * batch, hipMemcpyDeviceToHost, h->core.stream));
+    HIPCHK(hipMemcpyAsync(count, hd.o_count, sizeof(int) * batch, hipMemcpyDeviceToHost, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     return 0;
 }
 
 extern "C" int y355_forward_host(y355_engine *h, const float *x_host, int batch, int flags, float *boxes,
                                  float *scores, int32_t *cls, int32_t *count) {
     if (!h || !x_host || !boxes || !scores || !cls || !count) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    const size_t xin = (size_t)3 * h->cfg.height * h->cfg.width;
-    if (!h->x_stage) {
-        if (int rc = dmalloc(h, (void **)&h->x_stage, sizeof(float) * xin * h->cfg.max_batch, false)) return rc;
-    }
-    HIPCHK(hipMemcpyAsync(h->x_stage, x_host, sizeof(float) * xin * batch, hipMemcpyHostToDevice, h->stream));
-    if (int rc = y355_forward(h, h->x_stage, batch, flags, h->head.o_box, h->head.o_score, h->head.o_cls, h->head.o_count)) return rc;
+    if (int rc = y355_core_enter(&h->core, batch)) return rc;
+    if (int rc = need_x_stage(h)) return rc;
+    HIPCHK(hipMemcpyAsync(h->x_stage, x_host, sizeof(float) * 3 * h->core.H * h->core.W * batch, hipMemcpyHostToDevice, h->core.stream));
+    if (int rc = y355_forward(h, h->x_stage, batch, flags, h->core.head.o_box, h->core.head.o_score, h->core.head.o_cls, h->core.head.o_count)) return rc;
     return outputs_to_host(h, batch, boxes, scores, cls, count);
 }
 
 extern "C" int y355_forward_counters(y355_engine *h, int64_t *saturated, int64_t *guard) {
-    if (!h) return fail(Y355_EINVAL, "null engine");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    Counters c[10];
-    HIPCHK(hipMemcpyAsync(c, h->ctr_dev, sizeof c, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    int64_t s = 0, g = 0;
-    for (int k = 0; k < 10; ++k) {
-        s += (int64_t)c[k].sat + c[k].in_sat;
-        g += (int64_t)c[k].guard;
-    }
-    if (saturated) *saturated = s;
-    if (guard) *guard = g;
-    return 0;
+    return !h ? fail(Y355_EINVAL, "null engine") : y355_core_counters(&h->core, saturated, guard);      // (the guard counts too)
 }
 
 extern "C" int y355_get_candidates(y355_engine *h, int batch, float *boxes, float *scores, int32_t *cls) {
     if (!h || !boxes || !scores || !cls) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(y355_head_get_candidates(h->head, h->stream, batch, boxes, scores, cls));
-    return 0;
+    return y355_core_get_candidates(&h->core, batch, boxes, scores, cls);
 }
 
 extern "C" int y355_head_nms(y355_engine *h, const int8_t *pred_q, int batch, int sa_pred, float *boxes,
                              float *scores, int32_t *cls, int32_t *count) {
     if (!h || !pred_q || !boxes || !scores || !cls || !count) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core, batch)) return rc;
     const Layer &L = h->L[9];
     const int CS = L.cout_pad, Hs = h->Hs, Ws = h->Ws, PC = L.cout;
     std::vector<int8_t> tmp((size_t)batch * Hs * Ws * CS, 0);
@@ -1045,16 +924,16 @@ extern "C" int y355_head_nms(y355_engine *h, const int8_t *pred_q, int batch, in
             for (int y = 0; y < Hs; ++y)
                 for (int x = 0; x < Ws; ++x)
                     tmp[(((size_t)b * Hs + y) * Ws + x) * CS + c] = pred_q[(((size_t)b * PC + c) * Hs + y) * Ws + x];
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     HIPCHK(hipMemcpy(L.out_dev, tmp.data(), tmp.size(), hipMemcpyHostToDevice));
-    const HeadState &hd = h->head;
-    y355_launch_head_nms(head_params(h, sa_pred, hd.o_box, hd.o_score, hd.o_cls, hd.o_count, true), batch, hd, h->stream, nullptr);
+    const HeadState &hd = h->core.head;
+    y355_launch_head_nms(head_params(h, sa_pred, hd.o_box, hd.o_score, hd.o_cls, hd.o_count, true), batch, hd, h->core.stream, nullptr);
     HIPCHK(hipGetLastError());
     return outputs_to_host(h, batch, boxes, scores, cls, count);
 }
 
-extern "C" int y355_max_det(y355_engine *h) { return h ? h->head.max_det : Y355_EINVAL; }
-extern "C" int y355_num_anchors_total(y355_engine *h) { return h ? h->N : Y355_EINVAL; }
+extern "C" int y355_max_det(y355_engine *h) { return h ? h->core.head.max_det : Y355_EINVAL; }
+extern "C" int y355_num_anchors_total(y355_engine *h) { return h ? h->core.N : Y355_EINVAL; }
 
 // Evaluator-side step right after the path: `bboxes *= [[w, h, w, h]]` of every image
 // (test.py:88-90, utils/vocapi_evaluator_mask.py:71-72, utils/cocoapi_evaluator.py:77-85) for a whole batch on
@@ -1077,11 +956,7 @@ void y355_launch_scale_boxes(float *boxes, const int32_t *count, const float *wh
 }
 extern "C" int y355_scale_boxes(y355_engine *h, float *boxes_dev, const int32_t *count_dev, const float *wh_dev, int batch) {
     if (!h || !boxes_dev || !count_dev || !wh_dev) return fail(Y355_EINVAL, "null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_EINVAL, "batch out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    y355_launch_scale_boxes(boxes_dev, count_dev, wh_dev, batch, y355_max_det(h), h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return y355_core_scale_boxes(&h->core, boxes_dev, count_dev, wh_dev, batch);
 }
 
 extern "C" int y355_pack_front_weights(const int8_t *q_w1, const int8_t *q_w2, int8_t *dst) {
@@ -1093,12 +968,12 @@ extern "C" int y355_pack_front_weights(const int8_t *q_w1, const int8_t *q_w2, i
 // diagnostic: record s_memtime stamps of the production conv kernel of `layer` (-1 = off)
 extern "C" int y355_debug_stamps(y355_engine *h, int layer, unsigned long long *out_host, int nwg) {
     if (!h) return fail(Y355_EINVAL, "null engine");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core)) return rc;
     if (!h->stamps_dev) {
-        if (int rc = dmalloc(h, (void **)&h->stamps_dev, 8 * 32 * Y355_STAMP_ROWS, true)) return rc;
+        if (int rc = y355_core_alloc(&h->core, &h->stamps_dev, 8 * 32 * Y355_STAMP_ROWS, true)) return rc;
     }
     if (out_host) {
-        HIPCHK(hipStreamSynchronize(h->stream));
+        HIPCHK(hipStreamSynchronize(h->core.stream));
         HIPCHK(hipMemcpy(out_host, h->stamps_dev, 8 * 32 * (size_t)(nwg > Y355_STAMP_ROWS ? Y355_STAMP_ROWS : nwg), hipMemcpyDeviceToHost));
     }
     h->stamp_layer = layer;
@@ -1115,47 +990,32 @@ extern "C" int y355_debug_nms_stamps(unsigned long long *out_host) {
     return 0;
 }
 
-extern "C" void *y355_stream(y355_engine *h) { return h ? (void *)h->stream : nullptr; }
+extern "C" void *y355_stream(y355_engine *h) { return h ? (void *)h->core.stream : nullptr; }
 
 extern "C" int y355_sync(y355_engine *h) {
-    if (!h) return fail(Y355_EINVAL, "null engine");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return !h ? fail(Y355_EINVAL, "null engine") : y355_core_sync(&h->core);
 }
 
 extern "C" int y355_profile(y355_engine *h, int enable) {
     if (!h) return fail(Y355_EINVAL, "null engine");
-    h->profile = enable;
+    h->core.profile = enable;
     return 0;
 }
 
 extern "C" int y355_profile_get(y355_engine *h, float *ms) {
-    if (!h || !ms) return fail(Y355_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipEventSynchronize(h->ev[12]));
-    for (int i = 0; i < Y355_NUM_TIMERS; ++i) HIPCHK(hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
-    return 0;
+    return (!h || !ms) ? fail(Y355_EINVAL, "null argument") : y355_core_profile_get(&h->core, Y355_NUM_TIMERS, ms);
 }
 
-extern "C" int y355_profile_kernel_get(y355_engine *h, float *ms) {
+// ms [n]: the first n kernel timers of the last forward (0 where the launch recorded none)
+static int kernel_timers(y355_engine *h, int n, float *ms) {
     if (!h || !ms) return fail(Y355_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipEventSynchronize(h->ev[12]));
-    for (int k = 0; k < 10; ++k) {
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    HIPCHK(hipEventSynchronize(h->core.ev[12]));
+    for (int k = 0; k < n; ++k) {
         ms[k] = 0.f;
         if (h->kev_set[k]) HIPCHK(hipEventElapsedTime(&ms[k], h->kev[k][0], h->kev[k][1]));
     }
     return 0;
 }
-
-extern "C" int y355_profile_kernels_get(y355_engine *h, float *ms) {
-    if (!h || !ms) return fail(Y355_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipEventSynchronize(h->ev[12]));
-    for (int k = 0; k < Y355_NUM_KERNEL_TIMERS; ++k) {
-        ms[k] = 0.f;
-        if (h->kev_set[k]) HIPCHK(hipEventElapsedTime(&ms[k], h->kev[k][0], h->kev[k][1]));
-    }
-    return 0;
-}
+extern "C" int y355_profile_kernel_get(y355_engine *h, float *ms) { return kernel_timers(h, 10, ms); }
+extern "C" int y355_profile_kernels_get(y355_engine *h, float *ms) { return kernel_timers(h, Y355_NUM_KERNEL_TIMERS, ms); }

@@ -7,14 +7,6 @@
 
 #include <algorithm>
 
-int y355_fail(int code, const std::string &msg);
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
-
 static int hip_alloc(void **p, size_t bytes, bool zero) {
     HIPCHK(hipMalloc(p, bytes ? bytes : 16));
     if (zero) {

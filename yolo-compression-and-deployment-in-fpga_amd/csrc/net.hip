@@ -8,7 +8,7 @@
 // kernels of netops.hip.
 #include "../../include/yolo355.h"
 #include "y355_common.h"
-#include "head_nms.h"
+#include "handle_core.h"
 #include "net_arch.h"
 
 #include <algorithm>
@@ -17,15 +17,6 @@
 #include <cstring>
 #include <string>
 #include <vector>
-
-int y355_fail(int code, const std::string &msg);
-int y355_prepare_kernels();
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 
 namespace {
 struct Tensor {
@@ -74,24 +65,19 @@ NetMap map_of(const Tensor &t) { return NetMap{t.dev, t.H, t.W, (int)t.pb}; }
 #define Y355_USE_CONVR 1            // 0 (A/B builds): every layer of the generic nets on convg.hip
 #endif
 struct y355_net {
-    y355_net_config cfg{};
+    y355_net_config cfg{};            // arch, anchors and classes; the rest of it lives in the core
+    HandleCore core;
     const ArchDef *arch = nullptr;
     bool bf = true;
     int es = 2;
-    hipStream_t stream = nullptr;
-    bool own_stream = false;
     std::vector<Tensor> T;
     std::vector<NLayer> L;
     char *w0_dev = nullptr;           // first-layer fragments
-    int predc = 0, N = 0;
-    HeadState head;                   // the head's workspace, max_det, candidate tap
-    unsigned int *absmax_dev = nullptr;
+    int predc = 0;
     // int8 nets: activation exponents (value = q / 2^sa) of the input and of every tensor
     int sa_in = 0;
     bool sa_ok = false;
     std::vector<int> sa;
-    Counters *ctr_dev = nullptr;      // [nops + 1]: the set the last forward counted into (one of ctrs' two)
-    CounterSets ctrs;
     // int8 nets whose graph starts with conv(3 -> 16) + pool, conv(16 -> 32) + pool (SlimYOLOv2, YOLOv3tiny:
     // models/slim_yolo_v2.py:549-575, backbone/darknet.py:216-220): both layers in ONE launch of the q_bf engine's fused front
     // end (front.hip) when their epilogues are exact in fp32 (y355_front_eligible); tap forwards run the layers one by one
@@ -102,12 +88,6 @@ struct y355_net {
     Requant frq1{}, frq2{};
     int no_pxb = 0;                   // Y355_NET_OPT_THIN_RESIDENT = 0: the thin 3x3 layers of the bf16 graphs on convr.hip instead of convpxb.hip
     int tput_wgs = 0;                 // Y355_NET_OPT_WORKGROUPS: persistent workgroups per convr launch while several handles share the GPU (0 = one per CU)
-    int profile = 0;
-    std::vector<hipEvent_t> ev;
-    std::vector<void *> allocs;
-    // uint8 frame input (y355_net_forward_u8, y355_net_forward_frames): BaseTransform constants, the resize tables for one
-    // source size, and the resized frames the conv1 / fused front-end routes read when the frames are not at the network size
-    FrameStage stage;
     // calibration on the int8 graph (y355_net_calibrate): AveragedRangeTracker state of the network input [0] and of every
     // tensor [1 + t] (models/slim_yolo_v2.py:13-14), and one slot of maxima per op ([nops]: the input) on the device
     std::vector<float> trk_scale;
@@ -130,22 +110,9 @@ struct NetInput {
 
 static int in_kbytes(const y355_net *h, const OpDef &o);
 
-static int nmalloc(y355_net *h, void **p, size_t bytes, bool zero) {
-    HIPCHK(hipMalloc(p, bytes ? bytes : 16));
-    h->allocs.push_back(*p);
-    if (zero) HIPCHK(hipMemset(*p, 0, bytes ? bytes : 16));
-    return 0;
-}
-
 extern "C" void y355_net_destroy(y355_net *h) {
     if (!h) return;
-    (void)hipSetDevice(h->cfg.device_id);
-    if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : h->allocs) (void)hipFree(p);
-    y355_head_destroy(h->head);
-    y355_stage_destroy(h->stage);
-    for (auto &e : h->ev) (void)hipEventDestroy(e);
-    if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
+    y355_core_close(&h->core);
     delete h;
 }
 
@@ -155,23 +122,15 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     if (cfg->dtype != Y355_DT_BF16 && cfg->dtype != Y355_DT_INT8) return y355_fail(Y355_EINVAL, "unknown dtype");
     // SlimYOLOv2 has four 2x2 pools (stride 16: models/slim_yolo_v2.py:52); the other graphs reach stride 32
     const int mult = cfg->arch == Y355_ARCH_SLIM_V2 ? 16 : 32;
-    if (cfg->height <= 0 || cfg->width <= 0 || cfg->height % mult || cfg->width % mult)
-        return y355_fail(Y355_EINVAL, cfg->arch == Y355_ARCH_SLIM_V2 ? "input size must be a positive multiple of 16"
-                                                                      : "input size must be a positive multiple of 32");
     const ArchDef &A = kArch[cfg->arch];
-    if (cfg->num_anchors < 1 || cfg->num_anchors * A.nlev > Y355_HEAD_MAXA || cfg->num_classes < 1)
-        return y355_fail(Y355_EINVAL, "bad anchors / classes");
-    if (cfg->max_batch < 1) return y355_fail(Y355_EINVAL, "max_batch < 1");
     const int predc = cfg->num_anchors * (5 + cfg->num_classes);
-    if (predc > 256) return y355_fail(Y355_EINVAL, "A*(5+C) > 256 not supported");
     int N = 0;
     for (int l = 0; l < A.nlev; ++l) N += (cfg->height / (int)A.stride[l]) * (cfg->width / (int)A.stride[l]) * cfg->num_anchors;
-    const int Hb = cfg->height / (int)A.stride[0], Wb = cfg->width / (int)A.stride[0];
-    (void)Hb;
-    (void)Wb;
     // (the candidate sort of these heads bins by area octave or class on a grid of at most 16 x 16: 16 x 256 bins fit its
     // 4096-entry tables whatever the number of anchors; heads of more than 4096 anchors are thresholded and compacted first)
-    if (N > Y355_NMS_MAX_CAP) return y355_fail(Y355_EINVAL, "more than 65536 anchors per image not supported");
+    if (int rc = y355_core_check_config(cfg->height, cfg->width, mult, cfg->num_anchors, Y355_HEAD_MAXA / A.nlev, cfg->num_classes,
+                                        cfg->max_batch, N))
+        return rc;
     HIPCHK(hipSetDevice(cfg->device_id));
     if (int e = y355_prepare_kernels()) return e;
     if (y355_prepare_convr(cfg->device_id)) return y355_fail(Y355_EHIP, "hipFuncSetAttribute(convr) / sink allocation failed");
@@ -183,18 +142,9 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
     h->es = h->bf ? 2 : 1;
     h->predc = predc;
     h->sa.assign(A.ntensors, 0);
-    h->N = N;
-    y355_stage_init(h->stage, cfg->height, cfg->width, cfg->max_batch, y355_hip_mem());
-    if (!cfg->own_stream) h->stream = (hipStream_t)cfg->stream;
-    else {
-        if (hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking) != hipSuccess) {
-            delete h;
-            return y355_fail(Y355_EHIP, "hipStreamCreate failed");
-        }
-        h->own_stream = true;
-    }
     const int B = cfg->max_batch;
-    int rc = 0;
+    int rc = y355_core_open(&h->core, cfg->device_id, cfg->stream, cfg->own_stream != 0, cfg->height, cfg->width, B, N, cfg->conf_thresh,
+                            cfg->nms_thresh, y355_hip_mem());
     h->T.resize(A.ntensors);
     for (int i = 0; i < A.ntensors && !rc; ++i) {
         Tensor &t = h->T[i];
@@ -208,7 +158,7 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
         t.Cpad = t.pred ? y355_pred_channels(t.C) : (t.C + cq - 1) / cq * cq;
         t.pb = (size_t)t.Cpad * ((t.pred && h->bf) ? 4 : h->es);
         t.bytes = ((size_t)B * (t.H + 2 * t.halo) * (t.W + 2 * t.halo) + 64) * t.pb;
-        rc = nmalloc(h, (void **)&t.dev, t.bytes, true);
+        rc = y355_core_alloc(&h->core, &t.dev, t.bytes, true);
     }
     h->L.resize(A.nlayers);
     for (int i = 0; i < A.nops && !rc; ++i) {
@@ -224,10 +174,10 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
         L.ksize = o.ksize;
         if (o.type == OP_CONV1) {
             L.cout_pad = 16;
-            rc = nmalloc(h, (void **)&h->w0_dev, 2048, true);
+            rc = y355_core_alloc(&h->core, &h->w0_dev, 2048, true);
         } else {
             const Tensor &ti = h->T[o.in];
-            L.kid = y355_convg_select(in_kbytes(h, o), L.cout, o.pool, ti.H, ti.W, o.stride2 ? 2 : 1, h->cfg.max_batch);
+            L.kid = y355_convg_select(in_kbytes(h, o), L.cout, o.pool, ti.H, ti.W, o.stride2 ? 2 : 1, h->core.max_batch);
             if (L.kid < 0) { rc = y355_fail(Y355_EINVAL, "no convolution kernel for a layer of this graph"); break; }
             const ConvGInfo &ki = *y355_convg_kernel(h->bf, L.kid);
             if (in_kbytes(h, o) % ki.chb) { rc = y355_fail(Y355_EINVAL, "input channels not a multiple of the kernel's chunk"); break; }
@@ -238,31 +188,31 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
                 break;
             }
             L.w_bytes = y355_convg_packed_bytes(ki, in_kbytes(h, o), o.ksize * o.ksize, L.cout_pad);
-            rc = nmalloc(h, (void **)&L.w_dev, L.w_bytes, true);
+            rc = y355_core_alloc(&h->core, &L.w_dev, L.w_bytes, true);
             // (the pointwise launcher derives its k-steps from the input buffer's pixel pitch and has no pool: only an op that
             // consumes the WHOLE buffer, unpooled, may take it -- ADVICE r3)
             if (!rc && !h->bf && o.ksize == 1 && !o.stride2 && !o.res1 && !o.pool && ti.pb == in_kbytes(h, o) && L.cout_pad % 64 == 0 &&
                 in_kbytes(h, o) % 64 == 0 && in_kbytes(h, o) <= 1024 && Y355_USE_CONVR) {                              // int8 1x1: pointwise kernel of convr.hip (when the epilogue fits 32 bits)
                 L.rid = -2;
                 L.wr_bytes = (size_t)(in_kbytes(h, o) / 64) * (L.cout_pad / 16) * 1024;
-                rc = nmalloc(h, (void **)&L.wr_dev, L.wr_bytes, true);
+                rc = y355_core_alloc(&h->core, &L.wr_dev, L.wr_bytes, true);
             }
             if (!rc && h->bf && o.ksize == 3 && !o.stride2 && !o.res1 && !h->T[o.out].pred && Y355_USE_CONVPXB) {
                 L.pbid = y355_convpxb_select(in_kbytes(h, o), L.cout, o.pool);
                 if (L.pbid >= 0 && ((int)ti.pb != in_kbytes(h, o) || L.cout_pad != L.cout)) L.pbid = -1;     // whole-pixel inputs only
-                if (L.pbid >= 0) rc = nmalloc(h, (void **)&L.wpb_dev, y355_convpxb_packed_bytes(L.pbid), true);
+                if (L.pbid >= 0) rc = y355_core_alloc(&h->core, &L.wpb_dev, y355_convpxb_packed_bytes(L.pbid), true);
             }
             if (!rc && o.ksize == 3 && !o.stride2 && !o.res1 && Y355_USE_CONVR) {
                 L.rid = y355_convr_select(h->bf ? 1 : 0, in_kbytes(h, o), L.cout_pad, o.pool, ti.H, ti.W);
                 if (L.rid >= 0) {
                     L.wr_bytes = (size_t)(in_kbytes(h, o) / 64) * 9 * (L.cout_pad / 16) * 1024;
-                    rc = nmalloc(h, (void **)&L.wr_dev, L.wr_bytes, true);
+                    rc = y355_core_alloc(&h->core, &L.wr_dev, L.wr_bytes, true);
                 }
             }
         }
-        if (!rc) rc = nmalloc(h, (void **)&L.bias_dev, sizeof(float) * L.cout_pad, true);
-        if (!rc) rc = nmalloc(h, (void **)&L.bias_w_dev, sizeof(long long) * L.cout_pad, true);
-        if (!rc && !h->bf) rc = nmalloc(h, (void **)&L.shl_dev, sizeof(int) * L.cout_pad, true);
+        if (!rc) rc = y355_core_alloc(&h->core, &L.bias_dev, sizeof(float) * L.cout_pad, true);
+        if (!rc) rc = y355_core_alloc(&h->core, &L.bias_w_dev, sizeof(long long) * L.cout_pad, true);
+        if (!rc && !h->bf) rc = y355_core_alloc(&h->core, &L.shl_dev, sizeof(int) * L.cout_pad, true);
     }
     if (!rc && A.nops >= 2) {
         const OpDef &o0 = A.ops[0], &o1 = A.ops[1];
@@ -274,31 +224,17 @@ extern "C" int y355_net_create(const y355_net_config *cfg, y355_net **out) {
             if (A.ops[i].in == o0.out || A.ops[i].res1 - 1 == o0.out) fg = false;
         if (fg) {
             h->front_graph = true;
-            rc = nmalloc(h, (void **)&h->wf_dev, h->bf ? 32768 : 16384, true);      // y355_pack_frontb / y355_pack_front
-            if (!rc && !h->bf) rc = nmalloc(h, (void **)&h->fb1_dev, sizeof(int) * 16, true);
-            if (!rc && !h->bf) rc = nmalloc(h, (void **)&h->fb2_dev, sizeof(int) * 32, true);
+            rc = y355_core_alloc(&h->core, &h->wf_dev, h->bf ? 32768 : 16384, true);      // y355_pack_frontb / y355_pack_front
+            if (!rc && !h->bf) rc = y355_core_alloc(&h->core, &h->fb1_dev, sizeof(int) * 16, true);
+            if (!rc && !h->bf) rc = y355_core_alloc(&h->core, &h->fb2_dev, sizeof(int) * 32, true);
         }
     }
-    if (!rc) rc = nmalloc(h, (void **)&h->absmax_dev, 16, true);
-    if (!rc) rc = nmalloc(h, (void **)&h->ctr_dev, sizeof(Counters) * 2 * (A.nops + 1), true);
-    if (!rc && !h->bf) rc = nmalloc(h, (void **)&h->cal_dev, sizeof(Counters) * (A.nops + 1), true);
+    if (!rc && !h->bf) rc = y355_core_alloc(&h->core, &h->cal_dev, sizeof(Counters) * (A.nops + 1), true);
     h->trk_scale.assign(A.ntensors + 1, 0.f);
     h->trk_first.assign(A.ntensors + 1, 0);
-    h->ctrs.base = h->ctr_dev;
-    h->ctrs.n = A.nops + 1;
-    h->ctrs.clean[0] = h->ctrs.clean[1] = true;
-    if (!rc) rc = y355_head_create(h->head, N, B, cfg->max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, true, false, y355_hip_mem());
-    if (!rc) {
-        h->ev.resize(A.nops + 3);
-        for (auto &e : h->ev)
-            if (hipEventCreate(&e) != hipSuccess) { rc = y355_fail(Y355_EHIP, "hipEventCreate failed"); break; }
-    }
-    if (rc) {
-        std::string keep = y355_last_error();
-        y355_net_destroy(h);
-        y355_fail(rc, keep);
-        return rc;
-    }
+    if (!rc) rc = y355_core_state(&h->core, A.nops + 1, cfg->max_det, false);
+    if (!rc) rc = y355_core_events(&h->core, A.nops + 2);
+    if (rc) return y355_core_unwind(rc, [h] { y355_net_destroy(h); });
     *out = h;
     return 0;
 }
@@ -307,14 +243,9 @@ extern "C" int y355_net_set_option(y355_net *h, int option, int value) {
     if (!h) return y355_fail(Y355_EINVAL, "null net");
     if (option == Y355_NET_OPT_MAX_CANDIDATES || option == Y355_NET_OPT_HEAD_ROUTE) {
         const bool is_cap = option == Y355_NET_OPT_MAX_CANDIDATES;
-        if (int rc = y355_head_check_option(h->N, is_cap, value,
-                                            is_cap ? "Y355_NET_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)"
-                                                   : "Y355_NET_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)"))
-            return rc;
-        HIPCHK(hipSetDevice(h->cfg.device_id));
-        HIPCHK(hipStreamSynchronize(h->stream));         // nothing in flight reads the arrays that go
-        if (y355_head_set_option(h->head, is_cap, value)) return y355_fail(Y355_EHIP, "device allocation failed");
-        return 0;
+        return y355_core_head_option(&h->core, is_cap, value,
+                                     is_cap ? "Y355_NET_OPT_MAX_CANDIDATES: 4096 .. min(anchors per image, 65536)"
+                                            : "Y355_NET_OPT_HEAD_ROUTE takes 0 (auto) or 1 (large)");
     }
     if (option == Y355_NET_OPT_WORKGROUPS) {
         if (value < 0 || value > 256) return y355_fail(Y355_EINVAL, "workgroups per launch: 0 .. 256");
@@ -330,17 +261,14 @@ extern "C" int y355_net_set_option(y355_net *h, int option, int value) {
 }
 
 extern "C" int y355_net_set_thresholds(y355_net *h, float conf, float nms) {
-    if (!h) return y355_fail(Y355_EINVAL, "null net");
-    h->cfg.conf_thresh = conf;
-    h->cfg.nms_thresh = nms;
-    return 0;
+    return !h ? y355_fail(Y355_EINVAL, "null net") : y355_core_set_thresholds(&h->core, conf, nms);
 }
 
 extern "C" int y355_net_num_layers(y355_net *h) { return h ? h->arch->nlayers : Y355_EINVAL; }
 extern "C" int y355_net_num_tensors(y355_net *h) { return h ? h->arch->ntensors : Y355_EINVAL; }
-extern "C" int y355_net_max_candidates(y355_net *h) { return h ? y355_head_capacity(h->head) : Y355_EINVAL; }
-extern "C" int y355_net_max_det(y355_net *h) { return h ? h->head.max_det : Y355_EINVAL; }
-extern "C" int y355_net_num_anchors_total(y355_net *h) { return h ? h->N : Y355_EINVAL; }
+extern "C" int y355_net_max_candidates(y355_net *h) { return h ? y355_head_capacity(h->core.head) : Y355_EINVAL; }
+extern "C" int y355_net_max_det(y355_net *h) { return h ? h->core.head.max_det : Y355_EINVAL; }
+extern "C" int y355_net_num_anchors_total(y355_net *h) { return h ? h->core.N : Y355_EINVAL; }
 
 extern "C" int y355_net_layer_shape(y355_net *h, int idx, int32_t *shape) {
     if (!h || !shape || idx < 0 || idx >= h->arch->nlayers) return y355_fail(Y355_EINVAL, "bad argument");
@@ -367,8 +295,8 @@ extern "C" int y355_net_load_layer_f32(y355_net *h, int idx, const float *w, con
                  cout, cin, ksize, ksize);
         return y355_fail(Y355_EINVAL, buf);
     }
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     const OpDef &o = h->arch->ops[L.op];
     if (o.type == OP_CONV1) {
         char frag[2048];
@@ -423,8 +351,8 @@ static int load_layer_i8(y355_net *h, int idx, const int8_t *q_w, const int32_t 
     }
     for (int c = 0; e_wc && c < cout; ++c)                     // (cout is the layer's own by now)
         if (e_wc[c] < -128 || e_wc[c] > 128) return y355_fail(Y355_EINVAL, "weight exponent out of range");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     const OpDef &o = h->arch->ops[L.op];
     if (o.type == OP_CONV1) {
         int8_t frag[1024];
@@ -684,7 +612,7 @@ static int refresh_layer_i8(y355_net *h, int i) {
         L.rq1.gen32 = fits32(cf, cf.tw, sh) ? 1 : 0;
         std::vector<int32_t> bt(L.cout_pad, 0);
         if (L.rq1.gen32) for (int c = 0; c < L.cout; ++c) bt[c] = (int32_t)cf.bw[c];
-        HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int32_t) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int32_t) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
     }
     if (h->front_graph && (i == 0 || i == 1)) {
         // the same epilogue for front.hip: t = acc * 2^shl + bias below 2^24 (exact in fp32) on the layer's own weights
@@ -696,21 +624,22 @@ static int refresh_layer_i8(y355_net *h, int i) {
         fr.wide = (fr.tmax_log2 > 24 || cf.bmax >= std::ldexp(1.0L, 24) || sh > 30 || sh - lk < -8 || nm < 1 || nm > (1 << lk)) ? 1 : 0;
         std::vector<int32_t> fb(i == 0 ? 16 : 32, 0);
         if (!fr.wide) for (int c = 0; c < L.cout; ++c) fb[c] = (int32_t)cf.bw[c];
-        HIPCHK(hipMemcpyAsync(i == 0 ? h->fb1_dev : h->fb2_dev, fb.data(), sizeof(int32_t) * fb.size(), hipMemcpyHostToDevice, h->stream));
+        HIPCHK(hipMemcpyAsync(i == 0 ? h->fb1_dev : h->fb2_dev, fb.data(), sizeof(int32_t) * fb.size(), hipMemcpyHostToDevice, h->core.stream));
         h->front_dirty = true;
     }
     // every output channel's own accumulator shift: in the upper half of the bias word for the 32-bit epilogues of
     // convg.hip / convr.hip (y355_pc_word; the bias fits 32 bits there), in shl_dev for the 64-bit ones and for conv1.hip
     if (o.type == OP_CONV && L.rq.narrow)
         for (int c = 0; c < L.cout; ++c) cf.bw[c] = y355_pc_word(cf.shc[c], (int)cf.bw[c]);
-    HIPCHK(hipMemcpyAsync(L.shl_dev, cf.shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(L.bias_w_dev, cf.bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(L.shl_dev, cf.shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipMemcpyAsync(L.bias_w_dev, cf.bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     L.dirty = false;
     return 0;
 }
 
 static int refresh_i8(y355_net *h) {
+    if (h->bf) return 0;                                         // (bf16 nets have no epilogue constants)
     if (!h->sa_ok) return y355_fail(Y355_ENOTREADY, "activation exponents not set (calibrate first)");
     for (int i = 0; i < h->arch->nops; ++i)
         if (int rc = refresh_layer_i8(h, i)) return rc;
@@ -743,10 +672,10 @@ template <class P>
 static void fill_input(P &p, const y355_net *h, const NetInput &in, int B) {
     p.x = in.x;
     p.x_u8 = in.u8;
-    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->stage.norm.mean[c]; p.nstd[c] = h->stage.norm.sd[c]; }
+    for (int c = 0; c < 3; ++c) { p.nmean[c] = h->core.stage.norm.mean[c]; p.nstd[c] = h->core.stage.norm.sd[c]; }
     p.B = B;
-    p.H = h->cfg.height;
-    p.W = h->cfg.width;
+    p.H = h->core.H;
+    p.W = h->core.W;
 }
 
 // what a launch of run_op is for.  The two passes of a calibration step (y355_net_calibrate) run on the generic kernels:
@@ -756,7 +685,7 @@ enum Pass { PASS_FORWARD = 0, PASS_CAL_STAT, PASS_CAL_WRITE };
 
 static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
     const OpDef &o = h->arch->ops[i];
-    hipStream_t s = h->stream;
+    hipStream_t s = h->core.stream;
     const bool stat = pass == PASS_CAL_STAT, generic_only = pass != PASS_FORWARD;
     const bool bf = h->bf;
     if (o.type == OP_CONV1) {
@@ -772,7 +701,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
             p.bias_w = L.bias_w_dev;
             p.bias_t = L.rq1.gen32 ? (const int *)L.bias_dev : nullptr;          // (never in a statistics pass)
             p.shl_c = L.pc || stat ? L.shl_dev : nullptr;
-            p.ctr = (stat ? h->cal_dev : h->ctr_dev) + i;
+            p.ctr = (stat ? h->cal_dev : h->core.ctr_dev) + i;
             y355_conv1_tiles(p.H, p.W, &p.tiles_x, &p.tiles_y);
             p.in_scale = std::ldexp(1.0f, h->sa_in);
             p.rq = L.rq1;
@@ -803,7 +732,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
         p.bias_w = L.bias_w_dev;
         p.shl_w = L.shl_dev;
         p.pc = L.pc ? 1 : 0;
-        p.ctr = (stat ? h->cal_dev : h->ctr_dev) + i;
+        p.ctr = (stat ? h->cal_dev : h->core.ctr_dev) + i;
         p.rq = L.rq;
         const int rflags = bf ? 0 : ((L.rq.narrow ? 0 : Y355_ROUTE_EPI64) | (o.res1 ? Y355_ROUTE_RESIDUAL : 0) | (L.pc ? Y355_ROUTE_PER_CHANNEL : 0));
         p.B = B;
@@ -857,7 +786,7 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
             ConvGParams q = p;
             q.w = L.wr_dev;
             q.nblk = L.cout_pad / y355_convr_info(L.rid)->bn;
-            if (y355_launch_convr(L.rid, q, h->cfg.device_id, s)) {
+            if (y355_launch_convr(L.rid, q, h->core.device_id, s)) {
                 L.route = Y355_ROUTE_RING | rflags;
                 HIPCHK(hipGetLastError());
                 return 0;
@@ -866,15 +795,15 @@ static int run_op(y355_net *h, int i, int B, const NetInput &in, Pass pass) {
         L.route = (ki.wm * ki.wn == 8 ? Y355_ROUTE_GENERIC8 : Y355_ROUTE_GENERIC4) | rflags;
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * B, s);
     } else if (o.type == OP_INPUT) {
-        y355_launch_input(bf, in.x, in.u8, in.tab, in.sh, in.sw, h->stage.norm, map_of(h->T[o.out]), B, bf ? 1.0f : std::ldexp(1.0f, h->sa_in),
-                          h->ctr_dev + i, s);
+        y355_launch_input(bf, in.x, in.u8, in.tab, in.sh, in.sw, h->core.stage.norm, map_of(h->T[o.out]), B, bf ? 1.0f : std::ldexp(1.0f, h->sa_in),
+                          h->core.ctr_dev + i, s);
     } else if (o.type == OP_POOL) {
         y355_launch_pool(bf, map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin * h->es, o.pool ? 1 : 2, s);
     } else if (o.type == OP_SPP) {
         y355_launch_spp(bf, map_of(h->T[o.in]), B, o.cin, s);
     } else if (o.type == OP_REORG) {
         y355_launch_reorg(bf, map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin, o.choff * h->es, o.ksize,
-                          bf ? 0 : h->sa[o.out] - h->sa[o.in], h->ctr_dev + i, s);
+                          bf ? 0 : h->sa[o.out] - h->sa[o.in], h->core.ctr_dev + i, s);
     } else {                                                   // OP_UPSAMPLE (int8: y355_net_create checked y355_upsample_i8_ok)
         y355_launch_upsample(bf, map_of(h->T[o.in]), map_of(h->T[o.out]), B, o.cin, o.choff * h->es,
                              bf ? 1.0f : std::ldexp(1.0f, h->sa[o.out] - h->sa[o.in]), s);
@@ -907,22 +836,15 @@ static HeadParams net_head_params(y355_net *h, float *ob, float *os, int *oc, in
     // (YOLOv3tiny int8, B = 128: NMS 1.08 -> 0.50 ms; SlimYOLOv2 bf16: 0.45 -> 0.32 ms)
     y355_head_area_bins(p, h->T[A.pred_t[0]].H, h->T[A.pred_t[0]].W);
     p.pairs_wgs = h->tput_wgs > 0 ? 1 : 0;        // throughput mode: the pair walk holds one CU per image
-    y355_head_fill(p, h->head, h->cfg.conf_thresh, h->cfg.nms_thresh, h->cfg.height, h->cfg.width, ob, os, oc, on, tap);
+    y355_head_fill(p, h->core.head, h->core.conf_thresh, h->core.nms_thresh, h->core.H, h->core.W, ob, os, oc, on, tap);
     return p;
-}
-
-// batch within the handle's; a frame size (none: 1 x 1) within the resize stage's
-static int range_check(const y355_net *h, int batch, int frame_h = 1, int frame_w = 1) {
-    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "batch out of range");
-    if (frame_h < 1 || frame_w < 1 || frame_h > 16384 || frame_w > 16384) return y355_fail(Y355_EINVAL, "bad frame size");
-    return 0;
 }
 
 // the stage in front of the first op: frames of another size (in.stage), or a frame list (every frame through the ragged
 // stage), resized into the net-owned buffer the first op reads
 static int pre_stage(y355_net *h, const NetInput &in, int batch) {
-    if (in.stage) y355_launch_resize_u8(in.stage, h->stage.frames, in.tab, batch, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stream);
-    if (in.list) y355_launch_resize_frames(in.list, batch, h->stage.frames, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
+    if (in.stage) y355_launch_resize_u8(in.stage, h->core.stage.frames, in.tab, batch, in.sh, in.sw, h->core.H, h->core.W, h->core.stream);
+    if (in.list) y355_launch_resize_frames(in.list, batch, h->core.stage.frames, h->core.stage.tabs, h->core.H, h->core.W, h->core.stream);
     if (in.stage || in.list) HIPCHK(hipGetLastError());
     return 0;
 }
@@ -930,18 +852,15 @@ static int pre_stage(y355_net *h, const NetInput &in, int batch) {
 // the forward behind y355_net_forward and y355_net_forward_u8 (arguments checked, device set, int8 exponents refreshed)
 static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, float *boxes_dev, float *scores_dev, int32_t *cls_dev,
                        int32_t *count_dev) {
-    const bool prof = h->profile != 0;
+    const bool prof = h->core.profile != 0;
     const int nops = h->arch->nops;
-    if (!h->bf) {
-        bool need_zero = false;
-        h->ctr_dev = h->ctrs.begin(&need_zero);        // steady state: zeroed by the previous forward's fused front end
-        if (need_zero) HIPCHK((hipError_t)y355_zero_counters(h->ctr_dev, nops + 1, h->stream));
-    }
+    if (!h->bf)
+        if (int rc = y355_core_begin_counters(&h->core)) return rc;
     // tap forwards (parity tests read every tensor) run the first two layers one by one: the fused launch does not write conv1's map
     const bool fuse_front = h->front_graph && (h->bf || h->front_ok) && !(flags & Y355_F_TAP);
     h->t0_skipped = fuse_front;
     for (int i = 0; i < nops; ++i) {
-        if (prof) HIPCHK(hipEventRecord(h->ev[i], h->stream));
+        if (prof) HIPCHK(hipEventRecord(h->core.ev[i], h->core.stream));
         if (i == 0)                                     // (inside the first op's profile interval)
             if (int rc = pre_stage(h, in, batch)) return rc;
         if (fuse_front && i < 2) {
@@ -959,7 +878,7 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
                 y355_frontb_tiles(fb.H, fb.W, &fb.tiles_x, &fb.tiles_y);
                 fb.slope1 = act_slope(o0.act);
                 fb.slope2 = act_slope(o1.act);
-                y355_launch_frontb(fb, h->stream);
+                y355_launch_frontb(fb, h->core.stream);
             } else {
                 FrontParams fp{};
                 fill_input(fp, h, in, batch);
@@ -967,14 +886,14 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
                 fp.wf = h->wf_dev;
                 fp.bias1 = h->fb1_dev;
                 fp.bias2 = h->fb2_dev;
-                fp.ctr = h->ctr_dev;                                // [0] conv1 (+ input), [1] conv2: the two ops' own counters
-                fp.zero_next = (unsigned long long *)h->ctrs.other_zeroed_by_front();
+                fp.ctr = h->core.ctr_dev;                                // [0] conv1 (+ input), [1] conv2: the two ops' own counters
+                fp.zero_next = (unsigned long long *)h->core.ctrs.other_zeroed_by_front();
                 fp.zero_n = (nops + 1) * (int)(sizeof(Counters) / 8);
                 y355_front_tiles(fp.H, fp.W, &fp.tiles_x, &fp.tiles_y);
                 fp.in_scale = std::ldexp(1.0f, h->sa_in);
                 fp.rq1 = h->frq1;
                 fp.rq2 = h->frq2;
-                y355_launch_front(fp, h->stream);
+                y355_launch_front(fp, h->core.stream);
             }
             h->L[o0.layer].route = h->L[o1.layer].route = Y355_ROUTE_FRONT;
             HIPCHK(hipGetLastError());
@@ -982,21 +901,19 @@ static int net_forward(y355_net *h, const NetInput &in, int batch, int flags, fl
         }
         if (int rc = run_op(h, i, batch, in, PASS_FORWARD)) return rc;
     }
-    if (prof) HIPCHK(hipEventRecord(h->ev[nops], h->stream));
+    if (prof) HIPCHK(hipEventRecord(h->core.ev[nops], h->core.stream));
     const HeadParams hp = net_head_params(h, boxes_dev, scores_dev, cls_dev, count_dev, (flags & Y355_F_TAP) != 0);
-    y355_launch_head_nms(hp, batch, h->head, h->stream, prof ? h->ev[nops + 1] : nullptr);
+    y355_launch_head_nms(hp, batch, h->core.head, h->core.stream, prof ? h->core.ev[nops + 1] : nullptr);
     HIPCHK(hipGetLastError());
-    if (prof) HIPCHK(hipEventRecord(h->ev[nops + 2], h->stream));
+    if (prof) HIPCHK(hipEventRecord(h->core.ev[nops + 2], h->core.stream));
     return 0;
 }
 
 extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int flags, float *boxes_dev, float *scores_dev,
                                 int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !x_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = range_check(h, batch)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (!h->bf)
-        if (int rc = refresh_i8(h)) return rc;
+    if (int rc = y355_core_enter(&h->core, batch)) return rc;
+    if (int rc = refresh_i8(h)) return rc;
     NetInput in;
     in.x = x_dev;
     return net_forward(h, in, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
@@ -1005,7 +922,7 @@ extern "C" int y355_net_forward(y355_net *h, const float *x_dev, int batch, int 
 // BaseTransform constants of the uint8 input, in the reference's BGR order (data/__init__.py:50), as y355_set_normalization
 extern "C" int y355_net_set_normalization(y355_net *h, const float *mean_bgr, const float *std_bgr) {
     if (!h || !mean_bgr || !std_bgr) return y355_fail(Y355_EINVAL, "null argument");
-    return y355_stage_set_normalization(h->stage, mean_bgr, std_bgr);
+    return y355_stage_set_normalization(h->core.stage, mean_bgr, std_bgr);
 }
 
 // Camera frames as cv2 delivers them, uint8 HWC BGR [B][src_h][src_w][3], as the network's first input: BaseTransform
@@ -1022,13 +939,13 @@ static int u8_input(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w
     in->sh = src_h;
     in->sw = src_w;
     const bool fused = h->arch->ops[0].type == OP_INPUT;              // the input op resizes in its own load
-    if (src_h == h->cfg.height && src_w == h->cfg.width && (fused || !align4 || ((uintptr_t)frames_dev & 3) == 0)) return 0;
-    if (int rc = y355_stage_tables_for(h->stage, src_h, src_w, h->stream)) return rc;
-    in->tab = h->stage.tab;
+    if (src_h == h->core.H && src_w == h->core.W && (fused || !align4 || ((uintptr_t)frames_dev & 3) == 0)) return 0;
+    if (int rc = y355_stage_tables_for(h->core.stage, src_h, src_w, h->core.stream)) return rc;
+    in->tab = h->core.stage.tab;
     if (!fused) {                                                   // staged: pre_stage resizes into the stage's frames first
-        if (int rc = y355_stage_need_frames(h->stage)) return rc;
+        if (int rc = y355_stage_need_frames(h->core.stage)) return rc;
         in->stage = frames_dev;
-        in->u8 = h->stage.frames;
+        in->u8 = h->core.stage.frames;
     }
     return 0;
 }
@@ -1036,10 +953,8 @@ static int u8_input(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w
 extern "C" int y355_net_forward_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int flags,
                                    float *boxes_dev, float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !frames_dev || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = range_check(h, batch, src_h, src_w)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (!h->bf)
-        if (int rc = refresh_i8(h)) return rc;
+    if (int rc = y355_core_enter(&h->core, batch, src_h, src_w)) return rc;
+    if (int rc = refresh_i8(h)) return rc;
     NetInput in;
     if (int rc = u8_input(h, frames_dev, src_h, src_w, true, &in)) return rc;
     return net_forward(h, in, batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
@@ -1048,12 +963,8 @@ extern "C" int y355_net_forward_u8(y355_net *h, const uint8_t *frames_dev, int s
 // parity tap of the resize stage: frames [B][src_h][src_w][3] -> out_dev [B][H][W][3] at the network size, on the net's stream
 extern "C" int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, uint8_t *out_dev) {
     if (!h || !frames_dev || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = range_check(h, batch, src_h, src_w)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (int rc = y355_stage_tables_for(h->stage, src_h, src_w, h->stream)) return rc;
-    y355_launch_resize_u8(frames_dev, out_dev, h->stage.tab, batch, src_h, src_w, h->cfg.height, h->cfg.width, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
+    if (int rc = y355_core_enter(&h->core, batch, src_h, src_w)) return rc;
+    return y355_core_resize_u8(&h->core, frames_dev, src_h, src_w, batch, out_dev);
 }
 
 // ---- frame lists: every frame with its own pointer, size and pitch (the reference's callers: one image at a time, each of
@@ -1061,17 +972,17 @@ extern "C" int y355_net_resize_u8(y355_net *h, const uint8_t *frames_dev, int sr
 // the forward / calibration step then is the same-size uint8 path on that buffer (in.u8 = the frames, no table, no stage).
 // The stage builds its tables on the device and takes the descriptors as kernel arguments: nothing is uploaded, nothing
 // waits, whatever the sizes of the previous call were.
-// the stage's buffers, allocated at the first list call of a handle (frames: a forward / calibration step follows)
-static int net_list_buffers(y355_net *h, bool frames) {
-    if (int rc = y355_stage_need_list(h->stage)) return rc;
-    return frames ? y355_stage_need_frames(h->stage) : 0;
+// the stage's buffers, allocated at the first list call of a handle
+static int net_list_buffers(y355_net *h) {
+    if (int rc = y355_stage_need_list(h->core.stage)) return rc;
+    return y355_stage_need_frames(h->core.stage);
 }
 
 static NetInput list_input(const y355_net *h, const y355_frame *frames) {
     NetInput in;
-    in.u8 = h->stage.frames;
-    in.sh = h->cfg.height;
-    in.sw = h->cfg.width;
+    in.u8 = h->core.stage.frames;
+    in.sh = h->core.H;
+    in.sw = h->core.W;
     in.list = frames;
     return in;
 }
@@ -1079,56 +990,42 @@ static NetInput list_input(const y355_net *h, const y355_frame *frames) {
 extern "C" int y355_net_forward_frames(y355_net *h, const y355_frame *frames, int batch, int flags, float *boxes_dev,
                                        float *scores_dev, int32_t *cls_dev, int32_t *count_dev) {
     if (!h || !frames || !boxes_dev || !scores_dev || !cls_dev || !count_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (!h->bf)
-        if (int rc = refresh_i8(h)) return rc;
-    if (int rc = net_list_buffers(h, true)) return rc;
+    if (int rc = y355_frames_check(frames, batch, h->core.max_batch)) return rc;
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    if (int rc = refresh_i8(h)) return rc;
+    if (int rc = net_list_buffers(h)) return rc;
     return net_forward(h, list_input(h, frames), batch, flags, boxes_dev, scores_dev, cls_dev, count_dev);
 }
 
 // parity tap of the ragged stage: the list -> out_dev [batch][H][W][3] at the network size, on the net's stream
 extern "C" int y355_net_resize_frames(y355_net *h, const y355_frame *frames, int batch, uint8_t *out_dev) {
-    if (!h || !frames || !out_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (int rc = net_list_buffers(h, false)) return rc;
-    y355_launch_resize_frames(frames, batch, out_dev, h->stage.tabs, h->cfg.height, h->cfg.width, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return (!h || !frames || !out_dev) ? y355_fail(Y355_EINVAL, "null argument") : y355_core_resize_frames(&h->core, frames, batch, out_dev);
 }
 
 // the evaluators' `bboxes *= [[w, h, w, h]]` (test.py:88-90) on a forward's outputs, on the net's stream, in place (as
 // y355_scale_boxes): boxes_dev [B][max_det][4], count_dev [B], wh_dev [B][2] (width, height)
 extern "C" int y355_net_scale_boxes(y355_net *h, float *boxes_dev, const int32_t *count_dev, const float *wh_dev, int batch) {
     if (!h || !boxes_dev || !count_dev || !wh_dev) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = range_check(h, batch)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    y355_launch_scale_boxes(boxes_dev, count_dev, wh_dev, batch, h->head.max_det, h->stream);
-    HIPCHK(hipGetLastError());
-    return 0;
+    return y355_core_scale_boxes(&h->core, boxes_dev, count_dev, wh_dev, batch);
 }
 
 extern "C" int y355_net_get_candidates(y355_net *h, int batch, float *boxes, float *scores, int32_t *cls) {
     if (!h || !boxes || !scores || !cls) return y355_fail(Y355_EINVAL, "null argument");
-    if (int rc = range_check(h, batch)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(y355_head_get_candidates(h->head, h->stream, batch, boxes, scores, cls));
-    return 0;
+    return y355_core_get_candidates(&h->core, batch, boxes, scores, cls);
 }
 
 // parity tap: tensor idx as fp32 NCHW [B][C][H][W] on the host (halo and channel padding stripped)
 extern "C" int y355_net_get_tensor(y355_net *h, int idx, int batch, float *dst) {
     if (!h || !dst || idx < 0 || idx >= h->arch->ntensors) return y355_fail(Y355_EINVAL, "bad argument");
-    if (int rc = range_check(h, batch)) return rc;
+    if (int rc = y355_core_range(&h->core, batch)) return rc;
     if (idx == h->arch->ops[0].out && h->t0_skipped)
         return y355_fail(Y355_ENOTREADY, "the first layer's map of the last forward was not written (fused front end): "
                                          "run the forward with Y355_F_TAP to read it");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core)) return rc;
     const Tensor &t = h->T[idx];
     const int Hp = t.H + 2 * t.halo, Wp = t.W + 2 * t.halo;
     std::vector<char> tmp((size_t)batch * Hp * Wp * t.pb);
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     HIPCHK(hipMemcpy(tmp.data(), t.dev, tmp.size(), hipMemcpyDeviceToHost));
     for (int b = 0; b < batch; ++b)
         for (int c = 0; c < t.C; ++c)
@@ -1154,78 +1051,54 @@ extern "C" int y355_net_get_tensor(y355_net *h, int idx, int batch, float *dst) 
 // max |value| of tensor idx (calibration tap for the int8 recipe); synchronous
 extern "C" int y355_net_tensor_absmax(y355_net *h, int idx, int batch, float *out_max) {
     if (!h || !out_max || idx < 0 || idx >= h->arch->ntensors) return y355_fail(Y355_EINVAL, "bad argument");
-    if (int rc = range_check(h, batch)) return rc;
+    if (int rc = y355_core_range(&h->core, batch)) return rc;
     const Tensor &t = h->T[idx];
     if (!h->bf) return y355_fail(Y355_EINVAL, "absmax taps exist on bf16 nets (the calibration run)");
     if (t.pred) return y355_fail(Y355_EINVAL, "prediction maps are fp32: read them with y355_net_get_tensor");
     if (idx == h->arch->ops[0].out && h->t0_skipped)
         return y355_fail(Y355_ENOTREADY, "the first layer's map of the last forward was not written (fused front end): "
                                          "calibrate from a forward with Y355_F_TAP");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipMemsetAsync(h->absmax_dev, 0, 16, h->stream));
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    HIPCHK(hipMemsetAsync(h->core.absmax_dev, 0, 16, h->core.stream));
     const size_t n = (size_t)batch * (t.H + 2) * (t.W + 2) * t.Cpad;
-    y355_launch_absmax_bf16(t.dev, n, h->absmax_dev, h->stream);
-    HIPCHK(hipGetLastError());
-    unsigned int bits = 0;
-    HIPCHK(hipMemcpyAsync(&bits, h->absmax_dev, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    memcpy(out_max, &bits, 4);
-    return 0;
+    y355_launch_absmax_bf16(t.dev, n, h->core.absmax_dev, h->core.stream);
+    return y355_core_absmax_read(&h->core, out_max);
 }
 
 // values clamped to +-127 in the last forward of an int8 net (input quantisation included); synchronous
 extern "C" int y355_net_counters(y355_net *h, int64_t *saturated) {
-    if (!h || !saturated) return y355_fail(Y355_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    std::vector<Counters> c(h->arch->nops + 1);
-    HIPCHK(hipMemcpyAsync(c.data(), h->ctr_dev, sizeof(Counters) * c.size(), hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    int64_t s = 0;
-    for (auto &k : c) s += (int64_t)k.sat + (int64_t)k.in_sat;
-    *saturated = s;
-    return 0;
+    return (!h || !saturated) ? y355_fail(Y355_EINVAL, "null argument") : y355_core_counters(&h->core, saturated, nullptr);
 }
 
 // heads with more than 4096 anchors per image: 1 if, in any forward since the last call, more than 4096 anchors of an
 // image passed conf_thresh (the excess was dropped); synchronous; clears the flags
 extern "C" int y355_net_overflow(y355_net *h, int *overflow) {
-    if (!h || !overflow) return y355_fail(Y355_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(y355_head_overflow_read(h->head, h->stream, overflow));
-    return 0;
+    return (!h || !overflow) ? y355_fail(Y355_EINVAL, "null argument") : y355_core_overflow(&h->core, overflow);
 }
 
 // diagnostics: candidates and suppressing pairs per image of the last forward's NMS (count[batch], nedges[2 * batch]: list
 // length, overflow / abort flag); synchronous
 extern "C" int y355_net_debug_nms(y355_net *h, int batch, int32_t *count, int32_t *nedges) {
-    if (!h || !count || !nedges || batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_EINVAL, "bad argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(y355_head_debug_counts(h->head, h->stream, batch, count, nedges));
+    if (!h || !count || !nedges || batch < 1 || batch > h->core.max_batch) return y355_fail(Y355_EINVAL, "bad argument");
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    HIPCHK(y355_head_debug_counts(h->core.head, h->core.stream, batch, count, nedges));
     return 0;
 }
 
 extern "C" int y355_net_sync(y355_net *h) {
-    if (!h) return y355_fail(Y355_EINVAL, "null net");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    HIPCHK(hipStreamSynchronize(h->stream));
-    return 0;
+    return !h ? y355_fail(Y355_EINVAL, "null net") : y355_core_sync(&h->core);
 }
 
 extern "C" int y355_net_profile(y355_net *h, int enable) {
     if (!h) return y355_fail(Y355_EINVAL, "null net");
-    h->profile = enable;
+    h->core.profile = enable;
     return 0;
 }
 
 extern "C" int y355_net_num_timers(y355_net *h) { return h ? h->arch->nops + 2 : Y355_EINVAL; }
 
 extern "C" int y355_net_profile_get(y355_net *h, float *ms) {
-    if (!h || !ms) return y355_fail(Y355_EINVAL, "null argument");
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    const int n = h->arch->nops + 2;
-    HIPCHK(hipEventSynchronize(h->ev[n]));
-    for (int i = 0; i < n; ++i) HIPCHK(hipEventElapsedTime(&ms[i], h->ev[i], h->ev[i + 1]));
-    return 0;
+    return (!h || !ms) ? y355_fail(Y355_EINVAL, "null argument") : y355_core_profile_get(&h->core, h->arch->nops + 2, ms);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1238,10 +1111,7 @@ extern "C" int y355_net_get_trackers(y355_net *h, float *scale, int32_t *first_a
     if (!h || !scale || !first_a) return y355_fail(Y355_EINVAL, "null argument");
     if (h->bf) return y355_fail(Y355_EINVAL, "bf16 nets have no trackers");
     if (n != h->arch->ntensors + 1) return y355_fail(Y355_EINVAL, "one tracker for the input and one per tensor expected");
-    for (int i = 0; i < n; ++i) {
-        scale[i] = h->trk_scale[i];
-        first_a[i] = h->trk_first[i];
-    }
+    y355_trackers_get(h->trk_scale.data(), h->trk_first.data(), n, scale, first_a);
     return 0;
 }
 
@@ -1255,17 +1125,14 @@ extern "C" int y355_net_set_trackers(y355_net *h, const float *scale, const int3
     bool all = true;
     for (int i = 0; i < n; ++i) {
         if (!first_a[i]) { all = false; continue; }
-        if (!(scale[i] > 0.f) || !std::isfinite(scale[i])) return y355_fail(Y355_EINVAL, "tracker scale is not a positive finite number");
-        const int e = (int)std::floor(std::log2(scale[i]));
-        if (e < -64 || e > 64) return y355_fail(Y355_EINVAL, "tracker exponent out of range");
+        int e = 0;
+        if (const int bad = y355_tracker_exponent(scale[i], &e))
+            return y355_fail(Y355_EINVAL, bad == 1 ? "tracker scale is not a positive finite number" : "tracker exponent out of range");
         if (i == 0) sa_in = e;
         else sa[i - 1] = e;
     }
     if (int rc = install_act_exponents(h, sa_in, sa.data(), n - 1, all)) return rc;
-    for (int i = 0; i < n; ++i) {
-        h->trk_scale[i] = scale[i];
-        h->trk_first[i] = first_a[i] ? 1 : 0;
-    }
+    y355_trackers_set(h->trk_scale.data(), h->trk_first.data(), n, scale, first_a);
     return 0;
 }
 
@@ -1294,13 +1161,13 @@ static int cal_conv_max(y355_net *h, int i, int B, const NetInput &in, float *ou
     L.rq = RequantG{cf.shl, 0, cf.lk, cf.nm, 0, 0};
     L.rq1 = requant_of(cf, 0);
     L.rq1.wide = 1;
-    HIPCHK(hipMemcpyAsync(L.shl_dev, cf.shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipMemcpyAsync(L.bias_w_dev, cf.bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));                   // (the host vectors go out of scope)
+    HIPCHK(hipMemcpyAsync(L.shl_dev, cf.shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipMemcpyAsync(L.bias_w_dev, cf.bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));                   // (the host vectors go out of scope)
     if (int rc = run_op(h, i, B, in, PASS_CAL_STAT)) return rc;
     unsigned long long m = 0;
-    HIPCHK(hipMemcpyAsync(&m, &h->cal_dev[i].absmax, 8, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(&m, &h->cal_dev[i].absmax, 8, hipMemcpyDeviceToHost, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     *out_max = (float)(int64_t)m * std::ldexp(1.0f, -fb);
     return 0;
 }
@@ -1308,22 +1175,20 @@ static int cal_conv_max(y355_net *h, int i, int B, const NetInput &in, float *ou
 // the 32-bit maximum of slot i (fp32 bits or an unsigned int) back to the host
 static int cal_read_u32(y355_net *h, int i, void *v) {
     HIPCHK(hipGetLastError());
-    HIPCHK(hipMemcpyAsync(v, &h->cal_dev[i].absmax, 4, hipMemcpyDeviceToHost, h->stream));
-    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipMemcpyAsync(v, &h->cal_dev[i].absmax, 4, hipMemcpyDeviceToHost, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));
     return 0;
 }
 
 static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze, double momentum, std::vector<float> &mx) {
     const ArchDef &A = *h->arch;
     const int nops = A.nops, nt = A.ntensors;
-    hipStream_t s = h->stream;
+    hipStream_t s = h->core.stream;
     const std::vector<float> pre_scale = h->trk_scale;
     const std::vector<int> pre_first = h->trk_first;
     for (auto &L : h->L) L.dirty = true;                       // the step installs new exponents op by op: every layer's constants are stale
     HIPCHK(hipMemsetAsync(h->cal_dev, 0, sizeof(Counters) * (nops + 1), s));
-    bool need_zero = false;
-    h->ctr_dev = h->ctrs.begin(&need_zero);                    // the write passes count their clamps as a forward does
-    if (need_zero) HIPCHK((hipError_t)y355_zero_counters(h->ctr_dev, nops + 1, s));
+    if (int rc = y355_core_begin_counters(&h->core)) return rc;         // the write passes count their clamps as a forward does
     h->t0_skipped = false;
     auto step = [&](int k, float m, int *e) -> int {           // tracker k sees m
         int32_t first = h->trk_first[k], ex = 0;
@@ -1337,10 +1202,10 @@ static int net_calibrate_run(y355_net *h, const NetInput &in, int B, int freeze,
     // ---- tracker 0: max |x| of the fp32 input / of the normalised resized frames
     if (int rc = pre_stage(h, in, B)) return rc;
     if (in.x) {
-        y355_launch_absmax(in.x, (size_t)B * 3 * h->cfg.height * h->cfg.width, slot(nops), s);
+        y355_launch_absmax(in.x, (size_t)B * 3 * h->core.H * h->core.W, slot(nops), s);
     } else {
         const bool staged = in.stage != nullptr || A.ops[0].type != OP_INPUT;      // in.u8 is at the network size
-        y355_launch_absmax_u8(in.u8, staged ? nullptr : in.tab, B, in.sh, in.sw, h->cfg.height, h->cfg.width, h->stage.norm, slot(nops), s);
+        y355_launch_absmax_u8(in.u8, staged ? nullptr : in.tab, B, in.sh, in.sw, h->core.H, h->core.W, h->core.stage.norm, slot(nops), s);
     }
     float m = 0.f;
     if (int rc = cal_read_u32(h, nops, &m)) return rc;
@@ -1423,7 +1288,7 @@ static int net_calibrate(y355_net *h, const NetInput &in, int B, int freeze, dou
     h->front_dirty = true;
     if (rc) {                                                  // the handle keeps the pre-step state
         const std::string msg = y355_last_error();
-        (void)hipStreamSynchronize(h->stream);
+        (void)hipStreamSynchronize(h->core.stream);
         h->sa_in = keep_in;
         h->sa = keep;
         h->sa_ok = keep_ok;
@@ -1442,7 +1307,7 @@ static int cal_check(y355_net *h, const void *input, int batch, double momentum,
     if (!h || !input) return y355_fail(Y355_EINVAL, "null argument");
     if (h->bf) return y355_fail(Y355_EINVAL, "calibration steps run on int8 nets");
     if (n != h->arch->ntensors + 1) return y355_fail(Y355_EINVAL, "one tracker for the input and one per tensor expected");
-    if (int rc = range_check(h, batch)) return rc;
+    if (int rc = y355_core_range(&h->core, batch)) return rc;
     if (!(momentum >= 0.0 && momentum <= 1.0)) return y355_fail(Y355_EINVAL, "momentum outside [0, 1]");
     for (const auto &L : h->L)
         if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
@@ -1452,7 +1317,7 @@ static int cal_check(y355_net *h, const void *input, int batch, double momentum,
 extern "C" int y355_net_calibrate(y355_net *h, const float *x_dev, int batch, int freeze, double momentum, int32_t *sa_in_out,
                                   int32_t *sa_out, float *max_out, int n) {
     if (int rc = cal_check(h, x_dev, batch, momentum, n)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core)) return rc;
     NetInput in;
     in.x = x_dev;
     return net_calibrate(h, in, batch, freeze, momentum, sa_in_out, sa_out, max_out);
@@ -1461,8 +1326,7 @@ extern "C" int y355_net_calibrate(y355_net *h, const float *x_dev, int batch, in
 extern "C" int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int src_h, int src_w, int batch, int freeze,
                                      double momentum, int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n) {
     if (int rc = cal_check(h, frames_dev, batch, momentum, n)) return rc;
-    if (int rc = range_check(h, batch, src_h, src_w)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
+    if (int rc = y355_core_enter(&h->core, batch, src_h, src_w)) return rc;
     NetInput in;
     if (int rc = u8_input(h, frames_dev, src_h, src_w, false, &in)) return rc;      // conv1.hip reads single bytes: no alignment rule
     return net_calibrate(h, in, batch, freeze, momentum, sa_in_out, sa_out, max_out);
@@ -1471,9 +1335,9 @@ extern "C" int y355_net_calibrate_u8(y355_net *h, const uint8_t *frames_dev, int
 extern "C" int y355_net_calibrate_frames(y355_net *h, const y355_frame *frames, int batch, int freeze, double momentum,
                                          int32_t *sa_in_out, int32_t *sa_out, float *max_out, int n) {
     if (int rc = cal_check(h, frames, batch, momentum, n)) return rc;
-    if (int rc = y355_frames_check(frames, batch, h->cfg.max_batch)) return rc;
-    HIPCHK(hipSetDevice(h->cfg.device_id));
-    if (int rc = net_list_buffers(h, true)) return rc;
+    if (int rc = y355_frames_check(frames, batch, h->core.max_batch)) return rc;
+    if (int rc = y355_core_enter(&h->core)) return rc;
+    if (int rc = net_list_buffers(h)) return rc;
     return net_calibrate(h, list_input(h, frames), batch, freeze, momentum, sa_in_out, sa_out, max_out);
 }
 

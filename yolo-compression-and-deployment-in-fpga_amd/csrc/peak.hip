@@ -7,8 +7,6 @@
 #include "y355_common.h"
 #include <string>
 
-int y355_fail(int code, const std::string &msg);
-
 namespace {
 constexpr int NACC = 24;
 __global__ __launch_bounds__(512) void mfma_peak_kernel(int iters, int *out, unsigned long long *cyc) {

@@ -19,17 +19,10 @@
 
 bool y355_has_overflow_flags(y355_engine *h);              // engine.hip
 int y355_overflow_take(y355_engine *h, int *dst_dev);
-int y355_fail(int code, const std::string &msg);     // engine.hip: sets the message y355_last_error() returns
 int y355_frames_prepare(y355_engine *h, const y355_frame *frames, int batch);  // engine.hip: all that can fail in y355_forward_frames
 
 namespace {
 int pfail(int code, const std::string &msg) { return y355_fail(code, msg); }
-#define PHIPCHK(expr)                                                                      \
-    do {                                                                                   \
-        hipError_t e_ = (expr);                                                            \
-        if (e_ != hipSuccess)                                                              \
-            return pfail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));    \
-    } while (0)
 
 struct Slot {
     float *boxes = nullptr, *scores = nullptr;      // pipeline-owned outputs of the ticket in this slot (allocated on first use)
@@ -160,8 +153,8 @@ extern "C" int y355_pipeline_set_option(y355_pipeline *p, int option, int value)
         // pipeline-owned outputs are dropped (allocated again on first use): tickets still out are void
         for (auto *e : p->eng)
             if (int rc = y355_set_option(e, option, value)) return rc;
-        PHIPCHK(hipSetDevice(p->cfg.device_id));
-        PHIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipSetDevice(p->cfg.device_id));
+        HIPCHK(hipDeviceSynchronize());
         for (auto &s : p->slots) {
             (void)hipFree(s.boxes); (void)hipFree(s.scores); (void)hipFree(s.cls); (void)hipFree(s.count);
             s.boxes = s.scores = nullptr;
@@ -203,10 +196,10 @@ extern "C" int y355_pipeline_get_trackers(y355_pipeline *p, float *scale, int32_
 static int slot_outputs(y355_pipeline *p, Slot &s) {
     if (s.boxes) return 0;
     const size_t B = (size_t)p->cfg.max_batch, md = (size_t)p->max_det;
-    PHIPCHK(hipMalloc((void **)&s.boxes, sizeof(float) * 4 * md * B));
-    PHIPCHK(hipMalloc((void **)&s.scores, sizeof(float) * md * B));
-    PHIPCHK(hipMalloc((void **)&s.cls, sizeof(int32_t) * md * B));
-    PHIPCHK(hipMalloc((void **)&s.count, sizeof(int32_t) * B));
+    HIPCHK(hipMalloc((void **)&s.boxes, sizeof(float) * 4 * md * B));
+    HIPCHK(hipMalloc((void **)&s.scores, sizeof(float) * md * B));
+    HIPCHK(hipMalloc((void **)&s.cls, sizeof(int32_t) * md * B));
+    HIPCHK(hipMalloc((void **)&s.count, sizeof(int32_t) * B));
     return 0;
 }
 
@@ -218,17 +211,17 @@ static int submit_common(y355_pipeline *p, const void *in_dev, InputKind kind, i
     const bool own = !boxes_dev && !scores_dev && !cls_dev && !count_dev;
     if (!own && (!boxes_dev || !scores_dev || !cls_dev || !count_dev))
         return pfail(Y355_EINVAL, "give all four output pointers or none (none = pipeline-owned buffers, y355_pipeline_outputs)");
-    PHIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipSetDevice(p->cfg.device_id));
     const long long t = p->next;
     y355_engine *e = p->eng[(size_t)(t % (long long)p->eng.size())];
     Slot &s = p->slots[(size_t)(t % (long long)p->slots.size())];
     hipStream_t es = (hipStream_t)y355_stream(e);
     if (flags & Y355_PIPE_AFTER_STREAM) {             // the input is produced on the caller's stream: start after what is queued there
-        PHIPCHK(hipEventRecord(p->input_ready, (hipStream_t)caller_stream));
-        PHIPCHK(hipStreamWaitEvent(es, p->input_ready, 0));
+        HIPCHK(hipEventRecord(p->input_ready, (hipStream_t)caller_stream));
+        HIPCHK(hipStreamWaitEvent(es, p->input_ready, 0));
     }
     if (s.has_release) {                              // the consumer of the ticket that used this slot said when it is done with it
-        PHIPCHK(hipStreamWaitEvent(es, s.released, 0));
+        HIPCHK(hipStreamWaitEvent(es, s.released, 0));
         s.has_release = false;
     }
     if (own) {
@@ -242,10 +235,10 @@ static int submit_common(y355_pipeline *p, const void *in_dev, InputKind kind, i
     if (rc) return rc;
     s.has_ovf = y355_has_overflow_flags(e);           // heads of more than 4096 anchors, or with the large route forced
     if (s.has_ovf) {
-        if (!s.ovf) PHIPCHK(hipMalloc((void **)&s.ovf, sizeof(int32_t) * (size_t)p->cfg.max_batch));
+        if (!s.ovf) HIPCHK(hipMalloc((void **)&s.ovf, sizeof(int32_t) * (size_t)p->cfg.max_batch));
         if (int rc2 = y355_overflow_take(e, s.ovf)) return rc2;      // on the handle's stream, behind the forward: no host wait
     }
-    PHIPCHK(hipEventRecord(s.done, es));
+    HIPCHK(hipEventRecord(s.done, es));
     s.o_boxes = boxes_dev; s.o_scores = scores_dev; s.o_cls = cls_dev; s.o_count = count_dev;
     s.ticket = t;
     s.batch = batch;
@@ -293,9 +286,9 @@ static int find_slot(y355_pipeline *p, long long ticket, Slot **out) {
 extern "C" int y355_pipeline_wait(y355_pipeline *p, long long ticket, int on_stream, void *caller_stream) {
     Slot *s = nullptr;
     if (int rc = find_slot(p, ticket, &s)) return rc;
-    PHIPCHK(hipSetDevice(p->cfg.device_id));
-    if (on_stream) PHIPCHK(hipStreamWaitEvent((hipStream_t)caller_stream, s->done, 0));
-    else PHIPCHK(hipEventSynchronize(s->done));
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    if (on_stream) HIPCHK(hipStreamWaitEvent((hipStream_t)caller_stream, s->done, 0));
+    else HIPCHK(hipEventSynchronize(s->done));
     return 0;
 }
 
@@ -314,8 +307,8 @@ extern "C" int y355_pipeline_outputs(y355_pipeline *p, long long ticket, float *
 extern "C" int y355_pipeline_release(y355_pipeline *p, long long ticket, void *caller_stream) {
     Slot *s = nullptr;
     if (int rc = find_slot(p, ticket, &s)) return rc;
-    PHIPCHK(hipSetDevice(p->cfg.device_id));
-    PHIPCHK(hipEventRecord(s->released, (hipStream_t)caller_stream));
+    HIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipEventRecord(s->released, (hipStream_t)caller_stream));
     s->has_release = true;
     return 0;
 }
@@ -325,15 +318,15 @@ extern "C" int y355_pipeline_fetch(y355_pipeline *p, long long ticket, float *bo
     Slot *s = nullptr;
     if (int rc = find_slot(p, ticket, &s)) return rc;
     if (!boxes || !scores || !cls || !count) return pfail(Y355_EINVAL, "null argument");
-    PHIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipSetDevice(p->cfg.device_id));
     hipStream_t es = p->copy_stream;
-    PHIPCHK(hipStreamWaitEvent(es, s->done, 0));
+    HIPCHK(hipStreamWaitEvent(es, s->done, 0));
     const size_t md = (size_t)p->max_det, B = (size_t)s->batch;
-    PHIPCHK(hipMemcpyAsync(boxes, s->o_boxes, sizeof(float) * 4 * md * B, hipMemcpyDeviceToHost, es));
-    PHIPCHK(hipMemcpyAsync(scores, s->o_scores, sizeof(float) * md * B, hipMemcpyDeviceToHost, es));
-    PHIPCHK(hipMemcpyAsync(cls, s->o_cls, sizeof(int32_t) * md * B, hipMemcpyDeviceToHost, es));
-    PHIPCHK(hipMemcpyAsync(count, s->o_count, sizeof(int32_t) * B, hipMemcpyDeviceToHost, es));
-    PHIPCHK(hipStreamSynchronize(es));
+    HIPCHK(hipMemcpyAsync(boxes, s->o_boxes, sizeof(float) * 4 * md * B, hipMemcpyDeviceToHost, es));
+    HIPCHK(hipMemcpyAsync(scores, s->o_scores, sizeof(float) * md * B, hipMemcpyDeviceToHost, es));
+    HIPCHK(hipMemcpyAsync(cls, s->o_cls, sizeof(int32_t) * md * B, hipMemcpyDeviceToHost, es));
+    HIPCHK(hipMemcpyAsync(count, s->o_count, sizeof(int32_t) * B, hipMemcpyDeviceToHost, es));
+    HIPCHK(hipStreamSynchronize(es));
     return 0;
 }
 
@@ -345,12 +338,12 @@ extern "C" int y355_pipeline_ticket_overflow(y355_pipeline *p, long long ticket,
     if (!overflow) return pfail(Y355_EINVAL, "null argument");
     *overflow = 0;
     if (!s->has_ovf) return 0;
-    PHIPCHK(hipSetDevice(p->cfg.device_id));
+    HIPCHK(hipSetDevice(p->cfg.device_id));
     hipStream_t es = p->copy_stream;
-    PHIPCHK(hipStreamWaitEvent(es, s->done, 0));
+    HIPCHK(hipStreamWaitEvent(es, s->done, 0));
     std::vector<int32_t> v((size_t)p->cfg.max_batch, 0);
-    PHIPCHK(hipMemcpyAsync(v.data(), s->ovf, sizeof(int32_t) * v.size(), hipMemcpyDeviceToHost, es));
-    PHIPCHK(hipStreamSynchronize(es));
+    HIPCHK(hipMemcpyAsync(v.data(), s->ovf, sizeof(int32_t) * v.size(), hipMemcpyDeviceToHost, es));
+    HIPCHK(hipStreamSynchronize(es));
     for (int i = 0; i < s->batch; ++i) *overflow |= v[(size_t)i] != 0;
     return 0;
 }
@@ -362,7 +355,7 @@ extern "C" int y355_pipeline_scale_boxes(y355_pipeline *p, long long ticket, con
     if (int rc = find_slot(p, ticket, &s)) return rc;
     y355_engine *e = p->eng[(size_t)(ticket % (long long)p->eng.size())];
     if (int rc = y355_scale_boxes(e, s->o_boxes, s->o_count, wh_dev, s->batch)) return rc;
-    PHIPCHK(hipEventRecord(s->done, (hipStream_t)y355_stream(e)));
+    HIPCHK(hipEventRecord(s->done, (hipStream_t)y355_stream(e)));
     return 0;
 }
 

@@ -143,8 +143,6 @@ void y355_launch_resize_frames(const y355_frame *frames, int n, uint8_t *dst, in
 }
 
 // ---- the stage's host state (FrameStage, y355_common.h)
-int y355_fail(int code, const std::string &msg);
-
 void y355_stage_init(FrameStage &st, int H, int W, int max_batch, const DevMem &mem) {
     st = FrameStage{};
     st.H = H;

@@ -111,6 +111,13 @@ struct Counters {
 // engine.hip, for the other translation units
 int y355_fail(int code, const std::string &msg);     // keeps msg for y355_last_error(), returns code
 int y355_prepare_kernels();                          // one-time kernel attributes of the int8 engine's kernels; a y355 error code
+// a HIP call of a function that returns a y355 error code: on failure Y355_EHIP, the call and HIP's text as the message
+#define HIPCHK(expr)                                                                        \
+    do {                                                                                    \
+        hipError_t e_ = (expr);                                                             \
+        if (e_ != hipSuccess)                                                               \
+            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
+    } while (0)
 // the integer epilogue of one stand-alone layer (the operator layer of ops.hip): make_requant, with requantisation to sa_out
 // when have_out, else none (t' is the result)
 int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, const int32_t *q_b, int cout,

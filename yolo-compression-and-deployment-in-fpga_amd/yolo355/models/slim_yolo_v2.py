@@ -16,15 +16,18 @@ forward goes through the C ABI into the HIP kernels.  There is no PyTorch comput
 `quantization=True` runs the int8 engine (y355_engine), the default `quantization=False`
 (the call of test.py:84 / demo.py:81 / utils/vocapi_evaluator.py:67: trackers are the identity,
 fp32 math on whatever weights are loaded) runs the same graph on the bf16 MFMA (y355_net);
-`trainable=True` (losses) raises NotImplementedError.
+`trainable=True` with a `target` returns the reference's four losses (:360-382), computed on the GPU from the prediction
+map of that forward (yolo355/loss.py: the value only, there is no backward pass); without a target it raises
+NotImplementedError.
 """
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import framelist, prep
+from .. import loss as _loss
 from ..engine import Engine, Pipeline
-from ..netengine import Net
+from ..netengine import Net, PRED_TAIL
 from ..utils import Conv2d, Conv2d_fuse
 from ..utils.modules import folded_f32
 
@@ -59,6 +62,54 @@ def _cached(slots, slot, key, batch, version, build, load):
     return h
 
 
+class _LossBranch:
+    """The loss branch of the reference's forward (trainable=True and a target; models/slim_yolo_v2.py:360-382, :601-623,
+    models/yolo_v2.py:212-232, models/tiny_yolo_v3.py:249-273, models/yolo_v3.py) for every model class: the prediction
+    maps of one forward on the engine, then decode + IoU + the terms of tools.loss on the GPU (yolo355/loss.py).  The maps
+    reach the companion library through the engines' host taps: one host round trip per batch.
+    self.stride says which targets the family has: an int = tools.gt_creator (anchors in grid units), a list =
+    tools.multi_gt_creator (anchors in pixels)."""
+    MAX_LABELS_PER_IMAGE = 1024
+
+    def _anchors64(self):
+        """the anchor sizes as the constructor got them: tools.gt_creator works on those float64 values, not on the float32
+        tensor anchor_size"""
+        a = self.__dict__.get("_anchor_size64")
+        return a if a is not None else self.anchor_size.detach().double().view(-1, 2).tolist()
+
+    def _loss_handle(self, batch):
+        anchors = self._anchors64()
+        key = (tuple(self.input_size), self.num_classes, tuple(map(tuple, anchors)))
+        return _cached(self.__dict__, "_loss_state", key, batch, 0,
+                       lambda: _loss.YoloLoss(self.input_size, self.stride, anchors, self.num_classes, max_batch=max(batch, 1),
+                                              max_labels_per_image=self.MAX_LABELS_PER_IMAGE, device=_device(self)),
+                       lambda h: None)
+
+    def _prediction_maps(self, x, quantization, **kw):
+        """[fp32 [B, A(5+C), hs, ws] per level] of one forward of x, in the head's level order"""
+        raise NotImplementedError
+
+    def loss_batch(self, x, labels, quantization=False, **kw):
+        """The loss of a labelled batch: labels = per image a list of [xmin, ymin, xmax, ymax, cls] (coordinates in [0, 1]).
+        Targets are assigned on the GPU (tools.gt_creator / tools.multi_gt_creator of the family).  Returns (float64 [4] =
+        conf_loss, cls_loss, txtytwth_loss, total_loss; float64 [B, 5] = pos, neg, cls, txty, twth per image).  Works with
+        trainable False as well: the validation loss of the deployed graph."""
+        B = int(x.shape[0])
+        if len(labels) != B:
+            raise ValueError("%d label lists for a batch of %d" % (len(labels), B))
+        maps = self._prediction_maps(x, quantization, **kw)
+        h = self._loss_handle(B)
+        h.set_labels(labels)
+        return h.compute(maps)
+
+    def _forward_loss(self, x, target, quantization, **kw):
+        """forward(x, target=T) of a trainable model: T dense [B, N, 11] as tools.gt_creator makes it; the reference's return"""
+        maps = self._prediction_maps(x, quantization, **kw)
+        h = self._loss_handle(int(x.shape[0]))
+        out, _ = h.compute(maps, target)
+        return _loss.as_loss_tensors(out, h.device)
+
+
 class AveragedRangeTracker(nn.Module):
     """Checkpoint-compatible holder of the tracker buffers (models/slim_yolo_v2.py:9-14).
     The max|activation| statistics come from the GPU; the state update is prep.RangeTracker."""
@@ -70,7 +121,7 @@ class AveragedRangeTracker(nn.Module):
         self.register_buffer("first_a", torch.zeros(1))
 
 
-class SlimYOLOv2_quantize_bnfuse(nn.Module):
+class SlimYOLOv2_quantize_bnfuse(_LossBranch, nn.Module):
     def __init__(self, device, input_size=None, num_classes=20, trainable=False, conf_thresh=0.01,
                  nms_thresh=0.5, anchor_size=None, hr=False, max_candidates=4096):
         super().__init__()
@@ -82,6 +133,7 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         self.conf_thresh = conf_thresh
         self.nms_thresh = nms_thresh
         self.anchor_size = torch.tensor(anchor_size)
+        self._anchor_size64 = [[float(v) for v in a] for a in anchor_size]
         self.anchor_number = len(anchor_size)
         self.stride = 16
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
@@ -130,7 +182,11 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
 
     def forward(self, x, target=None, quantization=False, find=False):
         """Eval-mode return of the reference (:344-358): detections of image 0 as NumPy arrays
-        (bboxes float32 [n,4] in [0,1], scores float32 [n], cls_inds int64 [n]), anchor order."""
+        (bboxes float32 [n,4] in [0,1], scores float32 [n], cls_inds int64 [n]), anchor order.  trainable=True with a target
+        (dense [B, N, 11], tools.gt_creator): the four losses of :360-382 as 0-dim float32 tensors; with quantization=True the
+        trackers are updated first (freeze = not trainable, :212), as calibrate(x, freeze=False) does."""
+        if self.trainable and target is not None:
+            return self._forward_loss(x, target, quantization, find=find)
         return self.forward_batch(x, quantization=quantization, find=find)[0]
 
     def forward_batch(self, x, quantization=True, find=False, sizes_wh=None):
@@ -138,8 +194,8 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         (width, height)): boxes come back in pixels of the original images -- the evaluators'
         `bboxes *= scale` (utils/vocapi_evaluator_mask.py:71-72) done on the GPU for the whole batch."""
         if self.trainable:
-            raise NotImplementedError("yolo355 is an inference engine: the training branch "
-                                      "(models/slim_yolo_v2.py:360-382) is out of scope")
+            raise NotImplementedError("yolo355 is an inference engine: a trainable model gives its losses "
+                                      "(models/slim_yolo_v2.py:360-382), forward(x, target=T) or loss_batch(x, labels)")
         if not quantization:
             # models/slim_yolo_v2.py:212-358 with the default kwarg: every tracker returns its input (:17-18), so the
             # forward is conv + bias + LeakyReLU(0.125) / max-pool in fp32 on the loaded (possibly dyadic) weights; `find`
@@ -199,8 +255,8 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
 
     def calibrate(self, x, freeze=False, find=False):
         """One calibration step on a batch, the tracker side of the reference's calibration loop
-        (retune_bias_quantize.py:357-369: `model(images, target, quantization=True)` in training mode, whose loss branch is
-        out of scope here): every AveragedRangeTracker sees max|activation| over the batch -- first call: scale =
+        (retune_bias_quantize.py:357-369: `model(images, target, quantization=True)` in training mode; calibrate_with_loss
+        adds that call's losses): every AveragedRangeTracker sees max|activation| over the batch -- first call: scale =
         127 / max; later calls: scale = 0.9 scale + 0.1 * 127 / max (models/slim_yolo_v2.py:25-31), or unchanged with
         freeze=True -- layer by layer on the GPU, each layer running with the exponent just updated.  The buffers
         `a_tracker*.scale / first_a` are updated in place (they travel in the state_dict).  Returns the 11 exponents.
@@ -212,6 +268,36 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         sa = eng.calibrate(x, trackers, freeze=freeze)
         self._store_trackers(trackers)
         return sa
+
+    def calibrate_with_loss(self, x, labels, freeze=False, find=False):
+        """calibrate(x, freeze, find) and the four losses of that batch on the graph just calibrated -- the whole step of the
+        reference's calibration loop (retune_bias_quantize.py:341-358: gt_creator, then model(images, target, quantization=True)).
+        The loss is read from the prediction map of the calibration pass itself.  Returns (the 11 exponents, float64 [4])."""
+        B = int(x.shape[0])
+        if len(labels) != B:
+            raise ValueError("%d label lists for a batch of %d" % (len(labels), B))
+        sa = self.calibrate(x, freeze=freeze, find=find)
+        h = self._loss_handle(B)
+        h.set_labels(labels)
+        return sa, h.compute(self._engine_prediction_map(B, sa))[0]
+
+    def _engine_prediction_map(self, B, sa):
+        """the int8 prediction map of the engine's last pass: q * 2^-sa_pred, exact in fp32"""
+        return [torch.from_numpy(self._engine.get_feature(9, B).astype(np.float32) * np.float32(2.0 ** -int(sa[10])))]
+
+    def _prediction_maps(self, x, quantization, find=False):
+        B = int(x.shape[0])
+        if not quantization:
+            net = self._get_f32_net(B, find)
+            net.forward_device(net._dev_input(x))
+            return [torch.from_numpy(net.get_tensor(net.num_tensors - 1, B))]
+        # the reference's forward(quantization=True): every tracker sees this batch (freeze = not trainable, :212), each layer runs
+        # behind the exponent just updated; the loss branch then reads the prediction of that same pass
+        eng = self._get_engine(B, find)
+        trackers = self._tracker_states()
+        sa = eng.calibrate(x, trackers, freeze=not self.trainable)
+        self._store_trackers(trackers)
+        return self._engine_prediction_map(B, sa)
 
     def forward_frames(self, frames, find=False):
         """New: detections for camera frames, uint8 [B,H,W,3] BGR at the network size --
@@ -231,8 +317,8 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
         the bf16 y355_net of forward_batch(quantization=False)."""
         framelist.check_frame_list(frames)
         if self.trainable:
-            raise NotImplementedError("yolo355 is an inference engine: the training branch "
-                                      "(models/slim_yolo_v2.py:360-382) is out of scope")
+            raise NotImplementedError("yolo355 is an inference engine: a trainable model gives its losses "
+                                      "(models/slim_yolo_v2.py:360-382), forward(x, target=T) or loss_batch(x, labels)")
         n = len(frames)
         if not quantization:
             net = self._get_f32_net(n, find)
@@ -319,8 +405,8 @@ class SlimYOLOv2_quantize_bnfuse(nn.Module):
                 m.first_a.fill_(float(t.first_a))
 
 
-class _NetModel(nn.Module):
-    """Shared plumbing of the fp32 model drop-ins: fold BN, load the engine, batched forward."""
+class _NetModel(_LossBranch, nn.Module):
+    """Shared plumbing of the fp32 model drop-ins: fold BN, load the engine, batched forward, the loss branch."""
     _arch = None
 
     def _conv_modules(self):
@@ -333,9 +419,10 @@ class _NetModel(nn.Module):
         self.input_size = list(input_size)
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
 
-    def _check_inference(self):
-        if self.trainable:
-            raise NotImplementedError("yolo355 is an inference engine: the training branch is out of scope")
+    def _check_inference(self, loss=False):
+        if self.trainable and not loss:
+            raise NotImplementedError("yolo355 is an inference engine: a trainable model gives its losses, forward(x, target=T) or "
+                                      "loss_batch(x, labels); there is no training-mode forward without a target")
         if self.training and any(isinstance(m, nn.BatchNorm2d) for m in self.modules()):
             raise NotImplementedError("yolo355 folds BatchNorm with its running statistics: call .eval() first")
 
@@ -350,6 +437,32 @@ class _NetModel(nn.Module):
         if quantization and self.act_exponents is None:    # (a model calibrate()d on its int8 net never builds the bf16 one)
             self.act_exponents = self._get_net(int(x.shape[0])).calibration_exponents(x)
         return self._ready_net(int(x.shape[0]), quantization).forward(x, sizes_wh=sizes_wh)
+
+    def _prediction_maps(self, x, quantization=False):
+        self._check_inference(loss=True)
+        B = int(x.shape[0])
+        if quantization and self.act_exponents is None:    # the first-call rule of forward_batch
+            self.act_exponents = self._get_net(B).calibration_exponents(x)
+        net = self._ready_net(B, quantization)
+        net.forward_device(net._dev_input(x))
+        maps = [net.get_tensor(net.num_tensors - k, B) for k in PRED_TAIL[self._arch]]
+        # the head's level order is self.stride's, finest first; PRED_TAIL lists the maps in graph order (yolo_v3: coarsest first)
+        return [torch.from_numpy(m) for m in sorted(maps, key=lambda m: -m.shape[2] * m.shape[3])]
+
+    def _loss_or_none(self, x, target, quantization=False):
+        """forward's first statement: the four losses for a trainable model that got a target, else None"""
+        if self.trainable and target is not None:
+            return self._forward_loss(x, target, quantization)
+        return None
+
+    def calibrate_with_loss(self, x, labels, freeze=False):
+        """calibrate(x, freeze) and the four losses of that batch on the int8 graph behind the exponents just updated -- the
+        whole step of the reference's calibration loop (retune_bias_quantize.py:341-358).  Returns ((sa_in, [sa per tensor]),
+        float64 [4])."""
+        if len(labels) != int(x.shape[0]):
+            raise ValueError("%d label lists for a batch of %d" % (len(labels), int(x.shape[0])))
+        sa = self._calibrate_step(lambda net: net.calibrate(x, freeze=freeze), int(x.shape[0]), loss=True)
+        return sa, self.loss_batch(x, labels, quantization=True)[0]
 
     def _ready_net(self, batch, quantization):
         """the bf16 net, or the int8 net with the frozen activation exponents, at the model's thresholds"""
@@ -401,8 +514,8 @@ class _NetModel(nn.Module):
         Net.check_frames(frames)
         return self._calibrate_step(lambda net: net.calibrate_frames(frames, freeze=freeze), int(frames.shape[0]))
 
-    def _calibrate_step(self, step, batch):
-        self._check_inference()
+    def _calibrate_step(self, step, batch, loss=False):
+        self._check_inference(loss)
         qnet = self._get_net(batch, int8=True)
         if hasattr(self, "act_tracker_scale"):             # the state this model carries (a reloaded state_dict, an earlier net)
             qnet.trackers = (self.act_tracker_scale.cpu().numpy(), self.act_tracker_first_a.cpu().numpy())
@@ -480,6 +593,7 @@ class SlimYOLOv2(_NetModel):
         self.conf_thresh = conf_thresh
         self.nms_thresh = nms_thresh
         self.anchor_size = torch.tensor(anchor_size)
+        self._anchor_size64 = [[float(v) for v in a] for a in anchor_size]
         self.anchor_number = len(anchor_size)
         self.stride = 16
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
@@ -502,5 +616,7 @@ class SlimYOLOv2(_NetModel):
         return [getattr(self, n).convs for n in _CONVS] + [self.pred]
 
     def forward(self, x, target=None, quantization=False, find=False):
-        """Eval-mode return of the reference (:585-601): detections of image 0."""
-        return self.forward_batch(x)[0]
+        """Eval-mode return of the reference (:585-601): detections of image 0; trainable=True with a target: the four losses
+        (:601-623)."""
+        out = self._loss_or_none(x, target)
+        return out if out is not None else self.forward_batch(x)[0]

@@ -32,6 +32,7 @@ class YOLOv3tiny(_NetModel):
         self.nms_thresh = nms_thresh
         self.stride = [16, 32]
         self.anchor_size = torch.tensor(anchor_size).view(2, len(anchor_size) // 2, 2)
+        self._anchor_size64 = [[float(v) for v in a] for a in anchor_size]
         self.anchor_number = self.anchor_size.size(1)
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
         self.backbone = darknet_light(pretrained=False, hr=hr)
@@ -51,5 +52,7 @@ class YOLOv3tiny(_NetModel):
 
     def forward(self, x, target=None, quantization=False):
         """Eval-mode return of the reference (:224-243): detections of image 0.  quantization=True is
-        this build's int8 form of the model (the reference has none): see _NetModel.forward_batch."""
-        return self.forward_batch(x, quantization=quantization)[0]
+        this build's int8 form of the model (the reference has none): see _NetModel.forward_batch.  trainable=True with a
+        target (tools.multi_gt_creator's): the four losses (:249-273)."""
+        out = self._loss_or_none(x, target, quantization)
+        return out if out is not None else self.forward_batch(x, quantization=quantization)[0]

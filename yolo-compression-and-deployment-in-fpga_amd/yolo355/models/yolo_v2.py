@@ -5,7 +5,7 @@ BN-folded convolutions on the bf16 MFMA, pools fused or stand-alone, reorg + con
 -- csrc/net.hip); `forward_batch(x, quantization=True)` runs its int8 form (power-of-two weights, exponents frozen at the
 first quantized call).  `forward_batch_composed` / `prediction_map` run the same graph layer by layer through the
 operator API (y355_conv2d_bf16, y355_maxpool2x2_f32, y355_reorg_f32, y355_head_f32 -- SURVEY.md 8f-3), one host round
-trip per layer: the bring-up / cross-check form.  Training is not built."""
+trip per layer: the bring-up / cross-check form.  trainable=True with a target gives the four losses (the value only)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -22,8 +22,6 @@ class myYOLOv2(_NetModel):
                  anchor_size=None, hr=False, max_candidates=4096):
         super().__init__()
         self.max_candidates = int(max_candidates)      # most anchors of an image that may pass conf_thresh (Engine / Net max_candidates)
-        if trainable:
-            raise NotImplementedError("yolo355 is an inference engine: myYOLOv2(trainable=True) is not built")
         self.device = device
         self.input_size = list(input_size)
         self.num_classes = num_classes
@@ -31,6 +29,7 @@ class myYOLOv2(_NetModel):
         self.conf_thresh = conf_thresh
         self.nms_thresh = nms_thresh
         self.anchor_size = torch.tensor(anchor_size)
+        self._anchor_size64 = [[float(v) for v in a] for a in anchor_size]
         self.anchor_number = len(anchor_size)
         self.stride = 32
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
@@ -75,6 +74,9 @@ class myYOLOv2(_NetModel):
                         device_id=x.device.index if x.is_cuda and x.device.index is not None else 0)
 
     def forward(self, x, target=None):
+        out = self._loss_or_none(x, target)       # trainable=True with a target: the four losses (models/yolo_v2.py:212-232)
+        if out is not None:
+            return out
         if target is not None:
-            raise NotImplementedError("yolo355 is an inference engine: the training branch (models/yolo_v2.py:212-232) is not built")
+            raise NotImplementedError("yolo355: a target needs trainable=True (models/yolo_v2.py:212-232)")
         return self.forward_batch(x)[0]          # the reference decodes batch element 0 only (:200-204)

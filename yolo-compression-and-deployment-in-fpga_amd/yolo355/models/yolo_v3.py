@@ -8,7 +8,7 @@ forms of the generic kernel, SPP and bilinear x2 into concat buffers, three-leve
 `forward_batch_composed` / `prediction_maps` run the same graph layer by layer through the operator API
 (y355_conv2d_bf16, y355_spp_f32, y355_upsample2x_f32, y355_head_f32 -- SURVEY.md 8f-3): the bring-up / cross-check form.  At 416 x 416 an
 image has 10 647 anchors: the head thresholds and compacts them on the GPU, and at most 4096 may pass conf_thresh.
-Training is not built."""
+trainable=True with a target gives the four losses (the value only; there is no backward pass)."""
 import numpy as np
 import torch
 import torch.nn as nn
@@ -41,8 +41,6 @@ class myYOLOv3(_NetModel):
                  anchor_size=None, hr=False, max_candidates=4096):
         super().__init__()
         self.max_candidates = int(max_candidates)      # most anchors of an image that may pass conf_thresh (Engine / Net max_candidates)
-        if trainable:
-            raise NotImplementedError("yolo355 is an inference engine: trainable=True is not built")
         self.device = device
         self.input_size = list(input_size)
         self.num_classes = num_classes
@@ -51,6 +49,7 @@ class myYOLOv3(_NetModel):
         self.nms_thresh = nms_thresh
         self.stride = [8, 16, 32]
         self.anchor_size = torch.tensor(anchor_size).view(3, len(anchor_size) // 3, 2)
+        self._anchor_size64 = [[float(v) for v in a] for a in anchor_size]
         self.anchor_number = self.anchor_size.size(1)
         self.scale = np.array([[[input_size[1], input_size[0], input_size[1], input_size[0]]]])
         self.backbone = darknet53(pretrained=False, hr=hr)
@@ -117,8 +116,11 @@ class myYOLOv3(_NetModel):
                         1.0, self.conf_thresh, self.nms_thresh, device_id=_dev(x))
 
     def forward(self, x, target=None):
+        out = self._loss_or_none(x, target)       # trainable=True with a target: the four losses (the reference's loss branch)
+        if out is not None:
+            return out
         if target is not None:
-            raise NotImplementedError("yolo355 is an inference engine: the training branch is not built")
+            raise NotImplementedError("yolo355: a target needs trainable=True")
         return self.forward_batch(x)[0]          # the reference decodes batch element 0 only (:267-269)
 
 

@@ -1,10 +1,14 @@
-// Host-only check of the allocation logic in csrc/head_state.hip (HeadState: create, resize's swap and rollback, destroy),
-// csrc/resize.hip (FrameStage: lazy buffers, the cached same-size table) and csrc/handle_core.h (HandleCore: a create's
-// allocations and its unwinding; not its stream and events, which need a device).  Device memory is the host heap here, through
+// Host-only check of the allocation logic in csrc/y355_common.h (DevOwner), csrc/head_state.hip (HeadState: create, resize's
+// swap and rollback, destroy), csrc/resize.hip (FrameStage: lazy buffers, the cached same-size table), csrc/handle_core.h
+// (HandleCore: a create's allocations and its unwinding; not its stream and events, which need a device), csrc/apeval.hip and
+// csrc/cocoeval.hip (y355_apeval: create-time buffers, the two ground truths, the COCO workspaces, staging, close) and
+// csrc/pipeline_slot.h (a pipeline slot's outputs).  Device memory is the host heap here, through
 // a DevMem whose k-th allocation (or whose upload) fails on demand, so the program needs no GPU.  Built with the address and
 // undefined-behaviour sanitizers by `make -C csrc hostcheck`: a leak, a double free or a use after free ends it non-zero.
 #include "../include/yolo355.h"
+#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/apeval_shared.h"
 #include "../yolo-compression-and-deployment-in-fpga_amd/csrc/handle_core.h"
+#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/pipeline_slot.h"
 
 #include <cstdio>
 #include <cstdlib>
@@ -61,10 +65,11 @@ std::vector<uintptr_t> snapshot(const HeadState &s) {
     std::vector<uintptr_t> v;
     for (const void *p : ptrs) v.push_back((uintptr_t)p);
     for (int x : {w.rstride, s.N, s.max_batch, s.cfg_max_det, s.max_det, s.cap, s.route}) v.push_back((uintptr_t)x);
-    for (void *p : s.allocs) v.push_back((uintptr_t)p);
+    for (void *p : s.own.allocs) v.push_back((uintptr_t)p);
     return v;
 }
-bool owns_exactly_live(const HeadState &s) { return std::set<void *>(s.allocs.begin(), s.allocs.end()) == live && s.allocs.size() == live.size(); }
+bool owns_exactly_live(const DevOwner &o) { return std::set<void *>(o.allocs.begin(), o.allocs.end()) == live && o.allocs.size() == live.size(); }
+bool owns_exactly_live(const HeadState &s) { return owns_exactly_live(s.own); }
 
 void check_head(int N, int B, int cfg_max_det, bool tap, bool outs) {
     const DevMem mem = host_mem();
@@ -82,7 +87,7 @@ void check_head(int N, int B, int cfg_max_det, bool tap, bool outs) {
         fail_at = k;
         n_alloc = 0;
         CHECK(y355_head_create(st, N, B, cfg_max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, tap, outs, mem) != 0);
-        CHECK(live.empty() && st.allocs.empty() && !st.wk.cbox);
+        CHECK(live.empty() && st.own.allocs.empty() && !st.wk.cbox);
     }
     fail_at = -1;
     CHECK(y355_head_create(st, N, B, cfg_max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, tap, outs, mem) == 0);
@@ -184,11 +189,11 @@ void check_core(int N, bool outs) {
         HandleCore c;
         CHECK(core_create(c, N, outs) == 0 && !c.own_stream && !c.stream && c.ev.empty());
         CHECK(c.ctrs.base == c.ctr_dev && c.ctrs.n == 11 && c.ctrs.clean[0] && c.ctrs.clean[1] && c.absmax_dev);
-        CHECK(c.allocs.size() == 8 && c.allocs.size() + c.head.allocs.size() + c.stage.allocs.size() == live.size());
+        CHECK(c.own.allocs.size() == 8 && c.own.allocs.size() + c.head.own.allocs.size() + c.stage.own.allocs.size() == live.size());
         CHECK(y355_core_range(&c, 0) == Y355_EINVAL && g_err == "batch out of range" && y355_core_range(&c, 3) == Y355_EINVAL);
         CHECK(y355_core_range(&c, 2, 16385, 1) == Y355_EINVAL && g_err == "bad frame size" && y355_core_range(&c, 2, 16384, 1) == 0);
         y355_core_close(&c);
-        CHECK(live.empty() && c.allocs.empty());
+        CHECK(live.empty() && c.own.allocs.empty());
         y355_core_close(&c);                        // a second close is harmless
     }
     const int n_create = n_alloc;
@@ -198,16 +203,233 @@ void check_core(int N, bool outs) {
         n_alloc = 0;
         g_err.clear();
         CHECK(core_create(c, N, outs) == Y355_EHIP);
-        CHECK(live.empty() && c.allocs.empty() && c.head.allocs.empty() && c.stage.allocs.empty() && !c.stage.frames);
+        CHECK(live.empty() && c.own.allocs.empty() && c.head.own.allocs.empty() && c.stage.own.allocs.empty() && !c.stage.frames);
         CHECK(g_err == "injected allocation failure" && std::string(y355_last_error()) == "injected allocation failure");
         y355_core_close(&c);
         CHECK(live.empty());
     }
     fail_at = -1;
 }
+
+// ---- DevOwner: get, drop, grow, group grow, mark / rollback, release all
+void check_owner() {
+    DevOwner o{host_mem(), {}};
+    int dummy = 0, *a = &dummy;
+    fail_at = 0, n_alloc = 0;
+    CHECK(y355_dev_get(o, &a, 10) == Y355_EHIP && a == &dummy && live.empty() && o.allocs.empty());      // *p as it was
+    fail_at = -1;
+    CHECK(y355_dev_get(o, &a, 10, true) == 0 && a != &dummy && a[9] == 0 && owns_exactly_live(o) && live.size() == 1);
+    double *none = nullptr;
+    y355_dev_drop(o, &none);                        // null: nothing
+    y355_dev_drop(o, &a);
+    CHECK(!a && live.empty() && o.allocs.empty());
+    // grow
+    size_t have = 0;
+    fail_at = 0, n_alloc = 0;
+    CHECK(y355_dev_grow(o, &have, 10, &a) == Y355_EHIP && !a && have == 0 && live.empty());
+    fail_at = -1;
+    CHECK(y355_dev_grow(o, &have, 10, &a) == 0 && a && have == 10 && live.size() == 1);
+    a[9] = 1;
+    const int *a10 = a;
+    n_alloc = 0;
+    CHECK(y355_dev_grow(o, &have, 5, &a) == 0 && a == a10 && have == 10 && n_alloc == 0);       // smaller: nothing
+    fail_at = 0;
+    CHECK(y355_dev_grow(o, &have, 20, &a) == Y355_EHIP && !a && have == 0 && live.empty() && o.allocs.empty());
+    fail_at = -1;
+    CHECK(y355_dev_grow(o, &have, 20, &a) == 0 && have == 20 && owns_exactly_live(o));
+    a[19] = 1;
+    // group grow: three arrays of two element types, one capacity
+    double *b = nullptr;
+    char *c = nullptr;
+    unsigned int *d = nullptr;
+    size_t cap = 0;
+    for (size_t need : {(size_t)7, (size_t)3000}) {
+        for (int k = 0; k < 3; ++k) {
+            fail_at = k, n_alloc = 0;
+            CHECK(y355_dev_grow(o, &cap, need, &b, &c, &d) == Y355_EHIP && !b && !c && !d && cap == 0);
+            CHECK(live.size() == 1 && owns_exactly_live(o));     // (a stays)
+        }
+        fail_at = -1, n_alloc = 0;
+        CHECK(y355_dev_grow(o, &cap, need, &b, &c, &d) == 0 && b && c && d && cap == need && n_alloc == 3 && live.size() == 4);
+        b[need - 1] = 1.0, c[need - 1] = 1, d[need - 1] = 1u;
+        CHECK(y355_dev_grow(o, &cap, need - 1, &b, &c, &d) == 0 && cap == need && n_alloc == 3);
+    }
+    // all or nothing
+    const size_t mark = y355_dev_mark(o);
+    int *x = nullptr, *y = nullptr;
+    CHECK(y355_dev_get(o, &x, 4) == 0 && y355_dev_get(o, &y, 4) == 0 && live.size() == 6);
+    y355_dev_rollback(o, mark);
+    CHECK(live.size() == 4 && owns_exactly_live(o));
+    y355_dev_release_all(o);
+    CHECK(live.empty() && o.allocs.empty());
+    y355_dev_release_all(o);                        // a second one is harmless
+}
+
+// ---- the evaluator handle (no stream, no event: a null stream goes to the uploads)
+bool ap_all_null(const y355_apeval &e) {
+    const void *p[] = {e.gt_off, e.gt_box, e.gt_cls, e.gt_diff, e.gt_first, e.ctr, e.d_imgpos, e.d_cls, e.d_score, e.d_box, e.khi, e.perm[0],
+                       e.perm[1], e.hist, e.dtot, e.jm, e.flag, e.rec, e.prec, e.start, e.ap, e.stage, e.coco};
+    for (const void *q : p)
+        if (q) return false;
+    return e.own.allocs.empty() && !e.have_gt && !e.have_curve && e.stage_bytes == 0;
+}
+void ap_sizes(y355_apeval &e, long long max_dets) {
+    e.C = 3, e.num_images = 2, e.cap = max_dets, e.own.mem = host_mem();
+}
+void check_apeval_buffers(long long max_dets) {
+    y355_apeval e;
+    ap_sizes(e, max_dets);
+    fail_at = -1, n_alloc = 0;
+    CHECK(ap_buffers(&e) == 0);
+    const int n_create = n_alloc;
+    const size_t n = (size_t)max_dets, tiles = (n + AP_TILE - 1) / AP_TILE;
+    CHECK(n_create == 16 && (int)live.size() == n_create && owns_exactly_live(e.own));
+    e.ctr[7] = 1, e.d_box[4 * n - 1] = 1.f, e.perm[1][n - 1] = 1u, e.hist[256 * tiles - 1] = 1u, e.dtot[255] = 1u, e.prec[n - 1] = 1.0;
+    e.start[e.C] = 1, e.ap[e.C - 1] = 1.0;          // (the sanitizer sees a buffer that is too short)
+    ap_close(&e);
+    CHECK(live.empty() && ap_all_null(e) && e.C == 3 && e.cap == max_dets);
+    for (int k = 0; k < n_create; ++k) {
+        fail_at = k, n_alloc = 0;
+        CHECK(ap_buffers(&e) == Y355_EHIP && live.empty() && ap_all_null(e) && g_err == "injected allocation failure");
+    }
+    fail_at = -1;
+    CHECK(ap_buffers(&e) == 0 && owns_exactly_live(e.own));
+    ap_close(&e);
+    ap_close(&e);                                   // twice; the COCO part was never made
+    CHECK(live.empty() && ap_all_null(e));
+}
+
+const int32_t kOff2[3] = {0, 1, 2}, kCls2[2] = {0, 1}, kOff5[3] = {0, 3, 5}, kCls5[5] = {2, 0, 2, 1, 1};
+const uint8_t kDiff2[2] = {0, 1}, kDiff5[5] = {0, 0, 1, 0, 0};
+const float kBox[20] = {1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11, 12, 13, 14, 15, 16, 17, 18, 19, 20};
+
+void check_apeval_gt() {
+    for (int k = 0; k < 5; ++k) {                   // the k-th allocation of the replacement fails
+        y355_apeval e;
+        ap_sizes(e, 8);
+        fail_at = -1;
+        CHECK(ap_buffers(&e) == 0 && ap_set_gt(&e, kOff2, kBox, kCls2, kDiff2) == 0 && e.have_gt && e.n_gt == 2);
+        CHECK(e.npos == std::vector<int32_t>({1, 0, 0}) && memcmp(e.gt_box, kBox, 32) == 0 && memcmp(e.gt_off, kOff2, 12) == 0);
+        CHECK(live.size() == 21 && owns_exactly_live(e.own));
+        e.have_curve = true;
+        for (int round = 0; round < 2; ++round) {
+            fail_at = k, n_alloc = 0;
+            CHECK(ap_set_gt(&e, kOff5, kBox, kCls5, kDiff5) == Y355_EHIP && !e.have_gt && !e.have_curve && e.n_gt != 5);
+            CHECK(owns_exactly_live(e.own));
+            if (round) break;
+            fail_at = -1;                           // a retry
+            CHECK(ap_set_gt(&e, kOff5, kBox, kCls5, kDiff5) == 0 && e.have_gt && e.n_gt == 5 && e.npos == std::vector<int32_t>({1, 2, 1}));
+            CHECK(memcmp(e.gt_box, kBox, 80) == 0 && memcmp(e.gt_diff, kDiff5, 5) == 0 && live.size() == 21 && owns_exactly_live(e.own));
+            e.gt_first[4] = 0;
+        }
+        fail_at = -1;
+        if (k == 0) {                               // an upload that fails
+            fail_upload = true;
+            CHECK(ap_set_gt(&e, kOff2, kBox, kCls2, kDiff2) == Y355_EHIP && !e.have_gt && owns_exactly_live(e.own));
+            fail_upload = false;
+        }
+        ap_close(&e);                               // close returns everything
+        CHECK(live.empty() && ap_all_null(e));
+    }
+}
+
+int coco_gt(y355_apeval &e, int n, std::vector<int32_t> *cls_left = nullptr) {
+    const int32_t *off = n == 2 ? kOff2 : kOff5, rank[2] = {1, 0};
+    std::vector<int32_t> h_cls(n == 2 ? kCls2 : kCls5, (n == 2 ? kCls2 : kCls5) + n);
+    std::vector<double> h_box(kBox, kBox + 4 * n), h_area(n, 100.0);
+    std::vector<uint8_t> h_crowd(n, 0);
+    const int rc = coco_set_gt(&e, off, rank, h_box, h_cls, h_area, h_crowd);
+    if (cls_left) *cls_left = h_cls;
+    return rc;
+}
+void check_coco() {
+    std::vector<int32_t> left;
+    for (int k = 0; k < 6; ++k) {                   // the COCO ground truth, as the VOC one; the host copies move on success only
+        y355_apeval e;
+        ap_sizes(e, 8);
+        fail_at = -1;
+        CHECK(ap_buffers(&e) == 0 && coco_gt(e, 2, &left) == 0 && e.coco && e.coco->have_gt && e.coco->n_gt == 2 && left.empty());
+        CHECK(e.coco->h_cls.size() == 2 && e.coco->h_area.size() == 2 && e.coco->h_crowd.size() == 2 && live.size() == 22);
+        e.coco->have_result = true;
+        fail_at = k, n_alloc = 0;
+        CHECK(coco_gt(e, 5, &left) == Y355_EHIP && !e.coco->have_gt && !e.coco->have_result && e.coco->n_gt != 5);
+        CHECK(left.size() == 5 && e.coco->h_cls.size() == 2 && e.coco->h_area.size() == 2 && e.coco->h_crowd.size() == 2 && owns_exactly_live(e.own));
+        fail_at = -1;
+        if (k % 2) {
+            CHECK(coco_gt(e, 5, &left) == 0 && e.coco->have_gt && e.coco->n_gt == 5 && left.size() == 2 && e.coco->h_cls.size() == 5);
+            CHECK(e.coco->h_crowd.size() == 5 && e.coco->img_rank[0] == 1 && e.coco->gt_box[19] == 20.0 && live.size() == 22 && owns_exactly_live(e.own));
+        }
+        ap_close(&e);
+        CHECK(live.empty() && ap_all_null(e));
+    }
+    // the workspaces
+    y355_apeval e;
+    ap_sizes(e, 8);
+    CHECK(ap_buffers(&e) == 0 && coco_gt(e, 5) == 0);
+    e.coco->n_gt = 4;                               // (n 10, n_gt 4, A 4, T 10)
+    y355_coco *c = e.coco;
+    n_alloc = 0;
+    CHECK(coco_workspaces(&e, 10, 10, 101, 4, 3) == 0 && n_alloc == 11 && c->n_cap == 10 && c->flags_cap == 400 && c->marks_cap == 160);
+    CHECK(c->prec_cap == (size_t)10 * 101 * 3 * 4 * 3 && c->rec_cap == 360 && owns_exactly_live(e.own));
+    c->npig[3 * COCO_MAX_A - 1] = 1, c->rec_thrs[COCO_MAX_R - 1] = 1.0, c->w0[9] = 1, c->gidx[9] = 1u, c->flags[399] = 1, c->marks[159] = 1;
+    CHECK(coco_workspaces(&e, 5, 10, 101, 4, 3) == 0 && n_alloc == 11 && c->n_cap == 10);       // fewer detections: nothing
+    bool done = false;
+    for (int k = 0; k <= 6 && !done; ++k) {         // 3000 detections: the five arrays of n_cap and the flags, a failure at every k
+        fail_at = k, n_alloc = 0;
+        done = coco_workspaces(&e, 3000, 10, 101, 4, 3) == 0;
+        const bool gone = !c->permA;
+        CHECK(gone == !c->permB && gone == !c->gkey && gone == !c->gidx && gone == !c->w0 && gone == (c->n_cap == 0));
+        CHECK(!c->flags == (c->flags_cap == 0) && owns_exactly_live(e.own) && (done || g_err == "injected allocation failure"));
+    }
+    fail_at = -1;
+    CHECK(done && c->n_cap == 3000 && c->flags_cap == (size_t)40 * 3000 && c->marks_cap == 160 && live.size() == 22 + 11);
+    c->permB[2999] = 1u, c->flags[40 * 3000 - 1] = 1;
+    // the tap and the staging buffer
+    CHECK(coco_tap(&e, 100) == 0 && c->tap_cap == 100 && live.size() == 34);
+    fail_at = n_alloc;
+    CHECK(coco_tap(&e, 1000) == Y355_EHIP && !c->tap && c->tap_cap == 0 && live.size() == 33);
+    fail_at = -1;
+    CHECK(coco_tap(&e, 1000) == 0 && c->tap_cap == 1000 && coco_tap(&e, 10) == 0 && c->tap_cap == 1000);
+    c->tap[999] = 1;
+    CHECK(ap_stage(&e, 1024) == 0 && e.stage_bytes == 1024 && live.size() == 35);
+    fail_at = n_alloc;
+    CHECK(ap_stage(&e, 1 << 20) == Y355_EHIP && !e.stage && e.stage_bytes == 0 && live.size() == 34);
+    fail_at = -1;
+    CHECK(ap_stage(&e, 1 << 20) == 0 && e.stage_bytes == (1 << 20) && owns_exactly_live(e.own));
+    e.stage[(1 << 20) - 1] = 1;
+    ap_close(&e);
+    CHECK(live.empty() && ap_all_null(e));
+    ap_close(&e);
+}
+
+// ---- a pipeline slot's outputs: all four or none
+void check_slot() {
+    DevOwner o{host_mem(), {}};
+    Slot s;
+    for (int k = 0; k < 4; ++k) {
+        fail_at = k, n_alloc = 0;
+        CHECK(y355_slot_outputs(s, o, 2, 100) == Y355_EHIP && !s.boxes && !s.scores && !s.cls && !s.count && live.empty() && o.allocs.empty());
+    }
+    fail_at = -1, n_alloc = 0;
+    CHECK(y355_slot_outputs(s, o, 2, 100) == 0 && s.boxes && s.scores && s.cls && s.count && n_alloc == 4 && owns_exactly_live(o));
+    s.boxes[799] = 1.f, s.scores[199] = 1.f, s.cls[199] = 1, s.count[1] = 1;
+    CHECK(y355_slot_outputs(s, o, 2, 100) == 0 && n_alloc == 4);          // there already
+    CHECK(y355_dev_get(o, &s.ovf, 2) == 0 && live.size() == 5);
+    y355_slot_drop_outputs(s, o);
+    CHECK(!s.boxes && !s.scores && !s.cls && !s.count && s.ovf && live.size() == 1);
+    CHECK(y355_slot_outputs(s, o, 2, 50) == 0 && live.size() == 5);
+    y355_dev_release_all(o);
+    CHECK(live.empty());
+}
 }  // namespace
 
 int main() {
+    check_owner();
+    check_apeval_buffers(8);
+    check_apeval_buffers(5000);                     // five tiles of the sort's histogram
+    check_apeval_gt();
+    check_coco();
+    check_slot();
     check_head(2000, 2, 0, true, true);             // a small head: engine-like (tap and host outputs)
     check_head(2000, 1, 100, false, true);          // y355_head_f32_ex without the tap
     check_head(10647, 2, 0, true, false);           // more than 4096 anchors: y355_net-like (no host outputs)

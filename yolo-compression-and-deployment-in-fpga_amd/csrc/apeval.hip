@@ -14,12 +14,10 @@
 // The handle, the sort's entry points (ap_keys / ap_sort / ap_class_bounds) and the workgroup scans are in apeval_shared.h:
 // cocoeval.hip scores the same store the COCO way.
 #include "apeval_shared.h"
+#include "handle_core.h"
 
 #include <cfloat>
 #include <cmath>
-#include <cstdio>
-#include <string>
-#include <vector>
 
 namespace {
 // ---- append: one workgroup per image of the batch
@@ -358,7 +356,7 @@ __global__ void __launch_bounds__(AP_SCORE_THREADS) ap_score_kernel(int metric, 
 }
 
 int ap_check_add(y355_apeval *e, int first_image, int batch, int max_det, const void *a, const void *b, const void *c, const void *d) {
-    if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
+    if (int rc = ap_check_handle(e)) return rc;
     if (!a || !b || !c || !d) return y355_fail(Y355_EINVAL, "null detection buffer");
     if (batch < 1 || first_image < 0 || (long long)first_image + batch > e->num_images)
         return y355_fail(Y355_EINVAL, "images first_image .. first_image + batch - 1 are not inside 0 .. num_images - 1");
@@ -419,6 +417,64 @@ void ap_class_bounds(y355_apeval *e, long long n) {
     hipLaunchKernelGGL(ap_bounds_kernel, dim3((int)((n + 256) / 256)), dim3(256), 0, e->s, n, e->C, e->perm[e->cur], e->d_cls, e->start);
 }
 
+// ---- the handle's device memory (apeval_shared.h)
+int ap_buffers(y355_apeval *e) {
+    const size_t n = (size_t)e->cap, tiles = (n + AP_TILE - 1) / AP_TILE, C = (size_t)e->C;
+    DevOwner &o = e->own;
+    int rc = y355_dev_get(o, &e->ctr, 8);
+    rc = rc ? rc : y355_dev_get_all(o, n, &e->d_imgpos, &e->d_cls, &e->d_score, &e->khi, &e->perm[0], &e->perm[1], &e->jm, &e->flag, &e->rec, &e->prec);
+    rc = rc ? rc : y355_dev_get(o, &e->d_box, 4 * n);
+    rc = rc ? rc : y355_dev_get(o, &e->hist, 256 * tiles);
+    rc = rc ? rc : y355_dev_get(o, &e->dtot, 256);
+    rc = rc ? rc : y355_dev_get(o, &e->start, C + 1);
+    rc = rc ? rc : y355_dev_get(o, &e->ap, C);
+    if (rc) ap_close(e);
+    return rc;
+}
+
+int ap_check_gt(const y355_apeval *e, const int32_t *offsets, const int32_t *cls, bool have_arrays, long long *n) {
+    if (int rc = ap_check_handle(e)) return rc;
+    if (!offsets) return y355_fail(Y355_EINVAL, "null offsets");
+    if (offsets[0] != 0) return y355_fail(Y355_EINVAL, "offsets[0] must be 0");
+    for (int i = 0; i < e->num_images; ++i)
+        if (offsets[i + 1] < offsets[i]) return y355_fail(Y355_EINVAL, "offsets must not decrease");
+    *n = offsets[e->num_images];
+    if (*n > 0 && !have_arrays) return y355_fail(Y355_EINVAL, "null ground-truth array");
+    for (long long g = 0; g < *n; ++g)
+        if (cls[g] < 0 || cls[g] >= e->C) return y355_fail(Y355_EINVAL, "ground-truth class outside 0 .. num_classes - 1");
+    return 0;
+}
+
+int ap_set_gt(y355_apeval *e, const int32_t *offsets, const float *boxes, const int32_t *cls, const uint8_t *difficult) {
+    const size_t n = (size_t)offsets[e->num_images], ni = (size_t)e->num_images + 1;
+    DevOwner &o = e->own;
+    e->have_gt = false, e->have_curve = false, e->n_gt = 0;
+    y355_dev_drop(o, &e->gt_off, &e->gt_box, &e->gt_cls, &e->gt_diff, &e->gt_first);
+    int rc = y355_dev_get(o, &e->gt_off, ni);
+    rc = rc ? rc : y355_dev_get(o, &e->gt_box, 4 * n);
+    rc = rc ? rc : y355_dev_get_all(o, n, &e->gt_cls, &e->gt_diff, &e->gt_first);
+    rc = rc ? rc : o.mem.upload(e->gt_off, offsets, ni * sizeof(int32_t), e->s);
+    if (n > 0) {
+        rc = rc ? rc : o.mem.upload(e->gt_box, boxes, 4 * n * sizeof(float), e->s);
+        rc = rc ? rc : o.mem.upload(e->gt_cls, cls, n * sizeof(int32_t), e->s);
+        rc = rc ? rc : o.mem.upload(e->gt_diff, difficult, n, e->s);
+    }
+    if (rc) return rc;                                    // (what it took stays the handle's: the next set_gt or the close returns it)
+    e->npos.assign(e->C, 0);
+    for (size_t g = 0; g < n; ++g)
+        if (!difficult[g]) ++e->npos[cls[g]];
+    e->n_gt = (long long)n, e->have_gt = true;
+    return 0;
+}
+
+void ap_close(y355_apeval *e) {
+    y355_dev_release_all(e->own);
+    delete e->coco;
+    y355_apeval z;                                        // every pointer null, nothing ready
+    z.device = e->device, z.C = e->C, z.num_images = e->num_images, z.cap = e->cap, z.s = e->s, z.ev = e->ev, z.own.mem = e->own.mem;
+    *e = std::move(z);
+}
+
 extern "C" {
 
 int y355_apeval_create(int device_id, int num_classes, int num_images, int64_t max_dets, y355_apeval **out) {
@@ -430,35 +486,14 @@ int y355_apeval_create(int device_id, int num_classes, int num_images, int64_t m
     if (max_dets < 1 || max_dets > ((int64_t)1 << 27)) return y355_fail(Y355_EINVAL, "max_dets outside 1 .. 2^27");
     HIPCHK(hipSetDevice(device_id));
     y355_apeval *e = new y355_apeval;
-    e->device = device_id, e->C = num_classes, e->num_images = num_images, e->cap = max_dets;
-    e->npos.assign(num_classes, 0);
-    const size_t n = (size_t)max_dets, tiles = (n + AP_TILE - 1) / AP_TILE;
+    e->device = device_id, e->C = num_classes, e->num_images = num_images, e->cap = max_dets, e->own.mem = y355_hip_mem();
     int rc = 0;
     if (hipStreamCreateWithFlags(&e->s, hipStreamNonBlocking) != hipSuccess || hipEventCreateWithFlags(&e->ev, hipEventDisableTiming) != hipSuccess)
         rc = y355_fail(Y355_EHIP, "hipStreamCreate / hipEventCreate failed");
-    rc = rc ? rc : ap_alloc(&e->ctr, 8);
-    rc = rc ? rc : ap_alloc(&e->d_imgpos, n);
-    rc = rc ? rc : ap_alloc(&e->d_cls, n);
-    rc = rc ? rc : ap_alloc(&e->d_score, n);
-    rc = rc ? rc : ap_alloc(&e->d_box, 4 * n);
-    rc = rc ? rc : ap_alloc(&e->khi, n);
-    rc = rc ? rc : ap_alloc(&e->perm[0], n);
-    rc = rc ? rc : ap_alloc(&e->perm[1], n);
-    rc = rc ? rc : ap_alloc(&e->hist, 256 * tiles);
-    rc = rc ? rc : ap_alloc(&e->dtot, 256);
-    rc = rc ? rc : ap_alloc(&e->jm, n);
-    rc = rc ? rc : ap_alloc(&e->flag, n);
-    rc = rc ? rc : ap_alloc(&e->rec, n);
-    rc = rc ? rc : ap_alloc(&e->prec, n);
-    rc = rc ? rc : ap_alloc(&e->start, (size_t)num_classes + 1);
-    rc = rc ? rc : ap_alloc(&e->ap, (size_t)num_classes);
+    rc = rc ? rc : ap_buffers(e);
     if (!rc && (hipMemsetAsync(e->ctr, 0, 8 * sizeof(unsigned long long), e->s) != hipSuccess || hipStreamSynchronize(e->s) != hipSuccess))
         rc = y355_fail(Y355_EHIP, "hipMemset failed");
-    if (rc) {
-        const std::string keep = y355_last_error();
-        y355_apeval_destroy(e);
-        return y355_fail(rc, keep);
-    }
+    if (rc) return y355_core_unwind(rc, [e] { y355_apeval_destroy(e); });
     *out = e;
     return 0;
 }
@@ -467,55 +502,24 @@ void y355_apeval_destroy(y355_apeval *e) {
     if (!e) return;
     (void)hipSetDevice(e->device);
     if (e->s) (void)hipStreamSynchronize(e->s);
-    y355_coco_destroy(e);
-    void *bufs[] = {e->gt_off, e->gt_box, e->gt_cls, e->gt_diff, e->gt_first, e->ctr, e->d_imgpos, e->d_cls, e->d_score, e->d_box, e->khi,
-                    e->perm[0], e->perm[1], e->hist, e->dtot, e->jm, e->flag, e->rec, e->prec, e->start, e->ap, e->stage};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
+    ap_close(e);
     if (e->ev) (void)hipEventDestroy(e->ev);
     if (e->s) (void)hipStreamDestroy(e->s);
     delete e;
 }
 
 int y355_apeval_set_gt(y355_apeval *e, const int32_t *offsets, const float *boxes, const int32_t *cls, const uint8_t *difficult) {
-    if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
-    if (!offsets) return y355_fail(Y355_EINVAL, "null offsets");
-    if (offsets[0] != 0) return y355_fail(Y355_EINVAL, "offsets[0] must be 0");
-    for (int i = 0; i < e->num_images; ++i)
-        if (offsets[i + 1] < offsets[i]) return y355_fail(Y355_EINVAL, "offsets must not decrease");
-    const long long n = offsets[e->num_images];
-    if (n > 0 && (!boxes || !cls || !difficult)) return y355_fail(Y355_EINVAL, "null ground-truth array");
-    std::vector<int32_t> npos(e->C, 0);
-    for (long long g = 0; g < n; ++g) {
-        if (cls[g] < 0 || cls[g] >= e->C) return y355_fail(Y355_EINVAL, "ground-truth class outside 0 .. num_classes - 1");
-        if (!difficult[g]) ++npos[cls[g]];
-    }
-    if (ap_enter(e)) return Y355_EHIP;
-    HIPCHK(hipStreamSynchronize(e->s));
-    e->have_gt = false, e->have_curve = false;
-    void *old[] = {e->gt_off, e->gt_box, e->gt_cls, e->gt_diff, e->gt_first};
-    for (void *p : old)
-        if (p) (void)hipFree(p);
-    e->gt_off = nullptr, e->gt_box = nullptr, e->gt_cls = nullptr, e->gt_diff = nullptr, e->gt_first = nullptr;
-    if (ap_alloc(&e->gt_off, (size_t)e->num_images + 1) || ap_alloc(&e->gt_box, 4 * (size_t)n) || ap_alloc(&e->gt_cls, (size_t)n) ||
-        ap_alloc(&e->gt_diff, (size_t)n) || ap_alloc(&e->gt_first, (size_t)n))
-        return Y355_EHIP;
-    HIPCHK(hipMemcpy(e->gt_off, offsets, ((size_t)e->num_images + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (n > 0) {
-        HIPCHK(hipMemcpy(e->gt_box, boxes, 4 * (size_t)n * sizeof(float), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->gt_cls, cls, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(e->gt_diff, difficult, (size_t)n, hipMemcpyHostToDevice));
-    }
-    e->n_gt = n, e->npos = npos, e->have_gt = true;
-    return 0;
+    long long n = 0;
+    if (int rc = ap_check_gt(e, offsets, cls, boxes && cls && difficult, &n)) return rc;
+    if (int rc = ap_enter(e)) return rc;
+    HIPCHK(hipStreamSynchronize(e->s));                   // nothing in flight reads the arrays that go
+    return ap_set_gt(e, offsets, boxes, cls, difficult);
 }
 
 int y355_apeval_add(y355_apeval *e, int first_image, int batch, int max_det, const float *boxes_dev, const float *scores_dev,
                     const int32_t *cls_dev, const int32_t *count_dev, void *after_stream) {
     if (int rc = ap_check_add(e, first_image, batch, max_det, boxes_dev, scores_dev, cls_dev, count_dev)) return rc;
-    if (ap_enter(e)) return Y355_EHIP;
-    e->have_curve = false;
-    y355_coco_invalidate(e);
+    if (int rc = ap_mutate(e)) return rc;
     if (!after_stream) {
         ap_launch_append(e, first_image, batch, max_det, boxes_dev, scores_dev, cls_dev, count_dev, e->s);
         HIPCHK(hipGetLastError());
@@ -534,18 +538,11 @@ int y355_apeval_add(y355_apeval *e, int first_image, int batch, int max_det, con
 int y355_apeval_add_host(y355_apeval *e, int first_image, int batch, int max_det, const float *boxes, const float *scores, const int32_t *cls,
                          const int32_t *count) {
     if (int rc = ap_check_add(e, first_image, batch, max_det, boxes, scores, cls, count)) return rc;
-    if (ap_enter(e)) return Y355_EHIP;
-    e->have_curve = false;
-    y355_coco_invalidate(e);
+    if (int rc = ap_mutate(e)) return rc;
     const size_t m = (size_t)batch * max_det, need = m * 24 + (size_t)batch * 4;
-    if (need > e->stage_bytes) {
-        HIPCHK(hipStreamSynchronize(e->s));
-        if (e->stage) (void)hipFree(e->stage);
-        e->stage = nullptr, e->stage_bytes = 0;
-        HIPCHK(hipMalloc(&e->stage, need));
-        e->stage_bytes = need;
-    }
-    char *p = (char *)e->stage;
+    if (need > e->stage_bytes) HIPCHK(hipStreamSynchronize(e->s));       // (the buffer that goes is idle)
+    if (int rc = ap_stage(e, need)) return rc;
+    char *p = e->stage;
     float *db = (float *)p, *ds = (float *)(p + m * 16);
     int32_t *dc = (int32_t *)(p + m * 20), *dn = (int32_t *)(p + m * 24);
     HIPCHK(hipMemcpyAsync(db, boxes, m * 16, hipMemcpyHostToDevice, e->s));
@@ -559,23 +556,21 @@ int y355_apeval_add_host(y355_apeval *e, int first_image, int batch, int max_det
 }
 
 int y355_apeval_reset(y355_apeval *e) {
-    if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
-    if (ap_enter(e)) return Y355_EHIP;
-    e->have_curve = false;
-    y355_coco_invalidate(e);
+    if (int rc = ap_check_handle(e)) return rc;
+    if (int rc = ap_mutate(e)) return rc;
     HIPCHK(hipMemsetAsync(e->ctr, 0, 8 * sizeof(unsigned long long), e->s));      // behind every append so far
     HIPCHK(hipStreamSynchronize(e->s));
     return 0;
 }
 
 int y355_apeval_compute(y355_apeval *e, double ovthresh, int metric, int quantize, double *ap, int32_t *npos, int64_t *ndet, double *mean_ap) {
-    if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
+    if (int rc = ap_check_handle(e)) return rc;
     if (!ap || !npos || !ndet || !mean_ap) return y355_fail(Y355_EINVAL, "null output");
     if (metric != Y355_AP_VOC07 && metric != Y355_AP_AREA) return y355_fail(Y355_EINVAL, "metric: Y355_AP_VOC07 or Y355_AP_AREA");
     if (quantize != Y355_AP_Q_VOCFILE && quantize != Y355_AP_Q_NONE) return y355_fail(Y355_EINVAL, "quantize: Y355_AP_Q_VOCFILE or Y355_AP_Q_NONE");
     if (ovthresh != ovthresh) return y355_fail(Y355_EINVAL, "ovthresh is NaN");
     if (!e->have_gt) return y355_fail(Y355_ENOTREADY, "no ground truth: call y355_apeval_set_gt first");
-    if (ap_enter(e)) return Y355_EHIP;
+    if (int rc = ap_enter(e)) return rc;
     e->have_curve = false;
     hipStream_t s = e->s;
     long long n = 0;
@@ -618,7 +613,7 @@ int y355_apeval_compute(y355_apeval *e, double ovthresh, int metric, int quantiz
 }
 
 int y355_apeval_curve(y355_apeval *e, int cls, int64_t capacity, double *rec, double *prec, uint8_t *flag, int64_t *n) {
-    if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
+    if (int rc = ap_check_handle(e)) return rc;
     if (!n) return y355_fail(Y355_EINVAL, "null n");
     if (cls < 0 || cls >= e->C) return y355_fail(Y355_EINVAL, "class outside 0 .. num_classes - 1");
     if (capacity < 0) return y355_fail(Y355_EINVAL, "capacity < 0");
@@ -627,7 +622,7 @@ int y355_apeval_curve(y355_apeval *e, int cls, int64_t capacity, double *rec, do
     *n = nd;
     const size_t m = (size_t)(nd < capacity ? nd : capacity);
     if (!m) return 0;
-    if (ap_enter(e)) return Y355_EHIP;
+    if (int rc = ap_enter(e)) return rc;
     if (rec) HIPCHK(hipMemcpy(rec, e->rec + s0, m * sizeof(double), hipMemcpyDeviceToHost));
     if (prec) HIPCHK(hipMemcpy(prec, e->prec + s0, m * sizeof(double), hipMemcpyDeviceToHost));
     if (flag) HIPCHK(hipMemcpy(flag, e->flag + s0, m, hipMemcpyDeviceToHost));

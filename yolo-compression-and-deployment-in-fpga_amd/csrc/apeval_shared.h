@@ -5,20 +5,59 @@
 #include "../../include/yolo355.h"
 #include "y355_common.h"
 
-#include <string>
-#include <vector>
-
 #define AP_POS_BITS 20            // position of a detection in its image's list: max_det <= 2^20
 #define AP_TILE 1024              // keys per workgroup of a sort pass: 4 waves x 4 rounds x 64
 #define AP_SCORE_THREADS 1024
 
-struct y355_coco;                 // cocoeval.hip: the COCO ground truth, parameters and workspaces of a handle
+#define COCO_MAX_T 16
+#define COCO_MAX_A 8
+#define COCO_MAX_M 8
+#define COCO_MAX_R 1024
+
+struct CocoParams {
+    int T, A, M, R;
+    int max_det[COCO_MAX_M];
+    double thr[COCO_MAX_T];
+    double alo[COCO_MAX_A], ahi[COCO_MAX_A];
+};
+
+// the COCO ground truth, parameters and workspaces of a handle (cocoeval.hip); made by the first y355_apeval_set_gt_coco
+struct y355_coco {
+    // ground truth: CSR by image (the caller's image index), inside an image stable-sorted by class
+    bool have_gt = false;
+    long long n_gt = 0;
+    int *gt_off = nullptr, *gt_cls = nullptr, *img_rank = nullptr;
+    double *gt_box = nullptr, *gt_area = nullptr;
+    uint8_t *gt_crowd = nullptr;
+    std::vector<int32_t> h_cls;
+    std::vector<double> h_area;
+    std::vector<uint8_t> h_crowd;
+    // workspaces, grown on demand
+    unsigned long long *w0 = nullptr;     // [n] image rank << AP_POS_BITS | position
+    unsigned int *permA = nullptr, *permB = nullptr, *gkey = nullptr, *gidx = nullptr;
+    size_t n_cap = 0;                     // of w0, permA, permB, gkey and gidx
+    uint8_t *flags = nullptr;             // [A T][n] by store entry: bit 0 matched, bit 1 ignored
+    size_t flags_cap = 0;
+    uint8_t *marks = nullptr;             // [A T][n_gt]
+    size_t marks_cap = 0;
+    int *npig = nullptr;                  // [K][A]
+    double *rec_thrs = nullptr;           // [COCO_MAX_R]
+    double *prec_out = nullptr, *rec_out = nullptr;
+    size_t prec_cap = 0, rec_cap = 0;
+    int32_t *tap = nullptr;
+    size_t tap_cap = 0;
+    // last compute
+    bool have_result = false;
+    long long n = 0;
+    CocoParams P;
+};
 
 struct y355_apeval {
     int device = 0, C = 0, num_images = 0;
     long long cap = 0;
     hipStream_t s = nullptr;
     hipEvent_t ev = nullptr;
+    DevOwner own;                         // every device array of the handle, e->coco's included
     // ground truth, CSR by image
     bool have_gt = false;
     long long n_gt = 0;
@@ -45,7 +84,7 @@ struct y355_apeval {
     long long *start = nullptr;           // [C + 1]
     double *ap = nullptr;                 // [C]
     // staging of add_host
-    void *stage = nullptr;
+    char *stage = nullptr;
     size_t stage_bytes = 0;
     // last compute
     bool have_curve = false;
@@ -54,14 +93,36 @@ struct y355_apeval {
     y355_coco *coco = nullptr;
 };
 
-template <typename T> int ap_alloc(T **p, size_t count) {
-    HIPCHK(hipMalloc((void **)p, (count ? count : 1) * sizeof(T)));
-    return 0;
-}
+inline int ap_check_handle(const y355_apeval *e) { return e ? 0 : y355_fail(Y355_EINVAL, "null apeval handle"); }
 inline int ap_enter(y355_apeval *e) {
     HIPCHK(hipSetDevice(e->device));
     return 0;
 }
+// the top of add, add_host and reset: a mutation of the store forgets the last results, VOC and COCO
+inline int ap_mutate(y355_apeval *e) {
+    if (int rc = ap_enter(e)) return rc;
+    e->have_curve = false;
+    if (e->coco) e->coco->have_result = false;
+    return 0;
+}
+
+// ---- the handle's device memory (apeval.hip, cocoeval.hip).  These reach the device through e->own alone, so
+// host_state_check.cpp runs them on the CPU with an allocator that fails on demand.
+// the store and the compute workspace for e->C classes and e->cap detections: all of them or, after a failure, none
+int ap_buffers(y355_apeval *e);
+// the five rules of a ground truth, VOC or COCO, behind the null-handle check; have_arrays: no per-box array is null; *n = its boxes
+int ap_check_gt(const y355_apeval *e, const int32_t *offsets, const int32_t *cls, bool have_arrays, long long *n);
+// replace the ground truth by a checked one (the stream is idle); a failure leaves the handle without one
+int ap_set_gt(y355_apeval *e, const int32_t *offsets, const float *boxes, const int32_t *cls, const uint8_t *difficult);
+// the same for the COCO one (the per-box arrays grouped by class inside an image); the host copies are swapped in on success only
+int coco_set_gt(y355_apeval *e, const int32_t *offsets, const int32_t *rank, const std::vector<double> &h_box, std::vector<int32_t> &h_cls,
+                std::vector<double> &h_area, std::vector<uint8_t> &h_crowd);
+// e->coco's workspaces for n detections (and its n_gt boxes) under T thresholds, R recall points, A area ranges, M budgets
+int coco_workspaces(y355_apeval *e, long long n, int T, int R, int A, int M);
+inline int coco_tap(y355_apeval *e, size_t words) { return y355_dev_grow(e->own, &e->coco->tap_cap, words, &e->coco->tap); }
+inline int ap_stage(y355_apeval *e, size_t bytes) { return y355_dev_grow(e->own, &e->stage_bytes, bytes, &e->stage); }
+// returns every array and e->coco; the sizes, the stream and the event stay.  A second call does nothing
+void ap_close(y355_apeval *e);
 
 // ---- the store and its sort (apeval.hip)
 // One digit of a sort key: (word[src][entry] >> shift) & mask, mask <= 255.  src 0: the 64-bit word w0 of ap_sort (image <<
@@ -78,9 +139,6 @@ int ap_keys(y355_apeval *e, long long n, int quantize, const int *rank, unsigned
 int ap_sort(y355_apeval *e, long long n, const unsigned long long *w0, const unsigned long long h[8], const ApPass *passes, int np);
 // e->start[c] = the first rank of class c in e->perm[e->cur] (start[C] = n), for an order whose most significant key is the class
 void ap_class_bounds(y355_apeval *e, long long n);
-// cocoeval.hip: frees e->coco (y355_apeval_destroy), forgets its last result (add / reset)
-void y355_coco_destroy(y355_apeval *e);
-void y355_coco_invalidate(y355_apeval *e);
 
 #ifdef __HIPCC__
 __device__ __forceinline__ unsigned long long wave_or(unsigned long long v) {

@@ -18,62 +18,8 @@
 
 #include <cfloat>
 #include <cmath>
-#include <cstdio>
-#include <string>
-#include <vector>
-
-#define COCO_MAX_T 16
-#define COCO_MAX_A 8
-#define COCO_MAX_M 8
-#define COCO_MAX_R 1024
-
-struct CocoParams {
-    int T, A, M, R;
-    int max_det[COCO_MAX_M];
-    double thr[COCO_MAX_T];
-    double alo[COCO_MAX_A], ahi[COCO_MAX_A];
-};
-
-struct y355_coco {
-    // ground truth: CSR by image (the caller's image index), inside an image stable-sorted by class
-    bool have_gt = false;
-    long long n_gt = 0;
-    int *gt_off = nullptr, *gt_cls = nullptr, *img_rank = nullptr;
-    double *gt_box = nullptr, *gt_area = nullptr;
-    uint8_t *gt_crowd = nullptr;
-    std::vector<int32_t> h_cls;
-    std::vector<double> h_area;
-    std::vector<uint8_t> h_crowd;
-    // workspaces, grown on demand
-    unsigned long long *w0 = nullptr;     // [n] image rank << AP_POS_BITS | position
-    unsigned int *permA = nullptr, *permB = nullptr, *gkey = nullptr, *gidx = nullptr;
-    size_t n_cap = 0;
-    uint8_t *flags = nullptr;             // [A T][n] by store entry: bit 0 matched, bit 1 ignored
-    size_t flags_cap = 0;
-    uint8_t *marks = nullptr;             // [A T][n_gt]
-    size_t marks_cap = 0;
-    int *npig = nullptr;                  // [K][A]
-    double *rec_thrs = nullptr;           // [COCO_MAX_R]
-    double *prec_out = nullptr, *rec_out = nullptr;
-    size_t prec_cap = 0, rec_cap = 0;
-    int32_t *tap = nullptr;
-    size_t tap_cap = 0;
-    // last compute
-    bool have_result = false;
-    long long n = 0;
-    CocoParams P;
-};
 
 namespace {
-template <typename T> int coco_grow(T **p, size_t *have, size_t need) {
-    if (need <= *have && *p) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr, *have = 0;
-    if (ap_alloc(p, need)) return Y355_EHIP;
-    *have = need;
-    return 0;
-}
-
 // gkey[r] = class << 24 | image rank of the r-th entry of sort A: ascending, one run per (image, category) group
 __global__ void __launch_bounds__(256) coco_gkey_kernel(long long n, const unsigned int *permA, const uint8_t *scls, const unsigned long long *w0,
                                                         unsigned int *gkey) {
@@ -283,11 +229,6 @@ __global__ void __launch_bounds__(AP_SCORE_THREADS) coco_accum_kernel(CocoParams
     }
 }
 
-int coco_check_handle(y355_apeval *e) {
-    if (!e) return y355_fail(Y355_EINVAL, "null apeval handle");
-    return 0;
-}
-
 void coco_launch_match(y355_apeval *e, y355_coco *c, dim3 grid, int tap_img, int tap_cls, int tap_a, int32_t *tap, int cap_d, int cap_g) {
     hipLaunchKernelGGL(coco_match_kernel, grid, dim3(256), 0, e->s, c->P, c->n, c->n_gt, c->permA, c->gkey, c->w0, e->d_box, c->img_rank, c->gt_off,
                        c->gt_cls, c->gt_box, c->gt_area, c->gt_crowd, c->marks, c->flags, c->gidx, tap_img, tap_cls, tap_a, tap, cap_d, cap_g);
@@ -304,35 +245,54 @@ struct CocoMean {
 };
 }  // namespace
 
-void y355_coco_invalidate(y355_apeval *e) {
-    if (e->coco) e->coco->have_result = false;
+// ---- e->coco's device memory (apeval_shared.h)
+int coco_set_gt(y355_apeval *e, const int32_t *offsets, const int32_t *rank, const std::vector<double> &h_box, std::vector<int32_t> &h_cls,
+                std::vector<double> &h_area, std::vector<uint8_t> &h_crowd) {
+    const size_t n = h_cls.size(), N = (size_t)e->num_images;
+    if (!e->coco) e->coco = new y355_coco;
+    y355_coco *c = e->coco;
+    DevOwner &o = e->own;
+    c->have_gt = false, c->have_result = false, c->n_gt = 0;
+    y355_dev_drop(o, &c->gt_off, &c->gt_cls, &c->img_rank, &c->gt_box, &c->gt_area, &c->gt_crowd);
+    int rc = y355_dev_get(o, &c->gt_off, N + 1);
+    rc = rc ? rc : y355_dev_get(o, &c->img_rank, N);
+    rc = rc ? rc : y355_dev_get(o, &c->gt_box, 4 * n);
+    rc = rc ? rc : y355_dev_get_all(o, n, &c->gt_cls, &c->gt_area, &c->gt_crowd);
+    rc = rc ? rc : o.mem.upload(c->gt_off, offsets, (N + 1) * sizeof(int32_t), e->s);
+    rc = rc ? rc : o.mem.upload(c->img_rank, rank, N * sizeof(int32_t), e->s);
+    if (n > 0) {
+        rc = rc ? rc : o.mem.upload(c->gt_cls, h_cls.data(), n * sizeof(int32_t), e->s);
+        rc = rc ? rc : o.mem.upload(c->gt_box, h_box.data(), 4 * n * sizeof(double), e->s);
+        rc = rc ? rc : o.mem.upload(c->gt_area, h_area.data(), n * sizeof(double), e->s);
+        rc = rc ? rc : o.mem.upload(c->gt_crowd, h_crowd.data(), n, e->s);
+    }
+    if (rc) return rc;
+    c->h_cls.swap(h_cls), c->h_area.swap(h_area), c->h_crowd.swap(h_crowd);
+    c->n_gt = (long long)n, c->have_gt = true;
+    return 0;
 }
 
-void y355_coco_destroy(y355_apeval *e) {
+int coco_workspaces(y355_apeval *e, long long n, int T, int R, int A, int M) {
     y355_coco *c = e->coco;
-    if (!c) return;
-    void *bufs[] = {c->gt_off, c->gt_cls, c->img_rank, c->gt_box, c->gt_area, c->gt_crowd, c->w0, c->permA, c->permB, c->gkey, c->gidx,
-                    c->flags, c->marks, c->npig, c->rec_thrs, c->prec_out, c->rec_out, c->tap};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    delete c;
-    e->coco = nullptr;
+    DevOwner &o = e->own;
+    const size_t K = (size_t)e->C, n1 = (size_t)(n > 0 ? n : 1), g1 = (size_t)(c->n_gt > 0 ? c->n_gt : 1);
+    int rc = c->npig ? 0 : y355_dev_get(o, &c->npig, K * COCO_MAX_A);
+    rc = rc || c->rec_thrs ? rc : y355_dev_get(o, &c->rec_thrs, (size_t)COCO_MAX_R);
+    rc = rc ? rc : y355_dev_grow(o, &c->prec_cap, (size_t)T * R * K * A * M, &c->prec_out);
+    rc = rc ? rc : y355_dev_grow(o, &c->rec_cap, (size_t)T * K * A * M, &c->rec_out);
+    rc = rc ? rc : y355_dev_grow(o, &c->n_cap, n1, &c->permA, &c->permB, &c->gkey, &c->gidx, &c->w0);
+    rc = rc ? rc : y355_dev_grow(o, &c->flags_cap, (size_t)A * T * n1, &c->flags);
+    rc = rc ? rc : y355_dev_grow(o, &c->marks_cap, (size_t)A * T * g1, &c->marks);
+    return rc;
 }
 
 extern "C" {
 
 int y355_apeval_set_gt_coco(y355_apeval *e, const int32_t *offsets, const double *boxes_xywh, const double *area, const int32_t *cls,
                             const uint8_t *iscrowd, const int32_t *image_rank) {
-    if (int rc = coco_check_handle(e)) return rc;
-    if (!offsets) return y355_fail(Y355_EINVAL, "null offsets");
-    if (offsets[0] != 0) return y355_fail(Y355_EINVAL, "offsets[0] must be 0");
+    long long n = 0;
+    if (int rc = ap_check_gt(e, offsets, cls, boxes_xywh && area && cls && iscrowd, &n)) return rc;
     const int N = e->num_images;
-    for (int i = 0; i < N; ++i)
-        if (offsets[i + 1] < offsets[i]) return y355_fail(Y355_EINVAL, "offsets must not decrease");
-    const long long n = offsets[N];
-    if (n > 0 && (!boxes_xywh || !area || !cls || !iscrowd)) return y355_fail(Y355_EINVAL, "null ground-truth array");
-    for (long long g = 0; g < n; ++g)
-        if (cls[g] < 0 || cls[g] >= e->C) return y355_fail(Y355_EINVAL, "ground-truth class outside 0 .. num_classes - 1");
     std::vector<int32_t> rank(N);
     if (image_rank) {
         std::vector<uint8_t> seen(N, 0);
@@ -363,34 +323,14 @@ int y355_apeval_set_gt_coco(y355_apeval *e, const int32_t *offsets, const double
             }
         }
     }
-    if (ap_enter(e)) return Y355_EHIP;
-    HIPCHK(hipStreamSynchronize(e->s));
-    if (!e->coco) e->coco = new y355_coco;
-    y355_coco *c = e->coco;
-    c->have_gt = false, c->have_result = false;
-    void *old[] = {c->gt_off, c->gt_cls, c->img_rank, c->gt_box, c->gt_area, c->gt_crowd};
-    for (void *p : old)
-        if (p) (void)hipFree(p);
-    c->gt_off = c->gt_cls = c->img_rank = nullptr, c->gt_box = c->gt_area = nullptr, c->gt_crowd = nullptr;
-    if (ap_alloc(&c->gt_off, (size_t)N + 1) || ap_alloc(&c->gt_cls, (size_t)n) || ap_alloc(&c->img_rank, (size_t)N) ||
-        ap_alloc(&c->gt_box, 4 * (size_t)n) || ap_alloc(&c->gt_area, (size_t)n) || ap_alloc(&c->gt_crowd, (size_t)n))
-        return Y355_EHIP;
-    HIPCHK(hipMemcpy(c->gt_off, offsets, ((size_t)N + 1) * sizeof(int32_t), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(c->img_rank, rank.data(), (size_t)N * sizeof(int32_t), hipMemcpyHostToDevice));
-    if (n > 0) {
-        HIPCHK(hipMemcpy(c->gt_cls, h_cls.data(), (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->gt_box, h_box.data(), 4 * (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->gt_area, h_area.data(), (size_t)n * sizeof(double), hipMemcpyHostToDevice));
-        HIPCHK(hipMemcpy(c->gt_crowd, h_crowd.data(), (size_t)n, hipMemcpyHostToDevice));
-    }
-    c->h_cls.swap(h_cls), c->h_area.swap(h_area), c->h_crowd.swap(h_crowd);
-    c->n_gt = n, c->have_gt = true;
-    return 0;
+    if (int rc = ap_enter(e)) return rc;
+    HIPCHK(hipStreamSynchronize(e->s));                   // nothing in flight reads the arrays that go
+    return coco_set_gt(e, offsets, rank.data(), h_box, h_cls, h_area, h_crowd);
 }
 
 int y355_apeval_compute_coco(y355_apeval *e, const double *iou_thrs, int T, const double *rec_thrs, int R, const double *area_rng, int A,
                              const int32_t *max_dets, int M, double *precision, double *recall, double *stats) {
-    if (int rc = coco_check_handle(e)) return rc;
+    if (int rc = ap_check_handle(e)) return rc;
     if (!iou_thrs || !rec_thrs || !area_rng || !max_dets) return y355_fail(Y355_EINVAL, "null parameter array");
     if (!precision || !recall) return y355_fail(Y355_EINVAL, "null output");
     if (T < 1 || T > COCO_MAX_T) return y355_fail(Y355_EINVAL, "T outside 1 .. 16");
@@ -403,7 +343,7 @@ int y355_apeval_compute_coco(y355_apeval *e, const double *iou_thrs, int T, cons
     }
     y355_coco *c = e->coco;
     if (!c || !c->have_gt) return y355_fail(Y355_ENOTREADY, "no COCO ground truth: call y355_apeval_set_gt_coco first");
-    if (ap_enter(e)) return Y355_EHIP;
+    if (int rc = ap_enter(e)) return rc;
     c->have_result = false;
     hipStream_t s = e->s;
     long long n = 0;
@@ -420,14 +360,8 @@ int y355_apeval_compute_coco(y355_apeval *e, const double *iou_thrs, int T, cons
     for (long long g = 0; g < c->n_gt; ++g)
         for (int a = 0; a < A; ++a)
             if (!(c->h_crowd[g] || c->h_area[g] < P.alo[a] || c->h_area[g] > P.ahi[a])) ++npig[(size_t)c->h_cls[g] * A + a];
-    const size_t np = (size_t)T * R * K * A * M, nr = (size_t)T * K * A * M, n1 = (size_t)(n > 0 ? n : 1);
-    size_t one = c->npig ? (size_t)K * COCO_MAX_A : 0, rt = c->rec_thrs ? COCO_MAX_R : 0, ncap[4] = {c->n_cap, c->n_cap, c->n_cap, c->n_cap};
-    if (coco_grow(&c->npig, &one, (size_t)K * COCO_MAX_A) || coco_grow(&c->rec_thrs, &rt, (size_t)COCO_MAX_R) ||
-        coco_grow(&c->prec_out, &c->prec_cap, np) || coco_grow(&c->rec_out, &c->rec_cap, nr) || coco_grow(&c->permA, &ncap[0], n1) ||
-        coco_grow(&c->permB, &ncap[1], n1) || coco_grow(&c->gkey, &ncap[2], n1) || coco_grow(&c->gidx, &ncap[3], n1) ||
-        coco_grow(&c->w0, &c->n_cap, n1) || coco_grow(&c->flags, &c->flags_cap, (size_t)A * T * n1) ||
-        coco_grow(&c->marks, &c->marks_cap, (size_t)A * T * (size_t)(c->n_gt > 0 ? c->n_gt : 1)))
-        return Y355_EHIP;
+    const size_t np = (size_t)T * R * K * A * M, nr = (size_t)T * K * A * M;
+    if (int rc = coco_workspaces(e, n, T, R, A, M)) return rc;
     HIPCHK(hipMemcpyAsync(c->npig, npig.data(), npig.size() * sizeof(int32_t), hipMemcpyHostToDevice, s));
     HIPCHK(hipMemcpyAsync(c->rec_thrs, rec_thrs, (size_t)R * sizeof(double), hipMemcpyHostToDevice, s));
     if (n > 0) {
@@ -481,7 +415,7 @@ int y355_apeval_compute_coco(y355_apeval *e, const double *iou_thrs, int T, cons
 
 int y355_apeval_coco_matches(y355_apeval *e, int image, int cls, int area_index, int64_t cap_d, int64_t cap_g, int64_t *num_d, int64_t *num_g,
                              int32_t *det_pos, int32_t *dt_match, uint8_t *dt_ignore, uint8_t *gt_marked) {
-    if (int rc = coco_check_handle(e)) return rc;
+    if (int rc = ap_check_handle(e)) return rc;
     if (!num_d || !num_g) return y355_fail(Y355_EINVAL, "null count");
     if (image < 0 || image >= e->num_images) return y355_fail(Y355_EINVAL, "image outside 0 .. num_images - 1");
     if (cls < 0 || cls >= e->C) return y355_fail(Y355_EINVAL, "class outside 0 .. num_classes - 1");
@@ -490,10 +424,10 @@ int y355_apeval_coco_matches(y355_apeval *e, int image, int cls, int area_index,
     if (!c || !c->have_result)
         return y355_fail(Y355_ENOTREADY, "no matches: y355_apeval_compute_coco has not succeeded since the last add / reset");
     if (area_index < 0 || area_index >= c->P.A) return y355_fail(Y355_EINVAL, "area index outside 0 .. A - 1");
-    if (ap_enter(e)) return Y355_EHIP;
+    if (int rc = ap_enter(e)) return rc;
     const int T = c->P.T;
     const size_t words = 2 + (size_t)cap_d * (1 + 2 * (size_t)T) + (size_t)cap_g * T;
-    if (coco_grow(&c->tap, &c->tap_cap, words)) return Y355_EHIP;
+    if (int rc = coco_tap(e, words)) return rc;
     coco_launch_match(e, c, dim3(1), image, cls, area_index, c->tap, (int)cap_d, (int)cap_g);
     HIPCHK(hipGetLastError());
     std::vector<int32_t> h(words);

@@ -25,8 +25,7 @@ struct HandleCore {
     unsigned int *absmax_dev = nullptr;
     int profile = 0;
     std::vector<hipEvent_t> ev;     // n + 1 events around the n profile intervals of a forward
-    DevMem mem;
-    std::vector<void *> allocs;
+    DevOwner own;                   // the layers' buffers, the counter sets, the absmax word
 };
 
 // the configuration rules the two creates share, in their order; mult: the size multiple, max_anchors: per level
@@ -50,7 +49,7 @@ inline int y355_core_open(HandleCore *h, int device_id, void *stream, bool own_s
     h->N = N;
     h->conf_thresh = conf;
     h->nms_thresh = nms;
-    h->mem = mem;
+    h->own.mem = mem;
     y355_stage_init(h->stage, H, W, max_batch, mem);
     h->stream = (hipStream_t)stream;                 // NULL = default stream (torch's default on ROCm)
     if (!own_stream) return 0;
@@ -65,11 +64,7 @@ inline int y355_core_open(HandleCore *h, int device_id, void *stream, bool own_s
 // device memory the handle owns until y355_core_close
 template <typename T>
 inline int y355_core_alloc(HandleCore *h, T **p, size_t bytes, bool zero) {
-    void *q = nullptr;
-    if (int rc = h->mem.alloc(&q, bytes, zero)) return rc;
-    h->allocs.push_back(q);
-    *p = (T *)q;
-    return 0;
+    return y355_dev_get(h->own, p, bytes, zero, 1);
 }
 
 // the two counter sets of n_ctr each, the absmax word and the head's state
@@ -79,7 +74,7 @@ inline int y355_core_state(HandleCore *h, int n_ctr, int max_det, bool host_outp
     h->ctrs.n = n_ctr;
     h->ctrs.clean[0] = h->ctrs.clean[1] = true;       // zeroed by the allocation
     if (int rc = y355_core_alloc(h, &h->absmax_dev, 16, true)) return rc;
-    return y355_head_create(h->head, h->N, h->max_batch, max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, true, host_outputs, h->mem);
+    return y355_head_create(h->head, h->N, h->max_batch, max_det, Y355_NMS_CAP, Y355_HEAD_ROUTE_AUTO, true, host_outputs, h->own.mem);
 }
 
 // the events around n profile intervals
@@ -96,8 +91,7 @@ inline int y355_core_events(HandleCore *h, int n) {
 inline void y355_core_close(HandleCore *h) {
     (void)hipSetDevice(h->device_id);
     if (h->stream) (void)hipStreamSynchronize(h->stream);
-    for (void *p : h->allocs) h->mem.release(p);
-    h->allocs.clear();
+    y355_dev_release_all(h->own);
     y355_head_destroy(h->head);
     y355_stage_destroy(h->stage);
     for (hipEvent_t e : h->ev) (void)hipEventDestroy(e);

@@ -56,8 +56,7 @@ struct HeadState {
     int *cand_cls = nullptr;
     float *o_box = nullptr, *o_score = nullptr;         // [B][max_det][4], [B][max_det] outputs of the host calls, or null
     int *o_cls = nullptr, *o_count = nullptr;
-    DevMem mem;
-    std::vector<void *> allocs;
+    DevOwner own;             // every array above
 };
 inline int y355_head_capacity(const HeadState &st) { return st.cap ? st.cap : Y355_NMS_CAP; }
 // Allocates everything a head of N anchors per image and B images needs at capacity `cap` and `route`; a failure (non-zero,

@@ -29,33 +29,6 @@ const DevMem &y355_hip_mem(void) {
 }
 
 namespace {
-// allocations of one create / resize: all of them, or none (the destructor returns what a failure left behind)
-struct Fresh {
-    HeadState &st;
-    std::vector<void *> got;
-    int rc = 0;
-    explicit Fresh(HeadState &s) : st(s) {}
-    template <typename T>
-    void get(T **p, size_t bytes, bool zero = true) {
-        void *q = nullptr;
-        if (!rc) rc = st.mem.alloc(&q, bytes, zero);
-        if (rc) return;
-        got.push_back(q);
-        *p = (T *)q;
-    }
-    void commit() {
-        st.allocs.insert(st.allocs.end(), got.begin(), got.end());
-        got.clear();
-    }
-    ~Fresh() {
-        for (void *q : got) st.mem.release(q);
-    }
-};
-void drop(HeadState &st, void *q) {
-    if (!q) return;
-    st.mem.release(q);
-    st.allocs.erase(std::remove(st.allocs.begin(), st.allocs.end(), q), st.allocs.end());
-}
 int max_det_for(int cfg_max_det, int N, int cap) {
     const int ncand = std::min(N, cap);
     return (cfg_max_det <= 0 || cfg_max_det > ncand) ? ncand : cfg_max_det;
@@ -65,7 +38,7 @@ int max_det_for(int cfg_max_det, int N, int cap) {
 int y355_head_create(HeadState &st, int N, int B_, int cfg_max_det, int cap, int route, bool want_tap, bool want_host_outputs,
                      const DevMem &mem) {
     st = HeadState{};
-    st.mem = mem;
+    st.own.mem = mem;
     st.N = N;
     st.max_batch = B_;
     st.cfg_max_det = cfg_max_det;
@@ -73,49 +46,47 @@ int y355_head_create(HeadState &st, int N, int B_, int cfg_max_det, int cap, int
     st.max_det = max_det_for(cfg_max_det, N, Y355_NMS_CAP);
     const size_t B = (size_t)B_, c = Y355_NMS_CAP;
     HeadWork &w = st.wk;
-    Fresh f(st);
+    int rc = 0;             // the first failure; a failed create gives everything back below
+    auto get = [&](auto **p, size_t count, bool zero = true) { rc = rc ? rc : y355_dev_get(st.own, p, count, zero); };
     // the small route's arrays (sizes per image: HeadWork); what a kernel reads before it writes starts at zero
-    f.get(&w.cbox, sizeof(float) * 4 * c * B, false);
-    f.get(&w.cscore, sizeof(float) * c * B, false);
-    f.get(&w.ccls, sizeof(int) * c * B, false);
-    f.get(&w.corig, sizeof(int) * c * B, false);
-    f.get(&w.count, sizeof(int) * B);
-    f.get(&w.edges, sizeof(unsigned int) * (size_t)Y355_HEAD_EDGE_CAP * B, false);
-    f.get(&w.nedges, sizeof(int) * 2 * B);
-    f.get(&w.binstart, sizeof(int) * (c + 8) * B);
-    f.get(&w.astat, sizeof(float) * 4 * Y355_HEAD_MAXG * B);
-    f.get(&w.tiny, sizeof(int) * c * B);
-    f.get(&w.ntiny, sizeof(int) * B);
-    f.get(&w.ctype, sizeof(int) * c * B);
-    f.get(&w.dbox, sizeof(float) * 4 * c * B);
-    f.get(&w.dscore, sizeof(float) * c * B);
-    f.get(&w.dcls, sizeof(int) * c * B);
+    get(&w.cbox, 4 * c * B, false);
+    get(&w.cscore, c * B, false);
+    get(&w.ccls, c * B, false);
+    get(&w.corig, c * B, false);
+    get(&w.count, B);
+    get(&w.edges, (size_t)Y355_HEAD_EDGE_CAP * B, false);
+    get(&w.nedges, 2 * B);
+    get(&w.binstart, (c + 8) * B);
+    get(&w.astat, 4 * Y355_HEAD_MAXG * B);
+    get(&w.tiny, c * B);
+    get(&w.ntiny, B);
+    get(&w.ctype, c * B);
+    get(&w.dbox, 4 * c * B);
+    get(&w.dscore, c * B);
+    get(&w.dcls, c * B);
     if (want_tap) {
-        f.get(&st.cand_box, sizeof(float) * 4 * (size_t)N * B, false);
-        f.get(&st.cand_score, sizeof(float) * (size_t)N * B, false);
-        f.get(&st.cand_cls, sizeof(int) * (size_t)N * B, false);
+        get(&st.cand_box, 4 * (size_t)N * B, false);
+        get(&st.cand_score, (size_t)N * B, false);
+        get(&st.cand_cls, (size_t)N * B, false);
     }
-    if (want_host_outputs) f.get(&st.o_count, sizeof(int) * B);
-    if (!f.rc) {
-        f.commit();
-        f.rc = y355_head_resize(st, cap, route);        // the raw decode, the large route's lists, o_box / o_score / o_cls
-    }
-    if (f.rc) y355_head_destroy(st);
-    return f.rc;
+    if (want_host_outputs) get(&st.o_count, B);
+    if (!rc) rc = y355_head_resize(st, cap, route);     // the raw decode, the large route's lists, o_box / o_score / o_cls
+    if (rc) y355_head_destroy(st);
+    return rc;
 }
 
 void y355_head_destroy(HeadState &st) {
-    for (void *q : st.allocs) st.mem.release(q);
-    const DevMem mem = st.mem;
+    y355_dev_release_all(st.own);
+    const DevMem mem = st.own.mem;
     st = HeadState{};
-    st.mem = mem;
+    st.own.mem = mem;
 }
 
 int y355_head_resize(HeadState &st, int cap, int route) {
     static_assert(Y355_NMS_MAX_CAP <= 65536 && Y355_NMS_MAX_CLASSES <= 256, "sort_large_kernel packs class << 16 | rank, 8 + 16 bits");
     const size_t B = (size_t)st.max_batch, c = (size_t)cap;
     const int md = max_det_for(st.cfg_max_det, st.N, cap);
-    HeadState nw = st;              // (allocs is copied too: small, and only on this cold path)
+    HeadState nw = st;              // (the owner's list is copied too: small, and only on this cold path)
     HeadWork &w = nw.wk;
     w.lbox = w.lscore = nullptr;
     w.lcls = w.lcount = nullptr;
@@ -125,35 +96,38 @@ int y355_head_resize(HeadState &st, int cap, int route) {
     nw.cap = cap;
     nw.route = route;
     nw.max_det = md;
-    Fresh f(nw);
+    const size_t mark = y355_dev_mark(nw.own);      // all or nothing: what is got below goes back if one of them fails
+    int rc = 0;
+    auto get = [&](auto **p, size_t count) { rc = rc ? rc : y355_dev_get(nw.own, p, count, true); };
     const bool raw = st.N > Y355_NMS_CAP || route == Y355_HEAD_ROUTE_LARGE, big = cap > Y355_NMS_CAP || route == Y355_HEAD_ROUTE_LARGE;
     if (raw && !w.rbox) {           // once there they stay: the launcher hides them from a small head on the automatic route
         w.rstride = (st.N + 3) / 4 * 4;
-        f.get(&w.rbox, sizeof(float) * 4 * (size_t)w.rstride * B);
-        f.get(&w.rscore, sizeof(float) * (size_t)w.rstride * B);
-        f.get(&w.rcls, sizeof(int) * (size_t)w.rstride * B);
-        f.get(&w.rcount, sizeof(int) * B);
-        f.get(&w.ovf, sizeof(int) * B);
+        get(&w.rbox, 4 * (size_t)w.rstride * B);
+        get(&w.rscore, (size_t)w.rstride * B);
+        get(&w.rcls, (size_t)w.rstride * B);
+        get(&w.rcount, B);
+        get(&w.ovf, B);
     }
     if (big) {
-        f.get(&w.lbox, sizeof(float) * 4 * c * B);
-        f.get(&w.lscore, sizeof(float) * c * B);
-        f.get(&w.lcls, sizeof(int) * c * B);
-        f.get(&w.lcount, sizeof(int) * B);
-        f.get(&w.lsort, sizeof(uint2) * 2 * c * B);
-        f.get(&w.lkbox, sizeof(float) * 4 * c * B);
-        f.get(&w.lkeep, c * B);
+        get(&w.lbox, 4 * c * B);
+        get(&w.lscore, c * B);
+        get(&w.lcls, c * B);
+        get(&w.lcount, B);
+        get(&w.lsort, 2 * c * B);
+        get(&w.lkbox, 4 * c * B);
+        get(&w.lkeep, c * B);
     }
     if (st.o_count) {
-        f.get(&nw.o_box, sizeof(float) * 4 * (size_t)md * B);
-        f.get(&nw.o_score, sizeof(float) * (size_t)md * B);
-        f.get(&nw.o_cls, sizeof(int) * (size_t)md * B);
+        get(&nw.o_box, 4 * (size_t)md * B);
+        get(&nw.o_score, (size_t)md * B);
+        get(&nw.o_cls, (size_t)md * B);
     }
-    if (f.rc) return f.rc;
-    f.commit();
-    void *old[] = {st.wk.lbox, st.wk.lscore, st.wk.lcls, st.wk.lcount, st.wk.lsort, st.wk.lkbox, st.wk.lkeep,
-                   st.o_count ? st.o_box : nullptr, st.o_count ? st.o_score : nullptr, st.o_count ? st.o_cls : nullptr};
-    for (void *q : old) drop(nw, q);
+    if (rc) {
+        y355_dev_rollback(nw.own, mark);
+        return rc;
+    }
+    HeadWork &o = st.wk;            // what the new arrays replace (o_box .. o_cls are null without o_count)
+    y355_dev_drop(nw.own, &o.lbox, &o.lscore, &o.lcls, &o.lcount, &o.lsort, &o.lkbox, &o.lkeep, &st.o_box, &st.o_score, &st.o_cls);
     st = std::move(nw);
     return 0;
 }

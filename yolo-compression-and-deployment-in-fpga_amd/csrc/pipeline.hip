@@ -11,7 +11,7 @@
 // Built on the public engine ABI only (y355_create / y355_forward / ...): results are those of a stand-alone engine, bit for bit
 // (tests/test_pipeline.py).
 #include "../../include/yolo355.h"
-#include "y355_common.h"
+#include "pipeline_slot.h"
 
 #include <cstdio>
 #include <string>
@@ -21,24 +21,7 @@ bool y355_has_overflow_flags(y355_engine *h);              // engine.hip
 int y355_overflow_take(y355_engine *h, int *dst_dev);
 int y355_frames_prepare(y355_engine *h, const y355_frame *frames, int batch);  // engine.hip: all that can fail in y355_forward_frames
 
-namespace {
-int pfail(int code, const std::string &msg) { return y355_fail(code, msg); }
-
-struct Slot {
-    float *boxes = nullptr, *scores = nullptr;      // pipeline-owned outputs of the ticket in this slot (allocated on first use)
-    int32_t *cls = nullptr, *count = nullptr;
-    int32_t *ovf = nullptr;                          // [max_batch] overflow flags of the ticket's forward (heads that have them)
-    bool has_ovf = false;
-    // what the ticket's forward wrote to (the caller's buffers or the ones above)
-    float *o_boxes = nullptr, *o_scores = nullptr;
-    int32_t *o_cls = nullptr, *o_count = nullptr;
-    hipEvent_t done = nullptr;
-    hipEvent_t released = nullptr;                   // recorded by y355_pipeline_release on the consumer's stream
-    bool has_release = false;
-    long long ticket = -1;
-    int batch = 0;
-};
-}  // namespace
+static int pfail(int code, const std::string &msg) { return y355_fail(code, msg); }
 
 struct y355_pipeline {
     y355_config cfg{};
@@ -49,6 +32,7 @@ struct y355_pipeline {
     long long next = 0;
     int ring_wgs = 0;
     int max_det = 0;
+    DevOwner dev{y355_hip_mem(), {}};                // the slots' arrays
 };
 
 extern "C" void y355_pipeline_destroy(y355_pipeline *p) {
@@ -56,9 +40,8 @@ extern "C" void y355_pipeline_destroy(y355_pipeline *p) {
     (void)hipSetDevice(p->cfg.device_id);
     for (auto *e : p->eng)
         if (e) (void)y355_sync(e);
+    y355_dev_release_all(p->dev);
     for (auto &s : p->slots) {
-        (void)hipFree(s.boxes); (void)hipFree(s.scores); (void)hipFree(s.cls); (void)hipFree(s.count);
-        (void)hipFree(s.ovf);
         if (s.done) (void)hipEventDestroy(s.done);
         if (s.released) (void)hipEventDestroy(s.released);
     }
@@ -155,11 +138,7 @@ extern "C" int y355_pipeline_set_option(y355_pipeline *p, int option, int value)
             if (int rc = y355_set_option(e, option, value)) return rc;
         HIPCHK(hipSetDevice(p->cfg.device_id));
         HIPCHK(hipDeviceSynchronize());
-        for (auto &s : p->slots) {
-            (void)hipFree(s.boxes); (void)hipFree(s.scores); (void)hipFree(s.cls); (void)hipFree(s.count);
-            s.boxes = s.scores = nullptr;
-            s.cls = s.count = nullptr;
-        }
+        for (auto &s : p->slots) y355_slot_drop_outputs(s, p->dev);
         p->max_det = y355_max_det(p->eng[0]);
         return 0;
     }
@@ -193,16 +172,6 @@ extern "C" int y355_pipeline_get_trackers(y355_pipeline *p, float *scale, int32_
 }
 
 // ---- the hot path
-static int slot_outputs(y355_pipeline *p, Slot &s) {
-    if (s.boxes) return 0;
-    const size_t B = (size_t)p->cfg.max_batch, md = (size_t)p->max_det;
-    HIPCHK(hipMalloc((void **)&s.boxes, sizeof(float) * 4 * md * B));
-    HIPCHK(hipMalloc((void **)&s.scores, sizeof(float) * md * B));
-    HIPCHK(hipMalloc((void **)&s.cls, sizeof(int32_t) * md * B));
-    HIPCHK(hipMalloc((void **)&s.count, sizeof(int32_t) * B));
-    return 0;
-}
-
 enum InputKind { IN_F32, IN_U8, IN_LIST };
 
 static int submit_common(y355_pipeline *p, const void *in_dev, InputKind kind, int batch, int flags, void *caller_stream, float *boxes_dev,
@@ -225,7 +194,7 @@ static int submit_common(y355_pipeline *p, const void *in_dev, InputKind kind, i
         s.has_release = false;
     }
     if (own) {
-        if (int rc = slot_outputs(p, s)) return rc;
+        if (int rc = y355_slot_outputs(s, p->dev, p->cfg.max_batch, p->max_det)) return rc;
         boxes_dev = s.boxes; scores_dev = s.scores; cls_dev = s.cls; count_dev = s.count;
     }
     const int ef = flags & (Y355_F_GUARD | Y355_F_TAP);
@@ -235,7 +204,8 @@ static int submit_common(y355_pipeline *p, const void *in_dev, InputKind kind, i
     if (rc) return rc;
     s.has_ovf = y355_has_overflow_flags(e);           // heads of more than 4096 anchors, or with the large route forced
     if (s.has_ovf) {
-        if (!s.ovf) HIPCHK(hipMalloc((void **)&s.ovf, sizeof(int32_t) * (size_t)p->cfg.max_batch));
+        if (!s.ovf)
+            if (int rc2 = y355_dev_get(p->dev, &s.ovf, (size_t)p->cfg.max_batch)) return rc2;
         if (int rc2 = y355_overflow_take(e, s.ovf)) return rc2;      // on the handle's stream, behind the forward: no host wait
     }
     HIPCHK(hipEventRecord(s.done, es));

@@ -148,12 +148,11 @@ void y355_stage_init(FrameStage &st, int H, int W, int max_batch, const DevMem &
     st.H = H;
     st.W = W;
     st.max_batch = max_batch;
-    st.mem = mem;
+    st.own.mem = mem;
 }
 
 void y355_stage_destroy(FrameStage &st) {
-    for (void *q : st.allocs) st.mem.release(q);
-    st.allocs.clear();
+    y355_dev_release_all(st.own);
     st.tab = st.tabs = nullptr;
     st.frames = nullptr;
     st.src_h = st.src_w = 0;
@@ -169,25 +168,17 @@ int y355_stage_set_normalization(FrameStage &st, const float *mean_bgr, const fl
     return 0;
 }
 
-template <typename T>
-static int stage_need(FrameStage &st, T **p, size_t bytes) {
-    if (*p) return 0;
-    void *q = nullptr;
-    if (int rc = st.mem.alloc(&q, bytes, false)) return rc;
-    st.allocs.push_back(q);
-    *p = (T *)q;
-    return 0;
-}
-int y355_stage_need_frames(FrameStage &st) { return stage_need(st, &st.frames, (size_t)st.max_batch * st.H * st.W * 3); }
-int y355_stage_need_list(FrameStage &st) { return stage_need(st, &st.tabs, sizeof(int) * 3 * (size_t)(st.H + st.W) * st.max_batch); }
+int y355_stage_need_frames(FrameStage &st) { return st.frames ? 0 : y355_dev_get(st.own, &st.frames, (size_t)st.max_batch * st.H * st.W * 3); }
+int y355_stage_need_list(FrameStage &st) { return st.tabs ? 0 : y355_dev_get(st.own, &st.tabs, 3 * (size_t)(st.H + st.W) * st.max_batch); }
 
 int y355_stage_tables_for(FrameStage &st, int src_h, int src_w, hipStream_t s) {
     std::vector<int> tab(3 * (size_t)(st.H + st.W));
-    if (int rc = stage_need(st, &st.tab, sizeof(int) * tab.size())) return rc;
+    if (!st.tab)
+        if (int rc = y355_dev_get(st.own, &st.tab, tab.size())) return rc;
     if (st.src_h == src_h && st.src_w == src_w) return 0;
     y355_resize_tables(src_h, src_w, st.H, st.W, tab.data());
     // (the upload waits for s: a previous forward may still read the old tables)
-    if (int rc = st.mem.upload(st.tab, tab.data(), sizeof(int) * tab.size(), s)) {
+    if (int rc = st.own.mem.upload(st.tab, tab.data(), sizeof(int) * tab.size(), s)) {
         st.src_h = st.src_w = 0;        // the old tables may be partly overwritten
         return rc;
     }

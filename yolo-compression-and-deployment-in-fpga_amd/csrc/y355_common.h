@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
+#include <algorithm>
 #include <functional>
 #include <string>
 #include <vector>
@@ -365,6 +366,57 @@ struct DevMem {
 };
 const DevMem &y355_hip_mem(void);
 
+// The one owner of a piece of host state's device memory (HeadState, FrameStage, HandleCore, y355_apeval, y355_pipeline): what
+// it got and has not dropped goes back in y355_dev_release_all, whatever the fields that pointed to it say by then.
+struct DevOwner {
+    DevMem mem;
+    std::vector<void *> allocs;
+};
+// *p = count elements (of `elem` bytes: 1 = count is in bytes) the owner now holds, zeroed on demand; a failure (the allocator's
+// code) leaves *p alone
+template <typename T>
+inline int y355_dev_get(DevOwner &o, T **p, size_t count, bool zero = false, size_t elem = sizeof(T)) {
+    void *q = nullptr;
+    if (int rc = o.mem.alloc(&q, count * elem, zero)) return rc;
+    o.allocs.push_back(q);
+    *p = (T *)q;
+    return 0;
+}
+// releases what the pointers hold, forgets it, nulls them; a null one is left alone
+template <typename... T>
+inline void y355_dev_drop(DevOwner &o, T **...p) {
+    for (void *q : {(void *)*p...}) {
+        if (q) o.mem.release(q);
+        o.allocs.erase(std::remove(o.allocs.begin(), o.allocs.end(), q), o.allocs.end());
+    }
+    ((*p = nullptr), ...);
+}
+// several arrays (null now) of count elements each: all of them or, after a failure, none
+template <typename... T>
+inline int y355_dev_get_all(DevOwner &o, size_t count, T **...p) {
+    int rc = 0;
+    ((rc = rc ? rc : y355_dev_get(o, p, count)), ...);
+    if (rc) y355_dev_drop(o, p...);
+    return rc;
+}
+// one array, or several of one capacity *have (elements of each): nothing when they are there and need <= *have, else dropped
+// and got again at `need`; a failure leaves every one of them null and *have = 0
+template <typename... T>
+inline int y355_dev_grow(DevOwner &o, size_t *have, size_t need, T **...p) {
+    if (need <= *have && (... && (*p != nullptr))) return 0;
+    y355_dev_drop(o, p...);
+    const int rc = y355_dev_get_all(o, need, p...);
+    *have = rc ? 0 : need;
+    return rc;
+}
+// all or nothing across sizes: m = y355_dev_mark before a step's allocations; y355_dev_rollback(o, m) releases them when one
+// failed (their pointers: written to a copy of the state that is thrown away, or nulled by the caller)
+inline size_t y355_dev_mark(const DevOwner &o) { return o.allocs.size(); }
+inline void y355_dev_rollback(DevOwner &o, size_t mark) {
+    for (; o.allocs.size() > mark; o.allocs.pop_back()) o.mem.release(o.allocs.back());
+}
+inline void y355_dev_release_all(DevOwner &o) { y355_dev_rollback(o, 0); }       // idempotent
+
 // One prediction map of the detection head.  Channel layout [A obj | A*C cls | A*4 txtytwth],
 // anchor-major (models/slim_yolo_v2.py:330-341, models/tiny_yolo_v3.py:202-222).
 struct HeadLevel {
@@ -462,8 +514,7 @@ struct FrameStage {
     uint8_t *frames = nullptr;      // [max_batch][H][W][3]: the frames at the network size, where a forward reads them from here
     int *tabs = nullptr;            // frame lists: [max_batch][3 (H + W)], one set of tables per frame, built on the device; the
                                     // list route never touches tab / src_h / src_w
-    DevMem mem;
-    std::vector<void *> allocs;
+    DevOwner own;
 };
 void y355_stage_init(FrameStage &st, int H, int W, int max_batch, const DevMem &mem);
 void y355_stage_destroy(FrameStage &st);

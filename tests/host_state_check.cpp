@@ -1,11 +1,15 @@
-// Host-only check of the allocation logic in csrc/y355_common.h (DevOwner), csrc/head_state.hip (HeadState: create, resize's
+// Host-only check of the allocation logic in csrc/y355_host.h (DevOwner), csrc/head_state.hip (HeadState: create, resize's
 // swap and rollback, destroy), csrc/resize.hip (FrameStage: lazy buffers, the cached same-size table), csrc/handle_core.h
 // (HandleCore: a create's allocations and its unwinding; not its stream and events, which need a device), csrc/apeval.hip and
-// csrc/cocoeval.hip (y355_apeval: create-time buffers, the two ground truths, the COCO workspaces, staging, close) and
-// csrc/pipeline_slot.h (a pipeline slot's outputs).  Device memory is the host heap here, through
+// csrc/cocoeval.hip (y355_apeval: create-time buffers, the two ground truths, the COCO workspaces, staging, close),
+// csrc/pipeline_slot.h (a pipeline slot's outputs) and the two companion libraries' handles, csrc/loss.hip (y355_loss) and
+// csrc/anchors.hip (y355_anchors): the device-free half of each create, its buffers, their unwinding, the close.  Device memory
+// is the host heap here, through
 // a DevMem whose k-th allocation (or whose upload) fails on demand, so the program needs no GPU.  Built with the address and
 // undefined-behaviour sanitizers by `make -C csrc hostcheck`: a leak, a double free or a use after free ends it non-zero.
 #include "../include/yolo355.h"
+#include "../include/yolo355_anchors.h"
+#include "../include/yolo355_loss.h"
 #include "../yolo-compression-and-deployment-in-fpga_amd/csrc/apeval_shared.h"
 #include "../yolo-compression-and-deployment-in-fpga_amd/csrc/handle_core.h"
 #include "../yolo-compression-and-deployment-in-fpga_amd/csrc/pipeline_slot.h"
@@ -22,6 +26,17 @@ int y355_fail(int code, const std::string &msg) {
 }
 extern "C" const char *y355_last_error(void) { return g_err.c_str(); }
 
+// the companions' handles (loss.hip, anchors.hip; the structs stay theirs): the device-free half of a create, the buffers, the
+// owner, and what a destroy does once the device is set
+int loss_open(const y355_loss_config *cfg, const DevMem &mem, y355_loss **out);
+int loss_buffers(y355_loss *h);
+DevOwner &loss_owner(y355_loss *h);
+void loss_free(y355_loss *h);
+int anchors_open(int32_t device_id, int64_t max_boxes, int32_t max_restarts, int32_t max_k, const DevMem &mem, y355_anchors **out);
+int anchors_buffers(y355_anchors *h);
+DevOwner &anchors_owner(y355_anchors *h);
+void anchors_free(y355_anchors *h);
+
 #define CHECK(c)                                                          \
     do {                                                                  \
         if (!(c)) {                                                       \
@@ -33,12 +48,14 @@ extern "C" const char *y355_last_error(void) { return g_err.c_str(); }
 namespace {
 std::set<void *> live;
 int n_alloc = 0, fail_at = -1, n_upload = 0;
+size_t n_bytes = 0;                                 // asked for since it was last cleared
 bool fail_upload = false;
 
 DevMem host_mem() {
     DevMem m;
     m.alloc = [](void **p, size_t bytes, bool zero) -> int {
         if (n_alloc++ == fail_at) return y355_fail(Y355_EHIP, "injected allocation failure");
+        n_bytes += bytes;
         *p = zero ? calloc(1, bytes ? bytes : 16) : malloc(bytes ? bytes : 16);
         live.insert(*p);
         return 0;
@@ -402,6 +419,68 @@ void check_coco() {
     ap_close(&e);
 }
 
+// ---- the companions' handles, each fresh from the device-free half of its create (no memory yet), as a create makes them: the
+// buffers, n_want of them and bytes_want in all; the close, twice; a failure at every allocation; what a destroy does
+template <typename H>
+void check_companion(const std::function<H *()> &fresh, int (*buffers)(H *), DevOwner &(*owner)(H *), void (*free_handle)(H *), int n_want,
+                     size_t bytes_want) {
+    H *h = fresh();
+    CHECK(h && live.empty() && owner(h).allocs.empty());
+    fail_at = -1, n_alloc = 0, n_bytes = 0;
+    CHECK(buffers(h) == 0 && n_alloc == n_want && n_bytes == bytes_want && (int)live.size() == n_want && owns_exactly_live(owner(h)));
+    y355_dev_release_all(owner(h));
+    CHECK(live.empty() && owner(h).allocs.empty());
+    free_handle(h);                                 // (a second release: harmless)
+    for (int k = 0; k < n_want; ++k) {              // the k-th allocation fails: what was taken goes back, the message stays
+        h = fresh();
+        fail_at = k, n_alloc = 0, g_err.clear();
+        CHECK(buffers(h) == Y355_EHIP && live.empty() && owner(h).allocs.empty() && g_err == "injected allocation failure");
+        fail_at = -1;
+        free_handle(h);
+    }
+    h = fresh();
+    CHECK(buffers(h) == 0 && (int)live.size() == n_want && owns_exactly_live(owner(h)));
+    free_handle(h);
+    CHECK(live.empty());
+}
+void check_loss(int levels) {
+    const int A = 2, mb = 2, ml = 2, hs[3] = {levels == 1 ? 2 : 4, 2, 1};
+    y355_loss_config cfg;
+    CHECK(y355_loss_default_config(&cfg) == 0);
+    cfg.num_levels = levels, cfg.num_anchors = A, cfg.num_classes = 2, cfg.in_h = cfg.in_w = 64, cfg.max_batch = mb, cfg.max_labels_per_image = ml;
+    size_t N = 0;
+    for (int l = 0; l < levels; ++l) cfg.hs[l] = cfg.ws[l] = hs[l], cfg.stride[l] = 64 / hs[l], N += (size_t)hs[l] * hs[l] * A;
+    for (int i = 0; i < 2 * levels * A; ++i) cfg.anchors[i] = 1.5 + i;
+    y355_loss *h = nullptr;
+    CHECK(loss_open(nullptr, host_mem(), &h) == Y355_EINVAL && g_err == "y355_loss_create: null argument");
+    cfg.num_levels = 4;
+    CHECK(loss_open(&cfg, host_mem(), &h) == Y355_EINVAL && !h && g_err == "num_levels must be 1..3" && live.empty());
+    cfg.num_levels = levels;
+    const std::function<y355_loss *()> fresh = [&cfg, N] {
+        y355_loss *h = nullptr;
+        CHECK(loss_open(&cfg, host_mem(), &h) == 0 && y355_loss_num_anchors_total(h) == (int)N);
+        return h;
+    };
+    // target, labels, offsets, partial (one workgroup per image at these sizes), per_image, out
+    check_companion(fresh, loss_buffers, loss_owner, loss_free, 6, mb * N * 11 * 4 + mb * ml * 5 * 8 + (mb + 1) * 4 + mb * 5 * 8 + mb * 5 * 8 + 4 * 8);
+}
+void check_anchors(int64_t max_boxes) {
+    const size_t R = 2, nb = (size_t)max_boxes, chunks = (nb + Y355_ANCHORS_CHUNK - 1) / Y355_ANCHORS_CHUNK;
+    const size_t MR = Y355_ANCHORS_MAX_RESTARTS, MK = Y355_ANCHORS_MAX_K;
+    y355_anchors *h = nullptr;
+    CHECK(anchors_open(0, max_boxes, 65, 3, host_mem(), &h) == Y355_EINVAL && !h && g_err == "max_restarts must be 1..64" && live.empty());
+    const std::function<y355_anchors *()> fresh = [max_boxes] {
+        y355_anchors *h = nullptr;
+        CHECK(anchors_open(0, max_boxes, (int)R, 3, host_mem(), &h) == 0 && y355_anchors_num_boxes(h) == 0);
+        return h;
+    };
+    // boxes, groups, score_idx, partial; cent, init; loss, old_loss; iters, done, nfound, first; u; score_anchors, score_out; counts,
+    // init_index; flag
+    const size_t bytes = nb * 16 + R * nb + nb + R * (3 * MK + 1) * chunks * 8 + 2 * (MR * MK * 2 * 8) + 2 * MR * 8 + 4 * MR * 4 + MR * (MK - 1) * 8 +
+                         MK * 2 * 8 + (1 + MK) * 8 + 2 * (MR * MK * 4) + 4;
+    check_companion(fresh, anchors_buffers, anchors_owner, anchors_free, 18, bytes);
+}
+
 // ---- a pipeline slot's outputs: all four or none
 void check_slot() {
     DevOwner o{host_mem(), {}};
@@ -430,7 +509,11 @@ int main() {
     check_apeval_gt();
     check_coco();
     check_slot();
-    check_head(2000, 2, 0, true, true);             // a small head: engine-like (tap and host outputs)
+    check_loss(1);                                  // gt_creator's form
+    check_loss(3);                                  // multi_gt_creator's
+    check_anchors(1);                               // one chunk
+    check_anchors(Y355_ANCHORS_CHUNK + 1);          // two
+    check_head(2000, 2, 0, true, true);            // a small head: engine-like (tap and host outputs)
     check_head(2000, 1, 100, false, true);          // y355_head_f32_ex without the tap
     check_head(10647, 2, 0, true, false);           // more than 4096 anchors: y355_net-like (no host outputs)
     check_head(10647, 3, 5000, true, true);         // max_det between the two capacities

@@ -14,13 +14,17 @@
 // Nothing is handed from one workgroup to another inside a launch: the kernel boundary orders assign -> update -> assign.  Both
 // read done[r] first, so a finished restart costs nothing and keeps its result.  No floating-point atomics: every sum has one
 // fixed order, written down in the header.
-#include <hip/hip_runtime.h>
+//
+// Host side: y355_host.h's pieces (error return, HIPCHK, DeviceGuard, DevOwner).  Everything but the entry points of the public
+// header is hidden, so that this library's y355_fail and error text stay its own in a process that also holds libyolo355.so.
 #include <math.h>
-#include <stdint.h>
-#include <string>
-#include <vector>
 
 #include "../../include/yolo355_anchors.h"
+#pragma GCC visibility push(hidden)
+#include "y355_host.h"
+static_assert(Y355_ANCHORS_OK == Y355_OK && Y355_ANCHORS_EINVAL == Y355_EINVAL && Y355_ANCHORS_EHIP == Y355_EHIP &&
+                  Y355_ANCHORS_ENOTREADY == Y355_ENOTREADY,
+              "y355_fail and HIPCHK return yolo355.h's codes");
 
 #define CHUNK Y355_ANCHORS_CHUNK
 #define MAXK Y355_ANCHORS_MAX_K
@@ -37,17 +41,13 @@
 #define QUEUE_GROUP 8              // iterations queued between two reads of the done words
 static_assert(PER_THREAD == 4 && CHUNK == THREADS * PER_THREAD, "the header documents four boxes per thread");
 
-static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) {
+static thread_local std::string g_err;                  // y355_anchors_last_error's text
+#ifndef Y355_HOSTCHECK                                   // (host_state_check.cpp links its own)
+int y355_fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
-#define HIPCHK(expr)                                                                             \
-    do {                                                                                         \
-        hipError_t e_ = (expr);                                                                  \
-        if (e_ != hipSuccess)                                                                    \
-            return fail(Y355_ANCHORS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
+#endif
 
 struct y355_anchors {
     int device_id = 0, max_restarts = 0, max_k = 0;
@@ -62,21 +62,12 @@ struct y355_anchors {
     double *init = nullptr;            // the same, as the iterations found it
     double *loss = nullptr, *old_loss = nullptr;   // [max_restarts]
     double *u = nullptr;               // [max_restarts][MAXK - 1]
+    double *score_anchors = nullptr;   // [MAXK][2]: the anchor set of a y355_anchors_score
     double *score_out = nullptr;       // [1 + MAXK]: mean IoU, counts
     int *iters = nullptr, *done = nullptr, *nfound = nullptr, *first = nullptr;   // [max_restarts]
     int *counts = nullptr, *init_index = nullptr;  // [max_restarts][MAXK]
     int *flag = nullptr;               // [1]
-};
-
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t set(int dev) {
-        hipError_t e = hipGetDevice(&prev);
-        return e != hipSuccess ? e : hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
+    DevOwner own;                      // of every array above
 };
 
 // ------------------------------------------------------------------------------------------------------ device helpers
@@ -366,9 +357,54 @@ __global__ __launch_bounds__(THREADS) void score_finish_kernel(const double *__r
     if (threadIdx.x == 0) out[0] = s_sum[V_LOSS] / (double)n;
 }
 
-// ------------------------------------------------------------------------------------------------------ C ABI
-static bool bad_size(double v) { return !std::isfinite(v) || !(v > 0.0); }
+// ------------------------------------------------------------------------------------------------------ the handle
+// y355_anchors_create in two parts, as host_state_check.cpp runs them on the CPU: the rules of the sizes and the host state (no
+// device call; the handle gets its device memory from mem), ...
+int anchors_open(int32_t device_id, int64_t max_boxes, int32_t max_restarts, int32_t max_k, const DevMem &mem, y355_anchors **out) {
+    if (!out) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_create: null out");
+    *out = nullptr;
+    if (device_id < 0) return y355_fail(Y355_ANCHORS_EINVAL, "device_id < 0");
+    if (max_boxes < 1 || max_boxes > Y355_ANCHORS_MAX_BOXES) return y355_fail(Y355_ANCHORS_EINVAL, "max_boxes must be 1..2^28");
+    if (max_restarts < 1 || max_restarts > MAXR) return y355_fail(Y355_ANCHORS_EINVAL, "max_restarts must be 1..64");
+    if (max_k < 1 || max_k > MAXK) return y355_fail(Y355_ANCHORS_EINVAL, "max_k must be 1..16");
+    y355_anchors *h = new y355_anchors();
+    h->device_id = device_id;
+    h->max_boxes = max_boxes;
+    h->max_restarts = max_restarts;
+    h->max_k = max_k;
+    h->chunks_cap = (int)((max_boxes + CHUNK - 1) / CHUNK);
+    h->own.mem = mem;
+    *out = h;
+    return Y355_ANCHORS_OK;
+}
+// ... and all of its device memory (on the current device), or none of it
+int anchors_buffers(y355_anchors *h) {
+    const size_t R = (size_t)h->max_restarts, nb = (size_t)h->max_boxes;
+    DevOwner &o = h->own;
+    int rc = y355_dev_get(o, &h->boxes, nb * 2);
+    rc = rc ? rc : y355_dev_get(o, &h->groups, R * nb);
+    rc = rc ? rc : y355_dev_get(o, &h->score_idx, nb);
+    rc = rc ? rc : y355_dev_get(o, &h->partial, R * NV * h->chunks_cap);
+    rc = rc ? rc : y355_dev_get_all(o, MAXR * MAXK * 2, &h->cent, &h->init);
+    rc = rc ? rc : y355_dev_get_all(o, MAXR, &h->loss, &h->old_loss, &h->iters, &h->done, &h->nfound, &h->first);
+    rc = rc ? rc : y355_dev_get(o, &h->u, MAXR * (MAXK - 1));
+    rc = rc ? rc : y355_dev_get(o, &h->score_anchors, MAXK * 2);
+    rc = rc ? rc : y355_dev_get(o, &h->score_out, 1 + MAXK);
+    rc = rc ? rc : y355_dev_get_all(o, MAXR * MAXK, &h->counts, &h->init_index);
+    rc = rc ? rc : y355_dev_get(o, &h->flag, 1);
+    if (rc) y355_dev_release_all(o);
+    return rc;
+}
+DevOwner &anchors_owner(y355_anchors *h) { return h->own; }        // (host_state_check.cpp does not see the struct)
+void anchors_free(y355_anchors *h) {
+    y355_dev_release_all(h->own);
+    delete h;
+}
 
+static bool bad_size(double v) { return !std::isfinite(v) || !(v > 0.0); }
+#pragma GCC visibility pop
+
+// ------------------------------------------------------------------------------------------------------ C ABI
 extern "C" {
 
 const char *y355_anchors_last_error(void) { return g_err.c_str(); }
@@ -376,62 +412,28 @@ const char *y355_anchors_last_error(void) { return g_err.c_str(); }
 int y355_anchors_chunk(void) { return CHUNK; }
 
 int y355_anchors_create(int32_t device_id, int64_t max_boxes, int32_t max_restarts, int32_t max_k, y355_anchors **out) {
-    if (!out) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_create: null out");
-    *out = nullptr;
-    if (device_id < 0) return fail(Y355_ANCHORS_EINVAL, "device_id < 0");
-    if (max_boxes < 1 || max_boxes > Y355_ANCHORS_MAX_BOXES) return fail(Y355_ANCHORS_EINVAL, "max_boxes must be 1..2^28");
-    if (max_restarts < 1 || max_restarts > MAXR) return fail(Y355_ANCHORS_EINVAL, "max_restarts must be 1..64");
-    if (max_k < 1 || max_k > MAXK) return fail(Y355_ANCHORS_EINVAL, "max_k must be 1..16");
-    y355_anchors *h = new y355_anchors();
-    h->device_id = device_id;
-    h->max_boxes = max_boxes;
-    h->max_restarts = max_restarts;
-    h->max_k = max_k;
-    h->chunks_cap = (int)((max_boxes + CHUNK - 1) / CHUNK);
-    const size_t R = (size_t)max_restarts, nb = (size_t)max_boxes;
+    if (int rc = anchors_open(device_id, max_boxes, max_restarts, max_k, y355_hip_mem(), out)) return rc;
     DeviceGuard g;
-    hipError_t e = g.set(device_id);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->boxes, nb * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->groups, R * nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->score_idx, nb);
-    if (e == hipSuccess) e = hipMalloc((void **)&h->partial, R * NV * h->chunks_cap * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->cent, MAXR * MAXK * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->init, MAXR * MAXK * 2 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->loss, MAXR * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->old_loss, MAXR * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->u, MAXR * (MAXK - 1) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->score_out, (1 + MAXK) * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->iters, MAXR * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->done, MAXR * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->nfound, MAXR * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->first, MAXR * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->counts, MAXR * MAXK * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->init_index, MAXR * MAXK * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->flag, sizeof(int));
-    if (e != hipSuccess) {
-        const std::string msg = std::string("y355_anchors_create: ") + hipGetErrorString(e);
-        y355_anchors_destroy(h);
-        return fail(Y355_ANCHORS_EHIP, msg);
+    const hipError_t e = g.set(device_id);
+    const int rc = e != hipSuccess ? y355_fail(Y355_ANCHORS_EHIP, std::string("y355_anchors_create: ") + hipGetErrorString(e)) : anchors_buffers(*out);
+    if (rc) {
+        anchors_free(*out);
+        *out = nullptr;
     }
-    *out = h;
-    return Y355_ANCHORS_OK;
+    return rc;
 }
 
 void y355_anchors_destroy(y355_anchors *h) {
     if (!h) return;
     DeviceGuard g;
     (void)g.set(h->device_id);
-    void *bufs[] = {h->boxes, h->groups, h->score_idx, h->partial, h->cent, h->init, h->loss, h->old_loss, h->u,
-                    h->score_out, h->iters, h->done, h->nfound, h->first, h->counts, h->init_index, h->flag};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    delete h;
+    anchors_free(h);
 }
 
-int64_t y355_anchors_num_boxes(const y355_anchors *h) { return h ? h->n : fail(Y355_ANCHORS_EINVAL, "null handle"); }
+int64_t y355_anchors_num_boxes(const y355_anchors *h) { return h ? h->n : y355_fail(Y355_ANCHORS_EINVAL, "null handle"); }
 
 static int check_n(const y355_anchors *h, int64_t n) {
-    if (n < 1 || n > h->max_boxes) return fail(Y355_ANCHORS_EINVAL, "n must be 1..max_boxes (" + std::to_string(h->max_boxes) + ")");
+    if (n < 1 || n > h->max_boxes) return y355_fail(Y355_ANCHORS_EINVAL, "n must be 1..max_boxes (" + std::to_string(h->max_boxes) + ")");
     return Y355_ANCHORS_OK;
 }
 
@@ -442,11 +444,11 @@ static void hold(y355_anchors *h, int64_t n) {
 }
 
 int y355_anchors_set_boxes(y355_anchors *h, const double *wh, int64_t n) {
-    if (!h || !wh) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_set_boxes: null argument");
+    if (!h || !wh) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_set_boxes: null argument");
     if (check_n(h, n)) return Y355_ANCHORS_EINVAL;
     for (int64_t i = 0; i < 2 * n; ++i)
         if (bad_size(wh[i]))
-            return fail(Y355_ANCHORS_EINVAL, "box " + std::to_string(i / 2) + ": " + (i & 1 ? "h" : "w") + " must be finite and > 0");
+            return y355_fail(Y355_ANCHORS_EINVAL, "box " + std::to_string(i / 2) + ": " + (i & 1 ? "h" : "w") + " must be finite and > 0");
     hold(h, 0);
     DeviceGuard g;
     HIPCHK(g.set(h->device_id));
@@ -456,7 +458,7 @@ int y355_anchors_set_boxes(y355_anchors *h, const double *wh, int64_t n) {
 }
 
 int y355_anchors_set_boxes_dev(y355_anchors *h, const void *wh_dev, int64_t n, void *stream) {
-    if (!h || !wh_dev) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_set_boxes_dev: null argument");
+    if (!h || !wh_dev) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_set_boxes_dev: null argument");
     if (check_n(h, n)) return Y355_ANCHORS_EINVAL;
     hipStream_t s = (hipStream_t)stream;
     hold(h, 0);
@@ -469,23 +471,23 @@ int y355_anchors_set_boxes_dev(y355_anchors *h, const void *wh_dev, int64_t n, v
     HIPCHK(hipGetLastError());
     HIPCHK(hipMemcpyAsync(&flag, h->flag, sizeof(int), hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (flag) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_set_boxes_dev: every w and h must be finite and > 0");
+    if (flag) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_set_boxes_dev: every w and h must be finite and > 0");
     hold(h, n);
     return Y355_ANCHORS_OK;
 }
 
 int y355_anchors_fit(y355_anchors *h, int32_t k, int32_t restarts, int32_t max_iters, double convergence, const int32_t *first,
                      const double *u, const int32_t *init_index, void *stream) {
-    if (!h) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_fit: null handle");
-    if (k < 1 || k > h->max_k) return fail(Y355_ANCHORS_EINVAL, "k must be 1..max_k (" + std::to_string(h->max_k) + ")");
+    if (!h) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_fit: null handle");
+    if (k < 1 || k > h->max_k) return y355_fail(Y355_ANCHORS_EINVAL, "k must be 1..max_k (" + std::to_string(h->max_k) + ")");
     if (restarts < 1 || restarts > h->max_restarts)
-        return fail(Y355_ANCHORS_EINVAL, "restarts must be 1..max_restarts (" + std::to_string(h->max_restarts) + ")");
-    if (max_iters < 1) return fail(Y355_ANCHORS_EINVAL, "max_iters must be >= 1");
-    if (!std::isfinite(convergence) || convergence < 0.0) return fail(Y355_ANCHORS_EINVAL, "convergence must be finite and >= 0");
+        return y355_fail(Y355_ANCHORS_EINVAL, "restarts must be 1..max_restarts (" + std::to_string(h->max_restarts) + ")");
+    if (max_iters < 1) return y355_fail(Y355_ANCHORS_EINVAL, "max_iters must be >= 1");
+    if (!std::isfinite(convergence) || convergence < 0.0) return y355_fail(Y355_ANCHORS_EINVAL, "convergence must be finite and >= 0");
     if (init_index ? (first || u) : !first)
-        return fail(Y355_ANCHORS_EINVAL, "exactly one start: first (with u) or init_index");
-    if (!init_index && k > 1 && !u) return fail(Y355_ANCHORS_EINVAL, "u is null and k > 1");
-    if (h->n < 1) return fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_fit: no boxes set");
+        return y355_fail(Y355_ANCHORS_EINVAL, "exactly one start: first (with u) or init_index");
+    if (!init_index && k > 1 && !u) return y355_fail(Y355_ANCHORS_EINVAL, "u is null and k > 1");
+    if (h->n < 1) return y355_fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_fit: no boxes set");
     const int R = restarts, n = h->n;
     std::vector<int> h_first(MAXR, 0), h_index(MAXR * MAXK, 0);
     std::vector<double> h_u(MAXR * (MAXK - 1), 0.0);
@@ -493,15 +495,15 @@ int y355_anchors_fit(y355_anchors *h, int32_t k, int32_t restarts, int32_t max_i
         if (init_index) {
             for (int c = 0; c < k; ++c) {
                 const int v = init_index[r * k + c];
-                if (v < 0 || v >= n) return fail(Y355_ANCHORS_EINVAL, "init_index[" + std::to_string(r) + "][" + std::to_string(c) + "] outside 0..n-1");
+                if (v < 0 || v >= n) return y355_fail(Y355_ANCHORS_EINVAL, "init_index[" + std::to_string(r) + "][" + std::to_string(c) + "] outside 0..n-1");
                 h_index[r * MAXK + c] = v;
             }
         } else {
-            if (first[r] < 0 || first[r] >= n) return fail(Y355_ANCHORS_EINVAL, "first[" + std::to_string(r) + "] outside 0..n-1");
+            if (first[r] < 0 || first[r] >= n) return y355_fail(Y355_ANCHORS_EINVAL, "first[" + std::to_string(r) + "] outside 0..n-1");
             h_first[r] = first[r];
             for (int j = 0; j < k - 1; ++j) {
                 const double v = u[r * (k - 1) + j];
-                if (!(v >= 0.0) || !(v < 1.0)) return fail(Y355_ANCHORS_EINVAL, "u[" + std::to_string(r) + "][" + std::to_string(j) + "] outside [0, 1)");
+                if (!(v >= 0.0) || !(v < 1.0)) return y355_fail(Y355_ANCHORS_EINVAL, "u[" + std::to_string(r) + "][" + std::to_string(j) + "] outside [0, 1)");
                 h_u[r * (MAXK - 1) + j] = v;
             }
         }
@@ -552,8 +554,8 @@ int y355_anchors_fit(y355_anchors *h, int32_t k, int32_t restarts, int32_t max_i
 
 int y355_anchors_get_result(y355_anchors *h, double *centroids, double *loss, int32_t *iterations, int32_t *counts,
                             double *init_centroids, int32_t *best) {
-    if (!h) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_get_result: null handle");
-    if (!h->fit_r) return fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_get_result: no fit made");
+    if (!h) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_get_result: null handle");
+    if (!h->fit_r) return y355_fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_get_result: no fit made");
     const int R = h->fit_r, k = h->fit_k;
     std::vector<double> c(MAXR * MAXK * 2), c0(MAXR * MAXK * 2), l(MAXR);
     std::vector<int> it(MAXR), cn(MAXR * MAXK);
@@ -589,42 +591,36 @@ static int widen(const uint8_t *src_dev, int n, int32_t *dst) {
 }
 
 int y355_anchors_assignments(y355_anchors *h, int32_t restart, int32_t *dst) {
-    if (!h || !dst) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_assignments: null argument");
-    if (!h->fit_r) return fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_assignments: no fit made");
-    if (restart < 0 || restart >= h->fit_r) return fail(Y355_ANCHORS_EINVAL, "restart must be 0..restarts-1 of the last fit");
+    if (!h || !dst) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_assignments: null argument");
+    if (!h->fit_r) return y355_fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_assignments: no fit made");
+    if (restart < 0 || restart >= h->fit_r) return y355_fail(Y355_ANCHORS_EINVAL, "restart must be 0..restarts-1 of the last fit");
     DeviceGuard g;
     HIPCHK(g.set(h->device_id));
     return widen(h->groups + (size_t)restart * h->max_boxes, h->n, dst);
 }
 
 int y355_anchors_score(y355_anchors *h, const double *anchors, int32_t k, double *mean_iou, int32_t *counts, int32_t *best_index) {
-    if (!h || !anchors || !mean_iou || !counts) return fail(Y355_ANCHORS_EINVAL, "y355_anchors_score: null argument");
-    if (k < 1 || k > h->max_k) return fail(Y355_ANCHORS_EINVAL, "k must be 1..max_k (" + std::to_string(h->max_k) + ")");
+    if (!h || !anchors || !mean_iou || !counts) return y355_fail(Y355_ANCHORS_EINVAL, "y355_anchors_score: null argument");
+    if (k < 1 || k > h->max_k) return y355_fail(Y355_ANCHORS_EINVAL, "k must be 1..max_k (" + std::to_string(h->max_k) + ")");
     double a[MAXK * 2] = {0.0};
     for (int i = 0; i < 2 * k; ++i) {
-        if (!std::isfinite(anchors[i]) || anchors[i] < 0.0) return fail(Y355_ANCHORS_EINVAL, "anchors must be finite and >= 0");
+        if (!std::isfinite(anchors[i]) || anchors[i] < 0.0) return y355_fail(Y355_ANCHORS_EINVAL, "anchors must be finite and >= 0");
         a[i] = anchors[i];
     }
-    if (h->n < 1) return fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_score: no boxes set");
-    // slot 0 of `partial` is free between fits; the results of a fit (cent, loss, counts, groups) are not touched
+    if (h->n < 1) return y355_fail(Y355_ANCHORS_ENOTREADY, "y355_anchors_score: no boxes set");
+    // slot 0 of `partial` is free between fits; the results of a fit (cent, loss, counts, groups) are not touched.  The anchor
+    // set goes to the handle's score_anchors: the upload is synchronous, the two launches run on the null stream behind it,
+    // and the synchronous read-back returns only after them -- so the next call's upload cannot overtake this call's kernels.
     DeviceGuard g;
     HIPCHK(g.set(h->device_id));
-    double *a_dev = nullptr;
-    HIPCHK(hipMalloc((void **)&a_dev, sizeof(a)));
-    hipError_t e = hipMemcpy(a_dev, a, sizeof(a), hipMemcpyHostToDevice);
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(assign_kernel<true>, dim3(h->nchunks), dim3(THREADS), 0, nullptr, h->boxes, h->n, k, 1, (const int *)nullptr, a_dev,
-                           h->partial, h->chunks_cap, h->score_idx, (size_t)0);
-        e = hipGetLastError();
-    }
-    if (e == hipSuccess) {
-        hipLaunchKernelGGL(score_finish_kernel, dim3(1), dim3(THREADS), 0, nullptr, h->partial, h->chunks_cap, h->nchunks, k, h->n, h->score_out);
-        e = hipGetLastError();
-    }
+    HIPCHK(hipMemcpy(h->score_anchors, a, sizeof(a), hipMemcpyHostToDevice));
+    hipLaunchKernelGGL(assign_kernel<true>, dim3(h->nchunks), dim3(THREADS), 0, nullptr, h->boxes, h->n, k, 1, (const int *)nullptr,
+                       h->score_anchors, h->partial, h->chunks_cap, h->score_idx, (size_t)0);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(score_finish_kernel, dim3(1), dim3(THREADS), 0, nullptr, h->partial, h->chunks_cap, h->nchunks, k, h->n, h->score_out);
+    HIPCHK(hipGetLastError());
     double out[1 + MAXK];
-    if (e == hipSuccess) e = hipMemcpy(out, h->score_out, sizeof(out), hipMemcpyDeviceToHost);
-    (void)hipFree(a_dev);
-    if (e != hipSuccess) return fail(Y355_ANCHORS_EHIP, std::string("y355_anchors_score: ") + hipGetErrorString(e));
+    HIPCHK(hipMemcpy(out, h->score_out, sizeof(out), hipMemcpyDeviceToHost));
     *mean_iou = out[0];
     for (int q = 0; q < k; ++q) counts[q] = (int32_t)out[1 + q];
     if (best_index) return widen(h->score_idx, h->n, best_index);

@@ -1,32 +1,9 @@
 // yolo355 -- host state of the detection head (HeadState, head_nms.h): what y355_engine, y355_net and y355_head_f32_ex keep
 // for head_nms.hip / nms_large.hip -- the workspace, max_det, the candidate capacity and route, the candidate tap, the host
-// calls' outputs -- and the HIP form of DevMem.  No kernels here; host_state_check.cpp runs this file's allocation logic on
-// the CPU with an allocator that fails on demand.
+// calls' outputs.  No kernels here; host_state_check.cpp runs this file's allocation logic on the CPU with an allocator that
+// fails on demand.
 #include "../../include/yolo355.h"
 #include "head_nms.h"
-
-#include <algorithm>
-
-static int hip_alloc(void **p, size_t bytes, bool zero) {
-    HIPCHK(hipMalloc(p, bytes ? bytes : 16));
-    if (zero) {
-        const hipError_t e_ = hipMemset(*p, 0, bytes ? bytes : 16);
-        if (e_ != hipSuccess) {
-            (void)hipFree(*p);
-            return y355_fail(Y355_EHIP, std::string("hipMemset(*p, 0, bytes ? bytes : 16): ") + hipGetErrorString(e_));
-        }
-    }
-    return 0;
-}
-static int hip_upload(void *dst, const void *src, size_t bytes, hipStream_t s) {
-    HIPCHK(hipStreamSynchronize(s));
-    HIPCHK(hipMemcpy(dst, src, bytes, hipMemcpyHostToDevice));
-    return 0;
-}
-const DevMem &y355_hip_mem(void) {
-    static const DevMem m{hip_alloc, [](void *p) { (void)hipFree(p); }, hip_upload};
-    return m;
-}
 
 namespace {
 int max_det_for(int cfg_max_det, int N, int cap) {

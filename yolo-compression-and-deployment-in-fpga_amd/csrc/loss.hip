@@ -11,13 +11,16 @@
 //   loss_flat_kernel    the same terms on the flat tensors tools.loss itself takes (the drop-in of that signature)
 //   loss_finish_kernel  the partials of an image in workgroup order, then the batch means in image order
 // No floating-point atomics anywhere: every sum has one fixed order.
-#include <hip/hip_runtime.h>
+//
+// Host side: y355_host.h's pieces (error return, HIPCHK, DeviceGuard, DevOwner).  Everything but the entry points of the public
+// header is hidden, so that this library's y355_fail and error text stay its own in a process that also holds libyolo355.so.
 #include <math.h>
-#include <stdint.h>
-#include <string>
-#include <vector>
 
 #include "../../include/yolo355_loss.h"
+#pragma GCC visibility push(hidden)
+#include "y355_host.h"
+static_assert(Y355_LOSS_OK == Y355_OK && Y355_LOSS_EINVAL == Y355_EINVAL && Y355_LOSS_EHIP == Y355_EHIP && Y355_LOSS_ENOTREADY == Y355_ENOTREADY,
+              "y355_fail and HIPCHK return yolo355.h's codes");
 
 #define MAXL Y355_LOSS_MAX_LEVELS
 #define MAXA Y355_LOSS_MAX_ANCHORS
@@ -26,17 +29,13 @@
 #define LOSS_WAVES (LOSS_THREADS / 64)
 #define LOSS_MAX_WGS 32          // workgroups per image of loss_terms_kernel: a function of N only, never of the batch
 
-static thread_local std::string g_err;
-static int fail(int code, const std::string &msg) {
+static thread_local std::string g_err;                  // y355_loss_last_error's text
+#ifndef Y355_HOSTCHECK                                   // (host_state_check.cpp links its own)
+int y355_fail(int code, const std::string &msg) {
     g_err = msg;
     return code;
 }
-#define HIPCHK(expr)                                                                          \
-    do {                                                                                      \
-        hipError_t e_ = (expr);                                                               \
-        if (e_ != hipSuccess)                                                                 \
-            return fail(Y355_LOSS_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
+#endif
 
 struct LossDev {
     int nlev, A, C, N, grid_units;
@@ -61,17 +60,7 @@ struct y355_loss {
     double *partial = nullptr;        // [max_batch][nblk][5]
     double *per_image = nullptr;      // [max_batch][5]
     double *out = nullptr;            // [4]
-};
-
-struct DeviceGuard {
-    int prev = -1;
-    hipError_t set(int dev) {
-        hipError_t e = hipGetDevice(&prev);
-        return e != hipSuccess ? e : hipSetDevice(dev);
-    }
-    ~DeviceGuard() {
-        if (prev >= 0) (void)hipSetDevice(prev);
-    }
+    DevOwner own;                     // of the six arrays above
 };
 
 // ---------------------------------------------------------------------------------------------------------- targets
@@ -274,53 +263,39 @@ __global__ __launch_bounds__(LOSS_THREADS) void loss_finish_kernel(const double 
     }
 }
 
-// ---------------------------------------------------------------------------------------------------------- C ABI
-extern "C" {
-
-const char *y355_loss_last_error(void) { return g_err.c_str(); }
-
-int y355_loss_default_config(y355_loss_config *cfg) {
-    if (!cfg) return fail(Y355_LOSS_EINVAL, "y355_loss_default_config: null config");
-    *cfg = y355_loss_config{};
-    cfg->num_levels = 1;
-    cfg->wh_mul = 1.0f;
-    cfg->ignore_thresh = 0.5;
-    cfg->obj_weight = 5.0;
-    cfg->noobj_weight = 1.0;
-    cfg->max_batch = 1;
-    cfg->max_labels_per_image = 64;
-    return Y355_LOSS_OK;
-}
-
-int y355_loss_create(const y355_loss_config *cfg, y355_loss **out) {
-    if (!cfg || !out) return fail(Y355_LOSS_EINVAL, "y355_loss_create: null argument");
+// ---------------------------------------------------------------------------------------------------------- the handle
+// y355_loss_create in two parts, as host_state_check.cpp runs them on the CPU: the rules of a configuration and the host state
+// (no device call; the handle gets its device memory from mem), ...
+int loss_open(const y355_loss_config *cfg, const DevMem &mem, y355_loss **out) {
+    if (!cfg || !out) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_create: null argument");
     *out = nullptr;
     const y355_loss_config &c = *cfg;
-    if (c.device_id < 0) return fail(Y355_LOSS_EINVAL, "device_id < 0");
-    if (c.num_levels < 1 || c.num_levels > MAXL) return fail(Y355_LOSS_EINVAL, "num_levels must be 1..3");
-    if (c.num_anchors < 1 || c.num_anchors > MAXA) return fail(Y355_LOSS_EINVAL, "num_anchors must be 1..16 per level");
-    if (c.num_classes < 1 || c.num_classes > 4096) return fail(Y355_LOSS_EINVAL, "num_classes must be 1..4096");
-    if (c.in_h < 1 || c.in_w < 1 || c.in_h > 65536 || c.in_w > 65536) return fail(Y355_LOSS_EINVAL, "in_h / in_w must be 1..65536");
-    if (!(c.wh_mul > 0.0f) || !std::isfinite(c.wh_mul)) return fail(Y355_LOSS_EINVAL, "wh_mul must be finite and > 0");
+    if (c.device_id < 0) return y355_fail(Y355_LOSS_EINVAL, "device_id < 0");
+    if (c.num_levels < 1 || c.num_levels > MAXL) return y355_fail(Y355_LOSS_EINVAL, "num_levels must be 1..3");
+    if (c.num_anchors < 1 || c.num_anchors > MAXA) return y355_fail(Y355_LOSS_EINVAL, "num_anchors must be 1..16 per level");
+    if (c.num_classes < 1 || c.num_classes > 4096) return y355_fail(Y355_LOSS_EINVAL, "num_classes must be 1..4096");
+    if (c.in_h < 1 || c.in_w < 1 || c.in_h > 65536 || c.in_w > 65536) return y355_fail(Y355_LOSS_EINVAL, "in_h / in_w must be 1..65536");
+    if (!(c.wh_mul > 0.0f) || !std::isfinite(c.wh_mul)) return y355_fail(Y355_LOSS_EINVAL, "wh_mul must be finite and > 0");
     if (c.anchors_in_grid_units && c.num_levels != 1)
-        return fail(Y355_LOSS_EINVAL, "anchors_in_grid_units is gt_creator's form: one level only");
+        return y355_fail(Y355_LOSS_EINVAL, "anchors_in_grid_units is gt_creator's form: one level only");
     if (!std::isfinite(c.ignore_thresh) || !std::isfinite(c.obj_weight) || !std::isfinite(c.noobj_weight))
-        return fail(Y355_LOSS_EINVAL, "ignore_thresh / obj_weight / noobj_weight must be finite");
-    if (c.max_batch < 1 || c.max_batch > 65535) return fail(Y355_LOSS_EINVAL, "max_batch must be 1..65535");
-    if (c.max_labels_per_image < 1 || c.max_labels_per_image > (1 << 20)) return fail(Y355_LOSS_EINVAL, "max_labels_per_image must be 1..2^20");
+        return y355_fail(Y355_LOSS_EINVAL, "ignore_thresh / obj_weight / noobj_weight must be finite");
+    if (c.max_batch < 1 || c.max_batch > 65535) return y355_fail(Y355_LOSS_EINVAL, "max_batch must be 1..65535");
+    if (c.max_labels_per_image < 1 || c.max_labels_per_image > (1 << 20)) return y355_fail(Y355_LOSS_EINVAL, "max_labels_per_image must be 1..2^20");
     long long N = 0;
     for (int l = 0; l < c.num_levels; ++l) {
-        if (c.hs[l] < 1 || c.ws[l] < 1 || c.hs[l] > 4096 || c.ws[l] > 4096) return fail(Y355_LOSS_EINVAL, "hs / ws must be 1..4096");
-        if (c.stride[l] < 1) return fail(Y355_LOSS_EINVAL, "stride must be >= 1");
+        if (c.hs[l] < 1 || c.ws[l] < 1 || c.hs[l] > 4096 || c.ws[l] > 4096) return y355_fail(Y355_LOSS_EINVAL, "hs / ws must be 1..4096");
+        if (c.stride[l] < 1) return y355_fail(Y355_LOSS_EINVAL, "stride must be >= 1");
         N += (long long)c.hs[l] * c.ws[l] * c.num_anchors;
     }
     for (int i = 0; i < 2 * c.num_levels * c.num_anchors; ++i)
-        if (!(c.anchors[i] > 0.0) || !std::isfinite(c.anchors[i])) return fail(Y355_LOSS_EINVAL, "anchor sizes must be finite and > 0");
-    if (N * (5 + (long long)c.num_classes) > 0x7fffffffLL) return fail(Y355_LOSS_EINVAL, "prediction maps of an image exceed 2^31 elements");
-    if ((long long)c.max_batch * c.max_labels_per_image > (1LL << 26)) return fail(Y355_LOSS_EINVAL, "max_batch * max_labels_per_image exceeds 2^26");
+        if (!(c.anchors[i] > 0.0) || !std::isfinite(c.anchors[i])) return y355_fail(Y355_LOSS_EINVAL, "anchor sizes must be finite and > 0");
+    if (N * (5 + (long long)c.num_classes) > 0x7fffffffLL) return y355_fail(Y355_LOSS_EINVAL, "prediction maps of an image exceed 2^31 elements");
+    if ((long long)c.max_batch * c.max_labels_per_image > (1LL << 26)) return y355_fail(Y355_LOSS_EINVAL, "max_batch * max_labels_per_image exceeds 2^26");
 
     y355_loss *h = new y355_loss();
     h->cfg = c;
+    h->own.mem = mem;
     LossDev &d = h->dev;
     d = LossDev{};
     d.nlev = c.num_levels; d.A = c.num_anchors; d.C = c.num_classes; d.N = (int)N; d.grid_units = c.anchors_in_grid_units ? 1 : 0;
@@ -336,59 +311,90 @@ int y355_loss_create(const y355_loss_config *cfg, y355_loss **out) {
     d.wh_mul = c.wh_mul; d.ignore_thresh = c.ignore_thresh;
     h->nblk = (int)((N + LOSS_THREADS - 1) / LOSS_THREADS);
     if (h->nblk > LOSS_MAX_WGS) h->nblk = LOSS_MAX_WGS;
-
-    DeviceGuard g;
-    hipError_t e = g.set(c.device_id);
-    const size_t mb = (size_t)c.max_batch;
-    if (e == hipSuccess) e = hipMalloc((void **)&h->target, mb * (size_t)N * NF * sizeof(float));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->labels, mb * c.max_labels_per_image * 5 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->offsets, (mb + 1) * sizeof(int));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->partial, mb * h->nblk * 5 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->per_image, mb * 5 * sizeof(double));
-    if (e == hipSuccess) e = hipMalloc((void **)&h->out, 4 * sizeof(double));
-    if (e != hipSuccess) {
-        const std::string msg = std::string("y355_loss_create: ") + hipGetErrorString(e);
-        y355_loss_destroy(h);
-        return fail(Y355_LOSS_EHIP, msg);
-    }
     *out = h;
     return Y355_LOSS_OK;
+}
+// ... and all of its device memory (on the current device), or none of it
+int loss_buffers(y355_loss *h) {
+    const size_t mb = (size_t)h->cfg.max_batch;
+    DevOwner &o = h->own;
+    int rc = y355_dev_get(o, &h->target, mb * h->dev.N * NF);
+    rc = rc ? rc : y355_dev_get(o, &h->labels, mb * h->cfg.max_labels_per_image * 5);
+    rc = rc ? rc : y355_dev_get(o, &h->offsets, mb + 1);
+    rc = rc ? rc : y355_dev_get(o, &h->partial, mb * h->nblk * 5);
+    rc = rc ? rc : y355_dev_get(o, &h->per_image, mb * 5);
+    rc = rc ? rc : y355_dev_get(o, &h->out, 4);
+    if (rc) y355_dev_release_all(o);
+    return rc;
+}
+DevOwner &loss_owner(y355_loss *h) { return h->own; }      // (host_state_check.cpp does not see the struct)
+void loss_free(y355_loss *h) {
+    y355_dev_release_all(h->own);
+    delete h;
+}
+#pragma GCC visibility pop
+
+// ---------------------------------------------------------------------------------------------------------- C ABI
+extern "C" {
+
+const char *y355_loss_last_error(void) { return g_err.c_str(); }
+
+int y355_loss_default_config(y355_loss_config *cfg) {
+    if (!cfg) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_default_config: null config");
+    *cfg = y355_loss_config{};
+    cfg->num_levels = 1;
+    cfg->wh_mul = 1.0f;
+    cfg->ignore_thresh = 0.5;
+    cfg->obj_weight = 5.0;
+    cfg->noobj_weight = 1.0;
+    cfg->max_batch = 1;
+    cfg->max_labels_per_image = 64;
+    return Y355_LOSS_OK;
+}
+
+int y355_loss_create(const y355_loss_config *cfg, y355_loss **out) {
+    if (int rc = loss_open(cfg, y355_hip_mem(), out)) return rc;
+    DeviceGuard g;
+    const hipError_t e = g.set(cfg->device_id);
+    const int rc = e != hipSuccess ? y355_fail(Y355_LOSS_EHIP, std::string("y355_loss_create: ") + hipGetErrorString(e)) : loss_buffers(*out);
+    if (rc) {
+        loss_free(*out);
+        *out = nullptr;
+    }
+    return rc;
 }
 
 void y355_loss_destroy(y355_loss *h) {
     if (!h) return;
     DeviceGuard g;
     (void)g.set(h->cfg.device_id);
-    void *bufs[] = {h->target, h->labels, h->offsets, h->partial, h->per_image, h->out};
-    for (void *p : bufs)
-        if (p) (void)hipFree(p);
-    delete h;
+    loss_free(h);
 }
 
-int y355_loss_num_anchors_total(const y355_loss *h) { return h ? h->dev.N : fail(Y355_LOSS_EINVAL, "null handle"); }
+int y355_loss_num_anchors_total(const y355_loss *h) { return h ? h->dev.N : y355_fail(Y355_LOSS_EINVAL, "null handle"); }
 
 int y355_loss_set_labels(y355_loss *h, const int32_t *offsets, const double *labels, int32_t batch) {
-    if (!h || !offsets) return fail(Y355_LOSS_EINVAL, "y355_loss_set_labels: null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_LOSS_EINVAL, "batch must be 1..max_batch");
-    if (offsets[0] != 0) return fail(Y355_LOSS_EINVAL, "offsets[0] must be 0");
+    if (!h || !offsets) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_set_labels: null argument");
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_LOSS_EINVAL, "batch must be 1..max_batch");
+    if (offsets[0] != 0) return y355_fail(Y355_LOSS_EINVAL, "offsets[0] must be 0");
     for (int b = 0; b < batch; ++b) {
         const long long n = (long long)offsets[b + 1] - offsets[b];
-        if (n < 0) return fail(Y355_LOSS_EINVAL, "offsets must not decrease");
+        if (n < 0) return y355_fail(Y355_LOSS_EINVAL, "offsets must not decrease");
         if (n > h->cfg.max_labels_per_image)
-            return fail(Y355_LOSS_EINVAL, "image " + std::to_string(b) + " has " + std::to_string(n) + " labels, max_labels_per_image is " +
+            return y355_fail(Y355_LOSS_EINVAL, "image " + std::to_string(b) + " has " + std::to_string(n) + " labels, max_labels_per_image is " +
                                               std::to_string(h->cfg.max_labels_per_image));
     }
     const int n = offsets[batch];
-    if (n > 0 && !labels) return fail(Y355_LOSS_EINVAL, "y355_loss_set_labels: null labels");
+    if (n > 0 && !labels) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_set_labels: null labels");
     std::vector<double> host((size_t)n * 5);
     for (int k = 0; k < n; ++k) {
         const double *L = labels + 5 * (size_t)k;
         for (int j = 0; j < 5; ++j)
-            if (!std::isfinite(L[j])) return fail(Y355_LOSS_EINVAL, "label " + std::to_string(k) + ": non-finite value");
+            if (!std::isfinite(L[j])) return y355_fail(Y355_LOSS_EINVAL, "label " + std::to_string(k) + ": non-finite value");
         for (int j = 0; j < 4; ++j)
-            if (L[j] < 0.0 || L[j] > 1.0) return fail(Y355_LOSS_EINVAL, "label " + std::to_string(k) + ": coordinate outside [0, 1]");
+            if (L[j] < 0.0 || L[j] > 1.0) return y355_fail(Y355_LOSS_EINVAL, "label " + std::to_string(k) + ": coordinate outside [0, 1]");
         if (L[4] < 0.0 || L[4] >= (double)h->cfg.num_classes)
-            return fail(Y355_LOSS_EINVAL, "label " + std::to_string(k) + ": class outside 0.." + std::to_string(h->cfg.num_classes - 1));
+            return y355_fail(Y355_LOSS_EINVAL, "label " + std::to_string(k) + ": class outside 0.." + std::to_string(h->cfg.num_classes - 1));
         for (int j = 0; j < 4; ++j) host[5 * (size_t)k + j] = L[j];
         host[5 * (size_t)k + 4] = (double)(int)L[4];              // int(gt_label[-1])
     }
@@ -406,9 +412,9 @@ int y355_loss_set_labels(y355_loss *h, const int32_t *offsets, const double *lab
 }
 
 int y355_loss_get_targets(y355_loss *h, int32_t batch, float *dst_host) {
-    if (!h || !dst_host) return fail(Y355_LOSS_EINVAL, "y355_loss_get_targets: null argument");
-    if (h->labels_batch == 0) return fail(Y355_LOSS_ENOTREADY, "y355_loss_get_targets: no labels set");
-    if (batch < 1 || batch > h->labels_batch) return fail(Y355_LOSS_EINVAL, "batch must be 1..the batch of y355_loss_set_labels");
+    if (!h || !dst_host) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_get_targets: null argument");
+    if (h->labels_batch == 0) return y355_fail(Y355_LOSS_ENOTREADY, "y355_loss_get_targets: no labels set");
+    if (batch < 1 || batch > h->labels_batch) return y355_fail(Y355_LOSS_EINVAL, "batch must be 1..the batch of y355_loss_set_labels");
     DeviceGuard g;
     HIPCHK(g.set(h->cfg.device_id));
     HIPCHK(hipMemcpy(dst_host, h->target, (size_t)batch * h->dev.N * NF * sizeof(float), hipMemcpyDeviceToHost));
@@ -417,17 +423,17 @@ int y355_loss_get_targets(y355_loss *h, int32_t batch, float *dst_host) {
 
 int y355_loss_compute(y355_loss *h, const void *const *pred_dev, const void *target_dev, int32_t batch, void *stream, double *out,
                       double *per_image) {
-    if (!h || !pred_dev || !out) return fail(Y355_LOSS_EINVAL, "y355_loss_compute: null argument");
-    if (batch < 1 || batch > h->cfg.max_batch) return fail(Y355_LOSS_EINVAL, "batch must be 1..max_batch");
+    if (!h || !pred_dev || !out) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_compute: null argument");
+    if (batch < 1 || batch > h->cfg.max_batch) return y355_fail(Y355_LOSS_EINVAL, "batch must be 1..max_batch");
     PredPtrs pp{};
     for (int l = 0; l < h->dev.nlev; ++l) {
-        if (!pred_dev[l]) return fail(Y355_LOSS_EINVAL, "y355_loss_compute: null prediction map");
+        if (!pred_dev[l]) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_compute: null prediction map");
         pp.p[l] = (const float *)pred_dev[l];
     }
     if (!target_dev) {
-        if (h->labels_batch == 0) return fail(Y355_LOSS_ENOTREADY, "y355_loss_compute: no labels set and no target given");
+        if (h->labels_batch == 0) return y355_fail(Y355_LOSS_ENOTREADY, "y355_loss_compute: no labels set and no target given");
         if (h->labels_batch != batch)
-            return fail(Y355_LOSS_ENOTREADY, "y355_loss_compute: labels were set for a batch of " + std::to_string(h->labels_batch) + ", not " +
+            return y355_fail(Y355_LOSS_ENOTREADY, "y355_loss_compute: labels were set for a batch of " + std::to_string(h->labels_batch) + ", not " +
                                                  std::to_string(batch));
     }
     const float *target = target_dev ? (const float *)target_dev : h->target;
@@ -446,9 +452,9 @@ int y355_loss_compute(y355_loss *h, const void *const *pred_dev, const void *tar
 }
 
 int y355_loss_iou_score(int32_t device_id, const void *boxes_a_dev, const void *boxes_b_dev, int64_t n, void *out_dev, void *stream) {
-    if (device_id < 0 || n < 0 || n > (1LL << 31) * (long long)LOSS_THREADS) return fail(Y355_LOSS_EINVAL, "y355_loss_iou_score: bad device or n");
+    if (device_id < 0 || n < 0 || n > (1LL << 31) * (long long)LOSS_THREADS) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_iou_score: bad device or n");
     if (n == 0) return Y355_LOSS_OK;
-    if (!boxes_a_dev || !boxes_b_dev || !out_dev) return fail(Y355_LOSS_EINVAL, "y355_loss_iou_score: null argument");
+    if (!boxes_a_dev || !boxes_b_dev || !out_dev) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_iou_score: null argument");
     DeviceGuard g;
     HIPCHK(g.set(device_id));
     hipLaunchKernelGGL(iou_score_kernel, dim3((unsigned)((n + LOSS_THREADS - 1) / LOSS_THREADS)), dim3(LOSS_THREADS), 0, (hipStream_t)stream,
@@ -460,10 +466,10 @@ int y355_loss_iou_score(int32_t device_id, const void *boxes_a_dev, const void *
 int y355_loss_flat(int32_t device_id, const void *conf_dev, const void *cls_dev, const void *txtytwth_dev, const void *label_dev,
                    int32_t batch, int32_t num_anchors_total, int32_t num_classes, double obj_weight, double noobj_weight, void *stream,
                    double *out, double *per_image) {
-    if (device_id < 0 || !conf_dev || !cls_dev || !txtytwth_dev || !label_dev || !out) return fail(Y355_LOSS_EINVAL, "y355_loss_flat: null argument");
+    if (device_id < 0 || !conf_dev || !cls_dev || !txtytwth_dev || !label_dev || !out) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_flat: null argument");
     if (batch < 1 || batch > 65535 || num_anchors_total < 1 || num_classes < 1 || num_classes > 4096)
-        return fail(Y355_LOSS_EINVAL, "y355_loss_flat: batch must be 1..65535, num_anchors_total >= 1, num_classes 1..4096");
-    if (!std::isfinite(obj_weight) || !std::isfinite(noobj_weight)) return fail(Y355_LOSS_EINVAL, "y355_loss_flat: weights must be finite");
+        return y355_fail(Y355_LOSS_EINVAL, "y355_loss_flat: batch must be 1..65535, num_anchors_total >= 1, num_classes 1..4096");
+    if (!std::isfinite(obj_weight) || !std::isfinite(noobj_weight)) return y355_fail(Y355_LOSS_EINVAL, "y355_loss_flat: weights must be finite");
     int nblk = (num_anchors_total + LOSS_THREADS - 1) / LOSS_THREADS;
     if (nblk > LOSS_MAX_WGS) nblk = LOSS_MAX_WGS;
     hipStream_t s = (hipStream_t)stream;
@@ -471,7 +477,8 @@ int y355_loss_flat(int32_t device_id, const void *conf_dev, const void *cls_dev,
     HIPCHK(g.set(device_id));
     double *ws = nullptr;                                         // partial [batch][nblk][5], per_image [batch][5], out [4]
     const size_t n_part = (size_t)batch * nblk * 5, n_img = (size_t)batch * 5;
-    HIPCHK(hipMalloc((void **)&ws, (n_part + n_img + 4) * sizeof(double)));
+    DevOwner own{y355_hip_mem(), {}};                             // no handle: the workspace lives for this call
+    if (int rc = y355_dev_get(own, &ws, n_part + n_img + 4)) return rc;
     hipLaunchKernelGGL(loss_flat_kernel, dim3(nblk, batch), dim3(LOSS_THREADS), 0, s, (const float *)conf_dev, (const float *)cls_dev,
                        (const float *)txtytwth_dev, (const float *)label_dev, num_anchors_total, num_classes, ws);
     hipError_t e = hipGetLastError();
@@ -483,8 +490,8 @@ int y355_loss_flat(int32_t device_id, const void *conf_dev, const void *cls_dev,
     if (e == hipSuccess) e = hipMemcpyAsync(out, ws + n_part + n_img, 4 * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess && per_image) e = hipMemcpyAsync(per_image, ws + n_part, n_img * sizeof(double), hipMemcpyDeviceToHost, s);
     if (e == hipSuccess) e = hipStreamSynchronize(s);
-    (void)hipFree(ws);
-    if (e != hipSuccess) return fail(Y355_LOSS_EHIP, std::string("y355_loss_flat: ") + hipGetErrorString(e));
+    y355_dev_release_all(own);                                    // every path from the allocation comes through here
+    if (e != hipSuccess) return y355_fail(Y355_LOSS_EHIP, std::string("y355_loss_flat: ") + hipGetErrorString(e));
     return Y355_LOSS_OK;
 }
 

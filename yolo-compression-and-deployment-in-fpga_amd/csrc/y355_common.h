@@ -1,14 +1,13 @@
-// yolo355 -- shared device/host declarations (gfx950 only).
+// yolo355 -- shared device/host declarations of libyolo355.so (gfx950 only).  The host-side pieces that need no kernel parameter
+// struct -- y355_fail, HIPCHK, DevMem and its HIP form, DevOwner (users: HeadState, FrameStage, HandleCore, y355_apeval,
+// y355_pipeline, and in the companion libraries y355_loss and y355_anchors) -- are y355_host.h's.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <string.h>
-#include <algorithm>
-#include <functional>
-#include <string>
-#include <vector>
 
 #include <hip/hip_ext.h>
+#include "y355_host.h"      // y355_fail, HIPCHK, DevMem / DevOwner: the host-side pieces the companion libraries share
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -110,15 +109,7 @@ struct Counters {
 };
 
 // engine.hip, for the other translation units
-int y355_fail(int code, const std::string &msg);     // keeps msg for y355_last_error(), returns code
 int y355_prepare_kernels();                          // one-time kernel attributes of the int8 engine's kernels; a y355 error code
-// a HIP call of a function that returns a y355 error code: on failure Y355_EHIP, the call and HIP's text as the message
-#define HIPCHK(expr)                                                                        \
-    do {                                                                                    \
-        hipError_t e_ = (expr);                                                             \
-        if (e_ != hipSuccess)                                                               \
-            return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_)); \
-    } while (0)
 // the integer epilogue of one stand-alone layer (the operator layer of ops.hip): make_requant, with requantisation to sa_out
 // when have_out, else none (t' is the result)
 int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, const int32_t *q_b, int cout,
@@ -356,66 +347,6 @@ void y355_launch_conv1(const Conv1Params &p, hipStream_t s);
 void y355_conv1_tiles(int H, int W, int *tx, int *ty);
 void y355_pack_conv1(const int8_t *q_w /*[16][3][3][3]*/, int8_t *dst /*1024*/);
 
-// How a piece of host-side state (HeadState of head_nms.h, FrameStage below) gets and fills device memory: the HIP calls in the
-// handles (y355_hip_mem, head_state.hip), the host heap with a failure at the k-th allocation in host_state_check.cpp.
-struct DevMem {
-    std::function<int(void **p, size_t bytes, bool zero)> alloc;   // != 0: failure, y355_fail holds the message
-    std::function<void(void *p)> release;
-    // host -> device copy once everything enqueued on s has run (what s has in flight may still read dst); != 0: failure
-    std::function<int(void *dst, const void *src, size_t bytes, hipStream_t s)> upload;
-};
-const DevMem &y355_hip_mem(void);
-
-// The one owner of a piece of host state's device memory (HeadState, FrameStage, HandleCore, y355_apeval, y355_pipeline): what
-// it got and has not dropped goes back in y355_dev_release_all, whatever the fields that pointed to it say by then.
-struct DevOwner {
-    DevMem mem;
-    std::vector<void *> allocs;
-};
-// *p = count elements (of `elem` bytes: 1 = count is in bytes) the owner now holds, zeroed on demand; a failure (the allocator's
-// code) leaves *p alone
-template <typename T>
-inline int y355_dev_get(DevOwner &o, T **p, size_t count, bool zero = false, size_t elem = sizeof(T)) {
-    void *q = nullptr;
-    if (int rc = o.mem.alloc(&q, count * elem, zero)) return rc;
-    o.allocs.push_back(q);
-    *p = (T *)q;
-    return 0;
-}
-// releases what the pointers hold, forgets it, nulls them; a null one is left alone
-template <typename... T>
-inline void y355_dev_drop(DevOwner &o, T **...p) {
-    for (void *q : {(void *)*p...}) {
-        if (q) o.mem.release(q);
-        o.allocs.erase(std::remove(o.allocs.begin(), o.allocs.end(), q), o.allocs.end());
-    }
-    ((*p = nullptr), ...);
-}
-// several arrays (null now) of count elements each: all of them or, after a failure, none
-template <typename... T>
-inline int y355_dev_get_all(DevOwner &o, size_t count, T **...p) {
-    int rc = 0;
-    ((rc = rc ? rc : y355_dev_get(o, p, count)), ...);
-    if (rc) y355_dev_drop(o, p...);
-    return rc;
-}
-// one array, or several of one capacity *have (elements of each): nothing when they are there and need <= *have, else dropped
-// and got again at `need`; a failure leaves every one of them null and *have = 0
-template <typename... T>
-inline int y355_dev_grow(DevOwner &o, size_t *have, size_t need, T **...p) {
-    if (need <= *have && (... && (*p != nullptr))) return 0;
-    y355_dev_drop(o, p...);
-    const int rc = y355_dev_get_all(o, need, p...);
-    *have = rc ? 0 : need;
-    return rc;
-}
-// all or nothing across sizes: m = y355_dev_mark before a step's allocations; y355_dev_rollback(o, m) releases them when one
-// failed (their pointers: written to a copy of the state that is thrown away, or nulled by the caller)
-inline size_t y355_dev_mark(const DevOwner &o) { return o.allocs.size(); }
-inline void y355_dev_rollback(DevOwner &o, size_t mark) {
-    for (; o.allocs.size() > mark; o.allocs.pop_back()) o.mem.release(o.allocs.back());
-}
-inline void y355_dev_release_all(DevOwner &o) { y355_dev_rollback(o, 0); }       // idempotent
 
 // One prediction map of the detection head.  Channel layout [A obj | A*C cls | A*4 txtytwth],
 // anchor-major (models/slim_yolo_v2.py:330-341, models/tiny_yolo_v3.py:202-222).

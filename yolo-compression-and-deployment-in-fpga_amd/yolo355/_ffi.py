@@ -272,31 +272,34 @@ _SIGS = {
 }
 
 
-def lib():
-    """Load libyolo355.so (built by `make -C csrc` / __graft_entry__.build())."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError(
-                "yolo355: %s is missing -- build the HIP extension first "
-                "(python -c 'import __graft_entry__ as g; g.build()').  There is no CPU fallback." % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(_lib, name)
-            fn.restype = res
-            fn.argtypes = args
-    return _lib
+def loader(g, prefix, build_hint):
+    """(lib, check, declared_symbols) of one of the project's libraries for the binding module whose globals are g: LIB_PATH,
+    HEADER_PATH, _SIGS and _lib, read there at every call (a test may point them elsewhere).  prefix: of the header's function
+    names, <prefix>last_error among them.  lib() loads the library on its first call and fails loudly when it is absent."""
+    def lib():
+        if g["_lib"] is None:
+            if not os.path.exists(g["LIB_PATH"]):
+                raise ImportError("yolo355: %s is missing -- build the HIP %s.  There is no CPU fallback." % (g["LIB_PATH"], build_hint))
+            l = C.CDLL(g["LIB_PATH"])
+            for name, (res, args) in g["_SIGS"].items():
+                fn = getattr(l, name)
+                fn.restype, fn.argtypes = res, args
+            g["_lib"] = l
+        return g["_lib"]
+
+    def check(rc):
+        if rc != 0:
+            raise Y355Error(rc, getattr(lib(), prefix + "last_error")().decode("utf-8", "replace"))
+        return rc
+
+    def declared_symbols():
+        """Function names the header declares (used by the export tests)."""
+        import re
+        text = re.sub(r"/\*.*?\*/", "", open(g["HEADER_PATH"]).read(), flags=re.S)
+        return sorted(set(re.findall(r"\b(%s[a-z0-9_]+)\s*\(" % prefix, text)))
+
+    return lib, check, declared_symbols
 
 
-def check(rc):
-    if rc != 0:
-        raise Y355Error(rc, lib().y355_last_error().decode("utf-8", "replace"))
-    return rc
-
-
-def declared_symbols():
-    """Function names declared in include/yolo355.h (used by the export test)."""
-    import re
-    text = open(HEADER_PATH).read()
-    text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
-    return sorted(set(re.findall(r"\b(y355_[a-z0-9_]+)\s*\(", text)))
+# libyolo355.so, built by `make -C csrc` / __graft_entry__.build()
+lib, check, declared_symbols = loader(globals(), "y355_", "extension first (python -c 'import __graft_entry__ as g; g.build()')")

@@ -32,33 +32,8 @@ _SIGS = {
     "y355_anchors_score": (C.c_int, [C.c_void_p, P(C.c_double), C.c_int32, P(C.c_double), P(C.c_int32), P(C.c_int32)]),
 }
 _lib = None
-
-
-def lib():
-    """Load libyolo355_anchors.so (built with libyolo355.so by `make -C csrc`)."""
-    global _lib
-    if _lib is None:
-        if not os.path.exists(LIB_PATH):
-            raise ImportError("yolo355: %s is missing -- build the HIP extensions first (make -C csrc).  There is no CPU "
-                              "fallback." % LIB_PATH)
-        _lib = C.CDLL(LIB_PATH)
-        for name, (res, args) in _SIGS.items():
-            fn = getattr(_lib, name)
-            fn.restype, fn.argtypes = res, args
-    return _lib
-
-
-def check(rc):
-    if rc != 0:
-        raise _ffi.Y355Error(rc, lib().y355_anchors_last_error().decode("utf-8", "replace"))
-    return rc
-
-
-def declared_symbols():
-    """Function names declared in include/yolo355_anchors.h"""
-    import re
-    text = re.sub(r"/\*.*?\*/", "", open(HEADER_PATH).read(), flags=re.S)
-    return sorted(set(re.findall(r"\b(y355_anchors_[a-z0-9_]+)\s*\(", text)))
+# libyolo355_anchors.so, built with libyolo355.so by `make -C csrc`
+lib, check, declared_symbols = _ffi.loader(globals(), "y355_anchors_", "extensions first (make -C csrc)")
 
 
 def _f64(a):

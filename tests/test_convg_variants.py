@@ -2,7 +2,10 @@
 by the one B-fragment packer (y355_pack_bfrags, csrc/convg_shared.h), on the smallest shapes at which these can go wrong: a row and a column past the tile, a partial block of output channels, one and
 three input chunks (both LDS slabs and the last-chunk path of the 8-wave kernel), 3x3 and 1x1, the thin layout (two taps per
 k-step), stride 2 once.  Every case is bf16, so of ConvGInst's variant ladder only the plain instantiation runs here; the
-NARROW / PC / STAT branches are run by the int8 Net tests (test_int8_wide_models, test_int8_per_channel, test_net_calibration).
+NARROW / PC / STAT branches are run by the int8 Net tests: test_int8_wide_models and test_int8_per_channel (NARROW, PC and the
+64-bit epilogue on the tiles of 224-sized DarkNets with max_batch 2: 0, 1, 2, 3, 4, 6, 7, 9, 10, never 5), test_net_calibration
+(STAT, and the plain variants on every layer, on tiles 0, 1, 2, 3, 7, 8, 9), test_int8_production_tiles (all of them on the tiles of a
+416 x 416 net with max_batch 64: 0, 1, 2, 3, 4, 5, 6, 9, 10, with partial tiles; tests/int8_tile_cases.py restates the selection).
 
 bf16: small-integer operands -- every product and every partial sum is an integer below 2^24, so the fp32 accumulation is
 exact in any order and the result must EQUAL the float64 convolution (the method of test_bf16_route_is_exact_on_small_integers);

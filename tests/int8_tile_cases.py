@@ -3,8 +3,8 @@ tests/test_int8_production_tiles.py.
 
 The rules restated here: y355_convg_select and CONVG_SET (csrc/convg.hip), y355_convr_select with the int8 ring instantiations
 I0 .. I5 and the launchers' own conditions (csrc/convr.hip), and in_kbytes, cout_pad, the pointwise rule, the route of run_op and
-the 32-bit / 64-bit decision of refresh_layer_i8 and res_params (csrc/net.hip).  The C selectors have no Python binding, so this
-is a restatement and not a query: if the C rules change, it has to be changed with them, or the GPU cases stop reaching the tiles
+the 32-bit / 64-bit decision of y355_rq_net and y355_rq_res (csrc/y355_requant.h, applied by refresh_layer_i8 of csrc/net.hip).
+The C selectors have no Python binding, so this is a restatement and not a query: if the C rules change, it has to be changed with them, or the GPU cases stop reaching the tiles
 they are there for without a failure in the CPU tests.  Two things keep it honest: the family y355_net_layer_route reports is
 compared with predict()'s after every forward of the GPU tests, with the EPI64 / RESIDUAL / PER_CHANNEL flags, and
 test_net_calibration's sizes must predict exactly the tiles the issue behind these tests found them to take.
@@ -135,13 +135,38 @@ def forward_set(pred):
 
 
 # ------------------------------------------------------------------------------------------ the 32-bit / 64-bit decision
-def narrow_of(arch, qlayers, sa_in, sa, only=None):
-    """[layer] -> True when refresh_layer_i8 (csrc/net.hip) gives the layer the 32-bit epilogue under these exponents: fits32
-    on the layer's own weights, else the split form of the negative branch; a residual layer by res_params' 32-bit form alone.
-    Exact rational arithmetic (the C code's long doubles hold these integers times powers of two exactly).  only: one layer,
-    returns its bool."""
-    g = R.graph(arch)
+def narrow_rule(sa_i, e_wc, e_b, qb_max, wabs, lk, nm, sa_o, s_r=None):
+    """One layer's 32-bit / 64-bit decision from plain numbers, in exact rationals: the input's exponent, every output channel's
+    weight exponent and sum |q_w|, the bias exponent and max |q_b|, the slope nm / 2^lk, the output's exponent and, for a
+    residual layer, the residual's.  True = y355_rq_net's narrow (fits32 on the layer's own weights, else the split form of the
+    negative branch); a residual layer by y355_rq_res's 32-bit form alone (csrc/y355_requant.h)."""
     two = Fraction(2)
+    F = max(sa_i + max(int(e) for e in e_wc), int(e_b))
+    E = F + lk
+    bmax = int(qb_max) * two ** (F - int(e_b))
+    tb = max(127 * int(w) * two ** (F - sa_i - int(e)) for w, e in zip(wabs, e_wc)) + bmax
+    lim = two ** 31
+    if s_r is not None:
+        shp = E - sa_o
+        dp, dn = max(shp - lk, s_r - sa_o, 0), max(shp, s_r - sa_o, 0)
+        p_t, p_r, n_t, n_r = lk - shp + dp, sa_o - s_r + dp, dn - shp, sa_o - s_r + dn
+        return bool(max(dp, dn, p_t, p_r, n_t, n_r) <= 30 and tb < lim and bmax < lim and
+                    tb * two ** p_t + 127 * two ** p_r + two ** dp < lim and
+                    tb * nm * two ** n_t + 127 * two ** n_r + two ** dn < lim)
+    sh = E - sa_o
+    fits = tb * max(two ** max(0, lk - sh), nm * two ** max(0, -sh)) + two ** max(sh, 0) < lim and bmax < lim
+    if not fits and 9 <= sh <= 31 and 1 <= nm < 4096:
+        pos = tb * two ** max(0, lk - sh) + two ** max(sh - lk, 0)
+        neg = (tb / 256 + 1) * nm + 256 + two ** (sh - 9)
+        fits = tb < two ** 30 and pos < lim and neg < lim and bmax < lim
+    return bool(fits)
+
+
+def narrow_of(arch, qlayers, sa_in, sa, only=None):
+    """[layer] -> True when refresh_layer_i8 (csrc/net.hip, by the rules of csrc/y355_requant.h) gives the layer the 32-bit
+    epilogue under these exponents: narrow_rule on the layer's numbers (the C code's long doubles hold these integers times
+    powers of two exactly).  only: one layer, returns its bool."""
+    g = R.graph(arch)
     out = {}
     for o in g.ops:
         if o["op"] != "conv" or (only is not None and o["layer"] != only):
@@ -151,30 +176,10 @@ def narrow_of(arch, qlayers, sa_in, sa, only=None):
         qw = np.asarray(L["q_w"], np.int64)
         if e_wc.size == 1:
             e_wc = np.full(qw.shape[0], int(e_wc[0]), np.int64)
-        sa_i = sa_in if o["i"] < 0 else sa[o["i"]]
-        F = max(sa_i + int(e_wc.max()), int(L["e_b"]))
         lk, nm = R.W.ACT[o["act"]]
-        E = F + lk
-        bmax = int(np.abs(np.asarray(L["q_b"], np.int64)).max()) * two ** (F - int(L["e_b"]))
-        wabs = np.abs(qw).reshape(qw.shape[0], -1).sum(axis=1)
-        tb = max(127 * int(w) * two ** (F - sa_i - int(e)) for w, e in zip(wabs, e_wc)) + bmax
-        lim = two ** 31
-        if o["res"] >= 0:
-            sa_o, s_r = sa[o["o"]], sa[o["res"]]
-            shp = E - sa_o
-            dp, dn = max(shp - lk, s_r - sa_o, 0), max(shp, s_r - sa_o, 0)
-            p_t, p_r, n_t, n_r = lk - shp + dp, sa_o - s_r + dp, dn - shp, sa_o - s_r + dn
-            out[o["layer"]] = bool(max(dp, dn, p_t, p_r, n_t, n_r) <= 30 and tb < lim and bmax < lim and
-                                   tb * two ** p_t + 127 * two ** p_r + two ** dp < lim and
-                                   tb * nm * two ** n_t + 127 * two ** n_r + two ** dn < lim)
-            continue
-        sh = E - sa[o["o"]]
-        fits = tb * max(two ** max(0, lk - sh), nm * two ** max(0, -sh)) + two ** max(sh, 0) < lim and bmax < lim
-        if not fits and 9 <= sh <= 31 and 1 <= nm < 4096:
-            pos = tb * two ** max(0, lk - sh) + two ** max(sh - lk, 0)
-            neg = (tb / 256 + 1) * nm + 256 + two ** (sh - 9)
-            fits = tb < two ** 30 and pos < lim and neg < lim and bmax < lim
-        out[o["layer"]] = bool(fits)
+        out[o["layer"]] = narrow_rule(sa_in if o["i"] < 0 else sa[o["i"]], e_wc, L["e_b"], np.abs(np.asarray(L["q_b"], np.int64)).max(),
+                                      np.abs(qw).reshape(qw.shape[0], -1).sum(axis=1), lk, nm, sa[o["o"]],
+                                      sa[o["res"]] if o["res"] >= 0 else None)
     return out[only] if only is not None else [out[i] for i in range(len(out))]
 
 

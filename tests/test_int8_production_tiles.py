@@ -351,7 +351,7 @@ def _wide(net, tag, ql, exps, x, out):
                         break
                 else:
                     raise AssertionError("%s: no lowering up to 24 bits leaves the 32-bit epilogue" % name)
-                # valid for the engine: every accumulator shift at most 24 (conv_fixed of csrc/net.hip), the requantising
+                # valid for the engine: every accumulator shift at most 24 (Y355_RQ_SHL_MAX_NET of csrc/y355_requant.h), the requantising
                 # shift inside [-20, 62] (refresh_layer_i8)
                 Fb = max(sa[o["i"]] + int(q2[li]["e_w"].max()), int(ql[li]["e_b"]))
                 assert Fb - sa[o["i"]] - int(q2[li]["e_w"].min()) <= 24, name

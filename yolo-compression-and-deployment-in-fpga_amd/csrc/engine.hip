@@ -21,6 +21,7 @@ int y355_fail(int code, const std::string &msg) {
     return code;
 }
 static int fail(int code, const std::string &msg) { return y355_fail(code, msg); }
+static_assert(Y355_RQ_ERANGE == Y355_ERANGE, "y355_requant.h refuses with Y355_ERANGE");
 
 extern "C" const char *y355_last_error(void) { return g_err.c_str(); }
 extern "C" int y355_version(void) { return 2; }       // 2: round 6 (y355_pipeline_*, y355_calibrate, y355_conv_op, *_dev operators)
@@ -100,77 +101,6 @@ int y355_cu_count(void) {
     }
     return cached[dev];
 }
-namespace {
-// Fill the integer epilogue of one layer.  Returns Y355_ERANGE when the int32 path could
-// overflow for worst-case operands.
-// act: 0 none (prediction layer), 1 LeakyReLU(0.125) (t' = t >= 0 ? 8 t : t, F' = F + 3), 2 ReLU (utils/modules.py:26 with
-// leakyReLU=False: t' = max(t, 0), F' = F; runs on the generic kernels, whose epilogue honours neg_mul = 0)
-// wabs: max over output channels of sum |q_w| when known (else 0: 127 per weight is assumed) -- only Requant::tmax_log2, the
-// gate of the fp32-exact epilogues, uses this tight bound; `wide` keeps the operand-independent one
-// taps: kernel taps per input channel in the worst-case bound (9 for the 3x3 layers; the general geometry of convgeom.hip)
-int make_requant(int cin_real, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, int retune,
-                 const int32_t *q_b, int cout, int cout_pad, Requant *rq, int *frac_bits, std::vector<int32_t> *bias_t,
-                 std::vector<long long> *bias_w, long long wabs = 0) {
-    const int F = std::max(sa_in + e_w, e_b);
-    const int shl = F - sa_in - e_w, bshl = F - e_b;
-    const int leaky = act == 1 ? 1 : 0;
-    const int Fp = F + (leaky ? 3 : 0);
-    if (shl > 30 || bshl > 40) return fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
-    long long bmax = 0;
-    bias_t->assign(cout_pad, 0);
-    bias_w->assign(cout_pad, 0);
-    for (int c = 0; c < cout; ++c) {
-        const long long v = (long long)q_b[c] * (1ll << bshl);
-        bmax = std::max(bmax, std::llabs(v));
-        (*bias_w)[c] = v;
-        (*bias_t)[c] = (int32_t)v;     // only used when the 32-bit path is selected below
-    }
-    long long tmax = ((long long)127 * 127 * taps * cin_real) * (1ll << shl) + bmax;
-    if (leaky) tmax *= 8;
-    int sh = have_out ? Fp - sa_out : 0;
-    if (sh > 62) sh = 62;
-    if (sh < -30) return fail(Y355_ERANGE, "output exponent too large");
-    // worst-case magnitude through the rounding add / left shift
-    long double lim = (long double)tmax;
-    if (sh > 0) lim += std::ldexp(1.0L, sh - 1);
-    if (sh < 0) lim = std::ldexp((long double)tmax, -sh);
-    if (lim >= std::ldexp(1.0L, 62)) return fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
-    rq->wide = lim >= std::ldexp(1.0L, 30) ? 1 : 0;
-    long long negsafe_t0 = 0;
-    {
-        const long long rowsum = wabs > 0 ? wabs : (long long)127 * taps * cin_real;
-        const long long t0 = (127 * rowsum) * (1ll << shl) + bmax;
-        int n = 0;
-        while (n < 62 && t0 >= (1ll << n)) ++n;
-        rq->tmax_log2 = n;
-        rq->negsafe = 0;
-        negsafe_t0 = t0;
-    }
-    if (!rq->wide && sh > 31) sh = 31;
-    rq->shl = shl;
-    rq->sh = sh;
-    rq->leaky = act ? 1 : 0;
-    rq->lk = leaky ? 3 : 0;
-    rq->neg_mul = act == 2 ? 0 : 1;
-    rq->negsafe = std::ldexp((long double)negsafe_t0 * rq->neg_mul, -sh) <= 127.0L ? 1 : 0;
-    rq->sh_l = sh < 0 ? -sh : 0;
-    rq->sh_r = sh > 0 ? sh : 0;
-    rq->hm1 = sh > 0 ? (int)((1ll << (sh - 1)) - 1) : 0;
-    rq->bw = sh > 0 ? 1 : 0;
-    rq->split = 0;
-    int g = 15 + Fp - retune;
-    rq->guard_log2 = g < 0 ? 0 : (g > 63 ? 63 : g);
-    *frac_bits = Fp;
-    return 0;
-}
-}  // namespace
-
-// the integer epilogue of one stand-alone layer (the operator layer of ops.hip)
-int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, const int32_t *q_b, int cout,
-                    int cout_pad, Requant *rq, int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w) {
-    return make_requant(cin, taps, sa_in, e_w, e_b, sa_out, have_out, act, 10, q_b, cout, cout_pad, rq, frac_bits, bias_t, bias_w);
-}
-
 struct y355_engine {
     y355_config cfg{};              // anchors and classes; the rest of it lives in the core
     HandleCore core;
@@ -415,14 +345,15 @@ static int refresh_layer(y355_engine *h, int k, bool need_out) {
     if (!h->sa_set[k]) return fail(Y355_ENOTREADY, "input activation exponent not set (calibrate first)");
     if (need_out && !h->sa_set[k + 1]) return fail(Y355_ENOTREADY, "output activation exponent not set (calibrate first)");
     if (!L.bias_dirty) return 0;
-    std::vector<int32_t> bt;
-    std::vector<long long> bw;
-    int rc = make_requant(L.cin, 9, h->sa[k], L.e_w, L.e_b, h->sa[k + 1], h->sa_set[k + 1], L.leaky, h->retune[k],
-                          L.q_b.data(), L.cout, L.cout_pad, &L.rq, &L.frac_bits, &bt, &bw, L.wabs);
-    if (rc) return rc;
-    HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
-    HIPCHK(hipMemcpyAsync(L.bias_w_dev, bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
-    HIPCHK(hipStreamSynchronize(h->core.stream));   // bt is a stack-owned vector
+    Y355RqLayer q;              // the tight bound of the layer's own weights (L.wabs) goes into tmax_log2 / negsafe alone
+    if (int rc = y355_rq_fail(y355_rq_layer(L.cin, 9, h->sa[k], L.e_w, L.e_b, h->sa[k + 1], h->sa_set[k + 1], L.leaky, h->retune[k],
+                                            L.q_b.data(), L.cout, L.cout_pad, L.wabs, &q)))
+        return rc;
+    L.rq = q.rq;
+    L.frac_bits = q.frac_bits;
+    HIPCHK(hipMemcpyAsync(L.bias_dev, q.bias_t.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipMemcpyAsync(L.bias_w_dev, q.bias_w.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
+    HIPCHK(hipStreamSynchronize(h->core.stream));   // q's vectors are stack-owned
     L.bias_dirty = !h->sa_set[k + 1];
     return 0;
 }

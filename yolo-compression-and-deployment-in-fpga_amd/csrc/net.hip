@@ -47,7 +47,6 @@ struct NLayer {
     Requant rq1{};            // first layer (conv1.hip epilogue)
     bool dirty = true;
     // 3x3 layers that have a ring instantiation (convr.hip): its id and the weights in its fragment order
-    long long wabs = 0;       // int8: max over output channels of sum |q_w| (0 = unknown)
     int rid = -1;
     char *wr_dev = nullptr;
     size_t wr_bytes = 0;
@@ -388,17 +387,11 @@ static int load_layer_i8(y355_net *h, int idx, const int8_t *q_w, const int32_t 
     L.e_w = *std::max_element(L.e_wc.begin(), L.e_wc.end());
     L.pc = *std::min_element(L.e_wc.begin(), L.e_wc.end()) != L.e_w;
     L.e_b = e_b;
-    {   // sum |q_w| of every output channel and its maximum: the layer's own bound on |acc| (127 * wabs) for the 32-bit-epilogue test
-        long long wabs = 0;
+    {   // sum |q_w| of every output channel: the layer's own bound on |acc| (127 * wabs_c) for the 32-bit-epilogue test (all zero = unknown)
         const size_t per = (size_t)cin * ksize * ksize;
         L.wabs_c.assign(cout, 0);
-        for (int c = 0; c < cout; ++c) {
-            long long s = 0;
-            for (size_t k = 0; k < per; ++k) s += std::abs((int)q_w[(size_t)c * per + k]);
-            L.wabs_c[c] = s;
-            wabs = std::max(wabs, s);
-        }
-        L.wabs = wabs;
+        for (int c = 0; c < cout; ++c)
+            for (size_t k = 0; k < per; ++k) L.wabs_c[c] += std::abs((int)q_w[(size_t)c * per + k]);
     }
     L.loaded = true;
     L.dirty = true;
@@ -425,89 +418,12 @@ static void act_fixed(int act, int *lk, int *neg_mul) {
     else { *lk = 0; *neg_mul = 1; }
 }
 
-// Bound on |acc| * 2^shl[c] over the output channels, shl[c] = F - sa_i - e_wc[c].  own: |acc| <= 127 * (sum |q_w| of the
-// channel), the layer's own weights; otherwise 127 * 127 per product (a per-channel layer always takes its own weights: the
-// worst-case weight in the channel with the largest shift is a bound nobody needs)
-static long double acc_bound(const NLayer &L, const OpDef &o, int F, int sa_i, bool own) {
-    const long double generic = (long double)127 * 127 * o.ksize * o.ksize * o.cin;
-    if (L.wabs <= 0 || (!own && !L.pc)) return generic * std::ldexp(1.0L, F - sa_i - (L.pc ? *std::min_element(L.e_wc.begin(), L.e_wc.end()) : L.e_w));
-    long double m = 0;
-    for (int c = 0; c < L.cout; ++c) m = std::max(m, (long double)127 * L.wabs_c[c] * std::ldexp(1.0L, F - sa_i - L.e_wc[c]));
-    return m;
-}
-
-// The fixed-point epilogue of an int8 convolution up to t' (y355_common.h), for the exponents in front of the layer -- none of
-// this depends on the output's exponent:  t = acc * 2^shc[c] + bw[c] at exponent F = max(sa_i + e_w, e_b),
-// t' = t >= 0 ? t * 2^lk : t * nm at exponent E = F + lk
-struct ConvFixed {
-    int sa_i, F, shl, bshl, lk, nm, E;      // shl: of the channels with the largest weight exponent, the smallest of shc
-    std::vector<long long> bw;              // [cout_pad] q_b << bshl
-    std::vector<int> shc;                   // [cout_pad] every output channel's own accumulator shift
-    long double bmax;                       // max |bw|
-    long double tw, tb;                     // bounds on |t|: worst-case weights / the layer's own (|acc| <= 127 sum |q_w|)
-    long double slope() const { return std::max(std::ldexp(1.0L, lk), (long double)nm); }      // |t'| <= |t| * slope()
-};
-static int conv_fixed(const y355_net *h, const OpDef &o, const NLayer &L, ConvFixed *cf) {
-    cf->sa_i = o.in < 0 ? h->sa_in : h->sa[o.in];
-    cf->F = std::max(cf->sa_i + L.e_w, L.e_b);
-    cf->shl = cf->F - cf->sa_i - L.e_w;
-    cf->bshl = cf->F - L.e_b;
-    act_fixed(o.act, &cf->lk, &cf->nm);
-    cf->E = cf->F + cf->lk;
-    if (cf->F - cf->sa_i - *std::min_element(L.e_wc.begin(), L.e_wc.end()) > 24 || cf->bshl > 40)
-        return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
-    cf->bw.assign(L.cout_pad, 0);
-    cf->shc.assign(L.cout_pad, 0);
-    cf->bmax = 0;
-    for (int c = 0; c < L.cout; ++c) {
-        cf->bw[c] = (long long)L.q_b[c] * (1ll << cf->bshl);
-        cf->shc[c] = cf->F - cf->sa_i - L.e_wc[c];
-        cf->bmax = std::max(cf->bmax, std::fabs((long double)L.q_b[c]) * std::ldexp(1.0L, cf->bshl));
-    }
-    cf->tw = acc_bound(L, o, cf->F, cf->sa_i, false) + cf->bmax;
-    cf->tb = acc_bound(L, o, cf->F, cf->sa_i, true) + cf->bmax;
-    return 0;
-}
-
-// the general-slope epilogue fits 32 bits (y355_requant_gen32) for |t| <= t:
-//   |t| * max(2^max(0, lk - sh), nm * 2^max(0, -sh)) + rounding < 2^31
-static bool fits32(const ConvFixed &cf, long double t, int sh) {
-    const long double fpos = std::ldexp(1.0L, std::max(0, cf.lk - sh)), fneg = (long double)cf.nm * std::ldexp(1.0L, std::max(0, -sh));
-    return t * std::max(fpos, fneg) + std::ldexp(1.0L, std::max(sh, 0)) < std::ldexp(1.0L, 31) && cf.bmax < std::ldexp(1.0L, 31);
-}
-
-// conv1.hip / front.hip epilogue constants: never guarded; the caller adds what its kernel reads beyond these
-static Requant requant_of(const ConvFixed &cf, int sh) {
-    Requant r{};
-    r.shl = cf.shl; r.sh = sh; r.leaky = (cf.lk || cf.nm != 1) ? 1 : 0; r.lk = cf.lk; r.neg_mul = cf.nm; r.guard_log2 = 63;
-    return r;
-}
-
-// exponents of a residual layer's epilogue (ResQ, y355_common.h) and whether its 32-bit form holds for these weights.
-// Nonzero when no bound proves the 64-bit sum u = t' 2^(G-E) + q_r 2^(G-s_r) (and its rounding) below 2^62.
-static int res_params(const y355_net *h, const OpDef &o, const ConvFixed &cf, ResQ *rr, int *narrow) {
-    const int sa_o = h->sa[o.out], s_r = h->sa[o.res1 - 1], lk = cf.lk, nm = cf.nm;
-    const int E = cf.E, G = std::max(E, s_r);
-    *rr = ResQ{};
-    rr->t_sh = G - E;
-    rr->r_sh = G - s_r;
-    rr->sh = G - sa_o;
-    *narrow = 0;
-    if (rr->t_sh > 62 || rr->r_sh > 62 || rr->sh > 62 || rr->sh < -62) return 1;
-    long double u = cf.tw * cf.slope() * std::ldexp(1.0L, rr->t_sh) + 127.0L * std::ldexp(1.0L, rr->r_sh);
-    u = rr->sh < 0 ? u * std::ldexp(1.0L, -rr->sh) : u + std::ldexp(1.0L, rr->sh);
-    if (u >= std::ldexp(1.0L, 62)) return 1;
-    // 32-bit form: both branches over their common power of two, on the layer's own weights
-    const int shp = E - sa_o;
-    const int dp = std::max({shp - lk, s_r - sa_o, 0}), dn = std::max({shp, s_r - sa_o, 0});
-    rr->p_t = lk - shp + dp; rr->p_r = sa_o - s_r + dp; rr->p_d = dp;
-    rr->n_t = dn - shp; rr->n_r = sa_o - s_r + dn; rr->n_d = dn;
-    const long double tb = cf.tb, lim = std::ldexp(1.0L, 31);
-    if (dp <= 30 && dn <= 30 && rr->p_t <= 30 && rr->p_r <= 30 && rr->n_t <= 30 && rr->n_r <= 30 && tb < lim && cf.bmax < lim &&
-        tb * std::ldexp(1.0L, rr->p_t) + 127.0L * std::ldexp(1.0L, rr->p_r) + std::ldexp(1.0L, dp) < lim &&
-        tb * nm * std::ldexp(1.0L, rr->n_t) + 127.0L * std::ldexp(1.0L, rr->n_r) + std::ldexp(1.0L, dn) < lim)
-        *narrow = 1;
-    return 0;
+// y355_rq_fixed (y355_requant.h) of the convolution of op o: the exponent in front of it, the layer's exponents, biases and sums |q_w|
+static Y355RqErr conv_fixed(const y355_net *h, const OpDef &o, const NLayer &L, Y355RqFixed *cf) {
+    int lk, nm;
+    act_fixed(o.act, &lk, &nm);
+    return y355_rq_fixed(o.in < 0 ? h->sa_in : h->sa[o.in], L.e_wc.data(), L.wabs_c.data(), L.cout, L.e_b, L.q_b.data(), L.cout, L.cout_pad, lk, nm,
+                         (long long)o.ksize * o.ksize * o.cin, Y355_RQ_SHL_MAX_NET, cf);
 }
 
 // the range proof of every loaded residual layer for the handle's exponents: the 64-bit sum u must provably fit
@@ -515,10 +431,10 @@ static int res_range_check(const y355_net *h) {
     for (int i = 0; i < h->arch->nops; ++i) {
         const OpDef &o = h->arch->ops[i];
         if (o.type != OP_CONV || !o.res1 || !h->L[o.layer].loaded) continue;
-        ConvFixed cf;
+        Y355RqFixed cf;
         ResQ rr{};
         int narrow = 0;
-        if (conv_fixed(h, o, h->L[o.layer], &cf) || res_params(h, o, cf, &rr, &narrow))
+        if (conv_fixed(h, o, h->L[o.layer], &cf).code || y355_rq_res(cf, h->sa[o.out], h->sa[o.res1 - 1], &rr, &narrow).code)
             return y355_fail(Y355_ERANGE, "residual layer: the 64-bit sum of the residual epilogue is not provably in range "
                                           "for these exponents");
     }
@@ -581,49 +497,27 @@ static int refresh_layer_i8(y355_net *h, int i) {
     NLayer &L = h->L[o.layer];
     if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
     if (!L.dirty) return 0;
-    ConvFixed cf;
-    if (int rc = conv_fixed(h, o, L, &cf)) return rc;
-    const int lk = cf.lk, nm = cf.nm, sh = cf.E - h->sa[o.out];
-    if (sh > 62 || sh < -20) return y355_fail(Y355_ERANGE, "exponent gap too large for the fixed-point epilogue");
-    // worst case |t'| (through the slope and a left shift / the rounding add) must stay below 2^62
-    long double lim = cf.tw * cf.slope();
-    lim = sh < 0 ? lim * std::ldexp(1.0L, -sh) : lim + std::ldexp(1.0L, sh);
-    if (lim >= std::ldexp(1.0L, 62)) return y355_fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
-    // 32-bit epilogue on the layer's own weights: a tighter bound than 127 per weight
-    L.rq = RequantG{cf.shl, sh, lk, nm, fits32(cf, cf.tb, sh) ? 1 : 0, 0};
-    if (!L.rq.narrow && sh >= 9 && sh <= 31 && nm >= 1 && nm < 4096) {
-        // t itself and the positive branch fit 32 bits, only t * neg_mul does not: the negative branch goes in two halves
-        const long double pos = cf.tb * std::ldexp(1.0L, std::max(0, lk - sh)) + std::ldexp(1.0L, std::max(sh - lk, 0));
-        const long double neg = (cf.tb / 256 + 1) * nm + 256 + std::ldexp(1.0L, sh - 9);
-        if (cf.tb < std::ldexp(1.0L, 30) && pos < std::ldexp(1.0L, 31) && neg < std::ldexp(1.0L, 31) && cf.bmax < std::ldexp(1.0L, 31))
-            L.rq.narrow = L.rq.split = 1;
-    }
+    Y355RqFixed cf;
+    if (int rc = y355_rq_fail(conv_fixed(h, o, L, &cf))) return rc;
+    if (int rc = y355_rq_fail(y355_rq_net(cf, h->sa[o.out], &L.rq))) return rc;
+    const int sh = L.rq.sh;
     if (o.res1) {                  // residual: its own 64-bit bound, and its own 32-bit form (no split)
         int narrow = 0;
-        if (res_params(h, o, cf, &L.rr, &narrow)) return y355_fail(Y355_ERANGE, "residual epilogue exceeds 62 bits");
+        if (int rc = y355_rq_fail(y355_rq_res(cf, h->sa[o.out], h->sa[o.res1 - 1], &L.rr, &narrow))) return rc;
         L.rq.narrow = narrow;
         L.rq.split = 0;
     }
-    L.rq1 = requant_of(cf, sh);
-    L.rq1.wide = 1;
     if (o.type == OP_CONV1) {
-        // the first layer runs conv1.hip's fast kernel when the epilogue fits 32 bits for worst-case weights.  int8 nets have
-        // no float bias: the layer's bias_dev (4 bytes per channel) holds the 32-bit copy
-        L.rq1.gen32 = fits32(cf, cf.tw, sh) ? 1 : 0;
-        std::vector<int32_t> bt(L.cout_pad, 0);
-        if (L.rq1.gen32) for (int c = 0; c < L.cout; ++c) bt[c] = (int32_t)cf.bw[c];
+        // int8 nets have no float bias: the layer's bias_dev (4 bytes per channel) holds the 32-bit copy conv1.hip's fast kernel reads
+        L.rq1 = y355_rq_first(cf, sh);
+        const std::vector<int32_t> bt = L.rq1.gen32 ? y355_rq_bias32(cf) : std::vector<int32_t>(L.cout_pad, 0);
         HIPCHK(hipMemcpyAsync(L.bias_dev, bt.data(), sizeof(int32_t) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
     }
-    if (h->front_graph && (i == 0 || i == 1)) {
-        // the same epilogue for front.hip: t = acc * 2^shl + bias below 2^24 (exact in fp32) on the layer's own weights
+    if (h->front_graph && (i == 0 || i == 1)) {                  // the same epilogue for front.hip
         Requant &fr = i == 0 ? h->frq1 : h->frq2;
-        fr = requant_of(cf, sh);
-        while (fr.tmax_log2 < 62 && std::ldexp(1.0L, fr.tmax_log2) <= cf.tb) ++fr.tmax_log2;
-        fr.negsafe = std::ldexp(cf.tb * nm, -sh) <= 127.0L ? 1 : 0;
-        // the magic-number rounding needs |t * slope| < 2^22 only where it does not saturate, and |sh| moderate
-        fr.wide = (fr.tmax_log2 > 24 || cf.bmax >= std::ldexp(1.0L, 24) || sh > 30 || sh - lk < -8 || nm < 1 || nm > (1 << lk)) ? 1 : 0;
-        std::vector<int32_t> fb(i == 0 ? 16 : 32, 0);
-        if (!fr.wide) for (int c = 0; c < L.cout; ++c) fb[c] = (int32_t)cf.bw[c];
+        fr = y355_rq_front(cf, sh);
+        std::vector<int32_t> fb = fr.wide ? std::vector<int32_t>() : y355_rq_bias32(cf);
+        fb.resize(i == 0 ? 16 : 32, 0);
         HIPCHK(hipMemcpyAsync(i == 0 ? h->fb1_dev : h->fb2_dev, fb.data(), sizeof(int32_t) * fb.size(), hipMemcpyHostToDevice, h->core.stream));
         h->front_dirty = true;
     }
@@ -1144,23 +1038,10 @@ static int cal_conv_max(y355_net *h, int i, int B, const NetInput &in, float *ou
     const OpDef &o = h->arch->ops[i];
     NLayer &L = h->L[o.layer];
     if (!L.loaded) return y355_fail(Y355_ENOTREADY, "layer weights not loaded");
-    ConvFixed cf;
-    if (int rc = conv_fixed(h, o, L, &cf)) return rc;
-    int fb = cf.E;                                             // exponent of the tracked integers
-    long double lim = cf.tw * cf.slope();
-    L.rr = ResQ{};
-    if (o.res1) {
-        const int s_r = h->sa[o.res1 - 1], G = std::max(fb, s_r);
-        L.rr.t_sh = G - fb;
-        L.rr.r_sh = G - s_r;
-        if (L.rr.t_sh > 62 || L.rr.r_sh > 62) return y355_fail(Y355_ERANGE, "residual layer: exponent gap too large");
-        lim = lim * std::ldexp(1.0L, L.rr.t_sh) + 127.0L * std::ldexp(1.0L, L.rr.r_sh);
-        fb = G;
-    }
-    if (lim >= std::ldexp(1.0L, 62)) return y355_fail(Y355_ERANGE, "fixed-point epilogue exceeds 62 bits");
-    L.rq = RequantG{cf.shl, 0, cf.lk, cf.nm, 0, 0};
-    L.rq1 = requant_of(cf, 0);
-    L.rq1.wide = 1;
+    Y355RqFixed cf;
+    if (int rc = y355_rq_fail(conv_fixed(h, o, L, &cf))) return rc;
+    int fb = 0;                                                // exponent of the tracked integers
+    if (int rc = y355_rq_fail(y355_rq_stat(cf, o.res1 != 0, o.res1 ? h->sa[o.res1 - 1] : 0, &L.rq, &L.rq1, &L.rr, &fb))) return rc;
     HIPCHK(hipMemcpyAsync(L.shl_dev, cf.shc.data(), sizeof(int) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
     HIPCHK(hipMemcpyAsync(L.bias_w_dev, cf.bw.data(), sizeof(long long) * L.cout_pad, hipMemcpyHostToDevice, h->core.stream));
     HIPCHK(hipStreamSynchronize(h->core.stream));                   // (the host vectors go out of scope)

@@ -21,6 +21,7 @@
 // operator to an OpOwner, so no return path frees by hand.  Argument checks come before the first HIP call.
 #include "../../include/yolo355.h"
 #include "y355_common.h"
+#include "y355_requant.h"       // y355_rq_layer: the integer epilogue of a stand-alone layer
 
 #include <algorithm>
 #include <cmath>
@@ -373,7 +374,7 @@ extern "C" int y355_upsample2x_f32(int device_id, const float *in, int batch, in
 // verdict "is x a dyadic int8 tensor" select the route and the requantisation constants: two 4-byte read-backs per call.
 // General geometry (include/yolo355.h y355_conv_geom): any kernel size, stride, dilation and four zero pads on the
 // implicit-GEMM kernel of convgeom.hip, in the same layouts -- input NHWC with a one-pixel halo, bf16 output NHWC with a halo,
-// int8 t' [pixel][cout_pad] -- and with make_requant's integer epilogue at the layer's tap count.
+// int8 t' [pixel][cout_pad] -- and with y355_rq_layer's integer epilogue (y355_requant.h) at the layer's tap count.
 struct y355_conv_op {
     int device = 0, kind = 0;          // kind 0 bf16, 1 int8
     int cin = 0, cout = 0, ksize = 3, stride = 1;
@@ -805,13 +806,14 @@ static int i8_prepare(y355_conv_op *op, int batch, int height, int width, int sa
     if (int rc = conv_plan(op, batch, height, width, pl)) return rc;
     if (int rc = op_weights(op, *pl, s)) return rc;
     if (sa != op->sa_cached) {
-        std::vector<int32_t> bt;
-        std::vector<long long> bw;
-        if (int rc = y355_op_requant(op->cin, op->geom ? op->g.kh * op->g.kw : 9, sa, op->e_w, op->e_b, 0, false, op->act, op->qb.data(), op->cout,
-                                     pl->cout_pad, &op->rq, &op->frac_bits, &bt, &bw))
+        Y355RqLayer q;              // no requantisation (t' is the result), retune 10, the weights' own bound unknown
+        if (int rc = y355_rq_fail(y355_rq_layer(op->cin, op->geom ? op->g.kh * op->g.kw : 9, sa, op->e_w, op->e_b, 0, false, op->act, 10,
+                                                op->qb.data(), op->cout, pl->cout_pad, 0, &q)))
             return rc;
-        if (op->bt_dev) HIPTRY(hipMemcpy(op->bt_dev, bt.data(), sizeof(int) * pl->cout_pad, hipMemcpyHostToDevice));
-        HIPTRY(hipMemcpy(op->bw_dev, bw.data(), sizeof(long long) * pl->cout_pad, hipMemcpyHostToDevice));
+        op->rq = q.rq;
+        op->frac_bits = q.frac_bits;
+        if (op->bt_dev) HIPTRY(hipMemcpy(op->bt_dev, q.bias_t.data(), sizeof(int) * pl->cout_pad, hipMemcpyHostToDevice));
+        HIPTRY(hipMemcpy(op->bw_dev, q.bias_w.data(), sizeof(long long) * pl->cout_pad, hipMemcpyHostToDevice));
         op->sa_cached = sa;
     }
     // the 3x3 kernels prefetch past the last pixel: 64 pixels of slack
@@ -942,11 +944,8 @@ extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const in
     int cpad = 0;
     const ConvKernelInfo &ki = *y355_conv_kernel(gen16_kernel(cin, pool, &cpad));
     const int cout_pad = round_up(cout, ki.bn), Ho = pool ? H / 2 : H, Wo = pool ? W / 2 : W;
-    Requant rq{};
-    int fb = 0;
-    std::vector<int32_t> bt;
-    std::vector<long long> bw;
-    if (int rc = y355_op_requant(cin, 9, sa_in, e_w, e_b, sa_out, true, geom_act(flags), q_b, cout, cout_pad, &rq, &fb, &bt, &bw)) return rc;
+    Y355RqLayer q;
+    if (int rc = y355_rq_fail(y355_rq_layer(cin, 9, sa_in, e_w, e_b, sa_out, true, geom_act(flags), 10, q_b, cout, cout_pad, 0, &q))) return rc;
     const size_t in_bytes = ((size_t)batch * (H + 2) * (W + 2) + 64) * cpad, out_elems = (size_t)batch * Ho * Wo * cout_pad;
     const std::vector<int8_t> xin = nhwc_halo_i8(q_in, batch, cin, H, W, cpad, in_bytes);
     std::vector<int8_t> packed(y355_packed_bytes(ki, cout_pad));
@@ -964,13 +963,13 @@ extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const in
     HIPTRY(tmp.get(&d_c, sizeof(Counters)));
     HIPTRY(hipMemcpy(d_in, xin.data(), in_bytes, hipMemcpyHostToDevice));
     HIPTRY(hipMemcpy(d_w, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(d_b, bt.data(), sizeof(int) * cout_pad, hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(d_bw, bw.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(d_b, q.bias_t.data(), sizeof(int) * cout_pad, hipMemcpyHostToDevice));
+    HIPTRY(hipMemcpy(d_bw, q.bias_w.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
     HIPTRY(hipMemset(d_out, 0, out_elems + 64));
     Counters cz{}, cs{};
     for (int mode = 1; mode >= 0; --mode) {
         HIPTRY(hipMemset(d_c, 0, sizeof(Counters)));
-        ConvParams p = gen16_params(ki, d_in, d_w, d_b, d_bw, d_c, batch, H, W, cout_pad, rq);
+        ConvParams p = gen16_params(ki, d_in, d_w, d_b, d_bw, d_c, batch, H, W, cout_pad, q.rq);
         p.out = d_out; p.mode = mode; p.guard = 1;
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, 0);
         HIPTRY(hipGetLastError());
@@ -982,7 +981,7 @@ extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const in
     nhwc_to_nchw(o.data(), out, batch, cout, Ho, Wo, cout_pad);
     if (stats) {
         stats->absmax_t = (int64_t)cs.absmax;
-        stats->frac_bits = fb;
+        stats->frac_bits = q.frac_bits;
         stats->reserved = 0;
         stats->saturated = (int64_t)cz.sat;
         stats->guard = (int64_t)cz.guard;

@@ -8,6 +8,8 @@
 
 #include <hip/hip_ext.h>
 #include "y355_host.h"      // y355_fail, HIPCHK, DevMem / DevOwner: the host-side pieces the companion libraries share
+#include "y355_requant.h"   // Requant, RequantG, ResQ and their host-side derivation: the fixed-point epilogue's constants
+inline int y355_rq_fail(const Y355RqErr &e) { return e.code ? y355_fail(e.code, e.msg) : 0; }      // a refusal of y355_requant.h as a y355 error
 
 typedef int v4i __attribute__((ext_vector_type(4)));
 typedef float v4f __attribute__((ext_vector_type(4)));
@@ -21,43 +23,6 @@ typedef __bf16 v8bf __attribute__((ext_vector_type(8)));
         if ((e0) && (e1)) hipExtLaunchKernelGGL(kernel, grid, block, lds, stream, (hipEvent_t)(e0), (hipEvent_t)(e1), 0, __VA_ARGS__); \
         else hipLaunchKernelGGL(kernel, grid, block, lds, stream, __VA_ARGS__);                                          \
     } while (0)
-
-// Fixed-point epilogue of one fused layer (DESIGN.md "requantisation"):
-//   t  = (acc << shl) + bias_t[c]        bias_t = q_b << (F - e_b),  F = max(sa_in + e_w, e_b)
-//   t' = leaky ? max(t, 8 t) : t         LeakyReLU(0.125) scaled by 8, F' = F + 3
-//   q  = clamp(RNE(t' * 2^-sh), +-127)   sh = F' - sa_out
-// Restates models/slim_yolo_v2.py:220-231 + :33-38 exactly in integers;
-// shift composition as programmed by c_embedding/yolo_forward.c:233-257.
-struct Requant {
-    int shl;
-    int sh;
-    int leaky;
-    int guard_log2;   // guard trips when |t'| >= 2^guard_log2 ( >= 63: never )
-    int wide;         // 1: worst-case |t'| does not fit 30 bits -> 64-bit epilogue kernels
-    // branch-free form of the same pipeline (32-bit path), filled by the host:
-    //   t' = max(t, t << lk)                       lk = leaky ? 3 : 0
-    //   q  = ((t' << sh_l) + hm1 + bfe(t', sh_r, bw)) >> sh_r
-    // with sh_r = max(sh,0), sh_l = max(-sh,0), hm1 = sh>0 ? 2^(sh-1)-1 : 0, bw = sh>0 ? 1 : 0
-    int lk, sh_l, sh_r, hm1, bw;
-    // general LeakyReLU slope neg_mul / 2^lk (1 / 2^3 = the reference's 0.125); only the 64-bit
-    // epilogues (y355_pre) honour neg_mul != 1
-    int neg_mul;
-    // 1: the general slope fits 32 bits (host-checked: |t| * max(2^max(0, lk - sh), neg_mul * 2^max(0, -sh)) < 2^31):
-    //   q = t >= 0 ? rne(t * 2^(lk - sh)) : rne(t * neg_mul * 2^-sh)          (y355_requant_gen32; first layer of y355_net)
-    int gen32;
-    // |t| = |(acc << shl) + bias_t| < 2^tmax_log2 for worst-case operands (<= 24: t is exact in fp32, y355_fp32_exact)
-    int tmax_log2;
-    // gen32 only: 1 = the negative branch's product t * neg_mul does not fit 32 bits but t does; it is taken in two halves
-    // (y355_requant_gen32): needs sh >= 9 and (|t| / 256 + 1) * neg_mul + 256 < 2^31 (host-checked)
-    int split;
-    // 1: the LeakyReLU's negative branch cannot leave [-127, 127]: |t| * neg_mul * 2^-sh <= 127 for the worst-case |t| of these weights
-    // (host-checked on the exact bound, not on 2^tmax_log2): the hot passes of y355_fp32epi.h's NEGSAFE form (front.hip) then do not track that branch's minimum
-    int negsafe;
-};
-// Host rules of the fp32 epilogue on exact integers (y355_fp32epi.h has their reasons): slope in [0, 1]; t exact; the FOLD class
-inline bool y355_fp32_slope_ok(const Requant &rq) { return rq.neg_mul >= 0 && rq.neg_mul <= (1 << rq.lk); }
-inline bool y355_fp32_exact(const Requant &rq) { return !rq.wide && rq.tmax_log2 <= 24; }
-inline int y355_fp32_fold(const Requant &rq) { return rq.shl != 0 ? 0 : (rq.tmax_log2 <= 22 && rq.sh <= 22 && rq.sh - rq.lk >= -8) ? 2 : 1; }
 
 __device__ __forceinline__ int y355_rne_shift32(int x, int s) {            // s wave-uniform
     if (s <= 0) return x << (-s);
@@ -110,10 +75,6 @@ struct Counters {
 
 // engine.hip, for the other translation units
 int y355_prepare_kernels();                          // one-time kernel attributes of the int8 engine's kernels; a y355 error code
-// the integer epilogue of one stand-alone layer (the operator layer of ops.hip): make_requant, with requantisation to sa_out
-// when have_out, else none (t' is the result)
-int y355_op_requant(int cin, int taps, int sa_in, int e_w, int e_b, int sa_out, bool have_out, int act, const int32_t *q_b, int cout,
-                    int cout_pad, Requant *rq, int *frac_bits, std::vector<int32_t> *bias_t, std::vector<long long> *bias_w);
 int y355_cu_count(void);       // engine.hip: compute units of the current device (cached per device), 256 on an MI355X in SPX mode
 int y355_zero_counters(Counters *c, int n, hipStream_t s);    // engine.hip: a kernel launch, not hipMemsetAsync; returns the launch status (hipError_t)
 
@@ -484,28 +445,7 @@ void y355_launch_absmax_u8(const uint8_t *frames, const int *tab, int B, int sh,
 // the evaluators' `bboxes *= [[w, h, w, h]]` of every image, in place (engine.hip); wh [B][2]
 void y355_launch_scale_boxes(float *boxes, const int32_t *count, const float *wh, int batch, int max_det, hipStream_t s);
 
-// ---- generic chunked conv (convg.hip): bf16 nets and the int8 layers conv3x3.hip cannot hold --
-struct RequantG {
-    int shl;       // t = acc * 2^shl + bias (the kernels read it per output channel: bias_w / shl_w of ConvGParams)
-    int sh;        // q = clamp(RNE(t' * 2^-sh))
-    int lk;        // t' = t >= 0 ? t * 2^lk : t * neg_mul     (LeakyReLU slope neg_mul / 2^lk)
-    int neg_mul;
-    int narrow;    // 1: the whole epilogue fits 32 bits (host-checked bound): the 8-wave kernels take their 32-bit instantiation
-    int split;     // narrow only: Requant::split (the negative branch's product in two halves)
-};
-
-// int8 residual (backbone/darknet.py:36 `x + block(x)`), one rounding after the add (DESIGN.md "int8 DarkNet"):
-//   E = F + lk (exponent of t'), s_r the residual's, G = max(E, s_r)
-//   u = t' * 2^(G - E) + q_r * 2^(G - s_r);  q = clamp(RNE(u * 2^(s_out - G)))
-// 64-bit form: t_sh = G - E, r_sh = G - s_r, sh = G - s_out.  32-bit form (RequantG::narrow), the same rational per branch
-// over a common power of two 2^d: X = t * 2^(lk - sh' + d) + q_r * 2^(s_out - s_r + d) (t >= 0, sh' = E - s_out) or
-// X = t * neg_mul * 2^(d - sh') + q_r * 2^(s_out - s_r + d) (t < 0); q = clamp(RNE(X * 2^-d)) -- host-checked to fit 31 bits
-struct ResQ {
-    int t_sh, r_sh, sh;       // 64-bit form
-    int p_t, p_r, p_d;        // 32-bit form, t >= 0
-    int n_t, n_r, n_d;        // 32-bit form, t < 0
-};
-
+// ---- generic chunked conv (convg.hip): bf16 nets and the int8 layers conv3x3.hip cannot hold (RequantG, ResQ: y355_requant.h) --
 struct ConvGParams {
     const char *in;           // NHWC with halo, in_pb bytes per pixel
     char *out;                // NHWC, out_pb bytes per pixel

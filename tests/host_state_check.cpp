@@ -2,7 +2,9 @@
 // swap and rollback, destroy), csrc/resize.hip (FrameStage: lazy buffers, the cached same-size table), csrc/handle_core.h
 // (HandleCore: a create's allocations and its unwinding; not its stream and events, which need a device), csrc/apeval.hip and
 // csrc/cocoeval.hip (y355_apeval: create-time buffers, the two ground truths, the COCO workspaces, staging, close),
-// csrc/pipeline_slot.h (a pipeline slot's outputs) and the two companion libraries' handles, csrc/loss.hip (y355_loss) and
+// csrc/pipeline_slot.h (a pipeline slot's outputs), csrc/conv_op_state.h (ConvOpMem of the operator layer's y355_conv_op:
+// create-time buffers, the weight swap, the workspaces and the geometry each was last zeroed for, the close) and the two
+// companion libraries' handles, csrc/loss.hip (y355_loss) and
 // csrc/anchors.hip (y355_anchors): the device-free half of each create, its buffers, their unwinding, the close.  Device memory
 // is the host heap here, through
 // a DevMem whose k-th allocation (or whose upload) fails on demand, so the program needs no GPU.  Built with the address and
@@ -11,6 +13,7 @@
 #include "../include/yolo355_anchors.h"
 #include "../include/yolo355_loss.h"
 #include "../yolo-compression-and-deployment-in-fpga_amd/csrc/apeval_shared.h"
+#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/conv_op_state.h"
 #include "../yolo-compression-and-deployment-in-fpga_amd/csrc/handle_core.h"
 #include "../yolo-compression-and-deployment-in-fpga_amd/csrc/pipeline_slot.h"
 
@@ -500,10 +503,167 @@ void check_slot() {
     y355_dev_release_all(o);
     CHECK(live.empty());
 }
+
+// ---- a convolution operator's device memory (conv_op_state.h): create-time buffers, the weight swap, the workspaces and the
+// geometry each was last zeroed for, the close
+std::vector<uintptr_t> snapshot(const ConvOpMem &m) {
+    const void *ptrs[] = {m.w_dev, m.bias_dev, m.bw_dev, m.flag_dev, m.bt_dev, m.ctr_dev, m.in_dev, m.out_dev, m.res_dev};
+    std::vector<uintptr_t> v;
+    for (const void *p : ptrs) v.push_back((uintptr_t)p);
+    for (size_t x : {(size_t)m.w_kid, (size_t)m.w_cout_pad, m.in_cap, m.out_cap, m.res_cap, m.in_geo, m.out_geo, m.res_geo}) v.push_back(x);
+    for (void *p : m.own.allocs) v.push_back((uintptr_t)p);
+    return v;
+}
+// one forward of the 24 -> 40 channel 3x3 operator of tests/ops_parent_cases.py: 64-byte input pixels, the padded width of the
+// tile its map selects
+struct OpStep {
+    int B, H, W, cout_pad;
+    bool res, fp32;
+    size_t geo() const { return ((size_t)B << 40) ^ ((size_t)H << 20) ^ (size_t)W ^ ((size_t)fp32 << 62) ^ ((size_t)1 << 61); }
+    size_t in_bytes() const { return (size_t)B * (H + 2) * (W + 2) * 64; }
+    size_t out_bytes() const { return (size_t)B * (H + 2) * (W + 2) * cout_pad * (fp32 ? 4 : 2); }
+};
+int op_step(ConvOpMem &m, const OpStep &s, ConvOpZero *z) {
+    return y355_convop_workspaces(m, s.geo(), s.in_bytes(), s.out_bytes(), true, s.res ? s.out_bytes() : 0, z);
+}
+void check_conv_op() {
+    ConvOpMem m;
+    m.own.mem = host_mem();
+    // create-time buffers: all or none
+    for (int cout_pad : {0, 48}) {
+        const int n_create = cout_pad ? 3 : 1;
+        for (int k = 0; k < n_create; ++k) {
+            fail_at = k, n_alloc = 0;
+            CHECK(y355_convop_create_i8(m, cout_pad) == Y355_EHIP && live.empty() && m.own.allocs.empty());
+            CHECK(!m.flag_dev && !m.bt_dev && !m.ctr_dev);
+        }
+        fail_at = -1, n_alloc = 0;
+        CHECK(y355_convop_create_i8(m, cout_pad) == 0 && n_alloc == n_create && (int)live.size() == n_create && owns_exactly_live(m.own));
+        CHECK(m.flag_dev && (m.bt_dev != nullptr) == (cout_pad != 0) && (m.ctr_dev != nullptr) == (cout_pad != 0));
+        m.flag_dev[3] = 1u;
+        if (cout_pad) m.bt_dev[cout_pad - 1] = 1, m.ctr_dev->guard = 1;
+        y355_convop_close(m);
+        CHECK(live.empty() && snapshot(m) == snapshot(ConvOpMem{}));
+    }
+    // the weight swap, int8 (room for the 64-bit biases) and bf16 (the fp32 biases): a failure at every allocation and at an
+    // upload leaves the pointers, the key and the memory as they were -- nothing packed at first, then the first tile's
+    const std::vector<char> pk1(100, 1), pk2(300, 2);
+    const std::vector<float> b1(48, 1.f), b2(64, 2.f);
+    for (bool bf16 : {false, true}) {
+        CHECK(y355_convop_create_i8(m, 48) == 0);
+        const struct { int kid, cout_pad; const std::vector<char> *pk; const float *bias; } swaps[] = {{3, 48, &pk1, b1.data()}, {5, 64, &pk2, b2.data()}};
+        for (const auto &sw : swaps) {
+            m.in_geo = m.out_geo = m.res_geo = 7;
+            const std::vector<uintptr_t> before = snapshot(m);
+            const std::set<void *> live_before = live;
+            for (int k = 0; k < 3; ++k) {               // k = 2: the upload
+                fail_at = k < 2 ? k : -1, fail_upload = k == 2, n_alloc = 0;
+                CHECK(y355_convop_swap_weights(m, sw.kid, sw.cout_pad, *sw.pk, bf16 ? sw.bias : nullptr, nullptr) == Y355_EHIP);
+                CHECK(snapshot(m) == before && live == live_before);
+            }
+            fail_at = -1, fail_upload = false, n_alloc = 0;
+            CHECK(y355_convop_swap_weights(m, sw.kid, sw.cout_pad, *sw.pk, bf16 ? sw.bias : nullptr, nullptr) == 0 && n_alloc == 2);
+            CHECK(m.w_kid == sw.kid && m.w_cout_pad == sw.cout_pad && memcmp(m.w_dev, sw.pk->data(), sw.pk->size()) == 0);
+            CHECK(bf16 ? m.bias_dev && !m.bw_dev && m.bias_dev[sw.cout_pad - 1] == sw.bias[0] : m.bw_dev && !m.bias_dev);
+            if (!bf16) m.bw_dev[sw.cout_pad - 1] = 1;
+            CHECK(m.in_geo == 7 && m.out_geo == 0 && m.res_geo == 0);     // the padded width changed: out and res are zeroed again
+            CHECK(live.size() == 5 && owns_exactly_live(m.own));
+        }
+        y355_convop_close(m);
+        CHECK(live.empty());
+    }
+    // the workspaces on one operator object: a map, a smaller map (another tile: a swap in between), the first map again at a
+    // larger batch, with and without a residual, bf16 and fp32 output.  `zeroed` is this check's own record of the geometry
+    // each buffer was last reported for; what a step has to report follows from it and from the sizes alone.
+    const OpStep steps[] = {{2, 14, 27, 64, true, false},  {1, 9, 11, 48, false, false}, {1, 9, 11, 48, true, false}, {3, 14, 27, 64, false, false},
+                            {3, 14, 27, 64, true, false},  {3, 14, 27, 64, false, true}, {1, 9, 11, 48, false, true}, {1, 9, 11, 48, false, false},
+                            {2, 14, 27, 64, false, false}, {2, 14, 27, 64, true, false}, {2, 14, 27, 64, true, false}};
+    size_t zeroed[3] = {0, 0, 0}, cap[3] = {0, 0, 0};
+    for (const OpStep &s : steps) {
+        if (m.w_cout_pad != s.cout_pad) {
+            CHECK(y355_convop_swap_weights(m, s.cout_pad, s.cout_pad, pk1, b2.data(), nullptr) == 0);
+            zeroed[1] = zeroed[2] = 0;
+        }
+        const size_t need[3] = {s.in_bytes(), s.out_bytes(), s.res ? s.out_bytes() : 0};
+        bool want[3];
+        for (int i = 0; i < 3; ++i) {
+            if (need[i] > cap[i]) cap[i] = need[i], zeroed[i] = 0;      // new memory
+            want[i] = need[i] && zeroed[i] != s.geo();
+        }
+        // the step with its k-th allocation failing, k = 0, 1, ...: the first k it does not reach is the step itself, and
+        // reports what it would have reported without the failures before it
+        ConvOpZero z;
+        bool done = false;
+        for (int k = 0; k <= 3 && !done; ++k) {
+            const size_t geos[3] = {m.in_geo, m.out_geo, m.res_geo};
+            const char *ptrs[3] = {m.in_dev, m.out_dev, m.res_dev};
+            fail_at = k, n_alloc = 0;
+            done = op_step(m, s, &z) == 0;
+            CHECK(owns_exactly_live(m.own) && (done ? n_alloc <= k : g_err == "injected allocation failure"));
+            CHECK(!m.in_dev == (m.in_cap == 0) && !m.out_dev == (m.out_cap == 0) && !m.res_dev == (m.res_cap == 0));
+            // a recorded geometry changes in one way before the zeroing is enqueued: to "none", with the memory
+            CHECK((m.in_geo == geos[0] && m.in_dev == ptrs[0]) || m.in_geo == 0);
+            CHECK((m.out_geo == geos[1] && m.out_dev == ptrs[1]) || m.out_geo == 0);
+            CHECK((m.res_geo == geos[2] && m.res_dev == ptrs[2]) || m.res_geo == 0);
+        }
+        fail_at = -1;
+        CHECK(done && z.in == want[0] && z.out == want[1] && z.res == want[2]);
+        CHECK(m.in_cap >= need[0] && m.out_cap >= need[1] && m.res_cap >= need[2]);
+        m.in_dev[need[0] - 1] = 1, m.out_dev[need[1] - 1] = 1;        // (the sanitizer sees a buffer that is too short)
+        if (s.res) m.res_dev[need[2] - 1] = 1;
+        y355_convop_zeroed(m, s.geo(), z);
+        for (int i = 0; i < 3; ++i)
+            if (want[i]) zeroed[i] = s.geo();
+        CHECK(m.in_geo == s.geo() && m.out_geo == s.geo() && (!s.res || m.res_geo == s.geo()));
+        CHECK(op_step(m, s, &z) == 0 && !z.in && !z.out && !z.res);     // the same call again: nothing to zero
+    }
+    y355_convop_close(m);
+    CHECK(live.empty());
+    // in fits, out must grow and fails; then the same call again: in was not zeroed for the new geometry, and is reported
+    {
+        const OpStep a{1, 9, 11, 48, false, false}, b{1, 7, 9, 192, false, false};
+        ConvOpZero z;
+        CHECK(b.in_bytes() < a.in_bytes() && b.out_bytes() > a.out_bytes());
+        CHECK(op_step(m, a, &z) == 0 && z.in && z.out && !z.res);
+        y355_convop_zeroed(m, a.geo(), z);
+        const char *in_a = m.in_dev;
+        fail_at = 0, n_alloc = 0;
+        CHECK(op_step(m, b, &z) == Y355_EHIP && n_alloc == 1 && m.in_dev == in_a && m.in_geo == a.geo() && !m.out_dev && m.out_geo == 0);
+        fail_at = -1;
+        CHECK(op_step(m, b, &z) == 0 && z.in && z.out && !z.res && m.in_dev == in_a && m.in_geo == a.geo());
+        y355_convop_zeroed(m, b.geo(), z);
+        CHECK(m.in_geo == b.geo() && m.out_geo == b.geo() && m.res_geo == 0);
+        y355_convop_close(m);
+    }
+    // g1 with a residual, g2 without, g2 with: res is still in g1's layout, and is the one buffer reported
+    {
+        const OpStep g1r{2, 14, 27, 64, true, false}, g2{1, 9, 11, 64, false, false}, g2r{1, 9, 11, 64, true, false};
+        ConvOpZero z;
+        CHECK(op_step(m, g1r, &z) == 0 && z.in && z.out && z.res);
+        y355_convop_zeroed(m, g1r.geo(), z);
+        CHECK(op_step(m, g2, &z) == 0 && z.in && z.out && !z.res);
+        y355_convop_zeroed(m, g2.geo(), z);
+        CHECK(m.res_geo == g1r.geo());
+        n_alloc = 0;
+        CHECK(op_step(m, g2r, &z) == 0 && !z.in && !z.out && z.res && n_alloc == 0);
+        y355_convop_zeroed(m, g2r.geo(), z);
+        CHECK(m.res_geo == g2.geo() && live.size() == 3 && owns_exactly_live(m.own));
+    }
+    // an operator whose output has no halo to keep (int8 results, the general geometry): out is never reported
+    {
+        ConvOpZero z;
+        CHECK(y355_convop_workspaces(m, 5, 10, 10, false, 0, &z) == 0 && z.in && !z.out && !z.res);
+    }
+    y355_convop_close(m);
+    CHECK(live.empty() && m.own.allocs.empty() && snapshot(m) == snapshot(ConvOpMem{}));
+    y355_convop_close(m);                           // a second close does nothing
+    CHECK(live.empty());
+}
 }  // namespace
 
 int main() {
     check_owner();
+    check_conv_op();
     check_apeval_buffers(8);
     check_apeval_buffers(5000);                     // five tiles of the sort's histogram
     check_apeval_gt();

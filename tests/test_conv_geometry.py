@@ -331,6 +331,28 @@ def test_general_kernel_equals_the_existing_kernels(case):
         assert np.array_equal(E.conv2d_geom_bf16(x, w, g, b, neg_slope=slope, out_fp32=fp32), want), (case[0], slope, fp32)
 
 
+@pytest.mark.gpu
+def test_one_operator_keeps_each_workspace_zeroed_for_its_own_geometry():
+    """one bf16 operator object, 24 -> 40 channels, 3x3, stride 1: a map with a residual, a smaller map (another tile) without one,
+    the smaller map with one -- the residual's workspace was last zeroed for the first map's layout.  Each output is bit-equal to
+    conv2d_bf16, which runs a fresh operator, on the same data"""
+    from yolo355 import engine as E
+    from yolo355.synth import uniform_pm1
+    cin, cout = 24, 40
+    w = (uniform_pm1(41, (cout, cin, 3, 3)) * np.float32(1.0 / np.sqrt(cin * 9))).astype(np.float32)
+    b = uniform_pm1(42, (cout,))
+    op = E.ConvOp.bf16(w, b, neg_slope=0.1)
+    try:
+        for i, (shp, with_res) in enumerate((((2, cin, 14, 27), True), ((1, cin, 9, 11), False), ((1, cin, 9, 11), True))):
+            x = uniform_pm1(50 + 2 * i, shp)
+            res = uniform_pm1(51 + 2 * i, (shp[0], cout) + shp[2:]) if with_res else None
+            rd = None if res is None else torch.from_numpy(res).cuda()
+            got = op.forward(torch.from_numpy(x).cuda(), residual=rd).cpu().numpy()
+            assert np.array_equal(got, E.conv2d_bf16(x, w, b, residual=res, neg_slope=0.1)), (i, shp, with_res)
+    finally:
+        op.close()
+
+
 # ---- GPU: device-resident forms ------------------------------------------------------------------------------------------
 @pytest.mark.gpu
 def test_device_resident_forms():

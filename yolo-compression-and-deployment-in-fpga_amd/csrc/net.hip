@@ -1252,10 +1252,15 @@ extern "C" int y355_head_f32_ex(int device_id, int nlev, const float *const *pre
     HIPCHK(hipSetDevice(device_id));
     if (int e = y355_prepare_kernels()) return e;
     const int B = batch, cpad = y355_pred_channels(predc);
-    HeadState st;
-    int rc = y355_head_create(st, N, B, max_det, max_candidates, route, cand_box != nullptr, true, y355_hip_mem());
+    struct HeadScope {                              // the head's memory and the prediction maps go back whichever way this returns
+        HeadState st;
+        ~HeadScope() { y355_head_destroy(st); }
+    } head;
+    HeadState &st = head.st;
+    DevScope tmp;
+    if (int rc = y355_head_create(st, N, B, max_det, max_candidates, route, cand_box != nullptr, true, y355_hip_mem())) return rc;
     float *d_pred[3] = {nullptr, nullptr, nullptr};
-    for (int l = 0; l < nlev && !rc; ++l) {
+    for (int l = 0; l < nlev; ++l) {
         // NCHW -> NHWC with cpad channels
         const size_t px = (size_t)hs[l] * ws[l];
         std::vector<float> t((size_t)B * px * cpad, 0.f);
@@ -1264,14 +1269,9 @@ extern "C" int y355_head_f32_ex(int device_id, int nlev, const float *const *pre
                 const float *src = pred[l] + ((size_t)b * predc + c) * px;
                 for (size_t i = 0; i < px; ++i) t[((size_t)b * px + i) * cpad + c] = src[i];
             }
-        if (hipMalloc((void **)&d_pred[l], t.size() * 4 + 1024) != hipSuccess) rc = 1;
-        if (!rc && hipMemcpy(d_pred[l], t.data(), t.size() * 4, hipMemcpyHostToDevice) != hipSuccess) rc = 1;
+        if (int rc = y355_dev_get(tmp, &d_pred[l], t.size() + 256)) return rc;       // 1024 bytes of slack behind each map
+        HIPCHK(hipMemcpy(d_pred[l], t.data(), t.size() * 4, hipMemcpyHostToDevice));
     }
-    auto release = [&]() {
-        for (float *q : d_pred) (void)hipFree(q);
-        y355_head_destroy(st);
-    };
-    if (rc) { release(); return y355_fail(Y355_EHIP, "device allocation failed"); }
     HeadParams p{};
     p.nlev = nlev;
     for (int l = 0; l < nlev; ++l) {
@@ -1301,7 +1301,6 @@ extern "C" int y355_head_f32_ex(int device_id, int nlev, const float *const *pre
     if (e == hipSuccess && cand_box) e = y355_head_get_candidates(st, 0, B, cand_box, cand_score, cand_cls);
     int overflow = 0;
     if (e == hipSuccess) e = y355_head_overflow_read(st, 0, &overflow);
-    release();
     if (overflow) return y355_fail(Y355_EINVAL, y355_head_overflow_message(max_candidates));
     if (e != hipSuccess) return y355_fail(Y355_EHIP, std::string("head: ") + hipGetErrorString(e));
     return 0;

@@ -17,9 +17,11 @@
 //       y355_conv2d_geom_bf16 through conv_forward_bf16; y355_conv3x3_i8_raw and y355_conv_geom_i8_raw, whose input is int8
 //       at a GIVEN exponent, enter below the exponent detection, at i8_prepare / i8_launch.  y355_conv3x3_i8_fused (the
 //       requantising layer with its statistics pass) shares the kernel ladder, the parameter fill and the host layout helpers.
-// Errors: HIPTRY returns Y355_EHIP with the failing call; temporary device memory belongs to a Scratch and a temporary
-// operator to an OpOwner, so no return path frees by hand.  Argument checks come before the first HIP call.
+// Errors: HIPCHK returns Y355_EHIP with the failing call.  Device memory has one mechanism, the library's (y355_host.h): an
+// operator's belongs to its ConvOpMem (conv_op_state.h, run on the CPU by `make hostcheck`), a call's to a DevScope and a
+// temporary operator to an OpOwner, so no return path frees by hand.  Argument checks come before the first HIP call.
 #include "../../include/yolo355.h"
+#include "conv_op_state.h"
 #include "y355_common.h"
 #include "y355_requant.h"       // y355_rq_layer: the integer epilogue of a stand-alone layer
 
@@ -29,24 +31,7 @@
 #include <string>
 #include <vector>
 
-#define HIPTRY(expr)                                                                                            \
-    do {                                                                                                        \
-        hipError_t e_ = (expr);                                                                                 \
-        if (e_ != hipSuccess) return y355_fail(Y355_EHIP, std::string(#expr) + ": " + hipGetErrorString(e_));   \
-    } while (0)
-
 namespace {
-// temporary device memory of one call: freed when the call returns, whichever way
-struct Scratch {
-    std::vector<void *> bufs;
-    ~Scratch() { for (void *p : bufs) (void)hipFree(p); }
-    template <class T> hipError_t get(T **p, size_t bytes) {
-        const hipError_t e = hipMalloc((void **)p, bytes);
-        if (e == hipSuccess) bufs.push_back(*p);
-        return e;
-    }
-};
-
 inline int grid_for(size_t n) { return (int)std::min<size_t>((n + 255) / 256, 16384); }
 inline int round_up(int v, int m) { return (v + m - 1) / m * m; }
 
@@ -226,15 +211,15 @@ template <class S, class D> void nhwc_to_nchw(const S *o, D *out, int batch, int
 
 // host-pointer form of an element-wise fp32 operator: upload, the *_dev form on the null stream, synchronise, download
 template <class F> int host_form(int device_id, const float *x, size_t n_in, float *out, size_t n_out, F dev_form) {
-    Scratch tmp;
+    DevScope tmp;
     float *d_in = nullptr, *d_out = nullptr;
-    HIPTRY(hipSetDevice(device_id));
-    HIPTRY(tmp.get(&d_in, n_in * 4));
-    HIPTRY(tmp.get(&d_out, n_out * 4));
-    HIPTRY(hipMemcpy(d_in, x, n_in * 4, hipMemcpyHostToDevice));
+    HIPCHK(hipSetDevice(device_id));
+    if (int rc = y355_dev_get(tmp, &d_in, n_in)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_out, n_out)) return rc;
+    HIPCHK(hipMemcpy(d_in, x, n_in * 4, hipMemcpyHostToDevice));
     if (int rc = dev_form(d_in, d_out)) return rc;
-    HIPTRY(hipDeviceSynchronize());
-    HIPTRY(hipMemcpy(out, d_out, n_out * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, d_out, n_out * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -263,23 +248,23 @@ extern "C" int y355_quantize_input_f32_i8(int device_id, const float *x, size_t 
     if (!x || !q) return y355_fail(Y355_EINVAL, "null argument");
     if (n == 0) return y355_fail(Y355_EINVAL, "empty tensor");
     if (sa < -64 || sa > 64) return y355_fail(Y355_EINVAL, "activation exponent out of range");
-    Scratch tmp;
+    DevScope tmp;
     float *d_in = nullptr;
     int8_t *d_out = nullptr;
     unsigned long long *d_cnt = nullptr;
-    HIPTRY(hipSetDevice(device_id));
-    HIPTRY(tmp.get(&d_in, n * sizeof(float)));
-    HIPTRY(tmp.get(&d_out, n));
-    HIPTRY(tmp.get(&d_cnt, 8));
-    HIPTRY(hipMemcpy(d_in, x, n * sizeof(float), hipMemcpyHostToDevice));
-    HIPTRY(hipMemset(d_cnt, 0, 8));
+    HIPCHK(hipSetDevice(device_id));
+    if (int rc = y355_dev_get(tmp, &d_in, n)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_out, n)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_cnt, 1)) return rc;
+    HIPCHK(hipMemcpy(d_in, x, n * sizeof(float), hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_cnt, 0, 8));
     const int blocks = (int)std::min<size_t>((n + 255) / 256, 8192);
     hipLaunchKernelGGL(quantize_f32_i8_kernel, dim3(blocks), dim3(256), 0, 0, d_in, d_out, n, std::ldexp(1.0f, sa), d_cnt);
-    HIPTRY(hipGetLastError());
-    HIPTRY(hipDeviceSynchronize());
-    HIPTRY(hipMemcpy(q, d_out, n, hipMemcpyDeviceToHost));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(q, d_out, n, hipMemcpyDeviceToHost));
     unsigned long long c = 0;
-    HIPTRY(hipMemcpy(&c, d_cnt, 8, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(&c, d_cnt, 8, hipMemcpyDeviceToHost));
     if (clamped) *clamped = (int64_t)c;
     return 0;
 }
@@ -289,17 +274,17 @@ extern "C" int y355_maxpool2x2_i8(int device_id, const int8_t *in, int batch, in
     size_t nin = 0;
     if (int rc = pool_shape(batch, channels, height, width, &nin)) return rc;
     const size_t nout = nin / 4;
-    Scratch tmp;
+    DevScope tmp;
     int8_t *d_in = nullptr, *d_out = nullptr;
-    HIPTRY(hipSetDevice(device_id));
-    HIPTRY(tmp.get(&d_in, nin));
-    HIPTRY(tmp.get(&d_out, nout));
-    HIPTRY(hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice));
+    HIPCHK(hipSetDevice(device_id));
+    if (int rc = y355_dev_get(tmp, &d_in, nin)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_out, nout)) return rc;
+    HIPCHK(hipMemcpy(d_in, in, nin, hipMemcpyHostToDevice));
     const int blocks = (int)std::min<size_t>((nout + 255) / 256, 8192);
     hipLaunchKernelGGL(maxpool2x2_i8_kernel, dim3(blocks), dim3(256), 0, 0, d_in, d_out, (size_t)batch * channels, height, width);
-    HIPTRY(hipGetLastError());
-    HIPTRY(hipDeviceSynchronize());
-    HIPTRY(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost));
+    HIPCHK(hipGetLastError());
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, d_out, nout, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -308,7 +293,7 @@ extern "C" int y355_reorg_f32_dev(const float *x_dev, int batch, int channels, i
     size_t n = 0;
     if (int rc = reorg_shape(batch, channels, height, width, stride, &n)) return rc;
     hipLaunchKernelGGL(reorg_f32_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x_dev, out_dev, batch, channels, height, width, stride);
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 extern "C" int y355_spp_f32_dev(const float *x_dev, int batch, int channels, int height, int width, float *out_dev, void *stream) {
@@ -316,7 +301,7 @@ extern "C" int y355_spp_f32_dev(const float *x_dev, int batch, int channels, int
     size_t n = 0;
     if (int rc = map_shape(batch, channels, height, width, 1, &n)) return rc;
     hipLaunchKernelGGL(spp_f32_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, x_dev, out_dev, (size_t)batch, channels, height, width);
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 extern "C" int y355_maxpool2x2_f32_dev(const float *in_dev, int batch, int channels, int height, int width, float *out_dev, void *stream) {
@@ -325,7 +310,7 @@ extern "C" int y355_maxpool2x2_f32_dev(const float *in_dev, int batch, int chann
     if (int rc = pool_shape(batch, channels, height, width, &n)) return rc;
     hipLaunchKernelGGL(maxpool2x2_f32_kernel, dim3(grid_for(n / 4)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, (size_t)batch * channels,
                        height, width);
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 extern "C" int y355_upsample2x_f32_dev(const float *in_dev, int batch, int channels, int height, int width, float *out_dev, void *stream) {
@@ -334,7 +319,7 @@ extern "C" int y355_upsample2x_f32_dev(const float *in_dev, int batch, int chann
     if (int rc = map_shape(batch, channels, height, width, 1, &n)) return rc;
     hipLaunchKernelGGL(upsample2x_f32_kernel, dim3(grid_for(n * 4)), dim3(256), 0, (hipStream_t)stream, in_dev, out_dev, (size_t)batch * channels,
                        height, width);
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -381,28 +366,19 @@ struct y355_conv_op {
     int geom = 0;                      // 1: general geometry g on convgeom.hip; 0: ksize / stride on convg.hip (bf16), 3x3 on conv3x3.hip (int8)
     y355_conv_geom g{};
     int cpad = 0;                      // channels of a staged input pixel (bf16 or int8 elements)
-    // packed weights, for the kernel id and padded width the last shapes selected (op_weights); -1: nothing packed
-    char *w_dev = nullptr;
-    int w_kid = -1, w_cout_pad = 0;
+    // the device memory: the packed weights for the kernel id and padded width the last shapes selected (op_weights), the
+    // int8 operator's create-time buffers, the workspaces
+    ConvOpMem m;
     // bf16
     float slope = 1.f;
     std::vector<float> w_host, b_host;
-    float *bias_dev = nullptr;
     // int8
     std::vector<int8_t> qw;
     std::vector<int32_t> qb;
     int e_w = 0, e_b = 0, act = 0;
-    int *bt_dev = nullptr;             // 3x3 only: the 32-bit biases
-    long long *bw_dev = nullptr;
     int sa_cached = NO_SA;             // the input exponent rq / frac_bits / the device biases were made for
     Requant rq{};
     int frac_bits = 0;
-    Counters *ctr_dev = nullptr;       // 3x3 only
-    unsigned int *flag_dev = nullptr;  // [0] absmax bits, [1] non-dyadic count
-    // workspaces (grown on demand)
-    char *in_dev = nullptr, *out_dev = nullptr, *res_dev = nullptr;
-    size_t in_cap = 0, out_cap = 0, res_cap = 0;
-    size_t geo = 0;                    // (batch, H, W, output type) the halo buffers were last zeroed for
     static constexpr int NO_SA = 1 << 30;
 };
 
@@ -485,14 +461,19 @@ ConvParams gen16_params(const ConvKernelInfo &ki, const int8_t *in, const int8_t
     return p;
 }
 
-int op_grow(char **p, size_t *cap, size_t need, bool zero) {
-    if (*cap >= need) return 0;
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    HIPTRY(hipMalloc((void **)p, need));
-    if (zero) HIPTRY(hipMemset(*p, 0, need));
-    *cap = need;
+// (batch, H, W, output type) as one word, never 0: what a workspace's halo and padding channels were last zeroed for
+size_t geo_word(int batch, int height, int width, int out_fp32) {
+    return ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)out_fp32 << 62) ^ ((size_t)1 << 61);
+}
+// The workspaces of a forward at that geometry, grown and zeroed on s where they were last zeroed for another one; a failure
+// leaves the recorded geometries alone, so the next forward zeroes again.  res_bytes 0: no residual.
+int op_workspaces(y355_conv_op *op, size_t geo, size_t in_bytes, size_t out_bytes, bool out_halo, size_t res_bytes, hipStream_t s) {
+    ConvOpZero z;
+    if (int rc = y355_convop_workspaces(op->m, geo, in_bytes, out_bytes, out_halo, res_bytes, &z)) return rc;
+    if (z.in) HIPCHK(hipMemsetAsync(op->m.in_dev, 0, in_bytes, s));
+    if (z.out) HIPCHK(hipMemsetAsync(op->m.out_dev, 0, out_bytes, s));
+    if (z.res) HIPCHK(hipMemsetAsync(op->m.res_dev, 0, res_bytes, s));
+    y355_convop_zeroed(op->m, geo, z);
     return 0;
 }
 
@@ -532,7 +513,7 @@ int conv_plan(const y355_conv_op *op, int batch, int height, int width, ConvPlan
 // The packed weights for kernel pl.kid at pl.cout_pad output channels, with the bias vector that is padded alike: packed from
 // the host copy on first use, and again when a map size selects another tile shape.
 int op_weights(y355_conv_op *op, const ConvPlan &pl, hipStream_t s) {
-    if (op->w_kid == pl.kid && op->w_cout_pad == pl.cout_pad) return 0;
+    if (op->m.w_kid == pl.kid && op->m.w_cout_pad == pl.cout_pad) return 0;
     const int taps = op->geom ? op->g.kh * op->g.kw : op->ksize * op->ksize, in_pb = op->kind ? op->cpad : op->cpad * 2;
     const float *wf = op->kind ? nullptr : op->w_host.data();
     const int8_t *wq = op->kind ? op->qw.data() : nullptr;
@@ -548,28 +529,14 @@ int op_weights(y355_conv_op *op, const ConvPlan &pl, hipStream_t s) {
         wpk.resize(y355_packed_bytes(ki, pl.cout_pad));
         y355_pack_weights(ki, wq, op->cout, op->cin, pl.cout_pad, (int8_t *)wpk.data());
     }
-    HIPTRY(hipStreamSynchronize(s));                               // a previous forward may still read the old fragments
-    // nothing is packed from here until everything below has succeeded: a failure must not leave the key of a tile whose
-    // fragments are gone, or a later forward at that tile's size would launch on a null pointer
-    op->w_kid = -1;
-    op->sa_cached = y355_conv_op::NO_SA;                           // the int8 biases are padded to the new width by i8_prepare
-    (void)hipFree(op->w_dev);
-    (void)hipFree(op->bias_dev);
-    (void)hipFree(op->bw_dev);
-    op->w_dev = nullptr; op->bias_dev = nullptr; op->bw_dev = nullptr;
-    HIPTRY(hipMalloc((void **)&op->w_dev, wpk.size()));
-    HIPTRY(hipMemcpy(op->w_dev, wpk.data(), wpk.size(), hipMemcpyHostToDevice));
+    std::vector<float> bpad;
     if (op->kind == 0) {
-        std::vector<float> bpad(pl.cout_pad, 0.f);
+        bpad.assign(pl.cout_pad, 0.f);
         std::copy(op->b_host.begin(), op->b_host.end(), bpad.begin());
-        HIPTRY(hipMalloc((void **)&op->bias_dev, sizeof(float) * pl.cout_pad));
-        HIPTRY(hipMemcpy(op->bias_dev, bpad.data(), sizeof(float) * pl.cout_pad, hipMemcpyHostToDevice));
-        op->geo = 0;                                               // halo layouts depend on the padded channel counts: re-zero
-    } else {
-        HIPTRY(hipMalloc((void **)&op->bw_dev, sizeof(long long) * pl.cout_pad));
     }
-    op->w_kid = pl.kid;
-    op->w_cout_pad = pl.cout_pad;
+    HIPCHK(hipStreamSynchronize(s));                               // a previous forward may still read the old fragments
+    if (int rc = y355_convop_swap_weights(op->m, pl.kid, pl.cout_pad, wpk, op->kind ? nullptr : bpad.data(), s)) return rc;
+    op->sa_cached = y355_conv_op::NO_SA;                           // the int8 biases are padded to the new width by i8_prepare
     return 0;
 }
 
@@ -578,6 +545,7 @@ int attr_fail(int e) { return y355_fail(Y355_EHIP, std::string("kernel attribute
 y355_conv_op *op_new(int device_id, int kind, int cin, int cout, const y355_conv_geom *g) {
     y355_conv_op *op = new y355_conv_op();
     op->device = device_id; op->kind = kind; op->cin = cin; op->cout = cout;
+    op->m.own.mem = y355_hip_mem();
     if (g) {
         op->geom = 1;
         op->g = *g;
@@ -590,9 +558,7 @@ extern "C" void y355_conv_op_destroy(y355_conv_op *op) {
     if (!op) return;
     (void)hipSetDevice(op->device);
     (void)hipDeviceSynchronize();
-    for (void *q : {(void *)op->w_dev, (void *)op->bias_dev, (void *)op->bt_dev, (void *)op->bw_dev, (void *)op->ctr_dev, (void *)op->flag_dev,
-                    (void *)op->in_dev, (void *)op->out_dev, (void *)op->res_dev})
-        if (q) (void)hipFree(q);
+    y355_convop_close(op->m);
     delete op;
 }
 
@@ -604,7 +570,7 @@ extern "C" int y355_conv_geom_out_size(const y355_conv_geom *g, int height, int 
 // ---- create ----------------------------------------------------------------------------------------------------------------
 static int create_bf16(int device_id, const float *w, const float *bias, int cin, int cout, int ksize, int stride, const y355_conv_geom *g,
                        float neg_slope, y355_conv_op **out) {
-    HIPTRY(hipSetDevice(device_id));
+    HIPCHK(hipSetDevice(device_id));
     if (int e = g ? y355_prepare_convgeom() : y355_prepare_convg()) return attr_fail(e);
     y355_conv_op *op = op_new(device_id, 0, cin, cout, g);
     op->ksize = ksize; op->stride = stride; op->slope = neg_slope;
@@ -637,7 +603,7 @@ extern "C" int y355_conv_op_create_bf16_geom(int device_id, const float *w, cons
 // 3x3: the kernel depends on cin alone, so the weights are packed here and every forward finds them
 static int create_i8(int device_id, const int8_t *q_w, const int32_t *q_b, int cin, int cout, const y355_conv_geom *g, int e_w, int e_b, int flags,
                      y355_conv_op **out) {
-    HIPTRY(hipSetDevice(device_id));
+    HIPCHK(hipSetDevice(device_id));
     if (g) {
         if (int e = y355_prepare_convgeom()) return attr_fail(e);
     } else if (int e = y355_prepare_kernels()) {
@@ -649,16 +615,15 @@ static int create_i8(int device_id, const int8_t *q_w, const int32_t *q_b, int c
     op->act = geom_act(flags);
     op->qw.assign(q_w, q_w + (size_t)cout * cin * (g ? g->kh * g->kw : 9));
     op->qb.assign(q_b, q_b + cout);
-    HIPTRY(hipMalloc((void **)&op->flag_dev, 16));
     if (g) {
         op->cpad = round_up(cin, 64);
+        if (int rc = y355_convop_create_i8(op->m, 0)) return rc;
     } else {
         ConvPlan pl;
         (void)gen16_kernel(cin, 0, &op->cpad);
         if (int rc = conv_plan(op, 1, 1, 1, &pl)) return rc;
+        if (int rc = y355_convop_create_i8(op->m, pl.cout_pad)) return rc;
         if (int rc = op_weights(op, pl, nullptr)) return rc;
-        HIPTRY(hipMalloc((void **)&op->bt_dev, sizeof(int) * pl.cout_pad));
-        HIPTRY(hipMalloc((void **)&op->ctr_dev, sizeof(Counters)));
     }
     *out = op;
     own.op = nullptr;
@@ -688,43 +653,34 @@ static int conv_forward_bf16(y355_conv_op *op, const float *x_dev, const float *
     if (out_fp32 && residual_dev) return y355_fail(Y355_EINVAL, "fp32 output (prediction layers) takes no residual");
     ConvPlan pl;
     if (int rc = conv_out_size(op, batch, height, width, &pl)) return rc;
-    HIPTRY(hipSetDevice(op->device));
+    HIPCHK(hipSetDevice(op->device));
     if (int rc = conv_plan(op, batch, height, width, &pl)) return rc;
     if (int rc = op_weights(op, pl, s)) return rc;
     const int Ho = pl.Ho, Wo = pl.Wo, cout_pad = pl.cout_pad, in_pb = op->cpad * 2;
     const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * Ho * Wo;
     const size_t in_bytes = (size_t)batch * (height + 2) * (width + 2) * in_pb;
     const size_t out_pb = (size_t)cout_pad * (out_fp32 ? 4 : 2), out_bytes = (size_t)batch * (Ho + 2) * (Wo + 2) * out_pb;
-    // a buffer is zeroed when it is (re)allocated: the staging kernels only write the interior and the real channels, so the
-    // halo and the padding channels stay zero for every later call of the same or a smaller size... as long as the geometry is
-    // the same: a new geometry re-zeroes (cheap next to a reallocation)
-    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)out_fp32 << 62) ^ ((size_t)1 << 61);
-    const bool regeo = geo != op->geo;
-    op->geo = geo;
-    if (int rc = op_grow(&op->in_dev, &op->in_cap, in_bytes, true)) return rc;
-    if (int rc = op_grow(&op->out_dev, &op->out_cap, out_bytes, true)) return rc;
-    if (regeo) {
-        HIPTRY(hipMemsetAsync(op->in_dev, 0, in_bytes, s));
-        if (!op->geom) HIPTRY(hipMemsetAsync(op->out_dev, 0, out_bytes, s));   // convgeom.hip writes every channel of a pixel it owns
-    }
+    // the staging kernels only write the interior and the real channels, so the halo and the padding channels stay zero for
+    // every later call of the same geometry; a new geometry re-zeroes (cheap next to a reallocation).  convgeom.hip writes
+    // every channel of a pixel it owns, so its output is not kept zero
+    if (int rc = op_workspaces(op, geo_word(batch, height, width, out_fp32), in_bytes, out_bytes, !op->geom, residual_dev ? out_bytes : 0, s))
+        return rc;
     if (residual_dev) {
-        if (int rc = op_grow(&op->res_dev, &op->res_cap, out_bytes, true)) return rc;
-        if (regeo) HIPTRY(hipMemsetAsync(op->res_dev, 0, out_bytes, s));
-        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, residual_dev, (unsigned short *)op->res_dev, batch,
+        hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, residual_dev, (unsigned short *)op->m.res_dev, batch,
                            op->cout, Ho, Wo, cout_pad);
     }
-    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (unsigned short *)op->in_dev, batch, op->cin, height,
+    hipLaunchKernelGGL(nchw_to_nhwc_bf16_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (unsigned short *)op->m.in_dev, batch, op->cin, height,
                        width, op->cpad);
-    const char *res = residual_dev ? op->res_dev : nullptr;
+    const char *res = residual_dev ? op->m.res_dev : nullptr;
     if (op->geom) {
         ConvGeomParams p = geom_params(op->g, batch, height, width, Ho, Wo, in_pb, cout_pad, y355_convgeom_info(pl.kid)->bn);
-        p.in = op->in_dev; p.w = op->w_dev; p.bias_f = op->bias_dev; p.res = res; p.out = op->out_dev;
+        p.in = op->m.in_dev; p.w = op->m.w_dev; p.bias_f = op->m.bias_dev; p.res = res; p.out = op->m.out_dev;
         p.out_pb = (int)out_pb; p.out_f32 = out_fp32 ? 1 : 0; p.slope = op->slope;
         y355_launch_convgeom(pl.kid, 1, p, s);
     } else {
         const ConvGInfo &ki = *pl.kg;
         ConvGParams p{};
-        p.in = op->in_dev; p.out = op->out_dev; p.w = op->w_dev; p.bias_f = op->bias_dev;
+        p.in = op->m.in_dev; p.out = op->m.out_dev; p.w = op->m.w_dev; p.bias_f = op->m.bias_dev;
         p.B = batch; p.H = height; p.W = width;
         p.in_pb = in_pb; p.nchunks = in_pb / ki.chb;
         p.out_pb = (int)out_pb; p.out_off = 0; p.out_halo = 1;
@@ -735,14 +691,14 @@ static int conv_forward_bf16(y355_conv_op *op, const float *x_dev, const float *
         p.res = res; p.res_pb = (int)out_pb; p.res_off = 0;
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, s);
     }
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     if (out_fp32)
-        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const float *)op->out_dev, out_dev, batch, op->cout, Ho,
+        hipLaunchKernelGGL(nhwc_f32_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const float *)op->m.out_dev, out_dev, batch, op->cout, Ho,
                            Wo, cout_pad);
     else
-        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const unsigned short *)op->out_dev, out_dev, batch,
+        hipLaunchKernelGGL(nhwc_bf16_to_nchw_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const unsigned short *)op->m.out_dev, out_dev, batch,
                            op->cout, Ho, Wo, cout_pad);
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -760,18 +716,18 @@ static int bf16_host_form(y355_conv_op *op_, const float *x, const float *residu
     ConvPlan pl;
     if (int rc = conv_out_size(own.op, batch, height, width, &pl)) return rc;
     const size_t n_in = (size_t)batch * own.op->cin * height * width, n_out = (size_t)batch * own.op->cout * pl.Ho * pl.Wo;
-    Scratch tmp;
+    DevScope tmp;
     float *d_x = nullptr, *d_r = nullptr, *d_y = nullptr;
-    HIPTRY(tmp.get(&d_x, n_in * 4));
-    HIPTRY(tmp.get(&d_y, n_out * 4));
-    HIPTRY(hipMemcpy(d_x, x, n_in * 4, hipMemcpyHostToDevice));
+    if (int rc = y355_dev_get(tmp, &d_x, n_in)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_y, n_out)) return rc;
+    HIPCHK(hipMemcpy(d_x, x, n_in * 4, hipMemcpyHostToDevice));
     if (residual) {
-        HIPTRY(tmp.get(&d_r, n_out * 4));
-        HIPTRY(hipMemcpy(d_r, residual, n_out * 4, hipMemcpyHostToDevice));
+        if (int rc = y355_dev_get(tmp, &d_r, n_out)) return rc;
+        HIPCHK(hipMemcpy(d_r, residual, n_out * 4, hipMemcpyHostToDevice));
     }
     if (int rc = conv_forward_bf16(own.op, d_x, d_r, batch, height, width, out_fp32, d_y, nullptr)) return rc;
-    HIPTRY(hipDeviceSynchronize());
-    HIPTRY(hipMemcpy(out, d_y, n_out * 4, hipMemcpyDeviceToHost));
+    HIPCHK(hipDeviceSynchronize());
+    HIPCHK(hipMemcpy(out, d_y, n_out * 4, hipMemcpyDeviceToHost));
     return 0;
 }
 
@@ -812,37 +768,31 @@ static int i8_prepare(y355_conv_op *op, int batch, int height, int width, int sa
             return rc;
         op->rq = q.rq;
         op->frac_bits = q.frac_bits;
-        if (op->bt_dev) HIPTRY(hipMemcpy(op->bt_dev, q.bias_t.data(), sizeof(int) * pl->cout_pad, hipMemcpyHostToDevice));
-        HIPTRY(hipMemcpy(op->bw_dev, q.bias_w.data(), sizeof(long long) * pl->cout_pad, hipMemcpyHostToDevice));
+        if (op->m.bt_dev) HIPCHK(hipMemcpy(op->m.bt_dev, q.bias_t.data(), sizeof(int) * pl->cout_pad, hipMemcpyHostToDevice));
+        HIPCHK(hipMemcpy(op->m.bw_dev, q.bias_w.data(), sizeof(long long) * pl->cout_pad, hipMemcpyHostToDevice));
         op->sa_cached = sa;
     }
     // the 3x3 kernels prefetch past the last pixel: 64 pixels of slack
     *in_bytes = ((size_t)batch * (height + 2) * (width + 2) + (op->geom ? 0 : 64)) * op->cpad;
     const size_t raw_bytes = sizeof(long long) * (size_t)batch * pl->Ho * pl->Wo * pl->cout_pad;
-    const size_t geo = ((size_t)batch << 40) ^ ((size_t)height << 20) ^ (size_t)width ^ ((size_t)1 << 61);
-    const bool regeo = geo != op->geo;
-    op->geo = geo;
-    if (int rc = op_grow(&op->in_dev, &op->in_cap, *in_bytes, true)) return rc;
-    if (int rc = op_grow(&op->out_dev, &op->out_cap, raw_bytes, false)) return rc;
-    if (regeo) HIPTRY(hipMemsetAsync(op->in_dev, 0, *in_bytes, s));
-    return 0;
+    return op_workspaces(op, geo_word(batch, height, width, 0), *in_bytes, raw_bytes, false, 0, s);     // t' has no halo
 }
 // conv + bias + activation without requantisation on the staged input: t' [pixel][cout_pad] int64 into out_dev
 static int i8_launch(y355_conv_op *op, const ConvPlan &pl, int batch, int height, int width, hipStream_t s) {
     if (op->geom) {
         ConvGeomParams p = geom_params(op->g, batch, height, width, pl.Ho, pl.Wo, op->cpad, pl.cout_pad, y355_convgeom_info(pl.kid)->bn);
-        p.in = op->in_dev; p.w = op->w_dev; p.bias_w = op->bw_dev; p.raw = (long long *)op->out_dev;
+        p.in = op->m.in_dev; p.w = op->m.w_dev; p.bias_w = op->m.bw_dev; p.raw = (long long *)op->m.out_dev;
         p.shl = op->rq.shl; p.lk = op->rq.lk; p.neg_mul = op->rq.neg_mul;
         y355_launch_convgeom(pl.kid, 0, p, s);
     } else {
         const ConvKernelInfo &ki = *y355_conv_kernel(pl.kid);
-        HIPTRY(hipMemsetAsync(op->ctr_dev, 0, sizeof(Counters), s));
-        ConvParams p = gen16_params(ki, (const int8_t *)op->in_dev, (const int8_t *)op->w_dev, op->bt_dev, op->bw_dev, op->ctr_dev, batch, height,
+        HIPCHK(hipMemsetAsync(op->m.ctr_dev, 0, sizeof(Counters), s));
+        ConvParams p = gen16_params(ki, (const int8_t *)op->m.in_dev, (const int8_t *)op->m.w_dev, op->m.bt_dev, op->m.bw_dev, op->m.ctr_dev, batch, height,
                                     width, pl.cout_pad, op->rq);
-        p.raw = (long long *)op->out_dev; p.mode = 1; p.guard = 0;      // statistics mode dumps t'
+        p.raw = (long long *)op->m.out_dev; p.mode = 1; p.guard = 0;      // statistics mode dumps t'
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, s);
     }
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     return 0;
 }
 
@@ -854,16 +804,16 @@ extern "C" int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int
     ConvPlan pl;
     if (int rc = conv_out_size(op, batch, height, width, &pl)) return rc;
     hipStream_t s = (hipStream_t)stream;
-    HIPTRY(hipSetDevice(op->device));
+    HIPCHK(hipSetDevice(op->device));
     *exact = 0;
     const size_t n_in = (size_t)batch * op->cin * height * width, n_out = (size_t)batch * op->cout * pl.Ho * pl.Wo;
     // (1) the exponent of x: floor(log2(127 / max|x|)) -- the tensor is q / 2^e with |q| <= 127 (prep.as_dyadic_int8)
-    HIPTRY(hipMemsetAsync(op->flag_dev, 0, 16, s));
-    y355_launch_absmax(x_dev, n_in, op->flag_dev, s);
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipMemsetAsync(op->m.flag_dev, 0, 16, s));
+    y355_launch_absmax(x_dev, n_in, op->m.flag_dev, s);
+    HIPCHK(hipGetLastError());
     unsigned int bits = 0;
-    HIPTRY(hipMemcpyAsync(&bits, op->flag_dev, 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(&bits, op->m.flag_dev, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     float mx;
     memcpy(&mx, &bits, 4);
     if (!(mx > 0.f) || !std::isfinite(mx)) return 0;                              // all zero / not finite: not this route
@@ -873,18 +823,18 @@ extern "C" int y355_conv_op_forward_i8(y355_conv_op *op, const float *x_dev, int
     // (2) weights, integer epilogue, workspaces; (3) stage: int8 NHWC with halo + the dyadic verdict
     size_t in_bytes = 0;
     if (int rc = i8_prepare(op, batch, height, width, sa, s, &pl, &in_bytes)) return rc;
-    hipLaunchKernelGGL(dyadic_to_nhwc_i8_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (int8_t *)op->in_dev, batch, op->cin, height, width,
-                       op->cpad, std::ldexp(1.0f, sa), op->flag_dev + 1);
-    HIPTRY(hipGetLastError());
+    hipLaunchKernelGGL(dyadic_to_nhwc_i8_kernel, dim3(grid_for(n_in)), dim3(256), 0, s, x_dev, (int8_t *)op->m.in_dev, batch, op->cin, height, width,
+                       op->cpad, std::ldexp(1.0f, sa), op->m.flag_dev + 1);
+    HIPCHK(hipGetLastError());
     unsigned int bad = 0;
-    HIPTRY(hipMemcpyAsync(&bad, op->flag_dev + 1, 4, hipMemcpyDeviceToHost, s));
-    HIPTRY(hipStreamSynchronize(s));
+    HIPCHK(hipMemcpyAsync(&bad, op->m.flag_dev + 1, 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
     if (bad) return 0;
     // (4) the convolution, (5) t' / 2^F' -> fp32 NCHW
     if (int rc = i8_launch(op, pl, batch, height, width, s)) return rc;
-    hipLaunchKernelGGL(raw_to_nchw_f32_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const long long *)op->out_dev, out_dev, batch, op->cout, pl.Ho,
+    hipLaunchKernelGGL(raw_to_nchw_f32_kernel, dim3(grid_for(n_out)), dim3(256), 0, s, (const long long *)op->m.out_dev, out_dev, batch, op->cout, pl.Ho,
                        pl.Wo, pl.cout_pad, std::ldexp(1.0f, -op->frac_bits));
-    HIPTRY(hipGetLastError());
+    HIPCHK(hipGetLastError());
     *exact = 1;
     return 0;
 }
@@ -900,11 +850,11 @@ static int i8_raw_host_form(y355_conv_op *op_, const int8_t *q_in, int batch, in
     if (int rc = conv_out_size(op, batch, height, width, &pl)) return rc;
     if (int rc = i8_prepare(op, batch, height, width, sa_in, nullptr, &pl, &in_bytes)) return rc;
     const std::vector<int8_t> xin = nhwc_halo_i8(q_in, batch, op->cin, height, width, op->cpad, in_bytes);
-    HIPTRY(hipMemcpy(op->in_dev, xin.data(), in_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(op->m.in_dev, xin.data(), in_bytes, hipMemcpyHostToDevice));
     if (int rc = i8_launch(op, pl, batch, height, width, nullptr)) return rc;
-    HIPTRY(hipDeviceSynchronize());
+    HIPCHK(hipDeviceSynchronize());
     std::vector<long long> o((size_t)batch * pl.Ho * pl.Wo * pl.cout_pad);
-    HIPTRY(hipMemcpy(o.data(), op->out_dev, sizeof(long long) * o.size(), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(o.data(), op->m.out_dev, sizeof(long long) * o.size(), hipMemcpyDeviceToHost));
     nhwc_to_nchw(o.data(), out, batch, op->cout, pl.Ho, pl.Wo, pl.cout_pad);
     *frac_bits = op->frac_bits;
     return 0;
@@ -939,7 +889,7 @@ extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const in
     if (int rc = gen16_shape(batch, cin, cout, H, W, flags)) return rc;
     const int pool = (flags & Y355_OP_POOL) ? 1 : 0;
     if (pool && ((H | W) & 1)) return y355_fail(Y355_EINVAL, "pooling needs even H, W");
-    HIPTRY(hipSetDevice(device_id));
+    HIPCHK(hipSetDevice(device_id));
     if (int e = y355_prepare_kernels()) return e;
     int cpad = 0;
     const ConvKernelInfo &ki = *y355_conv_kernel(gen16_kernel(cin, pool, &cpad));
@@ -950,34 +900,34 @@ extern "C" int y355_conv3x3_i8_fused(int device_id, const int8_t *q_in, const in
     const std::vector<int8_t> xin = nhwc_halo_i8(q_in, batch, cin, H, W, cpad, in_bytes);
     std::vector<int8_t> packed(y355_packed_bytes(ki, cout_pad));
     y355_pack_weights(ki, q_w, cout, cin, cout_pad, packed.data());
-    Scratch tmp;
+    DevScope tmp;
     int8_t *d_in = nullptr, *d_w = nullptr, *d_out = nullptr;
     int *d_b = nullptr;
     long long *d_bw = nullptr;
     Counters *d_c = nullptr;
-    HIPTRY(tmp.get(&d_in, in_bytes));
-    HIPTRY(tmp.get(&d_w, packed.size()));
-    HIPTRY(tmp.get(&d_out, out_elems + 64));
-    HIPTRY(tmp.get(&d_b, sizeof(int) * cout_pad));
-    HIPTRY(tmp.get(&d_bw, sizeof(long long) * cout_pad));
-    HIPTRY(tmp.get(&d_c, sizeof(Counters)));
-    HIPTRY(hipMemcpy(d_in, xin.data(), in_bytes, hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(d_w, packed.data(), packed.size(), hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(d_b, q.bias_t.data(), sizeof(int) * cout_pad, hipMemcpyHostToDevice));
-    HIPTRY(hipMemcpy(d_bw, q.bias_w.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
-    HIPTRY(hipMemset(d_out, 0, out_elems + 64));
+    if (int rc = y355_dev_get(tmp, &d_in, in_bytes)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_w, packed.size())) return rc;
+    if (int rc = y355_dev_get(tmp, &d_out, out_elems + 64)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_b, (size_t)cout_pad)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_bw, (size_t)cout_pad)) return rc;
+    if (int rc = y355_dev_get(tmp, &d_c, 1)) return rc;
+    HIPCHK(hipMemcpy(d_in, xin.data(), in_bytes, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_w, packed.data(), packed.size(), hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_b, q.bias_t.data(), sizeof(int) * cout_pad, hipMemcpyHostToDevice));
+    HIPCHK(hipMemcpy(d_bw, q.bias_w.data(), sizeof(long long) * cout_pad, hipMemcpyHostToDevice));
+    HIPCHK(hipMemset(d_out, 0, out_elems + 64));
     Counters cz{}, cs{};
     for (int mode = 1; mode >= 0; --mode) {
-        HIPTRY(hipMemset(d_c, 0, sizeof(Counters)));
+        HIPCHK(hipMemset(d_c, 0, sizeof(Counters)));
         ConvParams p = gen16_params(ki, d_in, d_w, d_b, d_bw, d_c, batch, H, W, cout_pad, q.rq);
         p.out = d_out; p.mode = mode; p.guard = 1;
         ki.launch(p, p.tiles_x * p.tiles_y * p.nblk * batch, 0);
-        HIPTRY(hipGetLastError());
-        HIPTRY(hipDeviceSynchronize());
-        HIPTRY(hipMemcpy(mode ? &cs : &cz, d_c, sizeof(Counters), hipMemcpyDeviceToHost));
+        HIPCHK(hipGetLastError());
+        HIPCHK(hipDeviceSynchronize());
+        HIPCHK(hipMemcpy(mode ? &cs : &cz, d_c, sizeof(Counters), hipMemcpyDeviceToHost));
     }
     std::vector<int8_t> o(out_elems);
-    HIPTRY(hipMemcpy(o.data(), d_out, out_elems, hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(o.data(), d_out, out_elems, hipMemcpyDeviceToHost));
     nhwc_to_nchw(o.data(), out, batch, cout, Ho, Wo, cout_pad);
     if (stats) {
         stats->absmax_t = (int64_t)cs.absmax;

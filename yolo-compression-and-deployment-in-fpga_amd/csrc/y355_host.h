@@ -1,5 +1,5 @@
 // yolo355 -- the host-side pieces every library of the project needs, and nothing of a kernel: the error return, HIPCHK,
-// DeviceGuard, DevMem (how host state gets device memory), its HIP form, and DevOwner (the one owner of that memory).
+// DeviceGuard, DevMem (how host state gets device memory), its HIP form, DevOwner (the one owner of that memory) and DevScope.
 // libyolo355.so gets it through y355_common.h; loss.hip and anchors.hip include it alone.  The error codes are yolo355.h's;
 // the companions' families carry the same numbers (each asserts it next to its include).
 #pragma once
@@ -65,8 +65,8 @@ inline const DevMem &y355_hip_mem(void) {
 }
 
 // The one owner of a piece of host state's device memory (HeadState, FrameStage, HandleCore, y355_apeval, y355_pipeline,
-// y355_loss, y355_anchors): what it got and has not dropped goes back in y355_dev_release_all, whatever the fields that
-// pointed to it say by then.
+// y355_loss, y355_anchors, ConvOpMem of y355_conv_op, and a DevScope for what lives as long as one call): what it got and has
+// not dropped goes back in y355_dev_release_all, whatever the fields that pointed to it say by then.
 struct DevOwner {
     DevMem mem;
     std::vector<void *> allocs;
@@ -90,21 +90,21 @@ inline void y355_dev_drop(DevOwner &o, T **...p) {
     }
     ((*p = nullptr), ...);
 }
-// several arrays (null now) of count elements each: all of them or, after a failure, none
-template <typename... T>
+// several arrays (null now) of count elements each (<true>: zeroed): all of them or, after a failure, none
+template <bool Zero = false, typename... T>
 inline int y355_dev_get_all(DevOwner &o, size_t count, T **...p) {
     int rc = 0;
-    ((rc = rc ? rc : y355_dev_get(o, p, count)), ...);
+    ((rc = rc ? rc : y355_dev_get(o, p, count, Zero)), ...);
     if (rc) y355_dev_drop(o, p...);
     return rc;
 }
 // one array, or several of one capacity *have (elements of each): nothing when they are there and need <= *have, else dropped
-// and got again at `need`; a failure leaves every one of them null and *have = 0
-template <typename... T>
+// and got again at `need` (<true>: zeroed); a failure leaves every one of them null and *have = 0
+template <bool Zero = false, typename... T>
 inline int y355_dev_grow(DevOwner &o, size_t *have, size_t need, T **...p) {
     if (need <= *have && (... && (*p != nullptr))) return 0;
     y355_dev_drop(o, p...);
-    const int rc = y355_dev_get_all(o, need, p...);
+    const int rc = y355_dev_get_all<Zero>(o, need, p...);
     *have = rc ? 0 : need;
     return rc;
 }
@@ -115,3 +115,12 @@ inline void y355_dev_rollback(DevOwner &o, size_t mark) {
     for (; o.allocs.size() > mark; o.allocs.pop_back()) o.mem.release(o.allocs.back());
 }
 inline void y355_dev_release_all(DevOwner &o) { y355_dev_rollback(o, 0); }       // idempotent
+
+// The device memory of one call (the host-pointer forms of ops.hip, y355_head_f32_ex): an owner on the HIP calls whose memory
+// goes back when the call returns, whichever way.
+struct DevScope : DevOwner {
+    DevScope() : DevOwner{y355_hip_mem(), {}} {}
+    DevScope(const DevScope &) = delete;
+    DevScope &operator=(const DevScope &) = delete;
+    ~DevScope() { y355_dev_release_all(*this); }
+};

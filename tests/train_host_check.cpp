@@ -1,0 +1,200 @@
+// The host side of libyolo355_train.so on the CPU under the address and undefined-behaviour sanitizers
+// (make -C csrc hostcheck-train): the rules of y355_train_create (its device-free half), the handle's buffers -- all of them
+// or none -- under an allocator that fails at every allocation in turn, every refusal the entry points make before a device
+// call, and the set_size bookkeeping, on a handle whose "device" memory is the host heap.  A stand-alone program; needs no GPU.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <set>
+#include <string>
+
+#include "../include/yolo355_train.h"
+#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/y355_host.h"
+
+static std::string g_text;
+int y355_fail(int code, const std::string &msg) {      // the library's own is left out under -DY355_HOSTCHECK
+    g_text = msg;
+    return code;
+}
+
+// train.hip's two halves of a create and what goes with them (the struct stays the library's)
+int train_open(int max_h, int max_w, int num_classes, int num_anchors, int max_batch, const DevMem &mem, y355_train **out);
+int train_buffers(y355_train *h);
+DevOwner &train_owner(y355_train *h);
+void train_free(y355_train *h);
+void train_state(const y355_train *h, int *hw_batch);
+
+static int failures = 0;
+#define EXPECT(cond)                                                         \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            std::printf("%s:%d: %s   [%s]\n", __FILE__, __LINE__, #cond, g_text.c_str()); \
+            ++failures;                                                      \
+        }                                                                    \
+    } while (0)
+
+// the host heap as device memory: every block is tracked, the fail_at-th allocation from now (0-based) fails
+static std::set<void *> live;
+static int fail_at = -1, allocs_seen = 0;
+static DevMem host_mem() {
+    DevMem m;
+    m.alloc = [](void **p, size_t bytes, bool zero) {
+        if (allocs_seen++ == fail_at) return y355_fail(Y355_EHIP, "allocation refused");
+        *p = zero ? std::calloc(1, bytes ? bytes : 16) : std::malloc(bytes ? bytes : 16);
+        live.insert(*p);
+        return 0;
+    };
+    m.release = [](void *p) {
+        EXPECT(live.erase(p) == 1);                       // never twice, never a stranger
+        std::free(p);
+    };
+    m.upload = [](void *dst, const void *src, size_t bytes, hipStream_t) {
+        std::memcpy(dst, src, bytes);
+        return 0;
+    };
+    return m;
+}
+
+static void refused_create(const char *text, int h, int w, int c, int a, int b) {
+    y355_train *t = (y355_train *)16;
+    g_text.clear();
+    const int rc = train_open(h, w, c, a, b, host_mem(), &t);
+    if (rc != Y355_TRAIN_EINVAL || t || g_text.find(text) == std::string::npos || !live.empty()) {
+        std::printf("expected a create refused with \"%s\", got %d \"%s\"\n", text, rc, g_text.c_str());
+        ++failures;
+    }
+}
+
+static void check_rules() {
+    EXPECT(train_open(64, 64, 2, 5, 1, host_mem(), nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_create: null argument");
+    refused_create("multiples of 16", 60, 64, 2, 5, 1);
+    refused_create("multiples of 16", 64, 72, 2, 5, 1);
+    refused_create("multiples of 16", 0, 64, 2, 5, 1);
+    refused_create("multiples of 16", 64, 4112, 2, 5, 1);
+    refused_create("num_classes must be 1..200", 64, 64, 0, 5, 1);
+    refused_create("num_classes must be 1..200", 64, 64, 201, 5, 1);
+    refused_create("num_anchors must be 1..16", 64, 64, 2, 0, 1);
+    refused_create("num_anchors must be 1..16", 64, 64, 2, 17, 1);
+    refused_create("max_batch must be 1..1024", 64, 64, 2, 5, 0);
+    refused_create("max_batch must be 1..1024", 64, 64, 2, 5, 1025);
+}
+
+// all of the buffers or none, whichever allocation fails; returns the number of allocations of a whole handle
+static int check_all_or_none(int h, int w, int c, int a, int b) {
+    y355_train *t = nullptr;
+    fail_at = -1;
+    allocs_seen = 0;
+    EXPECT(train_open(h, w, c, a, b, host_mem(), &t) == 0 && t && live.empty());
+    EXPECT(train_buffers(t) == 0);
+    const int total = allocs_seen;
+    EXPECT(total > 0 && (int)live.size() == total && train_owner(t).allocs.size() == (size_t)total);
+    train_free(t);
+    EXPECT(live.empty());
+    for (int k = 0; k < total; ++k) {
+        t = nullptr;
+        EXPECT(train_open(h, w, c, a, b, host_mem(), &t) == 0 && t);
+        allocs_seen = 0;
+        fail_at = k;
+        g_text.clear();
+        EXPECT(train_buffers(t) == Y355_EHIP && g_text == "allocation refused");
+        EXPECT(live.empty() && train_owner(t).allocs.empty());          // none
+        fail_at = -1;
+        EXPECT(train_buffers(t) == 0 && (int)live.size() == total);      // the handle can still get them
+        train_free(t);
+        EXPECT(live.empty());
+    }
+    fail_at = -1;
+    return total;
+}
+
+static void check_refusals_and_sizes() {
+    y355_train *t = nullptr;
+    EXPECT(train_open(96, 160, 2, 5, 2, host_mem(), &t) == 0 && train_buffers(t) == 0);
+    int st[4];
+    train_state(t, st);
+    EXPECT(st[0] == 96 && st[1] == 160 && st[2] == 0 && st[3] == 0);
+    float x[4] = {0, 0, 0, 0};
+    int32_t shape[4];
+    void *p = nullptr;
+
+    EXPECT(y355_train_set_size(nullptr, 64, 64) == Y355_TRAIN_EINVAL && g_text == "y355_train_set_size: null handle");
+    EXPECT(y355_train_set_size(t, 60, 64) == Y355_TRAIN_EINVAL && g_text == "y355_train_set_size: height and width must be multiples of 16");
+    EXPECT(y355_train_set_size(t, 64, 8) == Y355_TRAIN_EINVAL && g_text == "y355_train_set_size: height and width must be multiples of 16");
+    EXPECT(y355_train_set_size(t, 112, 160) == Y355_TRAIN_EINVAL && g_text == "y355_train_set_size: size beyond the handle's maximum");
+    EXPECT(y355_train_set_size(t, 96, 176) == Y355_TRAIN_EINVAL && g_text == "y355_train_set_size: size beyond the handle's maximum");
+    train_state(t, st);
+    EXPECT(st[0] == 96 && st[1] == 160);                                  // a refused size changes nothing
+    EXPECT(y355_train_set_size(t, 64, 64) == 0);
+    train_state(t, st);
+    EXPECT(st[0] == 64 && st[1] == 64 && st[2] == 0 && st[3] == 0);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_ACT, 0, shape) == 0 && shape[0] == 0 && shape[1] == 64 && shape[2] == 64 && shape[3] == 8);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_ACT, 9, shape) == 0 && shape[1] == 4 && shape[2] == 4 && shape[3] == 256);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_ACT, 4, shape) == 0 && shape[1] == 8 && shape[2] == 8 && shape[3] == 64);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_IDX, 6, shape) == 0 && shape[1] == 4 && shape[2] == 4 && shape[3] == 128);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_GRAD, 1, shape) == 0 && shape[1] == 64 && shape[2] == 64 && shape[3] == 16);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_GRAD, 10, shape) == 0 && shape[1] == 4 && shape[2] == 4 && shape[3] == 64);      // 35 -> 64
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_IDX, 3, shape) == Y355_TRAIN_EINVAL && g_text == "y355_train_tensor_shape: no such tensor");
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_ACT, 10, shape) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_GRAD, 0, shape) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_tensor_shape(t, 3, 1, shape) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_tensor_shape(t, Y355_TRAIN_ACT, 1, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_tensor_shape: null argument");
+
+    EXPECT(y355_train_layer_shape(t, 10, shape) == 0 && shape[0] == 35 && shape[1] == 256);
+    EXPECT(y355_train_layer_shape(t, 1, shape) == 0 && shape[0] == 16 && shape[1] == 3);
+    EXPECT(y355_train_layer_shape(t, 0, shape) == Y355_TRAIN_EINVAL && g_text == "y355_train_layer_shape: layer index must be 1..10");
+    EXPECT(y355_train_layer_shape(t, 11, shape) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_layer_shape(nullptr, 1, shape) == Y355_TRAIN_EINVAL && g_text == "y355_train_layer_shape: null handle");
+    EXPECT(y355_train_layer_shape(t, 1, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_layer_shape: null argument");
+    EXPECT(y355_train_load_layer(t, 0, x, x) == Y355_TRAIN_EINVAL && g_text == "y355_train_load_layer: layer index must be 1..10");
+    EXPECT(y355_train_load_layer(t, 11, x, x) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_load_layer(t, 1, nullptr, x) == Y355_TRAIN_EINVAL && g_text == "y355_train_load_layer: null argument");
+    EXPECT(y355_train_load_layer(t, 1, x, nullptr) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_get_layer(t, 12, x, x) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_layer: layer index must be 1..10");
+    EXPECT(y355_train_get_layer(nullptr, 1, x, x) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_layer: null handle");
+    EXPECT(y355_train_get_momentum(t, -1, x, x) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_momentum: layer index must be 1..10");
+    EXPECT(y355_train_get_packed(t, 0, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_packed: layer index must be 1..10");
+    EXPECT(y355_train_get_packed(t, 1, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_packed: null argument");
+    EXPECT(y355_train_get_grad(t, 0, x, x) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_grad: layer index must be 1..10");
+    EXPECT(y355_train_get_grad(t, 1, x, x) == Y355_TRAIN_ENOTREADY && g_text == "y355_train_get_grad: no backward pass has run");
+
+    EXPECT(y355_train_forward(nullptr, x, 1, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_forward: null argument");
+    EXPECT(y355_train_forward(t, nullptr, 1, nullptr) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_forward(t, x, 0, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_forward: batch must be 1..max_batch");
+    EXPECT(y355_train_forward(t, x, 3, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_forward: batch must be 1..max_batch");
+    EXPECT(y355_train_backward(nullptr, x, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_backward: null argument");
+    EXPECT(y355_train_backward(t, nullptr, nullptr) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_backward(t, x, nullptr) == Y355_TRAIN_ENOTREADY && g_text == "y355_train_backward: no forward pass has run at this size");
+    EXPECT(y355_train_sgd_step(nullptr, 0.1f, 0.9f, 0.f, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_sgd_step: null handle");
+    EXPECT(y355_train_sgd_step(t, std::nanf(""), 0.9f, 0.f, nullptr) == Y355_TRAIN_EINVAL &&
+           g_text == "y355_train_sgd_step: lr, momentum and weight_decay must be numbers");
+    EXPECT(y355_train_sgd_step(t, 0.1f, 0.9f, 0.f, nullptr) == Y355_TRAIN_ENOTREADY && g_text == "y355_train_sgd_step: no backward pass has run");
+    EXPECT(y355_train_pred(t, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_pred: null argument");
+    EXPECT(y355_train_pred(t, &p) == 0 && p != nullptr && live.count(p) == 1);
+    EXPECT(y355_train_get_tensor(t, Y355_TRAIN_ACT, 1, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_tensor: null argument");
+    EXPECT(y355_train_get_tensor(t, Y355_TRAIN_IDX, 5, x) == Y355_TRAIN_EINVAL && g_text == "y355_train_get_tensor: no such tensor");
+    EXPECT(y355_train_get_tensor(t, Y355_TRAIN_ACT, 1, x) == Y355_TRAIN_ENOTREADY && g_text == "y355_train_get_tensor: no forward pass has run at this size");
+
+    // after all these refusals the handle is as it was
+    train_state(t, st);
+    EXPECT(st[0] == 64 && st[1] == 64 && st[2] == 0 && st[3] == 0);
+    EXPECT(y355_train_set_size(t, 96, 160) == 0);
+    train_state(t, st);
+    EXPECT(st[0] == 96 && st[1] == 160);
+    train_free(t);
+    EXPECT(live.empty());
+    y355_train_destroy(nullptr);
+}
+
+int main() {
+    check_rules();
+    const int n = check_all_or_none(64, 96, 2, 5, 2);
+    check_all_or_none(32, 16, 20, 5, 1);
+    check_refusals_and_sizes();
+    if (failures) {
+        std::printf("train_host_check: %d failure(s)\n", failures);
+        return 1;
+    }
+    std::printf("train_host_check ok (%d allocations per handle)\n", n);
+    return 0;
+}

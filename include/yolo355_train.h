@@ -76,6 +76,12 @@ int y355_train_get_grad(y355_train *h, int32_t k, float *dw, float *db);
 int y355_train_get_momentum(y355_train *h, int32_t k, float *mw, float *mb);
 int y355_train_get_packed(y355_train *h, int32_t k, uint16_t *w_bf16);
 
+/* How a backward after a forward of `batch` images (1..max_batch) at the current size splits layer k's weight gradient:
+ * out[4] = {npix, max_runs, runs, chunk}.  The npix = batch * h * w pixels of G_k go to `runs` <= max_runs workgroup runs of
+ * `chunk` pixels each (a multiple of 32; the last run takes the rest), added afterwards in the order of the runs.  The very
+ * function the backward launches from; no device call.  Refused where npix does not fit int32_t. */
+int y355_train_wgrad_plan(const y355_train *h, int32_t k, int32_t batch, int32_t *out);
+
 /* one launch over all parameters on `stream`; needs the gradients of a backward */
 int y355_train_sgd_step(y355_train *h, float lr, float momentum, float weight_decay, void *stream);
 

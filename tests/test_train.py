@@ -5,7 +5,27 @@ convolutions in the interval of tests/bf16_layer_ref.py, the stored pool positio
 gradients, G_10 == rb(dP), and the SGD update bit for bit against the NumPy restatement.  The whole step: the losses are
 libyolo355_grad.so's on the engine's P, the gradients lie within 2 * emu_relerr + 1e-6 of the reference's own backward()
 (tests/golden/train.npz), the same bits from run to run, set_size against fresh handles, the state round trip, an overfit
-run, the refusals, and several handles in one process."""
+run, the refusals, and several handles in one process.
+
+The weight gradient's long runs.  y355_train_backward cuts a layer's B H W pixels into at most max_runs runs of `chunk` pixels
+(a multiple of 32); a wave walks its run in steps of 32 and train_reduce_kernel adds the runs.  At the first three cases every
+chunk is 32 -- one step a wave, the cap never reached -- while every fine-tuning step (64 x 416 x 416, 32 x 240 x 320) has chunks
+of 160 to 5408 pixels.  The two TC.DEEP cases sit just above the threshold of that regime (524 288 input pixels), and the tests
+ask the live handle for the plan (SlimTrainer.wgrad_plan, the function the backward launches from) instead of restating it.
+As y355_train_wgrad_plan printed them on an MI355X (layer: runs x chunk, last run):
+
+  t416x448_b3_c2    1: 1942 x 288, 96    2: 1456 x 96, 96    3: 546 x 64, 64     4: 364 x 96, 96     5: 137 x 64, 32
+                    6: 91 x 96, 96       7: 35 x 64, 8       8: 23 x 96, 72      9: 23 x 96, 72      10: 35 x 64, 8
+  t240x272_b9_c20   1: 2040 x 288, 288   2: 1530 x 96, 96    3: 574 x 64, 48     4: 383 x 96, 48     5: 144 x 64, 28
+                    6: 96 x 96, 60       7: 36 x 64, 55      8: 24 x 96, 87      9: 24 x 96, 87      10: 36 x 64, 55
+
+On them: every per-op test; a sparse dP (K of the bound = the pixels where G_k is not zero, so a pixel dropped or taken twice
+fails) with its probes on both sides of run and image boundaries; a one-hot dP whose dW_10 is A_9 bit for bit; the same bits
+from run to run.  t16_b5_c2 and t16x32_b3_c20 have 1 x 1 and 1 x 2 maps at stride 16; a batch below max_batch runs on a handle
+whose buffers hold an older, larger one.
+
+Measured on one MI355X: the module (52 tests) in 9.9 s; its slowest new test is
+test_forward_convolutions_per_element[t416x448_b3_c2], 2.0 s (float64 on the CPU), every other new one below 0.6 s."""
 import functools
 import os
 
@@ -21,6 +41,7 @@ pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = TR.U
 CIN = [3, 16, 32, 64, 64, 128, 128, 256, 256, 256]
+DIV = [1, 2, 4, 4, 8, 8, 16, 16, 16, 16]                     # layer k's grid is the input's divided by DIV[k - 1]
 
 
 @pytest.fixture(scope="module")
@@ -72,6 +93,7 @@ def run(tag):
     r["Wb"] = [TR.bf16_bits_to_f64(t.get_packed(k)) for k in range(1, 11)]
     r["layers"] = [t.get_layer(k) for k in range(1, 11)]
     r["grads"] = all_grads(t)
+    r["plan"] = [t.wgrad_plan(k) for k in range(1, 11)]     # of the backward that has just run
     t.close()
     return r
 
@@ -137,23 +159,178 @@ def test_data_gradients_per_element(tag):
         assert not bad.any(), (tag, k, int(bad.sum()), torch.nonzero(bad)[:5].tolist())
 
 
+def assert_weight_gradients(tag, grads, G_of, A, support_only=False):
+    """every dW_k and db_k against float64 from G_k (G_of(k)) and A_{k-1}: |got - z| <= 2 K u S 1.001, S = sum |G| |A|, K the
+    number of pixels summed over -- B H W, or with support_only the pixels at which G_k has a nonzero channel (zeros add
+    exactly).  Returns {k: the [B, H, W] support of G_k}."""
+    support = {}
+    for k in range(1, 11):
+        dw, db = grads[k - 1]
+        cout, cin = dw.shape[:2]
+        G, Ap = G_of(k)[:, :cout], A[k - 1][:, :cin]
+        support[k] = (G != 0).any(1)
+        K = int(support[k].sum()) if support_only else G.shape[0] * G.shape[2] * G.shape[3]
+        zw, zb = TR.wgrad(G, Ap)
+        Sw, Sb = TR.wgrad(G.abs(), Ap.abs())
+        for what, got, z, S in (("dw", dw, zw, Sw), ("db", db, zb, Sb)):
+            err = (torch.from_numpy(got).double() - z).abs()
+            bound = 2 * K * U * S * 1.001
+            print(tag, "layer", k, what, "K %d max err / bound %.3g" % (K, float((err / bound.clamp(min=1e-300)).max())), "max |z| %.3g" % float(z.abs().max()))
+            assert bool((err <= bound).all()), (tag, k, what, float(err.max()), torch.nonzero(err > bound)[:3].tolist())
+        assert float(zw.abs().max()) > 0 and np.isfinite(dw).all()
+    return support
+
+
 @pytest.mark.parametrize("tag", TC.TAGS)
 def test_weight_and_bias_gradients_per_element(tag):
     """from the engine's G_k and A_{k-1} in float64: |got - z| <= 2 K u S 1.001, K = B H W, S = sum |G| |A|"""
     r = run(tag)
+    assert_weight_gradients(tag, r["grads"], lambda k: r["G"][k], r["A"])
+
+
+# ------------------------------------------------------------------------------------------- the weight gradient's long runs
+def last_run(p):
+    return p["npix"] - (p["runs"] - 1) * p["chunk"]
+
+
+def test_deep_cases_reach_the_long_run_regime():
+    """asked of the live handles (y355_train_wgrad_plan): every layer of a deep case sums over runs of two or more 32-pixel
+    steps in more than one run; over the two cases some layer's last run is shorter than the others and some layer's last
+    run ends inside an 8-pixel group.  A condition on the inputs of the tests below."""
+    lasts = []
+    for tag in TC.DEEP:
+        (h, w), B, _ = TC.CASES[tag]
+        for k, p in enumerate(run(tag)["plan"], 1):
+            print("PLAN", tag, "layer", k, "npix %d max_runs %d runs %d chunk %d last run %d" % (p["npix"], p["max_runs"], p["runs"], p["chunk"], last_run(p)))
+            assert p["npix"] == B * (h // DIV[k - 1]) * (w // DIV[k - 1])
+            assert p["chunk"] >= 64 and p["chunk"] % 32 == 0 and 1 < p["runs"] <= p["max_runs"] and 0 < last_run(p) <= p["chunk"]
+            lasts.append((last_run(p), p["chunk"]))
+    assert any(l < c for l, c in lasts) and any(l % 8 for l, c in lasts)
+    for tag in TC.TAGS[:3]:                                  # what the first three cases never left
+        assert all(p["chunk"] == 32 for p in run(tag)["plan"])
+
+
+def probes(t, B, h, w):
+    """stride-16 pixels (flat b, y, x) chosen from the plans of layers 10 and 8: the first pixel of image 0, the last of the
+    last image, both sides of an image boundary, both sides of a run boundary of either plan, the first and the last pixel of
+    either plan's last run"""
+    hw, npix = h * w, B * h * w
+    ps = {0, npix - 1, hw - 1, hw}
+    for k in (10, 8):
+        p = t.wgrad_plan(k)
+        assert p["npix"] == npix and p["runs"] > 2
+        mid = (p["runs"] // 2) * p["chunk"]
+        ps |= {mid - 1, mid, (p["runs"] - 1) * p["chunk"], npix - 1}
+    return sorted(ps)
+
+
+def forwarded(tag):
+    """a fresh trainer after one forward of the case: the tensors of run(tag)"""
+    t = trainer(tag)
+    P = t.forward(dev(TC.images(tag)))
+    assert same(P.cpu().numpy(), run(tag)["P"])
+    return t
+
+
+@pytest.mark.parametrize("tag", TC.DEEP)
+def test_sparse_upstream_gradient(tag):
+    """dP zero but at a handful of stride-16 pixels (probes) that carry random values in every channel: dW_k and db_k of all
+    ten layers against float64 from the engine's own G_k and A_{k-1}, with K the number of pixels at which G_k is not zero --
+    a pixel of the support dropped or taken twice is outside the bound.  Every layer has a run boundary inside the support."""
+    from yolo355 import synth, train as T
+    (h, w), B, C = TC.CASES[tag]
+    h, w = h // 16, w // 16
+    r, t = run(tag), forwarded(tag)
+    ps = probes(t, B, h, w)
+    dP = np.zeros((B, 5 * (5 + C), h, w), np.float32)
+    vals = synth.uniform_pm1(TC._seed(tag) + 7, (len(ps), dP.shape[1]))
+    for i, p in enumerate(ps):
+        dP[p // (h * w), :, p % (h * w) // w, p % w] = vals[i]
+    t.backward(dev(dP))
+    grads, plan = all_grads(t), [t.wgrad_plan(k) for k in range(1, 11)]
+    assert plan == r["plan"]
+    support = assert_weight_gradients(tag, grads, lambda k: TR.bf16_bits_to_f64(t.get_tensor(T.GRAD, k)), r["A"], support_only=True)
+    t.close()
+    assert int(support[10].sum()) == len(ps)
     for k in range(1, 11):
-        dw, db = r["grads"][k - 1]
-        cout, cin = dw.shape[:2]
-        G, A = r["G"][k][:, :cout], r["A"][k - 1][:, :cin]
-        K = G.shape[0] * G.shape[2] * G.shape[3]
-        zw, zb = TR.wgrad(G, A)
-        Sw, Sb = TR.wgrad(G.abs(), A.abs())
-        for what, got, z, S in (("dw", dw, zw, Sw), ("db", db, zb, Sb)):
-            err = (torch.from_numpy(got).double() - z).abs()
-            bound = 2 * K * U * S * 1.001
-            print(tag, "layer", k, what, "max err / bound %.3g" % float((err / bound.clamp(min=1e-300)).max()), "max |z| %.3g" % float(z.abs().max()))
-            assert bool((err <= bound).all()), (tag, k, what, float(err.max()))
-        assert float(zw.abs().max()) > 0 and np.isfinite(dw).all()
+        s, c = support[k].reshape(-1), plan[k - 1]["chunk"]
+        inside = sum(1 for i in range(1, plan[k - 1]["runs"]) if s[i * c - 1] and s[i * c])
+        print("SUPPORT", tag, "layer", k, "pixels %d of %d, run boundaries inside it %d of %d" % (int(s.sum()), s.numel(), inside, plan[k - 1]["runs"] - 1))
+        assert inside >= 1, (tag, k)
+
+
+@pytest.mark.parametrize("tag", TC.DEEP)
+def test_one_hot_upstream_gradient_bit_for_bit(tag):
+    """dP is 1.0 at one probe pixel per prediction channel (the probes taken in turn): dW_10[c, ci, tap] is the element of A_9
+    under that tap, or 0 in the padding, and db_10[c] is 1.0 -- sums of one nonzero term, so as bits (a -0.0 of A_9 comes out
+    of the fp32 sum from +0.0 as +0.0)"""
+    (h, w), B, C = TC.CASES[tag]
+    h, w = h // 16, w // 16
+    r, t = run(tag), forwarded(tag)
+    ps = probes(t, B, h, w)
+    cout = 5 * (5 + C)
+    dP = np.zeros((B, cout, h, w), np.float32)
+    A9 = np.pad(r["A"][9].numpy().astype(np.float32), ((0, 0), (0, 0), (1, 1), (1, 1)))
+    want = np.zeros((cout, 256, 3, 3), np.float32)
+    for c in range(cout):
+        p = ps[c % len(ps)]
+        b, y, x = p // (h * w), p % (h * w) // w, p % w
+        dP[b, c, y, x] = 1.0
+        want[c] = A9[b, :, y:y + 3, x:x + 3] + np.float32(0.0)
+    t.backward(dev(dP))
+    dw, db = t.get_grad(10)
+    t.close()
+    assert np.count_nonzero(want) > 0.5 * want.size                             # (the probes in corners have five taps in the padding)
+    bad = np.argwhere(bits(dw) != bits(want))
+    assert not len(bad), (tag, len(bad), bad[:5].tolist())
+    assert same(db, np.ones(cout, np.float32))
+
+
+@pytest.mark.parametrize("tag", TC.DEEP)
+def test_two_runs_of_a_deep_case_give_the_same_bits(tag):
+    """the order of the sum is fixed with the number of runs at or near its cap too"""
+    r = run(tag)
+    t = trainer(tag)
+    x = dev(TC.images(tag))
+    for _ in range(2):
+        t.forward_backward(x, TC.labels(tag))
+        assert same_grads(all_grads(t), r["grads"]) and same(t.losses, r["losses"])
+    t.close()
+
+
+def everything(t):
+    """the gradients, losses and P of the last forward_backward and every tensor the handle hands out"""
+    from yolo355 import train as T
+    out = [g for pair in all_grads(t) for g in pair] + [np.array(t.losses), t.pred().cpu().numpy().copy()]
+    out += [t.get_tensor(T.ACT, k) for k in range(10)] + [t.get_tensor(T.IDX, k) for k in T.POOLED] + [t.get_tensor(T.GRAD, k) for k in range(1, 11)]
+    return out
+
+
+@pytest.mark.parametrize("tag,sub", [("t48x80_b3_c2", (1, 2)), ("t16_b5_c2", (3, 5))], ids=["t48x80_b3_c2-1of3", "t16_b5_c2-2of5"])
+def test_a_batch_below_max_batch_after_a_full_one(tag, sub):
+    """a handle whose buffers hold the full batch runs images sub[0]:sub[1] of it: everything equals a fresh handle of that
+    max_batch on the same images, bit for bit and in shape; then the full batch again equals its first run.  Two images of
+    t16_b5_c2 are 2 stride-16 pixels, inside one 8-pixel group, with three older images behind them in every buffer."""
+    r = run(tag)
+    x, labels = dev(TC.images(tag)), TC.labels(tag)
+    xs, ls = x[sub[0]:sub[1]].contiguous(), labels[sub[0]:sub[1]]
+    f = trainer(tag, max_batch=sub[1] - sub[0])
+    f.forward_backward(xs, ls)
+    want = everything(f)
+    f.close()
+    assert want[-1].shape[0] == sub[1] - sub[0] and want[21].shape[0] == sub[1] - sub[0]
+    t = trainer(tag)
+    t.forward_backward(x, labels)
+    first = everything(t)
+    assert same_grads(all_grads(t), r["grads"]) and same(first[20], r["losses"]) and same(first[21], r["P"])
+    t.forward_backward(xs, ls)
+    got = everything(t)
+    assert len(got) == len(want) and all(same(a, b) for a, b in zip(got, want)), [i for i, (a, b) in enumerate(zip(got, want)) if not same(a, b)]
+    assert [p for p in (t.wgrad_plan(k) for k in range(1, 11))] == [t.wgrad_plan(k, sub[1] - sub[0]) for k in range(1, 11)]
+    t.forward_backward(x, labels)
+    again = everything(t)
+    assert all(same(a, b) for a, b in zip(again, first)), [i for i, (a, b) in enumerate(zip(again, first)) if not same(a, b)]
+    t.close()
 
 
 def test_sgd_is_the_numpy_restatement_bit_for_bit():
@@ -197,7 +374,7 @@ def test_losses_are_the_gradient_library_s_on_the_engine_s_map(tag):
     h.close()
 
 
-@pytest.mark.parametrize("tag", TC.TAGS)
+@pytest.mark.parametrize("tag", TC.GOLDEN_TAGS)
 def test_gradients_against_the_reference(gold, tag):
     """every layer within a relative L2 distance of 2 * emu_relerr + 1e-6 of the reference's own backward()"""
     r = run(tag)
@@ -208,7 +385,7 @@ def test_gradients_against_the_reference(gold, tag):
     for k, name in enumerate(TC.LAYERS, 1):
         dw, db = r["grads"][k - 1]
         rel = gold["train/%s/emu_relerr/%s" % (tag, name)]
-        got = (TC.rel_l2(dw.reshape(-1)[TC.sample_index(dw.size)], gold["train/%s/dw/%s" % (tag, name)]), TC.rel_l2(db, gold["train/%s/db/%s" % (tag, name)]))
+        got = (TC.rel_l2(dw.reshape(-1)[TC.sample_index(dw.size, tag)], gold["train/%s/dw/%s" % (tag, name)]), TC.rel_l2(db, gold["train/%s/db/%s" % (tag, name)]))
         print("DIST", tag, name, "dw %.4g (emulation %.4g)  db %.4g (emulation %.4g)" % (got[0], rel[0], got[1], rel[1]))
         if got[0] > 2 * rel[0] + 1e-6 or got[1] > 2 * rel[1] + 1e-6:
             worst.append((name, got, tuple(rel)))

@@ -16,11 +16,23 @@ CASES = {
     "t48x80_b3_c2": ([48, 80], 3, 2),
     "t64_b2_c20": ([64, 64], 2, 20),
     "t96x160_b1": ([96, 160], 1, 2),
+    # The deployed regime of the weight gradient, just above its threshold (more than 524 288 input pixels: every layer's run is
+    # then longer than 32 pixels, so each wave accumulates over several steps, runs start and end inside images and the number
+    # of runs is at or near its cap; tests/test_train.py asserts it from y355_train_wgrad_plan).  26 x 28 maps at stride 16
+    # with a last run of 8 pixels; 15 x 17 maps, eight image boundaries, an odd pixel count and 125 prediction channels.
+    "t416x448_b3_c2": ([416, 448], 3, 2),
+    "t240x272_b9_c20": ([240, 272], 9, 20),
+    # 1 x 1 and 1 x 2 maps at stride 16: every tap but the centre (and one neighbour) is padding, the last pool maps 2 x 2 to 1 x 1
+    "t16_b5_c2": ([16, 16], 5, 2),
+    "t16x32_b3_c20": ([16, 32], 3, 20),
 }
-TAGS = list(CASES)
+TAGS = list(CASES)                              # new cases go at the end: the seeds follow the index
+DEEP = ["t416x448_b3_c2", "t240x272_b9_c20"]
+GOLDEN_TAGS = list(TAGS)                        # the cases tests/golden/train.npz holds
 LAYERS = ["conv1", "conv2", "conv3_1", "conv3_2", "conv4_1", "conv4_2", "conv5", "conv6", "conv7", "pred"]
 POOL = [True, True, False, True, False, True, False, False, False, False]
 FULL_LIMIT, SAMPLE_LIMIT = 20000, 4096          # the fixture stays below the largest one there is (fp32.npz)
+ADDED_LIMIT = 512                               # ... so the cases after the first three keep this many elements of a gradient
 
 
 def _seed(tag):
@@ -60,11 +72,17 @@ def state_dict(ws):
     return sd
 
 
-def sample_index(n):
-    """the elements of a flattened gradient of n elements the fixture keeps: all up to FULL_LIMIT, else a fixed stride"""
-    if n <= FULL_LIMIT:
+def sample_index(n, tag):
+    """the elements of a flattened gradient of n elements the fixture keeps: all up to FULL_LIMIT, else a fixed stride that
+    leaves at most SAMPLE_LIMIT; in the cases after the first three ADDED_LIMIT takes the place of both, with a stride that
+    shares no factor with the nine taps (on a 1 x 1 map the centre tap alone is not padding)"""
+    added = TAGS.index(tag) >= 3
+    full, limit = (ADDED_LIMIT, ADDED_LIMIT) if added else (FULL_LIMIT, SAMPLE_LIMIT)
+    if n <= full:
         return np.arange(n)
-    step = -(-n // SAMPLE_LIMIT)
+    step = -(-n // limit)
+    while added and step % 3 == 0:
+        step += 1
     return np.arange(0, n, step)
 
 

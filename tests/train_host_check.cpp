@@ -1,7 +1,8 @@
 // The host side of libyolo355_train.so on the CPU under the address and undefined-behaviour sanitizers
 // (make -C csrc hostcheck-train): the rules of y355_train_create (its device-free half), the handle's buffers -- all of them
 // or none -- under an allocator that fails at every allocation in turn, every refusal the entry points make before a device
-// call, and the set_size bookkeeping, on a handle whose "device" memory is the host heap.  A stand-alone program; needs no GPU.
+// call, the set_size bookkeeping, and the weight-gradient plan (y355_train_wgrad_plan: its refusals, its rule, the plans of the
+// two shapes tools/train_bench.py times), on a handle whose "device" memory is the host heap.  A stand-alone program; needs no GPU.
 #include <cmath>
 #include <cstdio>
 #include <cstdlib>
@@ -186,8 +187,57 @@ static void check_refusals_and_sizes() {
     y355_train_destroy(nullptr);
 }
 
+// y355_train_wgrad_plan: its refusals, its own rule on every layer (runs <= max_runs, chunk a multiple of 32, the runs cover
+// the pixels and none is empty), and the plans of the two shapes tools/train_bench.py times, 20 classes, printed and asserted
+static void check_plan_rule(y355_train *t, int batch, const int32_t *chunks) {
+    int st[4];
+    train_state(t, st);
+    static const int div[10] = {1, 2, 4, 4, 8, 8, 16, 16, 16, 16};
+    std::printf("wgrad plan %d x %d x %d:", batch, st[0], st[1]);
+    for (int k = 1; k <= 10; ++k) {
+        int32_t p[4] = {-1, -1, -1, -1};
+        EXPECT(y355_train_wgrad_plan(t, k, batch, p) == 0);
+        const long long npix = (long long)batch * (st[0] / div[k - 1]) * (st[1] / div[k - 1]);
+        EXPECT(p[0] == npix && p[1] >= 1 && p[2] >= 1 && p[2] <= p[1] && p[3] >= 32 && p[3] % 32 == 0);
+        EXPECT((long long)p[2] * p[3] >= npix && (long long)(p[2] - 1) * p[3] < npix);
+        EXPECT((long long)p[1] * (p[3] - 32) < npix);        // no longer chunks than max_runs runs need
+        if (chunks) EXPECT(p[3] == chunks[k - 1]);
+        std::printf(" %d:{npix %d, max_runs %d, runs %d, chunk %d, last %lld}", k, p[0], p[1], p[2], p[3], npix - (long long)(p[2] - 1) * p[3]);
+    }
+    std::printf("\n");
+}
+
+static void check_plans() {
+    static const int32_t c416[10] = {5408, 1376, 704, 1376, 704, 1376, 704, 1376, 1376, 704};
+    static const int32_t c240[10] = {1216, 320, 160, 320, 160, 320, 160, 320, 320, 160};
+    y355_train *t = nullptr;
+    EXPECT(train_open(416, 416, 20, 5, 64, host_mem(), &t) == 0 && t);        // the rules alone: no buffers
+    int32_t p[4] = {7, 7, 7, 7};
+    EXPECT(y355_train_wgrad_plan(nullptr, 1, 1, p) == Y355_TRAIN_EINVAL && g_text == "y355_train_wgrad_plan: null handle");
+    EXPECT(y355_train_wgrad_plan(t, 0, 1, p) == Y355_TRAIN_EINVAL && g_text == "y355_train_wgrad_plan: layer index must be 1..10");
+    EXPECT(y355_train_wgrad_plan(t, 11, 1, p) == Y355_TRAIN_EINVAL);
+    EXPECT(y355_train_wgrad_plan(t, 1, 1, nullptr) == Y355_TRAIN_EINVAL && g_text == "y355_train_wgrad_plan: null argument");
+    EXPECT(y355_train_wgrad_plan(t, 1, 0, p) == Y355_TRAIN_EINVAL && g_text == "y355_train_wgrad_plan: batch must be 1..max_batch");
+    EXPECT(y355_train_wgrad_plan(t, 1, 65, p) == Y355_TRAIN_EINVAL && g_text == "y355_train_wgrad_plan: batch must be 1..max_batch");
+    EXPECT(p[0] == 7 && p[1] == 7 && p[2] == 7 && p[3] == 7);                 // a refusal writes nothing
+    check_plan_rule(t, 64, c416);
+    check_plan_rule(t, 1, nullptr);
+    EXPECT(y355_train_set_size(t, 240, 320) == 0);                            // the plan follows the current size
+    check_plan_rule(t, 32, c240);
+    EXPECT(y355_train_set_size(t, 16, 16) == 0);                              // 1 x 1 maps at stride 16: one run of 32
+    check_plan_rule(t, 1, nullptr);
+    EXPECT(y355_train_wgrad_plan(t, 10, 5, p) == 0 && p[0] == 5 && p[2] == 1 && p[3] == 32);
+    train_free(t);
+    EXPECT(live.empty());
+    EXPECT(train_open(4096, 4096, 2, 5, 1024, host_mem(), &t) == 0 && t);     // 2^34 pixels do not fit the int32 answer
+    EXPECT(y355_train_wgrad_plan(t, 1, 1024, p) == Y355_TRAIN_EINVAL && g_text == "y355_train_wgrad_plan: more than 2^31 - 1 pixels");
+    check_plan_rule(t, 127, nullptr);                                         // the largest that does
+    train_free(t);
+}
+
 int main() {
     check_rules();
+    check_plans();
     const int n = check_all_or_none(64, 96, 2, 5, 2);
     check_all_or_none(32, 16, 20, 5, 1);
     check_refusals_and_sizes();

@@ -96,8 +96,21 @@ def forward(ws, x, contract):
     return A, I, conv(A[-1], rnd(w), b)
 
 
-def backward(ws, A, I, dP, contract):
-    """-> ([(dW_k, db_k)] for k = 1..10, {k: G_k})"""
+def undecided_sides(A_lo, A_hi):
+    """int64 [n, 3] = (t, flat index into A_t, 1 where A_lo took the positive side): the elements of A_1..A_9 at which two
+    forwards of one input (fp32 and float64) lie on different sides of the LeakyReLU, whose pre-activation fp32 cannot tell
+    from zero.  There the gradient jumps by a factor of 8 and the side an fp32 forward takes is rounding noise."""
+    rows = []
+    for t in range(1, 10):
+        lo, hi = (A_lo[t] > 0).reshape(-1), (A_hi[t] > 0).reshape(-1)
+        for i in torch.nonzero(lo != hi).reshape(-1).tolist():
+            rows.append((t, i, int(lo[i])))
+    return np.array(rows, np.int64).reshape(-1, 3)
+
+
+def backward(ws, A, I, dP, contract, sides=None):
+    """-> ([(dW_k, db_k)] for k = 1..10, {k: G_k}).  sides: rows of undecided_sides; the slope of those elements is taken
+    from the row, not from the sign of A."""
     rnd = rb32 if contract else (lambda t: t)
     G = {10: rnd(dP)}
     grads = [None] * 10
@@ -105,7 +118,11 @@ def backward(ws, A, I, dP, contract):
         grads[k - 1] = wgrad(G[k], A[k - 1])
         if k == 1:
             break
-        D = dgrad(G[k], rnd(ws[k - 1][0])) * slope_mask(A[k - 1])
+        mask = slope_mask(A[k - 1])
+        for t, i, positive in ([] if sides is None else np.asarray(sides).reshape(-1, 3).tolist()):
+            if t == k - 1:
+                mask.view(-1)[i] = 1.0 if positive else SLOPE
+        D = dgrad(G[k], rnd(ws[k - 1][0])) * mask
         G[k - 1] = rnd(unpool(D, I[k - 1]) if TC.POOL[k - 2] else D)
     return grads, G
 
@@ -122,15 +139,15 @@ def targets(size, label_lists):
     return R.make_targets(size, TC.STRIDE, label_lists, TC.ANCHORS, False)
 
 
-def step(ws_np, x_np, target, size, C, contract):
-    """One forward + loss + backward.  contract=False: float64; True: the fp32 emulation.  Returns (losses float64 [4],
-    [(dW, db)] numpy float64, P numpy)."""
+def step(ws_np, x_np, target, size, C, contract, sides=None):
+    """One forward + loss + backward.  contract=False: float64; True: the fp32 emulation.  sides: see backward.  Returns
+    (losses float64 [4], [(dW, db)] numpy float64, P numpy)."""
     dt = torch.float32 if contract else torch.float64
     ws = [(torch.from_numpy(np.asarray(w)).to(dt), torch.from_numpy(np.asarray(b)).to(dt)) for w, b in ws_np]
     x = torch.from_numpy(np.asarray(x_np)).to(dt)
     A, I, P = forward(ws, x, contract)
     out, dP = loss_and_dpred(P, target, size, C)
-    grads, _ = backward(ws, A, I, torch.from_numpy(dP.astype(np.float32)).to(dt) if contract else torch.from_numpy(dP), contract)
+    grads, _ = backward(ws, A, I, torch.from_numpy(dP.astype(np.float32)).to(dt) if contract else torch.from_numpy(dP), contract, sides)
     return out, [(dw.double().numpy(), db.double().numpy()) for dw, db in grads], P.double().numpy()
 
 

@@ -437,6 +437,22 @@ static int wgrad_tiles(const LayerDesc &L) { return ((L.cinp + 15) / 16) * ((L.c
 static int wgrad_max_runs(const LayerDesc &L) { return std::max(1, 2048 / wgrad_tiles(L)); }       // about 2048 waves per layer
 static size_t wgrad_stride(const LayerDesc &L) { return (size_t)L.cout * L.cinp * 9 + L.cout; }
 
+// The split of a layer's npix = B H W pixels into runs of chunk pixels (a multiple of 32; the last run may be shorter): at most
+// wgrad_max_runs(L) of them.  y355_train_backward launches from it and y355_train_wgrad_plan reports it.
+struct WgradPlan {
+    size_t npix, chunk;
+    int max_runs, runs;
+};
+static WgradPlan wgrad_plan(const LayerDesc &L, int B, int H, int W) {
+    WgradPlan p;
+    p.npix = (size_t)B * H * W;
+    p.max_runs = wgrad_max_runs(L);
+    const size_t want = std::min<size_t>((size_t)p.max_runs, (p.npix + 31) / 32);
+    p.chunk = ((p.npix + want - 1) / want + 31) / 32 * 32;
+    p.runs = (int)((p.npix + p.chunk - 1) / p.chunk);
+    return p;
+}
+
 // y355_train_create in two parts, as train_host_check.cpp runs them on the CPU: the rules and the host state (no device
 // call), ...
 int train_open(int max_h, int max_w, int num_classes, int num_anchors, int max_batch, const DevMem &mem, y355_train **out) {
@@ -743,10 +759,10 @@ int y355_train_backward(y355_train *h, const void *dpred_dev, void *stream) {
         wa.act = h->act[k - 1];
         wa.ws = h->ws;
         wa.ws_stride = wgrad_stride(L);
-        wa.npix = (size_t)B * H * W;
-        int runs = (int)std::min<size_t>((size_t)wgrad_max_runs(L), (wa.npix + 31) / 32);
-        wa.chunk = ((wa.npix + runs - 1) / runs + 31) / 32 * 32;
-        runs = (int)((wa.npix + wa.chunk - 1) / wa.chunk);
+        const WgradPlan plan = wgrad_plan(L, B, H, W);
+        const int runs = plan.runs;
+        wa.npix = plan.npix;
+        wa.chunk = plan.chunk;
         wa.H = H;
         wa.W = W;
         wa.cinp = L.cinp;
@@ -783,6 +799,19 @@ int y355_train_backward(y355_train *h, const void *dpred_dev, void *stream) {
         }
     }
     h->have_grad = true;
+    return Y355_TRAIN_OK;
+}
+
+int y355_train_wgrad_plan(const y355_train *h, int32_t k, int32_t batch, int32_t *out) {
+    if (int rc = layer_arg("y355_train_wgrad_plan", h, k)) return rc;
+    if (!out) return y355_fail(Y355_TRAIN_EINVAL, "y355_train_wgrad_plan: null argument");
+    if (batch < 1 || batch > h->max_batch) return y355_fail(Y355_TRAIN_EINVAL, "y355_train_wgrad_plan: batch must be 1..max_batch");
+    const WgradPlan p = wgrad_plan(h->d.L[k - 1], batch, h->H / kDiv[k - 1], h->W / kDiv[k - 1]);
+    if (p.npix > (size_t)INT32_MAX) return y355_fail(Y355_TRAIN_EINVAL, "y355_train_wgrad_plan: more than 2^31 - 1 pixels");
+    out[0] = (int32_t)p.npix;
+    out[1] = p.max_runs;
+    out[2] = p.runs;
+    out[3] = (int32_t)p.chunk;
     return Y355_TRAIN_OK;
 }
 

@@ -32,6 +32,7 @@ _SIGS = {
     "y355_train_get_grad": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "y355_train_get_momentum": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_void_p]),
     "y355_train_get_packed": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p]),
+    "y355_train_wgrad_plan": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(C.c_int32)]),
     "y355_train_sgd_step": (C.c_int, [C.c_void_p, C.c_float, C.c_float, C.c_float, C.c_void_p]),
     "y355_train_tensor_shape": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, P(C.c_int32)]),
     "y355_train_get_tensor": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_void_p]),
@@ -190,6 +191,18 @@ class SlimTrainer(Handle):
         d = dpred.detach().to(device=self.device, dtype=torch.float32).contiguous()
         check(self._lib.y355_train_backward(self._h, d.data_ptr(), self._stream()))
         self._held_d = d
+
+    def wgrad_plan(self, k, batch=None):
+        """How the backward splits layer k's weight gradient at the current size: dict(npix, max_runs, runs, chunk) -- runs
+        workgroup runs of chunk pixels each, the last one the rest (y355_train_wgrad_plan, what the backward itself launches
+        from).  batch: None for that of the last forward."""
+        if batch is None:
+            if self._batch == 0:
+                raise RuntimeError("no forward pass has run at this size")
+            batch = self._batch
+        s = (C.c_int32 * 4)()
+        check(self._lib.y355_train_wgrad_plan(self._h, int(k), int(batch), s))
+        return dict(npix=int(s[0]), max_runs=int(s[1]), runs=int(s[2]), chunk=int(s[3]))
 
     def forward_backward(self, images, label_lists=None, target=None):
         """One forward, the loss and the backward pass -> (conf_loss, cls_loss, txtytwth_loss, total_loss) as tools.loss returns

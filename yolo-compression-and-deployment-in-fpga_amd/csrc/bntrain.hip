@@ -15,6 +15,11 @@
 //   bn_apply_kernel            G_k = rb((dY - m1 - xhat m2) (gamma invstd))
 // before the unchanged weight-gradient and reduce kernels.  bn_sgd_kernel is train_sgd_kernel's update on gamma and beta.
 // No atomics anywhere: the same bits from run to run.
+//
+// The handle's common state, the create rules, the common device memory, the bodies of the entry points yolo355_train.h has
+// too and the convolutions' launches are train_host.h's (train.hip compiles it too).  This file owns the BatchNorm kernels,
+// state, memory and entry points, the reductions' plan, and the two passes' loops with the BatchNorm launches between
+// train_host.h's.
 #include "../../include/yolo355_bntrain.h"
 #pragma GCC visibility push(hidden)
 #include "y355_host.h"
@@ -30,8 +35,11 @@ int y355_fail(int code, const std::string &msg) {
 }
 #endif
 
+#define TRAIN_FAMILY "y355_bntrain"
 #include "train_core.h"
+#include "train_host.h"
 static_assert(NL == Y355_BNTRAIN_LAYERS, "train_core.h's layer table");
+static_assert(Y355_BNTRAIN_ACT == T_ACT && Y355_BNTRAIN_IDX == T_IDX && Y355_BNTRAIN_GRAD == T_GRAD, "train_host.h's tensor kinds");
 constexpr int NBN = Y355_BNTRAIN_BN_LAYERS;
 constexpr int STAT_MAX_RUNS = 1024, STAT_ALIGN = 128;    // a workgroup of 256 lanes takes 8 (256 channels) to 128 (16) pixels a step
 
@@ -278,37 +286,20 @@ __global__ __launch_bounds__(256) void bn_sgd_kernel(size_t n, float *__restrict
 }
 
 // ---------------------------------------------------------------------------------------------------------- the handle
-struct y355_bntrain {
-    DevOwner own;
-    int device_id = 0;
-    int max_h = 0, max_w = 0, max_batch = 0, num_classes = 0, num_anchors = 0;
-    int H = 0, W = 0;
-    int batch = 0;                   // of the last forward at this size (0: none)
-    bool have_stats = false;         // a forward since create (batch statistics exist, whatever the size)
-    bool have_grad = false;          // a backward since the last forward
-    long long steps = 0;
-    long long nbt[NBN] = {};         // num_batches_tracked
-    NetDesc d;
-    size_t coff[NBN] = {}, cs = 0;   // of a layer's channels in the per-channel arrays; their sum
-    size_t pack_total = 0, ws_total = 0;
-    float *p = nullptr, *g = nullptr, *m = nullptr;
+struct BnDev {                       // BatchNorm's device memory, the owner's too: bntrain_buffers resets it in one assignment
     float *bnp = nullptr, *bng = nullptr, *bnm = nullptr;      // [gamma | beta], each cs
     float *rstat = nullptr;          // [running_mean | running_var]
     float *bstat = nullptr;          // [mean | var | invstd] of the last forward
     float *coef = nullptr;           // [m1 | m2 | gamma invstd] of the last backward
     double *sws = nullptr;           // the reductions' partials
-    bf16_t *packs = nullptr;
-    bf16_t *act[NL] = {};            // A_0 .. A_9
-    unsigned char *idx[NL] = {};     // I_t, t = 1, 2, 4, 6 (index t)
     bf16_t *z[NL] = {};              // Z_1 .. Z_9 (index k)
     bf16_t *dy[NL] = {};             // dY_1 .. dY_9 (index k)
-    bf16_t *grad[NL + 1] = {};       // G_1 .. G_10 (index k)
-    float *pred = nullptr, *ws = nullptr;
 };
-
-// channels and grid divisor of A_t
-static int act_c(const y355_bntrain *h, int t) { return t == 0 ? 8 : h->d.L[t - 1].cout; }
-static int act_div(int t) { return t == 0 ? 1 : kDiv[t - 1] * (kPool[t - 1] ? 2 : 1); }
+struct y355_bntrain : TrainCore, BnDev {
+    bool have_stats = false;         // a forward since create (batch statistics exist, whatever the size)
+    long long nbt[NBN] = {};         // num_batches_tracked
+    size_t coff[NBN] = {}, cs = 0;   // of a layer's channels in the per-channel arrays; their sum
+};
 
 // The split of a BatchNorm layer's N = B h w pixels into runs of chunk pixels (a multiple of STAT_ALIGN; the last run may be
 // shorter), at most STAT_MAX_RUNS of them: of the batch and the layer's grid alone.  Forward and backward launch from it and
@@ -326,220 +317,53 @@ static StatsPlan stats_plan(int B, int H, int W) {
     return p;
 }
 
-// y355_bntrain_create in two parts, as bntrain_host_check.cpp runs them on the CPU: the rules and the host state (no device
-// call), ...
+// The seams of bntrain_host_check.cpp, which does not see the struct.  y355_bntrain_create in two parts: train_host.h's rules
+// and host state with the per-channel offsets on top, ...
 int bntrain_open(int max_h, int max_w, int num_classes, int num_anchors, int max_batch, const DevMem &mem, y355_bntrain **out) {
-    if (!out) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_create: null argument");
-    *out = nullptr;
-    if (max_h < 16 || max_w < 16 || max_h % 16 || max_w % 16 || max_h > 4096 || max_w > 4096)
-        return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_create: max_h and max_w must be multiples of 16 in 16..4096");
-    if (num_classes < 1 || num_classes > 200) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_create: num_classes must be 1..200");
-    if (num_anchors < 1 || num_anchors > 16) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_create: num_anchors must be 1..16");
-    if (max_batch < 1 || max_batch > 1024) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_create: max_batch must be 1..1024");
-    y355_bntrain *h = new y355_bntrain;
-    h->own = DevOwner{mem, {}};
-    h->max_h = h->H = max_h;
-    h->max_w = h->W = max_w;
-    h->max_batch = max_batch;
-    h->num_classes = num_classes;
-    h->num_anchors = num_anchors;
-    size_t off = 0, poff = 0;
-    for (int k = 0; k < NL; ++k) {
-        LayerDesc &L = h->d.L[k];
-        L.cin = kCin[k];
-        L.cinp = k == 0 ? 8 : kCin[k];
-        L.cout = k == NL - 1 ? num_anchors * (5 + num_classes) : kCout[k];
-        L.coutp = k == NL - 1 ? pow2_at_least(L.cout, 32) : L.cout;
-        L.ct = tiles_per_wave(L.cout);
-        L.ksf = (9 * L.cinp + 31) / 32;
-        L.ksd = 9 * L.coutp / 32;
-        L.dct = tiles_per_wave(L.cin);
-        L.woff = off;
-        off += (size_t)L.cout * L.cin * 9;
-        L.boff = off;
-        off += L.cout;
-        const int tf = ((L.cout + 15) / 16 + L.ct - 1) / L.ct * L.ct;
-        L.wf_off = poff;
-        poff += (size_t)tf * L.ksf * 512;
-        L.wd_off = poff;
-        if (k > 0) poff += (size_t)(L.cin / 16) * L.ksd * 512;
-        h->ws_total = std::max(h->ws_total, (size_t)wgrad_max_runs(L) * wgrad_stride(L));
-        if (k < NBN) {
-            h->coff[k] = h->cs;
-            h->cs += L.cout;
-        }
+    if (int rc = core_open(max_h, max_w, num_classes, num_anchors, max_batch, mem, out)) return rc;
+    y355_bntrain *h = *out;
+    for (int k = 0; k < NBN; ++k) {
+        h->coff[k] = h->cs;
+        h->cs += h->d.L[k].cout;
     }
-    h->d.total = off;
-    h->pack_total = poff;
-    *out = h;
     return Y355_BNTRAIN_OK;
 }
-// ... and all of its device memory (on the current device) with BatchNorm2d's initial values, or none of it
+// ... and all of its device memory (on the current device) with BatchNorm2d's initial values, or none of it: the per-channel
+// arrays and the partials follow the parameters, Z_k and dY_k follow G_k
 int bntrain_buffers(y355_bntrain *h) {
     DevOwner &o = h->own;
     const size_t mark = y355_dev_mark(o);
-    const size_t B = h->max_batch;
-    int rc = y355_dev_get_all<true>(o, h->d.total, &h->p, &h->g, &h->m);
-    rc = rc ? rc : y355_dev_get_all<true>(o, 2 * h->cs, &h->bnp, &h->bng, &h->bnm);
-    rc = rc ? rc : y355_dev_get_all<true>(o, 2 * h->cs, &h->rstat);
-    rc = rc ? rc : y355_dev_get_all<true>(o, 3 * h->cs, &h->bstat, &h->coef);
-    rc = rc ? rc : y355_dev_get(o, &h->sws, (size_t)STAT_MAX_RUNS * 2 * 256, true);
-    rc = rc ? rc : y355_dev_get(o, &h->packs, h->pack_total, true);
-    rc = rc ? rc : y355_dev_get(o, &h->ws, h->ws_total, true);
-    for (int t = 0; t < NL && !rc; ++t) {
-        const size_t n = B * (h->max_h / act_div(t)) * (h->max_w / act_div(t)) * act_c(h, t);
-        rc = y355_dev_get(o, &h->act[t], n, true);
-        if (!rc && t >= 1 && kPool[t - 1]) rc = y355_dev_get(o, &h->idx[t], n, true);
-    }
-    for (int k = 1; k <= NL && !rc; ++k) {
-        const size_t n = B * (h->max_h / kDiv[k - 1]) * (h->max_w / kDiv[k - 1]) * h->d.L[k - 1].coutp;
-        rc = y355_dev_get(o, &h->grad[k], n, true);
-        if (k <= NBN) {
-            rc = rc ? rc : y355_dev_get(o, &h->z[k], n, true);
-            rc = rc ? rc : y355_dev_get(o, &h->dy[k], n, true);
-        }
-    }
-    rc = rc ? rc : y355_dev_get(o, &h->pred, B * h->d.L[NL - 1].cout * (h->max_h / 16) * (h->max_w / 16), true);
+    int rc = core_buffers(
+        h,
+        [&] {
+            int r = y355_dev_get_all<true>(o, 2 * h->cs, &h->bnp, &h->bng, &h->bnm);
+            r = r ? r : y355_dev_get_all<true>(o, 2 * h->cs, &h->rstat);
+            r = r ? r : y355_dev_get_all<true>(o, 3 * h->cs, &h->bstat, &h->coef);
+            return r ? r : y355_dev_get(o, &h->sws, (size_t)STAT_MAX_RUNS * 2 * 256, true);
+        },
+        [&](int k, size_t n) {
+            if (k > NBN) return 0;
+            const int r = y355_dev_get(o, &h->z[k], n, true);
+            return r ? r : y355_dev_get(o, &h->dy[k], n, true);
+        });
     if (!rc) {                                                // gamma = 1, running_var = 1
         const std::vector<float> ones(h->cs, 1.0f);
         rc = o.mem.upload(h->bnp, ones.data(), h->cs * sizeof(float), nullptr);
         rc = rc ? rc : o.mem.upload(h->rstat + h->cs, ones.data(), h->cs * sizeof(float), nullptr);
+        if (rc) core_rollback(h, mark);
     }
-    if (rc) {
-        y355_dev_rollback(o, mark);
-        h->p = h->g = h->m = h->bnp = h->bng = h->bnm = h->rstat = h->bstat = h->coef = h->ws = h->pred = nullptr;
-        h->sws = nullptr;
-        h->packs = nullptr;
-        for (int t = 0; t < NL; ++t) {
-            h->act[t] = nullptr;
-            h->idx[t] = nullptr;
-            h->z[t] = nullptr;
-            h->dy[t] = nullptr;
-            h->grad[t + 1] = nullptr;
-        }
-    }
+    if (rc) static_cast<BnDev &>(*h) = BnDev{};
     return rc;
 }
-DevOwner &bntrain_owner(y355_bntrain *h) { return h->own; }  // (bntrain_host_check.cpp does not see the struct)
-void bntrain_free(y355_bntrain *h) {
-    y355_dev_release_all(h->own);
-    delete h;
-}
-void bntrain_state(const y355_bntrain *h, int *hw_batch) {   // H, W, batch of the last forward, have_grad: for the host check
-    hw_batch[0] = h->H;
-    hw_batch[1] = h->W;
-    hw_batch[2] = h->batch;
-    hw_batch[3] = h->have_grad ? 1 : 0;
-}
+DevOwner &bntrain_owner(y355_bntrain *h) { return h->own; }
+void bntrain_free(y355_bntrain *h) { core_free(h); }
+void bntrain_state(const y355_bntrain *h, int *hw_batch) { core_state(h, hw_batch); }
 
-static int layer_arg(const char *who, const y355_bntrain *h, int k, int last = NL) {
-    if (!h) return y355_fail(Y355_BNTRAIN_EINVAL, std::string(who) + ": null handle");
-    if (k < 1 || k > last) return y355_fail(Y355_BNTRAIN_EINVAL, std::string(who) + (last == NL ? ": layer index must be 1..10" : ": layer index must be 1..9"));
-    return 0;
-}
-
-static hipError_t launch_pack(y355_bntrain *h, float lr, float momentum, float wd, int first, int update, hipStream_t s) {
-    hipLaunchKernelGGL(train_sgd_kernel, dim3((unsigned)((h->d.total + 255) / 256)), dim3(256), 0, s, h->d, h->p, h->g, h->m, h->packs, lr, momentum,
-                       wd, first, update);
-    return hipGetLastError();
-}
-
-// [B, h, w, c] of a tensor at the current size; false on a kind / index that does not exist
-static bool tensor_dims(const y355_bntrain *h, int kind, int t, int *shape) {
-    int div, c;
-    if (kind == Y355_BNTRAIN_ACT && t >= 0 && t <= 9) {
-        div = act_div(t);
-        c = act_c(h, t);
-    } else if (kind == Y355_BNTRAIN_IDX && t >= 1 && t <= 9 && kPool[t - 1]) {
-        div = act_div(t);
-        c = act_c(h, t);
-    } else if (kind == Y355_BNTRAIN_GRAD && t >= 1 && t <= NL) {
-        div = kDiv[t - 1];
-        c = h->d.L[t - 1].coutp;
-    } else if ((kind == Y355_BNTRAIN_Z || kind == Y355_BNTRAIN_DY) && t >= 1 && t <= NBN) {
-        div = kDiv[t - 1];
-        c = h->d.L[t - 1].cout;
-    } else {
-        return false;
-    }
-    shape[0] = h->batch;
-    shape[1] = h->H / div;
-    shape[2] = h->W / div;
-    shape[3] = c;
-    return true;
-}
-#pragma GCC visibility pop
-
-// ---------------------------------------------------------------------------------------------------------- C ABI
-extern "C" {
-
-const char *y355_bntrain_last_error(void) { return g_err.c_str(); }
-
-int y355_bntrain_create(int32_t max_h, int32_t max_w, int32_t num_classes, int32_t num_anchors, int32_t max_batch, y355_bntrain **out) {
-    if (int rc = bntrain_open(max_h, max_w, num_classes, num_anchors, max_batch, y355_hip_mem(), out)) return rc;
-    int dev = 0;
-    const hipError_t e = hipGetDevice(&dev);
-    (*out)->device_id = dev;
-    const int rc = e != hipSuccess ? y355_fail(Y355_BNTRAIN_EHIP, std::string("y355_bntrain_create: ") + hipGetErrorString(e)) : bntrain_buffers(*out);
-    if (rc) {
-        bntrain_free(*out);
-        *out = nullptr;
-    }
-    return rc;
-}
-
-void y355_bntrain_destroy(y355_bntrain *h) {
-    if (!h) return;
-    DeviceGuard g;
-    (void)g.set(h->device_id);
-    bntrain_free(h);
-}
-
-int y355_bntrain_set_size(y355_bntrain *h, int32_t height, int32_t width) {
-    if (!h) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_set_size: null handle");
-    if (height < 16 || width < 16 || height % 16 || width % 16)
-        return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_set_size: height and width must be multiples of 16");
-    if (height > h->max_h || width > h->max_w) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_set_size: size beyond the handle's maximum");
-    if (height != h->H || width != h->W) {
-        h->H = height;
-        h->W = width;
-        h->batch = 0;                                         // the stored tensors are of another size
-        h->have_grad = false;
-    }
-    return Y355_BNTRAIN_OK;
-}
-
-int y355_bntrain_layer_shape(const y355_bntrain *h, int32_t k, int32_t *shape) {
-    if (int rc = layer_arg("y355_bntrain_layer_shape", h, k)) return rc;
-    if (!shape) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_layer_shape: null argument");
-    shape[0] = h->d.L[k - 1].cout;
-    shape[1] = h->d.L[k - 1].cin;
-    return Y355_BNTRAIN_OK;
-}
-
-int y355_bntrain_load_layer(y355_bntrain *h, int32_t k, const float *w, const float *b) {
-    if (int rc = layer_arg("y355_bntrain_load_layer", h, k)) return rc;
-    if (!w || !b) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_load_layer: null argument");
-    const LayerDesc &L = h->d.L[k - 1];
-    DeviceGuard g;
-    HIPCHK(g.set(h->device_id));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(h->p + L.woff, w, (size_t)L.cout * L.cin * 9 * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(hipMemcpy(h->p + L.boff, b, (size_t)L.cout * sizeof(float), hipMemcpyHostToDevice));
-    HIPCHK(launch_pack(h, 0.f, 0.f, 0.f, 0, 0, nullptr));
-    HIPCHK(hipStreamSynchronize(nullptr));
-    return Y355_BNTRAIN_OK;
-}
-
-static int get_pair(const char *who, y355_bntrain *h, int k, const float *src, float *w, float *b) {
-    if (int rc = layer_arg(who, h, k)) return rc;
-    const LayerDesc &L = h->d.L[k - 1];
-    DeviceGuard g;
-    HIPCHK(g.set(h->device_id));
-    HIPCHK(hipDeviceSynchronize());
-    if (w) HIPCHK(hipMemcpy(w, src + L.woff, (size_t)L.cout * L.cin * 9 * sizeof(float), hipMemcpyDeviceToHost));
-    if (b) HIPCHK(hipMemcpy(b, src + L.boff, (size_t)L.cout * sizeof(float), hipMemcpyDeviceToHost));
-    return Y355_BNTRAIN_OK;
+// Z_t and dY_t, t = 1..9: the tensor kinds yolo355_train.h does not have
+static OwnTensor bn_tensor(const TrainCore *hc, int kind, int t) {
+    const y355_bntrain *h = static_cast<const y355_bntrain *>(hc);
+    if ((kind != Y355_BNTRAIN_Z && kind != Y355_BNTRAIN_DY) || t < 1 || t > NBN) return OwnTensor{nullptr, 0, false};
+    return kind == Y355_BNTRAIN_Z ? OwnTensor{h->z[t], h->d.L[t - 1].cout, false} : OwnTensor{h->dy[t], h->d.L[t - 1].cout, true};
 }
 
 // n per-channel arrays of layer k, the i-th at src + i * stride + coff, to the host pointers that are not null
@@ -553,16 +377,137 @@ static int get_channels(y355_bntrain *h, int k, const float *src, size_t stride,
     return Y355_BNTRAIN_OK;
 }
 
-int y355_bntrain_get_layer(y355_bntrain *h, int32_t k, float *w, float *b) { return get_pair("y355_bntrain_get_layer", h, k, h ? h->p : nullptr, w, b); }
-
-int y355_bntrain_get_grad(y355_bntrain *h, int32_t k, float *dw, float *db) {
-    if (int rc = layer_arg("y355_bntrain_get_grad", h, k)) return rc;
-    if (!h->have_grad) return y355_fail(Y355_BNTRAIN_ENOTREADY, "y355_bntrain_get_grad: no backward pass has run");
-    return get_pair("y355_bntrain_get_grad", h, k, h->g, dw, db);
+// BatchNorm of layer k = 1..9 in the forward, Z_k -> A_k (and I_k): the batch statistics, the running ones, the normalisation
+static int bn_forward(y355_bntrain *h, int k, int batch, hipStream_t s) {
+    const LayerDesc &L = h->d.L[k - 1];
+    const int H = h->H / kDiv[k - 1], W = h->W / kDiv[k - 1];
+    const size_t off = h->coff[k - 1], cs = h->cs;
+    const int cgl = ilog2_(L.cout / 8);
+    const StatsPlan plan = stats_plan(batch, H, W);
+    StatArgs sa{};
+    sa.z = h->z[k];
+    sa.ws = h->sws;
+    sa.N = plan.N;
+    sa.chunk = plan.chunk;
+    sa.C = L.cout;
+    sa.cg_log2 = cgl;
+    hipLaunchKernelGGL((bn_stats_kernel<false>), dim3((unsigned)plan.runs), dim3(256), 0, s, sa);
+    HIPCHK(hipGetLastError());
+    FinArgs fa{};
+    fa.ws = h->sws;
+    fa.runs = plan.runs;
+    fa.C = L.cout;
+    fa.N = (double)plan.N;
+    fa.mean = h->bstat + off;
+    fa.var = h->bstat + cs + off;
+    fa.invstd = h->bstat + 2 * cs + off;
+    fa.rmean = h->rstat + off;
+    fa.rvar = h->rstat + cs + off;
+    hipLaunchKernelGGL((bn_finalise_kernel<false>), dim3((unsigned)((L.cout + 255) / 256)), dim3(256), 0, s, fa);
+    HIPCHK(hipGetLastError());
+    ++h->nbt[k - 1];
+    NormArgs na{};
+    na.z = h->z[k];
+    na.mean = fa.mean;
+    na.invstd = fa.invstd;
+    na.gamma = h->bnp + off;
+    na.beta = h->bnp + cs + off;
+    na.out = h->act[k];
+    na.H = H;
+    na.W = W;
+    na.C = L.cout;
+    na.cg_log2 = cgl;
+    if (kPool[k - 1]) {
+        na.idx = h->idx[k];
+        na.nout = plan.N / 4;
+        hipLaunchKernelGGL((bn_norm_kernel<true>), dim3((unsigned)(((na.nout << cgl) + 255) / 256)), dim3(256), 0, s, na);
+    } else {
+        na.nout = plan.N;
+        hipLaunchKernelGGL((bn_norm_kernel<false>), dim3((unsigned)(((na.nout << cgl) + 255) / 256)), dim3(256), 0, s, na);
+    }
+    HIPCHK(hipGetLastError());
+    h->have_stats = true;
+    return Y355_BNTRAIN_OK;
 }
 
-int y355_bntrain_get_momentum(y355_bntrain *h, int32_t k, float *mw, float *mb) {
-    return get_pair("y355_bntrain_get_momentum", h, k, h ? h->m : nullptr, mw, mb);
+// ... and in the backward, dY_k -> dgamma_k, dbeta_k, G_k
+static int bn_backward(y355_bntrain *h, int k, hipStream_t s) {
+    const LayerDesc &L = h->d.L[k - 1];
+    const size_t off = h->coff[k - 1], cs = h->cs;
+    const int cgl = ilog2_(L.cout / 8);
+    const StatsPlan plan = stats_plan(h->batch, h->H / kDiv[k - 1], h->W / kDiv[k - 1]);
+    StatArgs sa{};
+    sa.z = h->z[k];
+    sa.dy = h->dy[k];
+    sa.mean = h->bstat + off;
+    sa.invstd = h->bstat + 2 * cs + off;
+    sa.ws = h->sws;
+    sa.N = plan.N;
+    sa.chunk = plan.chunk;
+    sa.C = L.cout;
+    sa.cg_log2 = cgl;
+    hipLaunchKernelGGL((bn_stats_kernel<true>), dim3((unsigned)plan.runs), dim3(256), 0, s, sa);
+    HIPCHK(hipGetLastError());
+    FinArgs fa{};
+    fa.ws = h->sws;
+    fa.runs = plan.runs;
+    fa.C = L.cout;
+    fa.N = (double)plan.N;
+    fa.Nf = (float)plan.N;
+    fa.invstd = h->bstat + 2 * cs + off;
+    fa.gamma = h->bnp + off;
+    fa.dgamma = h->bng + off;
+    fa.dbeta = h->bng + cs + off;
+    fa.m1 = h->coef + off;
+    fa.m2 = h->coef + cs + off;
+    fa.gs = h->coef + 2 * cs + off;
+    hipLaunchKernelGGL((bn_finalise_kernel<true>), dim3((unsigned)((L.cout + 255) / 256)), dim3(256), 0, s, fa);
+    HIPCHK(hipGetLastError());
+    ApplyArgs aa{};
+    aa.dy = h->dy[k];
+    aa.z = h->z[k];
+    aa.mean = sa.mean;
+    aa.invstd = sa.invstd;
+    aa.m1 = fa.m1;
+    aa.m2 = fa.m2;
+    aa.gs = fa.gs;
+    aa.out = h->grad[k];
+    aa.N = plan.N;
+    aa.C = L.cout;
+    aa.cg_log2 = cgl;
+    hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)(((plan.N << cgl) + 255) / 256)), dim3(256), 0, s, aa);
+    HIPCHK(hipGetLastError());
+    return Y355_BNTRAIN_OK;
+}
+#pragma GCC visibility pop
+
+// ---------------------------------------------------------------------------------------------------------- C ABI
+extern "C" {
+
+const char *y355_bntrain_last_error(void) { return g_err.c_str(); }
+
+// what yolo355_train.h has too: train_host.h's bodies
+int y355_bntrain_create(int32_t max_h, int32_t max_w, int32_t num_classes, int32_t num_anchors, int32_t max_batch, y355_bntrain **out) {
+    return core_create(max_h, max_w, num_classes, num_anchors, max_batch, out, bntrain_open, bntrain_buffers);
+}
+void y355_bntrain_destroy(y355_bntrain *h) { core_destroy(h); }
+int y355_bntrain_set_size(y355_bntrain *h, int32_t height, int32_t width) { return core_set_size(h, height, width); }
+int y355_bntrain_layer_shape(const y355_bntrain *h, int32_t k, int32_t *shape) { return core_layer_shape(h, k, shape); }
+int y355_bntrain_load_layer(y355_bntrain *h, int32_t k, const float *w, const float *b) { return core_load_layer(h, k, w, b); }
+int y355_bntrain_get_layer(y355_bntrain *h, int32_t k, float *w, float *b) { return core_get_layer(h, k, w, b); }
+int y355_bntrain_get_grad(y355_bntrain *h, int32_t k, float *dw, float *db) { return core_get_grad(h, k, dw, db); }
+int y355_bntrain_get_momentum(y355_bntrain *h, int32_t k, float *mw, float *mb) { return core_get_momentum(h, k, mw, mb); }
+int y355_bntrain_get_packed(y355_bntrain *h, int32_t k, uint16_t *w_bf16) { return core_get_packed(h, k, w_bf16); }
+int y355_bntrain_pred(y355_bntrain *h, void **out) { return core_pred(h, out); }
+int y355_bntrain_wgrad_plan(const y355_bntrain *h, int32_t k, int32_t batch, int32_t *out) { return core_wgrad_plan(h, k, batch, out); }
+int y355_bntrain_tensor_shape(const y355_bntrain *h, int32_t kind, int32_t t, int32_t *shape) { return core_tensor_shape(h, kind, t, shape, bn_tensor); }
+int y355_bntrain_get_tensor(y355_bntrain *h, int32_t kind, int32_t t, void *out) { return core_get_tensor(h, kind, t, out, bn_tensor); }
+int y355_bntrain_sgd_step(y355_bntrain *h, float lr, float momentum, float weight_decay, void *stream) {
+    return core_sgd_step(h, lr, momentum, weight_decay, stream, [=](int first) {      // gamma and beta of every layer
+        hipLaunchKernelGGL(bn_sgd_kernel, dim3((unsigned)((2 * h->cs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, 2 * h->cs, h->bnp, h->bng, h->bnm, lr,
+                           momentum, weight_decay, first);
+        return hipGetLastError();
+    });
 }
 
 int y355_bntrain_load_bn(y355_bntrain *h, int32_t k, const float *gamma, const float *beta, const float *running_mean, const float *running_var,
@@ -611,243 +556,6 @@ int y355_bntrain_get_batch_stats(y355_bntrain *h, int32_t k, float *mean, float 
     return get_channels(h, k, h->bstat, h->cs, 3, d);
 }
 
-int y355_bntrain_get_packed(y355_bntrain *h, int32_t k, uint16_t *w_bf16) {
-    if (int rc = layer_arg("y355_bntrain_get_packed", h, k)) return rc;
-    if (!w_bf16) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_get_packed: null argument");
-    const LayerDesc &L = h->d.L[k - 1];
-    const int tf = ((L.cout + 15) / 16 + L.ct - 1) / L.ct * L.ct;
-    std::vector<bf16_t> pk((size_t)tf * L.ksf * 512);
-    DeviceGuard g;
-    HIPCHK(g.set(h->device_id));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(pk.data(), h->packs + L.wf_off, pk.size() * sizeof(bf16_t), hipMemcpyDeviceToHost));
-    for (int co = 0; co < L.cout; ++co)
-        for (int ci = 0; ci < L.cin; ++ci)
-            for (int tap = 0; tap < 9; ++tap) {
-                const int kidx = tap * L.cinp + ci;
-                w_bf16[((size_t)co * L.cin + ci) * 9 + tap] =
-                    pk[((((size_t)(co >> 4) * L.ksf + (kidx >> 5)) * 64 + ((kidx >> 3) & 3) * 16 + (co & 15)) << 3) + (kidx & 7)];
-            }
-    return Y355_BNTRAIN_OK;
-}
-
-int y355_bntrain_forward(y355_bntrain *h, const void *x_dev, int32_t batch, void *stream) {
-    if (!h || !x_dev) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_forward: null argument");
-    if (batch < 1 || batch > h->max_batch) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_forward: batch must be 1..max_batch");
-    if ((long long)batch * (h->H / 16) * (h->W / 16) < 2)
-        return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_forward: BatchNorm in training mode needs more than one value per channel: batch * H/16 * W/16 >= 2");
-    hipStream_t s = (hipStream_t)stream;
-    DeviceGuard g;
-    HIPCHK(g.set(h->device_id));
-    h->batch = 0;
-    h->have_grad = false;
-    const size_t npix = (size_t)batch * h->H * h->W;
-    hipLaunchKernelGGL(train_input_kernel, dim3((unsigned)((npix + 255) / 256)), dim3(256), 0, s, (const float *)x_dev, h->act[0], npix,
-                       (size_t)h->H * h->W);
-    HIPCHK(hipGetLastError());
-    for (int k = 1; k <= NL; ++k) {
-        const LayerDesc &L = h->d.L[k - 1];
-        ConvArgs a{};
-        a.in = h->act[k - 1];
-        a.w = h->packs + L.wf_off;
-        a.bias = h->p + L.boff;
-        a.cinp_log2 = ilog2_(L.cinp);
-        a.ks = L.ksf;
-        a.B = batch;
-        a.H = h->H / kDiv[k - 1];
-        a.W = h->W / kDiv[k - 1];
-        a.cout = L.cout;
-        a.outc = L.cout;
-        const int tiles = (L.cout + 15) / 16;
-        if (k == NL) {
-            a.out = h->pred;
-            HIPCHK(launch_conv<M_PRED>(a, L.ct, tiles, s));
-            break;
-        }
-        a.out = h->z[k];
-        HIPCHK(launch_conv<M_Z>(a, L.ct, tiles, s));
-        const size_t off = h->coff[k - 1], cs = h->cs;
-        const int cgl = ilog2_(L.cout / 8);
-        const StatsPlan plan = stats_plan(batch, a.H, a.W);
-        StatArgs sa{};
-        sa.z = h->z[k];
-        sa.ws = h->sws;
-        sa.N = plan.N;
-        sa.chunk = plan.chunk;
-        sa.C = L.cout;
-        sa.cg_log2 = cgl;
-        hipLaunchKernelGGL((bn_stats_kernel<false>), dim3((unsigned)plan.runs), dim3(256), 0, s, sa);
-        HIPCHK(hipGetLastError());
-        FinArgs fa{};
-        fa.ws = h->sws;
-        fa.runs = plan.runs;
-        fa.C = L.cout;
-        fa.N = (double)plan.N;
-        fa.mean = h->bstat + off;
-        fa.var = h->bstat + cs + off;
-        fa.invstd = h->bstat + 2 * cs + off;
-        fa.rmean = h->rstat + off;
-        fa.rvar = h->rstat + cs + off;
-        hipLaunchKernelGGL((bn_finalise_kernel<false>), dim3((unsigned)((L.cout + 255) / 256)), dim3(256), 0, s, fa);
-        HIPCHK(hipGetLastError());
-        ++h->nbt[k - 1];
-        NormArgs na{};
-        na.z = h->z[k];
-        na.mean = fa.mean;
-        na.invstd = fa.invstd;
-        na.gamma = h->bnp + off;
-        na.beta = h->bnp + cs + off;
-        na.out = h->act[k];
-        na.H = a.H;
-        na.W = a.W;
-        na.C = L.cout;
-        na.cg_log2 = cgl;
-        if (kPool[k - 1]) {
-            na.idx = h->idx[k];
-            na.nout = plan.N / 4;
-            hipLaunchKernelGGL((bn_norm_kernel<true>), dim3((unsigned)(((na.nout << cgl) + 255) / 256)), dim3(256), 0, s, na);
-        } else {
-            na.nout = plan.N;
-            hipLaunchKernelGGL((bn_norm_kernel<false>), dim3((unsigned)(((na.nout << cgl) + 255) / 256)), dim3(256), 0, s, na);
-        }
-        HIPCHK(hipGetLastError());
-        h->have_stats = true;
-    }
-    h->batch = batch;
-    return Y355_BNTRAIN_OK;
-}
-
-int y355_bntrain_pred(y355_bntrain *h, void **out) {
-    if (!h || !out) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_pred: null argument");
-    *out = h->pred;
-    return Y355_BNTRAIN_OK;
-}
-
-int y355_bntrain_backward(y355_bntrain *h, const void *dpred_dev, void *stream) {
-    if (!h || !dpred_dev) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_backward: null argument");
-    if (h->batch == 0) return y355_fail(Y355_BNTRAIN_ENOTREADY, "y355_bntrain_backward: no forward pass has run at this size");
-    hipStream_t s = (hipStream_t)stream;
-    DeviceGuard g;
-    HIPCHK(g.set(h->device_id));
-    h->have_grad = false;
-    const int B = h->batch;
-    {
-        const LayerDesc &L = h->d.L[NL - 1];
-        const size_t hw = (size_t)(h->H / 16) * (h->W / 16), n = (size_t)B * hw * L.coutp;
-        hipLaunchKernelGGL(train_dpred_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float *)dpred_dev, h->grad[NL], n, L.cout,
-                           ilog2_(L.coutp), hw);
-        HIPCHK(hipGetLastError());
-    }
-    for (int k = NL; k >= 1; --k) {
-        const LayerDesc &L = h->d.L[k - 1];
-        const int H = h->H / kDiv[k - 1], W = h->W / kDiv[k - 1];
-        if (k <= NBN) {                                       // dY_k -> dgamma_k, dbeta_k, G_k
-            const size_t off = h->coff[k - 1], cs = h->cs;
-            const int cgl = ilog2_(L.cout / 8);
-            const StatsPlan plan = stats_plan(B, H, W);
-            StatArgs sa{};
-            sa.z = h->z[k];
-            sa.dy = h->dy[k];
-            sa.mean = h->bstat + off;
-            sa.invstd = h->bstat + 2 * cs + off;
-            sa.ws = h->sws;
-            sa.N = plan.N;
-            sa.chunk = plan.chunk;
-            sa.C = L.cout;
-            sa.cg_log2 = cgl;
-            hipLaunchKernelGGL((bn_stats_kernel<true>), dim3((unsigned)plan.runs), dim3(256), 0, s, sa);
-            HIPCHK(hipGetLastError());
-            FinArgs fa{};
-            fa.ws = h->sws;
-            fa.runs = plan.runs;
-            fa.C = L.cout;
-            fa.N = (double)plan.N;
-            fa.Nf = (float)plan.N;
-            fa.invstd = h->bstat + 2 * cs + off;
-            fa.gamma = h->bnp + off;
-            fa.dgamma = h->bng + off;
-            fa.dbeta = h->bng + cs + off;
-            fa.m1 = h->coef + off;
-            fa.m2 = h->coef + cs + off;
-            fa.gs = h->coef + 2 * cs + off;
-            hipLaunchKernelGGL((bn_finalise_kernel<true>), dim3((unsigned)((L.cout + 255) / 256)), dim3(256), 0, s, fa);
-            HIPCHK(hipGetLastError());
-            ApplyArgs aa{};
-            aa.dy = h->dy[k];
-            aa.z = h->z[k];
-            aa.mean = sa.mean;
-            aa.invstd = sa.invstd;
-            aa.m1 = fa.m1;
-            aa.m2 = fa.m2;
-            aa.gs = fa.gs;
-            aa.out = h->grad[k];
-            aa.N = plan.N;
-            aa.C = L.cout;
-            aa.cg_log2 = cgl;
-            hipLaunchKernelGGL(bn_apply_kernel, dim3((unsigned)(((plan.N << cgl) + 255) / 256)), dim3(256), 0, s, aa);
-            HIPCHK(hipGetLastError());
-        }
-        WgradArgs wa{};
-        wa.g = h->grad[k];
-        wa.act = h->act[k - 1];
-        wa.ws = h->ws;
-        wa.ws_stride = wgrad_stride(L);
-        const WgradPlan plan = wgrad_plan(L, B, H, W);
-        const int runs = plan.runs;
-        wa.npix = plan.npix;
-        wa.chunk = plan.chunk;
-        wa.H = H;
-        wa.W = W;
-        wa.cinp = L.cinp;
-        wa.coutp = L.coutp;
-        wa.cout = L.cout;
-        const int mt = wgrad_mt(L);
-        const dim3 grid((unsigned)((L.cinp + 15) / 16), (unsigned)((L.cout + 16 * mt - 1) / (16 * mt)), (unsigned)runs), block(64);
-        if (mt == 1) hipLaunchKernelGGL((train_wgrad_kernel<1>), grid, block, 0, s, wa);
-        else if (mt == 2) hipLaunchKernelGGL((train_wgrad_kernel<2>), grid, block, 0, s, wa);
-        else hipLaunchKernelGGL((train_wgrad_kernel<4>), grid, block, 0, s, wa);
-        HIPCHK(hipGetLastError());
-        const size_t n = (size_t)L.cout * L.cin * 9 + L.cout;
-        hipLaunchKernelGGL(train_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, h->ws, wa.ws_stride, runs, L.cin, L.cinp, L.cout,
-                           h->g + L.woff, h->g + L.boff);
-        HIPCHK(hipGetLastError());
-        if (k == 1) break;                                    // the gradient with respect to the image is not computed
-        ConvArgs a{};
-        a.in = h->grad[k];
-        a.w = h->packs + L.wd_off;
-        a.cinp_log2 = ilog2_(L.coutp);
-        a.ks = L.ksd;
-        a.B = B;
-        a.H = H;
-        a.W = W;
-        a.cout = L.cin;
-        a.outc = L.cin;
-        a.out = h->dy[k - 1];
-        a.act_prev = h->act[k - 1];
-        if (kPool[k - 2]) {
-            a.idx_prev = h->idx[k - 1];
-            HIPCHK(launch_conv<M_DGRAD_UNPOOL>(a, L.dct, L.cin / 16, s));
-        } else {
-            HIPCHK(launch_conv<M_DGRAD>(a, L.dct, L.cin / 16, s));
-        }
-    }
-    h->have_grad = true;
-    return Y355_BNTRAIN_OK;
-}
-
-int y355_bntrain_wgrad_plan(const y355_bntrain *h, int32_t k, int32_t batch, int32_t *out) {
-    if (int rc = layer_arg("y355_bntrain_wgrad_plan", h, k)) return rc;
-    if (!out) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_wgrad_plan: null argument");
-    if (batch < 1 || batch > h->max_batch) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_wgrad_plan: batch must be 1..max_batch");
-    const WgradPlan p = wgrad_plan(h->d.L[k - 1], batch, h->H / kDiv[k - 1], h->W / kDiv[k - 1]);
-    if (p.npix > (size_t)INT32_MAX) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_wgrad_plan: more than 2^31 - 1 pixels");
-    out[0] = (int32_t)p.npix;
-    out[1] = p.max_runs;
-    out[2] = p.runs;
-    out[3] = (int32_t)p.chunk;
-    return Y355_BNTRAIN_OK;
-}
-
 int y355_bntrain_stats_plan(const y355_bntrain *h, int32_t k, int32_t batch, int32_t *out) {
     if (int rc = layer_arg("y355_bntrain_stats_plan", h, k, NBN)) return rc;
     if (!out) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_stats_plan: null argument");
@@ -860,46 +568,38 @@ int y355_bntrain_stats_plan(const y355_bntrain *h, int32_t k, int32_t batch, int
     return Y355_BNTRAIN_OK;
 }
 
-int y355_bntrain_sgd_step(y355_bntrain *h, float lr, float momentum, float weight_decay, void *stream) {
-    if (!h) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_sgd_step: null handle");
-    if (!(lr == lr) || !(momentum == momentum) || !(weight_decay == weight_decay))
-        return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_sgd_step: lr, momentum and weight_decay must be numbers");
-    if (!h->have_grad) return y355_fail(Y355_BNTRAIN_ENOTREADY, "y355_bntrain_sgd_step: no backward pass has run");
+int y355_bntrain_forward(y355_bntrain *h, const void *x_dev, int32_t batch, void *stream) {
+    if (int rc = forward_args(h, x_dev, batch)) return rc;
+    if ((long long)batch * (h->H / 16) * (h->W / 16) < 2)
+        return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_forward: BatchNorm in training mode needs more than one value per channel: batch * H/16 * W/16 >= 2");
+    hipStream_t s = (hipStream_t)stream;
     DeviceGuard g;
     HIPCHK(g.set(h->device_id));
-    const int first = h->steps == 0 ? 1 : 0;
-    HIPCHK(launch_pack(h, lr, momentum, weight_decay, first, 1, (hipStream_t)stream));
-    hipLaunchKernelGGL(bn_sgd_kernel, dim3((unsigned)((2 * h->cs + 255) / 256)), dim3(256), 0, (hipStream_t)stream, 2 * h->cs, h->bnp, h->bng, h->bnm, lr,
-                       momentum, weight_decay, first);
-    HIPCHK(hipGetLastError());
-    ++h->steps;
+    HIPCHK(launch_input(h, x_dev, batch, s));
+    for (int k = 1; k < NL; ++k) {
+        HIPCHK(launch_forward<M_Z>(h, k, batch, h->z[k], nullptr, s));
+        if (int rc = bn_forward(h, k, batch, s)) return rc;
+    }
+    HIPCHK(launch_forward<M_PRED>(h, NL, batch, h->pred, nullptr, s));
+    h->batch = batch;
     return Y355_BNTRAIN_OK;
 }
 
-int y355_bntrain_tensor_shape(const y355_bntrain *h, int32_t kind, int32_t t, int32_t *shape) {
-    if (!h || !shape) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_tensor_shape: null argument");
-    if (!tensor_dims(h, kind, t, shape)) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_tensor_shape: no such tensor");
-    return Y355_BNTRAIN_OK;
-}
-
-int y355_bntrain_get_tensor(y355_bntrain *h, int32_t kind, int32_t t, void *out) {
-    if (!h || !out) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_get_tensor: null argument");
-    int shape[4];
-    if (!tensor_dims(h, kind, t, shape)) return y355_fail(Y355_BNTRAIN_EINVAL, "y355_bntrain_get_tensor: no such tensor");
-    if (h->batch == 0) return y355_fail(Y355_BNTRAIN_ENOTREADY, "y355_bntrain_get_tensor: no forward pass has run at this size");
-    if ((kind == Y355_BNTRAIN_GRAD || kind == Y355_BNTRAIN_DY) && !h->have_grad)
-        return y355_fail(Y355_BNTRAIN_ENOTREADY, "y355_bntrain_get_tensor: no backward pass has run");
-    const size_t n = (size_t)shape[0] * shape[1] * shape[2] * shape[3];
-    const void *src = kind == Y355_BNTRAIN_ACT   ? (const void *)h->act[t]
-                      : kind == Y355_BNTRAIN_IDX ? (const void *)h->idx[t]
-                      : kind == Y355_BNTRAIN_Z   ? (const void *)h->z[t]
-                      : kind == Y355_BNTRAIN_DY  ? (const void *)h->dy[t]
-                                                 : (const void *)h->grad[t];
+int y355_bntrain_backward(y355_bntrain *h, const void *dpred_dev, void *stream) {
+    if (int rc = backward_args(h, dpred_dev)) return rc;
+    hipStream_t s = (hipStream_t)stream;
     DeviceGuard g;
     HIPCHK(g.set(h->device_id));
-    HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, src, n * (kind == Y355_BNTRAIN_IDX ? 1 : 2), hipMemcpyDeviceToHost));
+    HIPCHK(launch_dpred(h, dpred_dev, s));
+    for (int k = NL; k >= 1; --k) {
+        if (k <= NBN)
+            if (int rc = bn_backward(h, k, s)) return rc;
+        HIPCHK(launch_wgrad(h, k, s));
+        if (k > 1) HIPCHK(launch_dgrad(h, k, h->dy[k - 1], s));       // the gradient with respect to the image is not computed
+    }
+    h->have_grad = true;
     return Y355_BNTRAIN_OK;
 }
 
 }  // extern "C"
+

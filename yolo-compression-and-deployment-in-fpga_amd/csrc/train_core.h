@@ -2,7 +2,7 @@
 // bntrain.hip: the BatchNorm SlimYOLOv2, section 6n): the layer table, the convolution forward / data-gradient kernel with its
 // epilogues, the weight-gradient and reduce kernels, the SGD + pack kernel, launch_conv and the weight gradient's plan.  Each
 // library compiles its own copy (everything here is hidden or static); the including file has pushed hidden visibility and
-// included y355_host.h.
+// included y355_host.h.  The handle and the entry points' bodies on top of these are train_host.h's.
 #ifndef Y355_TRAIN_CORE_H
 #define Y355_TRAIN_CORE_H
 
@@ -45,6 +45,13 @@ struct NetDesc {
 inline int tiles_per_wave(int channels) {
     const int t = (channels + 15) / 16;
     return t >= 3 ? 4 : t;
+}
+// elements of layer L's forward pack: its 16-row tiles, rounded up to what a wave takes, times its k-steps of 64 x 8
+inline size_t forward_pack_size(const LayerDesc &L) { return (size_t)(((L.cout + 15) / 16 + L.ct - 1) / L.ct * L.ct) * L.ksf * 512; }
+// where a pack of `ks` k-steps keeps the element (row, kidx) of the A operand: tile row >> 4, k-step kidx >> 5, lane
+// (g = (kidx >> 3) & 3, i = row & 15), element kidx & 7
+__device__ __host__ inline size_t pack_index(int row, int ks, int kidx) {
+    return ((((size_t)(row >> 4) * ks + (kidx >> 5)) * 64 + ((kidx >> 3) & 3) * 16 + (row & 15)) << 3) + (kidx & 7);
 }
 
 // ---------------------------------------------------------------------------------------------------------- kernels
@@ -384,7 +391,7 @@ __global__ __launch_bounds__(256) void train_sgd_kernel(const NetDesc d, float *
     const size_t e = i - L.woff;
     const int co = (int)(e / ((size_t)L.cin * 9)), rem = (int)(e - (size_t)co * L.cin * 9), ci = rem / 9, tap = rem % 9;
     const bf16_t h = rb_(w);
-    {
+    {                                                         // pack_index, kept as written: the inline moves the kernel's code
         const int kidx = tap * L.cinp + ci;
         packs[L.wf_off + ((((size_t)(co >> 4) * L.ksf + (kidx >> 5)) * 64 + ((kidx >> 3) & 3) * 16 + (co & 15)) << 3) + (kidx & 7)] = h;
     }

@@ -1,5 +1,5 @@
 // The kernels and host helpers the training libraries share (train.hip: the BN-folded SlimYOLOv2, DESIGN.md section 6m;
-// bntrain.hip: the BatchNorm SlimYOLOv2, section 6n): the layer table, the convolution forward / data-gradient kernel with its
+// bntrain.hip: the BatchNorm SlimYOLOv2, section 6n; qtrain.hip: the fake-quantised BN-folded SlimYOLOv2, section 6o): the layer table, the convolution forward / data-gradient kernel with its
 // epilogues, the weight-gradient and reduce kernels, the SGD + pack kernel, launch_conv and the weight gradient's plan.  Each
 // library compiles its own copy (everything here is hidden or static); the including file has pushed hidden visibility and
 // included y355_host.h.  The handle and the entry points' bodies on top of these are train_host.h's.
@@ -86,8 +86,13 @@ __global__ __launch_bounds__(256) void train_dpred_kernel(const float *__restric
     g[i] = c < cout ? rb_(dp[(b * cout + c) * hw + yx]) : (bf16_t)0;
 }
 
-// M_Z (bntrain.hip alone): Z_k = rb(conv + bias) on the pre-pool grid, no slope and no pool
-enum { M_FWD = 0, M_FWD_POOL = 1, M_PRED = 2, M_DGRAD = 3, M_DGRAD_UNPOOL = 4, M_Z = 5 };
+// M_Z (bntrain.hip alone): Z_k = rb(conv + bias) on the pre-pool grid, no slope and no pool.  M_Q* (qtrain.hip alone, DESIGN.md
+// section 6o): the epilogues of the fake-quantised network -- the output rounded to 8 bits at the power of two of its tracker,
+// a state byte per output element (bits 0-1: the window position, bit 2: the selected z <= 0, bit 3: clipped), the tracker's
+// max|v| and clipped count through integer atomics; the data gradient reads slope and mask from the state byte of A_{k-1}.
+enum { M_FWD = 0, M_FWD_POOL = 1, M_PRED = 2, M_DGRAD = 3, M_DGRAD_UNPOOL = 4, M_Z = 5, M_QFWD = 6, M_QFWD_POOL = 7, M_QPRED = 8, M_QDGRAD = 9,
+       M_QDGRAD_UNPOOL = 10 };
+enum { Q_POS = 3, Q_NEG = 4, Q_CLIP = 8 };          // the state byte's fields
 struct ConvArgs {
     const bf16_t *in;                // NHWC, cinp channels, on the H x W grid
     const bf16_t *w;                 // packed A fragments
@@ -100,11 +105,38 @@ struct ConvArgs {
     unsigned char *idx;              // M_FWD_POOL: I_k
     const bf16_t *act_prev;          // data gradient: A_{k-1}
     const unsigned char *idx_prev;   // M_DGRAD_UNPOOL: I_{k-1}
+    // M_Q* alone
+    float qs, qi;                    // 2^e and 2^-e of the output's tracker
+    unsigned char *state;            // S_k, on the output's grid at outc channels
+    const unsigned char *state_prev; // data gradient: S_{k-1}
+    unsigned int *stats;             // {bits of max|v|, elements with |rne(v 2^e)| > 127} of the output's tracker
 };
+
+// A tracker's statistics st = {bits of max|v|, clipped count} from every lane of a wave: the wave's maximum and sum, then at most
+// one atomic each.  Integers, exact in any order.  The maximum only grows, so a wave that reads a value at least its own has
+// nothing to add (a stale read costs an atomic, never a result): nearly every wave of a layer skips the contended address.
+__device__ __forceinline__ void wave_stats_(unsigned int vmax, unsigned int n, unsigned int *st) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) {
+        vmax = max(vmax, (unsigned int)__shfl_xor((int)vmax, m));
+        n += (unsigned int)__shfl_xor((int)n, m);
+    }
+    if ((threadIdx.x & 63) == 0) {
+        if (vmax > __hip_atomic_load(st, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) atomicMax(st, vmax);
+        if (n) atomicAdd(st + 1, n);
+    }
+}
+
+// clip(rne(v 2^e), -127, 127) and whether it clipped; a zero comes out as +0 (the integer 0 has no sign)
+__device__ __forceinline__ float quant_(float v, float qs, bool &clipped) {
+    const float r = rintf(v * qs);
+    clipped = fabsf(r) > 127.f;
+    return fminf(fmaxf(r, -127.f), 127.f) + 0.0f;
+}
 
 template <int MODE, int CT>
 __global__ __launch_bounds__(256) void train_conv_kernel(const ConvArgs a) {
-    constexpr bool POOL = MODE == M_FWD_POOL;
+    constexpr bool POOL = MODE == M_FWD_POOL || MODE == M_QFWD_POOL;
     const int lane = threadIdx.x & 63, j = lane & 15, g = lane >> 4;
     const size_t wave = (size_t)blockIdx.x * 4 + (threadIdx.x >> 6);
     const int H = a.H, W = a.W;
@@ -169,6 +201,7 @@ __global__ __launch_bounds__(256) void train_conv_kernel(const ConvArgs a) {
     }
 
     // lane: column j of every set, rows 4 g .. 4 g + 3 of every tile
+    [[maybe_unused]] unsigned int vmax = 0, nclip = 0;        // M_Q*: of the lane's elements before the pool
 #pragma unroll
     for (int t = 0; t < CT; ++t) {
         const int co = ((int)blockIdx.y * CT + t) * 16 + 4 * g;
@@ -204,6 +237,100 @@ __global__ __launch_bounds__(256) void train_conv_kernel(const ConvArgs a) {
 #pragma unroll
                 for (int s = 0; s < 4; ++s)
                     if (ok[s]) *(uint2 *)((bf16_t *)a.out + pl[s] * a.outc + co) = rb4_(v[s]);
+            }
+        } else if constexpr (MODE == M_QFWD || MODE == M_QFWD_POOL) {
+            float v[4][4];
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const float z = acc[s][t][r] + a.bias[co + r];
+                    v[s][r] = z > 0.f ? z : z * SLOPE;
+                    if (ok[s]) {
+                        vmax = max(vmax, __builtin_bit_cast(unsigned int, fabsf(v[s][r])));
+                        nclip += fabsf(v[s][r] * a.qs) >= 127.5f ? 1u : 0u;               // |rne(t)| > 127: 127.5 ties to 128
+                    }
+                }
+            if constexpr (POOL) {
+                if (ok[0]) {
+                    float out[4];
+                    unsigned int st = 0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        float best = v[0][r];
+                        unsigned int w = 0;
+#pragma unroll
+                        for (int s = 1; s < 4; ++s)
+                            if (v[s][r] > best) {
+                                best = v[s][r];
+                                w = s;
+                            }
+                        bool c;
+                        out[r] = quant_(best, a.qs, c) * a.qi;
+                        st |= (w | (best <= 0.f ? Q_NEG : 0u) | (c ? Q_CLIP : 0u)) << (8 * r);
+                    }
+                    *(uint2 *)((bf16_t *)a.out + q_pool * a.outc + co) = rb4_(out);
+                    *(unsigned int *)(a.state + q_pool * a.outc + co) = st;
+                }
+            } else {
+#pragma unroll
+                for (int s = 0; s < 4; ++s) {
+                    if (!ok[s]) continue;
+                    float out[4];
+                    unsigned int st = 0;
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) {
+                        bool c;
+                        out[r] = quant_(v[s][r], a.qs, c) * a.qi;
+                        st |= ((v[s][r] <= 0.f ? Q_NEG : 0u) | (c ? Q_CLIP : 0u)) << (8 * r);
+                    }
+                    *(uint2 *)((bf16_t *)a.out + pl[s] * a.outc + co) = rb4_(out);
+                    *(unsigned int *)(a.state + pl[s] * a.outc + co) = st;
+                }
+            }
+        } else if constexpr (MODE == M_QPRED) {                   // a.outc: the padded channels of S_10 (P itself has a.cout)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (!ok[s]) continue;
+                const size_t b = pl[s] / hw, yx = pl[s] - b * hw;
+                unsigned int st = 0;
+#pragma unroll
+                for (int r = 0; r < 4; ++r)
+                    if (co + r < a.cout) {
+                        const float z = acc[s][t][r] + a.bias[co + r];
+                        vmax = max(vmax, __builtin_bit_cast(unsigned int, fabsf(z)));
+                        bool c;
+                        ((float *)a.out)[(b * a.cout + co + r) * hw + yx] = quant_(z, a.qs, c) * a.qi;
+                        nclip += c ? 1u : 0u;
+                        st |= (c ? Q_CLIP : 0u) << (8 * r);
+                    }
+                if (co < a.outc) *(unsigned int *)(a.state + pl[s] * a.outc + co) = st;
+            }
+        } else if constexpr (MODE == M_QDGRAD || MODE == M_QDGRAD_UNPOOL) {
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                if (!ok[s]) continue;
+                const size_t at = pl[s] * a.outc + co;
+                const unsigned int st = *(const unsigned int *)(a.state_prev + at);
+                float v[4];
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const unsigned int sb = st >> (8 * r);
+                    v[r] = (sb & Q_CLIP) ? 0.f : acc[s][t][r] * ((sb & Q_NEG) ? SLOPE : 1.0f);
+                }
+                if constexpr (MODE == M_QDGRAD) {
+                    *(uint2 *)((bf16_t *)a.out + at) = rb4_(v);
+                } else {
+                    const size_t b = pl[s] / hw;
+                    const size_t row = (b * 2 * H + 2 * (size_t)py[s]) * 2 * W + 2 * (size_t)px[s];
+#pragma unroll
+                    for (int wpos = 0; wpos < 4; ++wpos) {
+                        float u[4];
+#pragma unroll
+                        for (int r = 0; r < 4; ++r) u[r] = ((st >> (8 * r)) & Q_POS) == (unsigned)wpos ? v[r] : 0.f;
+                        *(uint2 *)((bf16_t *)a.out + (row + (size_t)(wpos >> 1) * 2 * W + (wpos & 1)) * a.outc + co) = rb4_(u);
+                    }
+                }
             }
         } else if constexpr (MODE == M_Z) {
 #pragma unroll
@@ -250,6 +377,7 @@ __global__ __launch_bounds__(256) void train_conv_kernel(const ConvArgs a) {
             }
         }
     }
+    if constexpr (MODE == M_QFWD || MODE == M_QFWD_POOL || MODE == M_QPRED) wave_stats_(vmax, nclip, a.stats);
 }
 
 struct WgradArgs {
@@ -424,7 +552,7 @@ static WgradPlan wgrad_plan(const LayerDesc &L, int B, int H, int W) {
 
 template <int MODE>
 static hipError_t launch_conv(const ConvArgs &a, int ct, int tiles, hipStream_t s) {
-    const bool pool = MODE == M_FWD_POOL;
+    const bool pool = MODE == M_FWD_POOL || MODE == M_QFWD_POOL;
     const size_t cols = pool ? (size_t)a.B * (a.H / 2) * (a.W / 2) : (size_t)a.B * a.H * a.W;
     const size_t waves = pool ? (cols + 15) / 16 : (cols + 63) / 64;
     const dim3 grid((unsigned)((waves + 3) / 4), (unsigned)((tiles + ct - 1) / ct)), block(256);

@@ -1,4 +1,5 @@
-// The host side the two training libraries share (train.hip; bntrain.hip, section 6n), on the kernels
+// The host side the training libraries share (train.hip; bntrain.hip, section 6n; qtrain.hip, section 6o:
+// it has an input, a dP and a data-gradient launch of its own, so those here are marked as possibly unused), on the kernels
 // of train_core.h: the handle's common state, the create rules with the layer table, the common device memory, the bodies of
 // the entry points both headers declare, and the launches of a layer that both passes make.  Each library compiles its own copy
 // (everything here is static, under the including file's hidden visibility) after
@@ -271,26 +272,30 @@ static int core_sgd_step(TrainCore *h, float lr, float momentum, float weight_de
 }
 
 // A tensor kind of the including library's own, on the pre-pool grid of layer t: its device memory, its channels (0: no such
-// tensor) and whether only a backward fills it.
+// tensor) and whether only a backward fills it; the bytes of an element, and the divisor of its grid where it is another.
 struct OwnTensor {
     const void *src;
     int c;
     bool of_backward;
+    int elem = 2;
+    int div = 0;
 };
 typedef OwnTensor (*OwnTensorFn)(const TrainCore *h, int kind, int t);
 
-// [B, h, w, c] of a tensor at the current size, its memory and whether it needs a backward; false on a kind / index that does not exist
-static bool tensor_dims(const TrainCore *h, int kind, int t, OwnTensorFn own, int *shape, const void **src = nullptr, bool *of_backward = nullptr) {
+// [B, h, w, c] of a tensor at the current size, its memory, whether it needs a backward and the bytes of an element; false on
+// a kind / index that does not exist
+static bool tensor_dims(const TrainCore *h, int kind, int t, OwnTensorFn own, int *shape, const void **src = nullptr, bool *of_backward = nullptr,
+                        int *elem = nullptr) {
     int div;
     OwnTensor o{nullptr, 0, false};
     if ((kind == T_ACT && t >= 0 && t <= 9) || (kind == T_IDX && t >= 1 && t <= 9 && kPool[t - 1])) {
         div = act_div(t);
-        o = OwnTensor{kind == T_ACT ? (const void *)h->act[t] : (const void *)h->idx[t], act_c(h, t), false};
+        o = OwnTensor{kind == T_ACT ? (const void *)h->act[t] : (const void *)h->idx[t], act_c(h, t), false, kind == T_IDX ? 1 : 2};
     } else if (kind == T_GRAD && t >= 1 && t <= NL) {
         div = kDiv[t - 1];
         o = OwnTensor{h->grad[t], h->d.L[t - 1].coutp, true};
     } else if (own && (o = own(h, kind, t)).c) {
-        div = kDiv[t - 1];
+        div = o.div ? o.div : kDiv[t - 1];
     } else {
         return false;
     }
@@ -300,6 +305,7 @@ static bool tensor_dims(const TrainCore *h, int kind, int t, OwnTensorFn own, in
     shape[3] = o.c;
     if (src) *src = o.src;
     if (of_backward) *of_backward = o.of_backward;
+    if (elem) *elem = o.elem;
     return true;
 }
 
@@ -314,14 +320,15 @@ static int core_get_tensor(TrainCore *h, int kind, int t, void *out, OwnTensorFn
     int shape[4];
     const void *src;
     bool of_backward;
-    if (!tensor_dims(h, kind, t, own, shape, &src, &of_backward)) return y355_fail(Y355_EINVAL, TRAIN_FN("get_tensor") ": no such tensor");
+    int elem;
+    if (!tensor_dims(h, kind, t, own, shape, &src, &of_backward, &elem)) return y355_fail(Y355_EINVAL, TRAIN_FN("get_tensor") ": no such tensor");
     if (h->batch == 0) return y355_fail(Y355_ENOTREADY, TRAIN_FN("get_tensor") ": no forward pass has run at this size");
     if (of_backward && !h->have_grad) return y355_fail(Y355_ENOTREADY, TRAIN_FN("get_tensor") ": no backward pass has run");
     const size_t n = (size_t)shape[0] * shape[1] * shape[2] * shape[3];
     DeviceGuard g;
     HIPCHK(g.set(h->device_id));
     HIPCHK(hipDeviceSynchronize());
-    HIPCHK(hipMemcpy(out, src, n * (kind == T_IDX ? 1 : 2), hipMemcpyDeviceToHost));
+    HIPCHK(hipMemcpy(out, src, n * elem, hipMemcpyDeviceToHost));
     return Y355_OK;
 }
 
@@ -333,7 +340,7 @@ static int forward_args(const TrainCore *h, const void *x_dev, int batch) {
     return 0;
 }
 // ... its first launch, A_0 = rb(x): from here on the handle holds no finished forward until the caller sets h->batch, ...
-static hipError_t launch_input(TrainCore *h, const void *x_dev, int batch, hipStream_t s) {
+[[maybe_unused]] static hipError_t launch_input(TrainCore *h, const void *x_dev, int batch, hipStream_t s) {
     h->batch = 0;
     h->have_grad = false;
     const size_t npix = (size_t)batch * h->H * h->W;
@@ -341,9 +348,9 @@ static hipError_t launch_input(TrainCore *h, const void *x_dev, int batch, hipSt
                        (size_t)h->H * h->W);
     return hipGetLastError();
 }
-// ... and the convolution of layer k on A_{k-1} with epilogue MODE into out (idx: I_k of M_FWD_POOL)
-template <int MODE>
-static hipError_t launch_forward(const TrainCore *h, int k, int batch, void *out, unsigned char *idx, hipStream_t s) {
+// ... and the convolution of layer k on A_{k-1} into out (idx: I_k of M_FWD_POOL): its arguments, and its launch with epilogue
+// MODE (a library with epilogues of its own fills in the rest of the arguments and calls launch_conv itself)
+static ConvArgs forward_conv_args(const TrainCore *h, int k, int batch, void *out, unsigned char *idx) {
     const LayerDesc &L = h->d.L[k - 1];
     ConvArgs a{};
     a.in = h->act[k - 1];
@@ -358,7 +365,12 @@ static hipError_t launch_forward(const TrainCore *h, int k, int batch, void *out
     a.outc = L.cout;
     a.out = out;
     a.idx = idx;
-    return launch_conv<MODE>(a, L.ct, (L.cout + 15) / 16, s);
+    return a;
+}
+template <int MODE>
+static hipError_t launch_forward(const TrainCore *h, int k, int batch, void *out, unsigned char *idx, hipStream_t s) {
+    const LayerDesc &L = h->d.L[k - 1];
+    return launch_conv<MODE>(forward_conv_args(h, k, batch, out, idx), L.ct, (L.cout + 15) / 16, s);
 }
 
 // The arguments of <family>_backward, ...
@@ -368,7 +380,7 @@ static int backward_args(const TrainCore *h, const void *dpred_dev) {
     return 0;
 }
 // ... its first launch, G_10 = rb(dP): from here on the handle holds no finished backward until the caller sets h->have_grad, ...
-static hipError_t launch_dpred(TrainCore *h, const void *dpred_dev, hipStream_t s) {
+[[maybe_unused]] static hipError_t launch_dpred(TrainCore *h, const void *dpred_dev, hipStream_t s) {
     h->have_grad = false;
     const LayerDesc &L = h->d.L[NL - 1];
     const size_t hw = (size_t)(h->H / 16) * (h->W / 16), n = (size_t)h->batch * hw * L.coutp;
@@ -405,7 +417,7 @@ static hipError_t launch_wgrad(const TrainCore *h, int k, hipStream_t s) {
     return hipGetLastError();
 }
 // ... and the data gradient of layer k = 2..10 from G_k, through A_{k-1}'s slope mask and I_{k-1}, into dst on layer k - 1's grid
-static hipError_t launch_dgrad(const TrainCore *h, int k, bf16_t *dst, hipStream_t s) {
+static ConvArgs dgrad_conv_args(const TrainCore *h, int k, bf16_t *dst) {
     const LayerDesc &L = h->d.L[k - 1];
     ConvArgs a{};
     a.in = h->grad[k];
@@ -419,6 +431,11 @@ static hipError_t launch_dgrad(const TrainCore *h, int k, bf16_t *dst, hipStream
     a.outc = L.cin;
     a.out = dst;
     a.act_prev = h->act[k - 1];
+    return a;
+}
+[[maybe_unused]] static hipError_t launch_dgrad(const TrainCore *h, int k, bf16_t *dst, hipStream_t s) {
+    const LayerDesc &L = h->d.L[k - 1];
+    ConvArgs a = dgrad_conv_args(h, k, dst);
     if (!kPool[k - 2]) return launch_conv<M_DGRAD>(a, L.dct, L.cin / 16, s);
     a.idx_prev = h->idx[k - 1];
     return launch_conv<M_DGRAD_UNPOOL>(a, L.dct, L.cin / 16, s);

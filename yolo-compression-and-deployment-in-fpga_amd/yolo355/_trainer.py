@@ -1,5 +1,5 @@
-"""What the two trainers share (train.SlimTrainer over include/yolo355_train.h, bntrain.SlimBNTrainer over
-include/yolo355_bntrain.h): the seventeen entry points both headers declare under their own prefix (common_sigs), the layer
+"""What the trainers share (train.SlimTrainer over include/yolo355_train.h, bntrain.SlimBNTrainer over
+include/yolo355_bntrain.h, qtrain.SlimQatTrainer over include/yolo355_qtrain.h): the seventeen entry points the headers declare under their own prefix (common_sigs), the layer
 names of the network, and Trainer, the handle with the reference's loop body -- parameters in and out per layer, forward, the
 loss and its gradient of yolo355.grad, backward, the SGD update -- written once.  A trainer class names its prefix and its
 binding module's lib and check (_prefix, _lib_fn, _check) and adds what is its own."""
@@ -59,7 +59,7 @@ def _np(v):
 class Trainer(Handle):
     """A training step with torch.optim.SGD(lr, momentum, weight_decay) behind one of the two C ABIs.  input_size [H, W]
     (multiples of 16) is the largest size the trainer takes; set_grid switches within it."""
-    _prefix = None              # of the entry points, "y355_train_" / "y355_bntrain_"
+    _prefix = None              # of the entry points, "y355_train_" / "y355_bntrain_" / "y355_qtrain_"
     _lib_fn = _check = None     # the binding module's lib and check (staticmethod)
 
     def __init__(self, input_size, num_classes, anchor_size, max_batch, lr, momentum=0.9, weight_decay=5e-4, device=None):

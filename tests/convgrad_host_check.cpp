@@ -1,0 +1,245 @@
+// The host side of libyolo355_convgrad.so on the CPU under the address and undefined-behaviour sanitizers
+// (make -C csrc hostcheck-convgrad): the rules of y355_convgrad_create (its device-free half), the output size against the
+// formula, the weight gradient's plan, every refusal the entry points make before a device call, and the handle's device memory
+// -- the two packs, both or neither, and the growable workspaces -- under an allocator that fails at every allocation in turn,
+// on a handle whose "device" memory is the host heap.  A stand-alone program; needs no GPU.
+#include <cmath>
+#include <cstdio>
+#include <cstdlib>
+#include <cstring>
+#include <limits>
+#include <set>
+#include <string>
+
+#include "../include/yolo355_convgrad.h"
+#include "../yolo-compression-and-deployment-in-fpga_amd/csrc/y355_host.h"
+
+static std::string g_text;
+int y355_fail(int code, const std::string &msg) {      // the library's own is left out under -DY355_HOSTCHECK
+    g_text = msg;
+    return code;
+}
+
+// convgrad.hip's halves of a create and what goes with them (the struct stays the library's)
+int convgrad_open(int device_id, int cin, int cout, const y355_convgrad_geom *g, float neg_slope, const DevMem &mem, y355_convgrad **out);
+int convgrad_buffers(y355_convgrad *h);
+int convgrad_workspaces(y355_convgrad *h, size_t xs_n, size_t gs_n, size_t ws_n);
+DevOwner &convgrad_owner(y355_convgrad *h);
+void convgrad_caps(const y355_convgrad *h, size_t *caps);      // xs, gs, ws (0: not held), the two packs' elements
+void convgrad_free(y355_convgrad *h);
+
+static int failures = 0;
+#define EXPECT(cond)                                                         \
+    do {                                                                     \
+        if (!(cond)) {                                                       \
+            std::printf("%s:%d: %s   [%s]\n", __FILE__, __LINE__, #cond, g_text.c_str()); \
+            ++failures;                                                      \
+        }                                                                    \
+    } while (0)
+
+// the host heap as device memory: every block is tracked, the fail_at-th allocation from now (0-based) fails
+static std::set<void *> live;
+static int fail_at = -1, allocs_seen = 0;
+static DevMem host_mem() {
+    DevMem m;
+    m.alloc = [](void **p, size_t bytes, bool zero) {
+        if (allocs_seen++ == fail_at) return y355_fail(Y355_EHIP, "allocation refused");
+        *p = zero ? std::calloc(1, bytes ? bytes : 16) : std::malloc(bytes ? bytes : 16);
+        live.insert(*p);
+        return 0;
+    };
+    m.release = [](void *p) {
+        EXPECT(live.erase(p) == 1);                       // never twice, never a stranger
+        std::free(p);
+    };
+    m.upload = [](void *dst, const void *src, size_t bytes, hipStream_t) {
+        std::memcpy(dst, src, bytes);
+        return 0;
+    };
+    return m;
+}
+
+static const y355_convgrad_geom G3{3, 3, 1, 1, 1, 1, 1, 1, 1, 1};
+
+static void refused_create(const char *text, int dev, int cin, int cout, const y355_convgrad_geom *g, float slope) {
+    y355_convgrad *t = (y355_convgrad *)16;
+    g_text.clear();
+    const int rc = convgrad_open(dev, cin, cout, g, slope, host_mem(), &t);
+    if (rc != Y355_CONVGRAD_EINVAL || t || g_text.find(text) == std::string::npos || g_text.find("y355_convgrad_create: ") != 0 || !live.empty()) {
+        std::printf("expected a create refused with \"%s\", got %d \"%s\"\n", text, rc, g_text.c_str());
+        ++failures;
+    }
+}
+
+static void check_rules() {
+    EXPECT(convgrad_open(0, 3, 16, &G3, 0.125f, host_mem(), nullptr) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_create: null argument");
+    refused_create("null argument", 0, 3, 16, nullptr, 1.f);
+    refused_create("device_id must be >= 0", -1, 3, 16, &G3, 1.f);
+    refused_create("cin and cout must be 1..4096", 0, 0, 16, &G3, 1.f);
+    refused_create("cin and cout must be 1..4096", 0, 4097, 16, &G3, 1.f);
+    refused_create("cin and cout must be 1..4096", 0, 3, 0, &G3, 1.f);
+    refused_create("cin and cout must be 1..4096", 0, 3, 4097, &G3, 1.f);
+    refused_create("neg_slope must be finite and >= 0", 0, 3, 16, &G3, -0.1f);
+    refused_create("neg_slope must be finite and >= 0", 0, 3, 16, &G3, std::nanf(""));
+    refused_create("neg_slope must be finite and >= 0", 0, 3, 16, &G3, std::numeric_limits<float>::infinity());
+    // each field of the geometry at both ends
+    struct {
+        int field, value;
+        const char *text;
+    } bad[] = {{0, 0, "kernel size must be 1..32"}, {0, 33, "kernel size"},  {1, 0, "kernel size"},  {1, 33, "kernel size"},
+               {2, 0, "stride must be 1..16"},      {2, 17, "stride"},       {3, 0, "stride"},       {3, 17, "stride"},
+               {4, 0, "dilation must be 1..32"},    {4, 33, "dilation"},     {5, 0, "dilation"},     {5, 33, "dilation"},
+               {6, -1, "padding must be 0..64"},    {6, 65, "padding"},      {7, -1, "padding"},     {7, 65, "padding"},
+               {8, -1, "padding"},                  {8, 65, "padding"},      {9, -1, "padding"},     {9, 65, "padding"}};
+    for (const auto &b : bad) {
+        y355_convgrad_geom g;
+        int32_t f[10];
+        std::memcpy(f, &G3, sizeof(f));
+        f[b.field] = b.value;
+        std::memcpy(&g, f, sizeof(f));
+        refused_create(b.text, 0, 3, 16, &g, 1.f);
+        int32_t ho = -7, wo = -7;
+        EXPECT(y355_convgrad_out_size(&g, 16, 16, &ho, &wo) == Y355_CONVGRAD_EINVAL && ho == -7 && wo == -7);
+        EXPECT(g_text.find("y355_convgrad_out_size: ") == 0 && g_text.find(b.text) != std::string::npos);
+    }
+    const y355_convgrad_geom big{32, 32, 16, 16, 32, 32, 64, 64, 64, 64};        // every limit at once is a geometry
+    y355_convgrad *t = nullptr;
+    EXPECT(convgrad_open(3, 4096, 4096, &big, 0.f, host_mem(), &t) == 0 && t);
+    convgrad_free(t);
+}
+
+static void check_out_size() {
+    int32_t ho, wo;
+    for (int kh = 1; kh <= 7; ++kh)
+        for (int s = 1; s <= 3; ++s)
+            for (int d = 1; d <= 3; ++d)
+                for (int pt = 0; pt <= 2; ++pt)
+                    for (int H = 1; H <= 20; H += 3) {
+                        const y355_convgrad_geom g{kh, 2, s, 1, d, 2, pt, 1, 0, 2};
+                        const int W = H + 2, hn = H + pt + 1 - d * (kh - 1) - 1, wn = W + 2 - 2 - 1;
+                        const int rc = y355_convgrad_out_size(&g, H, W, &ho, &wo);
+                        if (hn < 0) EXPECT(rc == Y355_CONVGRAD_EINVAL && g_text.find("larger than the padded input") != std::string::npos);
+                        else EXPECT(rc == 0 && ho == hn / s + 1 && wo == wn + 1);
+                    }
+    EXPECT(y355_convgrad_out_size(&G3, 0, 4, &ho, &wo) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_out_size: bad shape");
+    EXPECT(y355_convgrad_out_size(&G3, 4, 4, nullptr, &wo) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_out_size: null argument");
+    EXPECT(y355_convgrad_out_size(nullptr, 4, 4, &ho, &wo) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_out_size(&G3, 50000, 50000, &ho, &wo) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_out_size: too many pixels");
+}
+
+// the plan's invariants over a sweep: the runs cover the pixels, every run but the last is a whole chunk of a multiple of 32
+static void check_plan() {
+    int32_t p[4];
+    const int chans[][2] = {{3, 16}, {16, 16}, {40, 35}, {384, 256}, {1024, 255}, {8, 64}};
+    for (const auto &c : chans)
+        for (int k = 1; k <= 5; k += 2) {
+            const y355_convgrad_geom g{k, k, 1, 1, 1, 1, k / 2, k / 2, k / 2, k / 2};
+            y355_convgrad *t = nullptr;
+            EXPECT(convgrad_open(0, c[0], c[1], &g, 0.125f, host_mem(), &t) == 0 && t);
+            for (int B = 1; B <= 33; B += 8)
+                for (int H = 1; H <= 97; H += 12) {
+                    EXPECT(y355_convgrad_wgrad_plan(t, B, H, H + 1, p) == 0);
+                    const long long npix = (long long)B * H * (H + 1);
+                    EXPECT(p[0] == npix && p[1] >= 1 && p[1] <= 2048 && p[2] % 32 == 0 && p[2] > 0);
+                    EXPECT(p[3] >= 1 && p[3] <= p[2] && (long long)(p[1] - 1) * p[2] + p[3] == npix);
+                }
+            convgrad_free(t);
+        }
+    y355_convgrad *t = nullptr;
+    EXPECT(convgrad_open(0, 16, 16, &G3, 1.f, host_mem(), &t) == 0);
+    EXPECT(y355_convgrad_wgrad_plan(t, 1, 9, 9, p) == 0 && p[0] == 81 && p[1] == 3 && p[2] == 32 && p[3] == 17);     // tests/test_convgrad.py's case h
+    EXPECT(y355_convgrad_wgrad_plan(t, 1, 4, 4, p) == 0 && p[1] == 1 && p[2] == 32 && p[3] == 16);
+    EXPECT(y355_convgrad_wgrad_plan(nullptr, 1, 4, 4, p) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_wgrad_plan: null argument");
+    EXPECT(y355_convgrad_wgrad_plan(t, 1, 4, 4, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_wgrad_plan(t, 0, 4, 4, p) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_wgrad_plan: bad shape");
+    convgrad_free(t);
+}
+
+// the packs: both or neither, whichever allocation fails; the workspaces: one that cannot grow is left empty, the rest stays
+static void check_memory() {
+    y355_convgrad *t = nullptr;
+    size_t caps[5];
+    for (int k = 0; k < 2; ++k) {
+        EXPECT(convgrad_open(0, 40, 35, &G3, 0.125f, host_mem(), &t) == 0 && t && live.empty());
+        allocs_seen = 0;
+        fail_at = k;
+        g_text.clear();
+        EXPECT(convgrad_buffers(t) == Y355_EHIP && g_text == "allocation refused");
+        EXPECT(live.empty() && convgrad_owner(t).allocs.empty());
+        fail_at = -1;
+        EXPECT(convgrad_buffers(t) == 0 && live.size() == 2 && convgrad_owner(t).allocs.size() == 2);
+        convgrad_free(t);
+        EXPECT(live.empty());
+    }
+    EXPECT(convgrad_open(0, 40, 35, &G3, 0.125f, host_mem(), &t) == 0 && convgrad_buffers(t) == 0);
+    convgrad_caps(t, caps);
+    // 35 rows -> 3 tiles -> 4 (what a wave takes), 9 * 40 / 32 -> 12 k-steps; 40 rows -> 4 tiles, 9 * 40 / 32 (coutp = 40)
+    EXPECT(caps[0] == 0 && caps[1] == 0 && caps[2] == 0 && caps[3] == (size_t)4 * 12 * 512 && caps[4] == (size_t)4 * 12 * 512);
+    EXPECT(convgrad_workspaces(t, 100, 0, 0) == 0 && live.size() == 3);
+    EXPECT(convgrad_workspaces(t, 50, 0, 0) == 0 && live.size() == 3);                   // fits: nothing moves
+    for (int k = 0; k < 3; ++k) {                                                        // growing all three, the k-th fails
+        allocs_seen = 0;
+        fail_at = k;
+        EXPECT(convgrad_workspaces(t, 200 + k, 300 + k, 400 + k) == Y355_EHIP);
+        fail_at = -1;
+        convgrad_caps(t, caps);
+        EXPECT(caps[k] == 0);
+        EXPECT(live.size() == convgrad_owner(t).allocs.size());
+        EXPECT(convgrad_workspaces(t, 200 + k, 300 + k, 400 + k) == 0 && live.size() == 5);
+        convgrad_caps(t, caps);
+        EXPECT(caps[0] == (size_t)200 + k && caps[1] == (size_t)300 + k && caps[2] == (size_t)400 + k);
+    }
+    convgrad_free(t);
+    EXPECT(live.empty());
+}
+
+static void check_refusals() {
+    y355_convgrad *t = nullptr, *u = nullptr;
+    EXPECT(convgrad_open(0, 8, 8, &G3, 0.125f, host_mem(), &t) == 0 && convgrad_buffers(t) == 0);
+    EXPECT(convgrad_open(0, 8, 8, &G3, 1.0f, host_mem(), &u) == 0 && convgrad_buffers(u) == 0);
+    float x[4] = {0, 0, 0, 0};
+    const size_t before = live.size();
+    EXPECT(y355_convgrad_forward(nullptr, x, x, x, 1, 4, 4, x, nullptr) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_forward: null argument");
+    EXPECT(y355_convgrad_forward(t, nullptr, x, x, 1, 4, 4, x, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_forward(t, x, nullptr, x, 1, 4, 4, x, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_forward(t, x, x, x, 1, 4, 4, nullptr, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_forward(t, x, x, nullptr, 0, 4, 4, x, nullptr) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_forward: bad shape");
+    EXPECT(y355_convgrad_forward(t, x, x, nullptr, 1, 0, 4, x, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_forward(t, x, x, nullptr, 40000, 300, 300, x, nullptr) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_forward: too many pixels");
+    y355_convgrad *wide = nullptr;                        // 1.8e9 pixels at 4096 channels: past 2^36 staged elements
+    EXPECT(convgrad_open(0, 4096, 8, &G3, 1.0f, host_mem(), &wide) == 0);
+    EXPECT(y355_convgrad_forward(wide, x, x, nullptr, 20000, 300, 300, x, nullptr) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_forward: tensor too large");
+    convgrad_free(wide);
+    EXPECT(y355_convgrad_backward(nullptr, x, x, x, x, 1, 4, 4, x, x, x, nullptr) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_backward: null argument");
+    EXPECT(y355_convgrad_backward(t, nullptr, x, x, x, 1, 4, 4, x, x, x, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_backward(t, x, nullptr, x, x, 1, 4, 4, x, x, x, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_backward(t, x, x, x, nullptr, 1, 4, 4, x, x, x, nullptr) == Y355_CONVGRAD_EINVAL);
+    EXPECT(y355_convgrad_backward(t, x, x, nullptr, x, 1, 4, 4, x, x, x, nullptr) == Y355_CONVGRAD_EINVAL &&
+           g_text == "y355_convgrad_backward: y is needed unless neg_slope is 1");
+    EXPECT(y355_convgrad_backward(u, x, x, nullptr, x, 1, 4, 0, x, x, x, nullptr) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_backward: bad shape");
+    EXPECT(y355_convgrad_backward(u, x, x, nullptr, x, 1, 4, 4, nullptr, nullptr, nullptr, nullptr) == 0);       // nothing asked for: nothing done
+    const y355_convgrad_geom g7{7, 7, 1, 1, 1, 1, 0, 0, 0, 0};
+    y355_convgrad *v = nullptr;
+    EXPECT(convgrad_open(0, 8, 8, &g7, 1.0f, host_mem(), &v) == 0);
+    EXPECT(y355_convgrad_forward(v, x, x, nullptr, 1, 6, 9, x, nullptr) == Y355_CONVGRAD_EINVAL && g_text.find("larger than the padded input") != std::string::npos);
+    convgrad_free(v);
+    EXPECT(live.size() == before);                        // no refusal touched the memory
+    convgrad_free(t);
+    convgrad_free(u);
+    EXPECT(live.empty());
+    y355_convgrad_destroy(nullptr);
+}
+
+int main() {
+    check_rules();
+    check_out_size();
+    check_plan();
+    check_memory();
+    check_refusals();
+    if (failures) {
+        std::printf("convgrad_host_check: %d failure(s)\n", failures);
+        return 1;
+    }
+    std::printf("convgrad_host_check ok\n");
+    return 0;
+}

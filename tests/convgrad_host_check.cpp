@@ -149,6 +149,32 @@ static void check_plan() {
     EXPECT(convgrad_open(0, 16, 16, &G3, 1.f, host_mem(), &t) == 0);
     EXPECT(y355_convgrad_wgrad_plan(t, 1, 9, 9, p) == 0 && p[0] == 81 && p[1] == 3 && p[2] == 32 && p[3] == 17);     // tests/test_convgrad.py's case h
     EXPECT(y355_convgrad_wgrad_plan(t, 1, 4, 4, p) == 0 && p[1] == 1 && p[2] == 32 && p[3] == 16);
+    // tests/convgrad_ref.py's RUNS (chunks of two and three iterations of 32, a last run that is no multiple of 8) and EDGES
+    const struct {
+        const char *name;
+        y355_convgrad_geom g;
+        int cin, cout, B, H, W, npix, runs, chunk, last;
+    } pins[] = {{"r1", G3, 256, 64, 2, 15, 17, 510, 8, 64, 62},
+                {"r2", G3, 128, 255, 3, 13, 13, 507, 6, 96, 27},
+                {"r3", {1, 1, 1, 1, 1, 1, 0, 0, 0, 0}, 1024, 255, 2, 13, 13, 338, 6, 64, 18},
+                {"r4", {3, 3, 2, 2, 1, 1, 1, 1, 1, 1}, 128, 128, 2, 33, 29, 510, 8, 64, 62},
+                {"p64", {3, 3, 1, 1, 1, 1, 64, 64, 64, 64}, 4, 6, 1, 5, 4, 17030, 178, 96, 38},
+                {"k32", {32, 32, 1, 1, 1, 1, 0, 0, 0, 0}, 1, 1, 1, 33, 34, 6, 1, 32, 6},
+                {"k1x32", {1, 32, 1, 1, 1, 1, 0, 0, 16, 15}, 3, 5, 2, 4, 20, 160, 5, 32, 32},
+                {"s16", {3, 3, 16, 16, 1, 1, 1, 1, 1, 1}, 8, 8, 1, 40, 37, 9, 1, 32, 9},
+                {"s53", {2, 3, 5, 3, 1, 1, 1, 0, 0, 2}, 8, 16, 2, 14, 13, 30, 1, 32, 30},
+                {"mix", {3, 4, 3, 2, 2, 3, 4, 0, 1, 5}, 20, 36, 2, 17, 19, 96, 3, 32, 32},
+                {"d32", {2, 2, 1, 1, 32, 32, 16, 16, 16, 16}, 8, 8, 1, 20, 18, 360, 12, 32, 8}};
+    for (const auto &c : pins) {
+        y355_convgrad *u = nullptr;
+        EXPECT(convgrad_open(0, c.cin, c.cout, &c.g, 1.f, host_mem(), &u) == 0 && u);
+        const bool same = y355_convgrad_wgrad_plan(u, c.B, c.H, c.W, p) == 0 && p[0] == c.npix && p[1] == c.runs && p[2] == c.chunk && p[3] == c.last;
+        if (!same) {
+            std::printf("plan of %s: npix %d runs %d chunk %d last %d\n", c.name, p[0], p[1], p[2], p[3]);
+            ++failures;
+        }
+        convgrad_free(u);
+    }
     EXPECT(y355_convgrad_wgrad_plan(nullptr, 1, 4, 4, p) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_wgrad_plan: null argument");
     EXPECT(y355_convgrad_wgrad_plan(t, 1, 4, 4, nullptr) == Y355_CONVGRAD_EINVAL);
     EXPECT(y355_convgrad_wgrad_plan(t, 0, 4, 4, p) == Y355_CONVGRAD_EINVAL && g_text == "y355_convgrad_wgrad_plan: bad shape");

@@ -46,6 +46,26 @@ CASES = collections.OrderedDict([
 CASES["s2k1"] = Case(geo(1, 2, 0), 8, 8, 1, 5, 6)
 CASES["s2p0"] = Case(geo(3, 2, 0), 8, 8, 1, 8, 8)
 TABLE = tuple("abcdefgh")
+# the weight gradient's pixel loop more than one iteration deep: chunks of 64 and 96 pixels (two and three iterations of 32 per
+# run), a last run that is shorter and no multiple of 8, runs that cross an image boundary; r2 and r3 with the 255 output channels
+# of a YOLOv3 pred layer; p64 at the pad limit, 178 runs.  (chunk, runs, last) are asserted from the plan query.
+CASES["r1"] = Case(geo(3, 1, 1), 256, 64, 2, 15, 17)
+CASES["r2"] = Case(geo(3, 1, 1), 128, 255, 3, 13, 13)
+CASES["r3"] = Case(geo(1), 1024, 255, 2, 13, 13)
+CASES["r4"] = Case(geo(3, 2, 1), 128, 128, 2, 33, 29)
+CASES["p64"] = Case(geo(3, 1, 64), 4, 6, 1, 5, 4)
+RUNS = ("r1", "r2", "r3", "r4", "p64")
+RUN_SLOPES = (0.1, 1.0)
+# the limits of the geometry (kernel 32, stride 16, dilation 32, pad 64) and what lies between: 1024 taps on one real channel in
+# eight; a kernel wider than the map; strides above the kernel, different and both above 1; every parameter different on the
+# two axes with 24 and 40 padded channels, so that a k-step of 32 starts inside one tap and ends in the next
+CASES["k32"] = Case(geo(32), 1, 1, 1, 33, 34)
+CASES["k1x32"] = Case(geo((1, 32), 1, (0, 0, 16, 15)), 3, 5, 2, 4, 20)
+CASES["s16"] = Case(geo(3, 16, 1), 8, 8, 1, 40, 37)
+CASES["s53"] = Case(geo((2, 3), (5, 3), (1, 0, 0, 2)), 8, 16, 2, 14, 13)
+CASES["mix"] = Case(geo((3, 4), (3, 2), (4, 0, 1, 5), (2, 3)), 20, 36, 2, 17, 19)
+CASES["d32"] = Case(geo(2, 1, "same", 32), 8, 8, 1, 20, 18)
+EDGES = ("k32", "k1x32", "s16", "s53", "mix", "d32", "p64")
 SLOPES = (0.125, 0.1, 0.0, 1.0)
 U = 2.0 ** -24
 
@@ -62,10 +82,13 @@ def rb(t):
 
 def inputs(name, seed=0):
     """(x, w, bias, dy) of a case as float32 tensors from the seeded generator"""
+    return make_inputs(CASES[name], 1000 * (list(CASES).index(name) + 1) + 10 * seed)
+
+
+def make_inputs(c, s):
+    """(x, w, bias, dy) of any Case from the generator's seeds s + 1 .. s + 4: |x|, |dy| < 1, |w| < 1 / sqrt(cin kh kw)"""
     from yolo355 import synth
-    c = CASES[name]
     ho, wo = out_size(c.geo, c.H, c.W)
-    s = 1000 * (list(CASES).index(name) + 1) + 10 * seed
     x = torch.from_numpy(synth.uniform_pm1(s + 1, (c.B, c.cin, c.H, c.W)))
     w = torch.from_numpy(synth.uniform_pm1(s + 2, (c.cout, c.cin, c.geo.kh, c.geo.kw))) * float(1.0 / np.sqrt(c.cin * c.geo.kh * c.geo.kw))
     b = torch.from_numpy(synth.uniform_pm1(s + 3, (c.cout,))) * 0.25
@@ -135,3 +158,29 @@ def untouched(g, H, W):
             if 0 <= yy < H and 0 <= xx < W:
                 m[yy, xx] = False
     return m
+
+
+def pixel(c, q):
+    """(image, oy, ox) of the flat output pixel q, the order in which the weight gradient walks them"""
+    ho, wo = out_size(c.geo, c.H, c.W)
+    return q // (ho * wo), q % (ho * wo) // wo, q % wo
+
+
+def patch(c, xr, bi, oy, ox):
+    """[cin, kh, kw] float32: xr under the window of output pixel (oy, ox) of image bi, zeros where the window leaves the map"""
+    g = c.geo
+    out = torch.zeros(c.cin, g.kh, g.kw)
+    for ky in range(g.kh):
+        for kx in range(g.kw):
+            iy, ix = oy * g.stride_h + ky * g.dil_h - g.pad_top, ox * g.stride_w + kx * g.dil_w - g.pad_left
+            if 0 <= iy < c.H and 0 <= ix < c.W:
+                out[:, ky, kx] = xr[bi, :, iy, ix].float()
+    return out
+
+
+def dead_taps(g, H, W):
+    """bool [kh, kw]: the taps that lie in the padding under every window (their rows of dw are exactly zero)"""
+    ho, wo = out_size(g, H, W)
+    rows = [any(0 <= oy * g.stride_h + ky * g.dil_h - g.pad_top < H for oy in range(ho)) for ky in range(g.kh)]
+    cols = [any(0 <= ox * g.stride_w + kx * g.dil_w - g.pad_left < W for ox in range(wo)) for kx in range(g.kw)]
+    return ~np.outer(np.array(rows, bool), np.array(cols, bool))

@@ -25,7 +25,7 @@ def rel(a, b):
 
 
 @pytest.mark.parametrize("slope", R.SLOPES)
-@pytest.mark.parametrize("name", R.TABLE)
+@pytest.mark.parametrize("name", list(R.CASES))
 def test_written_out_backward_is_autograd(name, slope):
     """float64, G unrounded: forward and (dx, dw, db) equal torch.autograd.grad of leaky_relu / relu / identity of F.conv2d
     within 1e-12 relative"""
@@ -48,6 +48,38 @@ def test_out_size_is_torch(name):
     g = CG.Geom(*c.geo)
     y = R.torch_forward(torch.zeros(1, 1, c.H, c.W), torch.zeros(1, 1, c.geo.kh, c.geo.kw), None, c.geo, 1.0)
     assert CG.out_size(g, c.H, c.W) == tuple(y.shape[2:]) == R.out_size(c.geo, c.H, c.W)
+
+
+def test_every_case_is_listed_once_and_within_the_limits():
+    assert set(R.TABLE + R.RUNS + R.EDGES + ("s2k1", "s2p0")) == set(R.CASES)
+    for c in R.CASES.values():
+        CG.geometry((c.geo.kh, c.geo.kw), (c.geo.stride_h, c.geo.stride_w), 0, (c.geo.dil_h, c.geo.dil_w))      # raises past a limit
+        assert max(c.geo[6:]) <= 64 and 1 <= c.cin <= CG.MAX_CHANNELS and 1 <= c.cout <= CG.MAX_CHANNELS
+    at = lambda i: max(c.geo[i] for c in R.CASES.values())
+    assert (at(0), at(1), at(2), at(4), at(5), at(6)) == (32, 32, 16, 32, 32, 64)       # every limit of the geometry is reached
+    cp = lambda n: (n + 7) // 8 * 8
+    assert (cp(R.CASES["mix"].cin), cp(R.CASES["mix"].cout)) == (24, 40)
+
+
+@pytest.mark.parametrize("name", list(R.CASES) + ["dead"])
+def test_helpers_of_the_exact_checks_agree_with_the_restatement(name):
+    """pixel / patch: a one-hot G at the case's last flat pixel makes dw[co] the patch; dead_taps: exactly the taps whose rows
+    of S (dw of absolute values under G = 1) are zero -- 'dead' is a 3x3 whose outer columns lie 8 pixels beside a 5-wide map"""
+    c = R.Case(R.geo(3, 1, (1, 1, 8, 8), (1, 8)), 2, 3, 1, 6, 5) if name == "dead" else R.CASES[name]
+    x, w, _, dy = (t.double() for t in R.make_inputs(c, 7))
+    ho, wo = R.out_size(c.geo, c.H, c.W)
+    q = c.B * ho * wo - 1
+    bi, oy, ox = R.pixel(c, q)
+    assert (bi, oy, ox) == (c.B - 1, ho - 1, wo - 1) and R.pixel(c, (c.B - 1) * ho * wo + wo - 1) == (c.B - 1, 0, wo - 1)
+    one = torch.zeros_like(dy)
+    one[bi, c.cout - 1, oy, ox] = 1.0
+    dw = R.backward(x, w, one, c.geo)[1]
+    assert torch.equal(dw[c.cout - 1].float(), R.patch(c, x, bi, oy, ox)) and not dw[:c.cout - 1].any()
+    S = R.backward(x.abs(), w.abs(), torch.ones_like(dy), c.geo)[1]
+    dead = torch.from_numpy(R.dead_taps(c.geo, c.H, c.W))
+    assert torch.equal(S.sum((0, 1)) == 0, dead) and (S[:, :, ~dead] > 0).all()
+    if name == "dead":
+        assert dead.tolist() == [[True, False, True]] * 3
 
 
 @pytest.mark.parametrize("k,d", [(2, 1), (4, 1), (4, 3), ((2, 6), (3, 2)), (3, 2), ((5, 4), 1)])
